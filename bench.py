@@ -7,17 +7,27 @@ X->Y->Z->Y->X transpose cycle of a 1024^3 fp64 array (BASELINE.json), through li
 
 A "step" is one full cycle (4 transposes) on device-resident synthetic data.  Protocol (the
 reference autotuner's, src/autotune.cc:541-636): W warm-up cycles, then K timed cycles bracketed by barriers + device
-syncs, every cycle also bracketed by its own HIP events -> min / max / avg / std over cycles and ranks; out of place
-AND in place.  Rank 0 prints ONE JSON line.
+syncs, every cycle also bracketed by its own HIP events -> min / max / avg / std over cycles and ranks.  Rank 0 prints
+ONE JSON line.
+
+A plain run measures the headline variant only (out of place unless --inplace).  --full adds everything else below:
+the other variant (in place / out of place), the per-hop splits, the roofline, the extras and the CPU baseline.
 
   value        effective GB/s = 4 * global array bytes / cycle time, out of place (whole job)
-  stats        per-cycle device times (HIP events on the library's stream), out of place and in place
-  roofline     dominant kernel of the cycle (N = 1) vs the HBM roofline; its name comes from the library
-  cpu_baseline the host-MPI CPU path (oracle/cpu_mpi_cycle: the oracle's pack / unpack around MPI_Alltoallv, one rank
-               per core) on the same workload, rank 0, N = 1 only
-  extra        N = 1 only: BASELINE config 4 (1024^3 complex<fp32> 3-D FFT forward + inverse, benchmark/fft3d_benchmark)
-               and config 5 (halo update of its per-rank pencil), measured after the timed region; `dtypes`: the cycle at
-               8-GiB pencils for fp32 / complex64 / complex128, both layouts, per-hop kernel and roofline fraction
+  stats        per-cycle device times (HIP events on the library's stream); with --full also of the other variant
+  roofline     --full: dominant kernel of the cycle (N = 1) vs the HBM roofline; its name comes from the library
+  cpu_baseline --full: the host-MPI CPU path (oracle/cpu_mpi_cycle: the oracle's pack / unpack around MPI_Alltoallv, one
+               rank per core) on the same workload, rank 0, N = 1 only
+  extra        --full, N = 1 only: BASELINE config 4 (1024^3 complex<fp32> 3-D FFT forward + inverse,
+               benchmark/fft3d_benchmark) and config 5 (halo update of its per-rank pencil), measured after the timed
+               region; `dtypes`: the cycle at 8-GiB pencils for fp32 / complex64 / complex128, both layouts, per-hop
+               kernel and roofline fraction
+
+--dump-outputs DIR writes what the last timed cycle left in the pencils (x_pencil: the X pencil the cycle returns;
+y_pencil: the Y pencil of its third hop, out of place only) as DIR/<name>.npy: a fixed, seeded sample of at most 2^20
+elements per pencil, each 64-bit element as its two 32-bit halves (low, high) in float64, which is exact.  The input
+pencil is seeded, so runs with the same arguments can be compared output for output.  N > 1: every rank writes its
+own pencils as <name>_rank<r>.npy.
   N > 1        the fixed 1024^3 problem on N ranks ("strong"); first over RCCL (process grid autotuned), then -- after
                a preflight that tries every one-sided transport on a small grid and reports pass/fail per transport
                to stderr -- with the library's autotuner choosing among all transports that passed; the faster valid
@@ -54,7 +64,11 @@ def parse():
     ap.add_argument("--watchdog", type=int, default=600, help="multi-GPU runs: give up after this many seconds (0 = never)")
     ap.add_argument("--cpu-sample", type=int, default=-1,
                     help="grid edge of the CPU-baseline sample (0 = skip, -1 = the full size if host memory allows, else half)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the config-4 / config-5 records (N = 1)")
+    ap.add_argument("--no-extras", action="store_true", help="skip the config-4 / config-5 records (N = 1, with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the other variant, the per-hop splits, the roofline, the extras and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the pencils of the last timed cycle as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -236,8 +250,11 @@ def cpu_baseline_mpi(sample, size, layout):
         if not os.path.exists(exe):
             subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "cpu_mpi_cycle"], stdout=sys.stderr,
                                   stderr=sys.stderr)
-        cores = os.cpu_count() or 1
-        # one rank per core, up to 64 (power of two, near-square process grid)
+        # one rank per core this process may use (its affinity; OMP_NUM_THREADS where the host sets a CPU budget), up to 64
+        # (power of two, near-square process grid)
+        cores = len(os.sched_getaffinity(0)) or 1
+        if os.environ.get("OMP_NUM_THREADS", "").isdigit() and int(os.environ["OMP_NUM_THREADS"]) > 0:
+            cores = min(cores, int(os.environ["OMP_NUM_THREADS"]))
         ranks = 1
         while ranks * 2 <= min(cores, 64):
             ranks *= 2
@@ -327,9 +344,9 @@ class Pencils:
             self.cd.cudecompFree(self.h, self.gd, p)
 
 
-def run_cycles(cd, torch, dist, world, h, gd, pen, inplace, warmup, steps, stream):
+def run_cycles(cd, torch, dist, world, h, gd, pen, inplace, warmup, steps, stream, detail=True):
     """W warm-up + K timed cycles.  Returns wall ms (barrier + sync bracket, max over ranks), per-cycle device ms of
-    this rank, per-op ms of one extra cycle and whether the X pencil came back bit for bit."""
+    this rank, per-op ms of one extra cycle (detail only) and whether the X pencil came back bit for bit."""
     def barrier():
         if world > 1:
             dist.barrier()
@@ -344,37 +361,38 @@ def run_cycles(cd, torch, dist, world, h, gd, pen, inplace, warmup, steps, strea
     for _ in range(warmup):
         cycle()
     torch.cuda.synchronize()
-    op_ms, op_kernels = [], []
-    cur, nxt = pen.a, (pen.a if inplace else pen.b)
-    for op in cd.OPS:  # per-op split, outside the timed region
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        cd.cudecompTranspose(op, h, gd, cur.data_ptr(), nxt.data_ptr(), pen.work, cd.DOUBLE, stream=stream)
-        e1.record()
-        torch.cuda.synchronize()
-        op_ms.append(e0.elapsed_time(e1))
-        op_kernels.append(cd.cudecompExtLastKernelName())
-        if not inplace:
-            cur, nxt = nxt, cur
-    # the same split INSIDE a sustained sequence (no host synchronisation between the hops; outside the timed region): events
-    # between the hops of 3 back-to-back cycles after one more warm-up cycle.  Isolated hops start on an idle memory system;
-    # sustained ones inherit the previous hop's tail (dirty lines of the 256 MB memory-side cache still draining to HBM).
-    op_sus = [0.0] * len(cd.OPS)
-    sus_cycles = 3
-    cycle()
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(sus_cycles * len(cd.OPS) + 1)]
-    marks[0].record()
-    for c in range(sus_cycles):
+    op_ms, op_kernels, op_sus = [], [], []
+    if detail:  # --full
         cur, nxt = pen.a, (pen.a if inplace else pen.b)
-        for i, op in enumerate(cd.OPS):
+        for op in cd.OPS:  # per-op split, outside the timed region
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
             cd.cudecompTranspose(op, h, gd, cur.data_ptr(), nxt.data_ptr(), pen.work, cd.DOUBLE, stream=stream)
-            marks[c * len(cd.OPS) + i + 1].record()
+            e1.record()
+            torch.cuda.synchronize()
+            op_ms.append(e0.elapsed_time(e1))
+            op_kernels.append(cd.cudecompExtLastKernelName())
             if not inplace:
                 cur, nxt = nxt, cur
-    torch.cuda.synchronize()
-    for c in range(sus_cycles):
-        for i in range(len(cd.OPS)):
-            op_sus[i] += marks[c * len(cd.OPS) + i].elapsed_time(marks[c * len(cd.OPS) + i + 1]) / sus_cycles
+        # the same split INSIDE a sustained sequence (no host synchronisation between the hops; outside the timed region): events
+        # between the hops of 3 back-to-back cycles after one more warm-up cycle.  Isolated hops start on an idle memory system;
+        # sustained ones inherit the previous hop's tail (dirty lines of the 256 MB memory-side cache still draining to HBM).
+        op_sus = [0.0] * len(cd.OPS)
+        sus_cycles = 3
+        cycle()
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(sus_cycles * len(cd.OPS) + 1)]
+        marks[0].record()
+        for c in range(sus_cycles):
+            cur, nxt = pen.a, (pen.a if inplace else pen.b)
+            for i, op in enumerate(cd.OPS):
+                cd.cudecompTranspose(op, h, gd, cur.data_ptr(), nxt.data_ptr(), pen.work, cd.DOUBLE, stream=stream)
+                marks[c * len(cd.OPS) + i + 1].record()
+                if not inplace:
+                    cur, nxt = nxt, cur
+        torch.cuda.synchronize()
+        for c in range(sus_cycles):
+            for i in range(len(cd.OPS)):
+                op_sus[i] += marks[c * len(cd.OPS) + i].elapsed_time(marks[c * len(cd.OPS) + i + 1]) / sus_cycles
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     barrier()
     torch.cuda.synchronize()
@@ -585,6 +603,30 @@ def dtype_table(cd, torch, h, stream, only=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+DUMP_SAMPLE = 1 << 20  # elements per pencil: 2 pencils x 2^20 x 2 halves x 8 B = 32 MiB at most
+
+
+def dump_outputs(path, torch, pen, inplace, rank, world):
+    """What the last timed cycle left in the pencils, as <path>/<name>.npy: the X pencil it returns in `a` and, out of
+    place, the Y pencil its third hop (ZToY) wrote into `b`.  A fixed, seeded sample of the elements (all of them when
+    the pencil has at most DUMP_SAMPLE); each 64-bit element as its low and high 32-bit halves in float64 (exact, and no
+    NaN from the random bit patterns)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    pencils = [("x_pencil", pen.a, pen.pinfo[0].size)]
+    if not inplace:
+        pencils.append(("y_pencil", pen.b, pen.pinfo[1].size))
+    torch.cuda.synchronize()
+    for name, buf, size in pencils:
+        if size <= DUMP_SAMPLE:
+            idx = np.arange(size, dtype=np.int64)
+        else:
+            idx = np.sort(np.random.default_rng(20240601).integers(0, size, DUMP_SAMPLE, dtype=np.int64))
+        words = buf[torch.from_numpy(idx).to(buf.device)].cpu().numpy()
+        halves = words.astype("<i8").view("<u4").reshape(-1, 2).astype(np.float64)
+        np.save(os.path.join(path, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), halves)
+
+
 _RESULT_FD = [None]
 
 
@@ -761,8 +803,11 @@ def main():
         pen = Pencils(cd, torch, h, gd, 1234 + rank)
         res = {}
         order = (True, False) if args.inplace else (False, True)
+        if not args.full:
+            order = order[:1]  # a plain run measures the headline variant only
         for inplace in order[::-1]:  # the headline variant LAST, so that the library's per-op samples are its own
-            res[inplace] = run_cycles(cd, torch, dist, world, h, gd, pen, inplace, args.warmup, args.steps, stream)
+            res[inplace] = run_cycles(cd, torch, dist, world, h, gd, pen, inplace, args.warmup, args.steps, stream,
+                                      detail=args.full)
         head = res[bool(args.inplace)]
         kernel = cd.cudecompExtLastKernelName()
         split = None
@@ -790,7 +835,7 @@ def main():
         counters = cd.cudecompExtGetCounters(h, gd)
         return {"gd": gd, "pen": pen, "pdims": pdims, "used": used, "autotuned": autotuned, "res": res, "head": head,
                 "kernel": kernel, "split": split, "cut": cut, "counters": counters,
-                "ok": head["ok"] and res[not args.inplace]["ok"]}
+                "ok": all(r["ok"] for r in res.values())}
 
     def release(m):
         m["pen"].free()
@@ -823,15 +868,16 @@ def main():
             # protocol of SURVEY 8(d): per-cycle device times (HIP events on the library's stream) over the timed cycles of
             # all ranks, both variants
             "stats": {"protocol": "%d warm-up + %d timed cycles, barrier + device sync on both sides; per-cycle HIP events"
-                                  % (args.warmup, args.steps),
-                      "out_of_place_cycle_ms": stats_of(m["res"][False]["cycle_ms_all_ranks"]),
-                      "in_place_cycle_ms": stats_of(m["res"][True]["cycle_ms_all_ranks"]),
-                      "out_of_place_GBps": round(4 * global_bytes / (m["res"][False]["wall_ms"] / args.steps * 1e-3) / 1e9, 2),
-                      "in_place_GBps": round(4 * global_bytes / (m["res"][True]["wall_ms"] / args.steps * 1e-3) / 1e9, 2),
-                      "in_place_per_op_ms": [round(x, 4) for x in m["res"][True]["op_ms"]],
-                      "in_place_round_trip_checksum_ok": bool(m["res"][True]["ok"])},
+                                  % (args.warmup, args.steps)},
             "roofline": None,
         }
+        for inplace, r in sorted(m["res"].items()):  # a plain run has the headline variant only
+            v = "in_place" if inplace else "out_of_place"
+            out["stats"][v + "_cycle_ms"] = stats_of(r["cycle_ms_all_ranks"])
+            out["stats"][v + "_GBps"] = round(4 * global_bytes / (r["wall_ms"] / args.steps * 1e-3) / 1e9, 2)
+        if True in m["res"]:
+            out["stats"]["in_place_per_op_ms"] = [round(x, 4) for x in m["res"][True]["op_ms"]]
+            out["stats"]["in_place_round_trip_checksum_ok"] = bool(m["res"][True]["ok"])
         if preflight is not None:
             out["config"]["preflight"] = preflight
         return out
@@ -839,6 +885,8 @@ def main():
     # ------------------------------------------------------------------------------------------------------ N = 1
     if world == 1:
         m = measure(args.backend, (1, 1), None)
+        if args.dump_outputs:  # before the roofline's copy-rate run overwrites pen.b
+            dump_outputs(args.dump_outputs, torch, m["pen"], args.inplace, rank, world)
         out = record(m)
         head = m["head"]
         pen = m["pen"]
@@ -847,7 +895,7 @@ def main():
         # is two launches per hop (permute into the workspace, copy back)
         launches_per_cycle = 4 if not args.inplace else (8 if args.layout == "contiguous" else 0)
         alg_bytes = 2 * pen.pinfo[0].size * es
-        if launches_per_cycle:
+        if args.full and launches_per_cycle:
             avg_ms = sum(head["cycle_ms"]) / len(head["cycle_ms"]) / launches_per_cycle
             achieved = alg_bytes / (avg_ms * 1e-3) / 1e9
             traffic, src = measured_traffic(args.layout) if n == 1024 and not args.inplace else (None, None)
@@ -901,10 +949,10 @@ def main():
                 cd.cudecompGridDescDestroy(h, gdc)
             out["roofline"] = roof
         release(m)
-        if not args.no_extras and n == 1024:
+        if args.full and not args.no_extras and n == 1024:
             out["extra"] = extras_single_gpu(cd, torch, h, stream)
             out["extra"]["dtypes"] = dtype_table(cd, torch, h, stream)
-        if args.cpu_sample != 0:
+        if args.full and args.cpu_sample != 0:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, n, args.layout)
         emit(out)
         cd.cudecompFinalize(h)
@@ -1032,6 +1080,8 @@ def main():
         best["config"]["also_measured"] = everything
         emit(best)
     if best_m is not None:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, torch, best_m["pen"], args.inplace, rank, world)
         release(best_m)
     cd.cudecompFinalize(h)
     dist.destroy_process_group()

@@ -95,7 +95,7 @@ for n in 2 4 8; do
   [ $n -le $MAXR ] || continue
   # (as a plain command: bench.py starts its own ranks under torch.distributed.run when no launcher is around it -- the
   # way the driver called `--gpus 1`; the driver's own multi-GPU line with torch.distributed.run in front works alike)
-  ( time timeout 1500 python bench.py --gpus $n --steps $STEPS --warmup $WARM --size $SIZE ) > $OUT/04_bench_n$n.log 2>&1
+  ( time timeout 1500 python bench.py --gpus $n --steps $STEPS --warmup $WARM --size $SIZE --full ) > $OUT/04_bench_n$n.log 2>&1
   grep -E '^\{' $OUT/04_bench_n$n.log | tail -1 > $OUT/04_bench_n$n.json
   echo "   n=$n: $(python -c "import json,sys; r=json.load(open('$OUT/04_bench_n$n.json')); print(r['ms_per_step'], 'ms per cycle,', r['config']['transport'], r['config']['pdims'])" 2>&1 | tail -1)" | tee -a $OUT/00_plan.txt
 done
@@ -106,7 +106,7 @@ for flags in 0 1; do
   n=$MAXR; [ $n -gt 8 ] && n=8
   [ $n -ge 2 ] || continue
   ( CUDECOMP_FLAGS_IN_DEVICE_MEMORY=$flags timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-      --master-port 2954$flags bench.py --gpus $n --steps $STEPS --warmup $WARM --size $SIZE --backend peer_pl --pdims 1 $n ) > $OUT/05_bench_peer_pl_flags$flags.log 2>&1
+      --master-port 2954$flags bench.py --gpus $n --steps $STEPS --warmup $WARM --size $SIZE --full --backend peer_pl --pdims 1 $n ) > $OUT/05_bench_peer_pl_flags$flags.log 2>&1
   grep -E '^\{' $OUT/05_bench_peer_pl_flags$flags.log | tail -1 > $OUT/05_bench_peer_pl_flags$flags.json
 done
 
@@ -115,7 +115,7 @@ for relay in 0 1; do
   n=$MAXR; [ $n -gt 8 ] && n=8
   [ $n -ge 4 ] || continue
   ( CUDECOMP_TWO_HOP_RELAY=$relay timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-      --master-port 2955$relay bench.py --gpus $n --steps $STEPS --warmup $WARM --size $SIZE --backend peer --pdims 2 $((n / 2)) ) > $OUT/05b_bench_2xN_relay$relay.log 2>&1
+      --master-port 2955$relay bench.py --gpus $n --steps $STEPS --warmup $WARM --size $SIZE --full --backend peer --pdims 2 $((n / 2)) ) > $OUT/05b_bench_2xN_relay$relay.log 2>&1
   grep -E '^\{' $OUT/05b_bench_2xN_relay$relay.log | tail -1 > $OUT/05b_bench_2xN_relay$relay.json
 done
 

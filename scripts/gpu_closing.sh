@@ -8,5 +8,5 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0 PYTHONPATH=$PWD
 grep -E "^(FAILED|ERROR)" $O/gpu_suite.log | head -20
 ( time CUDECOMP_TEST_EXTENDED=1 timeout 1200 python -m pytest tests -q -m "gpu and extended" -rA --durations=10 ) > $O/gpu_suite_extended.log 2>&1; tail -4 $O/gpu_suite_extended.log | cut -c1-250
 ( timeout 200 python -c "import __graft_entry__ as g; g.smoke()" ) > $O/smoke.log 2>&1; tail -1 $O/smoke.log | cut -c1-300
-( time timeout 400 python bench.py ) > $O/bench.log 2>&1; grep -E '^\{' $O/bench.log | tail -1 > $O/bench_n1.json
+( time timeout 600 python bench.py --full ) > $O/bench.log 2>&1; grep -E '^\{' $O/bench.log | tail -1 > $O/bench_n1.json
 python -c "import json; r = json.load(open('$O/bench_n1.json')); print(r['ms_per_step'], r['roofline']['frac'], r['stats'].get('in_place_cycle_ms'))"

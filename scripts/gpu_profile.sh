@@ -1,24 +1,27 @@
 #!/bin/bash
 # rocprofv3 evidence for the bench's dominant kernels: kernel trace + stats, then HBM counters in separate passes
-mkdir -p gpurun_out/prof
+#   scripts/gpu_profile.sh DIR && python scripts/summarize_profiles.py rNN DIR
+P=${1:?usage: scripts/gpu_profile.sh OUTPUT_DIR}
+mkdir -p $P && P=$(cd $P && pwd)
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 REPO=$PWD
 cd /tmp && export TMPDIR=/tmp
 for layout in contiguous default; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/gpurun_out/prof/${layout}_trace -o bench -- \
-     python $REPO/bench.py --steps 5 --warmup 3 --cpu-sample 0 --no-extras --layout $layout > $REPO/gpurun_out/prof/${layout}_trace.log 2>&1
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $REPO/gpurun_out/prof/${layout}_fetch -o bench -- \
-     python $REPO/bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-extras --layout $layout > $REPO/gpurun_out/prof/${layout}_fetch.log 2>&1
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $REPO/gpurun_out/prof/${layout}_write -o bench -- \
-     python $REPO/bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-extras --layout $layout > $REPO/gpurun_out/prof/${layout}_write.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $P/${layout}_trace -o bench -- \
+     python $REPO/bench.py --full --steps 5 --warmup 3 --cpu-sample 0 --no-extras --layout $layout > $P/${layout}_trace.log 2>&1
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $P/${layout}_fetch -o bench -- \
+     python $REPO/bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-extras --layout $layout > $P/${layout}_fetch.log 2>&1
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $P/${layout}_write -o bench -- \
+     python $REPO/bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-extras --layout $layout > $P/${layout}_write.log 2>&1
 done
 cd $REPO
-find gpurun_out/prof -type f | head -50
-for f in $(find gpurun_out/prof -name "*kernel_stats.csv"); do echo "== $f"; head -8 $f; done
+find $P -type f | head -50
+for f in $(find $P -name "*kernel_stats.csv"); do echo "== $f"; head -8 $f; done
 # drop the big per-dispatch traces, keep per-kernel summaries of the counter passes
-python - <<'PY'
-import csv, glob, collections
-for f in glob.glob("gpurun_out/prof/*_fetch/**/*counter_collection.csv", recursive=True) + glob.glob("gpurun_out/prof/*_write/**/*counter_collection.csv", recursive=True):
+python - "$P" <<'PY'
+import csv, glob, collections, sys
+P = sys.argv[1]
+for f in glob.glob(P + "/*_fetch/**/*counter_collection.csv", recursive=True) + glob.glob(P + "/*_write/**/*counter_collection.csv", recursive=True):
     agg = collections.defaultdict(lambda: [0, 0.0])
     for row in csv.DictReader(open(f)):
         k = (row.get("Kernel_Name"), row.get("Counter_Name"))
@@ -32,5 +35,5 @@ for f in glob.glob("gpurun_out/prof/*_fetch/**/*counter_collection.csv", recursi
     print("==", out)
     print(open(out).read()[:1500])
 PY
-find gpurun_out/prof -name "*kernel_trace.csv" -size +2M -delete
-find gpurun_out/prof -name "*counter_collection.csv" -size +2M -delete
+find $P -name "*kernel_trace.csv" -size +2M -delete
+find $P -name "*counter_collection.csv" -size +2M -delete

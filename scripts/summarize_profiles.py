@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Condense gpurun_out/prof (written by scripts/gpu_profile.sh on the GPU box) into the tracked summaries under
+"""Condense the directory scripts/gpu_profile.sh wrote (python scripts/summarize_profiles.py rNN DIR) into the tracked summaries under
 profiles/: per-kernel stats of the bench command for both layouts and the HBM traffic per launch from the
 FETCH_SIZE / WRITE_SIZE passes (FETCH_SIZE doubled on gfx950, see MI355X_MICROARCH.md)."""
 import csv
@@ -7,9 +7,12 @@ import json
 import sys
 
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r01"
+if len(sys.argv) < 3:
+    sys.exit("usage: summarize_profiles.py rNN DIR (DIR: what scripts/gpu_profile.sh wrote)")
+PROF = sys.argv[2]
 out = {"round": int(rnd[1:]),
        "command": "rocprofv3 --kernel-trace --stats / --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python "
-                  "bench.py --steps 5 --warmup 3 --cpu-sample 0 --no-extras --layout <layout>",
+                  "bench.py --full --steps 5 --warmup 3 --cpu-sample 0 --no-extras --layout <layout>",
        "note": "FETCH_SIZE is doubled: on gfx950 it counts 128-B requests of wide streaming reads as 64 B "
                "(MI355X_MICROARCH.md, HBM section)",
        "workload": "1024^3 fp64 X->Y->Z->Y->X, 1x1 grid, out-of-place", "layouts": {}}
@@ -19,7 +22,7 @@ def short(name):  # "void cudecomp::kern::transpose_kernel<8, 2, 64, 64, 2, true
 
 
 for layout in ("contiguous", "default"):
-    rows = list(csv.DictReader(open("gpurun_out/prof/%s_trace/bench_kernel_stats.csv" % layout)))
+    rows = list(csv.DictReader(open("%s/%s_trace/bench_kernel_stats.csv" % (PROF, layout))))
     with open("profiles/%s_bench_%s_kernel_stats.csv" % (rnd, layout), "w") as f:
         f.write("Name,Calls,TotalDurationNs,AverageNs,Percentage,MinNs,MaxNs,StdDev\n")
         for r in rows:
@@ -36,7 +39,7 @@ for layout in ("contiguous", "default"):
 
     def mean(kind, counter):
         tot, n = 0.0, 0
-        for r in csv.DictReader(open("gpurun_out/prof/%s_%s/bench_counter_summary.csv" % (layout, kind))):
+        for r in csv.DictReader(open("%s/%s_%s/bench_counter_summary.csv" % (PROF, layout, kind))):
             if r["counter"] == counter and any(r["kernel"] == k["Name"] for k in ks):
                 tot += float(r["sum"])
                 n += int(r["dispatches"])
@@ -54,7 +57,7 @@ for layout in ("contiguous", "default"):
 import os
 out["dtypes"] = {}
 for dt, es in (("fp32", 4), ("complex128", 16)):
-    stats = "gpurun_out/prof/dtype_%s_trace/bench_kernel_stats.csv" % dt
+    stats = "%s/dtype_%s_trace/bench_kernel_stats.csv" % (PROF, dt)
     if not os.path.exists(stats):
         continue
     rows = list(csv.DictReader(open(stats)))
@@ -65,7 +68,7 @@ for dt, es in (("fp32", 4), ("complex128", 16)):
 
     def dmean(kind, counter):
         try:
-            for r in csv.DictReader(open("gpurun_out/prof/dtype_%s_%s/bench_counter_summary.csv" % (dt, kind))):
+            for r in csv.DictReader(open("%s/dtype_%s_%s/bench_counter_summary.csv" % (PROF, dt, kind))):
                 if r["kernel"] == k["Name"] and r["counter"] == counter:
                     return float(r["mean_per_dispatch"])
         except OSError:

@@ -29,7 +29,7 @@ def _pytest_sessionstart_build(session):
         return
     lib = os.path.join(ROOT, "cudecomp_amd", "lib", "libcudecomp.so")
     if not os.path.exists(lib):
-        subprocess.check_call(["make", "-s", "-j", str(max(2, os.cpu_count() or 2)), "-C", os.path.join(ROOT, "cudecomp_amd")])
+        subprocess.check_call(["make", "-s", "-j", str(min(16, max(2, os.cpu_count() or 2))), "-C", os.path.join(ROOT, "cudecomp_amd")])
 
 
 @pytest.fixture(scope="session")
