@@ -454,30 +454,6 @@ cudecompResult_t cudecompInit(cudecompHandle_t* handle_out, MPI_Comm mpi_comm) {
     // lines (rows_dense_kernel, transpose_lines_kernel, transpose_rowlines_kernel): a caller who writes those cells on another stream WHILE the
     // transpose runs opts out with this switch.
     if (envIsOne("CUDECOMP_PRESERVE_OUTPUT_HALOS")) h->tuning.dense_rows = 0;
-    // Tuning switches (kernel variants, walk orders, diagnostic store policies): read by `make TUNING_VARIANTS=1` builds only
-    // (cudecomp_amd/lib_tuning); the default build has neither the variants nor the switches and says so once.
-    auto tuningSwitch = [&](const char* var, int* out) {
-      const char* v = std::getenv(var);
-      if (!v || !*v) return;
-#ifdef CUDECOMP_TUNING_VARIANTS
-      *out = (int)std::strtol(v, nullptr, 10);
-#else
-      (void)out;
-      if (h->rank == 0)
-        fprintf(stderr, "CUDECOMP:WARN: %s is a tuning switch of `make TUNING_VARIANTS=1` builds of this library; ignored.\n", var);
-#endif
-    };
-    tuningSwitch("CUDECOMP_INTERLEAVE_ROWS", &h->tuning.interleave_rows);
-    tuningSwitch("CUDECOMP_WINDOW_STORES", &h->tuning.window_mode);
-    tuningSwitch("CUDECOMP_WINDOW_WIDE", &h->tuning.window_wide);
-    tuningSwitch("CUDECOMP_TILE_WALK", &h->tuning.walk_order);
-    tuningSwitch("CUDECOMP_TILE_SHAPE", &h->tuning.tile_shape);
-    tuningSwitch("CUDECOMP_LINES_MODE", &h->tuning.lines_mode);
-    tuningSwitch("CUDECOMP_LINES_UNIT", &h->tuning.lines_unit);
-    tuningSwitch("CUDECOMP_LINES_RUN_KIB", &h->tuning.lines_run_kib);
-    tuningSwitch("CUDECOMP_LINES_WALK", &h->tuning.lines_walk);
-    tuningSwitch("CUDECOMP_LINES_GROUP", &h->tuning.lines_group);
-    tuningSwitch("CUDECOMP_ROTATE_WALK", &h->tuning.rotate_walk);
     if (const char* v = std::getenv("CUDECOMP_FORCE_GENERIC_KERNELS"))
       if (std::strtol(v, nullptr, 10) == 1) h->tuning.force_class = MOVE_GENERIC;
 

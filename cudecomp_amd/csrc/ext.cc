@@ -485,10 +485,6 @@ cudecompResult_t cudecompExtRunLocalPhases(const cudecompExtGridSpec_t* grid, in
     const int32_t zero[3] = {0, 0, 0};
     const TransposePlan p = buildTransposePlan(g, rank, (TransposeOp)op, zero, zero, zero, zero, input == output, traits, P);
     void* bufs[3] = {input, output, work};
-    KernelTuning t;
-#ifdef CUDECOMP_TUNING_VARIANTS
-    if (const char* v = std::getenv("CUDECOMP_INTERLEAVE_ROWS")) t.interleave_rows = (int)std::strtol(v, nullptr, 10);
-#endif
     // the launches of the executor: one batched launch per phase; pipelined: one launch per STAGE with all peers in it
     // for the one-sided transport (transport.cc: peerStagedExchange), one launch per PEER for RCCL / MPI (the reference's
     // pipeline, transpose.h:470-513, 683-744)
@@ -504,12 +500,12 @@ cudecompResult_t cudecompExtRunLocalPhases(const cudecompExtGridSpec_t* grid, in
         for (int k = 0; k < K; ++k) {
           part.clear();
           for (const Move3D& m : moves) part.push_back(stageOfMove(m, p.stage_axis, k, K));
-          launchMoves(part.data(), (int)part.size(), bufs, es, stream, &t);
+          launchMoves(part.data(), (int)part.size(), bufs, es, stream);
         }
       } else if (traits.pipelined) {
-        for (const Move3D& m : moves) launchMoves(&m, 1, bufs, es, stream, &t);
+        for (const Move3D& m : moves) launchMoves(&m, 1, bufs, es, stream);
       } else {
-        launchMoves(moves.data(), (int)moves.size(), bufs, es, stream, &t);
+        launchMoves(moves.data(), (int)moves.size(), bufs, es, stream);
       }
     };
     if (phases & 1) run(p.pack);
@@ -592,8 +588,6 @@ cudecompResult_t cudecompExtMove3D(const void* src, void* dst, int32_t es, const
     if (force_generic & 2) t.force_streaming = true;
     if (force_generic & 4) t.window_mode = 1;  // window kernel whenever the destination rows are off the 64-byte grid
     if (force_generic & 8) t.window_mode = 0;  // never
-    if (force_generic & 16) t.tile_shape = 1;  // 4-byte transposes: 128 x 64 tiles
-    if (force_generic & 32) t.tile_shape = 0;  // 4-byte transposes: 64 x 64 tiles (the default is 64 x 128)
     if (force_generic & 64) t.walk_order = 0;  // transposes: i first
     if (force_generic & 128) t.walk_order = 1;  // transposes: j first (no runs)
     KernelStats st;

@@ -32,13 +32,11 @@ struct Classified {
   int variant;  // rows: vector bytes; transpose: elements per vector
   DevMove dm;
   int p0, p1;
-  int stream;  // 0 default caching, 1 streaming loads, 2 streaming loads + stores, 3 streaming loads + remote stores
-  bool swizzle = false;  // transposes: XOR-swizzled LDS tile (else padded rows)
+  int stream;  // 0 default caching, 2 streaming loads + stores, 3 streaming loads + remote stores, 4 cached loads + streaming stores
   bool window = false;   // transposes: destination rows off the 64-byte grid -> transpose_window_kernel (rows: rows_shifted_kernel)
   bool dense = false;    // rows, with window: whole lines across the row ends (rows_dense_kernel)
   bool lines = false;    // transposes, with window: windows over the linear positions of adjacent rows (transpose_lines_kernel)
   bool rowlines = false; // transposes, with window: the tile's own rows are the adjacent ones (transpose_rowlines_kernel)
-  int unit = 0;          // ... and its alignment unit in bytes
   unsigned int t0, t1;
   unsigned long long blocks;
   i64 elements;
@@ -46,23 +44,37 @@ struct Classified {
 
 constexpr long long kDenseMaxGapBytes = 512;  // widest gap between rows the dense row copy rewrites (halo + padding cells)
 
+// tile (elements, i x j) of a transpose variant
+void tileOf(int es, int variant, bool window, int* ti, int* tj) {
+  if (es == 16) {
+    *ti = 32;
+    *tj = variant == 301 ? 64 : 32;
+  } else if (window) {
+    *ti = 64;
+    *tj = es == 4 ? 128 : 64;
+  } else {
+    *ti = 64;
+    *tj = (variant == 304 || variant == 302) ? 128 : 64;
+  }
+}
+
 int ilog2ceil(long long x) {
   int l = 0;
   while ((1LL << l) < x) ++l;
   return l;
 }
 
-Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelTuning* tuning, void* dst_base,
+Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelTuning& tuning, void* dst_base,
                     bool remote) {
   Move3D m = in;
   normalizeMove(m);
   Classified c{};
   c.elements = m.elements();
-  c.stream = ((c.elements * es >= kStreamBytes || (tuning && tuning->force_streaming)) && !(tuning && tuning->no_streaming)) ? 2 : 0;
+  c.stream = ((c.elements * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming) ? 2 : 0;
   if (remote) c.stream = 3;  // destination in a peer's memory: write-through stores, whatever the size
   c.dm.src = static_cast<const char*>(bufs[m.src_buf]) + m.src_off * es;
   c.dm.dst = static_cast<char*>(dst_base ? dst_base : bufs[m.dst_buf]) + m.dst_off * es;
-  const bool force_generic = tuning && tuning->force_class == MOVE_GENERIC;
+  const bool force_generic = tuning.force_class == MOVE_GENERIC;
 
   if (!force_generic && m.ss[0] <= 1 && m.ds[0] <= 1) {
     // rows contiguous on both sides (also the all-extents-1 case).  Widest vector that divides the row length;
@@ -81,7 +93,7 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
     // rows that land off the 64-byte grid (and are long enough for it to matter): lanes laid out from the unit boundary
     // below each row's start (rows_shifted_kernel), one unit of slack vectors per row
     const uintptr_t dst_bits = reinterpret_cast<uintptr_t>(c.dm.dst) | (uintptr_t)c.dm.ds[1] | (uintptr_t)c.dm.ds[2];
-    const int shift_mode = tuning ? tuning->window_mode : -1;
+    const int shift_mode = tuning.window_mode;  // -1 auto, 0 never, 1 whenever the destination is misaligned
     if ((dst_bits & 63) != 0 && m.extent[0] * es >= 256 && shift_mode != 0 && (shift_mode == 1 || c.elements * es >= (1ll << 20))) {
       c.window = true;
       c.p1 = (int)(m.extent[0] * es);  // row length in bytes (rows longer than 2 GiB keep the plain kernel)
@@ -95,8 +107,7 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
     i64 planned_row = -1;
     for (int i = 0; i < 3; ++i)
       if (in.ss[i] == 1 && in.ds[i] == 1 && in.extent[i] > 1) planned_row = in.extent[i];
-    if (c.window && in.dst_row_pitch > 0 && !remote && planned_row == m.extent[0] && c.dm.e[1] > 1 &&
-        (!tuning || tuning->dense_rows != 0)) {
+    if (c.window && in.dst_row_pitch > 0 && !remote && planned_row == m.extent[0] && c.dm.e[1] > 1 && tuning.dense_rows != 0) {
       DevMove d = c.dm;
       if (d.e[2] > 1 && d.ds[2] < d.ds[1]) {
         std::swap(d.e[1], d.e[2]);
@@ -150,7 +161,6 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
     if (c.dm.e[0] % vw != 0 || c.dm.e[1] % vw != 0) vw = 1;
     c.variant = vw;
     c.p1 = 1;  // XCD-contiguous tile walk
-    c.swizzle = es != 16;
     // Tile walk order inside an XCD's run: j first makes consecutive tiles extend the same DESTINATION rows
     // (contiguous write stream per row), i first the same source rows.  Measured on 8 GiB permutations
     // (profiles/r01_tuning.md): j first wins or ties for line-aligned moves (8-11 % at 16-byte elements and on
@@ -169,7 +179,7 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
     const uintptr_t dst_bits = reinterpret_cast<uintptr_t>(c.dm.dst) | (uintptr_t)(c.dm.ds[0] * es) | (uintptr_t)(c.dm.ds[2] * es);
     const uintptr_t align_req = 128;
     const bool src_mis = src_bits % align_req != 0, dst_mis = dst_bits % 64 != 0;
-    const int window_mode = tuning ? tuning->window_mode : -1;  // -1 auto, 0 never, 1 whenever the destination is misaligned
+    const int window_mode = tuning.window_mode;  // -1 auto, 0 never, 1 whenever the destination is misaligned
     c.window = dst_mis && window_mode != 0 && (window_mode == 1 || c.elements * es >= (1ll << 20));
     if (c.window) {
       if (c.stream == 2) c.stream = 4;  // cached loads (the overlap rows hit in L2), streaming whole-unit stores
@@ -185,42 +195,22 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
     // cache line) lose a third of their rate with streaming stores (8 GiB permutation: 4.0 ms streaming, 3.4 ms cached;
     // 4- and 8-byte elements with the same padding prefer streaming, profiles/r02_tuning.md).
     if (es == 16 && c.stream == 2 && !c.window && c.dm.e[2] > 1 && ((uintptr_t)(c.dm.ds[2] * es) % 4096) != 0) c.stream = 0;
-    const bool walk_forced = tuning && tuning->walk_order >= 0;
-    if (walk_forced) j_first = tuning->walk_order == 1;
+    const bool walk_forced = tuning.walk_order >= 0;
+    if (walk_forced) j_first = tuning.walk_order == 1;
     // (window kernel, 4-byte elements: 64 x 128 tiles -- a 64-byte unit is 16 elements, the longer window halves the
     // share of overlap rows)
-    // (window kernel, 8-byte elements, optional: 128 x 64 tiles with 512 threads -- 1-KiB source segments span nine
-    // lines instead of 2 x five; variant 102)
-#ifdef CUDECOMP_TUNING_VARIANTS
-    const bool wide = c.window && es == 8 && vw == 2 && tuning && tuning->window_wide == 1;
-#else
-    const bool wide = false;  // (the 128 x 64 / 512-thread window variant exists in tuning builds only)
-#endif
-    if (wide) c.variant = 102;
-    // (4-byte elements, 16-byte lanes, plain kernel: optional 128 x 64 / 64 x 128 tiles -- variants 204 / 304)
-    int shape = 0;
-    if (!c.window && es == 4 && vw == 4) shape = 2;
-#ifdef CUDECOMP_TUNING_VARIANTS
-    if (!c.window && es == 4 && vw == 4 && tuning && tuning->tile_shape >= 0) shape = tuning->tile_shape;
-#endif
-    if (shape == 1) c.variant = 204;
-    else if (shape == 2) c.variant = 304;
-    // (shape 0 keeps variant 4 = 64 x 64 tiles: only in builds with CUDECOMP_TUNING_VARIANTS)
+    // 4-byte elements, 16-byte lanes, plain kernel: 64 x 128 tiles, variant 304 (512-byte destination segments; measured on
+    // the 8-GiB fp32 cycle, profiles/r04_tuning.md: 11.22 ms against 11.69 for 64 x 64 and 128 x 64)
+    if (!c.window && es == 4 && vw == 4) c.variant = 304;
     // Large line-aligned moves whose SOURCE rows are the far-strided side (the inverse hops of an axis-contiguous cycle): twice
     // as many source rows per tile, 1-KiB destination segments.  Measured on the 8-GiB permutations (profiles/r05_tuning.md):
     // fp64 64 x 128 2.69 -> 2.65 ms, complex128 32 x 64 2.70 -> 2.66 ms; the forward hops lose with these tiles and keep theirs.
     const bool aligned = !c.window && !src_mis && dst_bits % align_req == 0;
     const bool far_src = aligned && c.stream == 2 && c.dm.ss[1] > 8 * c.dm.ds[0];
-    bool tall = false;
-    if (far_src && es == 8 && vw == 2 && c.swizzle) {
-      c.variant = 302;
-      tall = true;
-    } else if (far_src && es == 16 && !c.swizzle) {
-      c.variant = 301;
-      tall = true;
-    }
-    const int ti = (es == 16) ? 32 : ((wide || shape == 1) ? 128 : 64);
-    const int tj = (es == 16) ? (tall ? 64 : 32) : (((c.window && es == 4) || shape == 2 || tall) ? 128 : 64);
+    if (far_src && es == 8 && vw == 2) c.variant = 302;
+    else if (far_src && es == 16) c.variant = 301;
+    int ti = 0, tj = 0;
+    tileOf(es, c.variant, c.window, &ti, &tj);
     c.t0 = (unsigned int)((c.dm.e[0] + ti - 1) / ti);
     c.t1 = (unsigned int)((c.dm.e[1] + (c.window ? 64 / es - 1 : 0) + tj - 1) / tj);
     // Far-strided DESTINATION (the forward hops of an axis-contiguous cycle: destination rows e.g. 8 MiB apart, source rows
@@ -262,17 +252,16 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
     // planner says the move covers whole interior rows of the pencil (dst_row_pitch: the gap cells are then halo / padding
     // cells nobody else writes during the operation, the contract of rows_dense_kernel) j and k are fused into the slab's
     // linear positions and the windows run ACROSS the row ends (transpose_lines_kernel, kernels_lines.hip).
-    if (c.window && !wide && in.dst_row_pitch > 0 && !remote && (!tuning || (tuning->dense_rows != 0 && tuning->lines_mode != 0))) {
+    if (c.window && in.dst_row_pitch > 0 && !remote && tuning.dense_rows != 0) {
       i64 planned_row = -1;
       for (int i = 0; i < 3; ++i)
         if (in.ds[i] == 1 && in.extent[i] > 1) planned_row = in.extent[i];
-      const int ub = linesUnitBytes(tuning ? tuning->lines_unit : 128);
+      constexpr int ub = kLinesUnitBytes;
       const long long ej = c.dm.e[1], ek = c.dm.e[2], dk = c.dm.ds[2], gap = dk - ej;
       const long long span = (ek - 1) * dk + ej;
       if (ek > 1 && planned_row == ej && dk == in.dst_row_pitch && gap > 0 && gap * es <= kDenseMaxGapBytes && gap * 8 <= ej &&
           c.dm.ds[0] >= span && span < (1ll << 30) && c.dm.e[0] < (1ll << 30) && dk >= tj + ub / es) {
         c.lines = true;
-        c.unit = ub;
         // 16-byte lanes need whole vectors along i only: the windows run over linear positions, whatever the row length
         c.variant = (es < 16 && c.dm.e[0] % (16 / es) == 0) ? 16 / es : 1;
         c.t1 = (unsigned int)((span + ub / es - 1 + tj - 1) / tj);  // windows along the linear positions (+ one unit of phase slack)
@@ -282,16 +271,13 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
         // Measured on two boxes, fp64 forward hops onto halo pencils (profiles/r06_tuning.md): 1024^3 halo 1 window kernel
         // 3.52 ms -> 3.14 (2 KiB; 32 KiB 3.19-3.29, 256 KiB 3.45-3.77); config 5's pencil X->Y (2048 slabs) 1.72-1.77 -> 1.55-1.61
         // (32 KiB; 2 KiB 1.66), Y->Z (260-element rows) 1.81 -> 1.66 (2 KiB; 32 KiB 1.79-1.86).
-        const long long group = tuning ? tuning->lines_group : 16;
-        const bool several_groups = group > 0 && group < (long long)c.t0;
-        const long long run_kib = (tuning && tuning->lines_run_kib >= 0) ? tuning->lines_run_kib : (several_groups ? 32 : 2);
-        const long long run = run_kib > 0 ? std::max<long long>(1, (run_kib << 10) / ((long long)tj * es)) : 1;
+        constexpr long long kGroup = 16;
+        const bool several_groups = kGroup < (long long)c.t0;
+        const long long run_kib = several_groups ? 32 : 2;
+        const long long run = std::max<long long>(1, (run_kib << 10) / ((long long)tj * es));
         c.p0 = (long long)c.t1 >= 2 * run ? (int)run : 0;
         c.p1 = 1 | 2 | 8;  // XCD-contiguous, along the destination first, "lines"
-        if (group > 0 && group < (long long)c.t0) c.p1 |= (int)(group << 8);
-#ifdef CUDECOMP_TUNING_VARIANTS
-        if (tuning && tuning->lines_walk == 2) c.p1 |= 32;
-#endif
+        if (several_groups) c.p1 |= (int)(kGroup << 8);
         c.blocks = (unsigned long long)c.t0 * c.t1;
       }
       // ... and the other orientation: the tile's OWN rows i are the adjacent ones (inverse hops of the cycle, unpack-side
@@ -299,10 +285,8 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
       // same tile column of the next row: a row's last window runs on into it (transpose_rowlines_kernel, kernels_rowlines.hip).
       const long long ei = c.dm.e[0], di = c.dm.ds[0], rgap = di - ej;
       if (!c.lines && planned_row == ej && di == in.dst_row_pitch && rgap > 0 && rgap * es <= kDenseMaxGapBytes && rgap * 8 <= ej &&
-          ej > 2 * (tj + ub / es) && ei >= 2 && ei < (1ll << 30) && di < (1ll << 30) && (ek == 1 || dk >= (ei - 1) * di + ej) &&
-          ub == 128) {
+          ej > 2 * (tj + ub / es) && ei >= 2 && ei < (1ll << 30) && di < (1ll << 30) && (ek == 1 || dk >= (ei - 1) * di + ej)) {
         c.rowlines = true;
-        c.unit = ub;
         c.variant = (es < 16 && ei % (16 / es) == 0) ? 16 / es : 1;
         c.t1 = (unsigned int)((di - 1 + ub / es - 1) / tj + 1);  // windows per row: through the one that holds the last gap cell
         c.p0 = 0;
@@ -330,60 +314,47 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
 
 char g_last_kernel[96] = "";
 
-void tileOf(int es, int variant, bool window, int* ti, int* tj) {
-  if (es == 16) {
-    *ti = 32;
-    *tj = variant == 301 ? 64 : 32;
-  } else if (window) {
-    *ti = variant >= 100 ? 128 : 64;
-    *tj = es == 4 ? 128 : 64;
-  } else {
-    *ti = variant == 204 ? 128 : 64;
-    *tj = (variant == 304 || variant == 302) ? 128 : 64;
-  }
-}
-
-void launchBatch(MoveClass cls, int variant, int stream_access, bool swizzle, bool window, bool dense, int lines_unit, bool rowlines,
-                 int es, const Batch& b, unsigned int blocks, hipStream_t stream) {
+void launchBatch(const Classified& c, int es, const Batch& b, unsigned int blocks, hipStream_t stream) {
+  const int variant = c.variant, stream_access = c.stream;
   // what ran last, in the words of the kernel templates (bench.py reports its dominant kernel from here)
   int ti = 0, tj = 0;
-  tileOf(es, variant, window, &ti, &tj);
-  if (cls == MOVE_ROWS_VEC && dense)
+  tileOf(es, variant, c.window, &ti, &tj);
+  if (c.cls == MOVE_ROWS_VEC && c.dense)
     snprintf(g_last_kernel, sizeof(g_last_kernel), "rows_dense_kernel<%d>", stream_access >= 1 ? 1 : 0);
-  else if (cls == MOVE_ROWS_VEC)
-    snprintf(g_last_kernel, sizeof(g_last_kernel), "%s<%d,%d>", window ? "rows_shifted_kernel" : "rows_kernel",
+  else if (c.cls == MOVE_ROWS_VEC)
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "%s<%d,%d>", c.window ? "rows_shifted_kernel" : "rows_kernel",
              variant, stream_access == 3 ? 3 : (stream_access >= 1 ? 1 : 0));
-  else if (cls == MOVE_TRANSPOSE && rowlines)
-    snprintf(g_last_kernel, sizeof(g_last_kernel), "transpose_rowlines_kernel<%d,%d,%d,%d,%d,%d>", es, variant % 100, ti, tj,
-             (stream_access == 2 || stream_access == 4) ? 4 : 0, lines_unit);
-  else if (cls == MOVE_TRANSPOSE && lines_unit)
-    snprintf(g_last_kernel, sizeof(g_last_kernel), "transpose_lines_kernel<%d,%d,%d,%d,%d,%d>", es, variant % 100, ti, tj,
-             (stream_access == 2 || stream_access == 4) ? 4 : 0, lines_unit);
-  else if (cls == MOVE_TRANSPOSE && window)
-    snprintf(g_last_kernel, sizeof(g_last_kernel), "transpose_window_kernel<%d,%d,%d,%d,%d>", es, variant % 100, ti, tj,
+  else if (c.cls == MOVE_TRANSPOSE && (c.rowlines || c.lines))
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "%s<%d,%d,%d,%d,%d,%d>",
+             c.rowlines ? "transpose_rowlines_kernel" : "transpose_lines_kernel", es, variant, ti, tj,
+             (stream_access == 2 || stream_access == 4) ? 4 : 0, kLinesUnitBytes);
+  else if (c.cls == MOVE_TRANSPOSE && c.window)
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "transpose_window_kernel<%d,%d,%d,%d,%d>", es, variant, ti, tj,
              (stream_access == 2 || stream_access == 4) ? 4 : stream_access);
-  else if (cls == MOVE_TRANSPOSE)
+  else if (c.cls == MOVE_TRANSPOSE)
     snprintf(g_last_kernel, sizeof(g_last_kernel), "transpose_kernel<%d,%d,%d,%d,%d,%s>", es, variant % 100, ti, tj, stream_access,
-             swizzle ? "true" : "false");
+             es != 16 ? "true" : "false");  // (4- and 8-byte elements: swizzled LDS tile)
   else
     snprintf(g_last_kernel, sizeof(g_last_kernel), "generic_kernel<%d,%s>", es, stream_access == 3 ? "true" : "false");
-  switch (cls) {
+  switch (c.cls) {
     case MOVE_ROWS_VEC:
-      launchRowsBatch(dense ? 2 : (window ? 1 : 0), variant, stream_access, b, blocks, stream);
+      launchRowsBatch(c.dense ? 2 : (c.window ? 1 : 0), variant, stream_access, b, blocks, stream);
       break;
     case MOVE_TRANSPOSE:
-      if (rowlines) launchRowLinesBatch(es, variant % 100, stream_access, b, blocks, stream);
-      else if (lines_unit) launchLinesBatch(es, variant % 100, stream_access, lines_unit, b, blocks, stream);
-      else if (window) launchWindowBatch(es, variant % 100, variant >= 100, stream_access, b, blocks, stream);
-      else if (es == 4) launchTransposeBatch4(variant, stream_access, swizzle, b, blocks, stream);
-      else if (es == 8) launchTransposeBatch8(variant, stream_access, swizzle, b, blocks, stream);
-      else launchTransposeBatch16(variant, stream_access, swizzle, b, blocks, stream);
+      if (c.rowlines) launchRowLinesBatch(es, variant, stream_access, b, blocks, stream);
+      else if (c.lines) launchLinesBatch(es, variant, stream_access, b, blocks, stream);
+      else if (c.window) launchWindowBatch(es, variant, stream_access, b, blocks, stream);
+      else if (es == 4) launchTransposeBatch4(variant, stream_access, b, blocks, stream);
+      else if (es == 8) launchTransposeBatch8(variant, stream_access, b, blocks, stream);
+      else launchTransposeBatch16(variant, stream_access, b, blocks, stream);
       break;
     default:
       launchGenericBatch(es, stream_access == 3, b, blocks, stream);
       break;
   }
 }
+
+const KernelTuning kDefaultTuning;
 
 }  // namespace
 
@@ -395,7 +366,7 @@ void describeMove(const Move3D& m, const void* src, void* dst, int es, const Ker
   mm.dst_buf = BUF_OUT;
   mm.src_off = mm.dst_off = 0;
   void* bufs[3] = {const_cast<void*>(src), dst, nullptr};
-  const Classified c = classify(mm, bufs, es, tuning, nullptr, false);
+  const Classified c = classify(mm, bufs, es, tuning ? *tuning : kDefaultTuning, nullptr, false);
   int ti = 0, tj = 0;
   if (c.cls == MOVE_TRANSPOSE) tileOf(es, c.variant, c.window, &ti, &tj);
   else if (c.cls == MOVE_ROWS_VEC) ti = c.dense ? 2 : (c.window ? 1 : 0);  // rows: the kernel (plain / shifted / dense) in the tile_i slot
@@ -406,12 +377,13 @@ void describeMove(const Move3D& m, const void* src, void* dst, int es, const Ker
 void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
                  const KernelTuning* tuning, KernelStats* stats, void* const* dst_base_override) {
   const bool remote = dst_base_override != nullptr;
+  const KernelTuning& t = tuning ? *tuning : kDefaultTuning;
   if (es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
   std::vector<Classified> cs;
   cs.reserve(n);
   for (int i = 0; i < n; ++i) {
     if (moves[i].elements() == 0) continue;
-    cs.push_back(classify(moves[i], bufs, es, tuning, dst_base_override ? dst_base_override[i] : nullptr, remote));
+    cs.push_back(classify(moves[i], bufs, es, t, dst_base_override ? dst_base_override[i] : nullptr, remote));
   }
   // moves of one phase are independent, so they may be regrouped by kernel flavour
   std::vector<bool> done(cs.size(), false);
@@ -421,8 +393,8 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
     unsigned long long blocks = 0;
     for (size_t j = i; j < cs.size() && b.n < kMaxBatch; ++j) {
       if (done[j] || cs[j].cls != cs[i].cls || cs[j].variant != cs[i].variant || cs[j].stream != cs[i].stream ||
-          cs[j].swizzle != cs[i].swizzle || cs[j].window != cs[i].window || cs[j].dense != cs[i].dense ||
-          cs[j].lines != cs[i].lines || cs[j].unit != cs[i].unit || cs[j].rowlines != cs[i].rowlines)
+          cs[j].window != cs[i].window || cs[j].dense != cs[i].dense || cs[j].lines != cs[i].lines ||
+          cs[j].rowlines != cs[i].rowlines)
         continue;
       if (blocks + cs[j].blocks > 0x7fffffffULL) {
         if (b.n == 0) CD_NOT_SUPPORTED("single block move too large for one launch");
@@ -444,8 +416,7 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
     // run one after the other, a 2-KiB slice of every 8-KiB row keeps part of the memory channels idle.  Served round
     // robin, the workgroups in flight cover whole rows (C3 per-rank unpacks: 0.43-0.47 -> 0.35 ms, r02_tuning.md).
     // Transposes keep their XCD-contiguous tile walk (interleaving them measured slightly slower).
-    const bool il_local = cs[i].cls != MOVE_TRANSPOSE && (!tuning || tuning->interleave_rows != 0);
-    if ((dst_base_override || il_local) && b.n > 1) {
+    if ((dst_base_override || cs[i].cls != MOVE_TRANSPOSE) && b.n > 1) {
       unsigned long long widest = 0;
       for (int k = 0; k < b.n; ++k) widest = std::max<unsigned long long>(widest, b.first_block[k + 1] - b.first_block[k]);
       if (widest * b.n <= 0x7fffffffULL) {
@@ -453,8 +424,7 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
         blocks = widest * b.n;
       }
     }
-    launchBatch(cs[i].cls, cs[i].variant, cs[i].stream, cs[i].swizzle, cs[i].window, cs[i].dense,
-                (cs[i].lines || cs[i].rowlines) ? cs[i].unit : 0, cs[i].rowlines, es, b, (unsigned int)blocks, stream);
+    launchBatch(cs[i], es, b, (unsigned int)blocks, stream);
     if (stats) stats->launches[cs[i].cls] += 1;
   }
 }

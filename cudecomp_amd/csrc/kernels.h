@@ -23,24 +23,11 @@ struct KernelTuning {
   int force_class = -1;          // tests / CUDECOMP_FORCE_GENERIC_KERNELS: force MOVE_GENERIC (2) to cross-check the fast paths
   bool no_streaming = false;     // never use non-temporal access (CUDECOMP_DISABLE_STREAMING_ACCESS=1)
   bool force_streaming = false;  // tests: non-temporal access regardless of the move size
-  // tuning switches (read from the environment by `make TUNING_VARIANTS=1` builds only, csrc/api.cc):
-  int walk_order = -1;           // transposes walk tiles i first (0) / j first (1); -1 = by strides (CUDECOMP_TILE_WALK)
-  int interleave_rows = 1;       // batched row copies: workgroups serve the moves round robin (0: one move after the other)
+  int walk_order = -1;           // tests: transposes walk tiles i first (0) / j first (1, without runs); -1 = by strides
   int dense_rows = -1;           // moves of whole rows onto halo-carrying pencils: 0 = never rewrite the halo / padding cells between
                                  // consecutive rows (no rows_dense_kernel, no transpose_lines_kernel / transpose_rowlines_kernel: the shifted / window kernels
-                                 // instead); CUDECOMP_PRESERVE_OUTPUT_HALOS=1 in every build
-  int lines_mode = -1;           // permutations onto halo-carrying pencils whose consecutive batch planes are adjacent rows:
-                                 // -1 transpose_lines_kernel when it applies, 0 never (CUDECOMP_LINES_MODE, tuning builds)
-  int lines_unit = 128;          // its alignment unit in bytes (64: tuning builds only, CUDECOMP_LINES_UNIT)
-  int lines_walk = 0;            // 2 = no gap gather (timing only, results WRONG in the gap cells; CUDECOMP_LINES_WALK, tuning builds)
-  int lines_group = 16;          // its tile walk: tile rows per group, 0 = all (CUDECOMP_LINES_GROUP)
-  int lines_run_kib = -1;        // ... and KiB of every destination slab written before the next tile row of the group; 0 = one
-                                 // window (tile rows first inside the group), -1 = by shape (CUDECOMP_LINES_RUN_KIB)
-  int rotate_walk = -1;          // in-place rotation: the orbit walk, -1 = default (kernels_rotate.hip; CUDECOMP_ROTATE_WALK)
-  int window_mode = -1;          // transposes onto rows off the 64-byte grid: -1 window kernel for moves >= 1 MiB, 0 never, 1 always
-  int window_wide = 0;           // window kernel, 8-byte elements: 1 = 128 x 64 tiles with 512 threads (CUDECOMP_WINDOW_WIDE=1)
-  int tile_shape = -1;           // 4-byte transposes with 16-byte lanes: 64 x 128 tiles (2, the default), 64 x 64 (0) or 128 x 64 (1);
-                                 // CUDECOMP_TILE_SHAPE; measured on the 8-GiB fp32 cycle (profiles/r04_tuning.md): 11.22 / 11.69 / 11.69 ms
+                                 // instead); CUDECOMP_PRESERVE_OUTPUT_HALOS=1
+  int window_mode = -1;          // tests: transposes onto rows off the 64-byte grid: -1 window kernel for moves >= 1 MiB, 0 never, 1 always
 };
 
 // Execute `n` independent moves (disjoint destinations) of `es`-byte elements.  bufs[BufId] are the

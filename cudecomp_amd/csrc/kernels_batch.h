@@ -43,25 +43,26 @@ struct Batch {
 }  // namespace kern
 
 // ---- launchers, one per code object (host side; csrc/kernels.cc decides what runs) -------------------------------------------
-// stream_access: 0 default caching, 1 non-temporal loads, 2 non-temporal loads + stores, 3 non-temporal loads + remote
-// (system-scope write-through) stores, 4 cached loads + non-temporal stores (see storePolicyOf)
+// stream_access: 0 default caching, 2 non-temporal loads + stores, 3 non-temporal loads + remote (system-scope write-through)
+// stores, 4 cached loads + non-temporal stores (see storePolicyOf)
 // rows: mode 0 plain, 1 shifted (lanes on the destination's 64-byte grid), 2 dense (whole lines across row ends, Move3D::dst_row_pitch)
 void launchRowsBatch(int mode, int vector_bytes, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 int rowsDenseBytesPerBlock();  // bytes of a plane's span one workgroup of the dense row copy covers
 void launchGenericBatch(int es, bool remote, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-// transposes: `variant` = elements per 16-byte lane group (1 = element-wise lanes), plus 300 for the 64 x 128 tile of 4-byte
-// elements (tuning builds: 200 = 128 x 64, 0 = 64 x 64)
-void launchTransposeBatch4(int variant, int stream_access, bool swizzle, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-void launchTransposeBatch8(int variant, int stream_access, bool swizzle, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-void launchTransposeBatch16(int variant, int stream_access, bool swizzle, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-void launchWindowBatch(int es, int variant, bool wide, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-// kernels_lines.hip: windows over the destination's linear positions across row ends (unit_bytes: 128; 64 in tuning builds)
-void launchLinesBatch(int es, int variant, int stream_access, int unit_bytes, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-int linesUnitBytes(int unit_choice);  // the unit the build really has for a wish
+// transposes: `variant` = elements per 16-byte lane group (1 = element-wise lanes), plus 300 for the longer tiles: 64 x 128
+// for 4-byte elements with 16-byte lanes; 64 x 128 (8-byte) and 32 x 64 (16-byte) for far-strided sources.  4- and 8-byte
+// elements use the XOR-swizzled LDS tile, 16-byte elements the padded one.
+void launchTransposeBatch4(int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+void launchTransposeBatch8(int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+void launchTransposeBatch16(int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+void launchWindowBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+// kernels_lines.hip: windows over the destination's linear positions across row ends (128-byte units)
+constexpr int kLinesUnitBytes = 128;
+void launchLinesBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // kernels_rowlines.hip: the same idea for destinations whose adjacent rows are the tile's own rows (128-byte units)
 void launchRowLinesBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
-void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream, int walk = -1);
+void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);
 
 }  // namespace cudecomp

@@ -150,9 +150,6 @@ __global__ __launch_bounds__(kThreads) void transpose_lines_kernel(const Batch b
     }
     // gap rows: a gap cell of every slab of the tile -- what the destination holds there goes back unchanged.  After the
     // source rows, by the lanes that own the LDS rows (program order: no barrier needed before they overwrite their own cells).
-#ifdef CUDECOMP_TUNING_VARIANTS
-    if (b.p1[mi] & 32) gap_passes = 0;  // (bit 32, measurements only: no gap gather -- the gap cells come back WRONG)
-#endif
     if (gap_passes) {
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
@@ -213,28 +210,10 @@ void launchLinesT(int variant, int es, const Batch& b, unsigned int blocks, hipS
 }  // namespace
 }  // namespace kern
 
-int linesUnitBytes(int unit_choice) {
-#ifdef CUDECOMP_TUNING_VARIANTS
-  if (unit_choice == 64) return 64;
-#endif
-  (void)unit_choice;
-  return 128;
-}
-
-void launchLinesBatch(int es, int variant, int stream_access, int unit_bytes, const kern::Batch& b, unsigned int blocks,
-                      hipStream_t stream) {
+void launchLinesBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream) {
   // local destinations only (the gap cells are read back): never the remote-store policy
-  const bool streaming = stream_access == 4 || stream_access == 2;
-#ifdef CUDECOMP_TUNING_VARIANTS
-  if (unit_bytes == 64) {
-    if (streaming) kern::launchLinesT<4, 64>(variant, es, b, blocks, stream);
-    else kern::launchLinesT<0, 64>(variant, es, b, blocks, stream);
-    return;
-  }
-#endif
-  (void)unit_bytes;
-  if (streaming) kern::launchLinesT<4, 128>(variant, es, b, blocks, stream);
-  else kern::launchLinesT<0, 128>(variant, es, b, blocks, stream);
+  if (stream_access == 4 || stream_access == 2) kern::launchLinesT<4, kLinesUnitBytes>(variant, es, b, blocks, stream);
+  else kern::launchLinesT<0, kLinesUnitBytes>(variant, es, b, blocks, stream);
 }
 
 }  // namespace cudecomp

@@ -145,11 +145,10 @@ bool rotateSupported(int es, long long n) {
 }
 
 // direction: +1 forward (new[p0,p1,p2] = old[p2,p0,p1]), -1 inverse; buffer = the N^3 array (in place)
-// walk: -1 = default, else as rotate_walk.h says (CUDECOMP_ROTATE_WALK in tuning builds)
-void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream, int walk) {
+void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream) {
   if (!rotateSupported(es, n)) CD_INTERNAL_ERROR("in-place rotation not available for this shape");
   const int nb = (int)(n / rotateTile(es));
-  walk = rotateWalkFor(walk, nb);
+  const int walk = kRotateWalk;  // the per-XCD walk (rotate_walk.h)
   const dim3 grid((unsigned int)rotateWalkGrid(nb, walk)), block(kern::kThreads);
   char* b = static_cast<char*>(buffer);
   if (es == 8) {

@@ -131,32 +131,27 @@ __global__ __launch_bounds__(NT) void transpose_window_kernel(const Batch b) {
 }
 
 template <int STREAM>
-void launchWindowT(int variant, int es, const Batch& b, unsigned int blocks, hipStream_t stream, bool wide) {
+void launchWindowT(int variant, int es, const Batch& b, unsigned int blocks, hipStream_t stream) {
   const dim3 grid(blocks), block(kThreads);
   if (es == 4) {
     if (variant == 4) transpose_window_kernel<4, 4, 64, 128, STREAM><<<grid, block, 0, stream>>>(b);
     else transpose_window_kernel<4, 1, 64, 128, STREAM><<<grid, block, 0, stream>>>(b);
   } else if (es == 8) {
-#ifdef CUDECOMP_TUNING_VARIANTS
-    if (variant == 2 && wide) transpose_window_kernel<8, 2, 128, 64, STREAM, 512><<<grid, dim3(512), 0, stream>>>(b);
-    else
-#endif
     if (variant == 2) transpose_window_kernel<8, 2, 64, 64, STREAM><<<grid, block, 0, stream>>>(b);
     else transpose_window_kernel<8, 1, 64, 64, STREAM><<<grid, block, 0, stream>>>(b);
   } else {
     transpose_window_kernel<16, 1, 32, 32, STREAM><<<grid, block, 0, stream>>>(b);
   }
-  (void)wide;
   CD_CHECK_HIP(hipGetLastError());
 }
 
 }  // namespace
 }  // namespace kern
 
-void launchWindowBatch(int es, int variant, bool wide, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream) {
-  if (stream_access == 3) kern::launchWindowT<3>(variant, es, b, blocks, stream, wide);
-  else if (stream_access == 4 || stream_access == 2) kern::launchWindowT<4>(variant, es, b, blocks, stream, wide);
-  else kern::launchWindowT<0>(variant, es, b, blocks, stream, wide);
+void launchWindowBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream) {
+  if (stream_access == 3) kern::launchWindowT<3>(variant, es, b, blocks, stream);
+  else if (stream_access == 4 || stream_access == 2) kern::launchWindowT<4>(variant, es, b, blocks, stream);
+  else kern::launchWindowT<0>(variant, es, b, blocks, stream);
 }
 
 }  // namespace cudecomp

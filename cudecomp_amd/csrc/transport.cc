@@ -1094,10 +1094,6 @@ void peerMeasureLink(cudecompHandle_t h) {
     CD_CHECK_HIP(hipEventCreate(&e0));
     CD_CHECK_HIP(hipEventCreate(&e1));
     for (int engine = 0; engine < 2; ++engine) {
-#ifdef CUDECOMP_TUNING_VARIANTS  // (code-size bisect, scripts/probe/code_size_bisect.sh: probe with one engine only)
-      if (const char* only = std::getenv("CUDECOMP_LINK_PROBE_ENGINES"))
-        if ((engine == 0) != (std::strcmp(only, "sdma") == 0)) continue;
-#endif
       for (int rep = 0; rep < 3; ++rep) {  // rep 0 warms up (page mapping, code load)
         h->boot->barrier();
         CD_CHECK_HIP(hipEventRecord(e0, st));

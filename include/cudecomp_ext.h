@@ -217,9 +217,8 @@ cudecompResult_t cudecompExtEstimateCycleMs(cudecompHandle_t handle, const cudec
  * force_generic is a bit mask: 1 selects the element-wise fallback kernel, 2 forces the streaming
  * (non-temporal) variants that are normally used only for moves of 32 MiB and more, 4 selects the window variant of
  * the LDS transpose for every destination off the 64-byte grid (normally only for moves of 1 MiB and more), 8 disables
- * it; 16 / 32: 128 x 64 / 64 x 64 tiles for 4-byte transposes (tuning variants; the default is 64 x 128); 64 / 128: transposes walk
- * their tiles i first / j first (without runs); 256: the move covers whole rows of a halo-carrying destination, the cells between
- * consecutive rows may be rewritten with their own content (dense row copy).  *kernel_class (optional) receives the
+ * it; 64 / 128: transposes walk their tiles i first / j first (without runs); 256: the move covers whole rows of a
+ * halo-carrying destination, the cells between consecutive rows may be rewritten with their own content (dense row copy).  *kernel_class (optional) receives the
  * kernel flavour used: 0 rows, 1 LDS transpose, 2 generic. */
 cudecompResult_t cudecompExtMove3D(const void* src, void* dst, int32_t es, const int64_t extent[3],
                                    const int64_t ss[3], const int64_t ds[3], int32_t force_generic,

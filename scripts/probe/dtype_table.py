@@ -1,5 +1,5 @@
-"""bench.py's per-dtype table on its own (extra.dtypes), e.g. to A/B a tuning switch:
-    CUDECOMP_TILE_SHAPE=1 python scripts/probe/dtype_table.py [fp32|complex64|complex128 ...]"""
+"""bench.py's per-dtype table on its own (extra.dtypes):
+    python scripts/probe/dtype_table.py [fp32|complex64|complex128 ...]"""
 import json
 import os
 import sys

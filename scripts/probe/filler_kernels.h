@@ -1,5 +1,6 @@
-// filler_kernels.h -- device code that is never launched, to grow a code object by a chosen amount (code-size bisect of round 5,
-// scripts/probe/code_size_bisect.sh).  -DFILLER_NK=<kernels> -DFILLER_BODY=<statements per kernel>.
+// filler_kernels.h -- device code that is never launched, to grow a code object by a chosen amount (code-size bisect of round 5:
+// a code object of its own through scripts/probe/filler.hip, or -include'd into one of the library's .hip files).
+// -DFILLER_NK=<kernels> -DFILLER_BODY=<statements per kernel>.
 #pragma once
 #include <hip/hip_runtime.h>
 

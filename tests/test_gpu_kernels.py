@@ -20,12 +20,10 @@ def run_move(es, extent, ss, ds, src_len, dst_len, src_off=0, dst_off=0, seed=0,
     exp = dst0.copy()
     orc.move3d_reference(src, exp, extent, ss, ds, src_off, dst_off)
     # fast path, generic fallback, fast path with streaming access, window variant of the transposes (with and without
-    # streaming) for every destination off the 64-byte grid; 4-byte elements: the tile-shape switches (they select other
-    # tiles only in `make TUNING_VARIANTS=1` builds, the default build always uses 64 x 128); the diagnostic store policy /
-    # tile walk of the shared-GPU hunt
+    # streaming) for every destination off the 64-byte grid; the tile walks i first / j first (64, 128)
     # 256: "the cells between consecutive destination rows are the move's" -> row copies onto rows off the 64-byte grid take the
     # dense walk (rows_dense_kernel) when the gap is a few cells; every byte of the destination is compared either way
-    for force_generic in (0, 1, 2, 4, 6) + ((16, 32, 18, 34) if es == 4 else ()) + (64, 128 + 2, 256 + 4, 256 + 4 + 2):
+    for force_generic in (0, 1, 2, 4, 6, 64, 128 + 2, 256 + 4, 256 + 4 + 2):
         d_src, d_dst = G.to_device(src.view(np.uint8)), G.to_device(dst0.view(np.uint8))
         cls = cd.cudecompExtMove3D(d_src.data_ptr() + src_off * es, d_dst.data_ptr() + dst_off * es, es, extent, ss, ds,
                                    force_generic, G.stream_ptr())
@@ -68,6 +66,31 @@ def test_transposes_all_permutations(es):
             for i, p in enumerate(perm):
                 ds[p] = so[i]
             run_move(es, ext_in, sin, ds, sin[2] * c + 8, so[2] * ext_in[perm[2]] + 8, seed=a * 7 + b)
+
+
+@pytest.mark.parametrize("es", [4, 8, 16])
+def test_planned_moves_onto_halo_and_padding_pencils(es):
+    """The pack and unpack moves the planner makes for every rank of 4-rank grids whose pencils carry halos and padding
+    (halo 1 everywhere and padding 1 on X and Z pencils, axis-contiguous; per-axis halos (2,1,1) / (1,2,1) / (1,1,2), default
+    and axis-contiguous): their destinations lie off the 64-byte grid, so run_move's flags 4 / 6 put these small moves
+    through the window kernel (and 256 through the whole-line kernels) against numpy.  Each distinct move once."""
+    orders = {"default": [(0, 1, 2)] * 3, "contiguous": [(0, 1, 2), (1, 2, 0), (2, 0, 1)]}
+    axes = {"XToY": (0, 1), "YToZ": (1, 2), "ZToY": (2, 1), "YToX": (1, 0)}
+    shifted = [(2, 1, 1), (1, 2, 1), (1, 1, 2)]
+    configs = [("contiguous", [(1, 1, 1)] * 3, [(1, 1, 1), None, (1, 1, 1)]),
+               ("default", shifted, [None] * 3), ("contiguous", shifted, [None] * 3)]
+    moves = set()
+    for (layout, halo, pad), pdims in itertools.product(configs, [(1, 4), (2, 2), (4, 1)]):
+        grid = cd.make_grid_spec((64, 60, 68), pdims, orders[layout])
+        for rank, op in itertools.product(range(4), cd.OPS):
+            a, b = axes[op]
+            plan = cd.cudecompExtPlanTranspose(grid, rank, op, halo[a], halo[b], pad[a], pad[b])
+            for m in list(plan.pack)[:plan.n_pack] + list(plan.unpack)[:plan.n_unpack]:
+                moves.add((tuple(m.extent), tuple(m.ss), tuple(m.ds), m.src_off, m.dst_off))
+    span = lambda extent, strides: sum((e - 1) * s for e, s in zip(extent, strides)) + 1
+    for seed, (extent, ss, ds, src_off, dst_off) in enumerate(sorted(moves)):
+        if 0 not in extent:
+            run_move(es, extent, ss, ds, src_off + span(extent, ss), dst_off + span(extent, ds), src_off, dst_off, seed=seed)
 
 
 @pytest.mark.parametrize("es", [4, 8, 16])

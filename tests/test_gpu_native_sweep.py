@@ -21,10 +21,6 @@ pytestmark = pytest.mark.gpu
 PERMS = [" ".join(map(str, p)) for p in itertools.permutations((0, 1, 2))]
 PDIMS = [(1, 4), (2, 2), (4, 1)]
 Z = "0 0 0"
-# switches that only the `make TUNING_VARIANTS=1` build of the library reads (csrc/api.cc: tuningSwitch)
-TUNING_SWITCHES = {"CUDECOMP_INTERLEAVE_ROWS", "CUDECOMP_WINDOW_STORES", "CUDECOMP_WINDOW_WIDE", "CUDECOMP_TILE_WALK",
-                   "CUDECOMP_TILE_SHAPE"}
-TUNING_LIB_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cudecomp_amd", "lib_tuning")
 
 
 def _tcase(pr, pc, backend, gd=Z, hx=Z, hy=Z, hz=Z, px=Z, py=Z, pz=Z, extra="", oop=False):
@@ -150,25 +146,19 @@ def test_sweep_eight_ranks():
 @pytest.mark.parametrize("env", [{"CUDECOMP_ENABLE_CUDA_GRAPHS": "1"},
                                  {"CUDECOMP_ENABLE_PERFORMANCE_REPORT": "1", "CUDECOMP_PERFORMANCE_REPORT_DETAIL": "2",
                                   "CUDECOMP_PERFORMANCE_REPORT_WARMUP_SAMPLES": "0"},
-                                 {"CUDECOMP_DISABLE_STREAMING_ACCESS": "1", "CUDECOMP_TILE_WALK": "0"},
+                                 {"CUDECOMP_DISABLE_STREAMING_ACCESS": "1"},
                                  {"CUDECOMP_FORCE_GENERIC_KERNELS": "1"}, {"CUDECOMP_DISABLE_HALO_OVERLAP": "1"},
-                                 {"CUDECOMP_FORCE_HALO_OVERLAP": "1"}, {"CUDECOMP_WINDOW_STORES": "1"},
+                                 {"CUDECOMP_FORCE_HALO_OVERLAP": "1"},
                                  {"CUDECOMP_DISABLE_DIRECT_PUT": "1", "CUDECOMP_PEER_COPY_ENGINE": "sdma"},
-                                 {"CUDECOMP_PEER_COPY_ENGINE": "cu"}, {"CUDECOMP_INTERLEAVE_ROWS": "0"},
+                                 {"CUDECOMP_PEER_COPY_ENGINE": "cu"},
                                  {"CUDECOMP_PIPELINE_STAGES": "1"}, {"CUDECOMP_PIPELINE_STAGES": "7", "CUDECOMP_PEER_COPY_ENGINE": "sdma"},
                                  {"CUDECOMP_WORKSPACE_POOL_MIB": "0"}],
-                         ids=["graphs", "performance_report", "cached_access_i_first", "generic_kernels", "plain_halo_sequence",
-                              "overlapped_halo_any_size", "window_stores_any_size", "copy_engines_staged_put", "kernel_copies",
-                              "row_copies_one_move_after_the_other", "one_pipeline_stage", "seven_pipeline_stages_copy_engines",
-                              "no_workspace_pool"])
+                         ids=["graphs", "performance_report", "cached_access", "generic_kernels", "plain_halo_sequence",
+                              "overlapped_halo_any_size", "copy_engines_staged_put", "kernel_copies",
+                              "one_pipeline_stage", "seven_pipeline_stages_copy_engines", "no_workspace_pool"])
 def test_sweep_library_switches_do_not_change_results(env):
     """Environment switches of the library (graph capture of the pipelined pack loop, the performance report, kernel
-    tuning / debug switches) on a slice of the base sweep: results stay exact.  Tuning switches exist only in the
-    `make TUNING_VARIANTS=1` build of the library (cudecomp_amd/lib_tuning): those entries run against it."""
-    if TUNING_SWITCHES & set(env):
-        if not os.path.exists(os.path.join(TUNING_LIB_DIR, "libcudecomp.so")):
-            pytest.skip("cudecomp_amd/lib_tuning not built (make -C cudecomp_amd TUNING_VARIANTS=1)")
-        env = dict(env, LD_LIBRARY_PATH=TUNING_LIB_DIR + os.pathsep + os.environ.get("LD_LIBRARY_PATH", ""))
+    debug switches) on a slice of the base sweep: results stay exact."""
     _switch_sweep(env)
 
 
@@ -188,9 +178,6 @@ def _switch_sweep(env):
     lines += [_tcase(pr, pc, 8, hx="2 1 1", hy="1 2 1", hz="1 1 2", extra=mo + " -m", oop=True)   # direct put onto halo-shifted rows
               for (pr, pc), mo in itertools.product(PDIMS, _mem_orders()[::7])]
     jobs = [("transpose_test_R64", 4, lines, dict(env))]
-    if "CUDECOMP_WINDOW_STORES" in env:
-        for dtype in ("R32", "C64"):
-            jobs.append(("transpose_test_" + dtype, 4, [l for l in lines if "--hex 0 0 0" not in l], dict(env)))
     hl = [_hcase(pr, pc, b, ax, h=(1, 2, 1), pad=(1, 0, 0)) for (pr, pc), ax, b in itertools.product(PDIMS, (0, 1, 2), (1, 3))]
     henv = dict(env)
     if os.path.exists(SHIM):

@@ -367,7 +367,7 @@ def test_rotation_restatement_closes_every_orbit():
 
 def test_rotation_walks_visit_every_block_triple_once():
     """The orbit walk of rotate_kernel (csrc/rotate_walk.h, the code the kernel runs, through cudecompExtRotateWalk): for every array
-    size and walk -- the default per-XCD walk with its shears, the cube walks of tuning builds, more shears -- every block triple
+    size and walk -- the default per-XCD walk with its shears, the cube walks the kernel can still take, more shears -- every block triple
     is taken by exactly one workgroup, the rest of the grid maps to none, and the padding stays small.  On the default walk every
     XCD (workgroup % 8) steps through ALL p0 blocks of all three tiles of its orbits within any nb consecutive workgroups of
     its own: what the walk is for (profiles/r06_tuning.md section 8)."""
