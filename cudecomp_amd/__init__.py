@@ -18,6 +18,7 @@ TRANSPOSE_COMM_NCCL, TRANSPOSE_COMM_NCCL_PL = 4, 5
 TRANSPOSE_COMM_NVSHMEM, TRANSPOSE_COMM_NVSHMEM_PL, TRANSPOSE_COMM_NVSHMEM_SM = 6, 7, 8
 HALO_COMM_MPI, HALO_COMM_MPI_BLOCKING, HALO_COMM_NCCL, HALO_COMM_NVSHMEM, HALO_COMM_NVSHMEM_BLOCKING = 1, 2, 3, 4, 5
 FLOAT, DOUBLE, FLOAT_COMPLEX, DOUBLE_COMPLEX = -1, -2, -3, -4
+HALF, BFLOAT16, HALF_COMPLEX = 1, 2, 3  # cudecomp_amd.h: CUDECOMP_AMD_HALF, _BFLOAT16, _HALF_COMPLEX
 AUTOTUNE_GRID_TRANSPOSE, AUTOTUNE_GRID_HALO = 0, 1
 RANK_ORDER_DEFAULT, RANK_ORDER_ROW_MAJOR, RANK_ORDER_COL_MAJOR = 0, 1, 2
 (RESULT_SUCCESS, RESULT_INVALID_USAGE, RESULT_NOT_SUPPORTED, RESULT_INTERNAL_ERROR, RESULT_CUDA_ERROR,

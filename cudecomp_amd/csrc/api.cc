@@ -62,11 +62,14 @@ void checkGridDesc(cudecompHandle_t h, cudecompGridDesc_t gd) {
   if (gd->handle != h) CD_INVALID_USAGE("grid descriptor belongs to a different handle");
 }
 void checkDataType(cudecompDataType_t t) {
-  switch (t) {
+  switch (static_cast<int>(t)) {
     case CUDECOMP_FLOAT:
     case CUDECOMP_DOUBLE:
     case CUDECOMP_FLOAT_COMPLEX:
-    case CUDECOMP_DOUBLE_COMPLEX: return;
+    case CUDECOMP_DOUBLE_COMPLEX:
+    case CUDECOMP_AMD_HALF:  // cudecomp_amd.h
+    case CUDECOMP_AMD_BFLOAT16:
+    case CUDECOMP_AMD_HALF_COMPLEX: return;
     default: CD_INVALID_USAGE("unknown data type");
   }
 }

@@ -57,7 +57,16 @@ class MpiBootstrap : public Bootstrap {
   int rank_ = 0, size_ = 1;
 };
 
-MPI_Datatype mpiType(int es) { return es == 4 ? MPI_FLOAT : (es == 8 ? MPI_DOUBLE : MPI_C_DOUBLE_COMPLEX); }
+// (the exchanges only move bytes: the type gives MPI the element size; 2-byte elements go as MPI_UINT16_T)
+MPI_Datatype mpiType(int es) {
+  switch (es) {
+    case 2: return MPI_UINT16_T;
+    case 4: return MPI_FLOAT;
+    case 8: return MPI_DOUBLE;
+    case 16: return MPI_C_DOUBLE_COMPLEX;
+  }
+  CD_INTERNAL_ERROR("no MPI datatype for this element size");
+}
 
 int toInt(i64 v, const char* what) {
   if (v > std::numeric_limits<int32_t>::max())

@@ -541,7 +541,7 @@ cudecompResult_t cudecompExtDescribeMove(uint64_t src_address, uint64_t dst_addr
                                         const int64_t ss[3], const int64_t ds[3], int32_t flags, int64_t out[10]) {
   try {
     if (!extent || !ss || !ds || !out) CD_INVALID_USAGE("null argument");
-    if (es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 4, 8 or 16");
+    if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
     Move3D m;
     for (int i = 0; i < 3; ++i) {
       m.extent[i] = extent[i];
@@ -572,7 +572,7 @@ cudecompResult_t cudecompExtMove3D(const void* src, void* dst, int32_t es, const
                                    int32_t* kernel_class, hipStream_t stream) {
   try {
     if (!src || !dst || !extent || !ss || !ds) CD_INVALID_USAGE("null argument");
-    if (es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 4, 8 or 16");
+    if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
     Move3D m;
     m.src_buf = BUF_IN;
     m.dst_buf = BUF_OUT;

@@ -12,7 +12,9 @@
 
 #include "bootstrap.h"
 #include "cudecomp.h"
+#include "cudecomp_amd.h"
 #include "decomp.h"
+#include "errors.h"
 #include "kernels.h"
 #include "plan.h"
 
@@ -182,13 +184,19 @@ void ensureDevice(cudecompHandle_t handle);  // throws if no HIP device is usabl
 void buildCommInfo(cudecompHandle_t handle, cudecompGridDesc_t gd);
 void resetCommInfo(cudecompGridDesc_t gd);
 
+// every dtype the API accepts (checkDataType() in api.cc); switched on as an int: cudecomp_amd.h's values are not
+// enumerators of cudecompDataType_t
 inline int elementSize(cudecompDataType_t dtype) {
-  switch (dtype) {
-    case CUDECOMP_FLOAT: return 4;
+  switch (static_cast<int>(dtype)) {
+    case CUDECOMP_AMD_HALF:
+    case CUDECOMP_AMD_BFLOAT16: return 2;
+    case CUDECOMP_FLOAT:
+    case CUDECOMP_AMD_HALF_COMPLEX: return 4;
     case CUDECOMP_DOUBLE:
     case CUDECOMP_FLOAT_COMPLEX: return 8;
-    default: return 16;
+    case CUDECOMP_DOUBLE_COMPLEX: return 16;
   }
+  CD_INVALID_USAGE("unknown data type");
 }
 
 inline bool transposeBackendIsMpi(cudecompTransposeCommBackend_t b) {

@@ -8,6 +8,12 @@
 // element size), kernels_window.hip, kernels_lines.hip, kernels_rowlines.hip and kernels_rotate.hip (the in-place rotation:
 // launched by the executor, transpose.cc); kernels_batch.h says why they are separate code objects.
 //
+// 2-byte elements (fp16, bf16) take the row copy (plain kernel), the LDS-tiled transposition (128 x 128 tiles with 16-byte
+// lanes, 64 x 64 element-wise) and the generic kernel only: never the window, lines, row-lines, shifted-rows, dense-rows or
+// rotation kernels, whose 2-byte forms are not written (the row kernels copy row ends in 4-byte pieces).  Their accesses of 4
+// bytes or more are issued only at dword-aligned addresses: the vector width follows from the base addresses and the byte
+// strides, not only from the extents.
+//
 // Pure data movement: no MFMA; the bound is HBM (8 TB/s spec, ~6.3 TB/s achievable copy rate).
 #include <algorithm>
 #include <cstdio>
@@ -46,7 +52,9 @@ constexpr long long kDenseMaxGapBytes = 512;  // widest gap between rows the den
 
 // tile (elements, i x j) of a transpose variant
 void tileOf(int es, int variant, bool window, int* ti, int* tj) {
-  if (es == 16) {
+  if (es == 2) {
+    *ti = *tj = variant == 8 ? 128 : 64;
+  } else if (es == 16) {
     *ti = 32;
     *tj = variant == 301 ? 64 : 32;
   } else if (window) {
@@ -81,6 +89,11 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
     // addresses only need the element's natural alignment (see GlobalBytes).
     int vb = 16;
     while (vb > es && (m.extent[0] * es) % vb != 0) vb >>= 1;
+    // 2-byte elements: accesses of 4 bytes or more only at dword-aligned addresses -- a row that starts at 2 mod 4 (odd halo,
+    // extent or offset) is copied in 2-byte pieces
+    if (es == 2 && ((reinterpret_cast<uintptr_t>(c.dm.src) | reinterpret_cast<uintptr_t>(c.dm.dst) |
+                     (uintptr_t)((m.ss[1] | m.ss[2] | m.ds[1] | m.ds[2]) * es)) & 3) != 0)
+      vb = 2;
     c.cls = MOVE_ROWS_VEC;
     c.variant = vb;
     c.dm.e[0] = m.extent[0] * es / vb;
@@ -91,10 +104,11 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
       c.dm.ds[i] = m.ds[i] * es;
     }
     // rows that land off the 64-byte grid (and are long enough for it to matter): lanes laid out from the unit boundary
-    // below each row's start (rows_shifted_kernel), one unit of slack vectors per row
+    // below each row's start (rows_shifted_kernel), one unit of slack vectors per row.  Not for 2-byte elements: the shifted
+    // and dense kernels copy the row ends in 4-byte pieces (so no rows_dense_kernel either)
     const uintptr_t dst_bits = reinterpret_cast<uintptr_t>(c.dm.dst) | (uintptr_t)c.dm.ds[1] | (uintptr_t)c.dm.ds[2];
     const int shift_mode = tuning.window_mode;  // -1 auto, 0 never, 1 whenever the destination is misaligned
-    if ((dst_bits & 63) != 0 && m.extent[0] * es >= 256 && shift_mode != 0 && (shift_mode == 1 || c.elements * es >= (1ll << 20))) {
+    if (es != 2 && (dst_bits & 63) != 0 && m.extent[0] * es >= 256 && shift_mode != 0 && (shift_mode == 1 || c.elements * es >= (1ll << 20))) {
       c.window = true;
       c.p1 = (int)(m.extent[0] * es);  // row length in bytes (rows longer than 2 GiB keep the plain kernel)
       if (m.extent[0] * es > 0x7fffffffLL) c.window = false;
@@ -156,9 +170,13 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
     c.dm.ds[0] = m.ds[0];
     c.dm.ds[1] = 1;
     c.dm.ds[2] = m.ds[k];
-    // 16 bytes per lane whenever both tile edges hold whole vectors (no alignment requirement, see GlobalBytes)
+    // 16 bytes per lane whenever both tile edges hold whole vectors (dword alignment suffices, see GlobalBytes).  2-byte
+    // elements: only when every lane address is dword-aligned too -- bases and the byte strides of both sides
     int vw = 16 / es;
     if (c.dm.e[0] % vw != 0 || c.dm.e[1] % vw != 0) vw = 1;
+    if (es == 2 && ((reinterpret_cast<uintptr_t>(c.dm.src) | reinterpret_cast<uintptr_t>(c.dm.dst) |
+                     (uintptr_t)((c.dm.ss[1] | c.dm.ss[2] | c.dm.ds[0] | c.dm.ds[2]) * es)) & 3) != 0)
+      vw = 1;
     c.variant = vw;
     c.p1 = 1;  // XCD-contiguous tile walk
     // Tile walk order inside an XCD's run: j first makes consecutive tiles extend the same DESTINATION rows
@@ -167,7 +185,8 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
     // the strided-read side at 4-byte elements; 4-byte moves whose destination rows are the far-strided side
     // lose 1-3 % and keep i first), i first wins by 5-10 % for misaligned moves, where L2 merges the
     // partially read lines of neighbouring tiles.
-    bool j_first = es != 4 || c.dm.ss[1] > c.dm.ds[0];
+    // (2-byte elements: the rule of 4-byte ones, whose 16-byte-lane tile has the same shape in bytes)
+    bool j_first = (es != 4 && es != 2) || c.dm.ss[1] > c.dm.ds[0];
     // Rows that do not start on cache-line boundaries (halo-shifted or odd-extent pencils) leave partially covered
     // lines at both ends of every tile row.
     //  * Misaligned SOURCE rows only: the partially used lines are shared with the neighbouring tile; cached loads let
@@ -180,7 +199,9 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
     const uintptr_t align_req = 128;
     const bool src_mis = src_bits % align_req != 0, dst_mis = dst_bits % 64 != 0;
     const int window_mode = tuning.window_mode;  // -1 auto, 0 never, 1 whenever the destination is misaligned
-    c.window = dst_mis && window_mode != 0 && (window_mode == 1 || c.elements * es >= (1ll << 20));
+    // 2-byte elements never take the window kernel, nor therefore transpose_lines_kernel / transpose_rowlines_kernel: their
+    // 2-byte forms are not written; the plain kernel writes misaligned destinations correctly
+    c.window = es != 2 && dst_mis && window_mode != 0 && (window_mode == 1 || c.elements * es >= (1ll << 20));
     if (c.window) {
       if (c.stream == 2) c.stream = 4;  // cached loads (the overlap rows hit in L2), streaming whole-unit stores
       j_first = true;
@@ -344,6 +365,7 @@ void launchBatch(const Classified& c, int es, const Batch& b, unsigned int block
       if (c.rowlines) launchRowLinesBatch(es, variant, stream_access, b, blocks, stream);
       else if (c.lines) launchLinesBatch(es, variant, stream_access, b, blocks, stream);
       else if (c.window) launchWindowBatch(es, variant, stream_access, b, blocks, stream);
+      else if (es == 2) launchTransposeBatch2(variant, stream_access, b, blocks, stream);
       else if (es == 4) launchTransposeBatch4(variant, stream_access, b, blocks, stream);
       else if (es == 8) launchTransposeBatch8(variant, stream_access, b, blocks, stream);
       else launchTransposeBatch16(variant, stream_access, b, blocks, stream);
@@ -378,7 +400,7 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
                  const KernelTuning* tuning, KernelStats* stats, void* const* dst_base_override) {
   const bool remote = dst_base_override != nullptr;
   const KernelTuning& t = tuning ? *tuning : kDefaultTuning;
-  if (es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
+  if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
   std::vector<Classified> cs;
   cs.reserve(n);
   for (int i = 0; i < n; ++i) {

@@ -4,8 +4,8 @@
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
 // code object beyond roughly 0.6-0.7 MB puts the whole process into a regime where every small synchronous operation costs
 // 14 ms (bisected in round 5, profiles/r05_code_size.md: the same 0.74 MB of device code split over two code objects is
-// harmless, in one code object it is not).  The kernels therefore live in five small code objects -- row copies + generic,
-// the LDS-tiled transposes per element size (kernels_transpose.hip compiled three times), the window transposes -- and
+// harmless, in one code object it is not).  The kernels therefore live in several small code objects -- row copies + generic,
+// the LDS-tiled transposes per element size (kernels_transpose.hip compiled four times), the window transposes, ... -- and
 // tests/test_abi.py guards the size of each.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -50,8 +50,9 @@ void launchRowsBatch(int mode, int vector_bytes, int stream_access, const kern::
 int rowsDenseBytesPerBlock();  // bytes of a plane's span one workgroup of the dense row copy covers
 void launchGenericBatch(int es, bool remote, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // transposes: `variant` = elements per 16-byte lane group (1 = element-wise lanes), plus 300 for the longer tiles: 64 x 128
-// for 4-byte elements with 16-byte lanes; 64 x 128 (8-byte) and 32 x 64 (16-byte) for far-strided sources.  4- and 8-byte
-// elements use the XOR-swizzled LDS tile, 16-byte elements the padded one.
+// for 4-byte elements with 16-byte lanes; 64 x 128 (8-byte) and 32 x 64 (16-byte) for far-strided sources.  2-, 4- and
+// 8-byte elements use the XOR-swizzled LDS tile, 16-byte elements the padded one.
+void launchTransposeBatch2(int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 void launchTransposeBatch4(int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 void launchTransposeBatch8(int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 void launchTransposeBatch16(int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);

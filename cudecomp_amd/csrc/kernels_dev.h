@@ -13,6 +13,7 @@ namespace kern {
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 template <int N> struct BytesOf;
+template <> struct BytesOf<2> { using type = unsigned short; };
 template <> struct BytesOf<4> { using type = unsigned int; };
 template <> struct BytesOf<8> { using type = u32x2; };
 template <> struct BytesOf<16> { using type = u32x4; };
@@ -23,7 +24,10 @@ template <int N> using Bytes = typename BytesOf<N>::type;
 // boundary, say) still moves 16 bytes per lane; a wavefront then touches one extra cache line per KiB.
 typedef u32x2 __attribute__((aligned(4))) u32x2_g;
 typedef u32x4 __attribute__((aligned(4))) u32x4_g;
+// (The library issues global accesses of 4 bytes or more only at dword-aligned addresses; 2-byte elements whose rows or
+// bases sit at 2 mod 4 take 2-byte accesses, kernels.cc classify().)
 template <int N> struct GlobalBytesOf;
+template <> struct GlobalBytesOf<2> { using type = unsigned short; };
 template <> struct GlobalBytesOf<4> { using type = unsigned int; };
 template <> struct GlobalBytesOf<8> { using type = u32x2_g; };
 template <> struct GlobalBytesOf<16> { using type = u32x4_g; };
@@ -50,6 +54,28 @@ template <> struct Lane<8, 2> {
   }
 };
 
+// 2-byte elements, 8 per 16-byte lane: element v is the low (v even) or high (v odd) half of dword v / 2.  get / set are
+// the general form; the 8 x 8 transposition of transposeTile uses column(), which builds each output dword with one byte
+// permute (v_perm_b32) of the two input dwords that hold its halves instead of shift-and-mask chains.
+template <> struct Lane<2, 8> {
+  static __device__ __forceinline__ unsigned short get(const u32x4& x, int v) {
+    return (unsigned short)(x[v >> 1] >> ((v & 1) * 16));
+  }
+  static __device__ __forceinline__ void set(u32x4& x, int v, unsigned short e) {
+    const int s = (v & 1) * 16;
+    x[v >> 1] = (x[v >> 1] & ~(0xffffu << s)) | ((unsigned int)e << s);
+  }
+  // element a of every row in[0..7]: out dword d = {in[2d] element a (low half), in[2d + 1] element a (high half)}
+  static __device__ __forceinline__ u32x4 column(const u32x4 (&in)[8], int a) {
+    // __builtin_amdgcn_perm(hi, lo, sel): selector byte values 0-3 pick bytes of `lo`, 4-7 bytes of `hi`
+    const unsigned int sel = (a & 1) ? 0x07060302u : 0x05040100u;
+    u32x4 out;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) out[d] = __builtin_amdgcn_perm(in[2 * d + 1][a >> 1], in[2 * d][a >> 1], sel);
+    return out;
+  }
+};
+
 // Streaming (non-temporal) access for moves far larger than the caches: measured +3..15 % on the 1024^3
 // permutations (profiles/r01_tuning.md); small moves keep the default policy so a following kernel can
 // still find the data in L2 / Infinity Cache.
@@ -68,6 +94,11 @@ __device__ __forceinline__ Bytes<N> loadVec(const void* p) {
 // makes the compiler wait for every single store, which serialises a lane's 4-8 stores.)
 enum StorePolicy { ST_CACHED = 0, ST_STREAM = 1, ST_REMOTE = 2 };
 template <int N> __device__ __forceinline__ void storeRemote(void* p, const Bytes<N>& v);
+// 2 bytes: only what wider stores cannot cover (2-byte elements at 2 mod 4, odd rows); a system-scope short store costs
+// about 12x the time per byte of a dwordx4 one.  (A 32-bit VGPR holds the value; the store writes its low half.)
+template <> __device__ __forceinline__ void storeRemote<2>(void* p, const Bytes<2>& v) {
+  asm volatile("global_store_short %0, %1, off sc0 sc1" ::"v"(p), "v"((unsigned int)v) : "memory");
+}
 template <> __device__ __forceinline__ void storeRemote<4>(void* p, const Bytes<4>& v) {
   asm volatile("global_store_dword %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
 }

@@ -3,13 +3,13 @@
 //
 // These replace the batched strided 3-D copy kernel of NVIDIA/cuDecomp (reference include/internal/cudecomp_kernels.cuh:125-180:
 // one element per thread per iteration, two 64-bit div/mod pairs per element, no vector access):
-//   rows_kernel<VB>       fastest dim contiguous on both sides.  Each lane moves VB = 16 (8, 4) bytes, a 256-thread workgroup
+//   rows_kernel<VB>       fastest dim contiguous on both sides.  Each lane moves VB = 16 (8, 4, 2) bytes, a 256-thread workgroup
 //                         keeps 4 vectors per lane (16 KiB) in flight, lanes run along the row so that every wavefront touches
 //                         1 KiB contiguous segments.  No per-element index math: one (row, plane) decode per WORKGROUP.
 //   rows_shifted_kernel   the same for destination rows off the 64-byte grid.
 //   rows_dense_kernel     the same when, in addition, the cells between consecutive destination rows belong to the move
 //                         (whole interior rows of a halo-carrying pencil): whole cache lines across the row ends.
-//   generic_kernel<ES>    degenerate shapes (no unit stride on one side, 1-element rows).
+//   generic_kernel<ES>    degenerate shapes (no unit stride on one side, 1-element rows); ES = 2, 4, 8, 16.
 // Pure data movement: no MFMA; the bound is HBM (8 TB/s spec, ~6.3 TB/s achievable copy rate).
 #include "kernels_dev.h"
 
@@ -281,30 +281,35 @@ void launchRowsBatch(int mode, int vb, int stream_access, const Batch& b, unsign
     else if (rs == 1) K<VB, 1><<<grid, block, 0, stream>>>(b);            \
     else K<VB, 0><<<grid, block, 0, stream>>>(b);                         \
   } while (0)
-  if (shifted) {
-    if (vb == 16) CD_ROWS(rows_shifted_kernel, 16);
-    else if (vb == 8) CD_ROWS(rows_shifted_kernel, 8);
-    else CD_ROWS(rows_shifted_kernel, 4);
-  } else {
-    if (vb == 16) CD_ROWS(rows_kernel, 16);
-    else if (vb == 8) CD_ROWS(rows_kernel, 8);
-    else CD_ROWS(rows_kernel, 4);
-  }
+  // (2-byte rows: plain kernel only -- the shifted one copies the row ends in 4-byte pieces, kernels.cc classify())
+  if (shifted && vb == 16) CD_ROWS(rows_shifted_kernel, 16);
+  else if (shifted && vb == 8) CD_ROWS(rows_shifted_kernel, 8);
+  else if (shifted && vb == 4) CD_ROWS(rows_shifted_kernel, 4);
+  else if (!shifted && vb == 16) CD_ROWS(rows_kernel, 16);
+  else if (!shifted && vb == 8) CD_ROWS(rows_kernel, 8);
+  else if (!shifted && vb == 4) CD_ROWS(rows_kernel, 4);
+  else if (!shifted && vb == 2) CD_ROWS(rows_kernel, 2);
+  else CD_INTERNAL_ERROR("no row copy kernel for this vector width");
 #undef CD_ROWS
   CD_CHECK_HIP(hipGetLastError());
 }
 
 void launchGenericBatch(int es, bool remote, const Batch& b, unsigned int blocks, hipStream_t stream) {
   const dim3 grid(blocks), block(kThreads);
-  if (es == 4) {
+  if (es == 2) {
+    if (remote) generic_kernel<2, true><<<grid, block, 0, stream>>>(b);
+    else generic_kernel<2, false><<<grid, block, 0, stream>>>(b);
+  } else if (es == 4) {
     if (remote) generic_kernel<4, true><<<grid, block, 0, stream>>>(b);
     else generic_kernel<4, false><<<grid, block, 0, stream>>>(b);
   } else if (es == 8) {
     if (remote) generic_kernel<8, true><<<grid, block, 0, stream>>>(b);
     else generic_kernel<8, false><<<grid, block, 0, stream>>>(b);
-  } else {
+  } else if (es == 16) {
     if (remote) generic_kernel<16, true><<<grid, block, 0, stream>>>(b);
     else generic_kernel<16, false><<<grid, block, 0, stream>>>(b);
+  } else {
+    CD_INTERNAL_ERROR("no element-wise kernel for this element size");
   }
   CD_CHECK_HIP(hipGetLastError());
 }

@@ -68,8 +68,12 @@ __device__ __forceinline__ void transposeTile(Bytes<ES>* tile, const Bytes<ES>* 
 #pragma unroll
       for (int a = 0; a < VW; ++a) {
         V out;
+        if constexpr (ES == 2 && VW == 8) {
+          out = Lane<ES, VW>::column(in, a);  // 8 x 8 halves: byte permutes
+        } else {
 #pragma unroll
-        for (int v = 0; v < VW; ++v) Lane<ES, VW>::set(out, v, Lane<ES, VW>::get(in[v], a));
+          for (int v = 0; v < VW; ++v) Lane<ES, VW>::set(out, v, Lane<ES, VW>::get(in[v], a));
+        }
         const int ii = ig * VW + a;
         if (!GUARD || (i0 + ii < ei && j0 + lj < ej))
           storeVec<storePolicyOf<STREAM>(), ES * VW>(dst + (i0 + ii) * di + j0 + lj, out);

@@ -27,11 +27,12 @@ namespace {
 const char* kTransposeNames[4] = {"TransposeXY", "TransposeYZ", "TransposeZY", "TransposeYX"};
 const char* kHaloNames[3] = {"HaloX", "HaloY", "HaloZ"};
 
-// S, D, C, Z in this order (CUDECOMP_FLOAT = -1 ... CUDECOMP_DOUBLE_COMPLEX = -4)
-int dtypeRank(int dtype) { return -dtype - 1; }
+// S, D, C, Z in this order (CUDECOMP_FLOAT = -1 ... CUDECOMP_DOUBLE_COMPLEX = -4), then the 2-byte types of
+// cudecomp_amd.h: H (CUDECOMP_AMD_HALF = 1), BF (CUDECOMP_AMD_BFLOAT16 = 2), HC (CUDECOMP_AMD_HALF_COMPLEX = 3)
+int dtypeRank(int dtype) { return dtype < 0 ? -dtype - 1 : 3 + dtype; }
 const char* dtypeLetter(int rank) {
-  static const char* names[4] = {"S", "D", "C", "Z"};
-  return (rank >= 0 && rank < 4) ? names[rank] : "unknown";
+  static const char* names[7] = {"S", "D", "C", "Z", "H", "BF", "HC"};
+  return (rank >= 0 && rank < 7) ? names[rank] : "unknown";
 }
 
 hipEvent_t* beginSample(cudecompHandle_t h, cudecompGridDesc::PerfCollection& c, int64_t wire_bytes, hipStream_t stream) {

@@ -1021,7 +1021,8 @@ namespace {
 void peerCopy(cudecompHandle_t h, char* dst, const char* src, size_t bytes, hipStream_t stream, int engine = -1) {
   if (bytes == 0) return;
   if (engine < 0) engine = h->peer_copy_engine;
-  if (engine == 1 && bytes % 4 == 0) {
+  // (the kernel path moves 4 bytes or more per access: dword-aligned ends only, which 2-byte elements do not guarantee)
+  if (engine == 1 && bytes % 4 == 0 && ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 3) == 0) {
     const int es = (bytes % 16 == 0) ? 16 : (bytes % 8 == 0 ? 8 : 4);
     Move3D m;
     m.src_buf = BUF_IN;
