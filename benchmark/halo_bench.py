@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
-"""Halo-update timing on one rank: the per-rank X pencil of BASELINE config 5 (2048 x 2048 x 1024 fp64 on a
-2x4 grid -> 2048 x 1024 x 256 per rank, halo width 2) treated as a periodic single-rank grid, so every
-dim exercises the face-copy kernels (periodic self copy; reference include/internal/halo.h:165-193).
-Prints per-dim time and achieved GB/s against the algorithmic bytes 2 * faces * face_bytes."""
+"""Halo timing on one rank: the per-rank X pencil of BASELINE config 5 (2048 x 2048 x 1024 fp64 on a
+2x4 grid -> 2048 x 1024 x 256 per rank) treated as a periodic single-rank grid, so every dim exercises the
+face kernels: cudecompUpdateHalosX (periodic self copy; reference include/internal/halo.h:165-193) and, beside
+it on the same pencil, cudecompAmdAccumulateHalosX (cudecomp_amd.h: the two face additions).
+Per dim: `--reps` repetitions of `--calls` back-to-back calls each, ms per call of every repetition, their
+min / median / max, and GB/s of the median against the algorithmic bytes (update: 2 faces read + written,
+4 * face bytes; accumulation: 2 faces read, 2 destinations read and written, 6 * face bytes)."""
+import argparse
 import json
 import os
 import sys
@@ -11,40 +15,76 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def _time(fn, reps, calls):
+    import torch
+    for _ in range(3):
+        fn()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(calls):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / calls)
+    return out
+
+
+def _record(ms, alg_bytes):
+    s = sorted(ms)
+    med = s[len(s) // 2]
+    return {"ms": [round(x, 4) for x in ms], "min_ms": round(s[0], 4), "median_ms": round(med, 4), "max_ms": round(s[-1], 4),
+            "GBps": round(alg_bytes / med / 1e6, 1)}
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--halo", type=int, default=1, help="halo width along every dim")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--update-only", action="store_true", help="time cudecompUpdateHalosX only")
+    ap.add_argument("--json", metavar="FILE", default=None, help="also write the result line to FILE")
+    a = ap.parse_args()
     import torch
 
     import cudecomp_amd as cd
     torch.cuda.set_device(0)
-    gdims, halo = (2048, 1024, 256), (2, 2, 2)
+    gdims, halo = (2048, 1024, 256), (a.halo,) * 3
     h = cd.cudecompInit()
     res = {}
-    for name, ac in (("default", (0, 0, 0)),):
-        gd = cd.cudecompGridDescCreate(h, cd.make_config(gdims, (1, 1), axis_contiguous=ac))
-        p = cd.cudecompGetPencilInfo(h, gd, 0, halo)
-        data = torch.zeros(p.size, dtype=torch.float64, device="cuda")
-        ws = max(cd.cudecompGetHaloWorkspaceSize(h, gd, 0, halo), 1)
-        work = cd.cudecompMalloc(h, gd, ws * 8)
-        st = torch.cuda.current_stream().cuda_stream
-        shape = list(p.shape)
-        for dim in range(3):
-            face = halo[dim] * (shape[(dim + 1) % 3]) * (shape[(dim + 2) % 3])
-            for _ in range(3):
-                cd.cudecompUpdateHalos(0, h, gd, data.data_ptr(), work, cd.DOUBLE, halo, (1, 1, 1), dim, stream=st)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            reps = 20
-            for _ in range(reps):
-                cd.cudecompUpdateHalos(0, h, gd, data.data_ptr(), work, cd.DOUBLE, halo, (1, 1, 1), dim, stream=st)
-            e1.record()
-            torch.cuda.synchronize()
-            ms = e0.elapsed_time(e1) / reps
-            alg = 2 * 2 * face * 8  # two faces, read + write
-            res["dim%d" % dim] = {"ms": round(ms, 4), "face_MiB": round(face * 8 / 2**20, 2),
-                                  "GBps": round(alg / ms / 1e6, 1)}
-        cd.cudecompFree(h, gd, work)
-        cd.cudecompGridDescDestroy(h, gd)
-    print(json.dumps({"workload": "X pencil 2048x1024x256 fp64 + halo 2, periodic self copy per dim", "result": res}))
+    gd = cd.cudecompGridDescCreate(h, cd.make_config(gdims, (1, 1)))
+    p = cd.cudecompGetPencilInfo(h, gd, 0, halo)
+    data = torch.zeros(p.size, dtype=torch.float64, device="cuda")
+    ws = max(cd.cudecompGetHaloWorkspaceSize(h, gd, 0, halo), 1)
+    work = cd.cudecompMalloc(h, gd, ws * 8)
+    st = torch.cuda.current_stream().cuda_stream
+    shape = list(p.shape)
+    faces = [halo[dim] * (shape[(dim + 1) % 3]) * (shape[(dim + 2) % 3]) for dim in range(3)]
+    # two passes: every update first, the accumulations afterwards -- the update figures are then taken exactly as with
+    # --update-only (nothing else touches the pencil between their repetitions)
+    for dim in range(3):
+        ms = _time(lambda: cd.cudecompUpdateHalos(0, h, gd, data.data_ptr(), work, cd.DOUBLE, halo, (1, 1, 1), dim, stream=st),
+                   a.reps, a.calls)
+        res["dim%d" % dim] = {"face_MiB": round(faces[dim] * 8 / 2**20, 2), "update": _record(ms, 4 * faces[dim] * 8)}
+    for dim in range(3):
+        if a.update_only:
+            break
+        rec = res["dim%d" % dim]
+        ms = _time(lambda: cd.cudecompAccumulateHalos(0, h, gd, data.data_ptr(), work, cd.DOUBLE, halo, (1, 1, 1), dim, stream=st),
+                   a.reps, a.calls)
+        rec["accumulate"] = _record(ms, 6 * faces[dim] * 8)
+        rec["accumulate_kernel"] = cd.cudecompExtLastKernelName()
+        rec["accumulate_over_update"] = round(rec["accumulate"]["median_ms"] / rec["update"]["median_ms"], 3)
+    cd.cudecompFree(h, gd, work)
+    cd.cudecompGridDescDestroy(h, gd)
+    line = json.dumps({"workload": "X pencil 2048x1024x256 fp64 + halo %d, periodic single rank, per dim: update (self copy) and "
+                                   "accumulation (self add); %d repetitions of %d calls" % (a.halo, a.reps, a.calls),
+                       "device": torch.cuda.get_device_name(0), "result": res})
+    print(line)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
     cd.cudecompFinalize(h)
 
 

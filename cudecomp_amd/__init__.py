@@ -144,7 +144,9 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtPlanTranspose", "cudecompExtPlanHalo", "cudecompExtPencilInfo", "cudecompExtShiftedRank",
                "cudecompExtWorkspaceSizes", "cudecompExtGetLinkInfo", "cudecompExtLastKernelName",
                "cudecompExtRunLocalPhases", "cudecompExtEstimateCycleMs", "cudecompExtTrimWorkspacePool", "cudecompExtPlanRelay", "cudecompExtQueueCensus",
-               "cudecompExtDescribeMove", "cudecompExtRotateWalk"]
+               "cudecompExtDescribeMove", "cudecompExtRotateWalk", "cudecompExtPlanHaloAccumulate", "cudecompExtAccumulate3D"]
+# include/cudecomp_amd.h: extensions of the API a solver may use
+AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
 
 
 class ExtTransposeTimings(C.Structure):
@@ -201,7 +203,7 @@ def lib():
         for name in ("cudecompTransposeXToY", "cudecompTransposeYToZ", "cudecompTransposeZToY",
                      "cudecompTransposeYToX"):
             getattr(L, name).argtypes = [vp, vp, vp, vp, vp, i32, pi32, pi32, pi32, pi32, vp]
-        for name in ("cudecompUpdateHalosX", "cudecompUpdateHalosY", "cudecompUpdateHalosZ"):
+        for name in ("cudecompUpdateHalosX", "cudecompUpdateHalosY", "cudecompUpdateHalosZ") + tuple(AMD_SYMBOLS):
             getattr(L, name).argtypes = [vp, vp, vp, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         L.cudecompExtGetTransposePlan.argtypes = [vp, vp, i32, pi32, pi32, pi32, pi32, C.c_bool, i32,
                                                   C.POINTER(ExtTransposePlan)]
@@ -223,6 +225,8 @@ def lib():
                                            C.POINTER(ExtRelayPlan)]
         L.cudecompExtPlanHalo.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32,
                                           C.POINTER(ExtHaloPlan)]
+        L.cudecompExtPlanHaloAccumulate.argtypes = L.cudecompExtPlanHalo.argtypes
+        L.cudecompExtAccumulate3D.argtypes = [vp, vp, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, pi32, vp]
         L.cudecompExtGetLinkInfo.argtypes = [vp, C.POINTER(ExtLinkInfo)]
         L.cudecompExtEstimateCycleMs.argtypes = [vp, C.POINTER(ExtGridSpec), i32, i32, i32, i32, C.POINTER(C.c_double)]
         L.cudecompExtRunLocalPhases.argtypes = [C.POINTER(ExtGridSpec), i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]
@@ -360,6 +364,14 @@ def cudecompUpdateHalos(axis, handle, gd, inp, work, dtype, halo_extents, halo_p
            "cudecompUpdateHalos" + "XYZ"[axis])
 
 
+def cudecompAccumulateHalos(axis, handle, gd, inp, work, dtype, halo_extents, halo_periods, dim, padding=None,
+                            stream=None):
+    """cudecompAmdAccumulateHalos{X,Y,Z} (cudecomp_amd.h): ghost cells summed into their owners along `dim`."""
+    fn = getattr(lib(), "cudecompAmdAccumulateHalos" + "XYZ"[axis])
+    _check(fn(handle, gd, inp, work, dtype, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding), stream),
+           "cudecompAmdAccumulateHalos" + "XYZ"[axis])
+
+
 def cudecompExtGetTransposePlan(handle, gd, op, in_halo=None, out_halo=None, in_pad=None, out_pad=None, inplace=False,
                                 backend_override=0):
     p = ExtTransposePlan()
@@ -422,6 +434,14 @@ def cudecompExtPlanHalo(grid, rank, axis, halo_extents, halo_periods, dim, paddi
     p = ExtHaloPlan()
     _check(lib().cudecompExtPlanHalo(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding),
                                      int(force_packed), C.byref(p)), "cudecompExtPlanHalo")
+    return p
+
+
+def cudecompExtPlanHaloAccumulate(grid, rank, axis, halo_extents, halo_periods, dim, padding=None, force_packed=False):
+    """Stateless planner of cudecompAmdAccumulateHalos*; ExtHaloPlan.reserved marks the add-moves (cudecomp_ext.h)."""
+    p = ExtHaloPlan()
+    _check(lib().cudecompExtPlanHaloAccumulate(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim,
+                                               _i3(padding), int(force_packed), C.byref(p)), "cudecompExtPlanHaloAccumulate")
     return p
 
 
@@ -504,6 +524,15 @@ def cudecompExtMove3D(src, dst, es, extent, ss, ds, force_generic=False, stream=
     a = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
     _check(lib().cudecompExtMove3D(src, dst, es, a(extent), a(ss), a(ds), int(force_generic), C.byref(cls), stream),
            "cudecompExtMove3D")
+    return cls.value
+
+
+def cudecompExtAccumulate3D(src, dst, dtype, extent, ss, ds, force_generic=0, stream=None):
+    """One add-move (dst += src) through the kernel layer; returns the kernel class (0 rows, 2 generic)."""
+    cls = C.c_int32(-1)
+    a = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
+    _check(lib().cudecompExtAccumulate3D(src, dst, dtype, a(extent), a(ss), a(ds), int(force_generic), C.byref(cls), stream),
+           "cudecompExtAccumulate3D")
     return cls.value
 
 

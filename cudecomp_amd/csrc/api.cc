@@ -623,6 +623,7 @@ cudecompResult_t cudecompGridDescCreateVersioned(cudecompHandle_t handle, cudeco
     gd->transpose_plans.clear();
     gd->relay_plans.clear();
     gd->halo_plans.clear();
+    gd->halo_accumulate_plans.clear();
     perfReset(gd);  // autotuning trials are not part of the user's performance report
 
     *grid_desc_out = gd;
@@ -831,7 +832,7 @@ CD_DEFINE_TRANSPOSE(cudecompTransposeYToZ, OP_Y_TO_Z)
 CD_DEFINE_TRANSPOSE(cudecompTransposeZToY, OP_Z_TO_Y)
 CD_DEFINE_TRANSPOSE(cudecompTransposeYToX, OP_Y_TO_X)
 
-static cudecompResult_t haloEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
+static cudecompResult_t haloEntry(bool accumulate, int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
                                   void* work, cudecompDataType_t dtype, const int32_t halo_extents[],
                                   const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {
   try {
@@ -843,20 +844,25 @@ static cudecompResult_t haloEntry(int axis, cudecompHandle_t handle, cudecompGri
     if (!input) CD_INVALID_USAGE("input argument cannot be null");
     if (!work) CD_INVALID_USAGE("work argument cannot be null");
     if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
-    runHalo(handle, grid_desc, axis, input, work, dtype, halo_extents, halo_periods, dim, padding, stream);
+    if (accumulate) runHaloAccumulate(handle, grid_desc, axis, input, work, dtype, halo_extents, halo_periods, dim, padding, stream);
+    else runHalo(handle, grid_desc, axis, input, work, dtype, halo_extents, halo_periods, dim, padding, stream);
   }
   CD_API_CATCH()
   return CUDECOMP_RESULT_SUCCESS;
 }
 
-#define CD_DEFINE_HALO(NAME, AXIS)                                                                                \
+#define CD_DEFINE_HALO(NAME, ACCUMULATE, AXIS)                                                                              \
   cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, void* work,           \
                         cudecompDataType_t dtype, const int32_t halo_extents[], const bool halo_periods[],        \
                         int32_t dim, const int32_t padding[], hipStream_t stream) {                               \
-    return haloEntry(AXIS, handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, padding, stream); \
+    return haloEntry(ACCUMULATE, AXIS, handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, padding, stream); \
   }
-CD_DEFINE_HALO(cudecompUpdateHalosX, 0)
-CD_DEFINE_HALO(cudecompUpdateHalosY, 1)
-CD_DEFINE_HALO(cudecompUpdateHalosZ, 2)
+CD_DEFINE_HALO(cudecompUpdateHalosX, false, 0)
+CD_DEFINE_HALO(cudecompUpdateHalosY, false, 1)
+CD_DEFINE_HALO(cudecompUpdateHalosZ, false, 2)
+// cudecomp_amd.h: the transpose of the updates (ghost cells summed into their owners)
+CD_DEFINE_HALO(cudecompAmdAccumulateHalosX, true, 0)
+CD_DEFINE_HALO(cudecompAmdAccumulateHalosY, true, 1)
+CD_DEFINE_HALO(cudecompAmdAccumulateHalosZ, true, 2)
 
 }  // extern "C"

@@ -95,6 +95,13 @@ void exportHaloPlan(const HaloPlan& p, cudecompExtHaloPlan_t* out) {
     out->n_post = (int32_t)p.post.size();
     for (size_t i = 0; i < p.pre.size(); ++i) exportMove(p.pre[i], &out->pre[i]);
     for (size_t i = 0; i < p.post.size(); ++i) exportMove(p.post[i], &out->post[i]);
+    if (p.accumulate) {
+      out->reserved = 1 | (p.ordered ? 2 : 0);
+      for (size_t i = 0; i < p.pre.size(); ++i)
+        if (p.pre[i].add) out->reserved |= 16 << i;
+      for (size_t i = 0; i < p.post.size(); ++i)
+        if (p.post[i].add) out->reserved |= 64 << i;
+    }
 }
 
 GridShape shapeFromSpec(const cudecompExtGridSpec_t* spec) {
@@ -291,6 +298,27 @@ cudecompResult_t cudecompExtPlanHalo(const cudecompExtGridSpec_t* grid, int32_t 
     const int32_t zero[3] = {0, 0, 0};
     const bool none[3] = {false, false, false};
     const HaloPlan p = buildHaloPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, force_packed != 0);
+    exportHaloPlan(p, out);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtPlanHaloAccumulate(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
+                                               const int32_t halo[], const bool periods[], int32_t dim, const int32_t pad[],
+                                               int32_t force_packed, cudecompExtHaloPlan_t* out) {
+  try {
+    const GridShape g = shapeFromSpec(grid);
+    if (!out || !halo) CD_INVALID_USAGE("null argument");
+    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
+    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
+    const int32_t zero[3] = {0, 0, 0};
+    const bool none[3] = {false, false, false};
+    const HaloPlan p =
+        buildHaloAccumulatePlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, force_packed != 0);
     exportHaloPlan(p, out);
   } catch (const Error& e) {
     return fail(e);
@@ -592,6 +620,40 @@ cudecompResult_t cudecompExtMove3D(const void* src, void* dst, int32_t es, const
     if (force_generic & 128) t.walk_order = 1;  // transposes: j first (no runs)
     KernelStats st;
     launchMoves(&m, 1, bufs, es, stream, &t, &st);
+    if (kernel_class) {
+      *kernel_class = -1;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
+        if (st.launches[c]) *kernel_class = c;
+    }
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtAccumulate3D(const void* src, void* dst, cudecompDataType_t dtype, const int64_t extent[3],
+                                         const int64_t ss[3], const int64_t ds[3], int32_t force_generic,
+                                         int32_t* kernel_class, hipStream_t stream) {
+  try {
+    if (!src || !dst || !extent || !ss || !ds) CD_INVALID_USAGE("null argument");
+    const int es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
+    Move3D m;
+    m.src_buf = BUF_IN;
+    m.dst_buf = BUF_OUT;
+    m.add = true;
+    for (int i = 0; i < 3; ++i) {
+      m.extent[i] = extent[i];
+      m.ss[i] = ss[i];
+      m.ds[i] = ds[i];
+    }
+    void* bufs[3] = {const_cast<void*>(src), dst, nullptr};
+    KernelTuning t;
+    if (force_generic & 1) t.force_class = MOVE_GENERIC;
+    if (force_generic & 2) t.force_streaming = true;
+    KernelStats st;
+    launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, arithOf(dtype));
     if (kernel_class) {
       *kernel_class = -1;
       for (int c = 0; c < MOVE_CLASS_COUNT; ++c)

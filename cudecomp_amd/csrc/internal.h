@@ -134,6 +134,7 @@ struct cudecompGridDesc {
   std::map<TransposeKey, cudecomp::TransposePlan> transpose_plans;
   using HaloKey = std::tuple<int, int, std::array<int32_t, 6>, std::array<bool, 3>, bool>;
   std::map<HaloKey, cudecomp::HaloPlan> halo_plans;
+  std::map<HaloKey, cudecomp::HaloPlan> halo_accumulate_plans;  // cudecompAmdAccumulateHalos*: the same key, the other operation
 
   // CUDECOMP_ENABLE_CUDA_GRAPHS=1: the per-peer pack loop of the pipelined backends (one kernel + one event
   // record per destination) is captured once per (plan, buffers, element size) and replayed as one graph launch
@@ -199,6 +200,20 @@ inline int elementSize(cudecompDataType_t dtype) {
   CD_INVALID_USAGE("unknown data type");
 }
 
+// the real type the elements of `dtype` consist of: the arithmetic of add-moves (kernels.h)
+inline ArithType arithOf(cudecompDataType_t dtype) {
+  switch (static_cast<int>(dtype)) {
+    case CUDECOMP_AMD_HALF:
+    case CUDECOMP_AMD_HALF_COMPLEX: return ARITH_F16;
+    case CUDECOMP_AMD_BFLOAT16: return ARITH_BF16;
+    case CUDECOMP_FLOAT:
+    case CUDECOMP_FLOAT_COMPLEX: return ARITH_F32;
+    case CUDECOMP_DOUBLE:
+    case CUDECOMP_DOUBLE_COMPLEX: return ARITH_F64;
+  }
+  CD_INVALID_USAGE("unknown data type");
+}
+
 inline bool transposeBackendIsMpi(cudecompTransposeCommBackend_t b) {
   return b == CUDECOMP_TRANSPOSE_COMM_MPI_P2P || b == CUDECOMP_TRANSPOSE_COMM_MPI_P2P_PL ||
          b == CUDECOMP_TRANSPOSE_COMM_MPI_A2A;
@@ -240,6 +255,9 @@ void runTranspose(cudecompHandle_t handle, cudecompGridDesc_t gd, TransposeOp op
 void runHalo(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, void* work,
              cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
              hipStream_t stream);
+void runHaloAccumulate(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, void* work,
+                       cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
+                       hipStream_t stream);
 
 // perf.cc
 struct TransposeTimings {

@@ -43,6 +43,7 @@ struct Classified {
   bool dense = false;    // rows, with window: whole lines across the row ends (rows_dense_kernel)
   bool lines = false;    // transposes, with window: windows over the linear positions of adjacent rows (transpose_lines_kernel)
   bool rowlines = false; // transposes, with window: the tile's own rows are the adjacent ones (transpose_rowlines_kernel)
+  bool add = false;      // dst += src (rows_accumulate_kernel / generic_accumulate_kernel); stream: 0, 1 streaming source loads
   unsigned int t0, t1;
   unsigned long long blocks;
   i64 elements;
@@ -333,7 +334,80 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
   return c;
 }
 
+// Add-moves (Move3D::add): rows contiguous on both sides -> rows_accumulate_kernel with the lane width of the row copy (same
+// extent / address / stride rule), everything else -> generic_accumulate_kernel.  Only the cells of the move are touched.
+Classified classifyAdd(const Move3D& in, void* const bufs[3], int es, int real_bytes, const KernelTuning& tuning) {
+  Move3D m = in;
+  normalizeMove(m);
+  Classified c{};
+  c.add = true;
+  c.elements = m.elements();
+  // The source is read once: non-temporal loads for large moves.  The destination is read and rewritten by the same lane:
+  // default stores (non-temporal ones measured the same).
+  c.stream = ((c.elements * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming) ? 1 : 0;
+  c.dm.src = static_cast<const char*>(bufs[m.src_buf]) + m.src_off * es;
+  c.dm.dst = static_cast<char*>(bufs[m.dst_buf]) + m.dst_off * es;
+  if (tuning.force_class != MOVE_GENERIC && m.ss[0] <= 1 && m.ds[0] <= 1) {
+    int vb = 16;
+    while (vb > es && (m.extent[0] * es) % vb != 0) vb >>= 1;
+    // 2-byte elements: accesses of 4 bytes or more only at dword-aligned addresses (as the row copy)
+    if (es == 2 && ((reinterpret_cast<uintptr_t>(c.dm.src) | reinterpret_cast<uintptr_t>(c.dm.dst) |
+                     (uintptr_t)((m.ss[1] | m.ss[2] | m.ds[1] | m.ds[2]) * es)) & 3) != 0)
+      vb = 2;
+    if (vb < real_bytes) CD_INTERNAL_ERROR("add-move narrower than one real of its arithmetic type");
+    c.cls = MOVE_ROWS_VEC;
+    c.variant = vb;
+    c.dm.e[0] = m.extent[0] * es / vb;
+    c.dm.e[1] = m.extent[1];
+    c.dm.e[2] = m.extent[2];
+    for (int i = 1; i < 3; ++i) {
+      c.dm.ss[i] = m.ss[i] * es;
+      c.dm.ds[i] = m.ds[i] * es;
+    }
+    c.p0 = std::min(8, ilog2ceil(c.dm.e[0]));
+    const long long lpr = 1LL << c.p0, rows_per_block = (long long)(kThreads >> c.p0) * kRowsUnroll;
+    c.t0 = (unsigned int)((c.dm.e[0] + lpr - 1) / lpr);
+    c.t1 = (unsigned int)((c.dm.e[1] + rows_per_block - 1) / rows_per_block);
+    c.blocks = (unsigned long long)c.t0 * c.t1 * (unsigned long long)c.dm.e[2];
+    return c;
+  }
+  c.cls = MOVE_GENERIC;
+  c.variant = es;
+  c.stream = 0;
+  for (int i = 0; i < 3; ++i) {
+    c.dm.e[i] = m.extent[i];
+    c.dm.ss[i] = m.ss[i];
+    c.dm.ds[i] = m.ds[i];
+  }
+  c.p0 = 0;
+  for (int i = 0; i < 3; ++i)
+    if (m.ds[i] == 1 && m.extent[i] > 1) c.p0 = i;
+  const unsigned long long want = ((unsigned long long)c.elements + kThreads - 1) / kThreads;
+  c.blocks = std::min<unsigned long long>(std::max<unsigned long long>(want, 1), 8192);
+  return c;
+}
+
+const char* arithName(int arith) {
+  switch (arith) {
+    case ARITH_F16: return "_Float16";
+    case ARITH_BF16: return "__bf16";
+    case ARITH_F32: return "float";
+    default: return "double";
+  }
+}
+int arithBytes(int arith) { return arith == ARITH_F64 ? 8 : (arith == ARITH_F32 ? 4 : 2); }
+
 char g_last_kernel[96] = "";
+
+void launchAddBatch(const Classified& c, int es, int arith, const Batch& b, unsigned int blocks, hipStream_t stream) {
+  if (c.cls == MOVE_ROWS_VEC) {
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "rows_accumulate_kernel<%s,%d,%d>", arithName(arith), c.variant, c.stream);
+    launchAccumulateRowsBatch(arith, c.variant, c.stream, b, blocks, stream);
+  } else {
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "generic_accumulate_kernel<%s,%d>", arithName(arith), es / arithBytes(arith));
+    launchAccumulateGenericBatch(arith, es, b, blocks, stream);
+  }
+}
 
 void launchBatch(const Classified& c, int es, const Batch& b, unsigned int blocks, hipStream_t stream) {
   const int variant = c.variant, stream_access = c.stream;
@@ -397,7 +471,7 @@ void describeMove(const Move3D& m, const void* src, void* dst, int es, const Ker
 }
 
 void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
-                 const KernelTuning* tuning, KernelStats* stats, void* const* dst_base_override) {
+                 const KernelTuning* tuning, KernelStats* stats, void* const* dst_base_override, ArithType arith) {
   const bool remote = dst_base_override != nullptr;
   const KernelTuning& t = tuning ? *tuning : kDefaultTuning;
   if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
@@ -405,6 +479,13 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
   cs.reserve(n);
   for (int i = 0; i < n; ++i) {
     if (moves[i].elements() == 0) continue;
+    if (moves[i].add) {
+      if (arith == ARITH_NONE) CD_INTERNAL_ERROR("add-move without an arithmetic type");
+      if (remote) CD_INTERNAL_ERROR("add-moves never have remote destinations");
+      if (es % arithBytes(arith) != 0 || es / arithBytes(arith) > 2) CD_INTERNAL_ERROR("element size does not fit the arithmetic type");
+      cs.push_back(classifyAdd(moves[i], bufs, es, arithBytes(arith), t));
+      continue;
+    }
     cs.push_back(classify(moves[i], bufs, es, t, dst_base_override ? dst_base_override[i] : nullptr, remote));
   }
   // moves of one phase are independent, so they may be regrouped by kernel flavour
@@ -416,7 +497,7 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
     for (size_t j = i; j < cs.size() && b.n < kMaxBatch; ++j) {
       if (done[j] || cs[j].cls != cs[i].cls || cs[j].variant != cs[i].variant || cs[j].stream != cs[i].stream ||
           cs[j].window != cs[i].window || cs[j].dense != cs[i].dense || cs[j].lines != cs[i].lines ||
-          cs[j].rowlines != cs[i].rowlines)
+          cs[j].rowlines != cs[i].rowlines || cs[j].add != cs[i].add)
         continue;
       if (blocks + cs[j].blocks > 0x7fffffffULL) {
         if (b.n == 0) CD_NOT_SUPPORTED("single block move too large for one launch");
@@ -446,7 +527,8 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
         blocks = widest * b.n;
       }
     }
-    launchBatch(cs[i], es, b, (unsigned int)blocks, stream);
+    if (cs[i].add) launchAddBatch(cs[i], es, arith, b, (unsigned int)blocks, stream);
+    else launchBatch(cs[i], es, b, (unsigned int)blocks, stream);
     if (stats) stats->launches[cs[i].cls] += 1;
   }
 }

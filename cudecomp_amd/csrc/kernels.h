@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include "kernels_batch.h"
 #include "plan.h"
 
 namespace cudecomp {
@@ -32,9 +33,13 @@ struct KernelTuning {
 
 // Execute `n` independent moves (disjoint destinations) of `es`-byte elements.  bufs[BufId] are the
 // device pointers of the input / output / workspace buffers.  Asynchronous on `stream`.
+// Copy moves (Move3D::add == false) need nothing else.  Add-moves (dst += src; kernels_accumulate.hip) need `arith`, the real
+// type the elements consist of (arithOf(dtype), internal.h), and a local destination; they run as row or element-wise
+// additions over exactly the cells of the move -- never the transposing, shifted, dense or window forms.
 void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
                  const KernelTuning* tuning = nullptr, KernelStats* stats = nullptr,
-                 void* const* dst_base_override = nullptr);  // per-move destination base (remote buffers)
+                 void* const* dst_base_override = nullptr,  // per-move destination base (remote buffers)
+                 ArithType arith = ARITH_NONE);
 
 // How a move WOULD run (no launch, no device needed): class, kernel variant, tile, tile counts, walk parameters, access mode.
 // out[10] = {class, variant, tile_i (row copies: 0 plain / 1 shifted / 2 dense kernel), tile_j, tiles_i, tiles_j, batch, p0 (run length), p1 (walk bits: 1 XCD-contiguous, 2 j first,

@@ -13,6 +13,10 @@
 #include <cstdint>
 
 namespace cudecomp {
+
+// arithmetic of an add-move (Move3D::add): the REAL type the elements consist of (complex elements are two of them)
+enum ArithType { ARITH_NONE = 0, ARITH_F16 = 1, ARITH_BF16 = 2, ARITH_F32 = 3, ARITH_F64 = 4 };
+
 namespace kern {
 
 constexpr int kMaxBatch = 8;
@@ -62,6 +66,10 @@ constexpr int kLinesUnitBytes = 128;
 void launchLinesBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // kernels_rowlines.hip: the same idea for destinations whose adjacent rows are the tile's own rows (128-byte units)
 void launchRowLinesBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+// kernels_accumulate.hip: add-moves (dst += src).  Rows: the Batch of launchRowsBatch mode 0; stream_access 0 default caching,
+// 1 non-temporal source loads.  Generic: extents / strides in elements of es bytes.
+void launchAccumulateRowsBatch(int arith, int vector_bytes, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+void launchAccumulateGenericBatch(int arith, int es, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

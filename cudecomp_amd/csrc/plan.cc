@@ -49,6 +49,22 @@ Move3D blockMove(BufId sb, i64 soff, const i64 sst[3], BufId db, i64 doff, const
   return m;
 }
 
+// only nearest-neighbour halos (updates and accumulations alike): a halo of `he` cells along the split dim `dim` may not be
+// wider than my slab or a neighbour's slab
+void requireNearestNeighbourHalo(const GridShape& g, const std::array<int32_t, 2>& pidx, CommAxis comm_axis, int dim, i64 he,
+                                 bool periodic) {
+  const int np = g.pdims[comm_axis];
+  const auto splits = splitExtent(g.gdims_dist[dim], np, g.gdims[dim] - g.gdims_dist[dim]);
+  const int me = pidx[comm_axis == COMM_COL ? 0 : 1];
+  int l = me - 1, r = me + 1;
+  if (periodic) {
+    l = (l + np) % np;
+    r = (r + np) % np;
+  }
+  if ((l >= 0 && (he > splits[l] || he > splits[me])) || (r < np && (he > splits[r] || he > splits[me])))
+    CD_INVALID_USAGE("halo includes ranks other than nearest neighbor processes, this is not currently supported.");
+}
+
 }  // namespace
 
 TransposePlan buildTransposePlan(const GridShape& g, int rank, TransposeOp op, const int32_t* in_halo,
@@ -257,16 +273,7 @@ HaloPlan buildHaloPlan(const GridShape& g, int rank, int axis, int dim, const in
     if (p.neighbor[0] == rank && p.neighbor[1] == rank) {  // self_exchange: periodic wrap onto myself, through the transport
       if (he > h.extentG(dim) - 2 * he) CD_INVALID_USAGE("halo wider than the pencil it wraps around");
     } else {
-      const int np = g.pdims[p.comm_axis];
-      const auto splits = splitExtent(g.gdims_dist[dim], np, g.gdims[dim] - g.gdims_dist[dim]);
-      const int me = pidx[p.comm_axis == COMM_COL ? 0 : 1];
-      int l = me - 1, r = me + 1;
-      if (periodic) {
-        l = (l + np) % np;
-        r = (r + np) % np;
-      }
-      if ((l >= 0 && (he > splits[l] || he > splits[me])) || (r < np && (he > splits[r] || he > splits[me])))
-        CD_INVALID_USAGE("halo includes ranks other than nearest neighbor processes, this is not currently supported.");
+      requireNearestNeighbourHalo(g, pidx, p.comm_axis, dim, he, periodic);
     }
     const bool faces_contiguous = (dim == h.order[2]);
     p.kind = (faces_contiguous && !anySet(pad) && !force_packed) ? HaloPlan::DIRECT : HaloPlan::PACKED;
@@ -314,6 +321,74 @@ HaloPlan buildHaloPlan(const GridShape& g, int rank, int axis, int dim, const in
       p.recv_off[1] = hi_halo;
       break;
     default: break;
+  }
+  return p;
+}
+
+HaloPlan buildHaloAccumulatePlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                 const int32_t* pad, bool /*force_packed*/, bool self_exchange) {
+  HaloPlan p;
+  p.axis = axis;
+  p.dim = dim;
+  p.accumulate = true;
+  const auto pidx = gridIndexOfRank(g, rank);
+  const Pencil h = makePencil(g, pidx, axis, halo, nullptr);  // extents of what is exchanged
+  const Pencil hp = makePencil(g, pidx, axis, halo, pad);     // strides of the user's buffer
+  if (anyEmptyPencil(g, axis)) CD_NOT_SUPPORTED("halo operations on configurations with empty pencils not supported");
+
+  const bool periodic = periods && periods[dim];
+  p.neighbor[0] = shiftedRank(g, rank, axis, dim, -1, periodic);
+  p.neighbor[1] = shiftedRank(g, rank, axis, dim, +1, periodic);
+  const i64 he = halo[dim];
+  if (he == 0) return p;
+  if (p.neighbor[0] == -1 && p.neighbor[1] == -1) return p;  // one rank along a non-periodic dimension
+
+  p.comm_axis = commAxisOfDim(axis, dim);
+  const i64 interior = h.extentG(dim) - 2 * he;
+  if (p.neighbor[0] == rank && p.neighbor[1] == rank) {  // periodic wrap onto myself
+    if (he > interior) CD_INVALID_USAGE("halo wider than the pencil it wraps around");
+    p.kind = self_exchange ? HaloPlan::PACKED : HaloPlan::SELF_PERIODIC;
+  } else {
+    // only nearest-neighbour halos: the halo may not be wider than my slab or a neighbour's slab
+    requireNearestNeighbourHalo(g, pidx, p.comm_axis, dim, he, periodic);
+    p.kind = HaloPlan::PACKED;
+  }
+  p.ordered = interior < 2 * he;
+
+  // the slabs of buildHaloPlan: thickness he along `dim`, the other two dims INCLUDING their halos, not their padding
+  i64 E[3], st[3], fst[3];
+  for (int ga = 0; ga < 3; ++ga) {
+    E[ga] = (ga == dim) ? he : h.extentG(ga);
+    st[ga] = hp.strideG(ga);
+  }
+  denseStrides(h.order, E, fst);
+  p.face_elements = E[0] * E[1] * E[2];
+  const i64 sd = st[dim];
+  const i64 n = hp.extentG(dim) - (pad ? pad[dim] : 0);  // extent along dim without padding
+  const i64 lo_halo = 0, lo_face = he * sd, hi_face = (n - 2 * he) * sd, hi_halo = (n - he) * sd;
+  auto adding = [](Move3D m) {
+    m.add = true;
+    return m;
+  };
+
+  if (p.kind == HaloPlan::SELF_PERIODIC) {
+    p.pre.push_back(adding(blockMove(BUF_IN, hi_halo, st, BUF_IN, lo_face, st, E, -1)));
+    p.pre.push_back(adding(blockMove(BUF_IN, lo_halo, st, BUF_IN, hi_face, st, E, -1)));
+    return p;
+  }
+  const i64 A = alignElements(p.face_elements);
+  p.xbuf = BUF_WORK;
+  p.send_off[0] = 0;
+  p.send_off[1] = A;
+  p.recv_off[0] = 2 * A;
+  p.recv_off[1] = 3 * A;
+  if (p.neighbor[0] != -1) {
+    p.pre.push_back(blockMove(BUF_IN, lo_halo, st, BUF_WORK, p.send_off[0], fst, E, 0));
+    p.post.push_back(adding(blockMove(BUF_WORK, p.recv_off[0], fst, BUF_IN, lo_face, st, E, 0)));
+  }
+  if (p.neighbor[1] != -1) {
+    p.pre.push_back(blockMove(BUF_IN, hi_halo, st, BUF_WORK, p.send_off[1], fst, E, 1));
+    p.post.push_back(adding(blockMove(BUF_WORK, p.recv_off[1], fst, BUF_IN, hi_face, st, E, 1)));
   }
   return p;
 }

@@ -38,6 +38,10 @@ struct Move3D {
   // through workspaces or whole contiguous faces, buildHaloPlan), and no kernel of the caller on another stream (the
   // documented contract; CUDECOMP_PRESERVE_OUTPUT_HALOS=1 for callers who cannot promise that).
   i64 dst_row_pitch = 0;
+  // false: dst = src (every move of a transpose or a halo update).  true: dst = dst + src in the arithmetic of the call's data
+  // type (halo accumulation, buildHaloAccumulatePlan): the kernel layer reads and rewrites exactly the destination cells of
+  // the move -- never the gap cells between rows, never a peer's memory.
+  bool add = false;
 
   i64 elements() const { return extent[0] * extent[1] * extent[2]; }
 };
@@ -147,10 +151,23 @@ struct HaloPlan {
   i64 face_elements = 0;
   BufId xbuf = BUF_WORK;
   i64 send_off[2] = {0, 0}, recv_off[2] = {0, 0};
+  // accumulation plans (buildHaloAccumulatePlan) only
+  bool accumulate = false;
+  bool ordered = false;  // the destinations of the two add-moves overlap (interior narrower than two halos): one launch each, in order
 };
 
 HaloPlan buildHaloPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
                        const int32_t* pad, bool force_packed, bool self_exchange = false);
+
+// Halo ACCUMULATION along `dim` -- the transpose of the update: what the neighbours hold in the halo cells they keep of MY
+// cells is added to my face cells (low face += the low neighbour's high halo, then high face += the high neighbour's low
+// halo; include/cudecomp_amd.h has the contract).  Same arguments and refusals as buildHaloPlan, plus: a halo wider than my
+// own interior along `dim` is INVALID_USAGE.  Kinds: NONE, SELF_PERIODIC (two add-moves pencil -> pencil in `pre`), PACKED
+// (`pre`: my halos -> send slots 0 / 1, plain copies; the exchange of HaloExchange: slot i travels to neighbour i and lands in
+// its receive slot 1 - i; `post`: add-moves receive slot 0 -> low face, receive slot 1 -> high face).  Never DIRECT: what
+// arrives must be added, not stored.  The workspace layout is buildHaloPlan's (haloWorkspaceElements covers it).
+HaloPlan buildHaloAccumulatePlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                 const int32_t* pad, bool force_packed, bool self_exchange = false);
 
 // Number of stages every member of the communicator arrives at without talking: at most `wanted`, at most the smallest
 // chunk extent, at most 14 (flag steps), and no stage smaller than `min_stage_bytes` of the largest pencil (below that the extra

@@ -408,6 +408,22 @@ void executeTranspose(cudecompHandle_t h, cudecompGridDesc_t gd, const Transpose
 
 }  // namespace
 
+// the exchange of a halo plan (update or accumulation): send slot / face i travels to neighbour i and lands in ITS receive slot
+// 1 - i (update: my low face fills the low neighbour's HIGH halo; accumulation: my low halo is the addend of its HIGH face)
+static HaloExchange haloExchangeOf(const HaloPlan& plan, void* const bufs[3], int es) {
+  HaloExchange x;
+  x.send = x.recv = static_cast<char*>(bufs[plan.xbuf]);
+  for (int i = 0; i < 2; ++i) {
+    x.send_off[i] = plan.send_off[i] * es;
+    x.recv_off[i] = plan.recv_off[i] * es;
+    x.remote_off[i] = plan.recv_off[1 - i] * es;
+    x.neighbor[i] = plan.neighbor[i];
+  }
+  x.bytes = plan.face_elements * es;
+  x.comm_axis = plan.comm_axis;
+  return x;
+}
+
 void runHalo(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, void* work, cudecompDataType_t dtype,
              const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
   const int es = elementSize(dtype);
@@ -441,16 +457,7 @@ void runHalo(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, v
     perfMark(pev, 3, stream);
     return;
   }
-  HaloExchange x;
-  x.send = x.recv = static_cast<char*>(bufs[plan.xbuf]);
-  for (int i = 0; i < 2; ++i) {
-    x.send_off[i] = plan.send_off[i] * es;
-    x.recv_off[i] = plan.recv_off[i] * es;
-    x.remote_off[i] = plan.recv_off[1 - i] * es;  // my low face fills the low neighbour's HIGH halo slot
-    x.neighbor[i] = plan.neighbor[i];
-  }
-  x.bytes = plan.face_elements * es;
-  x.comm_axis = plan.comm_axis;
+  const HaloExchange x = haloExchangeOf(plan, bufs, es);
   // packed faces: pack, exchange and unpack overlap face by face (env CUDECOMP_DISABLE_HALO_OVERLAP=1 restores the
   // plain pack -> exchange -> unpack sequence of the reference, halo.h:200-260)
   if (plan.kind == HaloPlan::PACKED && !h->halo_overlap_disable) {
@@ -467,6 +474,50 @@ void runHalo(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, v
   perfMark(pev, 2, stream);
   if (plan.kind == HaloPlan::PACKED) launchMoves(plan.post.data(), (int)plan.post.size(), bufs, es, stream, &h->tuning);
   perfMark(pev, 3, stream);
+}
+
+// Halo accumulation (cudecompAmdAccumulateHalos*): the plain sequence pack my halos -> exchange -> add what arrived onto my
+// faces, with the exchange of the updates (haloExchange: same routing, same transports, same stream ordering).  Not sampled
+// by the performance report.
+void runHaloAccumulate(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, void* work, cudecompDataType_t dtype,
+                       const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
+  const int es = elementSize(dtype);
+  const ArithType arith = arithOf(dtype);
+  const auto backend = gd->config.halo_comm_backend;
+  const bool force_packed = usesPeerTransport(h, backend);
+
+  const auto hh = arr3(halo), pp = arr3(pad);
+  std::array<bool, 3> per{false, false, false};
+  if (periods)
+    for (int i = 0; i < 3; ++i) per[i] = periods[i];
+  const cudecompGridDesc::HaloKey key{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, force_packed};
+  // (force_packed stays in the key because it is HaloKey's: accumulation plans never take the direct form, so a descriptor whose
+  // backend changes between peer and non-peer transports would cache the same plan twice -- harmless)
+  auto it = gd->halo_accumulate_plans.find(key);
+  if (it == gd->halo_accumulate_plans.end()) {
+    HaloPlan p = buildHaloAccumulatePlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), force_packed, h->self_exchange);
+    it = gd->halo_accumulate_plans.emplace(key, std::move(p)).first;
+  }
+  const HaloPlan& plan = it->second;
+  if (plan.kind == HaloPlan::NONE) return;
+
+  ensureDevice(h);
+  void* bufs[3] = {input, input, work};
+  // the two additions of a phase go into one launch unless their destinations overlap (interior narrower than two halos):
+  // then one after the other, low face first
+  auto launch = [&](const std::vector<Move3D>& moves) {
+    if (moves.empty()) return;
+    if (plan.ordered && moves[0].add) {
+      for (const Move3D& m : moves) launchMoves(&m, 1, bufs, es, stream, &h->tuning, nullptr, nullptr, arith);
+    } else {
+      launchMoves(moves.data(), (int)moves.size(), bufs, es, stream, &h->tuning, nullptr, nullptr, arith);
+    }
+  };
+  launch(plan.pre);
+  if (plan.kind == HaloPlan::SELF_PERIODIC) return;
+  const HaloExchange x = haloExchangeOf(plan, bufs, es);
+  haloExchange(h, gd, x, backend, stream);
+  launch(plan.post);
 }
 
 }  // namespace cudecomp

@@ -398,6 +398,52 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompUpdateHalosZ_C
 
+    ! cudecomp_amd.h: halo accumulation, the transpose of the updates (ghost cells summed into their owners)
+    function cudecompAmdAccumulateHalosX_C(handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, &
+                                           padding, stream) bind(C, name="cudecompAmdAccumulateHalosX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input, work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdAccumulateHalosX_C
+
+    function cudecompAmdAccumulateHalosY_C(handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, &
+                                           padding, stream) bind(C, name="cudecompAmdAccumulateHalosY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input, work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdAccumulateHalosY_C
+
+    function cudecompAmdAccumulateHalosZ_C(handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, &
+                                           padding, stream) bind(C, name="cudecompAmdAccumulateHalosZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input, work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdAccumulateHalosZ_C
+
     function cudecomp_c_strlen(str) bind(C, name="strlen") result(n)
       import
       type(c_ptr), value :: str
@@ -810,6 +856,67 @@ contains
     res = cudecompUpdateHalosZ_C(handle, grid_desc, c_loc(input), c_loc(work), int(dtype, c_int), h, per, &
                                  int(dim - 1, c_int32_t), p, s)
   end function cudecompUpdateHalosZ
+
+  ! ---- halo accumulation (cudecomp_amd.h): same arguments as the updates ----------------------------------------
+  function cudecompAmdAccumulateHalosX(handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, padding, &
+                                       stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input, work
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdAccumulateHalosX_C(handle, grid_desc, c_loc(input), c_loc(work), int(dtype, c_int), h, per, &
+                                        int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdAccumulateHalosX
+
+  function cudecompAmdAccumulateHalosY(handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, padding, &
+                                       stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input, work
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdAccumulateHalosY_C(handle, grid_desc, c_loc(input), c_loc(work), int(dtype, c_int), h, per, &
+                                        int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdAccumulateHalosY
+
+  function cudecompAmdAccumulateHalosZ(handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, padding, &
+                                       stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input, work
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdAccumulateHalosZ_C(handle, grid_desc, c_loc(input), c_loc(work), int(dtype, c_int), h, per, &
+                                        int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdAccumulateHalosZ
 
   subroutine halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
     integer(c_int32_t), intent(out) :: h(3), p(3)

@@ -59,7 +59,12 @@ typedef struct {
 typedef struct {
   int32_t kind; /* 0 none, 1 periodic self copy, 2 packed, 3 direct */
   int32_t comm_axis, neighbor[2];
-  int32_t xbuf, n_pre, n_post, reserved;
+  int32_t xbuf, n_pre, n_post;
+  /* 0 for update plans.  Accumulation plans (cudecompExtPlanHaloAccumulate): bit 0 set; bit 1: the destinations of the two
+   * add-moves overlap, they run one after the other in list order; bits 4, 5: pre[0], pre[1] are add-moves (dst += src); bits
+   * 6, 7: post[0], post[1] are.  The exchange between pre and post is that of the updates: send slot i travels to neighbour i
+   * and lands in ITS receive slot 1 - i. */
+  int32_t reserved;
   int64_t face_elements, send_off[2], recv_off[2];
   cudecompExtMove_t pre[2], post[2];
 } cudecompExtHaloPlan_t;
@@ -111,6 +116,12 @@ cudecompResult_t cudecompExtPlanRelay(const cudecompExtGridSpec_t* grid, int32_t
 cudecompResult_t cudecompExtPlanHalo(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
                                      const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
                                      const int32_t padding[], int32_t force_packed, cudecompExtHaloPlan_t* plan);
+
+/* The plan cudecompAmdAccumulateHalos{X,Y,Z} (cudecomp_amd.h) would run on `rank`; fills the structure of the updates, see
+ * cudecompExtHaloPlan_t::reserved for what marks the add-moves.  kind is 0, 1 or 2, never 3. */
+cudecompResult_t cudecompExtPlanHaloAccumulate(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
+                                               const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
+                                               const int32_t padding[], int32_t force_packed, cudecompExtHaloPlan_t* plan);
 
 /* Stateless geometry queries on a grid spec (no handle, no communicator): what cudecompGetPencilInfo,
  * cudecompGetShiftedRank, cudecompGetTransposeWorkspaceSize and cudecompGetHaloWorkspaceSize would answer on `rank`. */
@@ -223,6 +234,13 @@ cudecompResult_t cudecompExtEstimateCycleMs(cudecompHandle_t handle, const cudec
 cudecompResult_t cudecompExtMove3D(const void* src, void* dst, int32_t es, const int64_t extent[3],
                                    const int64_t ss[3], const int64_t ds[3], int32_t force_generic,
                                    int32_t* kernel_class, hipStream_t stream);
+
+/* One add-move on the GPU: dst[...] += src[...] over the cells of the move, in the arithmetic of `dtype` (cudecomp_amd.h;
+ * strides in elements of that type).  force_generic: bit 0 the element-wise kernel, bit 1 streaming source loads regardless
+ * of the size.  *kernel_class (optional): 0 rows, 2 generic. */
+cudecompResult_t cudecompExtAccumulate3D(const void* src, void* dst, cudecompDataType_t dtype, const int64_t extent[3],
+                                         const int64_t ss[3], const int64_t ds[3], int32_t force_generic,
+                                         int32_t* kernel_class, hipStream_t stream);
 
 /* How the kernel layer WOULD execute a 3-D block move between buffers at the given addresses (no launch; works without a
  * GPU): out[10] = {class (0 rows, 1 LDS transpose, 2 generic), kernel variant, tile_i, tile_j, tiles_i, tiles_j, batch extent,
