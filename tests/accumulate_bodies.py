@@ -5,7 +5,14 @@ The restatement works on INTEGER arrays of shape (cells, reals per element): the
 cell (halos and padding included), any cell ends up as a sum of at most 27 cells (<= 189), and such integers are exact in
 every element type, bf16 included (8 significand bits hold up to 256) -- so the expected pencil is computed once in int64 and
 compared bit for bit in the type under test.  Every rank can build every rank's initial pencil (seeded by rank and axis) and
-therefore the expected value of every cell of its own pencil."""
+therefore the expected value of every cell of its own pencil.
+
+What is ADDED is stated a second time, without the code under test and without torch: typed_add (IEEE addition of numpy for
+fp16 / fp32 / fp64; bf16 from numpy integers and fp32 alone), pinned by tests/test_accumulate_reference.py.  It serves the edge
+value payloads of the kernel tests (edge_table, all_pairs, the three dense draws) and the payload="typed" mode of the
+restatement: non-integer reals, every sum rounds, so the ORDER of the two additions on overlapping faces shows in the bits.
+Comparison rule of everything typed (mismatches): where the expected real is a NaN the device real must be a NaN -- sign and
+payload are unspecified by the contract --, every other real is compared bit for bit."""
 import numpy as np
 
 import cudecomp_amd as cd
@@ -40,6 +47,135 @@ def to_bytes(values, dtype):
     return out.view(np.uint8).reshape(-1)
 
 
+# ---- the arithmetic in numpy ------------------------------------------------------------------------------------------------
+# real kind -> (unsigned type of its bit pattern, significand bits stored, exponent bits)
+FORMATS = {"fp16": (np.uint16, 10, 5), "bf16": (np.uint16, 7, 8), "fp32": (np.uint32, 23, 8), "fp64": (np.uint64, 52, 11)}
+_KIND_OF_REAL = {np.float16: "fp16", "bf16": "bf16", np.float32: "fp32", np.float64: "fp64"}
+_FLOAT_OF_KIND = {"fp16": np.float16, "fp32": np.float32, "fp64": np.float64}
+
+
+def kind_of(dtype):
+    """"fp16" / "bf16" / "fp32" / "fp64": the format of one real of `dtype`"""
+    return _KIND_OF_REAL[TYPES[dtype][0]]
+
+
+def typed_add(dtype, a, b):
+    """a + b, real by real, in the arithmetic the contract states for `dtype`.  a, b: arrays of the
+    reals' bit patterns (unsigned integers of the real's width; the only form for bf16) or of the native numpy type; the result
+    has the form of `a`.  fp16 / fp32 / fp64: numpy's IEEE addition.  bf16: widen by << 16, add in fp32, round to nearest even
+    with integers; a NaN sum gives the quiet NaN 0x7fc0 (which NaN comes out is unspecified: compare NaNs by class)."""
+    kind = kind_of(dtype)
+    a, b = np.asarray(a), np.asarray(b)
+    with np.errstate(all="ignore"):
+        if kind != "bf16":
+            f = _FLOAT_OF_KIND[kind]
+            if a.dtype == f:
+                return a + b.astype(f, copy=False)
+            assert a.dtype == FORMATS[kind][0] and b.dtype == a.dtype, (a.dtype, b.dtype)
+            return (a.view(f) + b.view(f)).view(a.dtype)
+        assert a.dtype == np.uint16 and b.dtype == np.uint16, (a.dtype, b.dtype)
+        s = (a.astype(np.uint32) << 16).view(np.float32) + (b.astype(np.uint32) << 16).view(np.float32)
+        u = np.ascontiguousarray(s).view(np.uint32).astype(np.uint64)
+        r = ((u + 0x7fff + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+        return np.where(np.isnan(s), np.uint16(0x7fc0), r)
+
+
+def bits_of(dtype, x):
+    """the bit patterns (unsigned integers) of an array of reals in either form typed_add takes"""
+    x = np.ascontiguousarray(x)
+    return x if x.dtype.kind == "u" else x.view(FORMATS[kind_of(dtype)][0])
+
+
+def classes(kind, bits):
+    """dict of boolean masks nan / inf / zero / subnormal of an array of bit patterns -- from the patterns (numpy has no bf16)"""
+    u, m, e = FORMATS[kind]
+    bits = np.asarray(bits, dtype=u)
+    expo = (bits >> u(m)) & u((1 << e) - 1)
+    mant = bits & u((1 << m) - 1)
+    top = u((1 << e) - 1)
+    return {"nan": (expo == top) & (mant != 0), "inf": (expo == top) & (mant == 0), "zero": (expo == 0) & (mant == 0),
+            "subnormal": (expo == 0) & (mant != 0)}
+
+
+def mismatches(kind, got, want):
+    """boolean mask of the reals (bit patterns) that break the comparison rule: expected NaN -> any NaN; otherwise bit-identical"""
+    want_nan = classes(kind, want)["nan"]
+    return np.where(want_nan, ~classes(kind, got)["nan"], np.asarray(got) != np.asarray(want))
+
+
+def edge_table(kind):
+    """24 bit patterns built from the format's parameters: the values at which an addition changes regime"""
+    u, m, e = FORMATS[kind]
+    bias, top = (1 << (e - 1)) - 1, (1 << e) - 1
+    ones = (1 << m) - 1
+
+    def pat(sign, expo, mant):
+        return (sign << (m + e)) | (expo << m) | mant
+
+    t = []
+    for expo, mant in ((0, 0), (0, 1), (0, ones), (1, 0), (bias, 0)):  # zero, smallest / largest subnormal, smallest normal, one
+        t += [pat(0, expo, mant), pat(1, expo, mant)]
+    t += [pat(0, bias, 1), pat(0, bias - m - 1, 0)]                    # 1 + ulp, half an ulp of 1
+    t += [pat(0, top - 1, ones), pat(1, top - 1, ones), pat(0, top - 1 - m - 1, 0)]  # +- largest finite, half its ulp
+    t += [pat(0, top, 0), pat(1, top, 0), pat(0, top, 1 << (m - 1)), pat(0, top, 1)]  # +- inf, a quiet NaN, NaN with payload 1
+    # ordinary values: 1.5, -2.75, about 0.3, about -106.6, the largest number below 1
+    t += [pat(0, bias, 1 << (m - 1)), pat(1, bias + 1, 3 << (m - 3)), pat(0, bias - 2, 0x3333333333333 >> (52 - m)),
+          pat(1, bias + 6, 0xaaaaaaaaaaaaa >> (52 - m)), pat(0, bias - 1, ones)]
+    assert len(t) == 24 and len(set(t)) == 24
+    return np.array(t, dtype=u)
+
+
+def all_pairs(table):
+    """(a, b) with a[i*K + j] = table[i], b[i*K + j] = table[j]: consecutive reals always differ in class on the b side"""
+    k = len(table)
+    return np.repeat(table, k), np.tile(table, k)
+
+
+def dense_draws(kind, n, seed):
+    """three draws of n operand pairs as bit patterns, {"uniform", "cancelling", "subnormal"}:
+    uniform    uniformly random patterns; in one pair of eight b takes the exponent field of a, and in half of those both keep
+               only the top four significand bits -- uniform patterns alone overflow, cancel and underflow (almost) never in the
+               wide formats (two fp64 exponents coincide once in 2048 pairs), so a uniform draw alone would not test those;
+    cancelling b = -a with the pattern of b moved up by 0..3 ulps: exact zeros and subnormal differences;
+    subnormal  both operands subnormal or zero, in one pair of eight b = -a."""
+    u, m, e = FORMATS[kind]
+    rng = np.random.default_rng([seed, m, e])
+    width = 1 + m + e
+    sign, emask, low = u(1 << (m + e)), u(((1 << e) - 1) << m), u((1 << (m - 4)) - 1)
+
+    def patterns(bits):
+        return rng.integers(0, 1 << bits, size=n, dtype=np.uint64).astype(u)
+
+    a, b = patterns(width), patterns(width)
+    pick = rng.integers(0, 8, n) == 0
+    b = np.where(pick, (b & ~emask) | (a & emask), b)
+    coarse = pick & (rng.integers(0, 2, n) == 0)
+    a, b = np.where(coarse, a & ~low, a), np.where(coarse, b & ~low, b)
+    draws = {"uniform": (a, b)}
+    a = patterns(width)
+    draws["cancelling"] = (a, ((a ^ sign) + rng.integers(0, 4, n).astype(u)).astype(u))
+    a = patterns(m) | (patterns(1) << u(m + e))
+    b = patterns(m) | (patterns(1) << u(m + e))
+    draws["subnormal"] = (a, np.where(rng.integers(0, 8, n) == 0, a ^ sign, b))
+    return draws
+
+
+def typed_cells(dtype, seed, rank, axis, cells, nc):
+    """non-integer random reals of `dtype` in every cell of rank `rank`'s pencil of axis `axis`, in the form typed_add takes
+    (native numpy type; bf16: bit patterns).  fp32 / fp64: standard normal.  fp16 / bf16: random sign and significand,
+    magnitudes spread over [2^-6, 2^6) -- sums of neighbours in magnitude and sums across it both round."""
+    rng = np.random.default_rng([int(seed), int(rank), int(axis), 77])
+    kind = kind_of(dtype)
+    shape = (int(cells), nc)
+    if kind in ("fp32", "fp64"):
+        return rng.standard_normal(shape).astype(_FLOAT_OF_KIND[kind])
+    u, m, e = FORMATS[kind]
+    bias = (1 << (e - 1)) - 1
+    bits = (rng.integers(0, 2, shape) << (m + e)) | (rng.integers(bias - 6, bias + 6, shape) << m) | rng.integers(0, 1 << m, shape)
+    bits = bits.astype(u)
+    return bits if kind == "bf16" else bits.view(np.float16)
+
+
 def initial_cells(seed, rank, axis, cells, nc):
     """integers 0..7 in every cell of rank `rank`'s pencil of axis `axis`"""
     return np.random.default_rng([int(seed), int(rank), int(axis)]).integers(0, 8, size=(int(cells), nc), dtype=np.int64)
@@ -64,19 +200,26 @@ def slab(p, dim, which, h):
     return tuple(idx)
 
 
-def accumulate_reference(g, axis, halo, periods, dim, infos, pencils):
+def accumulate_reference(g, axis, halo, periods, dim, infos, pencils, add=None, swapped=False):
     """one accumulation along `dim` on every rank of oracle grid `g`, in place on `pencils` (one (cells, nc) array per rank):
-    LF += H(low neighbour), then HF += L(high neighbour); halos are read as they were before the call"""
+    LF += H(low neighbour), then HF += L(high neighbour); halos are read as they were before the call.  add(x, y): the
+    addition (default: the arrays' own +).  swapped: the two additions in the OPPOSITE order -- not the contract; what a test
+    of the order must be able to tell from it."""
     h = int(halo[dim])
     if h == 0:
         return
     old = [a.copy() for a in pencils]
+    sides = ((-1, "LF", "H"), (+1, "HF", "L"))
     for r in range(len(pencils)):
-        for side, mine, theirs in ((-1, "LF", "H"), (+1, "HF", "L")):
+        for side, mine, theirs in (sides[::-1] if swapped else sides):
             nb = g.shifted_rank(r, axis, dim, side, bool(periods[dim]))
             if nb < 0:
                 continue
-            pencil3(infos[r], pencils[r])[slab(infos[r], dim, mine, h)] += pencil3(infos[nb], old[nb])[slab(infos[nb], dim, theirs, h)]
+            dst, src = pencil3(infos[r], pencils[r]), pencil3(infos[nb], old[nb])[slab(infos[nb], dim, theirs, h)]
+            if add is None:
+                dst[slab(infos[r], dim, mine, h)] += src
+            else:
+                dst[slab(infos[r], dim, mine, h)] = add(dst[slab(infos[r], dim, mine, h)], src)
 
 
 def update_reference(g, axis, halo, periods, dim, infos, pencils):
@@ -93,13 +236,18 @@ def update_reference(g, axis, halo, periods, dim, infos, pencils):
             pencil3(infos[r], pencils[r])[slab(infos[r], dim, mine, h)] = pencil3(infos[nb], old[nb])[slab(infos[nb], dim, theirs, h)]
 
 
-def expected_after(g, axis, halo, periods, padding, seed, nc, dims=(2, 1, 0)):
-    """(pencil infos, initial pencils, pencils after accumulating along `dims` in turn) of every rank"""
+def expected_after(g, axis, halo, periods, padding, seed, nc, dims=(2, 1, 0), typed=None, swapped=False):
+    """(pencil infos, initial pencils, pencils after accumulating along `dims` in turn) of every rank.  typed: a data type --
+    cells from typed_cells, every addition through typed_add in that type, in the documented order (swapped: in the other)"""
     infos = [g.pencil_info(r, axis, halo, padding) for r in range(g.nranks)]
-    init = [initial_cells(seed, r, axis, infos[r].size, nc) for r in range(g.nranks)]
+    if typed is None:
+        init, add = [initial_cells(seed, r, axis, infos[r].size, nc) for r in range(g.nranks)], None
+    else:
+        init = [typed_cells(typed, seed, r, axis, infos[r].size, nc) for r in range(g.nranks)]
+        add = lambda x, y: typed_add(typed, x, y)  # noqa: E731
     want = [a.copy() for a in init]
     for dim in dims:
-        accumulate_reference(g, axis, halo, periods, dim, infos, want)
+        accumulate_reference(g, axis, halo, periods, dim, infos, want, add, swapped)
     return infos, init, want
 
 
@@ -119,7 +267,11 @@ def _first_difference(got, want, es):
 def accumulate_sweep(rank, nranks, args):
     """cudecompAmdAccumulateHalos along dims 2, 1, 0 for every axis of args["axes"] and every type of args["dtypes"]: the whole
     pencil (halo and padding cells included) against the all-ranks numpy restatement, bit for bit.  args["adjoint"]: also
-    <U x, y> == <x, A y> (fp64, integers) with the library's own cudecompUpdateHalos as the witness."""
+    <U x, y> == <x, A y> (fp64, integers) with the library's own cudecompUpdateHalos as the witness.
+    args["payload"] == "typed": non-integer reals of the element type instead of the integers, the restatement in that type's
+    arithmetic (typed_add) in the documented order.  args["overlap"]: the faces of some rank overlap -- the restatement with the
+    two additions swapped must then differ from the expected pencils (of all ranks together) in at least one cell, or the case
+    could not see a swap."""
     import torch
     from tests import gpu_bodies as B
     h, gd, g = B._setup(rank, nranks, args)
@@ -131,16 +283,28 @@ def accumulate_sweep(rank, nranks, args):
         wsz = max(cd.cudecompGetHaloWorkspaceSize(h, gd, axis, halo), 1)
         for dtype in args.get("dtypes", ALL_TYPES):
             nc, es = TYPES[dtype][1], element_bytes(dtype)
-            infos, init, want = expected_after(g, axis, halo, periods, padding, args.get("seed", 5), nc)
+            typed = dtype if args.get("payload", "ints") == "typed" else None
+            infos, init, want = expected_after(g, axis, halo, periods, padding, args.get("seed", 5), nc, typed=typed)
             if infos[rank].as_dict() != p.as_dict():
                 failures.append("rank %d axis %d: pencil info differs from the oracle" % (rank, axis))
                 continue
+            if typed is not None and args.get("overlap"):
+                other = expected_after(g, axis, halo, periods, padding, args.get("seed", 5), nc, typed=typed, swapped=True)[2]
+                if all(np.array_equal(bits_of(dtype, a), bits_of(dtype, b)) for a, b in zip(want, other)):
+                    failures.append("rank %d axis %d %s: swapping the two additions changes no cell: this seed cannot see the order" %
+                                    (rank, axis, NAMES[dtype]))
             work_ptr = cd.cudecompMalloc(h, gd, wsz * es)
-            data = _dev(to_bytes(init[rank], dtype))
+            raw = (lambda a: to_bytes(a, dtype)) if typed is None else (lambda a: bits_of(dtype, a).view(np.uint8).reshape(-1))
+            data = _dev(raw(init[rank]))
             for dim in (2, 1, 0):
                 cd.cudecompAccumulateHalos(axis, h, gd, data.data_ptr(), work_ptr, dtype, halo, periods, dim, padding, stream)
             torch.cuda.synchronize()
-            diff = _first_difference(data.cpu().numpy(), to_bytes(want[rank], dtype), es)
+            got = data.cpu().numpy()
+            if typed is None:
+                diff = _first_difference(got, raw(want[rank]), es)
+            else:  # the rule of everything typed: NaN by class (none arises from these magnitudes), all else bit for bit
+                bad = np.nonzero(mismatches(kind_of(dtype), got.view(FORMATS[kind_of(dtype)][0]), bits_of(dtype, want[rank]).reshape(-1)))[0]
+                diff = "%d reals differ, first in cell %d" % (bad.size, bad[0] // nc) if bad.size else None
             if diff:
                 failures.append("rank %d axis %d %s halo %s periods %s padding %s: %s; last kernel %s" %
                                 (rank, axis, NAMES[dtype], tuple(halo), tuple(periods), tuple(padding), diff,
