@@ -1,4 +1,5 @@
-// kernels.h -- host entry points of the HIP data-movement kernels (kernels.cc: classification and batching; kernels_rows.hip, kernels_transpose.hip, kernels_window.hip: the kernels).
+// kernels.h -- host entry points of the HIP data-movement kernels (kernels.cc: classification and batching; kernels_batch.h:
+// the record of a kernel choice and the list of code objects the kernels live in).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -7,11 +8,11 @@
 
 namespace cudecomp {
 
-// How a normalized move is executed on the GPU.
+// How a normalized move is executed on the GPU: the three families KernelStats counts; KernelKind (kernels_batch.h) names the kernel.
 enum MoveClass {
-  MOVE_ROWS_VEC = 0,   // rows contiguous on both sides, everything 16-byte aligned: 16 B/lane streaming copy
-  MOVE_TRANSPOSE = 1,  // fastest source dim != fastest destination dim: LDS-tiled transpose (vector or scalar lanes)
-  MOVE_GENERIC = 2,    // anything else (odd extents, unaligned bases, degenerate dims): element-wise
+  MOVE_ROWS_VEC = 0,   // rows contiguous on both sides: row copy or addition, 2 ... 16 B/lane (the widest the row length allows)
+  MOVE_TRANSPOSE = 1,  // source rows along another dim than destination rows, both extents >= 4: LDS-tiled transposition
+  MOVE_GENERIC = 2,    // anything else (no unit stride, 1-element rows, forced): element-wise
   MOVE_CLASS_COUNT = 3
 };
 

@@ -199,31 +199,28 @@ bool launchGenericOfType(int nc, const Batch& b, const dim3& grid, const dim3& b
 
 using namespace kern;
 
-void launchAccumulateRowsBatch(int arith, int vb, int stream_access, const Batch& b, unsigned int blocks, hipStream_t stream) {
+void launchAccumulateBatch(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) {
   const dim3 grid(blocks), block(kThreads);
+  const int vb = k.vec, s = streamArgOf(k.kind, k.access), es = k.es;
   bool ok = false;
-  switch (arith) {
-    case ARITH_F16: ok = launchRowsOfType<_Float16>(vb, stream_access, b, grid, block, stream); break;
-    case ARITH_BF16: ok = launchRowsOfType<__bf16>(vb, stream_access, b, grid, block, stream); break;
-    case ARITH_F32: ok = launchRowsOfType<float>(vb, stream_access, b, grid, block, stream); break;
-    case ARITH_F64: ok = launchRowsOfType<double>(vb, stream_access, b, grid, block, stream); break;
-    default: break;
+  if (k.kind == K_ROWS_ADD) {
+    switch (k.arith) {
+      case ARITH_F16: ok = launchRowsOfType<_Float16>(vb, s, b, grid, block, stream); break;
+      case ARITH_BF16: ok = launchRowsOfType<__bf16>(vb, s, b, grid, block, stream); break;
+      case ARITH_F32: ok = launchRowsOfType<float>(vb, s, b, grid, block, stream); break;
+      case ARITH_F64: ok = launchRowsOfType<double>(vb, s, b, grid, block, stream); break;
+      default: break;
+    }
+  } else if (k.kind == K_GENERIC_ADD) {
+    switch (k.arith) {
+      case ARITH_F16: ok = launchGenericOfType<_Float16>(es / 2, b, grid, block, stream); break;
+      case ARITH_BF16: ok = es == 2 && launchGenericOfType<__bf16>(1, b, grid, block, stream); break;
+      case ARITH_F32: ok = launchGenericOfType<float>(es / 4, b, grid, block, stream); break;
+      case ARITH_F64: ok = launchGenericOfType<double>(es / 8, b, grid, block, stream); break;
+      default: break;
+    }
   }
-  if (!ok) CD_INTERNAL_ERROR("no row accumulation kernel for this arithmetic type and vector width");
-  CD_CHECK_HIP(hipGetLastError());
-}
-
-void launchAccumulateGenericBatch(int arith, int es, const Batch& b, unsigned int blocks, hipStream_t stream) {
-  const dim3 grid(blocks), block(kThreads);
-  bool ok = false;
-  switch (arith) {
-    case ARITH_F16: ok = launchGenericOfType<_Float16>(es / 2, b, grid, block, stream); break;
-    case ARITH_BF16: ok = es == 2 && launchGenericOfType<__bf16>(1, b, grid, block, stream); break;
-    case ARITH_F32: ok = launchGenericOfType<float>(es / 4, b, grid, block, stream); break;
-    case ARITH_F64: ok = launchGenericOfType<double>(es / 8, b, grid, block, stream); break;
-    default: break;
-  }
-  if (!ok) CD_INTERNAL_ERROR("no element-wise accumulation kernel for this arithmetic type and element size");
+  if (!ok) CD_INTERNAL_ERROR("no accumulation kernel for this arithmetic type, lane width and element size");
   CD_CHECK_HIP(hipGetLastError());
 }
 

@@ -1,5 +1,7 @@
-// kernels_batch.h -- what csrc/kernels.cc (host: classification, batching) and the kernel code objects (kernels_rows.hip,
-// kernels_transpose.hip, kernels_window.hip) share: the launch descriptor and one launcher per code object.
+// kernels_batch.h -- what csrc/kernels.cc (host: classification, batching) and the kernel code objects share: the record of a
+// kernel choice (KernelChoice), the launch descriptor (Batch) and the launchers.  The code objects the classifier dispatches
+// to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
+// kernels_rowlines.hip, kernels_accumulate.hip; kernels_rotate.hip and sync.hip are launched by the executor.
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
 // code object beyond roughly 0.6-0.7 MB puts the whole process into a regime where every small synchronous operation costs
@@ -32,12 +34,25 @@ struct DevMove {
   long long ds[3];  // dst strides
 };
 
+// tile walk of the LDS-tiled transposes: bits of Batch::p1
+constexpr int kWalkXcd = 1;            // every XCD gets a contiguous run of tiles
+constexpr int kWalkJFirst = 2;         // along the destination rows (j) first; clear: along the source rows (i) first
+constexpr int kWalkRunOverPlanes = 4;  // transpose_kernel: the runs of p0 are over batch planes; clear: over tiles along j
+constexpr int kWalkLines = 8;          // the walk of transpose_lines_kernel
+constexpr int kWalkRowLines = 16;      // the walk of transpose_rowlines_kernel
+constexpr int kWalkGroupShift = 8;     // transpose_lines_kernel: p1 >> kWalkGroupShift = tile rows per group (0: all)
+
 struct Batch {
   int n;
   int interleave;  // 1: workgroup b serves move b % n (moves with REMOTE destinations: keeps every xGMI link busy
                    // for the whole launch instead of draining one peer's chunk after the other)
-  int p0[kMaxBatch];                      // kernel-specific small parameter
-  int p1[kMaxBatch];                      // second small parameter (transpose: XCD-contiguous tile walk)
+  // p0, p1 per kind of kernel (KernelKind):
+  //   row copies and additions   p0 = log2 of the lanes per row; p1 = row length in BYTES (rows_shifted_kernel only);
+  //                              rows_dense_kernel reads neither
+  //   transposes                 p0 = run length of the tile walk (tiles or planes; 0 / 1 = no runs), p1 = kWalk* bits
+  //   element-wise               p0 = the dim the lanes run along, p1 unused
+  int p0[kMaxBatch];
+  int p1[kMaxBatch];
   unsigned int first_block[kMaxBatch + 1];
   unsigned int t0[kMaxBatch];             // tiles along dim 0
   unsigned int t1[kMaxBatch];             // tiles along dim 1
@@ -46,30 +61,57 @@ struct Batch {
 
 }  // namespace kern
 
-// ---- launchers, one per code object (host side; csrc/kernels.cc decides what runs) -------------------------------------------
-// stream_access: 0 default caching, 2 non-temporal loads + stores, 3 non-temporal loads + remote (system-scope write-through)
-// stores, 4 cached loads + non-temporal stores (see storePolicyOf)
-// rows: mode 0 plain, 1 shifted (lanes on the destination's 64-byte grid), 2 dense (whole lines across row ends, Move3D::dst_row_pitch)
-void launchRowsBatch(int mode, int vector_bytes, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+// ---- what runs: one record per kernel choice ----------------------------------------------------------------------------------
+// csrc/kernels.cc classify() fills it; the batching key, the launchers and the kernel's name (lastKernelName) all read it.
+enum KernelKind {
+  K_ROWS,                // rows_kernel
+  K_ROWS_SHIFTED,        // rows_shifted_kernel: lanes on the destination's 64-byte grid
+  K_ROWS_DENSE,          // rows_dense_kernel: whole lines across the row ends (Move3D::dst_row_pitch)
+  K_TRANSPOSE,           // transpose_kernel
+  K_TRANSPOSE_WINDOW,    // transpose_window_kernel: destination rows off the 64-byte grid
+  K_TRANSPOSE_LINES,     // transpose_lines_kernel: windows over the linear positions of adjacent rows (128-byte units)
+  K_TRANSPOSE_ROWLINES,  // transpose_rowlines_kernel: the tile's own rows are the adjacent ones (128-byte units)
+  K_GENERIC,             // generic_kernel
+  K_ROWS_ADD,            // rows_accumulate_kernel (dst += src)
+  K_GENERIC_ADD          // generic_accumulate_kernel
+};
+struct KernelChoice {
+  KernelKind kind;
+  int es;           // element size in bytes
+  int vec;          // row and element-wise kinds: bytes per lane; transposes: elements per lane (1 = element-wise lanes)
+  int ti, tj;       // transposes: the tile (elements, i x j); 0 otherwise
+  int access;       // copies: 0 default caching, 2 non-temporal loads + stores, 3 non-temporal loads + remote (system-scope
+                    // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads
+  ArithType arith;  // additions: the real type the elements consist of; ARITH_NONE otherwise
+  bool operator==(const KernelChoice& o) const {
+    return kind == o.kind && es == o.es && vec == o.vec && ti == o.ti && tj == o.tj && access == o.access && arith == o.arith;
+  }
+};
+constexpr int kLinesUnitBytes = 128;  // alignment unit of the lines and row-lines kernels
+
+// the STREAM template argument (kernels_dev.h, storePolicyOf) with which a kind of kernel serves an access mode
+inline int streamArgOf(KernelKind kind, int access) {
+  if (kind == K_TRANSPOSE || kind == K_ROWS_ADD) return access;
+  if (kind == K_GENERIC || kind == K_GENERIC_ADD) return access == 3 ? 3 : 0;
+  if (kind == K_TRANSPOSE_WINDOW || kind == K_TRANSPOSE_LINES || kind == K_TRANSPOSE_ROWLINES)
+    return access == 2 ? 4 : access;  // always cached loads: the overlap rows of neighbouring windows hit in L2
+  return access == 3 ? 3 : (access >= 1 ? 1 : 0);  // row copies: loads and stores stream together
+}
+
+// ---- launchers, one per code object (host side; csrc/kernels.cc decides what runs): each selects its instantiation from the
+// record and fails with an internal error when there is none.
+void launchRowsBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);  // K_ROWS*, K_GENERIC
 int rowsDenseBytesPerBlock();  // bytes of a plane's span one workgroup of the dense row copy covers
-void launchGenericBatch(int es, bool remote, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-// transposes: `variant` = elements per 16-byte lane group (1 = element-wise lanes), plus 300 for the longer tiles: 64 x 128
-// for 4-byte elements with 16-byte lanes; 64 x 128 (8-byte) and 32 x 64 (16-byte) for far-strided sources.  2-, 4- and
-// 8-byte elements use the XOR-swizzled LDS tile, 16-byte elements the padded one.
-void launchTransposeBatch2(int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-void launchTransposeBatch4(int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-void launchTransposeBatch8(int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-void launchTransposeBatch16(int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-void launchWindowBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-// kernels_lines.hip: windows over the destination's linear positions across row ends (128-byte units)
-constexpr int kLinesUnitBytes = 128;
-void launchLinesBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-// kernels_rowlines.hip: the same idea for destinations whose adjacent rows are the tile's own rows (128-byte units)
-void launchRowLinesBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-// kernels_accumulate.hip: add-moves (dst += src).  Rows: the Batch of launchRowsBatch mode 0; stream_access 0 default caching,
-// 1 non-temporal source loads.  Generic: extents / strides in elements of es bytes.
-void launchAccumulateRowsBatch(int arith, int vector_bytes, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-void launchAccumulateGenericBatch(int arith, int es, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+// kernels_transpose.hip: 2-, 4- and 8-byte elements use the XOR-swizzled LDS tile, 16-byte elements the padded one
+void launchTransposeBatch2(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+void launchTransposeBatch4(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+void launchTransposeBatch8(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+void launchTransposeBatch16(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+void launchWindowBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+void launchLinesBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+void launchRowLinesBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+// kernels_accumulate.hip: add-moves (dst += src).  Rows: the Batch of rows_kernel.  Generic: extents / strides in elements.
+void launchAccumulateBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

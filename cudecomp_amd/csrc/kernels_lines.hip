@@ -30,8 +30,8 @@ namespace {
 // destination and written back unchanged.  Nothing is touched below a slab's first interior cell or above its last one (masked
 // pieces there).  LDS row r of a tile holds linear position lb0 + r for the TI slabs of the tile: a source row (TI elements
 // along i) when it is an interior cell, TI gathered destination cells when it is a gap cell.
-// t0 = tiles along i, t1 = windows along l; p0 = run length of the tile walk (windows), p1 bit 1 = XCD-contiguous walk,
-// p1 >> 8 = tile rows per group.
+// t0 = tiles along i, t1 = windows along l; p0 = run length of the tile walk (windows), p1 & kWalkXcd = XCD-contiguous walk,
+// p1 >> kWalkGroupShift = tile rows per group.
 // ---------------------------------------------------------------------------------------------
 template <int ES, int VW, int TI, int TJ, int STREAM, int UB>
 __global__ __launch_bounds__(kThreads) void transpose_lines_kernel(const Batch b) {
@@ -56,18 +56,18 @@ __global__ __launch_bounds__(kThreads) void transpose_lines_kernel(const Batch b
   const unsigned int ti_n = b.t0[mi], tl_n = b.t1[mi];
   const unsigned int nb = b.first_block[mi + 1] - b.first_block[mi];
   unsigned int lt = lb;
-  if (b.p1[mi] & 1) {  // XCD-contiguous walk, see transpose_kernel
+  if (b.p1[mi] & kWalkXcd) {  // XCD-contiguous walk, see transpose_kernel
     const unsigned int per = nb >> 3;
     if (lb < (per << 3)) lt = (lb & 7u) * per + (lb >> 3);
   }
-  // Walk, outermost to innermost: groups of G tile rows (p1 >> 8; 0 = all of them) -- runs of R windows along l (p0; 0 = the
+  // Walk, outermost to innermost: groups of G tile rows (p1 >> kWalkGroupShift; 0 = all of them) -- runs of R windows along l (p0; 0 = the
   // whole range) -- the tile rows of the group -- the windows of the run.  The default (kernels.cc) is G = 16 with short runs
   // (2 KiB per slab; 32 KiB when the move has several groups): run after run, the 16 x TI slabs of the group each get their
   // next piece -- the source is then read in whole rows, plane by plane, and every slab's write stream advances steadily
   // (measured: profiles/r06_tuning.md).
   unsigned int bi, bl;
   {
-    const unsigned int G = (unsigned int)(b.p1[mi] >> 8) ? (unsigned int)(b.p1[mi] >> 8) : ti_n;
+    const unsigned int G = (unsigned int)(b.p1[mi] >> kWalkGroupShift) ? (unsigned int)(b.p1[mi] >> kWalkGroupShift) : ti_n;
     const unsigned int per_group = G * tl_n;
     const unsigned int g = lt / per_group, x = lt - g * per_group;
     const unsigned int gsize = (g + 1) * G <= ti_n ? G : ti_n - g * G;  // (the last group may have fewer rows)
@@ -192,28 +192,20 @@ __global__ __launch_bounds__(kThreads) void transpose_lines_kernel(const Batch b
   }
 }
 
-template <int STREAM, int UB>
-void launchLinesT(int variant, int es, const Batch& b, unsigned int blocks, hipStream_t stream) {
-  const dim3 grid(blocks), block(kThreads);
-  if (es == 4) {
-    if (variant == 4) transpose_lines_kernel<4, 4, 64, 128, STREAM, UB><<<grid, block, 0, stream>>>(b);
-    else transpose_lines_kernel<4, 1, 64, 128, STREAM, UB><<<grid, block, 0, stream>>>(b);
-  } else if (es == 8) {
-    if (variant == 2) transpose_lines_kernel<8, 2, 64, 64, STREAM, UB><<<grid, block, 0, stream>>>(b);
-    else transpose_lines_kernel<8, 1, 64, 64, STREAM, UB><<<grid, block, 0, stream>>>(b);
-  } else {
-    transpose_lines_kernel<16, 1, 32, 32, STREAM, UB><<<grid, block, 0, stream>>>(b);
-  }
-  CD_CHECK_HIP(hipGetLastError());
+template <int STREAM>
+bool launchLinesT(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) {
+  CD_WINDOW_SHAPES(transpose_lines_kernel, STREAM, kLinesUnitBytes)
 }
 
 }  // namespace
 }  // namespace kern
 
-void launchLinesBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream) {
+void launchLinesBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream) {
   // local destinations only (the gap cells are read back): never the remote-store policy
-  if (stream_access == 4 || stream_access == 2) kern::launchLinesT<4, kLinesUnitBytes>(variant, es, b, blocks, stream);
-  else kern::launchLinesT<0, kLinesUnitBytes>(variant, es, b, blocks, stream);
+  const int s = streamArgOf(k.kind, k.access);
+  const bool ok = s == 4 ? kern::launchLinesT<4>(k, b, blocks, stream) : s == 0 && kern::launchLinesT<0>(k, b, blocks, stream);
+  if (!ok) CD_INTERNAL_ERROR("no lines transpose kernel for this element size, lane width, tile and access mode");
+  CD_CHECK_HIP(hipGetLastError());
 }
 
 }  // namespace cudecomp

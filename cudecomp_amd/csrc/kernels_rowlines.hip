@@ -30,7 +30,7 @@ namespace {
 // lines; per plane only the first row's head and the last row's tail are partial.
 // LDS row r of a tile holds local position lb0 + r for the TI rows of the tile: a source row (TI elements along i; shifted by
 // one element when the position belongs to the next row), or TI gathered gap cells.
-// t0 = tiles along i, t1 = windows per row; p1 bit 1 = XCD-contiguous walk (windows first, then tile rows, then planes).
+// t0 = tiles along i, t1 = windows per row; p1 & kWalkXcd = XCD-contiguous walk (windows first, then tile rows, then planes).
 // ---------------------------------------------------------------------------------------------
 template <int ES, int VW, int TI, int TJ, int STREAM, int UB>
 __global__ __launch_bounds__(kThreads) void transpose_rowlines_kernel(const Batch b) {
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(kThreads) void transpose_rowlines_kernel(const Batc
   const unsigned int ti_n = b.t0[mi], tw_n = b.t1[mi];
   const unsigned int nb = b.first_block[mi + 1] - b.first_block[mi];
   unsigned int lt = lb;
-  if (b.p1[mi] & 1) {  // XCD-contiguous walk, see transpose_kernel
+  if (b.p1[mi] & kWalkXcd) {  // XCD-contiguous walk, see transpose_kernel
     const unsigned int per = nb >> 3;
     if (lb < (per << 3)) lt = (lb & 7u) * per + (lb >> 3);
   }
@@ -196,27 +196,19 @@ __global__ __launch_bounds__(kThreads) void transpose_rowlines_kernel(const Batc
 }
 
 template <int STREAM>
-void launchRowLinesT(int variant, int es, const Batch& b, unsigned int blocks, hipStream_t stream) {
-  const dim3 grid(blocks), block(kThreads);
-  if (es == 4) {
-    if (variant == 4) transpose_rowlines_kernel<4, 4, 64, 128, STREAM, 128><<<grid, block, 0, stream>>>(b);
-    else transpose_rowlines_kernel<4, 1, 64, 128, STREAM, 128><<<grid, block, 0, stream>>>(b);
-  } else if (es == 8) {
-    if (variant == 2) transpose_rowlines_kernel<8, 2, 64, 64, STREAM, 128><<<grid, block, 0, stream>>>(b);
-    else transpose_rowlines_kernel<8, 1, 64, 64, STREAM, 128><<<grid, block, 0, stream>>>(b);
-  } else {
-    transpose_rowlines_kernel<16, 1, 32, 32, STREAM, 128><<<grid, block, 0, stream>>>(b);
-  }
-  CD_CHECK_HIP(hipGetLastError());
+bool launchRowLinesT(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) {
+  CD_WINDOW_SHAPES(transpose_rowlines_kernel, STREAM, kLinesUnitBytes)
 }
 
 }  // namespace
 }  // namespace kern
 
-void launchRowLinesBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream) {
+void launchRowLinesBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream) {
   // local destinations only (the gap cells are read back): never the remote-store policy
-  if (stream_access == 4 || stream_access == 2) kern::launchRowLinesT<4>(variant, es, b, blocks, stream);
-  else kern::launchRowLinesT<0>(variant, es, b, blocks, stream);
+  const int s = streamArgOf(k.kind, k.access);
+  const bool ok = s == 4 ? kern::launchRowLinesT<4>(k, b, blocks, stream) : s == 0 && kern::launchRowLinesT<0>(k, b, blocks, stream);
+  if (!ok) CD_INTERNAL_ERROR("no row-lines transpose kernel for this element size, lane width, tile and access mode");
+  CD_CHECK_HIP(hipGetLastError());
 }
 
 }  // namespace cudecomp

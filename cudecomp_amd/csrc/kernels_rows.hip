@@ -265,11 +265,12 @@ using namespace kern;
 
 int rowsDenseBytesPerBlock() { return kern::kDenseBytes; }
 
-void launchRowsBatch(int mode, int vb, int stream_access, const Batch& b, unsigned int blocks, hipStream_t stream) {
+void launchRowsBatch(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) {
   const dim3 grid(blocks), block(kThreads);
-  const int rs = stream_access == 3 ? 3 : (stream_access >= 1 ? 1 : 0);  // (4 only occurs for transposes)
-  const bool shifted = mode == 1;
-  if (mode == 2) {  // local destinations only (kernels.cc classify())
+  const int rs = streamArgOf(k.kind, k.access), vb = k.vec;
+  const bool plain = k.kind == K_ROWS, shifted = k.kind == K_ROWS_SHIFTED, generic = k.kind == K_GENERIC;
+  if (k.kind == K_ROWS_DENSE) {  // local destinations only (kernels.cc classify())
+    if (vb != 16 || rs == 3) CD_INTERNAL_ERROR("no dense row copy kernel for this vector width and access mode");
     if (rs == 1) rows_dense_kernel<1><<<grid, block, 0, stream>>>(b);
     else rows_dense_kernel<0><<<grid, block, 0, stream>>>(b);
     CD_CHECK_HIP(hipGetLastError());
@@ -281,36 +282,26 @@ void launchRowsBatch(int mode, int vb, int stream_access, const Batch& b, unsign
     else if (rs == 1) K<VB, 1><<<grid, block, 0, stream>>>(b);            \
     else K<VB, 0><<<grid, block, 0, stream>>>(b);                         \
   } while (0)
+#define CD_GENERIC(ES)                                                           \
+  do {                                                                           \
+    if (rs == 3) generic_kernel<ES, true><<<grid, block, 0, stream>>>(b);        \
+    else generic_kernel<ES, false><<<grid, block, 0, stream>>>(b);               \
+  } while (0)
   // (2-byte rows: plain kernel only -- the shifted one copies the row ends in 4-byte pieces, kernels.cc classify())
   if (shifted && vb == 16) CD_ROWS(rows_shifted_kernel, 16);
   else if (shifted && vb == 8) CD_ROWS(rows_shifted_kernel, 8);
   else if (shifted && vb == 4) CD_ROWS(rows_shifted_kernel, 4);
-  else if (!shifted && vb == 16) CD_ROWS(rows_kernel, 16);
-  else if (!shifted && vb == 8) CD_ROWS(rows_kernel, 8);
-  else if (!shifted && vb == 4) CD_ROWS(rows_kernel, 4);
-  else if (!shifted && vb == 2) CD_ROWS(rows_kernel, 2);
-  else CD_INTERNAL_ERROR("no row copy kernel for this vector width");
+  else if (plain && vb == 16) CD_ROWS(rows_kernel, 16);
+  else if (plain && vb == 8) CD_ROWS(rows_kernel, 8);
+  else if (plain && vb == 4) CD_ROWS(rows_kernel, 4);
+  else if (plain && vb == 2) CD_ROWS(rows_kernel, 2);
+  else if (generic && k.es == 2) CD_GENERIC(2);
+  else if (generic && k.es == 4) CD_GENERIC(4);
+  else if (generic && k.es == 8) CD_GENERIC(8);
+  else if (generic && k.es == 16) CD_GENERIC(16);
+  else CD_INTERNAL_ERROR("no row copy or element-wise kernel for this lane width");
 #undef CD_ROWS
-  CD_CHECK_HIP(hipGetLastError());
-}
-
-void launchGenericBatch(int es, bool remote, const Batch& b, unsigned int blocks, hipStream_t stream) {
-  const dim3 grid(blocks), block(kThreads);
-  if (es == 2) {
-    if (remote) generic_kernel<2, true><<<grid, block, 0, stream>>>(b);
-    else generic_kernel<2, false><<<grid, block, 0, stream>>>(b);
-  } else if (es == 4) {
-    if (remote) generic_kernel<4, true><<<grid, block, 0, stream>>>(b);
-    else generic_kernel<4, false><<<grid, block, 0, stream>>>(b);
-  } else if (es == 8) {
-    if (remote) generic_kernel<8, true><<<grid, block, 0, stream>>>(b);
-    else generic_kernel<8, false><<<grid, block, 0, stream>>>(b);
-  } else if (es == 16) {
-    if (remote) generic_kernel<16, true><<<grid, block, 0, stream>>>(b);
-    else generic_kernel<16, false><<<grid, block, 0, stream>>>(b);
-  } else {
-    CD_INTERNAL_ERROR("no element-wise kernel for this element size");
-  }
+#undef CD_GENERIC
   CD_CHECK_HIP(hipGetLastError());
 }
 

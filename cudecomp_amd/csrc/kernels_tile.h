@@ -159,19 +159,19 @@ __global__ __launch_bounds__(kThreads) void transpose_kernel(const Batch b) {
   // fp64 permutations: 2.73 -> 2.66 ms strided-read side, 3.02 -> 2.93 ms strided-write side).
   const unsigned int nb = b.first_block[mi + 1] - b.first_block[mi];
   unsigned int lt = lb;
-  if (b.p1[mi] & 1) {
+  if (b.p1[mi] & kWalkXcd) {
     const unsigned int per = nb >> 3;
     if (lb < (per << 3)) lt = (lb & 7u) * per + (lb >> 3);
   }
   // Walk first along the tile dim that keeps the far-strided side on the same rows (same DRAM pages / TLB
   // entries): i first extends the source rows, j first extends the destination rows.
   unsigned int bi, bj, rest;
-  if (b.p1[mi] & 2) {
+  if (b.p1[mi] & kWalkJFirst) {
     // j first, optionally in RUNS (kernels.cc classify(), "far-strided destination"): p0 = R > 1 and
-    //   p1 bit 4 clear: R tiles along j, then all tile rows i, then the next R tiles along j;
-    //   p1 bit 4 set:   all tiles along j, then R consecutive batch planes, then the tile rows i, then the next R planes.
+    //   kWalkRunOverPlanes clear: R tiles along j, then all tile rows i, then the next R tiles along j;
+    //   kWalkRunOverPlanes set:   all tiles along j, then R consecutive batch planes, then the tile rows i, then the next R planes.
     const unsigned int run = (unsigned int)b.p0[mi];
-    if (run > 1 && !(b.p1[mi] & 4)) {
+    if (run > 1 && !(b.p1[mi] & kWalkRunOverPlanes)) {
       const unsigned int jlo = lt % run;
       rest = lt / run;
       bi = rest % ti_n;

@@ -24,54 +24,46 @@ namespace {
 constexpr bool SWZ = CUDECOMP_TRANSPOSE_ES != 16;  // XOR-swizzled LDS tile; 16-byte elements: padded rows
 
 template <int STREAM>
-void launchT(int variant, const Batch& b, unsigned int blocks, hipStream_t stream) {
-  const dim3 grid(blocks), block(kThreads);
+bool launchT(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) {
 #if CUDECOMP_TRANSPOSE_ES == 2
-  if (variant == 8) transpose_kernel<2, 8, 128, 128, STREAM, SWZ><<<grid, block, 0, stream>>>(b);
-  else transpose_kernel<2, 1, 64, 64, STREAM, SWZ><<<grid, block, 0, stream>>>(b);
+  CD_TILED_SHAPE(transpose_kernel, 2, 8, 128, 128, STREAM, SWZ)
+  CD_TILED_SHAPE(transpose_kernel, 2, 1, 64, 64, STREAM, SWZ)
 #elif CUDECOMP_TRANSPOSE_ES == 4
-  if (variant == 304) transpose_kernel<4, 4, 64, 128, STREAM, SWZ><<<grid, block, 0, stream>>>(b);
-  else transpose_kernel<4, 1, 64, 64, STREAM, SWZ><<<grid, block, 0, stream>>>(b);
+  CD_TILED_SHAPE(transpose_kernel, 4, 4, 64, 128, STREAM, SWZ)
+  CD_TILED_SHAPE(transpose_kernel, 4, 1, 64, 64, STREAM, SWZ)
 #elif CUDECOMP_TRANSPOSE_ES == 8
-  if (variant == 302) {
-    if constexpr (STREAM == 2) transpose_kernel<8, 2, 64, 128, 2, true><<<grid, block, 0, stream>>>(b);
-    else CD_INTERNAL_ERROR("64 x 128 tiles are instantiated for streaming moves only");
-  } else if (variant == 2) transpose_kernel<8, 2, 64, 64, STREAM, SWZ><<<grid, block, 0, stream>>>(b);
-  else transpose_kernel<8, 1, 64, 64, STREAM, SWZ><<<grid, block, 0, stream>>>(b);
+  if constexpr (STREAM == 2) {  // (the longer tiles are instantiated for streaming moves only)
+    CD_TILED_SHAPE(transpose_kernel, 8, 2, 64, 128, 2, true)
+  }
+  CD_TILED_SHAPE(transpose_kernel, 8, 2, 64, 64, STREAM, SWZ)
+  CD_TILED_SHAPE(transpose_kernel, 8, 1, 64, 64, STREAM, SWZ)
 #else
-  if (variant == 301) {
-    if constexpr (STREAM == 2) transpose_kernel<16, 1, 32, 64, 2, false><<<grid, block, 0, stream>>>(b);
-    else CD_INTERNAL_ERROR("32 x 64 tiles are instantiated for streaming moves only");
-  } else transpose_kernel<16, 1, 32, 32, STREAM, SWZ><<<grid, block, 0, stream>>>(b);
+  if constexpr (STREAM == 2) {  // (as for 8-byte elements)
+    CD_TILED_SHAPE(transpose_kernel, 16, 1, 32, 64, 2, false)
+  }
+  CD_TILED_SHAPE(transpose_kernel, 16, 1, 32, 32, STREAM, SWZ)
 #endif
-  CD_CHECK_HIP(hipGetLastError());
+  return false;
 }
 
-void launchAny(int variant, int stream_access, const Batch& b, unsigned int blocks, hipStream_t stream) {
-  if (stream_access == 4) launchT<4>(variant, b, blocks, stream);
-  else if (stream_access == 3) launchT<3>(variant, b, blocks, stream);
-  else if (stream_access == 2) launchT<2>(variant, b, blocks, stream);
-  else launchT<0>(variant, b, blocks, stream);
+void launchAny(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) {
+  const int s = streamArgOf(k.kind, k.access);
+  const bool ok = s == 4 ? launchT<4>(k, b, blocks, stream)
+                         : (s == 3 ? launchT<3>(k, b, blocks, stream) : (s == 2 ? launchT<2>(k, b, blocks, stream) : launchT<0>(k, b, blocks, stream)));
+  if (!ok) CD_INTERNAL_ERROR("no transpose kernel of this element size for this lane width, tile and access mode");
+  CD_CHECK_HIP(hipGetLastError());
 }
 
 }  // namespace
 
 #if CUDECOMP_TRANSPOSE_ES == 2
-void launchTransposeBatch2(int variant, int stream_access, const Batch& b, unsigned int blocks, hipStream_t stream) {
-  launchAny(variant, stream_access, b, blocks, stream);
-}
+void launchTransposeBatch2(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) { launchAny(k, b, blocks, stream); }
 #elif CUDECOMP_TRANSPOSE_ES == 4
-void launchTransposeBatch4(int variant, int stream_access, const Batch& b, unsigned int blocks, hipStream_t stream) {
-  launchAny(variant, stream_access, b, blocks, stream);
-}
+void launchTransposeBatch4(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) { launchAny(k, b, blocks, stream); }
 #elif CUDECOMP_TRANSPOSE_ES == 8
-void launchTransposeBatch8(int variant, int stream_access, const Batch& b, unsigned int blocks, hipStream_t stream) {
-  launchAny(variant, stream_access, b, blocks, stream);
-}
+void launchTransposeBatch8(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) { launchAny(k, b, blocks, stream); }
 #else
-void launchTransposeBatch16(int variant, int stream_access, const Batch& b, unsigned int blocks, hipStream_t stream) {
-  launchAny(variant, stream_access, b, blocks, stream);
-}
+void launchTransposeBatch16(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) { launchAny(k, b, blocks, stream); }
 #endif
 
 }  // namespace cudecomp

@@ -44,12 +44,12 @@ __global__ __launch_bounds__(NT) void transpose_window_kernel(const Batch b) {
   const unsigned int ti_n = b.t0[mi], tj_n = b.t1[mi];
   const unsigned int nb = b.first_block[mi + 1] - b.first_block[mi];
   unsigned int lt = lb;
-  if (b.p1[mi] & 1) {  // XCD-contiguous walk, see transpose_kernel
+  if (b.p1[mi] & kWalkXcd) {  // XCD-contiguous walk, see transpose_kernel
     const unsigned int per = nb >> 3;
     if (lb < (per << 3)) lt = (lb & 7u) * per + (lb >> 3);
   }
   unsigned int bi, bj, rest;
-  if (b.p1[mi] & 2) {
+  if (b.p1[mi] & kWalkJFirst) {
     bj = lt % tj_n;
     rest = lt / tj_n;
     bi = rest % ti_n;
@@ -131,27 +131,19 @@ __global__ __launch_bounds__(NT) void transpose_window_kernel(const Batch b) {
 }
 
 template <int STREAM>
-void launchWindowT(int variant, int es, const Batch& b, unsigned int blocks, hipStream_t stream) {
-  const dim3 grid(blocks), block(kThreads);
-  if (es == 4) {
-    if (variant == 4) transpose_window_kernel<4, 4, 64, 128, STREAM><<<grid, block, 0, stream>>>(b);
-    else transpose_window_kernel<4, 1, 64, 128, STREAM><<<grid, block, 0, stream>>>(b);
-  } else if (es == 8) {
-    if (variant == 2) transpose_window_kernel<8, 2, 64, 64, STREAM><<<grid, block, 0, stream>>>(b);
-    else transpose_window_kernel<8, 1, 64, 64, STREAM><<<grid, block, 0, stream>>>(b);
-  } else {
-    transpose_window_kernel<16, 1, 32, 32, STREAM><<<grid, block, 0, stream>>>(b);
-  }
-  CD_CHECK_HIP(hipGetLastError());
+bool launchWindowT(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) {
+  CD_WINDOW_SHAPES(transpose_window_kernel, STREAM)
 }
 
 }  // namespace
 }  // namespace kern
 
-void launchWindowBatch(int es, int variant, int stream_access, const kern::Batch& b, unsigned int blocks, hipStream_t stream) {
-  if (stream_access == 3) kern::launchWindowT<3>(variant, es, b, blocks, stream);
-  else if (stream_access == 4 || stream_access == 2) kern::launchWindowT<4>(variant, es, b, blocks, stream);
-  else kern::launchWindowT<0>(variant, es, b, blocks, stream);
+void launchWindowBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream) {
+  const int s = streamArgOf(k.kind, k.access);
+  const bool ok = s == 3 ? kern::launchWindowT<3>(k, b, blocks, stream)
+                         : (s == 4 ? kern::launchWindowT<4>(k, b, blocks, stream) : s == 0 && kern::launchWindowT<0>(k, b, blocks, stream));
+  if (!ok) CD_INTERNAL_ERROR("no window transpose kernel for this element size, lane width, tile and access mode");
+  CD_CHECK_HIP(hipGetLastError());
 }
 
 }  // namespace cudecomp

@@ -250,7 +250,7 @@ def test_two_runs_give_the_same_bytes():
 
 
 # ---- the grid-stride pass of the element-wise kernel -------------------------------------------------------------------------------
-# classifyAdd launches at most 8192 workgroups of 256 lanes: moves of more than 2,097,152 elements take a second pass.  Integer
+# The classifier launches at most 8192 workgroups of 256 lanes: moves of more than 2,097,152 elements take a second pass.  Integer
 # payload: these are about WHICH cells are visited -- an unvisited cell keeps its value, a cell visited twice gets the source twice.
 GRID_STRIDE = [
     ("fp16 gathered", cd.HALF, (1, 1500, 1400), (0, 3, 4503), (0, 1, 1504), "generic_accumulate_kernel<_Float16,1>"),
