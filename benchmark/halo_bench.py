@@ -2,10 +2,13 @@
 """Halo timing on one rank: the per-rank X pencil of BASELINE config 5 (2048 x 2048 x 1024 fp64 on a
 2x4 grid -> 2048 x 1024 x 256 per rank) treated as a periodic single-rank grid, so every dim exercises the
 face kernels: cudecompUpdateHalosX (periodic self copy; reference include/internal/halo.h:165-193) and, beside
-it on the same pencil, cudecompAmdAccumulateHalosX (cudecomp_amd.h: the two face additions).
+it on the same pencil, cudecompAmdAccumulateHalosX (cudecomp_amd.h: the two face additions) and, with --fill,
+cudecompAmdFillHalosX (cudecomp_amd_fill.h: the two halos set to zero).
 Per dim: `--reps` repetitions of `--calls` back-to-back calls each, ms per call of every repetition, their
 min / median / max, and GB/s of the median against the algorithmic bytes (update: 2 faces read + written,
-4 * face bytes; accumulation: 2 faces read, 2 destinations read and written, 6 * face bytes)."""
+4 * face bytes; accumulation: 2 faces read, 2 destinations read and written, 6 * face bytes; fill: 2 halos written, 2 * face
+bytes).  --fill also checks on the device that afterwards no ghost cell holds anything but zero and no interior cell changed,
+and times one contiguous 64 MiB fill with cached and with non-temporal stores (the store policy of the fill kernels)."""
 import argparse
 import json
 import os
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--update-only", action="store_true", help="time cudecompUpdateHalosX only")
+    ap.add_argument("--fill", action="store_true", help="also time cudecompAmdFillHalosX (value zero), after the other passes")
     ap.add_argument("--json", metavar="FILE", default=None, help="also write the result line to FILE")
     a = ap.parse_args()
     import torch
@@ -76,16 +80,41 @@ def main():
         rec["accumulate"] = _record(ms, 6 * faces[dim] * 8)
         rec["accumulate_kernel"] = cd.cudecompExtLastKernelName()
         rec["accumulate_over_update"] = round(rec["accumulate"]["median_ms"] / rec["update"]["median_ms"], 3)
+    extra = {}
+    if a.fill:
+        data.fill_(1.0)  # the fills store zero: what they wrote, and only that, shows afterwards
+        for dim in range(3):
+            rec = res["dim%d" % dim]
+            ms = _time(lambda: cd.cudecompFillHalos(0, h, gd, data.data_ptr(), cd.DOUBLE, halo, (1, 1, 1), dim, stream=st), a.reps, a.calls)
+            rec["fill"] = _record(ms, 2 * faces[dim] * 8)
+            rec["fill_kernel"] = cd.cudecompExtLastKernelName()
+            rec["fill_over_update"] = round(rec["fill"]["median_ms"] / rec["update"]["median_ms"], 3)
+        cells = data.view(shape[2], shape[1], shape[0])
+        interior = cells[a.halo:shape[2] - a.halo, a.halo:shape[1] - a.halo, a.halo:shape[0] - a.halo]
+        inside = int(torch.count_nonzero(interior))
+        extra["ghost_cells_not_zero"] = int(torch.count_nonzero(cells)) - inside
+        extra["interior_cells_changed"] = interior.numel() - inside
+        # store policy: one contiguous 64 MiB move, cached (force bit 2) against non-temporal (what the size rule picks)
+        n = (64 << 20) // 8
+        policy = {}
+        for name, force in (("cached", 4), ("non_temporal", 0), ("cached_again", 4), ("non_temporal_again", 0)):
+            ms = _time(lambda: cd.cudecompExtFill3D(data.data_ptr(), 8, None, (n, 1, 1), (1, 0, 0), force, st), a.reps, a.calls)
+            policy[name] = dict(_record(ms, n * 8), kernel=cd.cudecompExtLastKernelName())
+        extra["store_policy_64MiB"] = policy
     cd.cudecompFree(h, gd, work)
     cd.cudecompGridDescDestroy(h, gd)
-    line = json.dumps({"workload": "X pencil 2048x1024x256 fp64 + halo %d, periodic single rank, per dim: update (self copy) and "
-                                   "accumulation (self add); %d repetitions of %d calls" % (a.halo, a.reps, a.calls),
-                       "device": torch.cuda.get_device_name(0), "result": res})
+    line = json.dumps(dict({"workload": "X pencil 2048x1024x256 fp64 + halo %d, periodic single rank, per dim: update (self copy), "
+                                        "accumulation (self add)%s; %d repetitions of %d calls"
+                                        % (a.halo, " and fill (zero)" if a.fill else "", a.reps, a.calls),
+                            "device": torch.cuda.get_device_name(0), "result": res}, **extra))
     print(line)
     if a.json:
         with open(a.json, "w") as f:
             f.write(line + "\n")
     cd.cudecompFinalize(h)
+    if extra.get("ghost_cells_not_zero") or extra.get("interior_cells_changed"):
+        sys.exit("halo_bench.py: after the fills %d ghost cells are not zero and %d interior cells changed"
+                 % (extra["ghost_cells_not_zero"], extra["interior_cells_changed"]))
 
 
 if __name__ == "__main__":

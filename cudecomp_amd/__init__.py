@@ -144,9 +144,12 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtPlanTranspose", "cudecompExtPlanHalo", "cudecompExtPencilInfo", "cudecompExtShiftedRank",
                "cudecompExtWorkspaceSizes", "cudecompExtGetLinkInfo", "cudecompExtLastKernelName",
                "cudecompExtRunLocalPhases", "cudecompExtEstimateCycleMs", "cudecompExtTrimWorkspacePool", "cudecompExtPlanRelay", "cudecompExtQueueCensus",
-               "cudecompExtDescribeMove", "cudecompExtRotateWalk", "cudecompExtPlanHaloAccumulate", "cudecompExtAccumulate3D"]
+               "cudecompExtDescribeMove", "cudecompExtRotateWalk", "cudecompExtPlanHaloAccumulate", "cudecompExtAccumulate3D",
+               "cudecompExtPlanHaloFill", "cudecompExtFill3D"]
 # include/cudecomp_amd.h: extensions of the API a solver may use
 AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
+# include/cudecomp_amd_fill.h: halo fill
+AMD_FILL_SYMBOLS = ["cudecompAmdFillHalosX", "cudecompAmdFillHalosY", "cudecompAmdFillHalosZ"]
 
 
 class ExtTransposeTimings(C.Structure):
@@ -205,6 +208,8 @@ def lib():
             getattr(L, name).argtypes = [vp, vp, vp, vp, vp, i32, pi32, pi32, pi32, pi32, vp]
         for name in ("cudecompUpdateHalosX", "cudecompUpdateHalosY", "cudecompUpdateHalosZ") + tuple(AMD_SYMBOLS):
             getattr(L, name).argtypes = [vp, vp, vp, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
+        for name in AMD_FILL_SYMBOLS:  # (the update's arguments without `work`, plus the value)
+            getattr(L, name).argtypes = [vp, vp, vp, i32, vp, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         L.cudecompExtGetTransposePlan.argtypes = [vp, vp, i32, pi32, pi32, pi32, pi32, C.c_bool, i32,
                                                   C.POINTER(ExtTransposePlan)]
         L.cudecompExtGetHaloPlan.argtypes = [vp, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32,
@@ -227,6 +232,8 @@ def lib():
                                           C.POINTER(ExtHaloPlan)]
         L.cudecompExtPlanHaloAccumulate.argtypes = L.cudecompExtPlanHalo.argtypes
         L.cudecompExtAccumulate3D.argtypes = [vp, vp, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, pi32, vp]
+        L.cudecompExtPlanHaloFill.argtypes = L.cudecompExtPlanHalo.argtypes
+        L.cudecompExtFill3D.argtypes = [vp, i32, vp, C.POINTER(i64), C.POINTER(i64), i32, pi32, vp]
         L.cudecompExtGetLinkInfo.argtypes = [vp, C.POINTER(ExtLinkInfo)]
         L.cudecompExtEstimateCycleMs.argtypes = [vp, C.POINTER(ExtGridSpec), i32, i32, i32, i32, C.POINTER(C.c_double)]
         L.cudecompExtRunLocalPhases.argtypes = [C.POINTER(ExtGridSpec), i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]
@@ -372,6 +379,23 @@ def cudecompAccumulateHalos(axis, handle, gd, inp, work, dtype, halo_extents, ha
            "cudecompAmdAccumulateHalos" + "XYZ"[axis])
 
 
+def _value_bytes(value):
+    """bytes of one element: bytes as given, a numpy scalar's own; None stays None (zero bytes)"""
+    if value is None or isinstance(value, (bytes, bytearray)):
+        return None if value is None else bytes(value)
+    return value.tobytes()
+
+
+def cudecompFillHalos(axis, handle, gd, inp, dtype, halo_extents, halo_periods, dim, padding=None, value=None, stream=None):
+    """cudecompAmdFillHalos{X,Y,Z} (cudecomp_amd_fill.h): the ghost cells the update along `dim` would write receive `value`
+    (bytes or a numpy scalar of one element of `dtype`; None: zero bytes)."""
+    name = "cudecompAmdFillHalos" + "XYZ"[axis]
+    v = _value_bytes(value)
+    if v is not None and len(v) != cudecompGetDataTypeSize(dtype):
+        raise ValueError("value holds %d bytes, one element of the data type has %d" % (len(v), cudecompGetDataTypeSize(dtype)))
+    _check(getattr(lib(), name)(handle, gd, inp, dtype, v, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding), stream), name)
+
+
 def cudecompExtGetTransposePlan(handle, gd, op, in_halo=None, out_halo=None, in_pad=None, out_pad=None, inplace=False,
                                 backend_override=0):
     p = ExtTransposePlan()
@@ -442,6 +466,14 @@ def cudecompExtPlanHaloAccumulate(grid, rank, axis, halo_extents, halo_periods, 
     p = ExtHaloPlan()
     _check(lib().cudecompExtPlanHaloAccumulate(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim,
                                                _i3(padding), int(force_packed), C.byref(p)), "cudecompExtPlanHaloAccumulate")
+    return p
+
+
+def cudecompExtPlanHaloFill(grid, rank, axis, halo_extents, halo_periods, dim, padding=None, force_packed=False):
+    """Stateless planner of cudecompAmdFillHalos*; ExtHaloPlan.reserved bit 8 marks a fill plan (cudecomp_ext.h)."""
+    p = ExtHaloPlan()
+    _check(lib().cudecompExtPlanHaloFill(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim,
+                                         _i3(padding), int(force_packed), C.byref(p)), "cudecompExtPlanHaloFill")
     return p
 
 
@@ -533,6 +565,18 @@ def cudecompExtAccumulate3D(src, dst, dtype, extent, ss, ds, force_generic=0, st
     a = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
     _check(lib().cudecompExtAccumulate3D(src, dst, dtype, a(extent), a(ss), a(ds), int(force_generic), C.byref(cls), stream),
            "cudecompExtAccumulate3D")
+    return cls.value
+
+
+def cudecompExtFill3D(dst, es, value, extent, ds, force=0, stream=None):
+    """One fill-move (dst = value; bytes, a numpy scalar or None) through the kernel layer; returns the kernel class
+    (0 rows, 2 generic)."""
+    cls = C.c_int32(-1)
+    a = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
+    v = _value_bytes(value)
+    if v is not None and len(v) != es:
+        raise ValueError("value holds %d bytes, the element size is %d" % (len(v), es))
+    _check(lib().cudecompExtFill3D(dst, es, v, a(extent), a(ds), int(force), C.byref(cls), stream), "cudecompExtFill3D")
     return cls.value
 
 

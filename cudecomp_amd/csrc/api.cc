@@ -624,6 +624,7 @@ cudecompResult_t cudecompGridDescCreateVersioned(cudecompHandle_t handle, cudeco
     gd->relay_plans.clear();
     gd->halo_plans.clear();
     gd->halo_accumulate_plans.clear();
+    gd->halo_fill_plans.clear();
     perfReset(gd);  // autotuning trials are not part of the user's performance report
 
     *grid_desc_out = gd;
@@ -864,5 +865,33 @@ CD_DEFINE_HALO(cudecompUpdateHalosZ, false, 2)
 CD_DEFINE_HALO(cudecompAmdAccumulateHalosX, true, 0)
 CD_DEFINE_HALO(cudecompAmdAccumulateHalosY, true, 1)
 CD_DEFINE_HALO(cudecompAmdAccumulateHalosZ, true, 2)
+
+// cudecomp_amd_fill.h: the ghost cells an update would write receive one value.  The checks of haloEntry, in its order, without `work`.
+static cudecompResult_t haloFillEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
+                                      cudecompDataType_t dtype, const void* value, const int32_t halo_extents[],
+                                      const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {
+  try {
+    checkHandle(handle);
+    checkGridDesc(handle, grid_desc);
+    checkDataType(dtype);
+    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
+    if (halo_extents[0] == 0 && halo_extents[1] == 0 && halo_extents[2] == 0) return CUDECOMP_RESULT_SUCCESS;
+    if (!input) CD_INVALID_USAGE("input argument cannot be null");
+    if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
+    runHaloFill(handle, grid_desc, axis, input, dtype, value, halo_extents, halo_periods, dim, padding, stream);
+  }
+  CD_API_CATCH()
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+#define CD_DEFINE_HALO_FILL(NAME, AXIS)                                                                                   \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,     \
+                        const void* value, const int32_t halo_extents[], const bool halo_periods[], int32_t dim,          \
+                        const int32_t padding[], hipStream_t stream) {                                                    \
+    return haloFillEntry(AXIS, handle, grid_desc, input, dtype, value, halo_extents, halo_periods, dim, padding, stream); \
+  }
+CD_DEFINE_HALO_FILL(cudecompAmdFillHalosX, 0)
+CD_DEFINE_HALO_FILL(cudecompAmdFillHalosY, 1)
+CD_DEFINE_HALO_FILL(cudecompAmdFillHalosZ, 2)
 
 }  // extern "C"

@@ -102,6 +102,7 @@ void exportHaloPlan(const HaloPlan& p, cudecompExtHaloPlan_t* out) {
       for (size_t i = 0; i < p.post.size(); ++i)
         if (p.post[i].add) out->reserved |= 64 << i;
     }
+    if (p.fill) out->reserved = 256;
 }
 
 GridShape shapeFromSpec(const cudecompExtGridSpec_t* spec) {
@@ -319,6 +320,26 @@ cudecompResult_t cudecompExtPlanHaloAccumulate(const cudecompExtGridSpec_t* grid
     const bool none[3] = {false, false, false};
     const HaloPlan p =
         buildHaloAccumulatePlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, force_packed != 0);
+    exportHaloPlan(p, out);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtPlanHaloFill(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
+                                         const bool periods[], int32_t dim, const int32_t pad[], int32_t force_packed,
+                                         cudecompExtHaloPlan_t* out) {
+  try {
+    const GridShape g = shapeFromSpec(grid);
+    if (!out || !halo) CD_INVALID_USAGE("null argument");
+    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
+    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
+    const int32_t zero[3] = {0, 0, 0};
+    const bool none[3] = {false, false, false};
+    const HaloPlan p = buildHaloFillPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, force_packed != 0);
     exportHaloPlan(p, out);
   } catch (const Error& e) {
     return fail(e);
@@ -654,6 +675,39 @@ cudecompResult_t cudecompExtAccumulate3D(const void* src, void* dst, cudecompDat
     if (force_generic & 2) t.force_streaming = true;
     KernelStats st;
     launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, arithOf(dtype));
+    if (kernel_class) {
+      *kernel_class = -1;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
+        if (st.launches[c]) *kernel_class = c;
+    }
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtFill3D(void* dst, int32_t es, const void* value, const int64_t extent[3], const int64_t ds[3],
+                                   int32_t force, int32_t* kernel_class, hipStream_t stream) {
+  try {
+    if (!dst || !extent || !ds) CD_INVALID_USAGE("null argument");
+    if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
+    Move3D m;
+    m.src_buf = BUF_IN;
+    m.dst_buf = BUF_OUT;
+    m.fill = true;
+    for (int i = 0; i < 3; ++i) {
+      m.extent[i] = extent[i];
+      m.ds[i] = ds[i];
+    }
+    void* bufs[3] = {nullptr, dst, nullptr};
+    KernelTuning t;
+    if (force & 1) t.force_class = MOVE_GENERIC;
+    if (force & 2) t.force_streaming = true;
+    if (force & 4) t.no_streaming = true;
+    KernelStats st;
+    launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, ARITH_NONE, value);
     if (kernel_class) {
       *kernel_class = -1;
       for (int c = 0; c < MOVE_CLASS_COUNT; ++c)

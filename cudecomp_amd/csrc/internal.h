@@ -13,6 +13,7 @@
 #include "bootstrap.h"
 #include "cudecomp.h"
 #include "cudecomp_amd.h"
+#include "cudecomp_amd_fill.h"
 #include "decomp.h"
 #include "errors.h"
 #include "kernels.h"
@@ -135,6 +136,7 @@ struct cudecompGridDesc {
   using HaloKey = std::tuple<int, int, std::array<int32_t, 6>, std::array<bool, 3>, bool>;
   std::map<HaloKey, cudecomp::HaloPlan> halo_plans;
   std::map<HaloKey, cudecomp::HaloPlan> halo_accumulate_plans;  // cudecompAmdAccumulateHalos*: the same key, the other operation
+  std::map<HaloKey, cudecomp::HaloPlan> halo_fill_plans;        // cudecompAmdFillHalos*: likewise
 
   // CUDECOMP_ENABLE_CUDA_GRAPHS=1: the per-peer pack loop of the pipelined backends (one kernel + one event
   // record per destination) is captured once per (plan, buffers, element size) and replayed as one graph launch
@@ -258,6 +260,8 @@ void runHalo(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* inp
 void runHaloAccumulate(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, void* work,
                        cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
                        hipStream_t stream);
+void runHaloFill(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, const void* value,
+                 const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream);
 
 // perf.cc
 struct TransposeTimings {

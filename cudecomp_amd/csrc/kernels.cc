@@ -2,12 +2,12 @@
 //
 // A move is normalised (unit dims dropped, contiguous dims fused, dims sorted by source stride) and classified: classify()
 // writes WHAT runs into one KernelChoice (kernels_batch.h: the kind of kernel -- row copy plain / shifted / dense, LDS-tiled
-// transposition plain / window / lines / row lines, element-wise, the two additions -- element size, lane width, tile, access
-// mode) and HOW it walks into the Batch fields beside it.  Moves with equal choices are batched (up to kMaxBatch moves, e.g.
+// transposition plain / window / lines / row lines, element-wise, the two additions, the two fills -- element size, lane width,
+// tile, access mode) and HOW it walks into the Batch fields beside it.  Moves with equal choices are batched (up to kMaxBatch moves, e.g.
 // the per-peer pack copies of one transpose, share one launch; the descriptors travel in the kernel argument segment).  The
 // batching key, the launcher's instantiation and the kernel's name all come from that one record.  The kernels live in
 // kernels_rows.hip, kernels_transpose.hip (one code object per element size), kernels_window.hip, kernels_lines.hip,
-// kernels_rowlines.hip and kernels_accumulate.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
+// kernels_rowlines.hip, kernels_accumulate.hip and kernels_fill.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
 // transpose.cc.  kernels_batch.h says why they are separate code objects.
 //
 // 2-byte elements (fp16, bf16) take the row copy (plain kernel), the LDS-tiled transposition (128 x 128 tiles with 16-byte
@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "errors.h"
@@ -47,7 +48,7 @@ struct Classified {
 constexpr long long kDenseMaxGapBytes = 512;  // widest gap between rows the dense row copy rewrites (halo + padding cells)
 
 MoveClass classOf(KernelKind kind) {
-  if (kind == K_GENERIC || kind == K_GENERIC_ADD) return MOVE_GENERIC;
+  if (kind == K_GENERIC || kind == K_GENERIC_ADD || kind == K_GENERIC_FILL) return MOVE_GENERIC;
   return kind >= K_TRANSPOSE && kind <= K_TRANSPOSE_ROWLINES ? MOVE_TRANSPOSE : MOVE_ROWS_VEC;
 }
 
@@ -336,12 +337,40 @@ void classifyTranspose(Classified& c, const Move3D& in, const Move3D& m, int t, 
   }
 }
 
+// Fill-moves (Move3D::fill): rows whose fastest dim is contiguous in the destination, or element by element; nothing else.
+// The row kernel lays its lanes on the destination's 16-byte grid, from the boundary below each row's start: e[0] = the most
+// 16-byte slots a row can touch at any phase (addresses are 2-byte aligned at least), ss[0] = the row length in bytes.
+void classifyFill(Classified& c, const Move3D& m, const KernelTuning& tuning, bool streaming) {
+  const int es = c.k.es;
+  c.dm.src = nullptr;
+  if (tuning.force_class != MOVE_GENERIC && m.ds[0] <= 1) {
+    c.k.kind = K_ROWS_FILL;
+    c.k.vec = 16;
+    c.k.access = streaming ? 1 : 0;
+    const long long row_bytes = m.extent[0] * es;
+    c.dm.e[0] = (row_bytes + 14 + 15) / 16;
+    c.dm.e[1] = m.extent[1];
+    c.dm.e[2] = m.extent[2];
+    c.dm.ss[0] = row_bytes;
+    for (int i = 1; i < 3; ++i) c.dm.ds[i] = m.ds[i] * es;
+    rowTiles(c);
+    return;
+  }
+  c.k.kind = K_GENERIC_FILL;
+  c.k.access = 0;  // (always cached stores)
+  genericGeometry(c, m);
+}
+
 // Copy moves take any kind of kernel.  Add-moves (Move3D::add, `arith` their real type) take the row geometry of the copy
 // (same extent / address / stride rule) or the element-wise one and nothing else: never shifted, dense or transposing forms
 // (only the cells of the move are touched), never a remote destination, never lanes narrower than one real.
 Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelTuning& tuning, void* dst_base, bool remote,
                     ArithType arith) {
   Move3D m = in;
+  if (in.fill) {  // no source: nothing but the destination decides the order and the fusion of the dims
+    if (in.add || in.dst_row_pitch != 0 || remote) CD_INTERNAL_ERROR("fill-moves only store the cells of a local destination");
+    for (int i = 0; i < 3; ++i) m.ss[i] = m.ds[i];
+  }
   normalizeMove(m);
   const bool add = in.add;
   if (add) {
@@ -360,6 +389,10 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
   else c.k.access = remote ? 3 : (streaming ? 2 : 0);  // (a peer's memory: write-through stores, whatever the size)
   c.dm.src = static_cast<const char*>(bufs[m.src_buf]) + m.src_off * es;
   c.dm.dst = static_cast<char*>(dst_base ? dst_base : bufs[m.dst_buf]) + m.dst_off * es;
+  if (in.fill) {
+    classifyFill(c, m, tuning, streaming);
+    return c;
+  }
   const bool force_generic = tuning.force_class == MOVE_GENERIC;
 
   if (!force_generic && m.ss[0] <= 1 && m.ds[0] <= 1) {
@@ -418,10 +451,27 @@ void spellKernelName(const KernelChoice& k) {
     case K_GENERIC: snprintf(out, n, "generic_kernel<%d,%s>", k.es, s == 3 ? "true" : "false"); break;
     case K_ROWS_ADD: snprintf(out, n, "rows_accumulate_kernel<%s,%d,%d>", arithName(k.arith), k.vec, s); break;
     case K_GENERIC_ADD: snprintf(out, n, "generic_accumulate_kernel<%s,%d>", arithName(k.arith), k.es / arithBytes(k.arith)); break;
+    case K_ROWS_FILL: snprintf(out, n, "rows_fill_kernel<%d,%d>", k.vec, s); break;
+    case K_GENERIC_FILL: snprintf(out, n, "generic_fill_kernel<%d>", k.es); break;
   }
 }
 
-void launchBatch(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) {
+// The 16 bytes a fill stores into every 16-byte-aligned slot of its destination: byte i of a slot lies (i - a) mod es into an
+// element, a = the address of any cell of the move (all are congruent mod es).  For naturally aligned pencils this is the
+// element replicated; a destination that is only aligned to half its element (the C alignment of the complex types) gets the
+// rotated pattern and the same stores.  The moves of one launch lie whole elements apart (base + offset * es), so one pattern
+// serves them all.
+FillPattern fillPatternOf(const void* value, int es, const void* cell) {
+  unsigned char v[16] = {0}, bytes[16];
+  if (value) std::memcpy(v, value, es);
+  const int a = (int)(reinterpret_cast<uintptr_t>(cell) % (uintptr_t)es);
+  for (int i = 0; i < 16; ++i) bytes[i] = v[((i - a) % es + es) % es];
+  FillPattern p;
+  std::memcpy(p.w, bytes, 16);
+  return p;
+}
+
+void launchBatch(const KernelChoice& k, const Batch& b, const void* fill_value, unsigned int blocks, hipStream_t stream) {
   spellKernelName(k);
   switch (k.kind) {
     case K_ROWS:
@@ -439,6 +489,8 @@ void launchBatch(const KernelChoice& k, const Batch& b, unsigned int blocks, hip
     case K_TRANSPOSE_ROWLINES: launchRowLinesBatch(k, b, blocks, stream); break;
     case K_ROWS_ADD:
     case K_GENERIC_ADD: launchAccumulateBatch(k, b, blocks, stream); break;
+    case K_ROWS_FILL:
+    case K_GENERIC_FILL: launchFillBatch(k, b, fillPatternOf(fill_value, k.es, b.m[0].dst), blocks, stream); break;
   }
 }
 
@@ -465,7 +517,8 @@ void describeMove(const Move3D& m, const void* src, void* dst, int es, const Ker
 }
 
 void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
-                 const KernelTuning* tuning, KernelStats* stats, void* const* dst_base_override, ArithType arith) {
+                 const KernelTuning* tuning, KernelStats* stats, void* const* dst_base_override, ArithType arith,
+                 const void* fill_value) {
   const bool remote = dst_base_override != nullptr;
   const KernelTuning& t = tuning ? *tuning : kDefaultTuning;
   if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
@@ -512,7 +565,7 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
         blocks = widest * b.n;
       }
     }
-    launchBatch(cs[i].k, b, (unsigned int)blocks, stream);
+    launchBatch(cs[i].k, b, fill_value, (unsigned int)blocks, stream);
     if (stats) stats->launches[cls] += 1;
   }
 }

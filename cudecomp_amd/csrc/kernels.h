@@ -37,10 +37,13 @@ struct KernelTuning {
 // Copy moves (Move3D::add == false) need nothing else.  Add-moves (dst += src; kernels_accumulate.hip) need `arith`, the real
 // type the elements consist of (arithOf(dtype), internal.h), and a local destination; they run as row or element-wise
 // additions over exactly the cells of the move -- never the transposing, shifted, dense or window forms.
+// Fill-moves (Move3D::fill: dst = value; kernels_fill.hip) take `fill_value`, one element of `es` bytes read before the call
+// returns (nullptr: all-zero bytes), and a local destination; they run as row or element-wise fills that store exactly the
+// cells of the move and load nothing.
 void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
                  const KernelTuning* tuning = nullptr, KernelStats* stats = nullptr,
                  void* const* dst_base_override = nullptr,  // per-move destination base (remote buffers)
-                 ArithType arith = ARITH_NONE);
+                 ArithType arith = ARITH_NONE, const void* fill_value = nullptr);
 
 // How a move WOULD run (no launch, no device needed): class, kernel variant, tile, tile counts, walk parameters, access mode.
 // out[10] = {class, variant, tile_i (row copies: 0 plain / 1 shifted / 2 dense kernel), tile_j, tiles_i, tiles_j, batch, p0 (run length), p1 (walk bits: 1 XCD-contiguous, 2 j first,

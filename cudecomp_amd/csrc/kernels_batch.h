@@ -1,7 +1,7 @@
 // kernels_batch.h -- what csrc/kernels.cc (host: classification, batching) and the kernel code objects share: the record of a
 // kernel choice (KernelChoice), the launch descriptor (Batch) and the launchers.  The code objects the classifier dispatches
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
-// kernels_rowlines.hip, kernels_accumulate.hip; kernels_rotate.hip and sync.hip are launched by the executor.
+// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip; kernels_rotate.hip and sync.hip are launched by the executor.
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
 // code object beyond roughly 0.6-0.7 MB puts the whole process into a regime where every small synchronous operation costs
@@ -30,7 +30,7 @@ struct DevMove {
   const char* src;
   char* dst;
   long long e[3];   // extents   (units depend on the kernel, see the launchers)
-  long long ss[3];  // src strides
+  long long ss[3];  // src strides (rows_fill_kernel, which has no source: ss[0] = row length in bytes)
   long long ds[3];  // dst strides
 };
 
@@ -51,6 +51,7 @@ struct Batch {
   //                              rows_dense_kernel reads neither
   //   transposes                 p0 = run length of the tile walk (tiles or planes; 0 / 1 = no runs), p1 = kWalk* bits
   //   element-wise               p0 = the dim the lanes run along, p1 unused
+  //   fills                      p0 as for rows / element-wise; p1 unused
   int p0[kMaxBatch];
   int p1[kMaxBatch];
   unsigned int first_block[kMaxBatch + 1];
@@ -73,7 +74,9 @@ enum KernelKind {
   K_TRANSPOSE_ROWLINES,  // transpose_rowlines_kernel: the tile's own rows are the adjacent ones (128-byte units)
   K_GENERIC,             // generic_kernel
   K_ROWS_ADD,            // rows_accumulate_kernel (dst += src)
-  K_GENERIC_ADD          // generic_accumulate_kernel
+  K_GENERIC_ADD,         // generic_accumulate_kernel
+  K_ROWS_FILL,           // rows_fill_kernel (dst = value): lanes on the destination's 16-byte grid
+  K_GENERIC_FILL         // generic_fill_kernel
 };
 struct KernelChoice {
   KernelKind kind;
@@ -81,7 +84,8 @@ struct KernelChoice {
   int vec;          // row and element-wise kinds: bytes per lane; transposes: elements per lane (1 = element-wise lanes)
   int ti, tj;       // transposes: the tile (elements, i x j); 0 otherwise
   int access;       // copies: 0 default caching, 2 non-temporal loads + stores, 3 non-temporal loads + remote (system-scope
-                    // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads
+                    // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads;
+                    // fills: 0, 1 non-temporal stores
   ArithType arith;  // additions: the real type the elements consist of; ARITH_NONE otherwise
   bool operator==(const KernelChoice& o) const {
     return kind == o.kind && es == o.es && vec == o.vec && ti == o.ti && tj == o.tj && access == o.access && arith == o.arith;
@@ -93,6 +97,8 @@ constexpr int kLinesUnitBytes = 128;  // alignment unit of the lines and row-lin
 inline int streamArgOf(KernelKind kind, int access) {
   if (kind == K_TRANSPOSE || kind == K_ROWS_ADD) return access;
   if (kind == K_GENERIC || kind == K_GENERIC_ADD) return access == 3 ? 3 : 0;
+  if (kind == K_ROWS_FILL) return access;
+  if (kind == K_GENERIC_FILL) return 0;
   if (kind == K_TRANSPOSE_WINDOW || kind == K_TRANSPOSE_LINES || kind == K_TRANSPOSE_ROWLINES)
     return access == 2 ? 4 : access;  // always cached loads: the overlap rows of neighbouring windows hit in L2
   return access == 3 ? 3 : (access >= 1 ? 1 : 0);  // row copies: loads and stores stream together
@@ -112,6 +118,13 @@ void launchLinesBatch(const KernelChoice& k, const kern::Batch& b, unsigned int 
 void launchRowLinesBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // kernels_accumulate.hip: add-moves (dst += src).  Rows: the Batch of rows_kernel.  Generic: extents / strides in elements.
 void launchAccumulateBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+// kernels_fill.hip: fill-moves (dst = value).  `pattern`: the 16 bytes every 16-byte-aligned slot of the destination receives
+// -- the element replicated; it travels as a kernel argument of its own.  Rows: e[0] = 16-byte slots per row (upper bound),
+// ss[0] = row bytes, ds[1], ds[2] in bytes.  Generic: extents / strides in elements.
+struct FillPattern {
+  unsigned int w[4];
+};
+void launchFillBatch(const KernelChoice& k, const kern::Batch& b, const FillPattern& pattern, unsigned int blocks, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

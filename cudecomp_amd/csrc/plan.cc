@@ -393,6 +393,51 @@ HaloPlan buildHaloAccumulatePlan(const GridShape& g, int rank, int axis, int dim
   return p;
 }
 
+HaloPlan buildHaloFillPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                           const int32_t* pad, bool force_packed, bool self_exchange) {
+  const HaloPlan u = buildHaloPlan(g, rank, axis, dim, halo, periods, pad, force_packed, self_exchange);  // (its refusals)
+  HaloPlan p;
+  p.axis = axis;
+  p.dim = dim;
+  p.fill = true;
+  p.comm_axis = u.comm_axis;
+  p.neighbor[0] = u.neighbor[0];
+  p.neighbor[1] = u.neighbor[1];
+  p.face_elements = u.face_elements;
+  if (u.kind == HaloPlan::NONE) return p;
+  auto filling = [](const Move3D& w) {  // the destination of `w`, nothing else
+    Move3D m;
+    m.src_buf = BUF_IN;
+    m.dst_buf = BUF_IN;
+    m.dst_off = w.dst_off;
+    for (int i = 0; i < 3; ++i) {
+      m.extent[i] = w.extent[i];
+      m.ds[i] = w.ds[i];
+    }
+    m.peer = w.peer;
+    m.fill = true;
+    return m;
+  };
+  if (u.kind == HaloPlan::DIRECT) {  // what arrives lands in the pencil itself: whole contiguous faces
+    for (int i = 0; i < 2; ++i) {
+      if (u.neighbor[i] == -1) continue;
+      Move3D w;
+      w.dst_off = u.recv_off[i];
+      w.extent[0] = u.face_elements;
+      w.ds[0] = 1;
+      w.peer = i;
+      p.pre.push_back(filling(w));
+    }
+  } else {
+    for (const Move3D& w : (u.kind == HaloPlan::SELF_PERIODIC ? u.pre : u.post)) {
+      if (w.dst_buf != BUF_IN) CD_INTERNAL_ERROR("a halo update writes its pencil from outside the plan's last phase");
+      p.pre.push_back(filling(w));
+    }
+  }
+  p.kind = HaloPlan::SELF_PERIODIC;
+  return p;
+}
+
 int normalizeMove(Move3D& m) {
   struct D {
     i64 e, s, d;

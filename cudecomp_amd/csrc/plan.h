@@ -42,6 +42,10 @@ struct Move3D {
   // type (halo accumulation, buildHaloAccumulatePlan): the kernel layer reads and rewrites exactly the destination cells of
   // the move -- never the gap cells between rows, never a peer's memory.
   bool add = false;
+  // true: dst = the call's fill value (halo fill, buildHaloFillPlan).  The move has a destination only -- the source fields stay
+  // zero and nothing is loaded -- and the kernel layer stores exactly the destination cells of the move: never the gap cells
+  // between rows (dst_row_pitch is never set), never a peer's memory.
+  bool fill = false;
 
   i64 elements() const { return extent[0] * extent[1] * extent[2]; }
 };
@@ -154,6 +158,7 @@ struct HaloPlan {
   // accumulation plans (buildHaloAccumulatePlan) only
   bool accumulate = false;
   bool ordered = false;  // the destinations of the two add-moves overlap (interior narrower than two halos): one launch each, in order
+  bool fill = false;     // fill plans (buildHaloFillPlan) only
 };
 
 HaloPlan buildHaloPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
@@ -168,6 +173,15 @@ HaloPlan buildHaloPlan(const GridShape& g, int rank, int axis, int dim, const in
 // arrives must be added, not stored.  The workspace layout is buildHaloPlan's (haloWorkspaceElements covers it).
 HaloPlan buildHaloAccumulatePlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
                                  const int32_t* pad, bool force_packed, bool self_exchange = false);
+
+// Halo FILL along `dim`: the cells the update along `dim` writes (low halo where there is a low neighbour, high halo where there
+// is a high one; include/cudecomp_amd_fill.h has the contract) receive one value.  Same arguments and refusals as buildHaloPlan,
+// from which the destinations are taken -- the pencil destinations of its wrap copies (SELF_PERIODIC) or unpacks (PACKED), its
+// receive ranges (DIRECT: whole contiguous faces) -- so "the cells the update writes" holds by construction.  Kinds: NONE or
+// SELF_PERIODIC (the word for "local": nothing is exchanged whatever the update's kind).  `pre` holds at most two fill-moves
+// (Move3D::fill), the low side then the high side, destination only, in BUF_IN; their cells never overlap.
+HaloPlan buildHaloFillPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                           const int32_t* pad, bool force_packed, bool self_exchange = false);
 
 // Number of stages every member of the communicator arrives at without talking: at most `wanted`, at most the smallest
 // chunk extent, at most 14 (flag steps), and no stage smaller than `min_stage_bytes` of the largest pencil (below that the extra

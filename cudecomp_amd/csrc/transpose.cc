@@ -520,4 +520,29 @@ void runHaloAccumulate(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void
   launch(plan.post);
 }
 
+// Halo fill (cudecompAmdFillHalos*): the cells the update would write receive `value`, both sides in one launch.  Local: no
+// workspace, no exchange.  The key carries force_packed because the destinations are taken from the update's own plan.
+void runHaloFill(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, const void* value,
+                 const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
+  const int es = elementSize(dtype);
+  const bool force_packed = usesPeerTransport(h, gd->config.halo_comm_backend);
+
+  const auto hh = arr3(halo), pp = arr3(pad);
+  std::array<bool, 3> per{false, false, false};
+  if (periods)
+    for (int i = 0; i < 3; ++i) per[i] = periods[i];
+  const cudecompGridDesc::HaloKey key{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, force_packed};
+  auto it = gd->halo_fill_plans.find(key);
+  if (it == gd->halo_fill_plans.end()) {
+    HaloPlan p = buildHaloFillPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), force_packed, h->self_exchange);
+    it = gd->halo_fill_plans.emplace(key, std::move(p)).first;
+  }
+  const HaloPlan& plan = it->second;
+  if (plan.kind == HaloPlan::NONE) return;
+
+  ensureDevice(h);
+  void* bufs[3] = {input, input, nullptr};
+  launchMoves(plan.pre.data(), (int)plan.pre.size(), bufs, es, stream, &h->tuning, nullptr, nullptr, ARITH_NONE, value);
+}
+
 }  // namespace cudecomp

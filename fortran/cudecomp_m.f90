@@ -444,6 +444,55 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompAmdAccumulateHalosZ_C
 
+    ! cudecomp_amd_fill.h: halo fill (the ghost cells an update would write receive one value)
+    function cudecompAmdFillHalosX_C(handle, grid_desc, input, dtype, value, halo_extents, halo_periods, dim, &
+                                     padding, stream) bind(C, name="cudecompAmdFillHalosX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      type(c_ptr), value :: value
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdFillHalosX_C
+
+    function cudecompAmdFillHalosY_C(handle, grid_desc, input, dtype, value, halo_extents, halo_periods, dim, &
+                                     padding, stream) bind(C, name="cudecompAmdFillHalosY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      type(c_ptr), value :: value
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdFillHalosY_C
+
+    function cudecompAmdFillHalosZ_C(handle, grid_desc, input, dtype, value, halo_extents, halo_periods, dim, &
+                                     padding, stream) bind(C, name="cudecompAmdFillHalosZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      type(c_ptr), value :: value
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdFillHalosZ_C
+
     function cudecomp_c_strlen(str) bind(C, name="strlen") result(n)
       import
       type(c_ptr), value :: str
@@ -917,6 +966,76 @@ contains
     res = cudecompAmdAccumulateHalosZ_C(handle, grid_desc, c_loc(input), c_loc(work), int(dtype, c_int), h, per, &
                                         int(dim - 1, c_int32_t), p, s)
   end function cudecompAmdAccumulateHalosZ
+
+  ! ---- halo fill (cudecomp_amd_fill.h): the arguments of the updates without work, plus an optional value ---------
+  function cudecompAmdFillHalosX(handle, grid_desc, input, dtype, halo_extents, halo_periods, dim, padding, stream, &
+                                 value) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    type(*), target, optional :: value  ! one element of dtype, read before the call returns; absent: zero bytes
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    type(c_ptr) :: v
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    v = c_null_ptr
+    if (present(value)) v = c_loc(value)
+    res = cudecompAmdFillHalosX_C(handle, grid_desc, c_loc(input), int(dtype, c_int), v, h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdFillHalosX
+
+  function cudecompAmdFillHalosY(handle, grid_desc, input, dtype, halo_extents, halo_periods, dim, padding, stream, &
+                                 value) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    type(*), target, optional :: value
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    type(c_ptr) :: v
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    v = c_null_ptr
+    if (present(value)) v = c_loc(value)
+    res = cudecompAmdFillHalosY_C(handle, grid_desc, c_loc(input), int(dtype, c_int), v, h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdFillHalosY
+
+  function cudecompAmdFillHalosZ(handle, grid_desc, input, dtype, halo_extents, halo_periods, dim, padding, stream, &
+                                 value) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    type(*), target, optional :: value
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    type(c_ptr) :: v
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    v = c_null_ptr
+    if (present(value)) v = c_loc(value)
+    res = cudecompAmdFillHalosZ_C(handle, grid_desc, c_loc(input), int(dtype, c_int), v, h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdFillHalosZ
 
   subroutine halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
     integer(c_int32_t), intent(out) :: h(3), p(3)

@@ -63,7 +63,8 @@ typedef struct {
   /* 0 for update plans.  Accumulation plans (cudecompExtPlanHaloAccumulate): bit 0 set; bit 1: the destinations of the two
    * add-moves overlap, they run one after the other in list order; bits 4, 5: pre[0], pre[1] are add-moves (dst += src); bits
    * 6, 7: post[0], post[1] are.  The exchange between pre and post is that of the updates: send slot i travels to neighbour i
-   * and lands in ITS receive slot 1 - i. */
+   * and lands in ITS receive slot 1 - i.  Fill plans (cudecompExtPlanHaloFill): bit 8 set and nothing else; every move of
+   * `pre` is a fill-move (destination only, the source fields are zero). */
   int32_t reserved;
   int64_t face_elements, send_off[2], recv_off[2];
   cudecompExtMove_t pre[2], post[2];
@@ -122,6 +123,13 @@ cudecompResult_t cudecompExtPlanHalo(const cudecompExtGridSpec_t* grid, int32_t 
 cudecompResult_t cudecompExtPlanHaloAccumulate(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
                                                const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
                                                const int32_t padding[], int32_t force_packed, cudecompExtHaloPlan_t* plan);
+
+/* The plan cudecompAmdFillHalos{X,Y,Z} (cudecomp_amd_fill.h) would run on `rank`: kind 0 (nothing to do) or 1 (local); at most
+ * two fill-moves in `pre`, the low side then the high side, each a destination in buffer 0 with the source fields zero and
+ * row_pitch 0; n_post = 0; cudecompExtHaloPlan_t::reserved has bit 8 set.  The refusals are those of cudecompExtPlanHalo. */
+cudecompResult_t cudecompExtPlanHaloFill(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
+                                         const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
+                                         const int32_t padding[], int32_t force_packed, cudecompExtHaloPlan_t* plan);
 
 /* Stateless geometry queries on a grid spec (no handle, no communicator): what cudecompGetPencilInfo,
  * cudecompGetShiftedRank, cudecompGetTransposeWorkspaceSize and cudecompGetHaloWorkspaceSize would answer on `rank`. */
@@ -241,6 +249,13 @@ cudecompResult_t cudecompExtMove3D(const void* src, void* dst, int32_t es, const
 cudecompResult_t cudecompExtAccumulate3D(const void* src, void* dst, cudecompDataType_t dtype, const int64_t extent[3],
                                          const int64_t ss[3], const int64_t ds[3], int32_t force_generic,
                                          int32_t* kernel_class, hipStream_t stream);
+
+/* One fill-move on the GPU: every cell dst[k0*ds[0] + k1*ds[1] + k2*ds[2]], 0 <= k_i < extent[i] (strides in elements of `es`
+ * bytes), receives the `es` bytes of *value (NULL: zero bytes); nothing else is written and nothing is read.  force: bit 0 the
+ * element-wise kernel, bit 1 non-temporal stores regardless of the size, bit 2 cached stores regardless of the size (benchmark/halo_bench.py
+ * measures the one against the other).  *kernel_class (optional): 0 rows, 2 generic. */
+cudecompResult_t cudecompExtFill3D(void* dst, int32_t es, const void* value, const int64_t extent[3], const int64_t ds[3],
+                                   int32_t force, int32_t* kernel_class, hipStream_t stream);
 
 /* How the kernel layer WOULD execute a 3-D block move between buffers at the given addresses (no launch; works without a
  * GPU): out[10] = {class (0 rows, 1 LDS transpose, 2 generic), kernel variant, tile_i, tile_j, tiles_i, tiles_j, batch extent,
