@@ -123,6 +123,11 @@ class ExtLinkInfo(C.Structure):
                 ("crosses_devices", C.c_int32), ("copy_engine", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ExtLaunch(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("cls", "kind", "es", "vec", "tile_i", "tile_j", "access", "arith", "n", "interleave")] + [
+        ("blocks", C.c_int64), ("elements", C.c_int64), ("first_block", C.c_int64 * 9), ("index", C.c_int32 * 8)]
+
+
 class ExtGridSpec(C.Structure):
     _fields_ = [("gdims", C.c_int32 * 3), ("gdims_dist", C.c_int32 * 3), ("pdims", C.c_int32 * 2),
                 ("col_major", C.c_int32), ("mem_order", (C.c_int32 * 3) * 3)]
@@ -145,7 +150,7 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtWorkspaceSizes", "cudecompExtGetLinkInfo", "cudecompExtLastKernelName",
                "cudecompExtRunLocalPhases", "cudecompExtEstimateCycleMs", "cudecompExtTrimWorkspacePool", "cudecompExtPlanRelay", "cudecompExtQueueCensus",
                "cudecompExtDescribeMove", "cudecompExtRotateWalk", "cudecompExtPlanHaloAccumulate", "cudecompExtAccumulate3D",
-               "cudecompExtPlanHaloFill", "cudecompExtFill3D"]
+               "cudecompExtPlanHaloFill", "cudecompExtFill3D", "cudecompExtRunMoves", "cudecompExtDescribeMoves"]
 # include/cudecomp_amd.h: extensions of the API a solver may use
 AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
 # include/cudecomp_amd_fill.h: halo fill
@@ -243,6 +248,10 @@ def lib():
         L.cudecompExtDescribeMove.argtypes = [C.c_uint64, C.c_uint64, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32,
                                               C.POINTER(i64)]
         L.cudecompExtRotateWalk.argtypes = [i32, i32, i64, i64, pi32, C.POINTER(i64)]
+        L.cudecompExtRunMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(vp), i32, i32, i32, vp, i32, C.POINTER(vp), vp, pi32,
+                                          C.POINTER(i64), pi32]
+        L.cudecompExtDescribeMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, i32, i32, i32,
+                                               C.POINTER(C.c_uint64), C.POINTER(ExtLaunch), i32, pi32]
         _lib = L
     return _lib
 
@@ -603,6 +612,57 @@ def cudecompExtDescribeMove(src_address, dst_address, es, extent, ss, ds, flags=
            "cudecompExtDescribeMove")
     keys = ("cls", "variant", "tile_i", "tile_j", "tiles_i", "tiles_j", "batch", "run", "walk", "access")
     return dict(zip(keys, [int(x) for x in out]))
+
+
+MOVES_COPY, MOVES_ADD, MOVES_FILL = 0, 1, 2  # `mode` of cudecompExtRunMoves / cudecompExtDescribeMoves
+
+
+def make_move(extent, ss, ds, src_off=0, dst_off=0, src_buf=0, dst_buf=1, row_pitch=0):
+    """One entry of a move list (ExtMove): offsets and strides in elements."""
+    m = ExtMove()
+    m.src_buf, m.dst_buf, m.src_off, m.dst_off, m.peer, m.row_pitch = src_buf, dst_buf, int(src_off), int(dst_off), -1, int(row_pitch)
+    for i in range(3):
+        m.extent[i], m.ss[i], m.ds[i] = int(extent[i]), int(ss[i]), int(ds[i])
+    return m
+
+
+def _move_list(moves):
+    arr = (ExtMove * max(1, len(moves)))()
+    for i, m in enumerate(moves):
+        C.memmove(C.byref(arr[i]), C.byref(m), C.sizeof(ExtMove))
+    return arr
+
+
+def cudecompExtRunMoves(moves, bufs, es, mode=MOVES_COPY, dtype=0, value=None, flags=0, dst_bases=None, stream=None):
+    """A list of moves through the kernel layer's batching (cudecomp_ext.h): bufs = three device pointers (ints or None),
+    dst_bases = None or one device pointer per move.  Returns (launches per class, elements per class, launches in all)."""
+    v = _value_bytes(value)
+    if v is not None and len(v) != es:
+        raise ValueError("value holds %d bytes, the element size is %d" % (len(v), es))
+    b = (C.c_void_p * 3)(*[p or None for p in bufs])
+    bases = None if dst_bases is None else (C.c_void_p * max(1, len(moves)))(*[p or None for p in dst_bases])
+    launches, elements, total = (C.c_int32 * 3)(), (C.c_int64 * 3)(), C.c_int32(-1)
+    _check(lib().cudecompExtRunMoves(_move_list(moves), len(moves), b, es, int(mode), int(dtype), v, int(flags), bases, stream,
+                                     launches, elements, C.byref(total)), "cudecompExtRunMoves")
+    return [int(x) for x in launches], [int(x) for x in elements], total.value
+
+
+def cudecompExtDescribeMoves(moves, buf_addresses, es, mode=MOVES_COPY, dtype=0, flags=0, dst_base_addresses=None):
+    """The launches cudecompExtRunMoves would make for the list (no launch, no GPU): a list of dicts in launch order, with
+    the ExtLaunch fields; `first_block` and `index` cut to the launch's moves."""
+    b = (C.c_uint64 * 3)(*[int(p or 0) for p in buf_addresses])
+    bases = None if dst_base_addresses is None else (C.c_uint64 * max(1, len(moves)))(*[int(p or 0) for p in dst_base_addresses])
+    cap = len(moves) + 1
+    out, n = (ExtLaunch * cap)(), C.c_int32(-1)
+    _check(lib().cudecompExtDescribeMoves(_move_list(moves), len(moves), b, es, int(mode), int(dtype), int(flags), bases, out, cap,
+                                          C.byref(n)), "cudecompExtDescribeMoves")
+    res = []
+    for l in out[:n.value]:
+        d = {name: int(getattr(l, name)) for name, _ in ExtLaunch._fields_[:12]}
+        d["first_block"] = [int(x) for x in l.first_block[:l.n + 1]]
+        d["index"] = [int(x) for x in l.index[:l.n]]
+        res.append(d)
+    return res
 
 
 def make_config(gdims, pdims, gdims_dist=None, rank_order=0, axis_contiguous=(0, 0, 0), mem_order=None,

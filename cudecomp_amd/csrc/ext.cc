@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <vector>
 
 #include "cudecomp_ext.h"
 #include "errors.h"
@@ -124,6 +125,50 @@ GridShape shapeFromSpec(const cudecompExtGridSpec_t* spec) {
   if (g.pdims[0] < 1 || g.pdims[1] < 1) CD_INVALID_USAGE("bad pdims in grid spec");
   g.col_major = spec->col_major != 0;
   return g;
+}
+
+// cudecompExtRunMoves / cudecompExtDescribeMoves: the list, the tuning and the arithmetic as the kernel layer takes them
+KernelTuning tuningOfFlags(int32_t flags) {  // the bits of cudecompExtMove3D
+  KernelTuning t;
+  if (flags & 1) t.force_class = MOVE_GENERIC;
+  if (flags & 2) t.force_streaming = true;
+  if (flags & 4) t.window_mode = 1;
+  if (flags & 8) t.window_mode = 0;
+  if (flags & 64) t.walk_order = 0;
+  if (flags & 128) t.walk_order = 1;
+  return t;
+}
+
+std::vector<Move3D> importMoves(const cudecompExtMove_t* moves, int32_t n, int32_t es, int32_t mode, cudecompDataType_t dtype,
+                                ArithType* arith) {
+  if (n < 0 || (n > 0 && !moves)) CD_INVALID_USAGE("bad move list");
+  if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
+  if (mode < 0 || mode > 2) CD_INVALID_USAGE("mode must be 0 (copy), 1 (add) or 2 (fill)");
+  *arith = ARITH_NONE;
+  if (mode == 1) {
+    if (elementSize(dtype) != es) CD_INVALID_USAGE("element size does not match the data type of the addition");
+    *arith = arithOf(dtype);
+  }
+  std::vector<Move3D> out(n);
+  for (int32_t i = 0; i < n; ++i) {
+    const cudecompExtMove_t& e = moves[i];
+    Move3D& m = out[i];
+    if (e.src_buf < 0 || e.src_buf > 2 || e.dst_buf < 0 || e.dst_buf > 2) CD_INVALID_USAGE("buffer index out of range");
+    m.src_buf = (BufId)e.src_buf;
+    m.dst_buf = (BufId)e.dst_buf;
+    m.src_off = e.src_off;
+    m.dst_off = e.dst_off;
+    for (int d = 0; d < 3; ++d) {
+      if (e.extent[d] < 0) CD_INVALID_USAGE("negative extent");
+      m.extent[d] = e.extent[d];
+      m.ss[d] = e.ss[d];
+      m.ds[d] = e.ds[d];
+    }
+    m.dst_row_pitch = e.row_pitch;
+    m.add = mode == 1;
+    m.fill = mode == 2;
+  }
+  return out;
 }
 
 }  // namespace
@@ -713,6 +758,75 @@ cudecompResult_t cudecompExtFill3D(void* dst, int32_t es, const void* value, con
       for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
         if (st.launches[c]) *kernel_class = c;
     }
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtDescribeMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t buf_addresses[3], int32_t es,
+                                         int32_t mode, cudecompDataType_t dtype, int32_t flags, const uint64_t* dst_base_addresses,
+                                         cudecompExtLaunch_t* launches, int32_t max_launches, int32_t* n_launches) {
+  try {
+    if (!buf_addresses || !n_launches || max_launches < 0 || (max_launches > 0 && !launches)) CD_INVALID_USAGE("bad argument");
+    ArithType arith;
+    const std::vector<Move3D> list = importMoves(moves, n, es, mode, dtype, &arith);
+    const KernelTuning t = tuningOfFlags(flags);
+    void* bufs[3];
+    for (int i = 0; i < 3; ++i) bufs[i] = reinterpret_cast<void*>(buf_addresses[i]);
+    std::vector<void*> bases;
+    if (dst_base_addresses)
+      for (int32_t i = 0; i < n; ++i) bases.push_back(reinterpret_cast<void*>(dst_base_addresses[i]));
+    if (dst_base_addresses && bases.empty()) bases.push_back(nullptr);  // (an empty list with bases is still a remote one)
+    const std::vector<Launch> ls = planLaunches(list.data(), n, bufs, es, &t, dst_base_addresses ? bases.data() : nullptr, arith);
+    *n_launches = (int32_t)ls.size();
+    if ((int32_t)ls.size() > max_launches) CD_INVALID_USAGE("more launches than the output array holds");
+    for (size_t i = 0; i < ls.size(); ++i) {
+      const Launch& l = ls[i];
+      cudecompExtLaunch_t& o = launches[i];
+      std::memset(&o, 0, sizeof(o));
+      o.cls = l.cls;
+      o.kind = l.k.kind;
+      o.es = l.k.es;
+      o.vec = l.k.vec;
+      o.tile_i = l.k.ti;
+      o.tile_j = l.k.tj;
+      o.access = l.k.access;
+      o.arith = l.k.arith;
+      o.n = l.b.n;
+      o.interleave = l.b.interleave;
+      o.blocks = l.blocks;
+      o.elements = l.elements;
+      for (int k = 0; k <= l.b.n; ++k) o.first_block[k] = l.b.first_block[k];
+      for (int k = 0; k < 8; ++k) o.index[k] = k < l.b.n ? l.index[k] : -1;
+    }
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtRunMoves(const cudecompExtMove_t* moves, int32_t n, void* const bufs[3], int32_t es, int32_t mode,
+                                    cudecompDataType_t dtype, const void* fill_value, int32_t flags, void* const* dst_bases,
+                                    hipStream_t stream, int32_t launches[3], int64_t elements[3], int32_t* n_launches) {
+  try {
+    if (!bufs) CD_INVALID_USAGE("null argument");
+    ArithType arith;
+    const std::vector<Move3D> list = importMoves(moves, n, es, mode, dtype, &arith);
+    const KernelTuning t = tuningOfFlags(flags);
+    KernelStats st;
+    launchMoves(list.data(), n, bufs, es, stream, &t, &st, dst_bases, arith, mode == 2 ? fill_value : nullptr);
+    int total = 0;
+    for (int c = 0; c < MOVE_CLASS_COUNT; ++c) {
+      if (launches) launches[c] = st.launches[c];
+      if (elements) elements[c] = st.elements[c];
+      total += st.launches[c];
+    }
+    if (n_launches) *n_launches = total;
   } catch (const Error& e) {
     return fail(e);
   } catch (...) {

@@ -516,24 +516,29 @@ void describeMove(const Move3D& m, const void* src, void* dst, int es, const Ker
   for (int i = 0; i < 10; ++i) out[i] = v[i];
 }
 
-void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
-                 const KernelTuning* tuning, KernelStats* stats, void* const* dst_base_override, ArithType arith,
-                 const void* fill_value) {
+std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3], int es, const KernelTuning* tuning,
+                                 void* const* dst_base_override, ArithType arith) {
   const bool remote = dst_base_override != nullptr;
   const KernelTuning& t = tuning ? *tuning : kDefaultTuning;
   if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
   std::vector<Classified> cs;
+  std::vector<int> index;  // cs[i] is moves[index[i]]
   cs.reserve(n);
+  index.reserve(n);
   for (int i = 0; i < n; ++i) {
     if (moves[i].elements() == 0) continue;
     cs.push_back(classify(moves[i], bufs, es, t, dst_base_override ? dst_base_override[i] : nullptr, remote, arith));
+    index.push_back(i);
   }
   // moves of one phase are independent, so they may be regrouped by kernel flavour
+  std::vector<Launch> launches;
   std::vector<bool> done(cs.size(), false);
   for (size_t i = 0; i < cs.size(); ++i) {
     if (done[i]) continue;
-    Batch b{};
-    const MoveClass cls = classOf(cs[i].k.kind);
+    Launch l{};
+    Batch& b = l.b;
+    l.k = cs[i].k;
+    l.cls = classOf(cs[i].k.kind);
     unsigned long long blocks = 0;
     for (size_t j = i; j < cs.size() && b.n < kMaxBatch; ++j) {
       if (done[j] || !(cs[j].k == cs[i].k)) continue;
@@ -548,7 +553,8 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
       b.t0[b.n] = cs[j].t0;
       b.t1[b.n] = cs[j].t1;
       blocks += cs[j].blocks;
-      if (stats) stats->elements[cls] += cs[j].elements;
+      l.elements += cs[j].elements;
+      l.index[b.n] = index[j];
       ++b.n;
       done[j] = true;
     }
@@ -557,7 +563,7 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
     // run one after the other, a 2-KiB slice of every 8-KiB row keeps part of the memory channels idle.  Served round
     // robin, the workgroups in flight cover whole rows (C3 per-rank unpacks: 0.43-0.47 -> 0.35 ms, r02_tuning.md).
     // Transposes keep their XCD-contiguous tile walk (interleaving them measured slightly slower).
-    if ((dst_base_override || cls != MOVE_TRANSPOSE) && b.n > 1) {
+    if ((dst_base_override || l.cls != MOVE_TRANSPOSE) && b.n > 1) {
       unsigned long long widest = 0;
       for (int k = 0; k < b.n; ++k) widest = std::max<unsigned long long>(widest, b.first_block[k + 1] - b.first_block[k]);
       if (widest * b.n <= 0x7fffffffULL) {
@@ -565,8 +571,21 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
         blocks = widest * b.n;
       }
     }
-    launchBatch(cs[i].k, b, fill_value, (unsigned int)blocks, stream);
-    if (stats) stats->launches[cls] += 1;
+    l.blocks = (unsigned int)blocks;
+    launches.push_back(l);
+  }
+  return launches;
+}
+
+void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
+                 const KernelTuning* tuning, KernelStats* stats, void* const* dst_base_override, ArithType arith,
+                 const void* fill_value) {
+  for (const Launch& l : planLaunches(moves, n, bufs, es, tuning, dst_base_override, arith)) {
+    launchBatch(l.k, l.b, fill_value, l.blocks, stream);
+    if (stats) {
+      stats->launches[l.cls] += 1;
+      stats->elements[l.cls] += l.elements;
+    }
   }
 }
 

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <vector>
+
 #include "kernels_batch.h"
 #include "plan.h"
 
@@ -44,6 +46,23 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
                  const KernelTuning* tuning = nullptr, KernelStats* stats = nullptr,
                  void* const* dst_base_override = nullptr,  // per-move destination base (remote buffers)
                  ArithType arith = ARITH_NONE, const void* fill_value = nullptr);
+
+// One kernel launch of a list of moves: what runs, its descriptor, its workgroups (the padded count of an interleaved launch)
+// and which entries of the list it serves.
+struct Launch {
+  KernelChoice k;
+  kern::Batch b;
+  unsigned int blocks;
+  MoveClass cls;
+  i64 elements;                  // of all its moves
+  int index[kern::kMaxBatch];    // index[i]: the list entry b.m[i] is
+};
+// WHICH launches launchMoves makes for a list, in order (pure host code, no device needed; the arguments are launchMoves's):
+// empty moves dropped, the rest regrouped by equal KernelChoice in the order of first appearance, groups cut at kMaxBatch
+// moves and before the move whose workgroups would take the sum past 2^31 - 1, interleaved when there are several moves that
+// are no local transposes.  Throws what launchMoves throws, before anything is launched.
+std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3], int es, const KernelTuning* tuning = nullptr,
+                                 void* const* dst_base_override = nullptr, ArithType arith = ARITH_NONE);
 
 // How a move WOULD run (no launch, no device needed): class, kernel variant, tile, tile counts, walk parameters, access mode.
 // out[10] = {class, variant, tile_i (row copies: 0 plain / 1 shifted / 2 dense kernel), tile_j, tiles_i, tiles_j, batch, p0 (run length), p1 (walk bits: 1 XCD-contiguous, 2 j first,

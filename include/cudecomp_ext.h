@@ -268,6 +268,41 @@ cudecompResult_t cudecompExtFill3D(void* dst, int32_t es, const void* value, con
 cudecompResult_t cudecompExtDescribeMove(uint64_t src_address, uint64_t dst_address, int32_t es, const int64_t extent[3],
                                         const int64_t ss[3], const int64_t ds[3], int32_t flags, int64_t out[10]);
 
+/* Lists of moves through the kernel layer's batching (csrc/kernels.cc planLaunches / launchMoves), as the executor's phases
+ * and the one-sided transports call it.  Moves with equal kernel choices share a launch of up to 8 moves; a launch of several
+ * moves that are not local transposes is INTERLEAVED (workgroup b serves move b % n, padded to widest * n workgroups).
+ * Harness-only (tests/test_kernel_batches.py, tests/test_gpu_kernel_batches.py).
+ *
+ * cudecompExtRunMoves launches the list on `stream`: moves[i] reads bufs[src_buf] + src_off and writes bufs[dst_buf] + dst_off
+ * (elements of `es` bytes; row_pitch as the planner sets it; peer is ignored).  The destinations must be disjoint.  mode 0:
+ * copies (dtype and fill_value ignored); 1: additions dst += src in the arithmetic of `dtype`, whose size must be `es`; 2:
+ * fills with the `es` bytes at fill_value (NULL: zero bytes; the source fields are ignored).  flags: bits 1, 2, 4, 8, 64, 128
+ * of cudecompExtMove3D, same meanings.  dst_bases (optional, n entries): moves[i] writes dst_bases[i] + dst_off instead, with
+ * the system-scope stores of a peer's memory (access mode 3) -- the calling form of the one-sided transports; additions and
+ * fills refuse it with CUDECOMP_RESULT_INTERNAL_ERROR before anything is launched.  launches[3] / elements[3] (optional): launches
+ * and elements per class (0 rows, 1 LDS transpose, 2 generic); *n_launches (optional): launches in all.
+ *
+ * cudecompExtDescribeMoves answers which launches that call would make, without a device: the same arguments with addresses
+ * as integers.  launches[0 .. *n_launches - 1] in launch order; more than max_launches is CUDECOMP_RESULT_INVALID_USAGE (with
+ * *n_launches set).  A move that needs more than 2^31 - 1 workgroups by itself is CUDECOMP_RESULT_NOT_SUPPORTED.
+ * kind counts csrc/kernels_batch.h KernelKind: 0 rows, 1 rows shifted, 2 rows dense, 3 transpose, 4 transpose window, 5 transpose
+ * lines, 6 transpose row lines, 7 generic, 8 rows addition, 9 generic addition, 10 rows fill, 11 generic fill. */
+typedef struct {
+  int32_t cls;                                      /* 0 rows, 1 LDS transpose, 2 generic */
+  int32_t kind, es, vec, tile_i, tile_j, access, arith; /* csrc/kernels_batch.h KernelChoice */
+  int32_t n, interleave;                            /* moves in the launch; 1 = served round robin */
+  int64_t blocks;                                   /* workgroups launched (interleaved: widest * n) */
+  int64_t elements;                                 /* of all its moves */
+  int64_t first_block[9];                           /* first_block[i + 1] - first_block[i] = workgroups of its move i */
+  int32_t index[8];                                 /* index[i] = the list entry that is its move i (-1 beyond n) */
+} cudecompExtLaunch_t;
+cudecompResult_t cudecompExtRunMoves(const cudecompExtMove_t* moves, int32_t n, void* const bufs[3], int32_t es, int32_t mode,
+                                    cudecompDataType_t dtype, const void* fill_value, int32_t flags, void* const* dst_bases,
+                                    hipStream_t stream, int32_t launches[3], int64_t elements[3], int32_t* n_launches);
+cudecompResult_t cudecompExtDescribeMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t buf_addresses[3], int32_t es,
+                                         int32_t mode, cudecompDataType_t dtype, int32_t flags, const uint64_t* dst_base_addresses,
+                                         cudecompExtLaunch_t* launches, int32_t max_launches, int32_t* n_launches);
+
 /* The orbit walk of the in-place rotation kernel (csrc/rotate_walk.h; no launch, works without a GPU): for an array of nb
  * blocks per edge and walk (-1 = the default), *grid = the workgroups a launch has, and for workgroups first .. first + count - 1
  * blocks[3 * i .. 3 * i + 2] = the block triple (b0, b1, b2) of workgroup first + i, or -1 -1 -1 when it maps to none (padding).

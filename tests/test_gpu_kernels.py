@@ -10,6 +10,7 @@ import torch
 import cudecomp_amd as cd
 from oracle import oracle as orc
 from tests import gpu_util as G
+from tests import move_lists as ML
 
 pytestmark = pytest.mark.gpu
 
@@ -141,21 +142,11 @@ def test_random_moves_property_sweep():
     from hypothesis import strategies as st
 
     @settings(max_examples=500, deadline=None, suppress_health_check=list(HealthCheck))
-    @given(es=st.sampled_from([4, 8, 16]), ext=st.tuples(st.integers(1, 150), st.integers(1, 70), st.integers(1, 12)),
-           sperm=st.permutations((0, 1, 2)), dperm=st.permutations((0, 1, 2)),
-           spad=st.tuples(st.integers(0, 5), st.integers(0, 3)), dpad=st.tuples(st.integers(0, 5), st.integers(0, 3)),
-           soff=st.integers(0, 9), doff=st.integers(0, 9), seed=st.integers(0, 1 << 20))
+    @given(es=st.sampled_from([4, 8, 16]), seed=st.integers(0, 1 << 20), **ML.shape_strategies(st))
     def check(es, ext, sperm, dperm, spad, dpad, soff, doff, seed):
-        def strides(perm, pad):
-            # memory position i holds logical dim perm[i]; rows / planes padded like halo-carrying pencils
-            shape = [ext[p] for p in perm]
-            s_mem = [1, shape[0] + pad[0], (shape[0] + pad[0]) * (shape[1] + pad[1])]
-            out = [0, 0, 0]
-            for i, p in enumerate(perm):
-                out[p] = s_mem[i]
-            return out, s_mem[2] * shape[2]
-        ss, slen = strides(sperm, spad)
-        ds, dlen = strides(dperm, dpad)
+        # memory position i holds logical dim perm[i]; rows / planes padded like halo-carrying pencils
+        ss, slen = ML.padded_strides(ext, sperm, spad)
+        ds, dlen = ML.padded_strides(ext, dperm, dpad)
         run_move(es, ext, ss, ds, soff + slen + 16, doff + dlen + 16, soff, doff, seed=seed)
 
     check()
