@@ -3,11 +3,12 @@
 2x4 grid -> 2048 x 1024 x 256 per rank) treated as a periodic single-rank grid, so every dim exercises the
 face kernels: cudecompUpdateHalosX (periodic self copy; reference include/internal/halo.h:165-193) and, beside
 it on the same pencil, cudecompAmdAccumulateHalosX (cudecomp_amd.h: the two face additions) and, with --fill,
-cudecompAmdFillHalosX (cudecomp_amd_fill.h: the two halos set to zero).
+cudecompAmdFillHalosX (cudecomp_amd_fill.h: the two halos set to zero) and, with --accumulate-clear,
+cudecompAmdAccumulateAndClearHalosX (cudecomp_amd_fill.h: both in the accumulation's launches).
 Per dim: `--reps` repetitions of `--calls` back-to-back calls each, ms per call of every repetition, their
 min / median / max, and GB/s of the median against the algorithmic bytes (update: 2 faces read + written,
 4 * face bytes; accumulation: 2 faces read, 2 destinations read and written, 6 * face bytes; fill: 2 halos written, 2 * face
-bytes).  --fill also checks on the device that afterwards no ghost cell holds anything but zero and no interior cell changed,
+bytes; accumulate-and-clear: the sum of the last two, 8 * face bytes).  --fill also checks on the device that afterwards no ghost cell holds anything but zero and no interior cell changed,
 and times one contiguous 64 MiB fill with cached and with non-temporal stores (the store policy of the fill kernels)."""
 import argparse
 import json
@@ -48,6 +49,8 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--update-only", action="store_true", help="time cudecompUpdateHalosX only")
     ap.add_argument("--fill", action="store_true", help="also time cudecompAmdFillHalosX (value zero), after the other passes")
+    ap.add_argument("--accumulate-clear", action="store_true",
+                    help="also time cudecompAmdAccumulateAndClearHalosX, after the other passes")
     ap.add_argument("--json", metavar="FILE", default=None, help="also write the result line to FILE")
     a = ap.parse_args()
     import torch
@@ -101,17 +104,39 @@ def main():
             ms = _time(lambda: cd.cudecompExtFill3D(data.data_ptr(), 8, None, (n, 1, 1), (1, 0, 0), force, st), a.reps, a.calls)
             policy[name] = dict(_record(ms, n * 8), kernel=cd.cudecompExtLastKernelName())
         extra["store_policy_64MiB"] = policy
+    if a.accumulate_clear:
+        for dim in range(3):
+            rec = res["dim%d" % dim]
+            ms = _time(lambda: cd.cudecompAccumulateAndClearHalos(0, h, gd, data.data_ptr(), work, cd.DOUBLE, halo, (1, 1, 1), dim, stream=st),
+                       a.reps, a.calls)
+            rec["accumulate_clear"] = _record(ms, 8 * faces[dim] * 8)
+            rec["accumulate_clear_kernel"] = cd.cudecompExtLastKernelName()
+            if "accumulate" in rec and "fill" in rec:  # (this tree's own two calls: for orientation, not the figure to hold it against)
+                rec["accumulate_clear_over_accumulate_plus_fill"] = round(
+                    rec["accumulate_clear"]["median_ms"] / (rec["accumulate"]["median_ms"] + rec["fill"]["median_ms"]), 3)
+        # every call leaves the ghost cells along its dim zero: after dims 0, 1, 2 none holds anything else
+        data.fill_(1.0)
+        for dim in (2, 1, 0):
+            cd.cudecompAccumulateAndClearHalos(0, h, gd, data.data_ptr(), work, cd.DOUBLE, halo, (1, 1, 1), dim, stream=st)
+        cells = data.view(shape[2], shape[1], shape[0])
+        interior = cells[a.halo:shape[2] - a.halo, a.halo:shape[1] - a.halo, a.halo:shape[0] - a.halo]
+        extra["ghost_cells_not_zero_after_accumulate_clear"] = int(torch.count_nonzero(cells)) - int(torch.count_nonzero(interior))
+        extra["interior_sum_after_accumulate_clear"] = float(interior.sum())  # every cell of the pencil lands in the interior once
+        extra["cells"] = int(cells.numel())
     cd.cudecompFree(h, gd, work)
     cd.cudecompGridDescDestroy(h, gd)
     line = json.dumps(dict({"workload": "X pencil 2048x1024x256 fp64 + halo %d, periodic single rank, per dim: update (self copy), "
                                         "accumulation (self add)%s; %d repetitions of %d calls"
-                                        % (a.halo, " and fill (zero)" if a.fill else "", a.reps, a.calls),
+                                        % (a.halo, (" and fill (zero)" if a.fill else "") + (" and accumulate-and-clear" if a.accumulate_clear else ""), a.reps, a.calls),
                             "device": torch.cuda.get_device_name(0), "result": res}, **extra))
     print(line)
     if a.json:
         with open(a.json, "w") as f:
             f.write(line + "\n")
     cd.cudecompFinalize(h)
+    if extra.get("ghost_cells_not_zero_after_accumulate_clear") or extra.get("interior_sum_after_accumulate_clear", extra.get("cells")) != extra.get("cells"):
+        sys.exit("halo_bench.py: after accumulate-and-clear along 2, 1, 0 %d ghost cells are not zero, the interior sums to %r of %d"
+                 % (extra["ghost_cells_not_zero_after_accumulate_clear"], extra["interior_sum_after_accumulate_clear"], extra["cells"]))
     if extra.get("ghost_cells_not_zero") or extra.get("interior_cells_changed"):
         sys.exit("halo_bench.py: after the fills %d ghost cells are not zero and %d interior cells changed"
                  % (extra["ghost_cells_not_zero"], extra["interior_cells_changed"]))

@@ -150,11 +150,15 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtWorkspaceSizes", "cudecompExtGetLinkInfo", "cudecompExtLastKernelName",
                "cudecompExtRunLocalPhases", "cudecompExtEstimateCycleMs", "cudecompExtTrimWorkspacePool", "cudecompExtPlanRelay", "cudecompExtQueueCensus",
                "cudecompExtDescribeMove", "cudecompExtRotateWalk", "cudecompExtPlanHaloAccumulate", "cudecompExtAccumulate3D",
-               "cudecompExtPlanHaloFill", "cudecompExtFill3D", "cudecompExtRunMoves", "cudecompExtDescribeMoves"]
+               "cudecompExtPlanHaloFill", "cudecompExtFill3D", "cudecompExtRunMoves", "cudecompExtDescribeMoves",
+               "cudecompExtPlanHaloAccumulateClear"]
 # include/cudecomp_amd.h: extensions of the API a solver may use
 AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
 # include/cudecomp_amd_fill.h: halo fill
 AMD_FILL_SYMBOLS = ["cudecompAmdFillHalosX", "cudecompAmdFillHalosY", "cudecompAmdFillHalosZ"]
+# include/cudecomp_amd_accumulate_clear.h (included by cudecomp_amd_fill.h): accumulation that clears the ghost cells it has read
+AMD_ACCUMULATE_CLEAR_SYMBOLS = ["cudecompAmdAccumulateAndClearHalosX", "cudecompAmdAccumulateAndClearHalosY",
+                                "cudecompAmdAccumulateAndClearHalosZ"]
 
 
 class ExtTransposeTimings(C.Structure):
@@ -211,7 +215,8 @@ def lib():
         for name in ("cudecompTransposeXToY", "cudecompTransposeYToZ", "cudecompTransposeZToY",
                      "cudecompTransposeYToX"):
             getattr(L, name).argtypes = [vp, vp, vp, vp, vp, i32, pi32, pi32, pi32, pi32, vp]
-        for name in ("cudecompUpdateHalosX", "cudecompUpdateHalosY", "cudecompUpdateHalosZ") + tuple(AMD_SYMBOLS):
+        for name in ("cudecompUpdateHalosX", "cudecompUpdateHalosY", "cudecompUpdateHalosZ") + tuple(AMD_SYMBOLS) + tuple(
+                AMD_ACCUMULATE_CLEAR_SYMBOLS):
             getattr(L, name).argtypes = [vp, vp, vp, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         for name in AMD_FILL_SYMBOLS:  # (the update's arguments without `work`, plus the value)
             getattr(L, name).argtypes = [vp, vp, vp, i32, vp, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
@@ -238,6 +243,7 @@ def lib():
         L.cudecompExtPlanHaloAccumulate.argtypes = L.cudecompExtPlanHalo.argtypes
         L.cudecompExtAccumulate3D.argtypes = [vp, vp, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, pi32, vp]
         L.cudecompExtPlanHaloFill.argtypes = L.cudecompExtPlanHalo.argtypes
+        L.cudecompExtPlanHaloAccumulateClear.argtypes = L.cudecompExtPlanHalo.argtypes
         L.cudecompExtFill3D.argtypes = [vp, i32, vp, C.POINTER(i64), C.POINTER(i64), i32, pi32, vp]
         L.cudecompExtGetLinkInfo.argtypes = [vp, C.POINTER(ExtLinkInfo)]
         L.cudecompExtEstimateCycleMs.argtypes = [vp, C.POINTER(ExtGridSpec), i32, i32, i32, i32, C.POINTER(C.c_double)]
@@ -388,6 +394,14 @@ def cudecompAccumulateHalos(axis, handle, gd, inp, work, dtype, halo_extents, ha
            "cudecompAmdAccumulateHalos" + "XYZ"[axis])
 
 
+def cudecompAccumulateAndClearHalos(axis, handle, gd, inp, work, dtype, halo_extents, halo_periods, dim, padding=None,
+                                    stream=None):
+    """cudecompAmdAccumulateAndClearHalos{X,Y,Z} (cudecomp_amd_fill.h): cudecompAccumulateHalos, then zero bytes into the ghost
+    cells it has read -- the two-call form accumulate, fill(value=None) byte for byte, in the accumulation's launches."""
+    name = "cudecompAmdAccumulateAndClearHalos" + "XYZ"[axis]
+    _check(getattr(lib(), name)(handle, gd, inp, work, dtype, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding), stream), name)
+
+
 def _value_bytes(value):
     """bytes of one element: bytes as given, a numpy scalar's own; None stays None (zero bytes)"""
     if value is None or isinstance(value, (bytes, bytearray)):
@@ -475,6 +489,15 @@ def cudecompExtPlanHaloAccumulate(grid, rank, axis, halo_extents, halo_periods, 
     p = ExtHaloPlan()
     _check(lib().cudecompExtPlanHaloAccumulate(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim,
                                                _i3(padding), int(force_packed), C.byref(p)), "cudecompExtPlanHaloAccumulate")
+    return p
+
+
+def cudecompExtPlanHaloAccumulateClear(grid, rank, axis, halo_extents, halo_periods, dim, padding=None, force_packed=False):
+    """Stateless planner of cudecompAmdAccumulateAndClearHalos*; ExtHaloPlan.reserved: the accumulation bits, bit 9, and bits 10 /
+    11 for the moves of `pre` that clear their source (cudecomp_ext.h)."""
+    p = ExtHaloPlan()
+    _check(lib().cudecompExtPlanHaloAccumulateClear(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim,
+                                                    _i3(padding), int(force_packed), C.byref(p)), "cudecompExtPlanHaloAccumulateClear")
     return p
 
 
@@ -615,6 +638,7 @@ def cudecompExtDescribeMove(src_address, dst_address, es, extent, ss, ds, flags=
 
 
 MOVES_COPY, MOVES_ADD, MOVES_FILL = 0, 1, 2  # `mode` of cudecompExtRunMoves / cudecompExtDescribeMoves
+MOVES_TAKE, MOVES_ADD_TAKE = 3, 4  # ... the copy / the addition, then zero bytes into the source cells
 
 
 def make_move(extent, ss, ds, src_off=0, dst_off=0, src_buf=0, dst_buf=1, row_pitch=0):

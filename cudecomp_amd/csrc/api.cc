@@ -625,6 +625,7 @@ cudecompResult_t cudecompGridDescCreateVersioned(cudecompHandle_t handle, cudeco
     gd->halo_plans.clear();
     gd->halo_accumulate_plans.clear();
     gd->halo_fill_plans.clear();
+    gd->halo_accumulate_clear_plans.clear();
     perfReset(gd);  // autotuning trials are not part of the user's performance report
 
     *grid_desc_out = gd;
@@ -833,7 +834,8 @@ CD_DEFINE_TRANSPOSE(cudecompTransposeYToZ, OP_Y_TO_Z)
 CD_DEFINE_TRANSPOSE(cudecompTransposeZToY, OP_Z_TO_Y)
 CD_DEFINE_TRANSPOSE(cudecompTransposeYToX, OP_Y_TO_X)
 
-static cudecompResult_t haloEntry(bool accumulate, int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
+// accumulate: 0 the update, 1 accumulation, 2 accumulation that clears the ghost cells it has read (cudecomp_amd_fill.h)
+static cudecompResult_t haloEntry(int accumulate, int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
                                   void* work, cudecompDataType_t dtype, const int32_t halo_extents[],
                                   const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {
   try {
@@ -845,7 +847,8 @@ static cudecompResult_t haloEntry(bool accumulate, int axis, cudecompHandle_t ha
     if (!input) CD_INVALID_USAGE("input argument cannot be null");
     if (!work) CD_INVALID_USAGE("work argument cannot be null");
     if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
-    if (accumulate) runHaloAccumulate(handle, grid_desc, axis, input, work, dtype, halo_extents, halo_periods, dim, padding, stream);
+    if (accumulate == 2) runHaloAccumulateClear(handle, grid_desc, axis, input, work, dtype, halo_extents, halo_periods, dim, padding, stream);
+    else if (accumulate) runHaloAccumulate(handle, grid_desc, axis, input, work, dtype, halo_extents, halo_periods, dim, padding, stream);
     else runHalo(handle, grid_desc, axis, input, work, dtype, halo_extents, halo_periods, dim, padding, stream);
   }
   CD_API_CATCH()
@@ -858,13 +861,17 @@ static cudecompResult_t haloEntry(bool accumulate, int axis, cudecompHandle_t ha
                         int32_t dim, const int32_t padding[], hipStream_t stream) {                               \
     return haloEntry(ACCUMULATE, AXIS, handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, padding, stream); \
   }
-CD_DEFINE_HALO(cudecompUpdateHalosX, false, 0)
-CD_DEFINE_HALO(cudecompUpdateHalosY, false, 1)
-CD_DEFINE_HALO(cudecompUpdateHalosZ, false, 2)
+CD_DEFINE_HALO(cudecompUpdateHalosX, 0, 0)
+CD_DEFINE_HALO(cudecompUpdateHalosY, 0, 1)
+CD_DEFINE_HALO(cudecompUpdateHalosZ, 0, 2)
 // cudecomp_amd.h: the transpose of the updates (ghost cells summed into their owners)
-CD_DEFINE_HALO(cudecompAmdAccumulateHalosX, true, 0)
-CD_DEFINE_HALO(cudecompAmdAccumulateHalosY, true, 1)
-CD_DEFINE_HALO(cudecompAmdAccumulateHalosZ, true, 2)
+CD_DEFINE_HALO(cudecompAmdAccumulateHalosX, 1, 0)
+CD_DEFINE_HALO(cudecompAmdAccumulateHalosY, 1, 1)
+CD_DEFINE_HALO(cudecompAmdAccumulateHalosZ, 1, 2)
+// cudecomp_amd_fill.h: accumulation and the fill with zero bytes of the same ghost cells, in the accumulation's launches
+CD_DEFINE_HALO(cudecompAmdAccumulateAndClearHalosX, 2, 0)
+CD_DEFINE_HALO(cudecompAmdAccumulateAndClearHalosY, 2, 1)
+CD_DEFINE_HALO(cudecompAmdAccumulateAndClearHalosZ, 2, 2)
 
 // cudecomp_amd_fill.h: the ghost cells an update would write receive one value.  The checks of haloEntry, in its order, without `work`.
 static cudecompResult_t haloFillEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,

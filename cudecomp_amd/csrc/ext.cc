@@ -104,6 +104,13 @@ void exportHaloPlan(const HaloPlan& p, cudecompExtHaloPlan_t* out) {
         if (p.post[i].add) out->reserved |= 64 << i;
     }
     if (p.fill) out->reserved = 256;
+    if (p.clear) {
+      out->reserved |= 512;
+      for (size_t i = 0; i < p.pre.size(); ++i)
+        if (p.pre[i].take) out->reserved |= 1024 << i;
+      for (size_t i = 0; i < p.post.size(); ++i)
+        if (p.post[i].take) CD_INTERNAL_ERROR("a move after the exchange clears its source");
+    }
 }
 
 GridShape shapeFromSpec(const cudecompExtGridSpec_t* spec) {
@@ -143,9 +150,9 @@ std::vector<Move3D> importMoves(const cudecompExtMove_t* moves, int32_t n, int32
                                 ArithType* arith) {
   if (n < 0 || (n > 0 && !moves)) CD_INVALID_USAGE("bad move list");
   if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
-  if (mode < 0 || mode > 2) CD_INVALID_USAGE("mode must be 0 (copy), 1 (add) or 2 (fill)");
+  if (mode < 0 || mode > 4) CD_INVALID_USAGE("mode must be 0 (copy), 1 (add), 2 (fill), 3 (take) or 4 (add and take)");
   *arith = ARITH_NONE;
-  if (mode == 1) {
+  if (mode == 1 || mode == 4) {
     if (elementSize(dtype) != es) CD_INVALID_USAGE("element size does not match the data type of the addition");
     *arith = arithOf(dtype);
   }
@@ -165,8 +172,9 @@ std::vector<Move3D> importMoves(const cudecompExtMove_t* moves, int32_t n, int32
       m.ds[d] = e.ds[d];
     }
     m.dst_row_pitch = e.row_pitch;
-    m.add = mode == 1;
+    m.add = mode == 1 || mode == 4;
     m.fill = mode == 2;
+    m.take = mode == 3 || mode == 4;
   }
   return out;
 }
@@ -365,6 +373,27 @@ cudecompResult_t cudecompExtPlanHaloAccumulate(const cudecompExtGridSpec_t* grid
     const bool none[3] = {false, false, false};
     const HaloPlan p =
         buildHaloAccumulatePlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, force_packed != 0);
+    exportHaloPlan(p, out);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtPlanHaloAccumulateClear(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
+                                                    const int32_t halo[], const bool periods[], int32_t dim, const int32_t pad[],
+                                                    int32_t force_packed, cudecompExtHaloPlan_t* out) {
+  try {
+    const GridShape g = shapeFromSpec(grid);
+    if (!out || !halo) CD_INVALID_USAGE("null argument");
+    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
+    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
+    const int32_t zero[3] = {0, 0, 0};
+    const bool none[3] = {false, false, false};
+    const HaloPlan p =
+        buildHaloAccumulateClearPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, force_packed != 0);
     exportHaloPlan(p, out);
   } catch (const Error& e) {
     return fail(e);

@@ -137,6 +137,7 @@ struct cudecompGridDesc {
   std::map<HaloKey, cudecomp::HaloPlan> halo_plans;
   std::map<HaloKey, cudecomp::HaloPlan> halo_accumulate_plans;  // cudecompAmdAccumulateHalos*: the same key, the other operation
   std::map<HaloKey, cudecomp::HaloPlan> halo_fill_plans;        // cudecompAmdFillHalos*: likewise
+  std::map<HaloKey, cudecomp::HaloPlan> halo_accumulate_clear_plans;  // cudecompAmdAccumulateAndClearHalos*: likewise
 
   // CUDECOMP_ENABLE_CUDA_GRAPHS=1: the per-peer pack loop of the pipelined backends (one kernel + one event
   // record per destination) is captured once per (plan, buffers, element size) and replayed as one graph launch
@@ -260,6 +261,10 @@ void runHalo(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* inp
 void runHaloAccumulate(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, void* work,
                        cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
                        hipStream_t stream);
+// ... and zero bytes into the ghost cells it has read (cudecompAmdAccumulateAndClearHalos*): the same sequence, launch grouping and exchange
+void runHaloAccumulateClear(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, void* work,
+                            cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
+                            hipStream_t stream);
 void runHaloFill(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, const void* value,
                  const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream);
 

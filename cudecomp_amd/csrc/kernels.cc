@@ -2,12 +2,12 @@
 //
 // A move is normalised (unit dims dropped, contiguous dims fused, dims sorted by source stride) and classified: classify()
 // writes WHAT runs into one KernelChoice (kernels_batch.h: the kind of kernel -- row copy plain / shifted / dense, LDS-tiled
-// transposition plain / window / lines / row lines, element-wise, the two additions, the two fills -- element size, lane width,
+// transposition plain / window / lines / row lines, element-wise, the two additions, the two fills, the four takes -- element size, lane width,
 // tile, access mode) and HOW it walks into the Batch fields beside it.  Moves with equal choices are batched (up to kMaxBatch moves, e.g.
 // the per-peer pack copies of one transpose, share one launch; the descriptors travel in the kernel argument segment).  The
 // batching key, the launcher's instantiation and the kernel's name all come from that one record.  The kernels live in
 // kernels_rows.hip, kernels_transpose.hip (one code object per element size), kernels_window.hip, kernels_lines.hip,
-// kernels_rowlines.hip, kernels_accumulate.hip and kernels_fill.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
+// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip and kernels_take.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
 // transpose.cc.  kernels_batch.h says why they are separate code objects.
 //
 // 2-byte elements (fp16, bf16) take the row copy (plain kernel), the LDS-tiled transposition (128 x 128 tiles with 16-byte
@@ -48,7 +48,8 @@ struct Classified {
 constexpr long long kDenseMaxGapBytes = 512;  // widest gap between rows the dense row copy rewrites (halo + padding cells)
 
 MoveClass classOf(KernelKind kind) {
-  if (kind == K_GENERIC || kind == K_GENERIC_ADD || kind == K_GENERIC_FILL) return MOVE_GENERIC;
+  if (kind == K_GENERIC || kind == K_GENERIC_ADD || kind == K_GENERIC_FILL || kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE)
+    return MOVE_GENERIC;
   return kind >= K_TRANSPOSE && kind <= K_TRANSPOSE_ROWLINES ? MOVE_TRANSPOSE : MOVE_ROWS_VEC;
 }
 
@@ -363,16 +364,19 @@ void classifyFill(Classified& c, const Move3D& m, const KernelTuning& tuning, bo
 
 // Copy moves take any kind of kernel.  Add-moves (Move3D::add, `arith` their real type) take the row geometry of the copy
 // (same extent / address / stride rule) or the element-wise one and nothing else: never shifted, dense or transposing forms
-// (only the cells of the move are touched), never a remote destination, never lanes narrower than one real.
+// (only the cells of the move are touched), never a remote destination, never lanes narrower than one real.  Take-moves
+// (Move3D::take, with or without `add`: the copy or the addition, then zero bytes into the source cells) are offered the same two
+// geometries and nothing else, for the same reason -- and because the zero must go where the lane's load went, at its width.
 Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelTuning& tuning, void* dst_base, bool remote,
                     ArithType arith) {
   Move3D m = in;
   if (in.fill) {  // no source: nothing but the destination decides the order and the fusion of the dims
-    if (in.add || in.dst_row_pitch != 0 || remote) CD_INTERNAL_ERROR("fill-moves only store the cells of a local destination");
+    if (in.add || in.take || in.dst_row_pitch != 0 || remote) CD_INTERNAL_ERROR("fill-moves only store the cells of a local destination");
     for (int i = 0; i < 3; ++i) m.ss[i] = m.ds[i];
   }
   normalizeMove(m);
-  const bool add = in.add;
+  const bool add = in.add, take = in.take;
+  if (take && (in.dst_row_pitch != 0 || remote)) CD_INTERNAL_ERROR("take-moves only touch the cells of local buffers");
   if (add) {
     if (arith == ARITH_NONE) CD_INTERNAL_ERROR("add-move without an arithmetic type");
     if (remote) CD_INTERNAL_ERROR("add-moves never have remote destinations");
@@ -385,7 +389,9 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
   const bool streaming = (c.elements * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming;
   // Additions: the source is read once: non-temporal loads for large moves.  The destination is read and rewritten by the
   // same lane: default stores (non-temporal ones measured the same).
-  if (add) c.k.access = streaming ? 1 : 0;
+  // Takes: the zeroes follow the fill's rule for its stores (cached below kStreamBytes, non-temporal from there), the rest the
+  // rule of the copy / the addition; whether a store to a line just loaded wants another rule is unmeasured.
+  if (add || take) c.k.access = streaming ? 1 : 0;
   else c.k.access = remote ? 3 : (streaming ? 2 : 0);  // (a peer's memory: write-through stores, whatever the size)
   c.dm.src = static_cast<const char*>(bufs[m.src_buf]) + m.src_off * es;
   c.dm.dst = static_cast<char*>(dst_base ? dst_base : bufs[m.dst_buf]) + m.dst_off * es;
@@ -396,10 +402,10 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
   const bool force_generic = tuning.force_class == MOVE_GENERIC;
 
   if (!force_generic && m.ss[0] <= 1 && m.ds[0] <= 1) {
-    c.k.kind = add ? K_ROWS_ADD : K_ROWS;
+    c.k.kind = take ? (add ? K_ROWS_ADD_TAKE : K_ROWS_TAKE) : (add ? K_ROWS_ADD : K_ROWS);
     rowVectors(c, m);
     if (add && c.k.vec < arithBytes(arith)) CD_INTERNAL_ERROR("add-move narrower than one real of its arithmetic type");
-    if (!add && offerShiftedRows(c, m, tuning)) {
+    if (!add && !take && offerShiftedRows(c, m, tuning)) {
       if (offerDenseRows(c, in, m, tuning, remote)) return c;
       c.dm.e[0] += 64 / c.k.vec;  // one unit of slack vectors per row (see rows_shifted_kernel)
     }
@@ -408,7 +414,7 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
   }
 
   int t = -1;
-  if (!force_generic && !add && m.ss[0] == 1) {
+  if (!force_generic && !add && !take && m.ss[0] == 1) {
     if (m.ds[1] == 1) t = 1;
     if (m.ds[2] == 1) t = 2;
   }
@@ -417,8 +423,8 @@ Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelT
     return c;
   }
 
-  c.k.kind = add ? K_GENERIC_ADD : K_GENERIC;
-  if (add) c.k.access = 0;
+  c.k.kind = take ? (add ? K_GENERIC_ADD_TAKE : K_GENERIC_TAKE) : (add ? K_GENERIC_ADD : K_GENERIC);
+  if (add || take) c.k.access = 0;
   genericGeometry(c, m);
   return c;
 }
@@ -453,6 +459,12 @@ void spellKernelName(const KernelChoice& k) {
     case K_GENERIC_ADD: snprintf(out, n, "generic_accumulate_kernel<%s,%d>", arithName(k.arith), k.es / arithBytes(k.arith)); break;
     case K_ROWS_FILL: snprintf(out, n, "rows_fill_kernel<%d,%d>", k.vec, s); break;
     case K_GENERIC_FILL: snprintf(out, n, "generic_fill_kernel<%d>", k.es); break;
+    case K_ROWS_TAKE: snprintf(out, n, "rows_take_kernel<%d,%d>", k.vec, s); break;
+    case K_GENERIC_TAKE: snprintf(out, n, "generic_take_kernel<%d>", k.es); break;
+    case K_ROWS_ADD_TAKE: snprintf(out, n, "rows_accumulate_take_kernel<%s,%d,%d>", arithName(k.arith), k.vec, s); break;
+    case K_GENERIC_ADD_TAKE:
+      snprintf(out, n, "generic_accumulate_take_kernel<%s,%d>", arithName(k.arith), k.es / arithBytes(k.arith));
+      break;
   }
 }
 
@@ -491,6 +503,10 @@ void launchBatch(const KernelChoice& k, const Batch& b, const void* fill_value, 
     case K_GENERIC_ADD: launchAccumulateBatch(k, b, blocks, stream); break;
     case K_ROWS_FILL:
     case K_GENERIC_FILL: launchFillBatch(k, b, fillPatternOf(fill_value, k.es, b.m[0].dst), blocks, stream); break;
+    case K_ROWS_TAKE:
+    case K_GENERIC_TAKE:
+    case K_ROWS_ADD_TAKE:
+    case K_GENERIC_ADD_TAKE: launchTakeBatch(k, b, blocks, stream); break;
   }
 }
 

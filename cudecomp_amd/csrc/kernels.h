@@ -42,6 +42,8 @@ struct KernelTuning {
 // Fill-moves (Move3D::fill: dst = value; kernels_fill.hip) take `fill_value`, one element of `es` bytes read before the call
 // returns (nullptr: all-zero bytes), and a local destination; they run as row or element-wise fills that store exactly the
 // cells of the move and load nothing.
+// Take-moves (Move3D::take, copy or add; kernels_take.hip) store zero bytes to the source cells they have read: local buffers
+// only, sources disjoint from all destinations and from each other; row or element-wise forms over exactly the cells of the move.
 void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
                  const KernelTuning* tuning = nullptr, KernelStats* stats = nullptr,
                  void* const* dst_base_override = nullptr,  // per-move destination base (remote buffers)

@@ -9,9 +9,11 @@
 //                                          bytes of the destination, adds per element of T and stores VB bytes.
 //   generic_accumulate_kernel<T, NC>       element-wise (NC reals per element: 2 for the complex types), for everything else:
 //                                          faces one element thick along the fastest memory axis, degenerate shapes.
-// T: _Float16 (IEEE binary16 addition, packed), __bf16 (RNE-to-bf16 of the fp32 sum of the widened operands), float, double.
+// T: _Float16 (IEEE binary16 addition, packed), __bf16 (RNE-to-bf16 of the fp32 sum of the widened operands), float, double
+// (kernels_arith.h: addPayload, shared with kernels_take.hip).
 // Only the cells of the move are read or written: no dense / shifted / window forms (those rewrite gap cells), no remote
 // destinations.  Bound: HBM, 3 bytes moved per byte of the move (source read, destination read, destination written).
+#include "kernels_arith.h"
 #include "kernels_dev.h"
 
 #include "errors.h"
@@ -19,67 +21,6 @@
 namespace cudecomp {
 namespace kern {
 namespace {
-
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// ---- a + b on the raw bits of one T (2-byte types: of the PAIR held by a dword) ---------------------------------------------
-template <typename T> struct Arith;
-template <> struct Arith<float> {
-  static __device__ __forceinline__ unsigned int dword(unsigned int a, unsigned int b) {
-    return __float_as_uint(__uint_as_float(a) + __uint_as_float(b));
-  }
-};
-template <> struct Arith<_Float16> {
-  static __device__ __forceinline__ unsigned int dword(unsigned int a, unsigned int b) {  // v_pk_add_f16
-    return __builtin_bit_cast(unsigned int, (f16x2)(__builtin_bit_cast(f16x2, a) + __builtin_bit_cast(f16x2, b)));
-  }
-  static __device__ __forceinline__ unsigned short one(unsigned short a, unsigned short b) {
-    return __builtin_bit_cast(unsigned short, (_Float16)(__builtin_bit_cast(_Float16, a) + __builtin_bit_cast(_Float16, b)));
-  }
-};
-template <> struct Arith<__bf16> {
-  // widening is a shift (exact); the fp32 sums are rounded to nearest even by the packed convert (v_cvt_pk_bf16_f32)
-  static __device__ __forceinline__ unsigned int dword(unsigned int a, unsigned int b) {
-    f32x2 s;
-    s.x = __uint_as_float(a << 16) + __uint_as_float(b << 16);
-    s.y = __uint_as_float(a & 0xffff0000u) + __uint_as_float(b & 0xffff0000u);
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(s, bf16x2));
-  }
-  static __device__ __forceinline__ unsigned short one(unsigned short a, unsigned short b) {
-    const float s = __uint_as_float((unsigned int)a << 16) + __uint_as_float((unsigned int)b << 16);
-    return __builtin_bit_cast(unsigned short, (__bf16)s);
-  }
-};
-__device__ __forceinline__ u32x2 addDouble(const u32x2& a, const u32x2& b) {
-  return __builtin_bit_cast(u32x2, __builtin_bit_cast(double, a) + __builtin_bit_cast(double, b));
-}
-
-// a + b over a VB-byte lane payload
-template <typename T, int VB>
-__device__ __forceinline__ Bytes<VB> addPayload(const Bytes<VB>& a, const Bytes<VB>& b) {
-  static_assert(VB >= (int)sizeof(T), "a lane holds whole elements");
-  if constexpr (sizeof(T) == 8) {
-    if constexpr (VB == 8) {
-      return addDouble(a, b);
-    } else {
-      u32x4 r;
-      r.xy = addDouble(a.xy, b.xy);
-      r.zw = addDouble(a.zw, b.zw);
-      return r;
-    }
-  } else if constexpr (VB == 2) {
-    return Arith<T>::one(a, b);
-  } else if constexpr (VB == 4) {
-    return Arith<T>::dword(a, b);
-  } else {
-    Bytes<VB> r;
-#pragma unroll
-    for (int k = 0; k < VB / 4; ++k) r[k] = Arith<T>::dword(a[k], b[k]);
-    return r;
-  }
-}
 
 // ---------------------------------------------------------------------------------------------
 // rows_accumulate_kernel: e[0] = vectors per row, e[1] = rows, e[2] = planes; ss/ds[1], [2] in BYTES.

@@ -1,7 +1,8 @@
 // kernels_batch.h -- what csrc/kernels.cc (host: classification, batching) and the kernel code objects share: the record of a
 // kernel choice (KernelChoice), the launch descriptor (Batch) and the launchers.  The code objects the classifier dispatches
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
-// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip; kernels_rotate.hip and sync.hip are launched by the executor.
+// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip; kernels_rotate.hip and sync.hip are launched by
+// the executor.
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
 // code object beyond roughly 0.6-0.7 MB puts the whole process into a regime where every small synchronous operation costs
@@ -52,6 +53,7 @@ struct Batch {
   //   transposes                 p0 = run length of the tile walk (tiles or planes; 0 / 1 = no runs), p1 = kWalk* bits
   //   element-wise               p0 = the dim the lanes run along, p1 unused
   //   fills                      p0 as for rows / element-wise; p1 unused
+  //   takes                      p0 as for rows / element-wise; p1 unused
   int p0[kMaxBatch];
   int p1[kMaxBatch];
   unsigned int first_block[kMaxBatch + 1];
@@ -76,7 +78,11 @@ enum KernelKind {
   K_ROWS_ADD,            // rows_accumulate_kernel (dst += src)
   K_GENERIC_ADD,         // generic_accumulate_kernel
   K_ROWS_FILL,           // rows_fill_kernel (dst = value): lanes on the destination's 16-byte grid
-  K_GENERIC_FILL         // generic_fill_kernel
+  K_GENERIC_FILL,        // generic_fill_kernel
+  K_ROWS_TAKE,           // rows_take_kernel (dst = src; src = 0)
+  K_GENERIC_TAKE,        // generic_take_kernel
+  K_ROWS_ADD_TAKE,       // rows_accumulate_take_kernel (dst += src; src = 0)
+  K_GENERIC_ADD_TAKE     // generic_accumulate_take_kernel
 };
 struct KernelChoice {
   KernelKind kind;
@@ -85,7 +91,7 @@ struct KernelChoice {
   int ti, tj;       // transposes: the tile (elements, i x j); 0 otherwise
   int access;       // copies: 0 default caching, 2 non-temporal loads + stores, 3 non-temporal loads + remote (system-scope
                     // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads;
-                    // fills: 0, 1 non-temporal stores
+                    // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it)
   ArithType arith;  // additions: the real type the elements consist of; ARITH_NONE otherwise
   bool operator==(const KernelChoice& o) const {
     return kind == o.kind && es == o.es && vec == o.vec && ti == o.ti && tj == o.tj && access == o.access && arith == o.arith;
@@ -99,6 +105,8 @@ inline int streamArgOf(KernelKind kind, int access) {
   if (kind == K_GENERIC || kind == K_GENERIC_ADD) return access == 3 ? 3 : 0;
   if (kind == K_ROWS_FILL) return access;
   if (kind == K_GENERIC_FILL) return 0;
+  if (kind == K_ROWS_TAKE || kind == K_ROWS_ADD_TAKE) return access;
+  if (kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE) return 0;
   if (kind == K_TRANSPOSE_WINDOW || kind == K_TRANSPOSE_LINES || kind == K_TRANSPOSE_ROWLINES)
     return access == 2 ? 4 : access;  // always cached loads: the overlap rows of neighbouring windows hit in L2
   return access == 3 ? 3 : (access >= 1 ? 1 : 0);  // row copies: loads and stores stream together
@@ -125,6 +133,9 @@ struct FillPattern {
   unsigned int w[4];
 };
 void launchFillBatch(const KernelChoice& k, const kern::Batch& b, const FillPattern& pattern, unsigned int blocks, hipStream_t stream);
+// kernels_take.hip: take-moves (the copy or the addition, then src = 0).  The Batch of the row copies / additions and of their
+// generic forms; local buffers only.
+void launchTakeBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

@@ -393,6 +393,19 @@ HaloPlan buildHaloAccumulatePlan(const GridShape& g, int rank, int axis, int dim
   return p;
 }
 
+HaloPlan buildHaloAccumulateClearPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                      const int32_t* pad, bool force_packed, bool self_exchange) {
+  HaloPlan p = buildHaloAccumulatePlan(g, rank, axis, dim, halo, periods, pad, force_packed, self_exchange);
+  p.clear = true;
+  for (Move3D& m : p.pre) {  // (SELF_PERIODIC: the wrap additions; PACKED: the packs -- the moves that read the pencil)
+    if (m.src_buf != BUF_IN) CD_INTERNAL_ERROR("the first phase of a halo accumulation reads something other than the pencil");
+    m.take = true;
+  }
+  for (const Move3D& m : p.post)
+    if (m.src_buf != BUF_WORK) CD_INTERNAL_ERROR("the last phase of a halo accumulation reads something other than the workspace");
+  return p;
+}
+
 HaloPlan buildHaloFillPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
                            const int32_t* pad, bool force_packed, bool self_exchange) {
   const HaloPlan u = buildHaloPlan(g, rank, axis, dim, halo, periods, pad, force_packed, self_exchange);  // (its refusals)

@@ -46,6 +46,11 @@ struct Move3D {
   // zero and nothing is loaded -- and the kernel layer stores exactly the destination cells of the move: never the gap cells
   // between rows (dst_row_pitch is never set), never a peer's memory.
   bool fill = false;
+  // true: after the move has read its source cells it stores zero bytes to them (the pack moves and wrap additions of the fused
+  // halo accumulate-and-clear, buildHaloAccumulateClearPlan; with or without `add`).  The source is a local buffer whose cells
+  // are disjoint from every destination and every other source of the phase; exactly the source cells of the move are written,
+  // never the gap cells between rows (dst_row_pitch is never set), never a peer's memory.
+  bool take = false;
 
   i64 elements() const { return extent[0] * extent[1] * extent[2]; }
 };
@@ -159,6 +164,7 @@ struct HaloPlan {
   bool accumulate = false;
   bool ordered = false;  // the destinations of the two add-moves overlap (interior narrower than two halos): one launch each, in order
   bool fill = false;     // fill plans (buildHaloFillPlan) only
+  bool clear = false;    // fused accumulate-and-clear plans (buildHaloAccumulateClearPlan) only
 };
 
 HaloPlan buildHaloPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
@@ -173,6 +179,14 @@ HaloPlan buildHaloPlan(const GridShape& g, int rank, int axis, int dim, const in
 // arrives must be added, not stored.  The workspace layout is buildHaloPlan's (haloWorkspaceElements covers it).
 HaloPlan buildHaloAccumulatePlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
                                  const int32_t* pad, bool force_packed, bool self_exchange = false);
+
+// Halo accumulation along `dim` that CLEARS the ghost cells it has read (include/cudecomp_amd_fill.h has the contract): the plan
+// of buildHaloAccumulatePlan -- same kinds, neighbours, offsets, moves, refusals and `ordered` rule -- with Move3D::take set on
+// exactly the moves whose SOURCE is the pencil: the two add-moves of SELF_PERIODIC, the two pack moves of PACKED's `pre`.  The
+// add-moves of PACKED's `post` read the workspace and stay plain.  The sources are the low / high halo slabs, the cells
+// buildHaloFillPlan names for the same arguments.
+HaloPlan buildHaloAccumulateClearPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                      const int32_t* pad, bool force_packed, bool self_exchange = false);
 
 // Halo FILL along `dim`: the cells the update along `dim` writes (low halo where there is a low neighbour, high halo where there
 // is a high one; include/cudecomp_amd_fill.h has the contract) receive one value.  Same arguments and refusals as buildHaloPlan,

@@ -478,9 +478,11 @@ void runHalo(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, v
 
 // Halo accumulation (cudecompAmdAccumulateHalos*): the plain sequence pack my halos -> exchange -> add what arrived onto my
 // faces, with the exchange of the updates (haloExchange: same routing, same transports, same stream ordering).  Not sampled
-// by the performance report.
-void runHaloAccumulate(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, void* work, cudecompDataType_t dtype,
-                       const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
+// by the performance report.  `clear`: the fused accumulate-and-clear (cudecompAmdAccumulateAndClearHalos*) -- the plan of
+// buildHaloAccumulateClearPlan, whose moves out of the pencil zero what they have read; everything else is the same.
+static void runHaloAccumulateOf(bool clear, cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, void* work,
+                                cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
+                                hipStream_t stream) {
   const int es = elementSize(dtype);
   const ArithType arith = arithOf(dtype);
   const auto backend = gd->config.halo_comm_backend;
@@ -493,10 +495,12 @@ void runHaloAccumulate(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void
   const cudecompGridDesc::HaloKey key{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, force_packed};
   // (force_packed stays in the key because it is HaloKey's: accumulation plans never take the direct form, so a descriptor whose
   // backend changes between peer and non-peer transports would cache the same plan twice -- harmless)
-  auto it = gd->halo_accumulate_plans.find(key);
-  if (it == gd->halo_accumulate_plans.end()) {
-    HaloPlan p = buildHaloAccumulatePlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), force_packed, h->self_exchange);
-    it = gd->halo_accumulate_plans.emplace(key, std::move(p)).first;
+  auto& plans = clear ? gd->halo_accumulate_clear_plans : gd->halo_accumulate_plans;
+  auto it = plans.find(key);
+  if (it == plans.end()) {
+    HaloPlan p = (clear ? buildHaloAccumulateClearPlan : buildHaloAccumulatePlan)(gd->shape, h->rank, axis, dim, hh.data(), per.data(),
+                                                                                  pp.data(), force_packed, h->self_exchange);
+    it = plans.emplace(key, std::move(p)).first;
   }
   const HaloPlan& plan = it->second;
   if (plan.kind == HaloPlan::NONE) return;
@@ -518,6 +522,16 @@ void runHaloAccumulate(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void
   const HaloExchange x = haloExchangeOf(plan, bufs, es);
   haloExchange(h, gd, x, backend, stream);
   launch(plan.post);
+}
+
+void runHaloAccumulate(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, void* work, cudecompDataType_t dtype,
+                       const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
+  runHaloAccumulateOf(false, h, gd, axis, input, work, dtype, halo, periods, dim, pad, stream);
+}
+
+void runHaloAccumulateClear(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, void* work, cudecompDataType_t dtype,
+                            const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
+  runHaloAccumulateOf(true, h, gd, axis, input, work, dtype, halo, periods, dim, pad, stream);
 }
 
 // Halo fill (cudecompAmdFillHalos*): the cells the update would write receive `value`, both sides in one launch.  Local: no

@@ -493,6 +493,53 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompAmdFillHalosZ_C
 
+    ! cudecomp_amd_fill.h: halo accumulate-and-clear (accumulation, then zero bytes into the ghost cells it has read)
+    function cudecompAmdAccumulateAndClearHalosX_C(handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, &
+                                           padding, stream) bind(C, name="cudecompAmdAccumulateAndClearHalosX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input, work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdAccumulateAndClearHalosX_C
+
+    function cudecompAmdAccumulateAndClearHalosY_C(handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, &
+                                           padding, stream) bind(C, name="cudecompAmdAccumulateAndClearHalosY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input, work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdAccumulateAndClearHalosY_C
+
+    function cudecompAmdAccumulateAndClearHalosZ_C(handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, &
+                                           padding, stream) bind(C, name="cudecompAmdAccumulateAndClearHalosZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input, work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdAccumulateAndClearHalosZ_C
+
+
     function cudecomp_c_strlen(str) bind(C, name="strlen") result(n)
       import
       type(c_ptr), value :: str
@@ -1036,6 +1083,71 @@ contains
     if (present(value)) v = c_loc(value)
     res = cudecompAmdFillHalosZ_C(handle, grid_desc, c_loc(input), int(dtype, c_int), v, h, per, int(dim - 1, c_int32_t), p, s)
   end function cudecompAmdFillHalosZ
+
+  ! ---- halo accumulate-and-clear (cudecomp_amd_fill.h): same arguments as the accumulation --------------------------
+  function cudecompAmdAccumulateAndClearHalosX(handle, grid_desc, input, work, dtype, halo_extents, &
+      halo_periods, dim, padding, &
+                                       stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input, work
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdAccumulateAndClearHalosX_C(handle, grid_desc, c_loc(input), c_loc(work), int(dtype, c_int), h, per, &
+                                        int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdAccumulateAndClearHalosX
+
+  function cudecompAmdAccumulateAndClearHalosY(handle, grid_desc, input, work, dtype, halo_extents, &
+      halo_periods, dim, padding, &
+                                       stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input, work
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdAccumulateAndClearHalosY_C(handle, grid_desc, c_loc(input), c_loc(work), int(dtype, c_int), h, per, &
+                                        int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdAccumulateAndClearHalosY
+
+  function cudecompAmdAccumulateAndClearHalosZ(handle, grid_desc, input, work, dtype, halo_extents, &
+      halo_periods, dim, padding, &
+                                       stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input, work
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdAccumulateAndClearHalosZ_C(handle, grid_desc, c_loc(input), c_loc(work), int(dtype, c_int), h, per, &
+                                        int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdAccumulateAndClearHalosZ
+
 
   subroutine halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
     integer(c_int32_t), intent(out) :: h(3), p(3)

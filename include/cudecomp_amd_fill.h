@@ -44,7 +44,6 @@ extern "C" {
  * CUDECOMP_RESULT_NOT_SUPPORTED, a halo wider than a neighbour's slab is refused as the update refuses it, and without a usable
  * device (and with cells to write) the result is CUDECOMP_RESULT_CUDA_ERROR.
  *
- * With equal arguments,  cudecompAmdAccumulateHalos*(dim); cudecompAmdFillHalos*(dim, NULL)  is accumulate-and-clear.
  */
 cudecompResult_t cudecompAmdFillHalosX(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
                                        cudecompDataType_t dtype, const void* value, const int32_t halo_extents[],
@@ -56,8 +55,46 @@ cudecompResult_t cudecompAmdFillHalosZ(cudecompHandle_t handle, cudecompGridDesc
                                        cudecompDataType_t dtype, const void* value, const int32_t halo_extents[],
                                        const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream);
 
+/*
+ * Accumulate-and-clear: the second and the first part of the scatter step for the NEXT time step in one call -- ghost cells are
+ * summed into their owners and left as zero bytes, in the launches of the accumulation.  The argument list is that of
+ * cudecompAmdAccumulateHalos{X,Y,Z} (cudecomp_amd.h).
+ *
+ * Definition.  After the call every byte of the pencil -- interior, faces, both halos, padding and everything beyond -- is what it
+ * would be after this sequence with the same arguments:
+ *   1. cudecompAmdAccumulateHalos*(handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, padding, stream);
+ *   2. cudecompAmdFillHalos*(handle, grid_desc, input, dtype, NULL, halo_extents, halo_periods, dim, padding, stream).
+ *
+ * What is cleared.  The low halo L and the high halo H along `dim` (the slabs named above) end as all-zero bytes, on the sides
+ * that have a neighbour; a rank that is its own neighbour counts as having one.  What is not cleared: a side on a non-periodic
+ * edge of the domain is neither added nor cleared.
+ *
+ * Addend order.  That of accumulation: LF += H(low neighbour), then HF += L(high neighbour), LF and HF the low and high faces
+ * of cudecomp_amd.h.  The sums are bit-identical to those of the two-call form.
+ *
+ * Sequences over dims.  Calling dims 2, 1, 0 leaves the whole pencil equal, byte for byte, to accumulation along 2, 1, 0
+ * followed by fills (value NULL) along 0, 1, 2: a ghost cell cleared by an earlier call of the sequence is only ever added into
+ * cells that are themselves cleared by the end, and adding +0 instead of the cell's value changes nothing that survives.  A
+ * solver therefore clears once, before its first step, and never calls the fill again.
+ *
+ * Collective, workspace, transport, asynchrony.  Exactly those of cudecompAmdAccumulateHalos*: every rank of the communicator
+ * along `dim` calls it, `work` is sized by cudecompGetHaloWorkspaceSize, the transport is the descriptor's halo_comm_backend, the
+ * call is enqueued on `stream`, never blocks the host on GPU work and is capturable wherever accumulation is.  The contents of
+ * `work` after the call are unspecified.
+ *
+ * Validation.  For any argument tuple the result code, the order of the checks and the kind of CUDECOMP:ERROR message are those
+ * of cudecompAmdAccumulateHalos* for the same tuple.
+ *
+ * Touches nothing else.  Only cells of LF, HF, L and H are written: the kernels never take a whole-line form that would rewrite
+ * the cells between rows.
+ *
+ * The three prototypes are in cudecomp_amd_accumulate_clear.h, which this header includes below: every extension keeps a header of
+ * its own, so that the ones before it stay as they were.
+ */
 #ifdef __cplusplus
 }
 #endif
+
+#include "cudecomp_amd_accumulate_clear.h"
 
 #endif /* CUDECOMP_AMD_FILL_H */

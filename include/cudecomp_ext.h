@@ -64,7 +64,9 @@ typedef struct {
    * add-moves overlap, they run one after the other in list order; bits 4, 5: pre[0], pre[1] are add-moves (dst += src); bits
    * 6, 7: post[0], post[1] are.  The exchange between pre and post is that of the updates: send slot i travels to neighbour i
    * and lands in ITS receive slot 1 - i.  Fill plans (cudecompExtPlanHaloFill): bit 8 set and nothing else; every move of
-   * `pre` is a fill-move (destination only, the source fields are zero). */
+   * `pre` is a fill-move (destination only, the source fields are zero).  Fused accumulate-and-clear plans
+   * (cudecompExtPlanHaloAccumulateClear): the accumulation bits as above, bit 9 set, and bits 10, 11: pre[0], pre[1] store zero
+   * bytes to the source cells they have read; no move of `post` does. */
   int32_t reserved;
   int64_t face_elements, send_off[2], recv_off[2];
   cudecompExtMove_t pre[2], post[2];
@@ -123,6 +125,13 @@ cudecompResult_t cudecompExtPlanHalo(const cudecompExtGridSpec_t* grid, int32_t 
 cudecompResult_t cudecompExtPlanHaloAccumulate(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
                                                const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
                                                const int32_t padding[], int32_t force_packed, cudecompExtHaloPlan_t* plan);
+
+/* The plan cudecompAmdAccumulateAndClearHalos{X,Y,Z} (cudecomp_amd_fill.h) would run on `rank`: that of
+ * cudecompExtPlanHaloAccumulate for the same arguments -- kind, neighbours, offsets, moves, refusals -- with the moves that read
+ * the pencil (all of `pre`) marked as clearing their source, see cudecompExtHaloPlan_t::reserved. */
+cudecompResult_t cudecompExtPlanHaloAccumulateClear(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
+                                                    const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
+                                                    const int32_t padding[], int32_t force_packed, cudecompExtHaloPlan_t* plan);
 
 /* The plan cudecompAmdFillHalos{X,Y,Z} (cudecomp_amd_fill.h) would run on `rank`: kind 0 (nothing to do) or 1 (local); at most
  * two fill-moves in `pre`, the low side then the high side, each a destination in buffer 0 with the source fields zero and
@@ -276,17 +285,20 @@ cudecompResult_t cudecompExtDescribeMove(uint64_t src_address, uint64_t dst_addr
  * cudecompExtRunMoves launches the list on `stream`: moves[i] reads bufs[src_buf] + src_off and writes bufs[dst_buf] + dst_off
  * (elements of `es` bytes; row_pitch as the planner sets it; peer is ignored).  The destinations must be disjoint.  mode 0:
  * copies (dtype and fill_value ignored); 1: additions dst += src in the arithmetic of `dtype`, whose size must be `es`; 2:
- * fills with the `es` bytes at fill_value (NULL: zero bytes; the source fields are ignored).  flags: bits 1, 2, 4, 8, 64, 128
+ * fills with the `es` bytes at fill_value (NULL: zero bytes; the source fields are ignored); 3: takes, the copy followed by zero
+ * bytes into the source cells (dst = src; src = 0); 4: additions that clear their source (dst += src; src = 0; dtype as for mode
+ * 1).  The sources of a list of mode 3 or 4 must be disjoint from all destinations and from each other.  flags: bits 1, 2, 4, 8, 64, 128
  * of cudecompExtMove3D, same meanings.  dst_bases (optional, n entries): moves[i] writes dst_bases[i] + dst_off instead, with
- * the system-scope stores of a peer's memory (access mode 3) -- the calling form of the one-sided transports; additions and
- * fills refuse it with CUDECOMP_RESULT_INTERNAL_ERROR before anything is launched.  launches[3] / elements[3] (optional): launches
+ * the system-scope stores of a peer's memory (access mode 3) -- the calling form of the one-sided transports; additions,
+ * fills and both take modes refuse it with CUDECOMP_RESULT_INTERNAL_ERROR before anything is launched.  launches[3] / elements[3] (optional): launches
  * and elements per class (0 rows, 1 LDS transpose, 2 generic); *n_launches (optional): launches in all.
  *
  * cudecompExtDescribeMoves answers which launches that call would make, without a device: the same arguments with addresses
  * as integers.  launches[0 .. *n_launches - 1] in launch order; more than max_launches is CUDECOMP_RESULT_INVALID_USAGE (with
  * *n_launches set).  A move that needs more than 2^31 - 1 workgroups by itself is CUDECOMP_RESULT_NOT_SUPPORTED.
  * kind counts csrc/kernels_batch.h KernelKind: 0 rows, 1 rows shifted, 2 rows dense, 3 transpose, 4 transpose window, 5 transpose
- * lines, 6 transpose row lines, 7 generic, 8 rows addition, 9 generic addition, 10 rows fill, 11 generic fill. */
+ * lines, 6 transpose row lines, 7 generic, 8 rows addition, 9 generic addition, 10 rows fill, 11 generic fill, 12 rows take, 13 generic take, 14 rows addition
+ * with take, 15 generic addition with take. */
 typedef struct {
   int32_t cls;                                      /* 0 rows, 1 LDS transpose, 2 generic */
   int32_t kind, es, vec, tile_i, tile_j, access, arith; /* csrc/kernels_batch.h KernelChoice */
