@@ -4,7 +4,9 @@
 face kernels: cudecompUpdateHalosX (periodic self copy; reference include/internal/halo.h:165-193) and, beside
 it on the same pencil, cudecompAmdAccumulateHalosX (cudecomp_amd.h: the two face additions) and, with --fill,
 cudecompAmdFillHalosX (cudecomp_amd_fill.h: the two halos set to zero) and, with --accumulate-clear,
-cudecompAmdAccumulateAndClearHalosX (cudecomp_amd_fill.h: both in the accumulation's launches).
+cudecompAmdAccumulateAndClearHalosX (cudecomp_amd_fill.h: both in the accumulation's launches) and, with --reflect,
+cudecompAmdReflectHalosX (cudecomp_amd_reflect.h) on the same pencil as a NON-periodic single rank: the odd mirror, centering 0 --
+per dim the cells the periodic update writes, as many cells read, the same two sibling moves in one launch (4 * face bytes).
 Per dim: `--reps` repetitions of `--calls` back-to-back calls each, ms per call of every repetition, their
 min / median / max, and GB/s of the median against the algorithmic bytes (update: 2 faces read + written,
 4 * face bytes; accumulation: 2 faces read, 2 destinations read and written, 6 * face bytes; fill: 2 halos written, 2 * face
@@ -51,6 +53,8 @@ def main():
     ap.add_argument("--fill", action="store_true", help="also time cudecompAmdFillHalosX (value zero), after the other passes")
     ap.add_argument("--accumulate-clear", action="store_true",
                     help="also time cudecompAmdAccumulateAndClearHalosX, after the other passes")
+    ap.add_argument("--reflect", action="store_true",
+                    help="also time cudecompAmdReflectHalosX (non-periodic, parity -1, centering 0), after the other passes")
     ap.add_argument("--json", metavar="FILE", default=None, help="also write the result line to FILE")
     a = ap.parse_args()
     import torch
@@ -123,11 +127,27 @@ def main():
         extra["ghost_cells_not_zero_after_accumulate_clear"] = int(torch.count_nonzero(cells)) - int(torch.count_nonzero(interior))
         extra["interior_sum_after_accumulate_clear"] = float(interior.sum())  # every cell of the pencil lands in the interior once
         extra["cells"] = int(cells.numel())
+    if a.reflect:
+        for dim in range(3):
+            rec = res["dim%d" % dim]
+            ms = _time(lambda: cd.cudecompReflectHalos(0, h, gd, data.data_ptr(), cd.DOUBLE, -1, 0, halo, (0, 0, 0), dim, stream=st),
+                       a.reps, a.calls)
+            rec["reflect"] = _record(ms, 4 * faces[dim] * 8)
+            rec["reflect_kernel"] = cd.cudecompExtLastKernelName()
+            rec["reflect_over_update"] = round(rec["reflect"]["median_ms"] / rec["update"]["median_ms"], 3)
+        # the even mirror of an interior of ones over dims 0, 1, 2 leaves a one in every cell, edges and corners included
+        data.zero_()
+        cells = data.view(shape[2], shape[1], shape[0])
+        cells[a.halo:shape[2] - a.halo, a.halo:shape[1] - a.halo, a.halo:shape[0] - a.halo] = 1.0
+        for dim in range(3):
+            cd.cudecompReflectHalos(0, h, gd, data.data_ptr(), cd.DOUBLE, 1, 0, halo, (0, 0, 0), dim, stream=st)
+        extra["cells_not_one_after_reflect"] = int(cells.numel()) - int(torch.count_nonzero(cells == 1.0))
     cd.cudecompFree(h, gd, work)
     cd.cudecompGridDescDestroy(h, gd)
     line = json.dumps(dict({"workload": "X pencil 2048x1024x256 fp64 + halo %d, periodic single rank, per dim: update (self copy), "
                                         "accumulation (self add)%s; %d repetitions of %d calls"
-                                        % (a.halo, (" and fill (zero)" if a.fill else "") + (" and accumulate-and-clear" if a.accumulate_clear else ""), a.reps, a.calls),
+                                        % (a.halo, (" and fill (zero)" if a.fill else "") + (" and accumulate-and-clear" if a.accumulate_clear else "")
+                                           + (" and reflection (non-periodic, odd mirror, centering 0)" if a.reflect else ""), a.reps, a.calls),
                             "device": torch.cuda.get_device_name(0), "result": res}, **extra))
     print(line)
     if a.json:
@@ -137,6 +157,8 @@ def main():
     if extra.get("ghost_cells_not_zero_after_accumulate_clear") or extra.get("interior_sum_after_accumulate_clear", extra.get("cells")) != extra.get("cells"):
         sys.exit("halo_bench.py: after accumulate-and-clear along 2, 1, 0 %d ghost cells are not zero, the interior sums to %r of %d"
                  % (extra["ghost_cells_not_zero_after_accumulate_clear"], extra["interior_sum_after_accumulate_clear"], extra["cells"]))
+    if extra.get("cells_not_one_after_reflect"):
+        sys.exit("halo_bench.py: after the even mirror along 0, 1, 2 %d cells do not hold the interior's value" % extra["cells_not_one_after_reflect"])
     if extra.get("ghost_cells_not_zero") or extra.get("interior_cells_changed"):
         sys.exit("halo_bench.py: after the fills %d ghost cells are not zero and %d interior cells changed"
                  % (extra["ghost_cells_not_zero"], extra["interior_cells_changed"]))

@@ -151,7 +151,7 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtRunLocalPhases", "cudecompExtEstimateCycleMs", "cudecompExtTrimWorkspacePool", "cudecompExtPlanRelay", "cudecompExtQueueCensus",
                "cudecompExtDescribeMove", "cudecompExtRotateWalk", "cudecompExtPlanHaloAccumulate", "cudecompExtAccumulate3D",
                "cudecompExtPlanHaloFill", "cudecompExtFill3D", "cudecompExtRunMoves", "cudecompExtDescribeMoves",
-               "cudecompExtPlanHaloAccumulateClear"]
+               "cudecompExtPlanHaloAccumulateClear", "cudecompExtPlanHaloReflect", "cudecompExtReflect3D"]
 # include/cudecomp_amd.h: extensions of the API a solver may use
 AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
 # include/cudecomp_amd_fill.h: halo fill
@@ -159,6 +159,8 @@ AMD_FILL_SYMBOLS = ["cudecompAmdFillHalosX", "cudecompAmdFillHalosY", "cudecompA
 # include/cudecomp_amd_accumulate_clear.h (included by cudecomp_amd_fill.h): accumulation that clears the ghost cells it has read
 AMD_ACCUMULATE_CLEAR_SYMBOLS = ["cudecompAmdAccumulateAndClearHalosX", "cudecompAmdAccumulateAndClearHalosY",
                                 "cudecompAmdAccumulateAndClearHalosZ"]
+# include/cudecomp_amd_reflect.h: halo reflection (mirrored ghost cells at the non-periodic edges of the domain)
+AMD_REFLECT_SYMBOLS = ["cudecompAmdReflectHalosX", "cudecompAmdReflectHalosY", "cudecompAmdReflectHalosZ"]
 
 
 class ExtTransposeTimings(C.Structure):
@@ -220,6 +222,8 @@ def lib():
             getattr(L, name).argtypes = [vp, vp, vp, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         for name in AMD_FILL_SYMBOLS:  # (the update's arguments without `work`, plus the value)
             getattr(L, name).argtypes = [vp, vp, vp, i32, vp, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
+        for name in AMD_REFLECT_SYMBOLS:  # (the fill's arguments with parity and centering in the place of the value)
+            getattr(L, name).argtypes = [vp, vp, vp, i32, i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         L.cudecompExtGetTransposePlan.argtypes = [vp, vp, i32, pi32, pi32, pi32, pi32, C.c_bool, i32,
                                                   C.POINTER(ExtTransposePlan)]
         L.cudecompExtGetHaloPlan.argtypes = [vp, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32,
@@ -245,6 +249,9 @@ def lib():
         L.cudecompExtPlanHaloFill.argtypes = L.cudecompExtPlanHalo.argtypes
         L.cudecompExtPlanHaloAccumulateClear.argtypes = L.cudecompExtPlanHalo.argtypes
         L.cudecompExtFill3D.argtypes = [vp, i32, vp, C.POINTER(i64), C.POINTER(i64), i32, pi32, vp]
+        L.cudecompExtPlanHaloReflect.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32,
+                                                 C.POINTER(ExtHaloPlan)]
+        L.cudecompExtReflect3D.argtypes = [vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, pi32, vp]
         L.cudecompExtGetLinkInfo.argtypes = [vp, C.POINTER(ExtLinkInfo)]
         L.cudecompExtEstimateCycleMs.argtypes = [vp, C.POINTER(ExtGridSpec), i32, i32, i32, i32, C.POINTER(C.c_double)]
         L.cudecompExtRunLocalPhases.argtypes = [C.POINTER(ExtGridSpec), i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]
@@ -419,6 +426,19 @@ def cudecompFillHalos(axis, handle, gd, inp, dtype, halo_extents, halo_periods, 
     _check(getattr(lib(), name)(handle, gd, inp, dtype, v, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding), stream), name)
 
 
+def cudecompReflectHalos(axis, handle, gd, inp, dtype, parity, centering, halo_extents, halo_periods, dim, padding=None, stream=None):
+    """cudecompAmdReflectHalos{X,Y,Z} (cudecomp_amd_reflect.h): the ghost cells along `dim` that have no neighbour behind them
+    receive the mirror image of the interior; parity +1 (even mirror) or -1 (odd: sign bits flipped), centering 0 (mirror about
+    the face between ghost and interior cells) or 1 (about the first / last interior cell)."""
+    if parity not in (1, -1):
+        raise ValueError("parity must be +1 or -1, not %r" % (parity,))
+    if centering not in (0, 1):
+        raise ValueError("centering must be 0 or 1, not %r" % (centering,))
+    name = "cudecompAmdReflectHalos" + "XYZ"[axis]
+    _check(getattr(lib(), name)(handle, gd, inp, dtype, int(parity), int(centering), _i3(halo_extents), _b3(halo_periods), dim,
+                                _i3(padding), stream), name)
+
+
 def cudecompExtGetTransposePlan(handle, gd, op, in_halo=None, out_halo=None, in_pad=None, out_pad=None, inplace=False,
                                 backend_override=0):
     p = ExtTransposePlan()
@@ -506,6 +526,15 @@ def cudecompExtPlanHaloFill(grid, rank, axis, halo_extents, halo_periods, dim, p
     p = ExtHaloPlan()
     _check(lib().cudecompExtPlanHaloFill(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim,
                                          _i3(padding), int(force_packed), C.byref(p)), "cudecompExtPlanHaloFill")
+    return p
+
+
+def cudecompExtPlanHaloReflect(grid, rank, axis, halo_extents, halo_periods, dim, padding=None, centering=0, negate=False):
+    """Stateless planner of cudecompAmdReflectHalos*; ExtHaloPlan.reserved bit 12 marks a reflection plan, bit 13 the sign flip
+    (cudecomp_ext.h)."""
+    p = ExtHaloPlan()
+    _check(lib().cudecompExtPlanHaloReflect(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding),
+                                            int(centering), int(bool(negate)), C.byref(p)), "cudecompExtPlanHaloReflect")
     return p
 
 
@@ -612,6 +641,16 @@ def cudecompExtFill3D(dst, es, value, extent, ds, force=0, stream=None):
     return cls.value
 
 
+def cudecompExtReflect3D(src, dst, dtype, negate, extent, ss, ds, force=0, stream=None):
+    """One reflect-move (dst = src, or -src with `negate`; the negative entry of `ss` names the mirrored dim) through the kernel
+    layer; returns the kernel class (0 rows, 2 generic)."""
+    cls = C.c_int32(-1)
+    a = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
+    _check(lib().cudecompExtReflect3D(src, dst, dtype, int(bool(negate)), a(extent), a(ss), a(ds), int(force), C.byref(cls), stream),
+           "cudecompExtReflect3D")
+    return cls.value
+
+
 def cudecompExtRotateWalk(nb, walk=-1):
     """The in-place rotation kernel's orbit walk for nb blocks per edge (no launch, no GPU): (grid, blocks) with blocks an
     int32 array of shape (grid, 3): the block triple of every workgroup, -1 -1 -1 for the ones that map to none."""
@@ -639,6 +678,7 @@ def cudecompExtDescribeMove(src_address, dst_address, es, extent, ss, ds, flags=
 
 MOVES_COPY, MOVES_ADD, MOVES_FILL = 0, 1, 2  # `mode` of cudecompExtRunMoves / cudecompExtDescribeMoves
 MOVES_TAKE, MOVES_ADD_TAKE = 3, 4  # ... the copy / the addition, then zero bytes into the source cells
+MOVES_REFLECT, MOVES_REFLECT_NEGATE = 5, 6  # ... mirror copies (a negative `ss` entry names the mirrored dim), plain / sign bits flipped
 
 
 def make_move(extent, ss, ds, src_off=0, dst_off=0, src_buf=0, dst_buf=1, row_pitch=0):

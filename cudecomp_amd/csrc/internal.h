@@ -14,6 +14,7 @@
 #include "cudecomp.h"
 #include "cudecomp_amd.h"
 #include "cudecomp_amd_fill.h"
+#include "cudecomp_amd_reflect.h"
 #include "decomp.h"
 #include "errors.h"
 #include "kernels.h"
@@ -138,6 +139,8 @@ struct cudecompGridDesc {
   std::map<HaloKey, cudecomp::HaloPlan> halo_accumulate_plans;  // cudecompAmdAccumulateHalos*: the same key, the other operation
   std::map<HaloKey, cudecomp::HaloPlan> halo_fill_plans;        // cudecompAmdFillHalos*: likewise
   std::map<HaloKey, cudecomp::HaloPlan> halo_accumulate_clear_plans;  // cudecompAmdAccumulateAndClearHalos*: likewise
+  // cudecompAmdReflectHalos*: the same key (its last entry unused: always false) plus (centering, sign flip)
+  std::map<std::tuple<HaloKey, int, bool>, cudecomp::HaloPlan> halo_reflect_plans;
 
   // CUDECOMP_ENABLE_CUDA_GRAPHS=1: the per-peer pack loop of the pipelined backends (one kernel + one event
   // record per destination) is captured once per (plan, buffers, element size) and replayed as one graph launch
@@ -267,6 +270,8 @@ void runHaloAccumulateClear(cudecompHandle_t handle, cudecompGridDesc_t gd, int 
                             hipStream_t stream);
 void runHaloFill(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, const void* value,
                  const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream);
+void runHaloReflect(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, int parity,
+                    int centering, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream);
 
 // perf.cc
 struct TransposeTimings {

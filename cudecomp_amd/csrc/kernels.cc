@@ -2,12 +2,12 @@
 //
 // A move is normalised (unit dims dropped, contiguous dims fused, dims sorted by source stride) and classified: classify()
 // writes WHAT runs into one KernelChoice (kernels_batch.h: the kind of kernel -- row copy plain / shifted / dense, LDS-tiled
-// transposition plain / window / lines / row lines, element-wise, the two additions, the two fills, the four takes -- element size, lane width,
+// transposition plain / window / lines / row lines, element-wise, the two additions, the two fills, the four takes, the two reflections -- element size, lane width,
 // tile, access mode) and HOW it walks into the Batch fields beside it.  Moves with equal choices are batched (up to kMaxBatch moves, e.g.
 // the per-peer pack copies of one transpose, share one launch; the descriptors travel in the kernel argument segment).  The
 // batching key, the launcher's instantiation and the kernel's name all come from that one record.  The kernels live in
 // kernels_rows.hip, kernels_transpose.hip (one code object per element size), kernels_window.hip, kernels_lines.hip,
-// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip and kernels_take.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
+// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip and kernels_reflect.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
 // transpose.cc.  kernels_batch.h says why they are separate code objects.
 //
 // 2-byte elements (fp16, bf16) take the row copy (plain kernel), the LDS-tiled transposition (128 x 128 tiles with 16-byte
@@ -48,7 +48,8 @@ struct Classified {
 constexpr long long kDenseMaxGapBytes = 512;  // widest gap between rows the dense row copy rewrites (halo + padding cells)
 
 MoveClass classOf(KernelKind kind) {
-  if (kind == K_GENERIC || kind == K_GENERIC_ADD || kind == K_GENERIC_FILL || kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE)
+  if (kind == K_GENERIC || kind == K_GENERIC_ADD || kind == K_GENERIC_FILL || kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE ||
+      kind == K_GENERIC_REFLECT)
     return MOVE_GENERIC;
   return kind >= K_TRANSPOSE && kind <= K_TRANSPOSE_ROWLINES ? MOVE_TRANSPOSE : MOVE_ROWS_VEC;
 }
@@ -362,6 +363,78 @@ void classifyFill(Classified& c, const Move3D& m, const KernelTuning& tuning, bo
   genericGeometry(c, m);
 }
 
+// Reflect-moves (Move3D::reflect; `arith` the real type when the sign bits are flipped): the row geometry of the copy when the
+// fastest dim is contiguous on both sides and is not the mirrored one -- the mirror then is the sign of the source's row or plane
+// stride -- or the element-wise one; nothing else (only the cells of the move are touched).  They never pass normalizeMove as a
+// whole: the mirrored dim is set aside, the other two are normalised (and fused) as those of a copy, and the mirrored dim comes
+// back as the row or plane index.  Access mode: the project's rule, cached below kStreamBytes, non-temporal loads and stores from
+// there (unmeasured for this kernel); the element-wise kernel always caches.
+Classified classifyReflect(const Move3D& in, void* const bufs[3], int es, const KernelTuning& tuning, bool remote, ArithType arith) {
+  if (in.add || in.fill || in.take || in.dst_row_pitch != 0 || remote)
+    CD_INTERNAL_ERROR("reflect-moves only copy the cells of a local buffer");
+  if (in.negate && (arith == ARITH_NONE || es % arithBytes(arith) != 0 || es / arithBytes(arith) > 2))
+    CD_INTERNAL_ERROR("reflect-move that flips sign bits without a real type that fits the element size");
+  int mirrored = -1;
+  for (int i = 0; i < 3; ++i) {
+    if (in.ds[i] < 0) CD_INTERNAL_ERROR("negative destination stride");
+    if (in.ss[i] >= 0) continue;
+    if (mirrored >= 0) CD_INTERNAL_ERROR("reflect-move with more than one mirrored dim");
+    mirrored = i;
+  }
+  Move3D m = in;
+  const bool live = mirrored >= 0 && in.extent[mirrored] > 1;  // (a mirrored dim one cell thick has no direction)
+  if (mirrored >= 0) {
+    m.extent[mirrored] = 1;
+    m.ss[mirrored] = m.ds[mirrored] = 0;
+  }
+  normalizeMove(m);  // at most two dims remain, in slots 0 and 1
+  Classified c{};
+  c.k.es = es;
+  c.k.arith = in.negate ? arith : ARITH_NONE;
+  c.elements = in.elements();
+  const bool streaming = (c.elements * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming;
+  c.dm.src = static_cast<const char*>(bufs[in.src_buf]) + in.src_off * es;
+  c.dm.dst = static_cast<char*>(bufs[in.dst_buf]) + in.dst_off * es;
+  if (live) {  // back in, slower than the row: slot 1 or 2, ordered by the size of the source stride
+    const int at = (m.extent[1] > 1 && m.ss[1] < -in.ss[mirrored]) ? 2 : 1;
+    if (at == 1) {
+      m.extent[2] = m.extent[1];
+      m.ss[2] = m.ss[1];
+      m.ds[2] = m.ds[1];
+    }
+    m.extent[at] = in.extent[mirrored];
+    m.ss[at] = in.ss[mirrored];
+    m.ds[at] = in.ds[mirrored];
+  }
+  const bool mirrored_fastest = live && (in.ss[mirrored] == -1 || in.ds[mirrored] <= 1);
+  if (tuning.force_class != MOVE_GENERIC && m.ss[0] <= 1 && m.ds[0] <= 1 && !mirrored_fastest) {
+    c.k.kind = K_ROWS_REFLECT;
+    c.k.access = streaming ? 1 : 0;
+    rowVectors(c, m);
+    if (c.k.vec < es) CD_INTERNAL_ERROR("reflect-move narrower than one element");
+    rowTiles(c);
+    return c;
+  }
+  c.k.kind = K_GENERIC_REFLECT;
+  c.k.access = 0;
+  c.k.vec = es;
+  c.p0 = -1;
+  for (int i = 0; i < 3; ++i) {
+    c.dm.e[i] = m.extent[i];
+    c.dm.ss[i] = m.ss[i];
+    c.dm.ds[i] = m.ds[i];
+    if (m.ds[i] == 1 && m.extent[i] > 1) c.p0 = i;
+  }
+  if (c.p0 < 0) {  // no destination-fast dim: along the longest
+    c.p0 = 0;
+    for (int i = 1; i < 3; ++i)
+      if (m.extent[i] > m.extent[c.p0]) c.p0 = i;
+  }
+  const unsigned long long want = ((unsigned long long)c.elements + kThreads - 1) / kThreads;
+  c.blocks = std::min<unsigned long long>(std::max<unsigned long long>(want, 1), 8192);
+  return c;
+}
+
 // Copy moves take any kind of kernel.  Add-moves (Move3D::add, `arith` their real type) take the row geometry of the copy
 // (same extent / address / stride rule) or the element-wise one and nothing else: never shifted, dense or transposing forms
 // (only the cells of the move are touched), never a remote destination, never lanes narrower than one real.  Take-moves
@@ -369,6 +442,8 @@ void classifyFill(Classified& c, const Move3D& m, const KernelTuning& tuning, bo
 // geometries and nothing else, for the same reason -- and because the zero must go where the lane's load went, at its width.
 Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelTuning& tuning, void* dst_base, bool remote,
                     ArithType arith) {
+  if (in.negate && !in.reflect) CD_INTERNAL_ERROR("only reflect-moves flip sign bits");
+  if (in.reflect) return classifyReflect(in, bufs, es, tuning, remote || dst_base != nullptr, arith);
   Move3D m = in;
   if (in.fill) {  // no source: nothing but the destination decides the order and the fusion of the dims
     if (in.add || in.take || in.dst_row_pitch != 0 || remote) CD_INTERNAL_ERROR("fill-moves only store the cells of a local destination");
@@ -465,6 +540,8 @@ void spellKernelName(const KernelChoice& k) {
     case K_GENERIC_ADD_TAKE:
       snprintf(out, n, "generic_accumulate_take_kernel<%s,%d>", arithName(k.arith), k.es / arithBytes(k.arith));
       break;
+    case K_ROWS_REFLECT: snprintf(out, n, "rows_reflect_kernel<%d,%d,%s>", k.vec, s, k.arith != ARITH_NONE ? "true" : "false"); break;
+    case K_GENERIC_REFLECT: snprintf(out, n, "generic_reflect_kernel<%d,%s>", k.es, k.arith != ARITH_NONE ? "true" : "false"); break;
   }
 }
 
@@ -507,6 +584,8 @@ void launchBatch(const KernelChoice& k, const Batch& b, const void* fill_value, 
     case K_GENERIC_TAKE:
     case K_ROWS_ADD_TAKE:
     case K_GENERIC_ADD_TAKE: launchTakeBatch(k, b, blocks, stream); break;
+    case K_ROWS_REFLECT:
+    case K_GENERIC_REFLECT: launchReflectBatch(k, b, blocks, stream); break;
   }
 }
 

@@ -44,6 +44,9 @@ struct KernelTuning {
 // cells of the move and load nothing.
 // Take-moves (Move3D::take, copy or add; kernels_take.hip) store zero bytes to the source cells they have read: local buffers
 // only, sources disjoint from all destinations and from each other; row or element-wise forms over exactly the cells of the move.
+// Reflect-moves (Move3D::reflect: the source runs backwards along one dim; kernels_reflect.hip) copy between disjoint cells of a
+// local buffer, as rows or element-wise, over exactly the cells of the move; with Move3D::negate they need `arith`, the real
+// type whose sign bits are flipped.
 void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
                  const KernelTuning* tuning = nullptr, KernelStats* stats = nullptr,
                  void* const* dst_base_override = nullptr,  // per-move destination base (remote buffers)

@@ -1,8 +1,8 @@
 // kernels_batch.h -- what csrc/kernels.cc (host: classification, batching) and the kernel code objects share: the record of a
 // kernel choice (KernelChoice), the launch descriptor (Batch) and the launchers.  The code objects the classifier dispatches
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
-// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip; kernels_rotate.hip and sync.hip are launched by
-// the executor.
+// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip; kernels_rotate.hip and
+// sync.hip are launched by the executor.
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
 // code object beyond roughly 0.6-0.7 MB puts the whole process into a regime where every small synchronous operation costs
@@ -31,7 +31,8 @@ struct DevMove {
   const char* src;
   char* dst;
   long long e[3];   // extents   (units depend on the kernel, see the launchers)
-  long long ss[3];  // src strides (rows_fill_kernel, which has no source: ss[0] = row length in bytes)
+  long long ss[3];  // src strides (rows_fill_kernel, which has no source: ss[0] = row length in bytes); negative along the
+                    // mirrored dim of a reflect-move, and only there
   long long ds[3];  // dst strides
 };
 
@@ -54,6 +55,7 @@ struct Batch {
   //   element-wise               p0 = the dim the lanes run along, p1 unused
   //   fills                      p0 as for rows / element-wise; p1 unused
   //   takes                      p0 as for rows / element-wise; p1 unused
+  //   reflections                p0 as for rows / element-wise; p1 unused
   int p0[kMaxBatch];
   int p1[kMaxBatch];
   unsigned int first_block[kMaxBatch + 1];
@@ -82,7 +84,9 @@ enum KernelKind {
   K_ROWS_TAKE,           // rows_take_kernel (dst = src; src = 0)
   K_GENERIC_TAKE,        // generic_take_kernel
   K_ROWS_ADD_TAKE,       // rows_accumulate_take_kernel (dst += src; src = 0)
-  K_GENERIC_ADD_TAKE     // generic_accumulate_take_kernel
+  K_GENERIC_ADD_TAKE,    // generic_accumulate_take_kernel
+  K_ROWS_REFLECT,        // rows_reflect_kernel (dst = src or dst = -src, the source backwards along the row or plane index)
+  K_GENERIC_REFLECT      // generic_reflect_kernel
 };
 struct KernelChoice {
   KernelKind kind;
@@ -91,8 +95,9 @@ struct KernelChoice {
   int ti, tj;       // transposes: the tile (elements, i x j); 0 otherwise
   int access;       // copies: 0 default caching, 2 non-temporal loads + stores, 3 non-temporal loads + remote (system-scope
                     // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads;
-                    // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it)
-  ArithType arith;  // additions: the real type the elements consist of; ARITH_NONE otherwise
+                    // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it);
+                    // reflections: 0, 1 non-temporal loads and stores
+  ArithType arith;  // additions, reflections that flip the sign bits: the real type the elements consist of; ARITH_NONE otherwise
   bool operator==(const KernelChoice& o) const {
     return kind == o.kind && es == o.es && vec == o.vec && ti == o.ti && tj == o.tj && access == o.access && arith == o.arith;
   }
@@ -107,6 +112,8 @@ inline int streamArgOf(KernelKind kind, int access) {
   if (kind == K_GENERIC_FILL) return 0;
   if (kind == K_ROWS_TAKE || kind == K_ROWS_ADD_TAKE) return access;
   if (kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE) return 0;
+  if (kind == K_ROWS_REFLECT) return access;
+  if (kind == K_GENERIC_REFLECT) return 0;
   if (kind == K_TRANSPOSE_WINDOW || kind == K_TRANSPOSE_LINES || kind == K_TRANSPOSE_ROWLINES)
     return access == 2 ? 4 : access;  // always cached loads: the overlap rows of neighbouring windows hit in L2
   return access == 3 ? 3 : (access >= 1 ? 1 : 0);  // row copies: loads and stores stream together
@@ -136,6 +143,14 @@ void launchFillBatch(const KernelChoice& k, const kern::Batch& b, const FillPatt
 // kernels_take.hip: take-moves (the copy or the addition, then src = 0).  The Batch of the row copies / additions and of their
 // generic forms; local buffers only.
 void launchTakeBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+// kernels_reflect.hip: reflect-moves (dst = src or dst = -src with the source running backwards along one dim).  Rows: the Batch of
+// rows_kernel with SIGNED byte strides ss[1], ss[2] (the mirror is folded into them).  Generic: extents / strides in elements,
+// signed.  k.arith != ARITH_NONE: the sign bit of every real of that type is inverted; the mask travels as a 16-byte kernel
+// argument of its own.  Local buffers only.
+struct SignMask {
+  unsigned int w[4];
+};
+void launchReflectBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

@@ -451,6 +451,48 @@ HaloPlan buildHaloFillPlan(const GridShape& g, int rank, int axis, int dim, cons
   return p;
 }
 
+HaloPlan buildHaloReflectPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                              const int32_t* pad, int centering, bool negate, bool self_exchange) {
+  const HaloPlan u = buildHaloPlan(g, rank, axis, dim, halo, periods, pad, false, self_exchange);  // (its refusals, its neighbours)
+  if (centering != 0 && centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
+  HaloPlan p;
+  p.axis = axis;
+  p.dim = dim;
+  p.reflect = true;
+  p.negate = negate;
+  p.comm_axis = commAxisOfDim(axis, dim);
+  p.neighbor[0] = u.neighbor[0];
+  p.neighbor[1] = u.neighbor[1];
+  const i64 he = halo[dim];
+  if (he == 0 || (p.neighbor[0] != -1 && p.neighbor[1] != -1)) return p;
+
+  const auto pidx = gridIndexOfRank(g, rank);
+  const Pencil h = makePencil(g, pidx, axis, halo, nullptr);
+  const Pencil hp = makePencil(g, pidx, axis, halo, pad);
+  const i64 c = centering;
+  if (he + c > h.extentG(dim) - 2 * he) CD_INVALID_USAGE("halo reflection reaches beyond the interior of the pencil");
+  // the slabs of buildHaloPlan: thickness he along `dim`, the other two dims INCLUDING their halos, not their padding
+  i64 E[3], st[3], sst[3];
+  for (int ga = 0; ga < 3; ++ga) {
+    E[ga] = (ga == dim) ? he : h.extentG(ga);
+    st[ga] = hp.strideG(ga);
+    sst[ga] = (ga == dim) ? -st[ga] : st[ga];
+  }
+  p.face_elements = E[0] * E[1] * E[2];
+  const i64 sd = st[dim];
+  const i64 n = hp.extentG(dim) - (pad ? pad[dim] : 0);  // extent along dim without padding
+  auto mirroring = [&](i64 src_cell, i64 dst_cell, int side) {  // destination cell dst_cell + j takes source cell src_cell - j
+    Move3D m = blockMove(BUF_IN, src_cell * sd, sst, BUF_IN, dst_cell * sd, st, E, side);
+    m.reflect = true;
+    m.negate = negate;
+    return m;
+  };
+  if (p.neighbor[0] == -1) p.pre.push_back(mirroring(2 * he - 1 + c, 0, 0));
+  if (p.neighbor[1] == -1) p.pre.push_back(mirroring(n - he - 1 - c, n - he, 1));
+  p.kind = HaloPlan::SELF_PERIODIC;
+  return p;
+}
+
 int normalizeMove(Move3D& m) {
   struct D {
     i64 e, s, d;

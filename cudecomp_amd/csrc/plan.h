@@ -51,6 +51,14 @@ struct Move3D {
   // are disjoint from every destination and every other source of the phase; exactly the source cells of the move are written,
   // never the gap cells between rows (dst_row_pitch is never set), never a peer's memory.
   bool take = false;
+  // true: the source runs BACKWARDS along one dim (halo reflection, buildHaloReflectPlan): that dim has a negative source stride
+  // and src_off names the source cell of its index 0.  Only reflect-moves may have a negative stride.  Source and destination are
+  // disjoint cells of one local buffer; exactly the destination cells of the move are written and exactly its source cells read.
+  // A reflect-move never carries dst_row_pitch, add, fill, take or a remote destination (an internal error before any launch).
+  bool reflect = false;
+  // reflect-moves only: the sign bit of every real component is inverted on the way (one bit per real, two per complex element);
+  // nothing else about the bytes changes.
+  bool negate = false;
 
   i64 elements() const { return extent[0] * extent[1] * extent[2]; }
 };
@@ -165,6 +173,8 @@ struct HaloPlan {
   bool ordered = false;  // the destinations of the two add-moves overlap (interior narrower than two halos): one launch each, in order
   bool fill = false;     // fill plans (buildHaloFillPlan) only
   bool clear = false;    // fused accumulate-and-clear plans (buildHaloAccumulateClearPlan) only
+  bool reflect = false;  // reflection plans (buildHaloReflectPlan) only
+  bool negate = false;   // ... whose moves flip the sign bits (parity -1)
 };
 
 HaloPlan buildHaloPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
@@ -196,6 +206,16 @@ HaloPlan buildHaloAccumulateClearPlan(const GridShape& g, int rank, int axis, in
 // (Move3D::fill), the low side then the high side, destination only, in BUF_IN; their cells never overlap.
 HaloPlan buildHaloFillPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
                            const int32_t* pad, bool force_packed, bool self_exchange = false);
+
+// Halo REFLECTION along `dim` (include/cudecomp_amd_reflect.h has the contract): the ghost cells the update along `dim` does NOT
+// write -- the low halo where there is no low neighbour, the high halo where there is no high one -- receive the mirror image of
+// the interior: low side cell(h-1-k) = cell(h+k+c), high side cell(n-h+k) = cell(n-h-1-k-c), k in [0, h), c = centering.  The
+// refusals of buildHaloPlan first; then a side that would be written with h + c > n - 2h (the sources would leave the rank's
+// interior) is INVALID_USAGE.  Kinds: NONE or SELF_PERIODIC ("local", as for fill plans).  `pre` holds at most two reflect-moves
+// (Move3D::reflect, Move3D::negate = `negate`) pencil -> pencil in BUF_IN, the low side then the high side: the destination runs
+// forwards over the halo slab (the other two dims INCLUDING their halos, not their padding), the source backwards along `dim`.
+HaloPlan buildHaloReflectPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                              const int32_t* pad, int centering, bool negate, bool self_exchange = false);
 
 // Number of stages every member of the communicator arrives at without talking: at most `wanted`, at most the smallest
 // chunk extent, at most 14 (flag steps), and no stage smaller than `min_stage_bytes` of the largest pencil (below that the extra

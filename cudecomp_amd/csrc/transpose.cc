@@ -559,4 +559,35 @@ void runHaloFill(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* inpu
   launchMoves(plan.pre.data(), (int)plan.pre.size(), bufs, es, stream, &h->tuning, nullptr, nullptr, ARITH_NONE, value);
 }
 
+// Halo reflection (cudecompAmdReflectHalos*): the ghost cells the update does NOT write -- those at a non-periodic edge of the
+// domain -- receive the mirror image of the interior, both sides in one launch.  Local: no workspace, no exchange.  The checks
+// come in the contract's order: what the fill refuses, then parity / centering, then a mirror that reaches beyond the interior.
+void runHaloReflect(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, int parity,
+                    int centering, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
+  const int es = elementSize(dtype);
+  const auto hh = arr3(halo), pp = arr3(pad);
+  std::array<bool, 3> per{false, false, false};
+  if (periods)
+    for (int i = 0; i < 3; ++i) per[i] = periods[i];
+  if ((parity != 1 && parity != -1) || (centering != 0 && centering != 1)) {
+    buildHaloPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), false, h->self_exchange);  // (the fill's refusals)
+    if (parity != 1 && parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
+    CD_INVALID_USAGE("centering argument must be 0 or 1");
+  }
+  const bool negate = parity == -1;
+  const cudecompGridDesc::HaloKey hkey{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, false};
+  const auto key = std::make_tuple(hkey, centering, negate);
+  auto it = gd->halo_reflect_plans.find(key);
+  if (it == gd->halo_reflect_plans.end()) {
+    HaloPlan p = buildHaloReflectPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), centering, negate, h->self_exchange);
+    it = gd->halo_reflect_plans.emplace(key, std::move(p)).first;
+  }
+  const HaloPlan& plan = it->second;
+  if (plan.kind == HaloPlan::NONE) return;
+
+  ensureDevice(h);
+  void* bufs[3] = {input, input, nullptr};
+  launchMoves(plan.pre.data(), (int)plan.pre.size(), bufs, es, stream, &h->tuning, nullptr, nullptr, negate ? arithOf(dtype) : ARITH_NONE);
+}
+
 }  // namespace cudecomp

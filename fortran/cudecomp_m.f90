@@ -539,6 +539,55 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompAmdAccumulateAndClearHalosZ_C
 
+    ! cudecomp_amd_reflect.h: halo reflection (mirrored ghost cells at the non-periodic edges of the domain)
+    function cudecompAmdReflectHalosX_C(handle, grid_desc, input, dtype, parity, centering, halo_extents, halo_periods, dim, &
+                                        padding, stream) bind(C, name="cudecompAmdReflectHalosX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      integer(c_int32_t), value :: parity, centering
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdReflectHalosX_C
+
+    function cudecompAmdReflectHalosY_C(handle, grid_desc, input, dtype, parity, centering, halo_extents, halo_periods, dim, &
+                                        padding, stream) bind(C, name="cudecompAmdReflectHalosY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      integer(c_int32_t), value :: parity, centering
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdReflectHalosY_C
+
+    function cudecompAmdReflectHalosZ_C(handle, grid_desc, input, dtype, parity, centering, halo_extents, halo_periods, dim, &
+                                        padding, stream) bind(C, name="cudecompAmdReflectHalosZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      integer(c_int32_t), value :: parity, centering
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdReflectHalosZ_C
+
 
     function cudecomp_c_strlen(str) bind(C, name="strlen") result(n)
       import
@@ -1147,6 +1196,73 @@ contains
     res = cudecompAmdAccumulateAndClearHalosZ_C(handle, grid_desc, c_loc(input), c_loc(work), int(dtype, c_int), h, per, &
                                         int(dim - 1, c_int32_t), p, s)
   end function cudecompAmdAccumulateAndClearHalosZ
+
+  ! ---- halo reflection (cudecomp_amd_reflect.h): the arguments of the fill with parity and centering in the place of the value ----
+  function cudecompAmdReflectHalosX(handle, grid_desc, input, dtype, parity, centering, halo_extents, halo_periods, dim, &
+                                    padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: parity     ! +1: even mirror; -1: odd mirror (sign bits flipped)
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdReflectHalosX_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
+                                      int(centering, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdReflectHalosX
+
+  function cudecompAmdReflectHalosY(handle, grid_desc, input, dtype, parity, centering, halo_extents, halo_periods, dim, &
+                                    padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: parity     ! +1: even mirror; -1: odd mirror (sign bits flipped)
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdReflectHalosY_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
+                                      int(centering, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdReflectHalosY
+
+  function cudecompAmdReflectHalosZ(handle, grid_desc, input, dtype, parity, centering, halo_extents, halo_periods, dim, &
+                                    padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: parity     ! +1: even mirror; -1: odd mirror (sign bits flipped)
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdReflectHalosZ_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
+                                      int(centering, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdReflectHalosZ
 
 
   subroutine halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
