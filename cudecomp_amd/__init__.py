@@ -161,6 +161,9 @@ AMD_ACCUMULATE_CLEAR_SYMBOLS = ["cudecompAmdAccumulateAndClearHalosX", "cudecomp
                                 "cudecompAmdAccumulateAndClearHalosZ"]
 # include/cudecomp_amd_reflect.h: halo reflection (mirrored ghost cells at the non-periodic edges of the domain)
 AMD_REFLECT_SYMBOLS = ["cudecompAmdReflectHalosX", "cudecompAmdReflectHalosY", "cudecompAmdReflectHalosZ"]
+# the four extension headers and the functions each of them declares itself (checked by tests/test_abi.py, like API_SYMBOLS)
+AMD_HEADER_SYMBOLS = {"cudecomp_amd.h": AMD_SYMBOLS, "cudecomp_amd_fill.h": AMD_FILL_SYMBOLS,
+                      "cudecomp_amd_accumulate_clear.h": AMD_ACCUMULATE_CLEAR_SYMBOLS, "cudecomp_amd_reflect.h": AMD_REFLECT_SYMBOLS}
 
 
 class ExtTransposeTimings(C.Structure):

@@ -37,7 +37,12 @@
 #include "cudecomp.h"
 #include "cudecomp_ext.h"
 
-#if defined(R32)
+#if defined(H16)
+// (halo_ops_test only) 2-byte elements of cudecomp_amd.h, carried as bit patterns: the host never computes in them
+#include "cudecomp_amd.h"
+using elem_t = uint16_t;
+static const cudecompDataType_t kDtype = CUDECOMP_AMD_HALF;
+#elif defined(R32)
 using elem_t = float;
 static const cudecompDataType_t kDtype = CUDECOMP_FLOAT;
 #elif defined(C32)
@@ -55,6 +60,15 @@ inline void make(float& e, double v) { e = (float)v; }
 inline void make(double& e, double v) { e = v; }
 inline void make(std::complex<float>& e, double v) { e = std::complex<float>((float)v, (float)-v); }
 inline void make(std::complex<double>& e, double v) { e = std::complex<double>(v, -v); }
+// IEEE binary16 bit pattern of an integer of magnitude below 2048 (exact: eleven significant bits)
+inline uint16_t halfBitsOfInt(int v) {
+  if (v == 0) return 0;
+  const unsigned a = (unsigned)(v < 0 ? -v : v);
+  int e = 0;
+  while (a >> (e + 1)) ++e;  // a in [2^e, 2^(e+1))
+  return (uint16_t)((v < 0 ? 0x8000u : 0u) | ((unsigned)(e + 15) << 10) | ((a << (10 - e)) & 0x3ffu));
+}
+inline void make(uint16_t& e, double v) { e = halfBitsOfInt((int)v); }
 
 struct TestFailure : std::runtime_error {
   using std::runtime_error::runtime_error;

@@ -27,6 +27,77 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared | declared_functions("cudecomp_ext.h")):
         assert hasattr(L, name), name
     assert declared_functions("cudecomp_ext.h") == set(cd.EXT_SYMBOLS)
+    # the extensions a solver may use: one header each, every declared function exported and named in the package's list
+    assert sorted(cd.AMD_HEADER_SYMBOLS) == sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.startswith("cudecomp_amd"))
+    for header, names in cd.AMD_HEADER_SYMBOLS.items():
+        assert declared_functions(header) == set(names) and len(names) == 3, header
+        for name in names:
+            assert hasattr(L, name), name
+
+
+def declared_prototypes(header):
+    """{function: [parameter text, ...]} of the cudecompResult_t functions a header declares"""
+    src = open(os.path.join(ROOT, "include", header)).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return {name: [" ".join(a.split()) for a in args.split(",")]
+            for name, args in re.findall(r"cudecompResult_t\s+(cudecomp\w+)\s*\(([^)]*)\)\s*;", src)}
+
+
+def test_extension_prototypes_agree_with_the_argtypes():
+    """The twelve halo extensions: as many parameters in the header as in the ctypes argtypes every Python test calls through, and
+    the pointers -- arrays, buffers, and the handle, descriptor and stream, which are pointers in C -- at the same positions."""
+    L = cd.lib()
+    opaque = ("cudecompHandle_t", "cudecompGridDesc_t", "hipStream_t")
+    seen = 0
+    for header, names in cd.AMD_HEADER_SYMBOLS.items():
+        protos = declared_prototypes(header)
+        assert sorted(protos) == sorted(names)
+        for name, params in protos.items():
+            argtypes = getattr(L, name).argtypes
+            assert len(params) == len(argtypes), (name, params)
+            in_header = ["*" in p or "[" in p or p.split()[0] in opaque for p in params]
+            in_python = [t is C.c_void_p or t is C.c_char_p or hasattr(t, "contents") for t in argtypes]
+            assert in_header == in_python, (name, params, argtypes)
+            # what is passed by value is a 32-bit integer on both sides (the enum is one: values -4..3)
+            assert all(p.split()[0] in ("int32_t", "cudecompDataType_t") for p, ptr in zip(params, in_header) if not ptr), (name, params)
+            assert all(t is C.c_int32 for t, ptr in zip(argtypes, in_python) if not ptr), (name, argtypes)
+            seen += 1
+    assert seen == 12
+
+
+def test_extension_dtype_macros_are_the_values_the_library_takes():
+    """CUDECOMP_AMD_HALF, _BFLOAT16, _HALF_COMPLEX of cudecomp_amd.h against the package's numbers (what every Python test passes)
+    and the element sizes the library reports for them."""
+    src = open(os.path.join(ROOT, "include", "cudecomp_amd.h")).read()
+    macros = {n: int(v) for n, v in re.findall(r"#define\s+CUDECOMP_AMD_(\w+)\s+\(\(cudecompDataType_t\)\s*(-?\d+)\)", src)}
+    assert macros == {"HALF": cd.HALF, "BFLOAT16": cd.BFLOAT16, "HALF_COMPLEX": cd.HALF_COMPLEX} == {"HALF": 1, "BFLOAT16": 2, "HALF_COMPLEX": 3}
+    assert [cd.cudecompGetDataTypeSize(macros[n]) for n in ("HALF", "BFLOAT16", "HALF_COMPLEX")] == [2, 2, 4]
+
+
+def test_extension_headers_compile_as_c11():
+    """tests/native/headers_c11.c: the four headers in every order a user could include them, -Wall -Wextra -Werror, every function
+    assigned to a pointer of the prototype written out by hand; defines and include paths of tests/native/subcomm_test.c."""
+    import itertools
+    import shutil
+    import subprocess
+    if shutil.which("gcc") is None:
+        pytest.skip("no gcc")
+    mpi = ["-DCUDECOMP_USE_MPI_HEADER", "-I/opt/conda/include"] if os.path.exists("/opt/conda/include/mpi.h") else []
+    base = ["gcc", "-std=c11", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROOT, "include"),
+            "-I/opt/rocm/include"] + mpi
+    source = os.path.join(ROOT, "tests", "native", "headers_c11.c")
+    orders = [None] + list(itertools.permutations(sorted(cd.AMD_HEADER_SYMBOLS)))
+    for order in orders:
+        defs = [] if order is None else ['-DINC%d="%s"' % (i + 1, h) for i, h in enumerate(order)]
+        res = subprocess.run(base + defs + [source], capture_output=True, text=True)
+        assert res.returncode == 0 and not res.stderr.strip(), (order, res.stderr[-3000:])
+    # the file does notice a prototype that differs: `parity` and `centering` are int32_t, a pointer in their place is an error
+    with open(source) as f:
+        text = f.read()
+    broken = text.replace("int32_t parity, int32_t centering", "const int32_t* parity, int32_t centering")
+    assert broken != text
+    res = subprocess.run(base + ["-x", "c", "-"], input=broken, capture_output=True, text=True, cwd=os.path.dirname(source))
+    assert res.returncode != 0 and "incompatible" in res.stderr, res.stderr[-3000:]
 
 
 def test_struct_layouts_match_reference_abi():

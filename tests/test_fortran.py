@@ -119,6 +119,7 @@ def _run_fortran(name, dtype, nranks, lines, env=None):
             for r, text in enumerate(logs):
                 f.write("===== rank %d =====\n%s\n" % (r, text[-20000:]))
     assert ok, out[-3000:]
+    return out
 
 
 TRANSPOSE_LINES = {
@@ -163,6 +164,93 @@ HALO_LINES = {
 def test_fortran_halo_update(nranks, dtype):
     env = {"CUDECOMP_AUTOTUNE_HALO_BACKENDS": "^NCCL"} if nranks > 1 else None
     _run_fortran("halo_test", dtype, nranks, HALO_LINES[nranks], env)
+
+
+# ---- the halo extensions through the module's wrappers (tests/fortran/halo_ops_test.f90, twin of tests/native/halo_ops_test.cpp):
+# twelve hand-written wrappers and interface blocks that nothing else calls.  The lists vary the argument forms -- `padding`,
+# `stream` and the fill's `value` present and absent, mixed halo_periods -- so that every present() branch runs both ways.
+def _called_wrappers(out):
+    return sorted(line.split()[1] for line in out.splitlines() if line.startswith("WRAPPER "))
+
+
+def _all_wrappers():
+    import cudecomp_amd as cd
+    return sorted(cd.AMD_SYMBOLS + cd.AMD_FILL_SYMBOLS + cd.AMD_ACCUMULATE_CLEAR_SYMBOLS + cd.AMD_REFLECT_SYMBOLS)
+
+
+def _varies_every_form(lines):
+    """padding, stream and value each present and absent, and mixed periods, somewhere in the list"""
+    fills = [l for l in lines if l.startswith("--op fill ")]
+    return (any("--nullpad" in l for l in lines) and any("--nullpad" not in l for l in lines) and
+            any("--stream" in l for l in lines) and any("--stream" not in l for l in lines) and
+            any("--value" in l for l in fills) and any("--value" not in l for l in fills) and
+            any("--hpx 1 --hpy 0 --hpz 1" in l for l in lines))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["R32", "R64", "C32", "C64"])
+def test_fortran_halo_ops_single_rank(dtype):
+    from tests.halo_ops_cases import Forms, mem_order_lines, single_rank_lines
+    forms = Forms(base=1, stream=True)
+    lines = single_rank_lines(forms)
+    if dtype == "R64":
+        lines += mem_order_lines(forms)
+    assert _varies_every_form(lines)
+    out = _run_fortran("halo_ops_test", dtype, 1, lines)
+    assert _called_wrappers(out) == _all_wrappers() and len(_all_wrappers()) == 12
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["R64", "C32"])
+def test_fortran_halo_ops_four_ranks(dtype):
+    """Four ranks sharing the GPU: the communicating operations over 2 x 2, 1 x 4, 4 x 1 and halo backends 1, 2, 4; fill and
+    reflection over one backend."""
+    from tests.halo_ops_cases import COMMUNICATING, LOCAL, Forms, four_rank_lines
+    forms = Forms(base=1, stream=True)
+    grids = [(2, 2), (1, 4), (4, 1)]
+    lines = four_rank_lines(forms, grids, [1, 2, 4], COMMUNICATING, diagonal=True) + four_rank_lines(forms, grids, [1], LOCAL, diagonal=True)
+    assert _varies_every_form(lines)
+    out = _run_fortran("halo_ops_test", dtype, 4, lines)
+    assert _called_wrappers(out) == _all_wrappers()
+
+
+@pytest.mark.gpu
+def test_fortran_halo_ops_four_ranks_rccl_code_path():
+    from tests.halo_ops_cases import COMMUNICATING, Forms, four_rank_lines
+    shim = os.path.join(ROOT, "tests", "shim", "libfake_rccl.so")
+    if not os.path.exists(shim):
+        pytest.skip("tests/shim/libfake_rccl.so not built")
+    lines = four_rank_lines(Forms(base=1, stream=True), [(2, 2), (4, 1)], [3], COMMUNICATING, diagonal=True)
+    _run_fortran("halo_ops_test", "R64", 4, lines, {"LD_PRELOAD": shim})
+
+
+@pytest.mark.gpu
+def test_fortran_halo_ops_refusals():
+    from tests.halo_ops_cases import Forms, refusal_lines
+    lines, refused = refusal_lines(Forms(base=1, stream=True))
+    assert refused == 9
+    _run_fortran("halo_ops_test", "R64", 1, lines)
+
+
+@pytest.mark.gpu
+def test_fortran_halo_ops_comparison_can_fail():
+    """--self-check-shift-dim: the second of three cases calls along the next dim while expecting `dim`: FAILED, and the list ends there."""
+    import tempfile
+    import time
+    from tests.halo_ops_cases import Forms, single_rank_lines
+    good = single_rank_lines(Forms(base=1), ops=("accumulate_clear",))[:3]
+    with tempfile.NamedTemporaryFile("w", suffix="_cases.txt", delete=False) as f:
+        f.write("\n".join([good[0], good[1] + " --self-check-shift-dim", good[2]]) + "\n")
+    t0 = time.time()
+    try:
+        with pytest.raises(AssertionError) as e:
+            run_binary_ranks(1, [_fbin("halo_ops_test", "R64"), "--testfile", f.name], 120)
+    finally:
+        os.unlink(f.name)
+    text = str(e.value)
+    assert text.count(" PASSED") == 1 and text.count(" FAILED") == 1 and "Failed 1/3 tests." in text, text[-2000:]
+    assert "words differ after accumulate_clear along dim" in text, text[-2000:]
+    assert time.time() - t0 < 30
 
 
 @pytest.mark.gpu
