@@ -6,7 +6,10 @@ it on the same pencil, cudecompAmdAccumulateHalosX (cudecomp_amd.h: the two face
 cudecompAmdFillHalosX (cudecomp_amd_fill.h: the two halos set to zero) and, with --accumulate-clear,
 cudecompAmdAccumulateAndClearHalosX (cudecomp_amd_fill.h: both in the accumulation's launches) and, with --reflect,
 cudecompAmdReflectHalosX (cudecomp_amd_reflect.h) on the same pencil as a NON-periodic single rank: the odd mirror, centering 0 --
-per dim the cells the periodic update writes, as many cells read, the same two sibling moves in one launch (4 * face bytes).
+per dim the cells the periodic update writes, as many cells read, the same two sibling moves in one launch (4 * face bytes) and, with
+--fold / --fold-clear, cudecompAmdFoldHalosX (cudecomp_halo_fold.h), the reflection's transpose, on the same non-periodic single rank
+with parity -1, centering 0 and clear 0 / 1: the reflection's two sibling moves the other way round, the destinations read as well
+(6 * face bytes), the ghost cells zeroed as well (8 * face bytes).
 Per dim: `--reps` repetitions of `--calls` back-to-back calls each, ms per call of every repetition, their
 min / median / max, and GB/s of the median against the algorithmic bytes (update: 2 faces read + written,
 4 * face bytes; accumulation: 2 faces read, 2 destinations read and written, 6 * face bytes; fill: 2 halos written, 2 * face
@@ -55,6 +58,9 @@ def main():
                     help="also time cudecompAmdAccumulateAndClearHalosX, after the other passes")
     ap.add_argument("--reflect", action="store_true",
                     help="also time cudecompAmdReflectHalosX (non-periodic, parity -1, centering 0), after the other passes")
+    ap.add_argument("--fold", action="store_true",
+                    help="also time cudecompAmdFoldHalosX (non-periodic, parity -1, centering 0, clear 0), after the other passes")
+    ap.add_argument("--fold-clear", action="store_true", help="... and with clear 1")
     ap.add_argument("--json", metavar="FILE", default=None, help="also write the result line to FILE")
     a = ap.parse_args()
     import torch
@@ -142,12 +148,43 @@ def main():
         for dim in range(3):
             cd.cudecompReflectHalos(0, h, gd, data.data_ptr(), cd.DOUBLE, 1, 0, halo, (0, 0, 0), dim, stream=st)
         extra["cells_not_one_after_reflect"] = int(cells.numel()) - int(torch.count_nonzero(cells == 1.0))
+    for clear, wanted in ((0, a.fold), (1, a.fold_clear)):
+        if not wanted:
+            continue
+        name = "fold_clear" if clear else "fold"
+        data.zero_()
+        for dim in range(3):
+            rec = res["dim%d" % dim]
+            ms = _time(lambda: cd.cudecompFoldHalos(0, h, gd, data.data_ptr(), cd.DOUBLE, -1, 0, clear, halo, (0, 0, 0), dim, stream=st),
+                       a.reps, a.calls)
+            rec[name] = _record(ms, (8 if clear else 6) * faces[dim] * 8)
+            rec[name + "_kernel"] = cd.cudecompExtLastKernelName()
+            rec[name + "_over_update"] = round(rec[name]["median_ms"] / rec["update"]["median_ms"], 3)
+        # a pencil of ones folded with parity +1 and clearing along dims 2, 1, 0: an interior cell holds the number of cells of the
+        # pencil that mirror onto it -- per dim one more for every wall it lies within `halo` cells of -- and every ghost cell zero
+        data.fill_(1.0)
+        cells = data.view(shape[2], shape[1], shape[0])
+        for dim in (2, 1, 0):
+            cd.cudecompFoldHalos(0, h, gd, data.data_ptr(), cd.DOUBLE, 1, 0, 1, halo, (0, 0, 0), dim, stream=st)
+        count = []
+        for dim in range(3):
+            g = shape[dim] - 2 * a.halo
+            c = torch.ones(g, dtype=torch.float64, device="cuda")
+            c[:a.halo] += 1.0
+            c[g - a.halo:] += 1.0
+            count.append(c)
+        expected = count[2][:, None, None] * count[1][None, :, None] * count[0][None, None, :]
+        interior = cells[a.halo:shape[2] - a.halo, a.halo:shape[1] - a.halo, a.halo:shape[0] - a.halo]
+        extra["interior_cells_with_another_count_after_" + name] = int(torch.count_nonzero(interior != expected))
+        extra["ghost_cells_not_zero_after_" + name] = int(torch.count_nonzero(cells)) - int(torch.count_nonzero(interior))
     cd.cudecompFree(h, gd, work)
     cd.cudecompGridDescDestroy(h, gd)
     line = json.dumps(dict({"workload": "X pencil 2048x1024x256 fp64 + halo %d, periodic single rank, per dim: update (self copy), "
                                         "accumulation (self add)%s; %d repetitions of %d calls"
                                         % (a.halo, (" and fill (zero)" if a.fill else "") + (" and accumulate-and-clear" if a.accumulate_clear else "")
-                                           + (" and reflection (non-periodic, odd mirror, centering 0)" if a.reflect else ""), a.reps, a.calls),
+                                           + (" and reflection (non-periodic, odd mirror, centering 0)" if a.reflect else "")
+                                           + (" and fold (non-periodic, parity -1, centering 0)" if a.fold else "")
+                                           + (" and fold with clear" if a.fold_clear else ""), a.reps, a.calls),
                             "device": torch.cuda.get_device_name(0), "result": res}, **extra))
     print(line)
     if a.json:
@@ -157,6 +194,11 @@ def main():
     if extra.get("ghost_cells_not_zero_after_accumulate_clear") or extra.get("interior_sum_after_accumulate_clear", extra.get("cells")) != extra.get("cells"):
         sys.exit("halo_bench.py: after accumulate-and-clear along 2, 1, 0 %d ghost cells are not zero, the interior sums to %r of %d"
                  % (extra["ghost_cells_not_zero_after_accumulate_clear"], extra["interior_sum_after_accumulate_clear"], extra["cells"]))
+    for name in ("fold", "fold_clear"):
+        if extra.get("interior_cells_with_another_count_after_" + name) or extra.get("ghost_cells_not_zero_after_" + name):
+            sys.exit("halo_bench.py: after folding a pencil of ones along 2, 1, 0 (%s pass) %d interior cells do not hold their count and %d "
+                     "ghost cells are not zero" % (name, extra["interior_cells_with_another_count_after_" + name],
+                                                   extra["ghost_cells_not_zero_after_" + name]))
     if extra.get("cells_not_one_after_reflect"):
         sys.exit("halo_bench.py: after the even mirror along 0, 1, 2 %d cells do not hold the interior's value" % extra["cells_not_one_after_reflect"])
     if extra.get("ghost_cells_not_zero") or extra.get("interior_cells_changed"):

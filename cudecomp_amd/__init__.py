@@ -151,7 +151,8 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtRunLocalPhases", "cudecompExtEstimateCycleMs", "cudecompExtTrimWorkspacePool", "cudecompExtPlanRelay", "cudecompExtQueueCensus",
                "cudecompExtDescribeMove", "cudecompExtRotateWalk", "cudecompExtPlanHaloAccumulate", "cudecompExtAccumulate3D",
                "cudecompExtPlanHaloFill", "cudecompExtFill3D", "cudecompExtRunMoves", "cudecompExtDescribeMoves",
-               "cudecompExtPlanHaloAccumulateClear", "cudecompExtPlanHaloReflect", "cudecompExtReflect3D"]
+               "cudecompExtPlanHaloAccumulateClear", "cudecompExtPlanHaloReflect", "cudecompExtReflect3D",
+               "cudecompExtPlanHaloFold", "cudecompExtFold3D"]
 # include/cudecomp_amd.h: extensions of the API a solver may use
 AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
 # include/cudecomp_amd_fill.h: halo fill
@@ -161,6 +162,8 @@ AMD_ACCUMULATE_CLEAR_SYMBOLS = ["cudecompAmdAccumulateAndClearHalosX", "cudecomp
                                 "cudecompAmdAccumulateAndClearHalosZ"]
 # include/cudecomp_amd_reflect.h: halo reflection (mirrored ghost cells at the non-periodic edges of the domain)
 AMD_REFLECT_SYMBOLS = ["cudecompAmdReflectHalosX", "cudecompAmdReflectHalosY", "cudecompAmdReflectHalosZ"]
+# include/cudecomp_halo_fold.h: halo folding (the ghost cells the reflection writes, summed into their mirror images)
+AMD_FOLD_SYMBOLS = ["cudecompAmdFoldHalosX", "cudecompAmdFoldHalosY", "cudecompAmdFoldHalosZ"]
 # the four extension headers and the functions each of them declares itself (checked by tests/test_abi.py, like API_SYMBOLS)
 AMD_HEADER_SYMBOLS = {"cudecomp_amd.h": AMD_SYMBOLS, "cudecomp_amd_fill.h": AMD_FILL_SYMBOLS,
                       "cudecomp_amd_accumulate_clear.h": AMD_ACCUMULATE_CLEAR_SYMBOLS, "cudecomp_amd_reflect.h": AMD_REFLECT_SYMBOLS}
@@ -227,6 +230,8 @@ def lib():
             getattr(L, name).argtypes = [vp, vp, vp, i32, vp, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         for name in AMD_REFLECT_SYMBOLS:  # (the fill's arguments with parity and centering in the place of the value)
             getattr(L, name).argtypes = [vp, vp, vp, i32, i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
+        for name in AMD_FOLD_SYMBOLS:  # (the reflection's arguments with `clear` after the centering)
+            getattr(L, name).argtypes = [vp, vp, vp, i32, i32, i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         L.cudecompExtGetTransposePlan.argtypes = [vp, vp, i32, pi32, pi32, pi32, pi32, C.c_bool, i32,
                                                   C.POINTER(ExtTransposePlan)]
         L.cudecompExtGetHaloPlan.argtypes = [vp, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32,
@@ -255,6 +260,9 @@ def lib():
         L.cudecompExtPlanHaloReflect.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32,
                                                  C.POINTER(ExtHaloPlan)]
         L.cudecompExtReflect3D.argtypes = [vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, pi32, vp]
+        L.cudecompExtPlanHaloFold.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32, i32,
+                                              C.POINTER(ExtHaloPlan)]
+        L.cudecompExtFold3D.argtypes = [vp, vp, i32, i32, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, pi32, vp]
         L.cudecompExtGetLinkInfo.argtypes = [vp, C.POINTER(ExtLinkInfo)]
         L.cudecompExtEstimateCycleMs.argtypes = [vp, C.POINTER(ExtGridSpec), i32, i32, i32, i32, C.POINTER(C.c_double)]
         L.cudecompExtRunLocalPhases.argtypes = [C.POINTER(ExtGridSpec), i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]
@@ -442,6 +450,22 @@ def cudecompReflectHalos(axis, handle, gd, inp, dtype, parity, centering, halo_e
                                 _i3(padding), stream), name)
 
 
+def cudecompFoldHalos(axis, handle, gd, inp, dtype, parity, centering, clear, halo_extents, halo_periods, dim, padding=None,
+                      stream=None):
+    """cudecompAmdFoldHalos{X,Y,Z} (cudecomp_halo_fold.h), the transpose of the reflection: the ghost cells along `dim` that have
+    no neighbour behind them are added onto the interior cells they mirror (parity -1: with their sign bits flipped first), and
+    hold zero bytes afterwards with clear = 1."""
+    if parity not in (1, -1):
+        raise ValueError("parity must be +1 or -1, not %r" % (parity,))
+    if centering not in (0, 1):
+        raise ValueError("centering must be 0 or 1, not %r" % (centering,))
+    if clear not in (0, 1):
+        raise ValueError("clear must be 0 or 1, not %r" % (clear,))
+    name = "cudecompAmdFoldHalos" + "XYZ"[axis]
+    _check(getattr(lib(), name)(handle, gd, inp, dtype, int(parity), int(centering), int(clear), _i3(halo_extents),
+                                _b3(halo_periods), dim, _i3(padding), stream), name)
+
+
 def cudecompExtGetTransposePlan(handle, gd, op, in_halo=None, out_halo=None, in_pad=None, out_pad=None, inplace=False,
                                 backend_override=0):
     p = ExtTransposePlan()
@@ -538,6 +562,15 @@ def cudecompExtPlanHaloReflect(grid, rank, axis, halo_extents, halo_periods, dim
     p = ExtHaloPlan()
     _check(lib().cudecompExtPlanHaloReflect(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding),
                                             int(centering), int(bool(negate)), C.byref(p)), "cudecompExtPlanHaloReflect")
+    return p
+
+
+def cudecompExtPlanHaloFold(grid, rank, axis, halo_extents, halo_periods, dim, padding=None, centering=0, negate=False, clear=0):
+    """Stateless planner of cudecompAmdFoldHalos*; ExtHaloPlan.reserved bit 14 marks a fold plan, bit 13 the sign flip, bit 1
+    overlapping destination ranges, bits 9-11 the clearing (cudecomp_ext.h)."""
+    p = ExtHaloPlan()
+    _check(lib().cudecompExtPlanHaloFold(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding),
+                                         int(centering), int(bool(negate)), int(clear), C.byref(p)), "cudecompExtPlanHaloFold")
     return p
 
 
@@ -654,6 +687,16 @@ def cudecompExtReflect3D(src, dst, dtype, negate, extent, ss, ds, force=0, strea
     return cls.value
 
 
+def cudecompExtFold3D(src, dst, dtype, negate, take, extent, ss, ds, force=0, stream=None):
+    """One fold-move (dst += src, or dst += -src with `negate`; src = 0 afterwards with `take`; the negative entry of `ss` names
+    the mirrored dim) through the kernel layer; returns the kernel class (0 rows, 2 generic)."""
+    cls = C.c_int32(-1)
+    a = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
+    _check(lib().cudecompExtFold3D(src, dst, dtype, int(bool(negate)), int(bool(take)), a(extent), a(ss), a(ds), int(force),
+                                   C.byref(cls), stream), "cudecompExtFold3D")
+    return cls.value
+
+
 def cudecompExtRotateWalk(nb, walk=-1):
     """The in-place rotation kernel's orbit walk for nb blocks per edge (no launch, no GPU): (grid, blocks) with blocks an
     int32 array of shape (grid, 3): the block triple of every workgroup, -1 -1 -1 for the ones that map to none."""
@@ -682,6 +725,9 @@ def cudecompExtDescribeMove(src_address, dst_address, es, extent, ss, ds, flags=
 MOVES_COPY, MOVES_ADD, MOVES_FILL = 0, 1, 2  # `mode` of cudecompExtRunMoves / cudecompExtDescribeMoves
 MOVES_TAKE, MOVES_ADD_TAKE = 3, 4  # ... the copy / the addition, then zero bytes into the source cells
 MOVES_REFLECT, MOVES_REFLECT_NEGATE = 5, 6  # ... mirror copies (a negative `ss` entry names the mirrored dim), plain / sign bits flipped
+# ... folds (additions whose source runs backwards along the dim its negative `ss` entry names): plain / sign bits flipped first /
+# then zero bytes into the source cells / both
+MOVES_FOLD, MOVES_FOLD_NEGATE, MOVES_FOLD_TAKE, MOVES_FOLD_NEGATE_TAKE = 7, 8, 9, 10
 
 
 def make_move(extent, ss, ds, src_off=0, dst_off=0, src_buf=0, dst_buf=1, row_pitch=0):

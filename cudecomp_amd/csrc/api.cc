@@ -627,6 +627,7 @@ cudecompResult_t cudecompGridDescCreateVersioned(cudecompHandle_t handle, cudeco
     gd->halo_fill_plans.clear();
     gd->halo_accumulate_clear_plans.clear();
     gd->halo_reflect_plans.clear();
+    gd->halo_fold_plans.clear();
     perfReset(gd);  // autotuning trials are not part of the user's performance report
 
     *grid_desc_out = gd;
@@ -935,5 +936,41 @@ static cudecompResult_t haloReflectEntry(int axis, cudecompHandle_t handle, cude
 CD_DEFINE_HALO_REFLECT(cudecompAmdReflectHalosX, 0)
 CD_DEFINE_HALO_REFLECT(cudecompAmdReflectHalosY, 1)
 CD_DEFINE_HALO_REFLECT(cudecompAmdReflectHalosZ, 2)
+
+// cudecomp_halo_fold.h: the ghost cells the reflection writes are added onto their mirror images.  The checks of haloReflectEntry,
+// in its order, with `clear` after centering (also when every halo is zero); then the plan's own.
+static cudecompResult_t haloFoldEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
+                                      cudecompDataType_t dtype, int32_t parity, int32_t centering, int32_t clear,
+                                      const int32_t halo_extents[], const bool halo_periods[], int32_t dim, const int32_t padding[],
+                                      hipStream_t stream) {
+  try {
+    checkHandle(handle);
+    checkGridDesc(handle, grid_desc);
+    checkDataType(dtype);
+    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
+    if (halo_extents[0] == 0 && halo_extents[1] == 0 && halo_extents[2] == 0) {
+      if (parity != 1 && parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
+      if (centering != 0 && centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
+      if (clear != 0 && clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
+      return CUDECOMP_RESULT_SUCCESS;
+    }
+    if (!input) CD_INVALID_USAGE("input argument cannot be null");
+    if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
+    runHaloFold(handle, grid_desc, axis, input, dtype, parity, centering, clear, halo_extents, halo_periods, dim, padding, stream);
+  }
+  CD_API_CATCH()
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+#define CD_DEFINE_HALO_FOLD(NAME, AXIS)                                                                                   \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,     \
+                        int32_t parity, int32_t centering, int32_t clear, const int32_t halo_extents[],                   \
+                        const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {            \
+    return haloFoldEntry(AXIS, handle, grid_desc, input, dtype, parity, centering, clear, halo_extents, halo_periods,     \
+                         dim, padding, stream);                                                                           \
+  }
+CD_DEFINE_HALO_FOLD(cudecompAmdFoldHalosX, 0)
+CD_DEFINE_HALO_FOLD(cudecompAmdFoldHalosY, 1)
+CD_DEFINE_HALO_FOLD(cudecompAmdFoldHalosZ, 2)
 
 }  // extern "C"

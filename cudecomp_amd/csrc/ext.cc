@@ -105,6 +105,7 @@ void exportHaloPlan(const HaloPlan& p, cudecompExtHaloPlan_t* out) {
     }
     if (p.fill) out->reserved = 256;
     if (p.reflect) out->reserved = 4096 | (p.negate ? 8192 : 0);
+    if (p.fold) out->reserved = 16384 | (p.negate ? 8192 : 0) | (p.ordered ? 2 : 0);
     if (p.clear) {
       out->reserved |= 512;
       for (size_t i = 0; i < p.pre.size(); ++i)
@@ -151,10 +152,11 @@ std::vector<Move3D> importMoves(const cudecompExtMove_t* moves, int32_t n, int32
                                 ArithType* arith) {
   if (n < 0 || (n > 0 && !moves)) CD_INVALID_USAGE("bad move list");
   if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
-  if (mode < 0 || mode > 6)
-    CD_INVALID_USAGE("mode must be 0 (copy), 1 (add), 2 (fill), 3 (take), 4 (add and take), 5 (mirror copy) or 6 (mirror copy with sign flip)");
+  if (mode < 0 || mode > 10)
+    CD_INVALID_USAGE("mode must be 0 (copy), 1 (add), 2 (fill), 3 (take), 4 (add and take), 5 (mirror copy), 6 (mirror copy with sign flip) "
+                     "or 7 ... 10 (fold: plain, with sign flip, with take, with both)");
   *arith = ARITH_NONE;
-  if (mode == 1 || mode == 4 || mode == 6) {
+  if (mode == 1 || mode == 4 || mode >= 6) {
     if (elementSize(dtype) != es) CD_INVALID_USAGE("element size does not match the data type of the arithmetic");
     *arith = arithOf(dtype);
   }
@@ -174,14 +176,16 @@ std::vector<Move3D> importMoves(const cudecompExtMove_t* moves, int32_t n, int32
       m.ds[d] = e.ds[d];
     }
     m.dst_row_pitch = e.row_pitch;
-    m.add = mode == 1 || mode == 4;
+    m.add = mode == 1 || mode == 4 || mode >= 7;
     m.fill = mode == 2;
-    m.take = mode == 3 || mode == 4;
-    m.reflect = mode == 5 || mode == 6;
-    m.negate = mode == 6;
+    m.take = mode == 3 || mode == 4 || mode == 9 || mode == 10;
+    m.reflect = mode >= 5;
+    m.negate = mode == 6 || mode == 8 || mode == 10;
     // a mirror copy says which dim it mirrors: without a negative source stride the entry is a plain copy in the wrong mode
-    if (m.reflect && e.ss[0] >= 0 && e.ss[1] >= 0 && e.ss[2] >= 0)
+    if (m.reflect && e.ss[0] >= 0 && e.ss[1] >= 0 && e.ss[2] >= 0) {
+      if (mode >= 7) CD_INVALID_USAGE("a fold (mode 7 ... 10) names its mirrored dim with a negative source stride");
       CD_INVALID_USAGE("a mirror copy (mode 5 / 6) names its mirrored dim with a negative source stride");
+    }
   }
   return out;
 }
@@ -441,6 +445,28 @@ cudecompResult_t cudecompExtPlanHaloReflect(const cudecompExtGridSpec_t* grid, i
     const int32_t zero[3] = {0, 0, 0};
     const bool none[3] = {false, false, false};
     const HaloPlan p = buildHaloReflectPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, centering, negate != 0);
+    exportHaloPlan(p, out);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtPlanHaloFold(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
+                                         const bool periods[], int32_t dim, const int32_t pad[], int32_t centering, int32_t negate,
+                                         int32_t clear, cudecompExtHaloPlan_t* out) {
+  try {
+    const GridShape g = shapeFromSpec(grid);
+    if (!out || !halo) CD_INVALID_USAGE("null argument");
+    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
+    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
+    const int32_t zero[3] = {0, 0, 0};
+    const bool none[3] = {false, false, false};
+    const HaloPlan p = buildHaloFoldPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, centering, negate != 0,
+                                         clear == 1);
+    if (clear != 0 && clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");  // (after the reflection's refusals)
     exportHaloPlan(p, out);
   } catch (const Error& e) {
     return fail(e);
@@ -845,6 +871,44 @@ cudecompResult_t cudecompExtReflect3D(const void* src, void* dst, cudecompDataTy
     if (force & 4) t.no_streaming = true;
     KernelStats st;
     launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, m.negate ? arithOf(dtype) : ARITH_NONE);
+    if (kernel_class) {
+      *kernel_class = -1;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
+        if (st.launches[c]) *kernel_class = c;
+    }
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtFold3D(const void* src, void* dst, cudecompDataType_t dtype, int32_t negate, int32_t take,
+                                   const int64_t extent[3], const int64_t ss[3], const int64_t ds[3], int32_t force,
+                                   int32_t* kernel_class, hipStream_t stream) {
+  try {
+    if (!src || !dst || !extent || !ss || !ds) CD_INVALID_USAGE("null argument");
+    const int es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
+    Move3D m;
+    m.src_buf = BUF_IN;
+    m.dst_buf = BUF_OUT;
+    m.reflect = true;
+    m.add = true;
+    m.negate = negate != 0;
+    m.take = take != 0;
+    for (int i = 0; i < 3; ++i) {
+      m.extent[i] = extent[i];
+      m.ss[i] = ss[i];
+      m.ds[i] = ds[i];
+    }
+    void* bufs[3] = {const_cast<void*>(src), dst, nullptr};
+    KernelTuning t;
+    if (force & 1) t.force_class = MOVE_GENERIC;
+    if (force & 2) t.force_streaming = true;
+    if (force & 4) t.no_streaming = true;
+    KernelStats st;
+    launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, arithOf(dtype));
     if (kernel_class) {
       *kernel_class = -1;
       for (int c = 0; c < MOVE_CLASS_COUNT; ++c)

@@ -15,6 +15,7 @@
 #include "cudecomp_amd.h"
 #include "cudecomp_amd_fill.h"
 #include "cudecomp_amd_reflect.h"
+#include "cudecomp_halo_fold.h"
 #include "decomp.h"
 #include "errors.h"
 #include "kernels.h"
@@ -141,6 +142,8 @@ struct cudecompGridDesc {
   std::map<HaloKey, cudecomp::HaloPlan> halo_accumulate_clear_plans;  // cudecompAmdAccumulateAndClearHalos*: likewise
   // cudecompAmdReflectHalos*: the same key (its last entry unused: always false) plus (centering, sign flip)
   std::map<std::tuple<HaloKey, int, bool>, cudecomp::HaloPlan> halo_reflect_plans;
+  // cudecompAmdFoldHalos*: the same key plus (centering, sign flip, clear)
+  std::map<std::tuple<HaloKey, int, bool, bool>, cudecomp::HaloPlan> halo_fold_plans;
 
   // CUDECOMP_ENABLE_CUDA_GRAPHS=1: the per-peer pack loop of the pipelined backends (one kernel + one event
   // record per destination) is captured once per (plan, buffers, element size) and replayed as one graph launch
@@ -272,6 +275,8 @@ void runHaloFill(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void*
                  const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream);
 void runHaloReflect(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, int parity,
                     int centering, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream);
+void runHaloFold(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, int parity,
+                 int centering, int clear, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream);
 
 // perf.cc
 struct TransposeTimings {

@@ -2,12 +2,12 @@
 //
 // A move is normalised (unit dims dropped, contiguous dims fused, dims sorted by source stride) and classified: classify()
 // writes WHAT runs into one KernelChoice (kernels_batch.h: the kind of kernel -- row copy plain / shifted / dense, LDS-tiled
-// transposition plain / window / lines / row lines, element-wise, the two additions, the two fills, the four takes, the two reflections -- element size, lane width,
+// transposition plain / window / lines / row lines, element-wise, the two additions, the two fills, the four takes, the two reflections, the four folds -- element size, lane width,
 // tile, access mode) and HOW it walks into the Batch fields beside it.  Moves with equal choices are batched (up to kMaxBatch moves, e.g.
 // the per-peer pack copies of one transpose, share one launch; the descriptors travel in the kernel argument segment).  The
 // batching key, the launcher's instantiation and the kernel's name all come from that one record.  The kernels live in
 // kernels_rows.hip, kernels_transpose.hip (one code object per element size), kernels_window.hip, kernels_lines.hip,
-// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip and kernels_reflect.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
+// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip and kernels_fold.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
 // transpose.cc.  kernels_batch.h says why they are separate code objects.
 //
 // 2-byte elements (fp16, bf16) take the row copy (plain kernel), the LDS-tiled transposition (128 x 128 tiles with 16-byte
@@ -49,7 +49,7 @@ constexpr long long kDenseMaxGapBytes = 512;  // widest gap between rows the den
 
 MoveClass classOf(KernelKind kind) {
   if (kind == K_GENERIC || kind == K_GENERIC_ADD || kind == K_GENERIC_FILL || kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE ||
-      kind == K_GENERIC_REFLECT)
+      kind == K_GENERIC_REFLECT || kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE)
     return MOVE_GENERIC;
   return kind >= K_TRANSPOSE && kind <= K_TRANSPOSE_ROWLINES ? MOVE_TRANSPOSE : MOVE_ROWS_VEC;
 }
@@ -369,11 +369,22 @@ void classifyFill(Classified& c, const Move3D& m, const KernelTuning& tuning, bo
 // whole: the mirrored dim is set aside, the other two are normalised (and fused) as those of a copy, and the mirrored dim comes
 // back as the row or plane index.  Access mode: the project's rule, cached below kStreamBytes, non-temporal loads and stores from
 // there (unmeasured for this kernel); the element-wise kernel always caches.
+// Fold-moves (Move3D::reflect with Move3D::add, `arith` their real type; Move3D::take as well when they clear their source) come
+// the same way and are offered the same two geometries and nothing else.  Access mode: the accumulation's rule, cached below
+// kStreamBytes, from there non-temporal source loads and zero stores, the destination always cached (unmeasured for these
+// kernels too); the element-wise kernel always caches.
 Classified classifyReflect(const Move3D& in, void* const bufs[3], int es, const KernelTuning& tuning, bool remote, ArithType arith) {
-  if (in.add || in.fill || in.take || in.dst_row_pitch != 0 || remote)
-    CD_INTERNAL_ERROR("reflect-moves only copy the cells of a local buffer");
-  if (in.negate && (arith == ARITH_NONE || es % arithBytes(arith) != 0 || es / arithBytes(arith) > 2))
-    CD_INTERNAL_ERROR("reflect-move that flips sign bits without a real type that fits the element size");
+  const bool fold = in.add;
+  if (fold) {
+    if (in.fill || in.dst_row_pitch != 0 || remote) CD_INTERNAL_ERROR("fold-moves only add onto the cells of a local buffer");
+    if (arith == ARITH_NONE) CD_INTERNAL_ERROR("fold-move without an arithmetic type");
+    if (es % arithBytes(arith) != 0 || es / arithBytes(arith) > 2) CD_INTERNAL_ERROR("element size does not fit the arithmetic type");
+  } else {
+    if (in.fill || in.take || in.dst_row_pitch != 0 || remote)
+      CD_INTERNAL_ERROR("reflect-moves only copy the cells of a local buffer");
+    if (in.negate && (arith == ARITH_NONE || es % arithBytes(arith) != 0 || es / arithBytes(arith) > 2))
+      CD_INTERNAL_ERROR("reflect-move that flips sign bits without a real type that fits the element size");
+  }
   int mirrored = -1;
   for (int i = 0; i < 3; ++i) {
     if (in.ds[i] < 0) CD_INTERNAL_ERROR("negative destination stride");
@@ -390,7 +401,8 @@ Classified classifyReflect(const Move3D& in, void* const bufs[3], int es, const 
   normalizeMove(m);  // at most two dims remain, in slots 0 and 1
   Classified c{};
   c.k.es = es;
-  c.k.arith = in.negate ? arith : ARITH_NONE;
+  c.k.arith = (fold || in.negate) ? arith : ARITH_NONE;
+  c.k.neg = fold && in.negate;
   c.elements = in.elements();
   const bool streaming = (c.elements * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming;
   c.dm.src = static_cast<const char*>(bufs[in.src_buf]) + in.src_off * es;
@@ -408,14 +420,14 @@ Classified classifyReflect(const Move3D& in, void* const bufs[3], int es, const 
   }
   const bool mirrored_fastest = live && (in.ss[mirrored] == -1 || in.ds[mirrored] <= 1);
   if (tuning.force_class != MOVE_GENERIC && m.ss[0] <= 1 && m.ds[0] <= 1 && !mirrored_fastest) {
-    c.k.kind = K_ROWS_REFLECT;
+    c.k.kind = fold ? (in.take ? K_ROWS_FOLD_TAKE : K_ROWS_FOLD) : K_ROWS_REFLECT;
     c.k.access = streaming ? 1 : 0;
     rowVectors(c, m);
     if (c.k.vec < es) CD_INTERNAL_ERROR("reflect-move narrower than one element");
     rowTiles(c);
     return c;
   }
-  c.k.kind = K_GENERIC_REFLECT;
+  c.k.kind = fold ? (in.take ? K_GENERIC_FOLD_TAKE : K_GENERIC_FOLD) : K_GENERIC_REFLECT;
   c.k.access = 0;
   c.k.vec = es;
   c.p0 = -1;
@@ -442,7 +454,8 @@ Classified classifyReflect(const Move3D& in, void* const bufs[3], int es, const 
 // geometries and nothing else, for the same reason -- and because the zero must go where the lane's load went, at its width.
 Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelTuning& tuning, void* dst_base, bool remote,
                     ArithType arith) {
-  if (in.negate && !in.reflect) CD_INTERNAL_ERROR("only reflect-moves flip sign bits");
+  if (in.negate && !in.reflect) CD_INTERNAL_ERROR("only reflect- and fold-moves flip sign bits");
+  if (in.reflect && in.take && !in.add) CD_INTERNAL_ERROR("a reflect-move that clears its source must be a fold-move (add)");
   if (in.reflect) return classifyReflect(in, bufs, es, tuning, remote || dst_base != nullptr, arith);
   Move3D m = in;
   if (in.fill) {  // no source: nothing but the destination decides the order and the fusion of the dims
@@ -542,6 +555,15 @@ void spellKernelName(const KernelChoice& k) {
       break;
     case K_ROWS_REFLECT: snprintf(out, n, "rows_reflect_kernel<%d,%d,%s>", k.vec, s, k.arith != ARITH_NONE ? "true" : "false"); break;
     case K_GENERIC_REFLECT: snprintf(out, n, "generic_reflect_kernel<%d,%s>", k.es, k.arith != ARITH_NONE ? "true" : "false"); break;
+    case K_ROWS_FOLD:
+    case K_ROWS_FOLD_TAKE:
+      snprintf(out, n, "rows_fold_kernel<%s,%d,%d,%s>", arithName(k.arith), k.vec, s, k.kind == K_ROWS_FOLD_TAKE ? "true" : "false");
+      break;
+    case K_GENERIC_FOLD:
+    case K_GENERIC_FOLD_TAKE:
+      snprintf(out, n, "generic_fold_kernel<%s,%d,%s>", arithName(k.arith), k.es / arithBytes(k.arith),
+               k.kind == K_GENERIC_FOLD_TAKE ? "true" : "false");
+      break;
   }
 }
 
@@ -586,6 +608,10 @@ void launchBatch(const KernelChoice& k, const Batch& b, const void* fill_value, 
     case K_GENERIC_ADD_TAKE: launchTakeBatch(k, b, blocks, stream); break;
     case K_ROWS_REFLECT:
     case K_GENERIC_REFLECT: launchReflectBatch(k, b, blocks, stream); break;
+    case K_ROWS_FOLD:
+    case K_GENERIC_FOLD:
+    case K_ROWS_FOLD_TAKE:
+    case K_GENERIC_FOLD_TAKE: launchFoldBatch(k, b, blocks, stream); break;
   }
 }
 

@@ -47,6 +47,9 @@ struct KernelTuning {
 // Reflect-moves (Move3D::reflect: the source runs backwards along one dim; kernels_reflect.hip) copy between disjoint cells of a
 // local buffer, as rows or element-wise, over exactly the cells of the move; with Move3D::negate they need `arith`, the real
 // type whose sign bits are flipped.
+// Fold-moves (Move3D::reflect with Move3D::add; kernels_fold.hip) add the source, running backwards along one dim, onto disjoint
+// cells of the same local buffer, with its sign bits flipped first under Move3D::negate, and clear it under Move3D::take; they
+// always need `arith`.
 void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
                  const KernelTuning* tuning = nullptr, KernelStats* stats = nullptr,
                  void* const* dst_base_override = nullptr,  // per-move destination base (remote buffers)

@@ -1,8 +1,8 @@
 // kernels_batch.h -- what csrc/kernels.cc (host: classification, batching) and the kernel code objects share: the record of a
 // kernel choice (KernelChoice), the launch descriptor (Batch) and the launchers.  The code objects the classifier dispatches
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
-// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip; kernels_rotate.hip and
-// sync.hip are launched by the executor.
+// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip;
+// kernels_rotate.hip and sync.hip are launched by the executor.  Fifteen code objects in all.
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
 // code object beyond roughly 0.6-0.7 MB puts the whole process into a regime where every small synchronous operation costs
@@ -32,7 +32,7 @@ struct DevMove {
   char* dst;
   long long e[3];   // extents   (units depend on the kernel, see the launchers)
   long long ss[3];  // src strides (rows_fill_kernel, which has no source: ss[0] = row length in bytes); negative along the
-                    // mirrored dim of a reflect-move, and only there
+                    // mirrored dim of a reflect- or fold-move, and only there
   long long ds[3];  // dst strides
 };
 
@@ -56,6 +56,7 @@ struct Batch {
   //   fills                      p0 as for rows / element-wise; p1 unused
   //   takes                      p0 as for rows / element-wise; p1 unused
   //   reflections                p0 as for rows / element-wise; p1 unused
+  //   folds                      p0 as for rows / element-wise; p1 unused
   int p0[kMaxBatch];
   int p1[kMaxBatch];
   unsigned int first_block[kMaxBatch + 1];
@@ -86,7 +87,11 @@ enum KernelKind {
   K_ROWS_ADD_TAKE,       // rows_accumulate_take_kernel (dst += src; src = 0)
   K_GENERIC_ADD_TAKE,    // generic_accumulate_take_kernel
   K_ROWS_REFLECT,        // rows_reflect_kernel (dst = src or dst = -src, the source backwards along the row or plane index)
-  K_GENERIC_REFLECT      // generic_reflect_kernel
+  K_GENERIC_REFLECT,     // generic_reflect_kernel
+  K_ROWS_FOLD,           // rows_fold_kernel (dst += src or dst += -src, the source backwards along the row or plane index) = 18
+  K_GENERIC_FOLD,        // generic_fold_kernel = 19
+  K_ROWS_FOLD_TAKE,      // rows_fold_kernel with TAKE (... ; src = 0) = 20
+  K_GENERIC_FOLD_TAKE    // generic_fold_kernel with TAKE = 21
 };
 struct KernelChoice {
   KernelKind kind;
@@ -96,10 +101,12 @@ struct KernelChoice {
   int access;       // copies: 0 default caching, 2 non-temporal loads + stores, 3 non-temporal loads + remote (system-scope
                     // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads;
                     // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it);
-                    // reflections: 0, 1 non-temporal loads and stores
-  ArithType arith;  // additions, reflections that flip the sign bits: the real type the elements consist of; ARITH_NONE otherwise
+                    // reflections: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores
+  ArithType arith;  // additions, folds, reflections that flip the sign bits: the real type the elements consist of; ARITH_NONE otherwise
+  bool neg;         // folds: the sign bits of the source are flipped before the addition (one sign mask per launch)
   bool operator==(const KernelChoice& o) const {
-    return kind == o.kind && es == o.es && vec == o.vec && ti == o.ti && tj == o.tj && access == o.access && arith == o.arith;
+    return kind == o.kind && es == o.es && vec == o.vec && ti == o.ti && tj == o.tj && access == o.access && arith == o.arith &&
+           neg == o.neg;
   }
 };
 constexpr int kLinesUnitBytes = 128;  // alignment unit of the lines and row-lines kernels
@@ -114,6 +121,8 @@ inline int streamArgOf(KernelKind kind, int access) {
   if (kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE) return 0;
   if (kind == K_ROWS_REFLECT) return access;
   if (kind == K_GENERIC_REFLECT) return 0;
+  if (kind == K_ROWS_FOLD || kind == K_ROWS_FOLD_TAKE) return access;
+  if (kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE) return 0;
   if (kind == K_TRANSPOSE_WINDOW || kind == K_TRANSPOSE_LINES || kind == K_TRANSPOSE_ROWLINES)
     return access == 2 ? 4 : access;  // always cached loads: the overlap rows of neighbouring windows hit in L2
   return access == 3 ? 3 : (access >= 1 ? 1 : 0);  // row copies: loads and stores stream together
@@ -151,6 +160,11 @@ struct SignMask {
   unsigned int w[4];
 };
 void launchReflectBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+// kernels_fold.hip: fold-moves (dst += src or dst += -src with the source running backwards along one dim; the TAKE kinds then
+// store zero bytes to the source cells).  The Batch of the reflections: rows with SIGNED byte strides ss[1], ss[2], generic with
+// signed strides in elements.  k.arith: the real type of the addition; k.neg: the sign mask of that type travels as a 16-byte
+// kernel argument of its own, all zero otherwise.  Local buffers only.
+void launchFoldBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

@@ -493,6 +493,41 @@ HaloPlan buildHaloReflectPlan(const GridShape& g, int rank, int axis, int dim, c
   return p;
 }
 
+HaloPlan buildHaloFoldPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                           const int32_t* pad, int centering, bool negate, bool clear, bool self_exchange) {
+  // (its refusals, its neighbours, its sides: one fold-move per reflect-move, the same cells with source and destination swapped)
+  const HaloPlan r = buildHaloReflectPlan(g, rank, axis, dim, halo, periods, pad, centering, negate, self_exchange);
+  HaloPlan p;
+  p.axis = axis;
+  p.dim = dim;
+  p.fold = true;
+  p.negate = negate;
+  p.clear = clear;
+  p.comm_axis = r.comm_axis;
+  p.neighbor[0] = r.neighbor[0];
+  p.neighbor[1] = r.neighbor[1];
+  p.face_elements = r.face_elements;
+  if (r.kind == HaloPlan::NONE) return p;
+
+  const i64 he = halo[dim], c = centering;
+  const i64 sd = -r.pre[0].ss[dim];                                                // (the pencil's stride along dim)
+  const Pencil hp = makePencil(g, gridIndexOfRank(g, rank), axis, halo, pad);
+  const i64 n = hp.extentG(dim) - (pad ? pad[dim] : 0);  // extent along dim without padding
+  for (const Move3D& rm : r.pre) {  // destination cell dst_cell + j takes source cell src_cell - j
+    const bool low = rm.peer == 0;  // (the side)
+    const i64 src_cell = low ? he - 1 : n - 1, dst_cell = low ? he + c : n - 2 * he - c;
+    Move3D m = rm;
+    m.src_off = src_cell * sd;
+    m.dst_off = dst_cell * sd;
+    m.add = true;
+    m.take = clear;
+    p.pre.push_back(m);
+  }
+  p.ordered = p.pre.size() == 2 && n < 4 * he + 2 * c;
+  p.kind = HaloPlan::SELF_PERIODIC;
+  return p;
+}
+
 int normalizeMove(Move3D& m) {
   struct D {
     i64 e, s, d;

@@ -54,10 +54,14 @@ struct Move3D {
   // true: the source runs BACKWARDS along one dim (halo reflection, buildHaloReflectPlan): that dim has a negative source stride
   // and src_off names the source cell of its index 0.  Only reflect-moves may have a negative stride.  Source and destination are
   // disjoint cells of one local buffer; exactly the destination cells of the move are written and exactly its source cells read.
-  // A reflect-move never carries dst_row_pitch, add, fill, take or a remote destination (an internal error before any launch).
+  // A reflect-move never carries dst_row_pitch, fill or a remote destination (an internal error before any launch).
+  // `reflect` together with `add` is the FOLD-MOVE (halo folding, buildHaloFoldPlan): dst = dst + src, or dst + (-src) with
+  // `negate`, the source running backwards; it may carry `take` as well (zero bytes into the source cells it has read, under the
+  // rule of take-moves: sources disjoint from every destination and every other source of the phase).  `reflect` with `take` but
+  // without `add`, and a fold-move with dst_row_pitch, fill or a remote destination, are internal errors before any launch.
   bool reflect = false;
-  // reflect-moves only: the sign bit of every real component is inverted on the way (one bit per real, two per complex element);
-  // nothing else about the bytes changes.
+  // reflect- and fold-moves only: the sign bit of every real component is inverted on the way (one bit per real, two per complex
+  // element); nothing else about the bytes changes.  A fold-move flips the bits first and adds then.
   bool negate = false;
 
   i64 elements() const { return extent[0] * extent[1] * extent[2]; }
@@ -174,7 +178,8 @@ struct HaloPlan {
   bool fill = false;     // fill plans (buildHaloFillPlan) only
   bool clear = false;    // fused accumulate-and-clear plans (buildHaloAccumulateClearPlan) only
   bool reflect = false;  // reflection plans (buildHaloReflectPlan) only
-  bool negate = false;   // ... whose moves flip the sign bits (parity -1)
+  bool negate = false;   // ... whose moves flip the sign bits (parity -1); fold plans likewise
+  bool fold = false;     // fold plans (buildHaloFoldPlan) only; `ordered` and `clear` as for accumulation plans
 };
 
 HaloPlan buildHaloPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
@@ -216,6 +221,17 @@ HaloPlan buildHaloFillPlan(const GridShape& g, int rank, int axis, int dim, cons
 // forwards over the halo slab (the other two dims INCLUDING their halos, not their padding), the source backwards along `dim`.
 HaloPlan buildHaloReflectPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
                               const int32_t* pad, int centering, bool negate, bool self_exchange = false);
+
+// Halo FOLDING along `dim` (include/cudecomp_halo_fold.h has the contract) -- the transpose of the reflection: the ghost cells the
+// reflection along `dim` writes are ADDED to the interior cells it reads them from: low side cell(h+k+c) += s * cell(h-1-k), then
+// high side cell(n-h-1-k-c) += s * cell(n-h+k), k in [0, h).  Refusals, neighbours and sides are buildHaloReflectPlan's, which is
+// called first, so "the sides the reflection writes" holds by construction.  Kinds: NONE or SELF_PERIODIC ("local").  `pre`
+// holds at most two fold-moves (Move3D::reflect and Move3D::add, Move3D::negate = `negate`, Move3D::take = `clear`) pencil ->
+// pencil in BUF_IN, the low side then the high side.  As in a reflect-move only the SOURCE stride is negative: the low
+// destinations run forwards over [h+c, 2h+c) with src_off at ghost cell h-1, the high ones over [n-2h-c, n-h-c) with src_off at
+// ghost cell n-1.  `ordered`: both sides present and their destination ranges overlap (n < 4h + 2c): one launch per side, in order.
+HaloPlan buildHaloFoldPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                           const int32_t* pad, int centering, bool negate, bool clear, bool self_exchange = false);
 
 // Number of stages every member of the communicator arrives at without talking: at most `wanted`, at most the smallest
 // chunk extent, at most 14 (flag steps), and no stage smaller than `min_stage_bytes` of the largest pencil (below that the extra

@@ -590,4 +590,43 @@ void runHaloReflect(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* i
   launchMoves(plan.pre.data(), (int)plan.pre.size(), bufs, es, stream, &h->tuning, nullptr, nullptr, negate ? arithOf(dtype) : ARITH_NONE);
 }
 
+// Halo folding (cudecompAmdFoldHalos*), the transpose of the reflection: the ghost cells the reflection writes are added onto the
+// interior cells it reads them from, and cleared in the same launches with `clear`.  Local: no workspace, no exchange.  The
+// checks come in the reflection's order, then `clear`.  Both sides go into one launch unless their destinations overlap (a rank
+// alone along the dim with n < 4h + 2c): then one after the other, low side first, as for accumulation plans.
+void runHaloFold(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, int parity, int centering,
+                 int clear, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
+  const int es = elementSize(dtype);
+  const auto hh = arr3(halo), pp = arr3(pad);
+  std::array<bool, 3> per{false, false, false};
+  if (periods)
+    for (int i = 0; i < 3; ++i) per[i] = periods[i];
+  if ((parity != 1 && parity != -1) || (centering != 0 && centering != 1) || (clear != 0 && clear != 1)) {
+    buildHaloPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), false, h->self_exchange);  // (the fill's refusals)
+    if (parity != 1 && parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
+    if (centering != 0 && centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
+    CD_INVALID_USAGE("clear argument must be 0 or 1");
+  }
+  const bool negate = parity == -1;
+  const cudecompGridDesc::HaloKey hkey{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, false};
+  const auto key = std::make_tuple(hkey, centering, negate, clear == 1);
+  auto it = gd->halo_fold_plans.find(key);
+  if (it == gd->halo_fold_plans.end()) {
+    HaloPlan p = buildHaloFoldPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), centering, negate, clear == 1,
+                                   h->self_exchange);
+    it = gd->halo_fold_plans.emplace(key, std::move(p)).first;
+  }
+  const HaloPlan& plan = it->second;
+  if (plan.kind == HaloPlan::NONE) return;
+
+  ensureDevice(h);
+  void* bufs[3] = {input, input, nullptr};
+  const ArithType arith = arithOf(dtype);
+  if (plan.ordered) {
+    for (const Move3D& m : plan.pre) launchMoves(&m, 1, bufs, es, stream, &h->tuning, nullptr, nullptr, arith);
+  } else {
+    launchMoves(plan.pre.data(), (int)plan.pre.size(), bufs, es, stream, &h->tuning, nullptr, nullptr, arith);
+  }
+}
+
 }  // namespace cudecomp

@@ -588,6 +588,55 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompAmdReflectHalosZ_C
 
+    ! cudecomp_halo_fold.h: halo folding (the ghost cells the reflection writes, summed into their mirror images)
+    function cudecompAmdFoldHalosX_C(handle, grid_desc, input, dtype, parity, centering, clear, halo_extents, halo_periods, dim, &
+                                        padding, stream) bind(C, name="cudecompAmdFoldHalosX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      integer(c_int32_t), value :: parity, centering, clear
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdFoldHalosX_C
+
+    function cudecompAmdFoldHalosY_C(handle, grid_desc, input, dtype, parity, centering, clear, halo_extents, halo_periods, dim, &
+                                        padding, stream) bind(C, name="cudecompAmdFoldHalosY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      integer(c_int32_t), value :: parity, centering, clear
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdFoldHalosY_C
+
+    function cudecompAmdFoldHalosZ_C(handle, grid_desc, input, dtype, parity, centering, clear, halo_extents, halo_periods, dim, &
+                                        padding, stream) bind(C, name="cudecompAmdFoldHalosZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      integer(c_int32_t), value :: parity, centering, clear
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdFoldHalosZ_C
+
 
     function cudecomp_c_strlen(str) bind(C, name="strlen") result(n)
       import
@@ -1263,6 +1312,76 @@ contains
     res = cudecompAmdReflectHalosZ_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
                                       int(centering, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
   end function cudecompAmdReflectHalosZ
+
+  ! ---- halo folding (cudecomp_halo_fold.h): the arguments of the reflection with `clear` after the centering ----
+  function cudecompAmdFoldHalosX(handle, grid_desc, input, dtype, parity, centering, clear, halo_extents, halo_periods, dim, &
+                                    padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: parity     ! +1: the ghost cells are added as they are; -1: with their sign bits flipped first
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: clear      ! 1: the ghost cells that were read hold zero bytes afterwards; 0: they are only read
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdFoldHalosX_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
+                                      int(centering, c_int32_t), int(clear, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdFoldHalosX
+
+  function cudecompAmdFoldHalosY(handle, grid_desc, input, dtype, parity, centering, clear, halo_extents, halo_periods, dim, &
+                                    padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: parity     ! +1: the ghost cells are added as they are; -1: with their sign bits flipped first
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: clear      ! 1: the ghost cells that were read hold zero bytes afterwards; 0: they are only read
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdFoldHalosY_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
+                                      int(centering, c_int32_t), int(clear, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdFoldHalosY
+
+  function cudecompAmdFoldHalosZ(handle, grid_desc, input, dtype, parity, centering, clear, halo_extents, halo_periods, dim, &
+                                    padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: parity     ! +1: the ghost cells are added as they are; -1: with their sign bits flipped first
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: clear      ! 1: the ghost cells that were read hold zero bytes afterwards; 0: they are only read
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdFoldHalosZ_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
+                                      int(centering, c_int32_t), int(clear, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdFoldHalosZ
 
 
   subroutine halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)

@@ -68,7 +68,9 @@ typedef struct {
    * (cudecompExtPlanHaloAccumulateClear): the accumulation bits as above, bit 9 set, and bits 10, 11: pre[0], pre[1] store zero
    * bytes to the source cells they have read; no move of `post` does.  Reflection plans (cudecompExtPlanHaloReflect): bit 12 set,
    * bit 13: the moves flip the sign bits (parity -1), and nothing else; every move of `pre` is a reflect-move (its source stride
-   * along the mirrored dim is negative). */
+   * along the mirrored dim is negative).  Fold plans (cudecompExtPlanHaloFold): bit 14 set, bit 13: the moves flip the sign bits,
+   * bit 1: the two destination ranges overlap (one launch per side, in order), and with `clear` bit 9 and bits 10, 11 as above;
+   * every move of `pre` is a fold-move (a reflect-move that adds). */
   int32_t reserved;
   int64_t face_elements, send_off[2], recv_off[2];
   cudecompExtMove_t pre[2], post[2];
@@ -152,6 +154,16 @@ cudecompResult_t cudecompExtPlanHaloReflect(const cudecompExtGridSpec_t* grid, i
                                             const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
                                             const int32_t padding[], int32_t centering, int32_t negate,
                                             cudecompExtHaloPlan_t* plan);
+
+/* The plan cudecompAmdFoldHalos{X,Y,Z} (cudecomp_halo_fold.h) would run on `rank`: kind 0 (nothing to do) or 1 (local); at most
+ * two fold-moves in `pre`, the low side then the high side, pencil -> pencil in buffer 0, row_pitch 0: the destination runs
+ * forwards over the interior cells [h + c, 2h + c) / [n - 2h - c, n - h - c), the source backwards along `dim` from ghost cell
+ * h - 1 / n - 1 (ss negative there); n_post = 0; cudecompExtHaloPlan_t::reserved as described there.  The refusals are those of
+ * cudecompExtPlanHaloReflect, then CUDECOMP_RESULT_INVALID_USAGE for a `clear` that is not 0 / 1. */
+cudecompResult_t cudecompExtPlanHaloFold(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
+                                         const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
+                                         const int32_t padding[], int32_t centering, int32_t negate, int32_t clear,
+                                         cudecompExtHaloPlan_t* plan);
 
 /* Stateless geometry queries on a grid spec (no handle, no communicator): what cudecompGetPencilInfo,
  * cudecompGetShiftedRank, cudecompGetTransposeWorkspaceSize and cudecompGetHaloWorkspaceSize would answer on `rank`. */
@@ -288,6 +300,15 @@ cudecompResult_t cudecompExtReflect3D(const void* src, void* dst, cudecompDataTy
                                       const int64_t ss[3], const int64_t ds[3], int32_t force, int32_t* kernel_class,
                                       hipStream_t stream);
 
+/* One fold-move on the GPU: dst[k0*ds[0] + k1*ds[1] + k2*ds[2]] += src[k0*ss[0] + k1*ss[1] + k2*ss[2]] in the arithmetic of
+ * `dtype`, 0 <= k_i < extent[i] (strides in elements of `dtype`), where at most one entry of ss is negative: the mirrored dim,
+ * src pointing at the source cell of its index 0.  negate != 0: the sign bit of every real of the source is inverted before the
+ * addition.  take != 0: zero bytes are stored to the source cells afterwards.  src and dst are disjoint cells, usually of one
+ * buffer.  force: the bits of cudecompExtReflect3D.  *kernel_class (optional): 0 rows, 2 generic. */
+cudecompResult_t cudecompExtFold3D(const void* src, void* dst, cudecompDataType_t dtype, int32_t negate, int32_t take,
+                                   const int64_t extent[3], const int64_t ss[3], const int64_t ds[3], int32_t force,
+                                   int32_t* kernel_class, hipStream_t stream);
+
 /* How the kernel layer WOULD execute a 3-D block move between buffers at the given addresses (no launch; works without a
  * GPU): out[10] = {class (0 rows, 1 LDS transpose, 2 generic), kernel variant, tile_i, tile_j, tiles_i, tiles_j, batch extent,
  * run length of the tile walk, walk bits (1 XCD-contiguous, 2 j first, 4 runs over batch planes), access mode}.  flags: 2 =
@@ -310,11 +331,14 @@ cudecompResult_t cudecompExtDescribeMove(uint64_t src_address, uint64_t dst_addr
  * fills with the `es` bytes at fill_value (NULL: zero bytes; the source fields are ignored); 3: takes, the copy followed by zero
  * bytes into the source cells (dst = src; src = 0); 4: additions that clear their source (dst += src; src = 0; dtype as for mode
  * 1); 5: mirror copies (reflect-moves: a move's negative `ss` entry names the mirrored dim, src_off the source cell of its index
- * 0; exactly one per move -- an entry without one is CUDECOMP_RESULT_INVALID_USAGE, two are an internal error); 6: mirror copies with the sign bit of every real of `dtype` inverted (its size must be `es`).  The
- * sources of a list of mode 3 or 4 must be disjoint from all destinations and from each other.  flags: bits 1, 2, 4, 8, 64, 128
+ * 0; exactly one per move -- an entry without one is CUDECOMP_RESULT_INVALID_USAGE, two are an internal error); 6: mirror copies with the sign bit of every real of `dtype` inverted (its size must be `es`); 7: folds
+ * (fold-moves: dst += src in the arithmetic of `dtype`, the source running backwards along the dim its negative `ss` entry names,
+ * as for mode 5; an entry without one is CUDECOMP_RESULT_INVALID_USAGE); 8: folds with the sign bits of the source flipped
+ * first; 9: folds that clear their source (src = 0 afterwards); 10: both.  The
+ * sources of a list of mode 3, 4 or 7 ... 10 must be disjoint from all destinations and from each other.  flags: bits 1, 2, 4, 8, 64, 128
  * of cudecompExtMove3D, same meanings.  dst_bases (optional, n entries): moves[i] writes dst_bases[i] + dst_off instead, with
  * the system-scope stores of a peer's memory (access mode 3) -- the calling form of the one-sided transports; additions,
- * fills, both take modes and both mirror modes refuse it (as they refuse a row_pitch) with CUDECOMP_RESULT_INTERNAL_ERROR before anything is launched.  launches[3] / elements[3] (optional): launches
+ * fills, both take modes, both mirror modes and the four fold modes refuse it (as they refuse a row_pitch) with CUDECOMP_RESULT_INTERNAL_ERROR before anything is launched.  launches[3] / elements[3] (optional): launches
  * and elements per class (0 rows, 1 LDS transpose, 2 generic); *n_launches (optional): launches in all.
  *
  * cudecompExtDescribeMoves answers which launches that call would make, without a device: the same arguments with addresses
@@ -322,7 +346,8 @@ cudecompResult_t cudecompExtDescribeMove(uint64_t src_address, uint64_t dst_addr
  * *n_launches set).  A move that needs more than 2^31 - 1 workgroups by itself is CUDECOMP_RESULT_NOT_SUPPORTED.
  * kind counts csrc/kernels_batch.h KernelKind: 0 rows, 1 rows shifted, 2 rows dense, 3 transpose, 4 transpose window, 5 transpose
  * lines, 6 transpose row lines, 7 generic, 8 rows addition, 9 generic addition, 10 rows fill, 11 generic fill, 12 rows take, 13 generic take, 14 rows addition
- * with take, 15 generic addition with take, 16 rows reflection, 17 generic reflection. */
+ * with take, 15 generic addition with take, 16 rows reflection, 17 generic reflection, 18 rows fold, 19 generic fold, 20 rows
+ * fold with take, 21 generic fold with take. */
 typedef struct {
   int32_t cls;                                      /* 0 rows, 1 LDS transpose, 2 generic */
   int32_t kind, es, vec, tile_i, tile_j, access, arith; /* csrc/kernels_batch.h KernelChoice */
