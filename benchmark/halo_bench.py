@@ -9,7 +9,8 @@ cudecompAmdReflectHalosX (cudecomp_amd_reflect.h) on the same pencil as a NON-pe
 per dim the cells the periodic update writes, as many cells read, the same two sibling moves in one launch (4 * face bytes) and, with
 --fold / --fold-clear, cudecompAmdFoldHalosX (cudecomp_halo_fold.h), the reflection's transpose, on the same non-periodic single rank
 with parity -1, centering 0 and clear 0 / 1: the reflection's two sibling moves the other way round, the destinations read as well
-(6 * face bytes), the ghost cells zeroed as well (8 * face bytes).
+(6 * face bytes), the ghost cells zeroed as well (8 * face bytes) and, with --fields N, cudecompAmdUpdateFieldHalosX
+(cudecomp_halo_fields.h) on N such pencils, periodic: the update's two wrap copies for all N in one launch (N * 4 * face bytes).
 Per dim: `--reps` repetitions of `--calls` back-to-back calls each, ms per call of every repetition, their
 min / median / max, and GB/s of the median against the algorithmic bytes (update: 2 faces read + written,
 4 * face bytes; accumulation: 2 faces read, 2 destinations read and written, 6 * face bytes; fill: 2 halos written, 2 * face
@@ -61,6 +62,9 @@ def main():
     ap.add_argument("--fold", action="store_true",
                     help="also time cudecompAmdFoldHalosX (non-periodic, parity -1, centering 0, clear 0), after the other passes")
     ap.add_argument("--fold-clear", action="store_true", help="... and with clear 1")
+    ap.add_argument("--fields", type=int, default=0, metavar="N",
+                    help="also time cudecompAmdUpdateFieldHalosX on N pencils (periodic; one launch for all of them), after the other "
+                         "passes, and compare every field on the device with a clone updated by single calls")
     ap.add_argument("--json", metavar="FILE", default=None, help="also write the result line to FILE")
     a = ap.parse_args()
     import torch
@@ -177,6 +181,33 @@ def main():
         interior = cells[a.halo:shape[2] - a.halo, a.halo:shape[1] - a.halo, a.halo:shape[0] - a.halo]
         extra["interior_cells_with_another_count_after_" + name] = int(torch.count_nonzero(interior != expected))
         extra["ghost_cells_not_zero_after_" + name] = int(torch.count_nonzero(cells)) - int(torch.count_nonzero(interior))
+    if a.fields:
+        # N pencils of the same descriptor; the figure to hold against is N times the update's median of the same dim
+        n = a.fields
+        fields = [torch.randn(p.size, dtype=torch.float64, device="cuda") for _ in range(n)]
+        fwork = cd.cudecompMalloc(h, gd, n * ws * 8)
+        ptrs = [t.data_ptr() for t in fields]
+        for dim in range(3):
+            rec = res["dim%d" % dim]
+            ms = _time(lambda: cd.cudecompUpdateFieldHalos(0, h, gd, ptrs, fwork, cd.DOUBLE, halo, (1, 1, 1), dim, stream=st), a.reps, a.calls)
+            rec["fields"] = _record(ms, n * 4 * faces[dim] * 8)
+            rec["fields_kernel"] = cd.cudecompExtLastKernelName()
+            rec["fields_over_n_updates"] = round(rec["fields"]["median_ms"] / (n * rec["update"]["median_ms"]), 3)
+        # after the timing: fresh payloads, dims 0, 1, 2 by the fields call against single calls on clones, on the device
+        differ = 0
+        for t in fields:
+            t.normal_()
+        clones = [t.clone() for t in fields]
+        for dim in range(3):
+            cd.cudecompUpdateFieldHalos(0, h, gd, ptrs, fwork, cd.DOUBLE, halo, (1, 1, 1), dim, stream=st)
+            for c in clones:
+                cd.cudecompUpdateHalos(0, h, gd, c.data_ptr(), work, cd.DOUBLE, halo, (1, 1, 1), dim, stream=st)
+        torch.cuda.synchronize()
+        for t, c in zip(fields, clones):
+            differ += int(torch.count_nonzero(t.view(torch.int64) != c.view(torch.int64)))
+        extra["n_fields"] = n
+        extra["field_cells_that_differ_from_single_calls"] = differ
+        cd.cudecompFree(h, gd, fwork)
     cd.cudecompFree(h, gd, work)
     cd.cudecompGridDescDestroy(h, gd)
     line = json.dumps(dict({"workload": "X pencil 2048x1024x256 fp64 + halo %d, periodic single rank, per dim: update (self copy), "
@@ -184,7 +215,8 @@ def main():
                                         % (a.halo, (" and fill (zero)" if a.fill else "") + (" and accumulate-and-clear" if a.accumulate_clear else "")
                                            + (" and reflection (non-periodic, odd mirror, centering 0)" if a.reflect else "")
                                            + (" and fold (non-periodic, parity -1, centering 0)" if a.fold else "")
-                                           + (" and fold with clear" if a.fold_clear else ""), a.reps, a.calls),
+                                           + (" and fold with clear" if a.fold_clear else "")
+                                           + (" and the update of %d pencils in one call" % a.fields if a.fields else ""), a.reps, a.calls),
                             "device": torch.cuda.get_device_name(0), "result": res}, **extra))
     print(line)
     if a.json:
@@ -194,6 +226,8 @@ def main():
     if extra.get("ghost_cells_not_zero_after_accumulate_clear") or extra.get("interior_sum_after_accumulate_clear", extra.get("cells")) != extra.get("cells"):
         sys.exit("halo_bench.py: after accumulate-and-clear along 2, 1, 0 %d ghost cells are not zero, the interior sums to %r of %d"
                  % (extra["ghost_cells_not_zero_after_accumulate_clear"], extra["interior_sum_after_accumulate_clear"], extra["cells"]))
+    if extra.get("field_cells_that_differ_from_single_calls"):
+        sys.exit("halo_bench.py: after the fields call along 0, 1, 2 %d cells differ from single calls on clones" % extra["field_cells_that_differ_from_single_calls"])
     for name in ("fold", "fold_clear"):
         if extra.get("interior_cells_with_another_count_after_" + name) or extra.get("ghost_cells_not_zero_after_" + name):
             sys.exit("halo_bench.py: after folding a pencil of ones along 2, 1, 0 (%s pass) %d interior cells do not hold their count and %d "

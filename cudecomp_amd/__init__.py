@@ -97,6 +97,13 @@ class ExtHaloPlan(C.Structure):
                 ("send_off", C.c_int64 * 2), ("recv_off", C.c_int64 * 2), ("pre", ExtMove * 2), ("post", ExtMove * 2)]
 
 
+class ExtHaloFieldsPlan(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("comm_axis", C.c_int32), ("neighbor", C.c_int32 * 2), ("n_fields", C.c_int32),
+                ("n_pre", C.c_int32), ("n_post", C.c_int32), ("reserved", C.c_int32), ("face_elements", C.c_int64),
+                ("slot_elements", C.c_int64), ("send_off", C.c_int64 * 2), ("recv_off", C.c_int64 * 2), ("pre", ExtMove * 2),
+                ("post", ExtMove * 2)]
+
+
 class ExtRelayMove(C.Structure):
     _fields_ = [("dst_rank", C.c_int32), ("to_relay", C.c_int32), ("src_off", C.c_int64), ("dst_off", C.c_int64),
                 ("count", C.c_int64)]
@@ -152,7 +159,8 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtDescribeMove", "cudecompExtRotateWalk", "cudecompExtPlanHaloAccumulate", "cudecompExtAccumulate3D",
                "cudecompExtPlanHaloFill", "cudecompExtFill3D", "cudecompExtRunMoves", "cudecompExtDescribeMoves",
                "cudecompExtPlanHaloAccumulateClear", "cudecompExtPlanHaloReflect", "cudecompExtReflect3D",
-               "cudecompExtPlanHaloFold", "cudecompExtFold3D"]
+               "cudecompExtPlanHaloFold", "cudecompExtFold3D", "cudecompExtPlanHaloFields", "cudecompExtRunFieldMoves",
+               "cudecompExtDescribeFieldMoves", "cudecompExtDataLaunchCount"]
 # include/cudecomp_amd.h: extensions of the API a solver may use
 AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
 # include/cudecomp_amd_fill.h: halo fill
@@ -164,6 +172,9 @@ AMD_ACCUMULATE_CLEAR_SYMBOLS = ["cudecompAmdAccumulateAndClearHalosX", "cudecomp
 AMD_REFLECT_SYMBOLS = ["cudecompAmdReflectHalosX", "cudecompAmdReflectHalosY", "cudecompAmdReflectHalosZ"]
 # include/cudecomp_halo_fold.h: halo folding (the ghost cells the reflection writes, summed into their mirror images)
 AMD_FOLD_SYMBOLS = ["cudecompAmdFoldHalosX", "cudecompAmdFoldHalosY", "cudecompAmdFoldHalosZ"]
+# include/cudecomp_halo_fields.h: multi-field halo updates (several pencils in one exchange)
+AMD_FIELDS_SYMBOLS = ["cudecompAmdUpdateFieldHalosX", "cudecompAmdUpdateFieldHalosY", "cudecompAmdUpdateFieldHalosZ"]
+MAX_HALO_FIELDS = 32  # CUDECOMP_AMD_MAX_HALO_FIELDS
 # the four extension headers and the functions each of them declares itself (checked by tests/test_abi.py, like API_SYMBOLS)
 AMD_HEADER_SYMBOLS = {"cudecomp_amd.h": AMD_SYMBOLS, "cudecomp_amd_fill.h": AMD_FILL_SYMBOLS,
                       "cudecomp_amd_accumulate_clear.h": AMD_ACCUMULATE_CLEAR_SYMBOLS, "cudecomp_amd_reflect.h": AMD_REFLECT_SYMBOLS}
@@ -232,6 +243,14 @@ def lib():
             getattr(L, name).argtypes = [vp, vp, vp, i32, i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         for name in AMD_FOLD_SYMBOLS:  # (the reflection's arguments with `clear` after the centering)
             getattr(L, name).argtypes = [vp, vp, vp, i32, i32, i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
+        for name in AMD_FIELDS_SYMBOLS:  # (the update's arguments with the list of fields and its length in the place of `input`)
+            getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
+        L.cudecompExtPlanHaloFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32,
+                                                C.POINTER(ExtHaloFieldsPlan)]
+        L.cudecompExtRunFieldMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(vp), i32, vp, i64, i32, i32, vp, pi32]
+        L.cudecompExtDescribeFieldMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, C.c_uint64, i64, i32, i32,
+                                                    C.POINTER(i64)]
+        L.cudecompExtDataLaunchCount.argtypes = [C.POINTER(i64)]
         L.cudecompExtGetTransposePlan.argtypes = [vp, vp, i32, pi32, pi32, pi32, pi32, C.c_bool, i32,
                                                   C.POINTER(ExtTransposePlan)]
         L.cudecompExtGetHaloPlan.argtypes = [vp, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32,
@@ -466,6 +485,15 @@ def cudecompFoldHalos(axis, handle, gd, inp, dtype, parity, centering, clear, ha
                                 _b3(halo_periods), dim, _i3(padding), stream), name)
 
 
+def cudecompUpdateFieldHalos(axis, handle, gd, ptrs, work, dtype, halo_extents, halo_periods, dim, padding=None, stream=None):
+    """cudecompAmdUpdateFieldHalos{X,Y,Z} (cudecomp_halo_fields.h): the halo update along `dim` of every pencil in `ptrs` (device
+    pointers) with one pack launch, one exchange and one unpack launch; `work` holds len(ptrs) single workspaces."""
+    name = "cudecompAmdUpdateFieldHalos" + "XYZ"[axis]
+    arr = None if ptrs is None else (C.c_void_p * max(1, len(ptrs)))(*[p or None for p in ptrs])
+    _check(getattr(lib(), name)(handle, gd, arr, 0 if ptrs is None else len(ptrs), work, dtype, _i3(halo_extents), _b3(halo_periods),
+                                dim, _i3(padding), stream), name)
+
+
 def cudecompExtGetTransposePlan(handle, gd, op, in_halo=None, out_halo=None, in_pad=None, out_pad=None, inplace=False,
                                 backend_override=0):
     p = ExtTransposePlan()
@@ -571,6 +599,14 @@ def cudecompExtPlanHaloFold(grid, rank, axis, halo_extents, halo_periods, dim, p
     p = ExtHaloPlan()
     _check(lib().cudecompExtPlanHaloFold(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding),
                                          int(centering), int(bool(negate)), int(clear), C.byref(p)), "cudecompExtPlanHaloFold")
+    return p
+
+
+def cudecompExtPlanHaloFields(grid, rank, axis, halo_extents, halo_periods, dim, padding=None, n_fields=1, force_packed=False):
+    """Stateless planner of cudecompAmdUpdateFieldHalos*: the moves of field 0, the slot layout and the offsets (cudecomp_ext.h)."""
+    p = ExtHaloFieldsPlan()
+    _check(lib().cudecompExtPlanHaloFields(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding),
+                                           int(n_fields), int(force_packed), C.byref(p)), "cudecompExtPlanHaloFields")
     return p
 
 
@@ -776,6 +812,33 @@ def cudecompExtDescribeMoves(moves, buf_addresses, es, mode=MOVES_COPY, dtype=0,
         d["index"] = [int(x) for x in l.index[:l.n]]
         res.append(d)
     return res
+
+
+def cudecompExtRunFieldMoves(moves, fields, work, work_field_stride, es, force=0, stream=None):
+    """One or two moves for every buffer of `fields` (device pointers) in one launch (cudecomp_ext.h): an end of a move in buffer 2
+    lies in `work` at its offset + f * work_field_stride, any other end in fields[f].  Returns the number of launches (0 or 1)."""
+    f = (C.c_void_p * max(1, len(fields)))(*[p or None for p in fields])
+    total = C.c_int32(-1)
+    _check(lib().cudecompExtRunFieldMoves(_move_list(moves), len(moves), f, len(fields), work or None, int(work_field_stride), es,
+                                          int(force), stream, C.byref(total)), "cudecompExtRunFieldMoves")
+    return total.value
+
+
+def cudecompExtDescribeFieldMoves(moves, field_addresses, work_address, work_field_stride, es, force=0):
+    """How cudecompExtRunFieldMoves would run (no launch, no GPU): a dict of kind (22 rows, 23 generic, -1 nothing), lane bytes,
+    access mode, workgroups per field and workgroups in all."""
+    f = (C.c_uint64 * max(1, len(field_addresses)))(*[int(p) for p in field_addresses])
+    out = (C.c_int64 * 5)()
+    _check(lib().cudecompExtDescribeFieldMoves(_move_list(moves), len(moves), f, len(field_addresses), int(work_address or 0),
+                                               int(work_field_stride), es, int(force), out), "cudecompExtDescribeFieldMoves")
+    return dict(zip(("kind", "vec", "access", "blocks_per_field", "blocks"), [int(x) for x in out]))
+
+
+def cudecompExtDataLaunchCount():
+    """Data-movement kernel launches of this process so far (cudecomp_ext.h)."""
+    n = C.c_int64(-1)
+    _check(lib().cudecompExtDataLaunchCount(C.byref(n)), "cudecompExtDataLaunchCount")
+    return n.value
 
 
 def make_config(gdims, pdims, gdims_dist=None, rank_order=0, axis_contiguous=(0, 0, 0), mem_order=None,

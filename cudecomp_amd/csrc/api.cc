@@ -973,4 +973,41 @@ CD_DEFINE_HALO_FOLD(cudecompAmdFoldHalosX, 0)
 CD_DEFINE_HALO_FOLD(cudecompAmdFoldHalosY, 1)
 CD_DEFINE_HALO_FOLD(cudecompAmdFoldHalosZ, 2)
 
+// cudecomp_halo_fields.h: the update of several pencils with one exchange.  The checks of haloEntry, in its order, with the list
+// of fields checked where the update checks `input`; all of it on the host, before anything is launched.
+static cudecompResult_t haloFieldsEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const inputs[],
+                                        int32_t n_fields, void* work, cudecompDataType_t dtype, const int32_t halo_extents[],
+                                        const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {
+  try {
+    checkHandle(handle);
+    checkGridDesc(handle, grid_desc);
+    checkDataType(dtype);
+    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
+    if (halo_extents[0] == 0 && halo_extents[1] == 0 && halo_extents[2] == 0) return CUDECOMP_RESULT_SUCCESS;
+    if (!inputs) CD_INVALID_USAGE("inputs argument cannot be null");
+    if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_HALO_FIELDS) CD_INVALID_USAGE("n_fields argument out of range");
+    for (int32_t i = 0; i < n_fields; ++i) {
+      if (!inputs[i]) CD_INVALID_USAGE("inputs argument cannot hold a null entry");
+      for (int32_t j = 0; j < i; ++j)
+        if (inputs[j] == inputs[i]) CD_INVALID_USAGE("inputs argument cannot hold the same field twice");
+    }
+    if (!work) CD_INVALID_USAGE("work argument cannot be null");
+    if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
+    runHaloFields(handle, grid_desc, axis, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, padding, stream);
+  }
+  CD_API_CATCH()
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+#define CD_DEFINE_HALO_FIELDS(NAME, AXIS)                                                                                      \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const inputs[], int32_t n_fields,         \
+                        void* work, cudecompDataType_t dtype, const int32_t halo_extents[], const bool halo_periods[],         \
+                        int32_t dim, const int32_t padding[], hipStream_t stream) {                                            \
+    return haloFieldsEntry(AXIS, handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, padding,   \
+                           stream);                                                                                            \
+  }
+CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosX, 0)
+CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosY, 1)
+CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosZ, 2)
+
 }  // extern "C"

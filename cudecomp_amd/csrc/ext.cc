@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "cudecomp_ext.h"
+#include "cudecomp_halo_fields.h"
 #include "errors.h"
 #include "internal.h"
 #include "rotate_walk.h"
@@ -919,6 +920,114 @@ cudecompResult_t cudecompExtFold3D(const void* src, void* dst, cudecompDataType_
   } catch (...) {
     return CUDECOMP_RESULT_INTERNAL_ERROR;
   }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+static std::vector<Move3D> importFieldMoves(const cudecompExtMove_t* moves, int32_t n, int32_t n_fields, int32_t es) {
+  if (n < 0 || n > 2 || (n > 0 && !moves)) CD_INVALID_USAGE("a field launch takes at most two moves");
+  if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_HALO_FIELDS) CD_INVALID_USAGE("n_fields out of range");
+  if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
+  std::vector<Move3D> list(n);
+  for (int32_t i = 0; i < n; ++i) {
+    const cudecompExtMove_t& e = moves[i];
+    if (e.src_buf < 0 || e.src_buf > 2 || e.dst_buf < 0 || e.dst_buf > 2) CD_INVALID_USAGE("buffer number out of range");
+    Move3D& m = list[i];
+    m.src_buf = (BufId)e.src_buf;
+    m.dst_buf = (BufId)e.dst_buf;
+    m.src_off = e.src_off;
+    m.dst_off = e.dst_off;
+    for (int d = 0; d < 3; ++d) {
+      m.extent[d] = e.extent[d];
+      m.ss[d] = e.ss[d];
+      m.ds[d] = e.ds[d];
+    }
+    m.dst_row_pitch = e.row_pitch;
+  }
+  return list;
+}
+
+cudecompResult_t cudecompExtPlanHaloFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
+                                           const bool periods[], int32_t dim, const int32_t pad[], int32_t n_fields,
+                                           int32_t force_packed, cudecompExtHaloFieldsPlan_t* out) {
+  try {
+    const GridShape g = shapeFromSpec(grid);
+    if (!out || !halo) CD_INVALID_USAGE("null argument");
+    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
+    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
+    const int32_t zero[3] = {0, 0, 0};
+    const bool none[3] = {false, false, false};
+    const HaloFieldsPlan fp = buildHaloFieldsPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, n_fields,
+                                                  force_packed != 0);
+    const HaloPlan& p = fp.base;
+    std::memset(out, 0, sizeof(*out));
+    out->kind = (int32_t)p.kind;
+    out->comm_axis = p.comm_axis;
+    out->n_fields = fp.n_fields;
+    out->face_elements = p.face_elements;
+    out->slot_elements = fp.slot_elements;
+    for (int i = 0; i < 2; ++i) {
+      out->neighbor[i] = p.neighbor[i];
+      out->send_off[i] = p.send_off[i];
+      out->recv_off[i] = p.recv_off[i];
+    }
+    out->n_pre = (int32_t)p.pre.size();
+    out->n_post = (int32_t)p.post.size();
+    for (size_t i = 0; i < p.pre.size(); ++i) exportMove(p.pre[i], &out->pre[i]);
+    for (size_t i = 0; i < p.post.size(); ++i) exportMove(p.post[i], &out->post[i]);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtRunFieldMoves(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
+                                         void* work, int64_t work_field_stride, int32_t es, int32_t force, hipStream_t stream,
+                                         int32_t* n_launches) {
+  try {
+    if (!fields) CD_INVALID_USAGE("null argument");
+    const std::vector<Move3D> list = importFieldMoves(moves, n, n_fields, es);
+    KernelStats st;
+    launchFieldMoves(list.data(), n, fields, n_fields, work, work_field_stride, es, stream, force, &st);
+    if (n_launches) {
+      *n_launches = 0;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c) *n_launches += st.launches[c];
+    }
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtDescribeFieldMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
+                                              int32_t n_fields, uint64_t work_address, int64_t work_field_stride, int32_t es,
+                                              int32_t force, int64_t out[5]) {
+  try {
+    if (!field_addresses || !out) CD_INVALID_USAGE("null argument");
+    const std::vector<Move3D> list = importFieldMoves(moves, n, n_fields, es);
+    std::vector<void*> fields(n_fields);
+    for (int32_t f = 0; f < n_fields; ++f) fields[f] = reinterpret_cast<void*>(field_addresses[f]);
+    const FieldLaunch l = planFieldLaunch(list.data(), n, fields.data(), n_fields, reinterpret_cast<void*>(work_address),
+                                          work_field_stride, es, force);
+    out[0] = l.blocks ? (int64_t)l.k.kind : -1;
+    out[1] = l.k.vec;
+    out[2] = l.k.access;
+    out[3] = l.blocks_per_field;
+    out[4] = l.blocks;
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtDataLaunchCount(int64_t* launches) {
+  if (!launches) return CUDECOMP_RESULT_INVALID_USAGE;
+  *launches = dataLaunchCount();
   return CUDECOMP_RESULT_SUCCESS;
 }
 

@@ -16,6 +16,7 @@
 #include "cudecomp_amd_fill.h"
 #include "cudecomp_amd_reflect.h"
 #include "cudecomp_halo_fold.h"
+#include "cudecomp_halo_fields.h"
 #include "decomp.h"
 #include "errors.h"
 #include "kernels.h"
@@ -144,6 +145,8 @@ struct cudecompGridDesc {
   std::map<std::tuple<HaloKey, int, bool>, cudecomp::HaloPlan> halo_reflect_plans;
   // cudecompAmdFoldHalos*: the same key plus (centering, sign flip, clear)
   std::map<std::tuple<HaloKey, int, bool, bool>, cudecomp::HaloPlan> halo_fold_plans;
+  // cudecompAmdUpdateFieldHalos* with two fields or more: the same key plus n_fields
+  std::map<std::tuple<HaloKey, int>, cudecomp::HaloFieldsPlan> halo_fields_plans;
 
   // CUDECOMP_ENABLE_CUDA_GRAPHS=1: the per-peer pack loop of the pipelined backends (one kernel + one event
   // record per destination) is captured once per (plan, buffers, element size) and replayed as one graph launch
@@ -277,6 +280,10 @@ void runHaloReflect(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, vo
                     int centering, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream);
 void runHaloFold(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, int parity,
                  int centering, int clear, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream);
+// cudecompAmdUpdateFieldHalos*: n_fields pencils, one exchange (n_fields == 1 IS runHalo)
+void runHaloFields(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* const* inputs, int n_fields, void* work,
+                   cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
+                   hipStream_t stream);
 
 // perf.cc
 struct TransposeTimings {

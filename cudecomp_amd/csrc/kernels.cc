@@ -8,7 +8,8 @@
 // batching key, the launcher's instantiation and the kernel's name all come from that one record.  The kernels live in
 // kernels_rows.hip, kernels_transpose.hip (one code object per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip and kernels_fold.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
-// transpose.cc.  kernels_batch.h says why they are separate code objects.
+// transpose.cc; kernels_fields.hip (field-moves: the moves of a halo phase for several pencils in one launch) has an entry of its
+// own at the end of this file, launchFieldMoves.  kernels_batch.h says why they are separate code objects.
 //
 // 2-byte elements (fp16, bf16) take the row copy (plain kernel), the LDS-tiled transposition (128 x 128 tiles with 16-byte
 // lanes, 64 x 64 element-wise) and the generic kernel only: never the window, lines, row-lines, shifted-rows, dense-rows or
@@ -49,7 +50,7 @@ constexpr long long kDenseMaxGapBytes = 512;  // widest gap between rows the den
 
 MoveClass classOf(KernelKind kind) {
   if (kind == K_GENERIC || kind == K_GENERIC_ADD || kind == K_GENERIC_FILL || kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE ||
-      kind == K_GENERIC_REFLECT || kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE)
+      kind == K_GENERIC_REFLECT || kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE || kind == K_GENERIC_FIELDS)
     return MOVE_GENERIC;
   return kind >= K_TRANSPOSE && kind <= K_TRANSPOSE_ROWLINES ? MOVE_TRANSPOSE : MOVE_ROWS_VEC;
 }
@@ -564,6 +565,8 @@ void spellKernelName(const KernelChoice& k) {
       snprintf(out, n, "generic_fold_kernel<%s,%d,%s>", arithName(k.arith), k.es / arithBytes(k.arith),
                k.kind == K_GENERIC_FOLD_TAKE ? "true" : "false");
       break;
+    case K_ROWS_FIELDS: snprintf(out, n, "rows_fields_kernel<%d,%d>", k.vec, s); break;
+    case K_GENERIC_FIELDS: snprintf(out, n, "generic_fields_kernel<%d>", k.es); break;
   }
 }
 
@@ -582,8 +585,11 @@ FillPattern fillPatternOf(const void* value, int es, const void* cell) {
   return p;
 }
 
+long long g_data_launches = 0;
+
 void launchBatch(const KernelChoice& k, const Batch& b, const void* fill_value, unsigned int blocks, hipStream_t stream) {
   spellKernelName(k);
+  ++g_data_launches;
   switch (k.kind) {
     case K_ROWS:
     case K_ROWS_SHIFTED:
@@ -612,6 +618,8 @@ void launchBatch(const KernelChoice& k, const Batch& b, const void* fill_value, 
     case K_GENERIC_FOLD:
     case K_ROWS_FOLD_TAKE:
     case K_GENERIC_FOLD_TAKE: launchFoldBatch(k, b, blocks, stream); break;
+    case K_ROWS_FIELDS:
+    case K_GENERIC_FIELDS: CD_INTERNAL_ERROR("field-moves are launched by launchFieldMoves");
   }
 }
 
@@ -620,6 +628,7 @@ const KernelTuning kDefaultTuning;
 }  // namespace
 
 const char* lastKernelName() { return g_last_kernel; }
+long long dataLaunchCount() { return g_data_launches; }
 
 void describeMove(const Move3D& m, const void* src, void* dst, int es, const KernelTuning* tuning, long long out[10]) {
   Move3D mm = m;  // (keeps dst_row_pitch)
@@ -707,6 +716,119 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
       stats->launches[l.cls] += 1;
       stats->elements[l.cls] += l.elements;
     }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// field-moves (kernels.h; kernels_fields.hip)
+// ---------------------------------------------------------------------------------------------
+FieldLaunch planFieldLaunch(const Move3D* moves, int n, void* const* fields, int n_fields, void* work, i64 work_field_stride,
+                            int es, int force) {
+  if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
+  if (n < 0 || n > 2) CD_INTERNAL_ERROR("a field launch serves at most two moves");
+  if (n_fields < 1 || n_fields > kMaxFields || !fields) CD_INTERNAL_ERROR("field count out of range");
+  for (int f = 0; f < n_fields; ++f)
+    if (!fields[f]) CD_INTERNAL_ERROR("null field buffer");
+  FieldLaunch l{};
+  FieldBatch& b = l.b;
+  b.n_fields = n_fields;
+  b.work = static_cast<char*>(work);
+  for (int f = 0; f < n_fields; ++f) b.field[f] = static_cast<char*>(fields[f]);
+  l.k.es = es;
+  const bool force_generic = (force & 1) != 0;
+
+  // the shared geometry, normalised, and every address a lane's first element can have, or-ed together (the 2-byte rule)
+  Move3D norm[2];
+  uintptr_t address_bits = 0;
+  bool rows = !force_generic;
+  i64 largest = 0;
+  for (int i = 0; i < n; ++i) {
+    const Move3D& in = moves[i];
+    if (in.add || in.fill || in.take || in.reflect || in.negate || in.dst_row_pitch != 0)
+      CD_INTERNAL_ERROR("field-moves are plain copies of exactly their cells");
+    if ((in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK) && !work) CD_INTERNAL_ERROR("field-move through a workspace that was not given");
+    for (int d = 0; d < 3; ++d)
+      if (in.ss[d] < 0 || in.ds[d] < 0 || in.extent[d] < 0) CD_INTERNAL_ERROR("negative stride or extent in a field-move");
+    if (in.elements() == 0) continue;
+    Move3D m = in;
+    normalizeMove(m);
+    rows = rows && m.ss[0] <= 1 && m.ds[0] <= 1;
+    largest = std::max(largest, m.elements());
+    FieldSide& s = b.side[b.n_sides];
+    s.src_work = in.src_buf == BUF_WORK;
+    s.dst_work = in.dst_buf == BUF_WORK;
+    s.src_off = in.src_off * es;
+    s.dst_off = in.dst_off * es;
+    s.src_step = s.src_work ? work_field_stride * es : 0;
+    s.dst_step = s.dst_work ? work_field_stride * es : 0;
+    for (int f = 0; f < n_fields; ++f) {
+      address_bits |= reinterpret_cast<uintptr_t>(s.src_work ? b.work + f * s.src_step : b.field[f]) + (uintptr_t)s.src_off;
+      address_bits |= reinterpret_cast<uintptr_t>(s.dst_work ? b.work + f * s.dst_step : b.field[f]) + (uintptr_t)s.dst_off;
+    }
+    norm[b.n_sides++] = m;
+  }
+  if (b.n_sides == 0) return l;
+
+  const bool streaming = (largest * es >= kStreamBytes || (force & 2)) && !(force & 4);
+  Classified c[2] = {};
+  int vb = 16;
+  for (int i = 0; i < b.n_sides; ++i) {
+    c[i].k.es = es;
+    c[i].elements = norm[i].elements();
+    c[i].dm.src = reinterpret_cast<const char*>(address_bits);  // (only its alignment is read)
+    c[i].dm.dst = reinterpret_cast<char*>(address_bits);
+    if (rows) {
+      rowVectors(c[i], norm[i]);
+      vb = std::min(vb, c[i].k.vec);
+    } else {
+      genericGeometry(c[i], norm[i]);
+    }
+  }
+  l.k.kind = rows ? K_ROWS_FIELDS : K_GENERIC_FIELDS;
+  l.k.vec = rows ? vb : es;
+  l.k.access = rows && streaming ? 1 : 0;
+  l.k.arith = ARITH_NONE;
+  l.cls = classOf(l.k.kind);
+  if (rows && vb < es) CD_INTERNAL_ERROR("field-move narrower than one element");
+  unsigned long long per_field = 0;
+  for (int i = 0; i < b.n_sides; ++i) {
+    if (rows) {  // one lane width for the launch: the narrowest (a power of two, so it divides every row)
+      c[i].k.vec = vb;
+      c[i].dm.e[0] = norm[i].extent[0] * es / vb;
+      rowTiles(c[i]);
+    }
+    if (c[i].blocks == 0 || c[i].blocks > 0x7fffffffULL) CD_NOT_SUPPORTED("single block move too large for one launch");
+    FieldSide& s = b.side[i];
+    for (int d = 0; d < 3; ++d) {
+      s.e[d] = c[i].dm.e[d];
+      s.ss[d] = c[i].dm.ss[d];
+      s.ds[d] = c[i].dm.ds[d];
+    }
+    s.p0 = c[i].p0;
+    s.t0 = c[i].t0;
+    s.t1 = c[i].t1;
+    s.blocks = (unsigned int)c[i].blocks;
+    per_field += c[i].blocks;
+    l.elements += c[i].elements * n_fields;
+  }
+  const unsigned long long total = per_field * (unsigned long long)n_fields;
+  if (total > 0x7fffffffULL) CD_NOT_SUPPORTED("field-moves too large for one launch");
+  b.side1_first = (unsigned int)((unsigned long long)b.side[0].blocks * n_fields);
+  l.blocks_per_field = (unsigned int)per_field;
+  l.blocks = (unsigned int)total;
+  return l;
+}
+
+void launchFieldMoves(const Move3D* moves, int n, void* const* fields, int n_fields, void* work, i64 work_field_stride, int es,
+                      hipStream_t stream, int force, KernelStats* stats) {
+  const FieldLaunch l = planFieldLaunch(moves, n, fields, n_fields, work, work_field_stride, es, force);
+  if (l.blocks == 0) return;
+  spellKernelName(l.k);
+  ++g_data_launches;
+  launchFieldsBatch(l.k, l.b, l.blocks, stream);
+  if (stats) {
+    stats->launches[l.cls] += 1;
+    stats->elements[l.cls] += l.elements;
   }
 }
 

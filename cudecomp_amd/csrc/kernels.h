@@ -77,6 +77,34 @@ std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3]
 // 4 runs over batch planes, 8 transpose_lines_kernel, 16 transpose_rowlines_kernel), access mode}.  (Tests of the planning logic: tests/test_kernel_plan.py.)
 void describeMove(const Move3D& m, const void* src, void* dst, int es, const KernelTuning* tuning, long long out[10]);
 
+// ---- field-moves: the same one or two copy moves for several buffers in ONE launch (kernels_fields.hip) ---------------------
+// The moves of one phase of a multi-field halo update (include/cudecomp_halo_fields.h): moves[0 .. n - 1], n <= 2, share their
+// geometry among `n_fields` (1 .. kern::kMaxFields) fields.  An end of a move whose buffer is BUF_WORK lies in the workspace, at
+// work + (offset + f * work_field_stride) elements for field f; any other end lies in field f's own buffer, fields[f] + offset.
+// The kernels copy exactly the cells of the moves -- rows (rowVectors' rule) or element by element (genericGeometry's), never a
+// transposing, shifted or dense form -- and ONE kernel choice serves the launch: rows only when every move has contiguous rows,
+// the narrowest of the moves' lane widths, and for 2-byte elements 2-byte lanes as soon as ANY field's address or any stride is
+// 2 mod 4.  Access: cached while every move is below kStreamBytes PER FIELD, non-temporal loads and stores from there; the
+// element-wise kernel always caches.  force: bit 0 the element-wise kernel, bit 1 non-temporal access regardless of the size, bit 2
+// cached access regardless of the size.  A move with add, fill, take, reflect, negate or dst_row_pitch, and a workspace end
+// without a workspace, are internal errors before anything is launched; more than 2^31 - 1 workgroups is NOT_SUPPORTED.
+struct FieldLaunch {
+  KernelChoice k;
+  kern::FieldBatch b;
+  unsigned int blocks;            // 0: every move is empty, nothing is launched
+  unsigned int blocks_per_field;  // of all its sides
+  MoveClass cls;
+  i64 elements;                   // of all moves and fields
+};
+// WHICH launch launchFieldMoves makes (pure host code, no device needed; `fields` and `work` are only looked at as addresses)
+FieldLaunch planFieldLaunch(const Move3D* moves, int n, void* const* fields, int n_fields, void* work, i64 work_field_stride,
+                            int es, int force = 0);
+void launchFieldMoves(const Move3D* moves, int n, void* const* fields, int n_fields, void* work, i64 work_field_stride, int es,
+                      hipStream_t stream, int force = 0, KernelStats* stats = nullptr);
+
+// data-movement launches this process has made so far (launchMoves and launchFieldMoves; tests count launches per call with it)
+long long dataLaunchCount();
+
 // name (template spelling) of the data-movement kernel launched last by this process, "" before the first launch
 const char* lastKernelName();
 

@@ -2,7 +2,8 @@
 // kernel choice (KernelChoice), the launch descriptor (Batch) and the launchers.  The code objects the classifier dispatches
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip;
-// kernels_rotate.hip and sync.hip are launched by the executor.  Fifteen code objects in all.
+// kernels_fields.hip is reached through launchFieldMoves (kernels.h); kernels_rotate.hip and sync.hip are launched by the
+// executor.  Sixteen code objects in all.
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
 // code object beyond roughly 0.6-0.7 MB puts the whole process into a regime where every small synchronous operation costs
@@ -65,6 +66,34 @@ struct Batch {
   DevMove m[kMaxBatch];
 };
 
+// ---- field-moves: the same one or two moves for up to kMaxFields buffers, in ONE launch (kernels_fields.hip) ------------------
+// A phase of a multi-field halo update has at most two sides (low, high) whose geometry is the same for every field: only the
+// base pointers differ.  A side therefore carries byte OFFSETS in the place of DevMove's pointers; each end of it is either
+// "field f's pencil" (base = field[f]) or "the workspace" (base = work + f * step bytes: the fields' pieces of one slot lie one
+// behind the other).  Workgroup b serves side 0 while b < side1_first, side 1 from there; inside a side, field b / blocks and
+// that field's workgroup b % blocks -- one decode per workgroup.
+constexpr int kMaxFields = 32;  // one 256-byte table of pointers in the kernel arguments (include/cudecomp_halo_fields.h)
+
+struct FieldSide {
+  long long src_off, dst_off;    // bytes from the base of that end
+  long long src_step, dst_step;  // workspace ends: bytes between the pieces of consecutive fields (unused for pencil ends)
+  long long e[3];                // as DevMove: rows_fields_kernel vectors per row / rows / planes, strides in BYTES;
+  long long ss[3];               // generic_fields_kernel extents and strides in ELEMENTS
+  long long ds[3];
+  int src_work, dst_work;        // 1: that end is the workspace, 0: field f's pencil
+  int p0;                        // rows: log2 of the lanes per row; element-wise: the dim the lanes run along
+  unsigned int t0, t1;           // rows: tile columns / tile rows per plane
+  unsigned int blocks;           // workgroups PER FIELD
+};
+
+struct FieldBatch {
+  int n_sides, n_fields;
+  unsigned int side1_first;  // n_fields * side[0].blocks
+  char* work;
+  FieldSide side[2];
+  char* field[kMaxFields];
+};
+
 }  // namespace kern
 
 // ---- what runs: one record per kernel choice ----------------------------------------------------------------------------------
@@ -91,7 +120,9 @@ enum KernelKind {
   K_ROWS_FOLD,           // rows_fold_kernel (dst += src or dst += -src, the source backwards along the row or plane index) = 18
   K_GENERIC_FOLD,        // generic_fold_kernel = 19
   K_ROWS_FOLD_TAKE,      // rows_fold_kernel with TAKE (... ; src = 0) = 20
-  K_GENERIC_FOLD_TAKE    // generic_fold_kernel with TAKE = 21
+  K_GENERIC_FOLD_TAKE,   // generic_fold_kernel with TAKE = 21
+  K_ROWS_FIELDS,         // rows_fields_kernel (dst = src, the same move for every field of a FieldBatch) = 22
+  K_GENERIC_FIELDS       // generic_fields_kernel = 23
 };
 struct KernelChoice {
   KernelKind kind;
@@ -101,7 +132,8 @@ struct KernelChoice {
   int access;       // copies: 0 default caching, 2 non-temporal loads + stores, 3 non-temporal loads + remote (system-scope
                     // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads;
                     // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it);
-                    // reflections: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores
+                    // reflections: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores;
+                    // field-moves: 0, 1 non-temporal loads and stores
   ArithType arith;  // additions, folds, reflections that flip the sign bits: the real type the elements consist of; ARITH_NONE otherwise
   bool neg;         // folds: the sign bits of the source are flipped before the addition (one sign mask per launch)
   bool operator==(const KernelChoice& o) const {
@@ -123,6 +155,8 @@ inline int streamArgOf(KernelKind kind, int access) {
   if (kind == K_GENERIC_REFLECT) return 0;
   if (kind == K_ROWS_FOLD || kind == K_ROWS_FOLD_TAKE) return access;
   if (kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE) return 0;
+  if (kind == K_ROWS_FIELDS) return access;
+  if (kind == K_GENERIC_FIELDS) return 0;
   if (kind == K_TRANSPOSE_WINDOW || kind == K_TRANSPOSE_LINES || kind == K_TRANSPOSE_ROWLINES)
     return access == 2 ? 4 : access;  // always cached loads: the overlap rows of neighbouring windows hit in L2
   return access == 3 ? 3 : (access >= 1 ? 1 : 0);  // row copies: loads and stores stream together
@@ -165,6 +199,8 @@ void launchReflectBatch(const KernelChoice& k, const kern::Batch& b, unsigned in
 // signed strides in elements.  k.arith: the real type of the addition; k.neg: the sign mask of that type travels as a 16-byte
 // kernel argument of its own, all zero otherwise.  Local buffers only.
 void launchFoldBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+// kernels_fields.hip: field-moves (plain copies of exactly the cells of the moves; local buffers only)
+void launchFieldsBatch(const KernelChoice& k, const kern::FieldBatch& b, unsigned int blocks, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

@@ -233,6 +233,25 @@ HaloPlan buildHaloReflectPlan(const GridShape& g, int rank, int axis, int dim, c
 HaloPlan buildHaloFoldPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
                            const int32_t* pad, int centering, bool negate, bool clear, bool self_exchange = false);
 
+// Multi-field halo UPDATE along `dim` (include/cudecomp_halo_fields.h has the contract): `n_fields` pencils of one descriptor, axis,
+// halos and padding updated by one exchange.  Derived from buildHaloPlan(..., force_packed = true for n_fields >= 2): its refusals,
+// neighbours, faces and "which cells" hold by construction.  Kinds: NONE, SELF_PERIODIC (the two wrap copies, pencil -> pencil,
+// carried out for every field) or PACKED -- never DIRECT for n_fields >= 2: one message per direction is the point, and the
+// exchange describes one contiguous piece per direction.  The moves in `base` are those of field 0: an end in BUF_IN is "field
+// f's pencil" at the same offset, an end in BUF_WORK lies at its offset + f * face_elements.  Workspace: [send low | send high |
+// recv low | recv high], each slot slot_elements = alignElements(n_fields * face_elements) long -- never more than n_fields times
+// haloWorkspaceElements.  Neighbours along `dim` share the extents of the other two dims, so the slot size and the offsets are the
+// same on both ends of every exchange (the one-sided transport needs that).  The exchange moves n_fields * face_elements elements
+// per direction, from send_off[i] to the neighbour's recv_off[1 - i].  n_fields == 1: the plan of buildHaloPlan with the caller's
+// force_packed, unchanged.
+struct HaloFieldsPlan {
+  HaloPlan base;
+  int n_fields = 1;
+  i64 slot_elements = 0;
+};
+HaloFieldsPlan buildHaloFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                   const int32_t* pad, int n_fields, bool force_packed, bool self_exchange = false);
+
 // Number of stages every member of the communicator arrives at without talking: at most `wanted`, at most the smallest
 // chunk extent, at most 14 (flag steps), and no stage smaller than `min_stage_bytes` of the largest pencil (below that the extra
 // launches cost more than the overlap gains).

@@ -476,6 +476,44 @@ void runHalo(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, v
   perfMark(pev, 3, stream);
 }
 
+// Multi-field halo update (cudecompAmdUpdateFieldHalos*): the plain sequence pack all fields (one launch) -> one exchange of
+// n_fields faces per direction -> unpack all fields (one launch); self-periodic: the wrap copies of all fields in one launch.
+// The overlapped path of runHalo (haloExchangePackedOverlapped) is not used: it runs the plan's moves itself through bufs[3].
+// Not sampled by the performance report.  One field: runHalo itself.
+void runHaloFields(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* const* inputs, int n_fields, void* work,
+                   cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
+  if (n_fields == 1) return runHalo(h, gd, axis, inputs[0], work, dtype, halo, periods, dim, pad, stream);
+  const int es = elementSize(dtype);
+  const auto backend = gd->config.halo_comm_backend;
+  const bool force_packed = true;  // (always, for two fields or more)
+
+  const auto hh = arr3(halo), pp = arr3(pad);
+  std::array<bool, 3> per{false, false, false};
+  if (periods)
+    for (int i = 0; i < 3; ++i) per[i] = periods[i];
+  const cudecompGridDesc::HaloKey hkey{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, force_packed};
+  const std::tuple<cudecompGridDesc::HaloKey, int> key{hkey, n_fields};
+  auto it = gd->halo_fields_plans.find(key);
+  if (it == gd->halo_fields_plans.end()) {
+    HaloFieldsPlan p = buildHaloFieldsPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), n_fields, force_packed,
+                                           h->self_exchange);
+    it = gd->halo_fields_plans.emplace(key, std::move(p)).first;
+  }
+  const HaloFieldsPlan& fp = it->second;
+  const HaloPlan& plan = fp.base;
+  if (plan.kind == HaloPlan::NONE) return;
+
+  ensureDevice(h);
+  const int force = (h->tuning.force_class == MOVE_GENERIC ? 1 : 0) | (h->tuning.force_streaming ? 2 : 0) | (h->tuning.no_streaming ? 4 : 0);
+  launchFieldMoves(plan.pre.data(), (int)plan.pre.size(), inputs, n_fields, work, plan.face_elements, es, stream, force);
+  if (plan.kind == HaloPlan::SELF_PERIODIC) return;
+  void* bufs[3] = {nullptr, nullptr, work};
+  HaloExchange x = haloExchangeOf(plan, bufs, es);
+  x.bytes = (i64)n_fields * plan.face_elements * es;
+  haloExchange(h, gd, x, backend, stream);
+  launchFieldMoves(plan.post.data(), (int)plan.post.size(), inputs, n_fields, work, plan.face_elements, es, stream, force);
+}
+
 // Halo accumulation (cudecompAmdAccumulateHalos*): the plain sequence pack my halos -> exchange -> add what arrived onto my
 // faces, with the exchange of the updates (haloExchange: same routing, same transports, same stream ordering).  Not sampled
 // by the performance report.  `clear`: the fused accumulate-and-clear (cudecompAmdAccumulateAndClearHalos*) -- the plan of

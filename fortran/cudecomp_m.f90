@@ -637,6 +637,56 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompAmdFoldHalosZ_C
 
+    function cudecompAmdUpdateFieldHalosX_C(handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, &
+                                            padding, stream) bind(C, name="cudecompAmdUpdateFieldHalosX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      integer(c_int32_t), value :: n_fields
+      type(c_ptr) :: inputs(*)
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdUpdateFieldHalosX_C
+
+    function cudecompAmdUpdateFieldHalosY_C(handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, &
+                                            padding, stream) bind(C, name="cudecompAmdUpdateFieldHalosY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      integer(c_int32_t), value :: n_fields
+      type(c_ptr) :: inputs(*)
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdUpdateFieldHalosY_C
+
+    function cudecompAmdUpdateFieldHalosZ_C(handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, &
+                                            padding, stream) bind(C, name="cudecompAmdUpdateFieldHalosZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      integer(c_int32_t), value :: n_fields
+      type(c_ptr) :: inputs(*)
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdUpdateFieldHalosZ_C
 
     function cudecomp_c_strlen(str) bind(C, name="strlen") result(n)
       import
@@ -1382,6 +1432,76 @@ contains
     res = cudecompAmdFoldHalosZ_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
                                       int(centering, c_int32_t), int(clear, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
   end function cudecompAmdFoldHalosZ
+
+  ! ---- multi-field halo updates (include/cudecomp_halo_fields.h): n_fields pencils, one exchange --------------------------
+  ! inputs: the device addresses of the n_fields pencils (c_loc of each field); the other arguments as for cudecompUpdateHalosX
+  function cudecompAmdUpdateFieldHalosX(handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, padding, &
+                                        stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    type(*), dimension(..), target :: work
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdUpdateFieldHalosX_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), c_loc(work), int(dtype, c_int), h, per, &
+                                         int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdUpdateFieldHalosX
+
+  ! inputs: the device addresses of the n_fields pencils (c_loc of each field); the other arguments as for cudecompUpdateHalosY
+  function cudecompAmdUpdateFieldHalosY(handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, padding, &
+                                        stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    type(*), dimension(..), target :: work
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdUpdateFieldHalosY_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), c_loc(work), int(dtype, c_int), h, per, &
+                                         int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdUpdateFieldHalosY
+
+  ! inputs: the device addresses of the n_fields pencils (c_loc of each field); the other arguments as for cudecompUpdateHalosZ
+  function cudecompAmdUpdateFieldHalosZ(handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, padding, &
+                                        stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    type(*), dimension(..), target :: work
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdUpdateFieldHalosZ_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), c_loc(work), int(dtype, c_int), h, per, &
+                                         int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdUpdateFieldHalosZ
 
 
   subroutine halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)

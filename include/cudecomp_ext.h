@@ -165,6 +165,24 @@ cudecompResult_t cudecompExtPlanHaloFold(const cudecompExtGridSpec_t* grid, int3
                                          const int32_t padding[], int32_t centering, int32_t negate, int32_t clear,
                                          cudecompExtHaloPlan_t* plan);
 
+/* The plan cudecompAmdUpdateFieldHalos{X,Y,Z} (cudecomp_halo_fields.h) would run on `rank` for n_fields fields (csrc/plan.h
+ * buildHaloFieldsPlan).  kind as in cudecompExtHaloPlan_t; never 3 for n_fields >= 2, whatever force_packed says (n_fields == 1:
+ * the plan of cudecompExtPlanHalo with that force_packed).  pre / post are the moves of FIELD 0: an end in buffer 0 is "field f's
+ * pencil" at the same offset for every f, an end in buffer 2 (the workspace) lies at its offset + f * face_elements.  The
+ * workspace is [send low | send high | recv low | recv high], each slot slot_elements long (0 unless kind is 2); send_off / recv_off
+ * are the slots' starts; the exchange moves n_fields * face_elements elements per direction.  The refusals are those of
+ * cudecompExtPlanHalo, then CUDECOMP_RESULT_INVALID_USAGE for n_fields < 1. */
+typedef struct {
+  int32_t kind, comm_axis, neighbor[2];
+  int32_t n_fields, n_pre, n_post, reserved;
+  int64_t face_elements, slot_elements, send_off[2], recv_off[2];
+  cudecompExtMove_t pre[2], post[2];
+} cudecompExtHaloFieldsPlan_t;
+cudecompResult_t cudecompExtPlanHaloFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
+                                           const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
+                                           const int32_t padding[], int32_t n_fields, int32_t force_packed,
+                                           cudecompExtHaloFieldsPlan_t* plan);
+
 /* Stateless geometry queries on a grid spec (no handle, no communicator): what cudecompGetPencilInfo,
  * cudecompGetShiftedRank, cudecompGetTransposeWorkspaceSize and cudecompGetHaloWorkspaceSize would answer on `rank`. */
 cudecompResult_t cudecompExtPencilInfo(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
@@ -363,6 +381,28 @@ cudecompResult_t cudecompExtRunMoves(const cudecompExtMove_t* moves, int32_t n, 
 cudecompResult_t cudecompExtDescribeMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t buf_addresses[3], int32_t es,
                                          int32_t mode, cudecompDataType_t dtype, int32_t flags, const uint64_t* dst_base_addresses,
                                          cudecompExtLaunch_t* launches, int32_t max_launches, int32_t* n_launches);
+
+/* Field-moves (csrc/kernels.h launchFieldMoves; kernels_fields.hip): moves[0 .. n - 1], n <= 2, carried out for n_fields (1 .. 32)
+ * buffers in ONE launch.  The two buffer numbers of a move are its direction flags: an end in buffer 2 lies in the workspace, at
+ * work + (offset + f * work_field_stride) elements for field f; an end in buffer 0 or 1 lies in field f's own buffer, fields[f] +
+ * offset (elements of `es` bytes; peer and row_pitch must be 0 / are refused as launchFieldMoves refuses them).  Destinations
+ * must be disjoint from each other and from all sources.  force: bit 0 the element-wise kernel, bit 1 non-temporal access
+ * regardless of the size, bit 2 cached access regardless of the size (as for cudecompExtFill3D).  *n_launches (optional): 1, or
+ * 0 when every move is empty.
+ *
+ * cudecompExtDescribeFieldMoves answers how that call would run, without a device: the same arguments with addresses as
+ * integers; out[5] = {kind (csrc/kernels_batch.h KernelKind: 22 rows_fields_kernel, 23 generic_fields_kernel; -1 nothing to
+ * launch), bytes per lane, access mode (0 cached, 1 non-temporal loads and stores), workgroups per field, workgroups in all}. */
+cudecompResult_t cudecompExtRunFieldMoves(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
+                                         void* work, int64_t work_field_stride, int32_t es, int32_t force, hipStream_t stream,
+                                         int32_t* n_launches);
+cudecompResult_t cudecompExtDescribeFieldMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
+                                              int32_t n_fields, uint64_t work_address, int64_t work_field_stride, int32_t es,
+                                              int32_t force, int64_t out[5]);
+
+/* Data-movement kernel launches this process has made so far through the kernel layer (launchMoves and launchFieldMoves; the
+ * signal / wait kernels and copies of the transports are not counted).  Tests take the difference around a call. */
+cudecompResult_t cudecompExtDataLaunchCount(int64_t* launches);
 
 /* The orbit walk of the in-place rotation kernel (csrc/rotate_walk.h; no launch, works without a GPU): for an array of nb
  * blocks per edge and walk (-1 = the default), *grid = the workgroups a launch has, and for workgroups first .. first + count - 1
