@@ -135,6 +135,11 @@ class ExtLaunch(C.Structure):
         ("blocks", C.c_int64), ("elements", C.c_int64), ("first_block", C.c_int64 * 9), ("index", C.c_int32 * 8)]
 
 
+class ExtFieldMoveLaunch(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kind", "es", "vec", "ti", "tj", "access", "guard", "n_moves")] + [
+        ("blocks", C.c_int64), ("blocks_per_field", C.c_int64), ("index", C.c_int32 * 8)]
+
+
 class ExtGridSpec(C.Structure):
     _fields_ = [("gdims", C.c_int32 * 3), ("gdims_dist", C.c_int32 * 3), ("pdims", C.c_int32 * 2),
                 ("col_major", C.c_int32), ("mem_order", (C.c_int32 * 3) * 3)]
@@ -160,7 +165,8 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtPlanHaloFill", "cudecompExtFill3D", "cudecompExtRunMoves", "cudecompExtDescribeMoves",
                "cudecompExtPlanHaloAccumulateClear", "cudecompExtPlanHaloReflect", "cudecompExtReflect3D",
                "cudecompExtPlanHaloFold", "cudecompExtFold3D", "cudecompExtPlanHaloFields", "cudecompExtRunFieldMoves",
-               "cudecompExtDescribeFieldMoves", "cudecompExtDataLaunchCount"]
+               "cudecompExtDescribeFieldMoves", "cudecompExtDataLaunchCount", "cudecompExtPlanTransposeFields",
+               "cudecompExtRunFieldMoveList", "cudecompExtDescribeFieldMoveList"]
 # include/cudecomp_amd.h: extensions of the API a solver may use
 AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
 # include/cudecomp_amd_fill.h: halo fill
@@ -175,6 +181,10 @@ AMD_FOLD_SYMBOLS = ["cudecompAmdFoldHalosX", "cudecompAmdFoldHalosY", "cudecompA
 # include/cudecomp_halo_fields.h: multi-field halo updates (several pencils in one exchange)
 AMD_FIELDS_SYMBOLS = ["cudecompAmdUpdateFieldHalosX", "cudecompAmdUpdateFieldHalosY", "cudecompAmdUpdateFieldHalosZ"]
 MAX_HALO_FIELDS = 32  # CUDECOMP_AMD_MAX_HALO_FIELDS
+# include/cudecomp_transpose_fields.h: multi-field transposes (several pencils in one exchange)
+TRANSPOSE_FIELDS_SYMBOLS = ["cudecompAmdTransposeFieldsXToY", "cudecompAmdTransposeFieldsYToZ", "cudecompAmdTransposeFieldsZToY",
+                            "cudecompAmdTransposeFieldsYToX"]
+MAX_TRANSPOSE_FIELDS = 32  # CUDECOMP_AMD_MAX_TRANSPOSE_FIELDS
 # the four extension headers and the functions each of them declares itself (checked by tests/test_abi.py, like API_SYMBOLS)
 AMD_HEADER_SYMBOLS = {"cudecomp_amd.h": AMD_SYMBOLS, "cudecomp_amd_fill.h": AMD_FILL_SYMBOLS,
                       "cudecomp_amd_accumulate_clear.h": AMD_ACCUMULATE_CLEAR_SYMBOLS, "cudecomp_amd_reflect.h": AMD_REFLECT_SYMBOLS}
@@ -251,6 +261,15 @@ def lib():
         L.cudecompExtDescribeFieldMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, C.c_uint64, i64, i32, i32,
                                                     C.POINTER(i64)]
         L.cudecompExtDataLaunchCount.argtypes = [C.POINTER(i64)]
+        for name in TRANSPOSE_FIELDS_SYMBOLS:  # (the transpose's arguments with the two lists and their length in the place of `input`, `output`)
+            getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), i32, vp, i32, pi32, pi32, pi32, pi32, vp]
+        L.cudecompExtPlanTransposeFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, pi32, pi32, pi32, C.c_bool, i32, i32, i32,
+                                                     i32, C.POINTER(ExtTransposePlan), C.POINTER(i64), C.POINTER(i64)]
+        L.cudecompExtRunFieldMoveList.argtypes = [C.POINTER(ExtMove), C.POINTER(i64), i32, C.POINTER(vp), C.POINTER(vp), i32, vp, i32,
+                                                  i32, vp, pi32]
+        L.cudecompExtDescribeFieldMoveList.argtypes = [C.POINTER(ExtMove), C.POINTER(i64), i32, C.POINTER(C.c_uint64),
+                                                       C.POINTER(C.c_uint64), i32, C.c_uint64, i32, i32,
+                                                       C.POINTER(ExtFieldMoveLaunch), i32, pi32]
         L.cudecompExtGetTransposePlan.argtypes = [vp, vp, i32, pi32, pi32, pi32, pi32, C.c_bool, i32,
                                                   C.POINTER(ExtTransposePlan)]
         L.cudecompExtGetHaloPlan.argtypes = [vp, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32,
@@ -492,6 +511,20 @@ def cudecompUpdateFieldHalos(axis, handle, gd, ptrs, work, dtype, halo_extents, 
     arr = None if ptrs is None else (C.c_void_p * max(1, len(ptrs)))(*[p or None for p in ptrs])
     _check(getattr(lib(), name)(handle, gd, arr, 0 if ptrs is None else len(ptrs), work, dtype, _i3(halo_extents), _b3(halo_periods),
                                 dim, _i3(padding), stream), name)
+
+
+def cudecompTransposeFields(op, handle, gd, inputs, outputs, work, dtype, in_halo=None, out_halo=None, in_pad=None, out_pad=None,
+                            stream=None):
+    """cudecompAmdTransposeFields{XToY,YToZ,ZToY,YToX} (cudecomp_transpose_fields.h): op in OPS; the transpose of every pencil in
+    `inputs` into the pencil of `outputs` at the same position (device pointers) with one pack launch, one exchange and one unpack
+    launch; `work` holds len(inputs) single workspaces."""
+    name = "cudecompAmdTransposeFields" + op
+
+    def table(ptrs):
+        return None if ptrs is None else (C.c_void_p * max(1, len(ptrs)))(*[p or None for p in ptrs])
+    n = len(inputs) if inputs is not None else (len(outputs) if outputs is not None else 0)
+    _check(getattr(lib(), name)(handle, gd, table(inputs), table(outputs), n, work, dtype, _i3(in_halo), _i3(out_halo), _i3(in_pad),
+                                _i3(out_pad), stream), name)
 
 
 def cudecompExtGetTransposePlan(handle, gd, op, in_halo=None, out_halo=None, in_pad=None, out_pad=None, inplace=False,
@@ -832,6 +865,56 @@ def cudecompExtDescribeFieldMoves(moves, field_addresses, work_address, work_fie
     _check(lib().cudecompExtDescribeFieldMoves(_move_list(moves), len(moves), f, len(field_addresses), int(work_address or 0),
                                                int(work_field_stride), es, int(force), out), "cudecompExtDescribeFieldMoves")
     return dict(zip(("kind", "vec", "access", "blocks_per_field", "blocks"), [int(x) for x in out]))
+
+
+def cudecompExtPlanTransposeFields(grid, rank, op, in_halo=None, out_halo=None, in_pad=None, out_pad=None, inplace=False,
+                                   pipelined=False, symmetric_recv=False, npergroup=0, n_fields=1, no_elide=False):
+    """Stateless planner of cudecompAmdTransposeFields*: (plan of field 0 with the scaled exchange, pack steps, unpack steps); an end
+    of pack[i] / unpack[i] in buffer 2 lies at its offset + f * step[i] for field f (cudecomp_ext.h).  no_elide with n_fields == 1: the
+    single plan with both elisions off, from which the plans of two fields or more are derived."""
+    p = ExtTransposePlan()
+    ps, us = (C.c_int64 * EXT_MAX_MEMBERS)(), (C.c_int64 * EXT_MAX_MEMBERS)()
+    _check(lib().cudecompExtPlanTransposeFields(C.byref(grid), rank, OPS.index(op), _i3(in_halo), _i3(out_halo), _i3(in_pad),
+                                                _i3(out_pad), bool(inplace), int(bool(pipelined)) | (2 if no_elide else 0),
+                                                int(symmetric_recv), npergroup, int(n_fields), C.byref(p), ps, us),
+           "cudecompExtPlanTransposeFields")
+    return p, [int(x) for x in ps[:p.n_pack]], [int(x) for x in us[:p.n_unpack]]
+
+
+def _i64_list(values, n):
+    return None if values is None else (C.c_int64 * max(1, n))(*[int(v) for v in values])
+
+
+def cudecompExtRunFieldMoveList(moves, work_steps, inputs, outputs, work, es, force=0, stream=None):
+    """A list of moves for every (inputs[f], outputs[f]) pair in as few launches as their kernel choices allow (cudecomp_ext.h): an
+    end in buffer 0 lies in inputs[f], in buffer 1 in outputs[f], in buffer 2 in `work` at its offset + f * work_steps[i].  Returns
+    the number of launches."""
+    fi = (C.c_void_p * max(1, len(inputs)))(*[p or None for p in inputs])
+    fo = None if outputs is None else (C.c_void_p * max(1, len(outputs)))(*[p or None for p in outputs])
+    total = C.c_int32(-1)
+    _check(lib().cudecompExtRunFieldMoveList(_move_list(moves), _i64_list(work_steps, len(moves)), len(moves), fi, fo, len(inputs),
+                                             work or None, es, int(force), stream, C.byref(total)), "cudecompExtRunFieldMoveList")
+    return total.value
+
+
+def cudecompExtDescribeFieldMoveList(moves, work_steps, input_addresses, output_addresses, work_address, es, force=0):
+    """Which launches cudecompExtRunFieldMoveList would make (no launch, no GPU): a list of dicts (kind 24 transposing, 25 rows, 26
+    element-wise; es, vec, ti, tj, access, guard, blocks, blocks_per_field, index)."""
+    fi = (C.c_uint64 * max(1, len(input_addresses)))(*[int(p) for p in input_addresses])
+    fo = None if output_addresses is None else (C.c_uint64 * max(1, len(output_addresses)))(*[int(p) for p in output_addresses])
+    cap = max(1, len(moves))
+    out = (ExtFieldMoveLaunch * cap)()
+    n = C.c_int32(-1)
+    _check(lib().cudecompExtDescribeFieldMoveList(_move_list(moves), _i64_list(work_steps, len(moves)), len(moves), fi, fo,
+                                                  len(input_addresses), int(work_address or 0), es, int(force), out, cap, C.byref(n)),
+           "cudecompExtDescribeFieldMoveList")
+    res = []
+    for i in range(n.value):
+        l = out[i]
+        d = {k: int(getattr(l, k)) for k in ("kind", "es", "vec", "ti", "tj", "access", "guard", "blocks", "blocks_per_field")}
+        d["index"] = [int(l.index[j]) for j in range(l.n_moves)]
+        res.append(d)
+    return res
 
 
 def cudecompExtDataLaunchCount():

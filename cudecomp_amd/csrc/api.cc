@@ -1010,4 +1010,52 @@ CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosX, 0)
 CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosY, 1)
 CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosZ, 2)
 
+// cudecomp_transpose_fields.h: the transpose of several pencils with one exchange.  The checks of transposeEntry, in its order,
+// with the lists checked where the transpose checks `input` and `output`; all of it on the host, before anything is launched.
+static cudecompResult_t transposeFieldsEntry(TransposeOp op, cudecompHandle_t handle, cudecompGridDesc_t grid_desc,
+                                             void* const inputs[], void* const outputs[], int32_t n_fields, void* work,
+                                             cudecompDataType_t dtype, const int32_t in_halo[], const int32_t out_halo[],
+                                             const int32_t in_pad[], const int32_t out_pad[], hipStream_t stream) {
+  try {
+    checkHandle(handle);
+    checkGridDesc(handle, grid_desc);
+    checkDataType(dtype);
+    if (!inputs) CD_INVALID_USAGE("inputs argument cannot be null");
+    if (!outputs) CD_INVALID_USAGE("outputs argument cannot be null");
+    if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_TRANSPOSE_FIELDS) CD_INVALID_USAGE("n_fields argument out of range");
+    for (int32_t i = 0; i < n_fields; ++i)
+      if (!inputs[i]) CD_INVALID_USAGE("inputs argument cannot hold a null entry");
+    for (int32_t i = 0; i < n_fields; ++i)
+      if (!outputs[i]) CD_INVALID_USAGE("outputs argument cannot hold a null entry");
+    for (int32_t i = 0; i < n_fields; ++i)
+      for (int32_t j = 0; j < i; ++j) {
+        if (inputs[j] == inputs[i]) CD_INVALID_USAGE("inputs argument cannot hold the same field twice");
+        if (outputs[j] == outputs[i]) CD_INVALID_USAGE("outputs argument cannot hold the same field twice");
+      }
+    for (int32_t i = 0; i < n_fields; ++i)
+      for (int32_t j = 0; j < n_fields; ++j)
+        if (i != j && inputs[i] == outputs[j]) CD_INVALID_USAGE("an input field cannot be the output of another field");
+    for (int32_t i = 1; i < n_fields; ++i)
+      if ((inputs[i] == outputs[i]) != (inputs[0] == outputs[0]))
+        CD_INVALID_USAGE("fields must be all in place or all out of place");
+    if (!work) CD_INVALID_USAGE("work argument cannot be null");
+    runTransposeFields(handle, grid_desc, op, inputs, outputs, n_fields, work, dtype, in_halo, out_halo, in_pad, out_pad, stream);
+  }
+  CD_API_CATCH()
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+#define CD_DEFINE_TRANSPOSE_FIELDS(NAME, OP)                                                                                   \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const inputs[], void* const outputs[],    \
+                        int32_t n_fields, void* work, cudecompDataType_t dtype, const int32_t input_halo_extents[],            \
+                        const int32_t output_halo_extents[], const int32_t input_padding[], const int32_t output_padding[],    \
+                        hipStream_t stream) {                                                                                  \
+    return transposeFieldsEntry(OP, handle, grid_desc, inputs, outputs, n_fields, work, dtype, input_halo_extents,             \
+                                output_halo_extents, input_padding, output_padding, stream);                                   \
+  }
+CD_DEFINE_TRANSPOSE_FIELDS(cudecompAmdTransposeFieldsXToY, OP_X_TO_Y)
+CD_DEFINE_TRANSPOSE_FIELDS(cudecompAmdTransposeFieldsYToZ, OP_Y_TO_Z)
+CD_DEFINE_TRANSPOSE_FIELDS(cudecompAmdTransposeFieldsZToY, OP_Z_TO_Y)
+CD_DEFINE_TRANSPOSE_FIELDS(cudecompAmdTransposeFieldsYToX, OP_Y_TO_X)
+
 }  // extern "C"

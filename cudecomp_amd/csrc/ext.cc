@@ -7,6 +7,7 @@
 
 #include "cudecomp_ext.h"
 #include "cudecomp_halo_fields.h"
+#include "cudecomp_transpose_fields.h"
 #include "errors.h"
 #include "internal.h"
 #include "rotate_walk.h"
@@ -1017,6 +1018,123 @@ cudecompResult_t cudecompExtDescribeFieldMoves(const cudecompExtMove_t* moves, i
     out[2] = l.k.access;
     out[3] = l.blocks_per_field;
     out[4] = l.blocks;
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+static std::vector<Move3D> importFieldMoveList(const cudecompExtMove_t* moves, int32_t n, int32_t n_fields, int32_t es) {
+  if (n < 0 || n > CUDECOMP_EXT_MAX_MEMBERS || (n > 0 && !moves)) CD_INVALID_USAGE("a field-move list takes at most 64 moves");
+  if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_TRANSPOSE_FIELDS) CD_INVALID_USAGE("n_fields out of range");
+  if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
+  std::vector<Move3D> list(n);
+  for (int32_t i = 0; i < n; ++i) {
+    const cudecompExtMove_t& e = moves[i];
+    if (e.src_buf < 0 || e.src_buf > 2 || e.dst_buf < 0 || e.dst_buf > 2) CD_INVALID_USAGE("buffer number out of range");
+    Move3D& m = list[i];
+    m.src_buf = (BufId)e.src_buf;
+    m.dst_buf = (BufId)e.dst_buf;
+    m.src_off = e.src_off;
+    m.dst_off = e.dst_off;
+    for (int d = 0; d < 3; ++d) {
+      m.extent[d] = e.extent[d];
+      m.ss[d] = e.ss[d];
+      m.ds[d] = e.ds[d];
+    }
+    m.dst_row_pitch = e.row_pitch;
+  }
+  return list;
+}
+
+cudecompResult_t cudecompExtPlanTransposeFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t op, const int32_t in_halo[],
+                                                const int32_t out_halo[], const int32_t in_pad[], const int32_t out_pad[],
+                                                bool inplace, int32_t pipelined, int32_t symmetric_recv, int32_t npergroup,
+                                                int32_t n_fields, cudecompExtTransposePlan_t* out, int64_t* pack_step,
+                                                int64_t* unpack_step) {
+  try {
+    const GridShape g = shapeFromSpec(grid);
+    if (!out || !pack_step || !unpack_step) CD_INVALID_USAGE("plan argument cannot be null");
+    if (op < 0 || op > 3) CD_INVALID_USAGE("op out of range");
+    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
+    TransportTraits traits;
+    traits.pipelined = (pipelined & 1) != 0;
+    traits.no_elide = (pipelined & 2) != 0;  // (n_fields == 1: the single plan with both elisions off, what n_fields >= 2 derive from)
+    traits.symmetric_recv = symmetric_recv != 0;
+    const CommAxis ca = (op == OP_X_TO_Y || op == OP_Y_TO_X) ? COMM_COL : COMM_ROW;
+    const int P = g.pdims[ca == COMM_COL ? 0 : 1];
+    const TransposeFieldsPlan fp = buildTransposeFieldsPlan(g, rank, (TransposeOp)op, in_halo, out_halo, in_pad, out_pad, inplace,
+                                                            traits, npergroup > 0 ? npergroup : P, n_fields);
+    std::vector<int> members(P);
+    const auto pidx = gridIndexOfRank(g, rank);
+    for (int i = 0; i < P; ++i) members[i] = globalRankOf(g, pidx, ca, i);
+    exportTransposePlan(fp.base, members, out);
+    for (int i = 0; i < CUDECOMP_EXT_MAX_MEMBERS; ++i) {
+      pack_step[i] = i < (int)fp.pack_step.size() ? fp.pack_step[i] : 0;
+      unpack_step[i] = i < (int)fp.unpack_step.size() ? fp.unpack_step[i] : 0;
+    }
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtRunFieldMoveList(const cudecompExtMove_t* moves, const int64_t* work_steps, int32_t n,
+                                             void* const* inputs, void* const* outputs, int32_t n_fields, void* work, int32_t es,
+                                             int32_t force, hipStream_t stream, int32_t* n_launches) {
+  try {
+    if (!inputs) CD_INVALID_USAGE("null argument");
+    const std::vector<Move3D> list = importFieldMoveList(moves, n, n_fields, es);
+    KernelStats st;
+    launchFieldMoveList(list.data(), work_steps, n, inputs, outputs, n_fields, work, es, stream, force, &st);
+    if (n_launches) {
+      *n_launches = 0;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c) *n_launches += st.launches[c];
+    }
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtDescribeFieldMoveList(const cudecompExtMove_t* moves, const int64_t* work_steps, int32_t n,
+                                                  const uint64_t* input_addresses, const uint64_t* output_addresses,
+                                                  int32_t n_fields, uint64_t work_address, int32_t es, int32_t force,
+                                                  cudecompExtFieldMoveLaunch_t* launches, int32_t max_launches,
+                                                  int32_t* n_launches) {
+  try {
+    if (!input_addresses || !n_launches || (max_launches > 0 && !launches)) CD_INVALID_USAGE("null argument");
+    const std::vector<Move3D> list = importFieldMoveList(moves, n, n_fields, es);
+    std::vector<void*> in(n_fields), out(n_fields);
+    for (int32_t f = 0; f < n_fields; ++f) {
+      in[f] = reinterpret_cast<void*>(input_addresses[f]);
+      if (output_addresses) out[f] = reinterpret_cast<void*>(output_addresses[f]);
+    }
+    const std::vector<FieldMoveLaunch> ls = planFieldMoveLaunches(list.data(), work_steps, n, in.data(), output_addresses ? out.data() : nullptr,
+                                                                  n_fields, reinterpret_cast<void*>(work_address), es, force);
+    *n_launches = (int32_t)ls.size();
+    for (int32_t i = 0; i < (int32_t)ls.size() && i < max_launches; ++i) {
+      const FieldMoveLaunch& l = ls[i];
+      cudecompExtFieldMoveLaunch_t& o = launches[i];
+      std::memset(&o, 0, sizeof(o));
+      o.kind = (int32_t)l.k.kind;
+      o.es = l.k.es;
+      o.vec = l.k.vec;
+      o.ti = l.k.ti;
+      o.tj = l.k.tj;
+      o.access = l.k.access;
+      o.guard = l.k.guard ? 1 : 0;
+      o.n_moves = l.b.n;
+      o.blocks = l.blocks;
+      o.blocks_per_field = l.blocks_per_field;
+      for (int j = 0; j < l.b.n; ++j) o.index[j] = l.index[j];
+    }
   } catch (const Error& e) {
     return fail(e);
   } catch (...) {

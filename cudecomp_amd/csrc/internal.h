@@ -17,6 +17,7 @@
 #include "cudecomp_amd_reflect.h"
 #include "cudecomp_halo_fold.h"
 #include "cudecomp_halo_fields.h"
+#include "cudecomp_transpose_fields.h"
 #include "decomp.h"
 #include "errors.h"
 #include "kernels.h"
@@ -147,6 +148,8 @@ struct cudecompGridDesc {
   std::map<std::tuple<HaloKey, int, bool, bool>, cudecomp::HaloPlan> halo_fold_plans;
   // cudecompAmdUpdateFieldHalos* with two fields or more: the same key plus n_fields
   std::map<std::tuple<HaloKey, int>, cudecomp::HaloFieldsPlan> halo_fields_plans;
+  // cudecompAmdTransposeFields* with two fields or more: TransposeKey (never pipelined) plus n_fields
+  std::map<std::tuple<TransposeKey, int>, cudecomp::TransposeFieldsPlan> transpose_fields_plans;
 
   // CUDECOMP_ENABLE_CUDA_GRAPHS=1: the per-peer pack loop of the pipelined backends (one kernel + one event
   // record per destination) is captured once per (plan, buffers, element size) and replayed as one graph launch
@@ -284,6 +287,11 @@ void runHaloFold(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void*
 void runHaloFields(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* const* inputs, int n_fields, void* work,
                    cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
                    hipStream_t stream);
+
+// cudecompAmdTransposeFields*: n_fields pencils, one exchange (n_fields == 1 IS runTranspose)
+void runTransposeFields(cudecompHandle_t handle, cudecompGridDesc_t gd, TransposeOp op, void* const* inputs, void* const* outputs,
+                        int n_fields, void* work, cudecompDataType_t dtype, const int32_t* in_halo, const int32_t* out_halo,
+                        const int32_t* in_pad, const int32_t* out_pad, hipStream_t stream);
 
 // perf.cc
 struct TransposeTimings {

@@ -50,9 +50,10 @@ constexpr long long kDenseMaxGapBytes = 512;  // widest gap between rows the den
 
 MoveClass classOf(KernelKind kind) {
   if (kind == K_GENERIC || kind == K_GENERIC_ADD || kind == K_GENERIC_FILL || kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE ||
-      kind == K_GENERIC_REFLECT || kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE || kind == K_GENERIC_FIELDS)
+      kind == K_GENERIC_REFLECT || kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE || kind == K_GENERIC_FIELDS ||
+      kind == K_GENERIC_FIELDMOVES)
     return MOVE_GENERIC;
-  return kind >= K_TRANSPOSE && kind <= K_TRANSPOSE_ROWLINES ? MOVE_TRANSPOSE : MOVE_ROWS_VEC;
+  return (kind >= K_TRANSPOSE && kind <= K_TRANSPOSE_ROWLINES) || kind == K_TRANSPOSE_FIELDS ? MOVE_TRANSPOSE : MOVE_ROWS_VEC;
 }
 
 int arithBytes(int arith) { return arith == ARITH_F64 ? 8 : (arith == ARITH_F32 ? 4 : 2); }
@@ -158,15 +159,22 @@ bool offerDenseRows(Classified& c, const Move3D& in, const Move3D& m, const Kern
   return true;
 }
 
+// Lane width (elements) of a transposition whose geometry is in c.dm: 16 bytes per lane whenever both tile edges hold whole
+// vectors (dword alignment suffices, see GlobalBytes).  2-byte elements: only when every lane address is dword-aligned too --
+// bases and the byte strides of both sides
+int transposeLaneWidth(const Classified& c) {
+  const int es = c.k.es;
+  int vw = 16 / es;
+  if (c.dm.e[0] % vw != 0 || c.dm.e[1] % vw != 0) vw = 1;
+  if (halfMisaligned(c.dm, es, c.dm.ss[1] | c.dm.ss[2] | c.dm.ds[0] | c.dm.ds[2])) vw = 1;
+  return vw;
+}
+
 // Kernel (plain or window), lane width, access mode, tile and tile counts of a transposition whose geometry is in c.dm; also
 // j_first (tile walk along the destination rows first) and aligned (plain kernel, both sides' rows on the 128-byte grid).
 void chooseTranspose(Classified& c, const KernelTuning& tuning, bool& j_first, bool& aligned) {
   const int es = c.k.es;
-  // 16 bytes per lane whenever both tile edges hold whole vectors (dword alignment suffices, see GlobalBytes).  2-byte
-  // elements: only when every lane address is dword-aligned too -- bases and the byte strides of both sides
-  int vw = 16 / es;
-  if (c.dm.e[0] % vw != 0 || c.dm.e[1] % vw != 0) vw = 1;
-  if (halfMisaligned(c.dm, es, c.dm.ss[1] | c.dm.ss[2] | c.dm.ds[0] | c.dm.ds[2])) vw = 1;
+  const int vw = transposeLaneWidth(c);
   c.k.vec = vw;
   // Tile walk order inside an XCD's run: j first makes consecutive tiles extend the same DESTINATION rows
   // (contiguous write stream per row), i first the same source rows.  Measured on 8 GiB permutations
@@ -567,6 +575,11 @@ void spellKernelName(const KernelChoice& k) {
       break;
     case K_ROWS_FIELDS: snprintf(out, n, "rows_fields_kernel<%d,%d>", k.vec, s); break;
     case K_GENERIC_FIELDS: snprintf(out, n, "generic_fields_kernel<%d>", k.es); break;
+    case K_TRANSPOSE_FIELDS:
+      snprintf(out, n, "transpose_fields_kernel<%d,%d,%d,%d,%d,%s>", k.es, k.vec, k.ti, k.tj, s, k.guard ? "true" : "false");
+      break;
+    case K_ROWS_FIELDMOVES: snprintf(out, n, "rows_fieldmoves_kernel<%d,%d>", k.vec, s); break;
+    case K_GENERIC_FIELDMOVES: snprintf(out, n, "generic_fieldmoves_kernel<%d>", k.es); break;
   }
 }
 
@@ -620,6 +633,9 @@ void launchBatch(const KernelChoice& k, const Batch& b, const void* fill_value, 
     case K_GENERIC_FOLD_TAKE: launchFoldBatch(k, b, blocks, stream); break;
     case K_ROWS_FIELDS:
     case K_GENERIC_FIELDS: CD_INTERNAL_ERROR("field-moves are launched by launchFieldMoves");
+    case K_TRANSPOSE_FIELDS:
+    case K_ROWS_FIELDMOVES:
+    case K_GENERIC_FIELDMOVES: CD_INTERNAL_ERROR("lists of field-moves are launched by launchFieldMoveList");
   }
 }
 
@@ -829,6 +845,163 @@ void launchFieldMoves(const Move3D* moves, int n, void* const* fields, int n_fie
   if (stats) {
     stats->launches[l.cls] += 1;
     stats->elements[l.cls] += l.elements;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// lists of field-moves (kernels.h; kernels_field_transpose.hip)
+// ---------------------------------------------------------------------------------------------
+std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i64* work_steps, int n, void* const* inputs,
+                                                   void* const* outputs, int n_fields, void* work, int es, int force) {
+  if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
+  if (n < 0 || (n > 0 && !moves)) CD_INTERNAL_ERROR("field-move list without moves");
+  if (n_fields < 1 || n_fields > kMaxFields || !inputs) CD_INTERNAL_ERROR("field count out of range");
+  for (int f = 0; f < n_fields; ++f)
+    if (!inputs[f] || (outputs && !outputs[f])) CD_INTERNAL_ERROR("null field buffer");
+  const bool force_generic = (force & 1) != 0;
+  char* const w = static_cast<char*>(work);
+
+  // classify each move's shared geometry once; the addresses every field's first element can have are or-ed together (the
+  // 2-byte rule: all fields' pencils and all workspace pieces)
+  std::vector<Classified> cs;
+  std::vector<FieldMove> fms;
+  std::vector<int> index;
+  for (int i = 0; i < n; ++i) {
+    const Move3D& in = moves[i];
+    if (in.add || in.fill || in.take || in.reflect || in.negate || in.dst_row_pitch != 0)
+      CD_INTERNAL_ERROR("field-moves are plain copies of exactly their cells");
+    if ((in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK) && !work) CD_INTERNAL_ERROR("field-move through a workspace that was not given");
+    if ((in.src_buf == BUF_OUT || in.dst_buf == BUF_OUT) && !outputs) CD_INTERNAL_ERROR("field-move onto an output list that was not given");
+    for (int d = 0; d < 3; ++d)
+      if (in.ss[d] < 0 || in.ds[d] < 0 || in.extent[d] < 0) CD_INTERNAL_ERROR("negative stride or extent in a field-move");
+    if (in.elements() == 0) continue;
+    const i64 step = work_steps ? work_steps[i] : 0;
+    if (step < 0) CD_INTERNAL_ERROR("negative workspace step in a field-move");
+    Move3D m = in;
+    normalizeMove(m);
+    FieldMove fm{};
+    fm.src_end = in.src_buf == BUF_WORK ? kEndWork : (in.src_buf == BUF_OUT ? kEndOutput : kEndInput);
+    fm.dst_end = in.dst_buf == BUF_WORK ? kEndWork : (in.dst_buf == BUF_OUT ? kEndOutput : kEndInput);
+    fm.src_off = in.src_off * es;
+    fm.dst_off = in.dst_off * es;
+    fm.src_step = fm.src_end == kEndWork ? step * es : 0;
+    fm.dst_step = fm.dst_end == kEndWork ? step * es : 0;
+    uintptr_t address_bits = 0;
+    for (int f = 0; f < n_fields; ++f) {
+      const char* sb = fm.src_end == kEndWork ? w + f * fm.src_step : static_cast<const char*>(fm.src_end == kEndOutput ? outputs[f] : inputs[f]);
+      const char* db = fm.dst_end == kEndWork ? w + f * fm.dst_step : static_cast<const char*>(fm.dst_end == kEndOutput ? outputs[f] : inputs[f]);
+      address_bits |= reinterpret_cast<uintptr_t>(sb) + (uintptr_t)fm.src_off;
+      address_bits |= reinterpret_cast<uintptr_t>(db) + (uintptr_t)fm.dst_off;
+    }
+    Classified c{};
+    c.k.es = es;
+    c.k.arith = ARITH_NONE;
+    c.elements = m.elements();
+    c.dm.src = reinterpret_cast<const char*>(address_bits);  // (only its alignment is read)
+    c.dm.dst = reinterpret_cast<char*>(address_bits);
+    // Access: cached while the move is below kStreamBytes PER FIELD, non-temporal loads and stores from there -- the project's
+    // rule for copies, unmeasured for these kernels; the element-wise kernel always caches.
+    const bool streaming = (c.elements * es >= kStreamBytes || (force & 2)) && !(force & 4);
+    int t = -1;
+    if (!force_generic && m.ss[0] == 1) {
+      if (m.ds[1] == 1) t = 1;
+      if (m.ds[2] == 1) t = 2;
+    }
+    if (!force_generic && m.ss[0] <= 1 && m.ds[0] <= 1) {
+      c.k.kind = K_ROWS_FIELDMOVES;
+      c.k.access = streaming ? 1 : 0;
+      rowVectors(c, m);
+      if (c.k.vec < es) CD_INTERNAL_ERROR("field-move narrower than one element");
+      rowTiles(c);
+    } else if (t > 0 && m.extent[0] >= 4 && m.extent[t] >= 4) {
+      const int k = 3 - t;
+      c.k.kind = K_TRANSPOSE_FIELDS;
+      c.k.access = streaming ? 2 : 0;
+      c.dm.e[0] = m.extent[0];
+      c.dm.e[1] = m.extent[t];
+      c.dm.e[2] = m.extent[k];
+      c.dm.ss[0] = 1;
+      c.dm.ss[1] = m.ss[t];
+      c.dm.ss[2] = m.ss[k];
+      c.dm.ds[0] = m.ds[0];
+      c.dm.ds[1] = 1;
+      c.dm.ds[2] = m.ds[k];
+      // one tile per element size and lane width: 2-byte 128 x 128 with 16-byte lanes, 64 x 64 element-wise; 4-byte 64 x 128 /
+      // 64 x 64; 8-byte 64 x 64; 16-byte 32 x 32
+      const int vw = transposeLaneWidth(c);
+      c.k.vec = vw;
+      c.k.ti = es == 2 ? (vw == 8 ? 128 : 64) : (es == 16 ? 32 : 64);
+      c.k.tj = es == 4 && vw == 4 ? 128 : c.k.ti;
+      c.k.guard = c.dm.e[0] % c.k.ti != 0 || c.dm.e[1] % c.k.tj != 0;
+      c.t0 = (unsigned int)((c.dm.e[0] + c.k.ti - 1) / c.k.ti);
+      c.t1 = (unsigned int)((c.dm.e[1] + c.k.tj - 1) / c.k.tj);
+      c.blocks = (unsigned long long)c.t0 * c.t1 * (unsigned long long)c.dm.e[2];
+    } else {
+      c.k.kind = K_GENERIC_FIELDMOVES;
+      c.k.access = 0;
+      genericGeometry(c, m);
+    }
+    if (c.blocks == 0 || c.blocks * (unsigned long long)n_fields > 0x7fffffffULL)
+      CD_NOT_SUPPORTED("single block move too large for one launch");
+    for (int d = 0; d < 3; ++d) {
+      fm.e[d] = c.dm.e[d];
+      fm.ss[d] = c.dm.ss[d];
+      fm.ds[d] = c.dm.ds[d];
+    }
+    fm.p0 = c.p0;
+    fm.t0 = c.t0;
+    fm.t1 = c.t1;
+    fm.blocks = (unsigned int)c.blocks;
+    cs.push_back(c);
+    fms.push_back(fm);
+    index.push_back(i);
+  }
+  // moves of one phase are independent: regrouped by equal kernel choice in the order of first appearance, cut at kMaxBatch
+  std::vector<FieldMoveLaunch> launches;
+  std::vector<bool> done(cs.size(), false);
+  for (size_t i = 0; i < cs.size(); ++i) {
+    if (done[i]) continue;
+    FieldMoveLaunch l{};
+    FieldMoveBatch& b = l.b;
+    l.k = cs[i].k;
+    l.cls = classOf(cs[i].k.kind);
+    b.n_fields = n_fields;
+    b.work = w;
+    for (int f = 0; f < n_fields; ++f) {
+      b.in[f] = static_cast<char*>(inputs[f]);
+      b.out[f] = outputs ? static_cast<char*>(outputs[f]) : nullptr;
+    }
+    unsigned long long blocks = 0;
+    for (size_t j = i; j < cs.size() && b.n < kMaxBatch; ++j) {
+      if (done[j] || !(cs[j].k == cs[i].k)) continue;
+      const unsigned long long mine = cs[j].blocks * (unsigned long long)n_fields;
+      if (blocks + mine > 0x7fffffffULL) break;  // (never the first of a group: checked per move above)
+      b.first_block[b.n] = (unsigned int)blocks;
+      b.m[b.n] = fms[j];
+      blocks += mine;
+      l.elements += cs[j].elements * n_fields;
+      l.blocks_per_field += (unsigned int)cs[j].blocks;
+      l.index[b.n] = index[j];
+      ++b.n;
+      done[j] = true;
+    }
+    for (int k = b.n; k <= kMaxBatch; ++k) b.first_block[k] = (unsigned int)blocks;
+    l.blocks = (unsigned int)blocks;
+    launches.push_back(l);
+  }
+  return launches;
+}
+
+void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void* const* inputs, void* const* outputs, int n_fields,
+                         void* work, int es, hipStream_t stream, int force, KernelStats* stats) {
+  for (const FieldMoveLaunch& l : planFieldMoveLaunches(moves, work_steps, n, inputs, outputs, n_fields, work, es, force)) {
+    spellKernelName(l.k);
+    ++g_data_launches;
+    launchFieldMoveBatch(l.k, l.b, l.blocks, stream);
+    if (stats) {
+      stats->launches[l.cls] += 1;
+      stats->elements[l.cls] += l.elements;
+    }
   }
 }
 

@@ -102,7 +102,36 @@ FieldLaunch planFieldLaunch(const Move3D* moves, int n, void* const* fields, int
 void launchFieldMoves(const Move3D* moves, int n, void* const* fields, int n_fields, void* work, i64 work_field_stride, int es,
                       hipStream_t stream, int force = 0, KernelStats* stats = nullptr);
 
-// data-movement launches this process has made so far (launchMoves and launchFieldMoves; tests count launches per call with it)
+// ---- lists of field-moves: a list of copy moves, each for several (input, output) pairs of buffers (kernels_field_transpose.hip) --
+// The moves of one phase of a multi-field transpose (include/cudecomp_transpose_fields.h): moves[0 .. n - 1] share their geometry
+// among `n_fields` (1 .. kern::kMaxFields) fields.  An end of a move in BUF_IN lies in inputs[f] + offset, an end in BUF_OUT in
+// outputs[f] + offset, an end in BUF_WORK at work + (offset + f * work_steps[i]) elements (work_steps == nullptr: all zero).
+// Each move's shared geometry is classified once: rows (rowVectors' rule) when its fastest dim is contiguous on both sides, the
+// LDS-tiled transposition (chooseTranspose's lane-width rule, one tile per element size and lane width) when source and
+// destination rows run along different dims of at least 4 elements, element by element (genericGeometry's) otherwise.  For
+// 2-byte elements the lanes narrow as soon as ANY field's address, any workspace piece or any stride is 2 mod 4.  Moves with equal
+// KernelChoice share a launch, in the order of first appearance, cut at kMaxBatch moves (and before 2^31 - 1 workgroups).  The
+// kernels copy exactly the cells of the moves -- never a window, lines, shifted or dense form.  Access: cached while a move is
+// below kStreamBytes PER FIELD, non-temporal loads and stores from there (unmeasured for these kernels); the element-wise kernel
+// always caches.  force: as for launchFieldMoves.  A move with add, fill, take, reflect, negate or dst_row_pitch, a workspace end
+// without a workspace and an output end without `outputs` are internal errors before anything is launched; a move of more than
+// 2^31 - 1 workgroups is NOT_SUPPORTED.
+struct FieldMoveLaunch {
+  KernelChoice k;
+  kern::FieldMoveBatch b;
+  unsigned int blocks;            // of all its moves and fields
+  unsigned int blocks_per_field;  // of all its moves
+  MoveClass cls;
+  i64 elements;                   // of all its moves and fields
+  int index[kern::kMaxBatch];     // index[i]: the list entry b.m[i] is
+};
+// WHICH launches launchFieldMoveList makes, in order (pure host code, no device needed; buffers are only looked at as addresses)
+std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i64* work_steps, int n, void* const* inputs,
+                                                   void* const* outputs, int n_fields, void* work, int es, int force = 0);
+void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void* const* inputs, void* const* outputs, int n_fields,
+                         void* work, int es, hipStream_t stream, int force = 0, KernelStats* stats = nullptr);
+
+// data-movement launches this process has made so far (launchMoves, launchFieldMoves and launchFieldMoveList; tests count launches per call with it)
 long long dataLaunchCount();
 
 // name (template spelling) of the data-movement kernel launched last by this process, "" before the first launch

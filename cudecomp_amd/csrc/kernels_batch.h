@@ -3,7 +3,7 @@
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip;
 // kernels_fields.hip is reached through launchFieldMoves (kernels.h); kernels_rotate.hip and sync.hip are launched by the
-// executor.  Sixteen code objects in all.
+// executor; kernels_field_transpose.hip is reached through launchFieldMoveList (kernels.h).  Seventeen code objects in all.
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
 // code object beyond roughly 0.6-0.7 MB puts the whole process into a regime where every small synchronous operation costs
@@ -94,6 +94,37 @@ struct FieldBatch {
   char* field[kMaxFields];
 };
 
+// ---- lists of field-moves: up to kMaxBatch moves, each for up to kMaxFields (input, output) pairs of buffers, in ONE launch
+// (kernels_field_transpose.hip; multi-field transposes, include/cudecomp_transpose_fields.h) ------------------------------------
+// The geometry is held once per move, with byte OFFSETS in the place of DevMove's pointers.  Each end of a move names its base:
+// kEndInput "field f's entry of the input table", kEndOutput "field f's entry of the output table", kEndWork "the workspace at
+// f * a per-move byte step" (the fields' pieces of one peer's chunk lie one behind the other).  Workgroup b serves the move
+// whose [first_block[i], first_block[i + 1]) holds it; inside the move, field rel / blocks and that field's workgroup
+// rel % blocks -- one decode per workgroup.  The struct travels in the kernel arguments and stays under their 4 KB (1.7 KB).
+constexpr int kEndInput = 0, kEndOutput = 1, kEndWork = 2;
+
+struct FieldMove {
+  long long src_off, dst_off;    // bytes from the base of that end
+  long long src_step, dst_step;  // kEndWork ends: bytes between the pieces of consecutive fields (0 for table ends)
+  long long e[3];                // transpose_fields_kernel: {ei, ej, ek}, ss = {1, sj, sk}, ds = {di, 1, dk} in ELEMENTS;
+  long long ss[3];               // rows_fieldmoves_kernel: vectors per row / rows / planes, strides in BYTES;
+  long long ds[3];               // generic_fieldmoves_kernel: extents and strides in ELEMENTS
+  int src_end, dst_end;          // kEnd*
+  int p0;                        // rows: log2 of the lanes per row; element-wise: the dim the lanes run along
+  unsigned int t0, t1;           // transposes: tiles along i / j; rows: tile columns / tile rows per plane
+  unsigned int blocks;           // workgroups PER FIELD
+};
+
+struct FieldMoveBatch {
+  int n, n_fields;
+  unsigned int first_block[kMaxBatch + 1];  // first_block[i + 1] - first_block[i] = n_fields * m[i].blocks
+  char* work;
+  FieldMove m[kMaxBatch];
+  char* in[kMaxFields];
+  char* out[kMaxFields];
+};
+static_assert(sizeof(FieldMoveBatch) < 4096, "FieldMoveBatch must fit the kernel arguments");
+
 }  // namespace kern
 
 // ---- what runs: one record per kernel choice ----------------------------------------------------------------------------------
@@ -122,7 +153,10 @@ enum KernelKind {
   K_ROWS_FOLD_TAKE,      // rows_fold_kernel with TAKE (... ; src = 0) = 20
   K_GENERIC_FOLD_TAKE,   // generic_fold_kernel with TAKE = 21
   K_ROWS_FIELDS,         // rows_fields_kernel (dst = src, the same move for every field of a FieldBatch) = 22
-  K_GENERIC_FIELDS       // generic_fields_kernel = 23
+  K_GENERIC_FIELDS,      // generic_fields_kernel = 23
+  K_TRANSPOSE_FIELDS,    // transpose_fields_kernel (LDS-tiled, one move of a FieldMoveBatch for every field) = 24
+  K_ROWS_FIELDMOVES,     // rows_fieldmoves_kernel = 25
+  K_GENERIC_FIELDMOVES   // generic_fieldmoves_kernel = 26
 };
 struct KernelChoice {
   KernelKind kind;
@@ -133,12 +167,13 @@ struct KernelChoice {
                     // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads;
                     // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it);
                     // reflections: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores;
-                    // field-moves: 0, 1 non-temporal loads and stores
+                    // field-moves: 0, 1 non-temporal loads and stores; transpose_fields_kernel: 0, 2
   ArithType arith;  // additions, folds, reflections that flip the sign bits: the real type the elements consist of; ARITH_NONE otherwise
   bool neg;         // folds: the sign bits of the source are flipped before the addition (one sign mask per launch)
+  bool guard;       // transpose_fields_kernel: some tile of the move ends inside the move (the GUARD template argument); false otherwise
   bool operator==(const KernelChoice& o) const {
     return kind == o.kind && es == o.es && vec == o.vec && ti == o.ti && tj == o.tj && access == o.access && arith == o.arith &&
-           neg == o.neg;
+           neg == o.neg && guard == o.guard;
   }
 };
 constexpr int kLinesUnitBytes = 128;  // alignment unit of the lines and row-lines kernels
@@ -156,7 +191,8 @@ inline int streamArgOf(KernelKind kind, int access) {
   if (kind == K_ROWS_FOLD || kind == K_ROWS_FOLD_TAKE) return access;
   if (kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE) return 0;
   if (kind == K_ROWS_FIELDS) return access;
-  if (kind == K_GENERIC_FIELDS) return 0;
+  if (kind == K_GENERIC_FIELDS || kind == K_GENERIC_FIELDMOVES) return 0;
+  if (kind == K_ROWS_FIELDMOVES || kind == K_TRANSPOSE_FIELDS) return access;
   if (kind == K_TRANSPOSE_WINDOW || kind == K_TRANSPOSE_LINES || kind == K_TRANSPOSE_ROWLINES)
     return access == 2 ? 4 : access;  // always cached loads: the overlap rows of neighbouring windows hit in L2
   return access == 3 ? 3 : (access >= 1 ? 1 : 0);  // row copies: loads and stores stream together
@@ -201,6 +237,8 @@ void launchReflectBatch(const KernelChoice& k, const kern::Batch& b, unsigned in
 void launchFoldBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // kernels_fields.hip: field-moves (plain copies of exactly the cells of the moves; local buffers only)
 void launchFieldsBatch(const KernelChoice& k, const kern::FieldBatch& b, unsigned int blocks, hipStream_t stream);
+// kernels_field_transpose.hip: lists of field-moves (plain copies of exactly the cells of the moves; local buffers only)
+void launchFieldMoveBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, unsigned int blocks, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

@@ -146,7 +146,7 @@ TransposePlan buildTransposePlan(const GridShape& g, int rank, TransposeOp op, c
   // chunks already sit in the input: send from there (W = input order).  If ax_b is the slowest axis of a
   // halo-free output the chunks can land in place: receive there (W = output order).  Per-peer overlapped
   // in-place operation keeps both stagings so a chunk never lands on data still to be sent.
-  const bool elide_ok = !(traits.pipelined && inplace);
+  const bool elide_ok = !(traits.pipelined && inplace) && !traits.no_elide;
   const bool skip_pack = elide_ok && a.order[2] == ax.a && !in_hp;
   const bool skip_unpack = !skip_pack && elide_ok && !traits.symmetric_recv && b.order[2] == ax.b && !out_hp;
   Int3 W = a.order;
@@ -230,6 +230,79 @@ TransposePlan buildTransposePlan(const GridShape& g, int rank, TransposeOp op, c
     }
   }
   return p;
+}
+
+TransposeFieldsPlan buildTransposeFieldsPlan(const GridShape& g, int rank, TransposeOp op, const int32_t* in_halo,
+                                             const int32_t* out_halo, const int32_t* in_pad, const int32_t* out_pad, bool inplace,
+                                             const TransportTraits& traits, int npergroup, int n_fields) {
+  if (n_fields < 1) CD_INVALID_USAGE("n_fields argument out of range");
+  TransposeFieldsPlan fp;
+  fp.n_fields = n_fields;
+  TransportTraits t = traits;
+  if (n_fields >= 2) {
+    t.no_elide = true;
+    t.pipelined = false;
+  }
+  fp.base = buildTransposePlan(g, rank, op, in_halo, out_halo, in_pad, out_pad, inplace, t, npergroup);
+  TransposePlan& p = fp.base;
+  fp.pack_step.assign(p.pack.size(), 0);
+  fp.unpack_step.assign(p.unpack.size(), 0);
+  if (n_fields == 1) return fp;
+  const i64 n = n_fields;
+  p.direct.clear();
+  p.rotate = 0;
+  p.rotate_n = 0;
+  for (Move3D& m : p.pack) m.dst_row_pitch = 0;
+  for (Move3D& m : p.unpack) m.dst_row_pitch = 0;
+  if (p.noop) return fp;
+  if (!p.exchange) {
+    // out of place: pencil -> pencil.  In place: the interior of every field staged through its own piece of the workspace
+    for (size_t i = 0; i < p.pack.size(); ++i) {
+      const Move3D& m = p.pack[i];
+      if (m.src_buf != BUF_IN || (m.dst_buf == BUF_WORK && (m.dst_off != 0 || p.pack.size() != 1 || p.unpack.size() != 1)))
+        CD_INTERNAL_ERROR("a local transpose plan of unexpected shape");
+      if (m.dst_buf == BUF_WORK) fp.pack_step[i] = p.pencil_elements_a;
+    }
+    for (size_t i = 0; i < p.unpack.size(); ++i) {
+      const Move3D& m = p.unpack[i];
+      if (m.src_buf != BUF_WORK || m.src_off != 0 || m.dst_buf != BUF_OUT) CD_INTERNAL_ERROR("a local transpose plan of unexpected shape");
+      fp.unpack_step[i] = p.pencil_elements_a;
+    }
+    return fp;
+  }
+  if (p.send_buf != BUF_WORK || p.recv_buf != BUF_WORK || p.send_base != 0 || (int)p.pack.size() != p.nranks ||
+      (int)p.unpack.size() != p.nranks)
+    CD_INTERNAL_ERROR("a multi-field transpose plan came out with an elided pack or unpack");
+  const i64 unaligned = t.symmetric_recv ? p.stage_elements : p.pencil_elements_a;
+  if (alignElements(unaligned) != p.recv_base) CD_INTERNAL_ERROR("a transpose plan with an unexpected receive base");
+  const i64 single_recv_base = p.recv_base;
+  p.recv_base = alignElements(n * unaligned);
+  for (size_t i = 0; i < p.pack.size(); ++i) {
+    Move3D& m = p.pack[i];
+    const int d = m.peer;
+    if (m.src_buf != BUF_IN || m.dst_buf != BUF_WORK || d < 0 || d >= p.nranks || m.dst_off != p.send_off[d] ||
+        m.elements() != p.send_cnt[d])
+      CD_INTERNAL_ERROR("a transpose pack that does not fill its peer's chunk");
+    m.dst_off = n * p.send_off[d];
+    fp.pack_step[i] = p.send_cnt[d];
+  }
+  for (size_t i = 0; i < p.unpack.size(); ++i) {
+    Move3D& m = p.unpack[i];
+    const int s = m.peer;
+    if (m.src_buf != BUF_WORK || m.dst_buf != BUF_OUT || s < 0 || s >= p.nranks || m.src_off != single_recv_base + p.recv_off[s] ||
+        m.elements() != p.recv_cnt[s])
+      CD_INTERNAL_ERROR("a transpose unpack that does not drain its peer's chunk");
+    m.src_off = p.recv_base + n * p.recv_off[s];
+    fp.unpack_step[i] = p.recv_cnt[s];
+  }
+  for (int i = 0; i < p.nranks; ++i) {
+    p.send_cnt[i] *= n;
+    p.send_off[i] *= n;
+    p.recv_cnt[i] *= n;
+    p.recv_off[i] *= n;
+    p.remote_recv_off[i] *= n;
+  }
+  return fp;
 }
 
 int stageCount(const TransposePlan& p, int wanted, int es, i64 min_stage_bytes) {

@@ -75,6 +75,9 @@ struct TransportTraits {
   bool self_exchange = false;    // test aid (CUDECOMP_TEST_SELF_EXCHANGE=1): a one-member communicator still runs
                                  // pack -> exchange (with itself) -> unpack, so that a single GPU drives the real
                                  // transports end to end
+  bool no_elide = false;         // multi-field transposes (buildTransposeFieldsPlan): never send from the input or receive
+                                 // into the output -- the plan always has `pack` and `unpack` and send_buf == recv_buf ==
+                                 // BUF_WORK, because one message per peer must hold the chunks of ALL fields
 };
 
 struct TransposePlan {
@@ -125,6 +128,29 @@ enum TransposeOp { OP_X_TO_Y = 0, OP_Y_TO_Z = 1, OP_Z_TO_Y = 2, OP_Y_TO_X = 3 };
 TransposePlan buildTransposePlan(const GridShape& g, int rank, TransposeOp op, const int32_t* in_halo,
                                  const int32_t* out_halo, const int32_t* in_pad, const int32_t* out_pad, bool inplace,
                                  const TransportTraits& traits, int npergroup);
+
+// Multi-field TRANSPOSE (include/cudecomp_transpose_fields.h has the contract): `n_fields` pencils of one descriptor, op, halos
+// and padding transposed by one exchange.  Derived from buildTransposePlan with TransportTraits::no_elide (and never
+// pipelined): its refusals, peers, schedule and "which cells" hold by construction.  The moves in `base` are those of FIELD 0:
+// an end in BUF_IN / BUF_OUT is field f's input / output pencil at the same offset; an end in BUF_WORK lies at its offset +
+// f * step, step = pack_step[i] for base.pack[i] and unpack_step[i] for base.unpack[i] (elements).  With an exchange the chunk
+// for member d is n_fields pieces of the single plan's send_cnt[d], one behind the other, at n_fields * (the single plan's
+// send_off[d]); the receive side likewise behind recv_base = alignElements(n_fields * the single plan's unaligned base): the
+// same number on every rank, as the one-sided transport needs.  base.send_cnt, send_off, recv_cnt, recv_off and
+// remote_recv_off are the single plan's multiplied by n_fields: the exchange reads nothing else.  The total stays within
+// n_fields x transposeWorkspaceElements: alignElements(n * x) + n * y <= n * (alignElements(x) + y).  Without an exchange:
+// out of place one move pencil -> pencil (steps 0), in place with differing layouts pack and unpack through n_fields pieces
+// of one pencil each, in place with identical layouts a no-op.  No move carries dst_row_pitch (the field kernels write exactly
+// the cells of their moves); `direct` is empty and `rotate` 0.  n_fields == 1: the plan of buildTransposePlan with the caller's
+// traits, unchanged (steps 0).
+struct TransposeFieldsPlan {
+  TransposePlan base;
+  int n_fields = 1;
+  std::vector<i64> pack_step, unpack_step;
+};
+TransposeFieldsPlan buildTransposeFieldsPlan(const GridShape& g, int rank, TransposeOp op, const int32_t* in_halo,
+                                             const int32_t* out_halo, const int32_t* in_pad, const int32_t* out_pad, bool inplace,
+                                             const TransportTraits& traits, int npergroup, int n_fields);
 
 // ---- two-hop relay of a low-fan-out exchange over the whole node (transport.cc: peerRelayAlltoall) ----------------------
 // On a full xGMI mesh an exchange among P members drives P - 1 of a GPU's links.  On a pencil grid P is small -- the

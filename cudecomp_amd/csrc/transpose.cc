@@ -229,6 +229,75 @@ void runTranspose(cudecompHandle_t h, cudecompGridDesc_t gd, TransposeOp op, voi
   }
 }
 
+// Multi-field transpose (cudecompAmdTransposeFields*): always the plain sequence pack all fields -> ONE exchange whose message
+// for a peer holds all fields' chunks -> unpack all fields, through the workspace.  The backend enum only selects the transport
+// of the plain barrier path (RCCL, MPI, one-sided peer; the _PL and _SM enums take that same path): no elision, no per-peer or
+// staged pipeline, no fused or direct put, no relay, no rotation, no whole-operation graph.  Not sampled by the performance
+// report, not seen by the autotuner.  One field: runTranspose itself.
+void runTransposeFields(cudecompHandle_t h, cudecompGridDesc_t gd, TransposeOp op, void* const* inputs, void* const* outputs,
+                        int n_fields, void* work, cudecompDataType_t dtype, const int32_t* in_halo, const int32_t* out_halo,
+                        const int32_t* in_pad, const int32_t* out_pad, hipStream_t stream) {
+  if (n_fields == 1) return runTranspose(h, gd, op, inputs[0], outputs[0], work, dtype, in_halo, out_halo, in_pad, out_pad, stream);
+  const int es = elementSize(dtype);
+  const bool inplace = (inputs[0] == outputs[0]);
+  const auto backend = gd->config.transpose_comm_backend;
+  TransportTraits traits;
+  traits.pipelined = false;
+  traits.symmetric_recv = usesPeerTransport(h, backend);
+  traits.self_exchange = h->self_exchange;
+
+  std::array<int32_t, 12> hp;
+  {
+    const auto a = arr3(in_halo), b = arr3(out_halo), c = arr3(in_pad), d = arr3(out_pad);
+    for (int i = 0; i < 3; ++i) {
+      hp[i] = a[i];
+      hp[3 + i] = b[i];
+      hp[6 + i] = c[i];
+      hp[9 + i] = d[i];
+    }
+  }
+  const cudecompGridDesc::TransposeKey tkey{(int)op, hp, inplace, false, traits.symmetric_recv};
+  const std::tuple<cudecompGridDesc::TransposeKey, int> key{tkey, n_fields};
+  auto it = gd->transpose_fields_plans.find(key);
+  if (it == gd->transpose_fields_plans.end()) {
+    const auto& ci = gd->comm((op == OP_X_TO_Y || op == OP_Y_TO_X) ? COMM_COL : COMM_ROW);
+    TransposeFieldsPlan p = buildTransposeFieldsPlan(gd->shape, h->rank, op, &hp[0], &hp[3], &hp[6], &hp[9], inplace, traits,
+                                                     ci.npergroup, n_fields);
+    it = gd->transpose_fields_plans.emplace(key, std::move(p)).first;
+  }
+  const TransposeFieldsPlan& fp = it->second;
+  const TransposePlan& plan = fp.base;
+  if (plan.noop) return;
+
+  ensureDevice(h);
+  const int force = (h->tuning.force_class == MOVE_GENERIC ? 1 : 0) | (h->tuning.force_streaming ? 2 : 0) | (h->tuning.no_streaming ? 4 : 0);
+  auto launch = [&](const std::vector<Move3D>& moves, const std::vector<i64>& steps) {
+    launchFieldMoveList(moves.data(), steps.data(), (int)moves.size(), inputs, outputs, n_fields, work, es, stream, force);
+  };
+  if (!plan.exchange) {
+    gd->path_count[PATH_LOCAL]++;
+    launch(plan.pack, fp.pack_step);
+    launch(plan.unpack, fp.unpack_step);
+    return;
+  }
+  cudecompCommInfo& ci = gd->comm(plan.comm_axis);
+  ExchangeBuffers xb;
+  xb.send = static_cast<char*>(work) + plan.send_base * es;
+  xb.recv = static_cast<char*>(work) + plan.recv_base * es;
+  const ExecPath xpath = exchangePath(h, ci, backend);
+  const bool one_sided = xpath == PATH_PEER_BARRIER;
+  PeerCall call;
+  if (one_sided) {
+    // symmetric workspace (cudecompMalloc) for the NVSHMEM enums, a rendezvous per call otherwise, as for the single transpose
+    const bool rendezvous = backend == CUDECOMP_TRANSPOSE_COMM_NVSHMEM_SM || !transposeBackendIsPeer(backend);
+    call = peerBegin(h, ci, rendezvous, xb.recv, nullptr, false, stream);
+  }
+  gd->path_count[xpath]++;
+  launch(plan.pack, fp.pack_step);
+  alltoallExchange(h, gd, ci, plan, xb, es, backend, one_sided ? &call : nullptr, stream);
+  launch(plan.unpack, fp.unpack_step);
+}
+
 namespace {
 
 void executeTranspose(cudecompHandle_t h, cudecompGridDesc_t gd, const TransposePlan& plan,

@@ -688,6 +688,62 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompAmdUpdateFieldHalosZ_C
 
+    function cudecompAmdTransposeFieldsXToY_C(handle, grid_desc, inputs, outputs, n_fields, work, dtype, ihalo, ohalo, ipad, opad, &
+                                                stream) bind(C, name="cudecompAmdTransposeFieldsXToY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*), outputs(*)
+      integer(c_int32_t), value :: n_fields
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: ihalo(3), ohalo(3), ipad(3), opad(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdTransposeFieldsXToY_C
+
+    function cudecompAmdTransposeFieldsYToZ_C(handle, grid_desc, inputs, outputs, n_fields, work, dtype, ihalo, ohalo, ipad, opad, &
+                                                stream) bind(C, name="cudecompAmdTransposeFieldsYToZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*), outputs(*)
+      integer(c_int32_t), value :: n_fields
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: ihalo(3), ohalo(3), ipad(3), opad(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdTransposeFieldsYToZ_C
+
+    function cudecompAmdTransposeFieldsZToY_C(handle, grid_desc, inputs, outputs, n_fields, work, dtype, ihalo, ohalo, ipad, opad, &
+                                                stream) bind(C, name="cudecompAmdTransposeFieldsZToY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*), outputs(*)
+      integer(c_int32_t), value :: n_fields
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: ihalo(3), ohalo(3), ipad(3), opad(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdTransposeFieldsZToY_C
+
+    function cudecompAmdTransposeFieldsYToX_C(handle, grid_desc, inputs, outputs, n_fields, work, dtype, ihalo, ohalo, ipad, opad, &
+                                                stream) bind(C, name="cudecompAmdTransposeFieldsYToX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*), outputs(*)
+      integer(c_int32_t), value :: n_fields
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: ihalo(3), ohalo(3), ipad(3), opad(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdTransposeFieldsYToX_C
+
     function cudecomp_c_strlen(str) bind(C, name="strlen") result(n)
       import
       type(c_ptr), value :: str
@@ -1502,6 +1558,92 @@ contains
     res = cudecompAmdUpdateFieldHalosZ_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), c_loc(work), int(dtype, c_int), h, per, &
                                          int(dim - 1, c_int32_t), p, s)
   end function cudecompAmdUpdateFieldHalosZ
+
+
+  ! ---- multi-field transposes (include/cudecomp_transpose_fields.h): n_fields pencils, one exchange ------------------------
+  ! inputs / outputs: the device addresses of the n_fields input / output pencils (c_loc of each field), all in place or all out
+  ! of place; the other arguments as for cudecompTransposeXToY
+  function cudecompAmdTransposeFieldsXToY(handle, grid_desc, inputs, outputs, n_fields, work, dtype, input_halo_extents, &
+                                          output_halo_extents, input_padding, output_padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields), outputs(n_fields)
+    type(*), dimension(..), target :: work
+    integer :: dtype
+    integer, optional :: input_halo_extents(3), output_halo_extents(3), input_padding(3), output_padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: ih(3), oh(3), ip(3), op(3)
+    integer(c_intptr_t) :: s
+    call transpose_defaults(ih, oh, ip, op, s, input_halo_extents, output_halo_extents, input_padding, &
+                            output_padding, stream)
+    res = cudecompAmdTransposeFieldsXToY_C(handle, grid_desc, inputs, outputs, int(n_fields, c_int32_t), c_loc(work), &
+                                           int(dtype, c_int), ih, oh, ip, op, s)
+  end function cudecompAmdTransposeFieldsXToY
+
+  ! inputs / outputs: the device addresses of the n_fields input / output pencils (c_loc of each field), all in place or all out
+  ! of place; the other arguments as for cudecompTransposeYToZ
+  function cudecompAmdTransposeFieldsYToZ(handle, grid_desc, inputs, outputs, n_fields, work, dtype, input_halo_extents, &
+                                          output_halo_extents, input_padding, output_padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields), outputs(n_fields)
+    type(*), dimension(..), target :: work
+    integer :: dtype
+    integer, optional :: input_halo_extents(3), output_halo_extents(3), input_padding(3), output_padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: ih(3), oh(3), ip(3), op(3)
+    integer(c_intptr_t) :: s
+    call transpose_defaults(ih, oh, ip, op, s, input_halo_extents, output_halo_extents, input_padding, &
+                            output_padding, stream)
+    res = cudecompAmdTransposeFieldsYToZ_C(handle, grid_desc, inputs, outputs, int(n_fields, c_int32_t), c_loc(work), &
+                                           int(dtype, c_int), ih, oh, ip, op, s)
+  end function cudecompAmdTransposeFieldsYToZ
+
+  ! inputs / outputs: the device addresses of the n_fields input / output pencils (c_loc of each field), all in place or all out
+  ! of place; the other arguments as for cudecompTransposeZToY
+  function cudecompAmdTransposeFieldsZToY(handle, grid_desc, inputs, outputs, n_fields, work, dtype, input_halo_extents, &
+                                          output_halo_extents, input_padding, output_padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields), outputs(n_fields)
+    type(*), dimension(..), target :: work
+    integer :: dtype
+    integer, optional :: input_halo_extents(3), output_halo_extents(3), input_padding(3), output_padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: ih(3), oh(3), ip(3), op(3)
+    integer(c_intptr_t) :: s
+    call transpose_defaults(ih, oh, ip, op, s, input_halo_extents, output_halo_extents, input_padding, &
+                            output_padding, stream)
+    res = cudecompAmdTransposeFieldsZToY_C(handle, grid_desc, inputs, outputs, int(n_fields, c_int32_t), c_loc(work), &
+                                           int(dtype, c_int), ih, oh, ip, op, s)
+  end function cudecompAmdTransposeFieldsZToY
+
+  ! inputs / outputs: the device addresses of the n_fields input / output pencils (c_loc of each field), all in place or all out
+  ! of place; the other arguments as for cudecompTransposeYToX
+  function cudecompAmdTransposeFieldsYToX(handle, grid_desc, inputs, outputs, n_fields, work, dtype, input_halo_extents, &
+                                          output_halo_extents, input_padding, output_padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields), outputs(n_fields)
+    type(*), dimension(..), target :: work
+    integer :: dtype
+    integer, optional :: input_halo_extents(3), output_halo_extents(3), input_padding(3), output_padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: ih(3), oh(3), ip(3), op(3)
+    integer(c_intptr_t) :: s
+    call transpose_defaults(ih, oh, ip, op, s, input_halo_extents, output_halo_extents, input_padding, &
+                            output_padding, stream)
+    res = cudecompAmdTransposeFieldsYToX_C(handle, grid_desc, inputs, outputs, int(n_fields, c_int32_t), c_loc(work), &
+                                           int(dtype, c_int), ih, oh, ip, op, s)
+  end function cudecompAmdTransposeFieldsYToX
 
 
   subroutine halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)

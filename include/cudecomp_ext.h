@@ -400,8 +400,52 @@ cudecompResult_t cudecompExtDescribeFieldMoves(const cudecompExtMove_t* moves, i
                                               int32_t n_fields, uint64_t work_address, int64_t work_field_stride, int32_t es,
                                               int32_t force, int64_t out[5]);
 
-/* Data-movement kernel launches this process has made so far through the kernel layer (launchMoves and launchFieldMoves; the
- * signal / wait kernels and copies of the transports are not counted).  Tests take the difference around a call. */
+/* The plan cudecompAmdTransposeFields{XToY,YToZ,ZToY,YToX} (cudecomp_transpose_fields.h) would run on `rank` for n_fields fields
+ * (csrc/plan.h buildTransposeFieldsPlan), stateless like cudecompExtPlanTranspose and with its arguments.  pack / unpack are the
+ * moves of FIELD 0: an end in buffer 0 / 1 is field f's input / output pencil at the same offset, an end in buffer 2 (the
+ * workspace) lies at its offset + f * pack_step[i] (unpack_step[i]) elements; both arrays hold CUDECOMP_EXT_MAX_MEMBERS entries.
+ * `pipelined` is a word of flags: bit 0 the trait of cudecompExtPlanTranspose, bit 1 (value 2) both elisions off -- with n_fields == 1
+ * that is the single plan every plan of n_fields >= 2 is derived from, as data.  For n_fields >= 2: bit 0 is ignored, bit 1 implied, send_buf == recv_buf == 2, no move carries row_pitch, n_direct and rotate are 0, and
+ * send_cnt / send_off / recv_cnt / recv_off / remote_recv_off are those of the single plan with both elisions off multiplied by
+ * n_fields, behind recv_base = alignElements(n_fields * its unaligned base).  n_fields == 1 without bit 1: the plan of
+ * cudecompExtPlanTranspose, unchanged, and steps of 0.  The refusals are those of cudecompExtPlanTranspose, then INVALID_USAGE for n_fields < 1. */
+cudecompResult_t cudecompExtPlanTransposeFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t op,
+                                                const int32_t input_halo_extents[], const int32_t output_halo_extents[],
+                                                const int32_t input_padding[], const int32_t output_padding[], bool inplace,
+                                                int32_t pipelined, int32_t symmetric_recv, int32_t npergroup, int32_t n_fields,
+                                                cudecompExtTransposePlan_t* plan, int64_t* pack_step, int64_t* unpack_step);
+
+/* Lists of field-moves (csrc/kernels.h launchFieldMoveList; kernels_field_transpose.hip): moves[0 .. n - 1], n <= 64, each carried
+ * out for n_fields (1 .. 32) fields.  An end of a move in buffer 0 lies in inputs[f] + offset, an end in buffer 1 in outputs[f] +
+ * offset (outputs may be NULL when no move names buffer 1), an end in buffer 2 in the workspace at work + (offset + f *
+ * work_steps[i]) elements (work_steps NULL: all zero); elements of `es` bytes; row_pitch must be 0 (refused as launchFieldMoveList
+ * refuses it).  Destinations must be disjoint from each other and from all sources.  force: as for cudecompExtRunFieldMoves.
+ * *n_launches (optional): the launches made.
+ *
+ * cudecompExtDescribeFieldMoveList answers which launches that call would make, without a device: the same arguments with
+ * addresses as integers; at most max_launches records are written, *n_launches is the full count.  kind: csrc/kernels_batch.h
+ * KernelKind -- 24 transpose_fields_kernel, 25 rows_fieldmoves_kernel, 26 generic_fieldmoves_kernel; vec: rows and element-wise
+ * bytes per lane, transposes elements per lane; ti, tj: the tile of a transposing launch; access: 0 cached, 1 (rows) / 2
+ * (transposes) non-temporal loads and stores; guard: the transposing kernel tests the tile edges; index[j]: the list entry its
+ * j-th move is; blocks_per_field: workgroups of all its moves for one field; blocks = n_fields * blocks_per_field. */
+typedef struct {
+  int32_t kind, es, vec, ti, tj, access, guard, n_moves;
+  int64_t blocks, blocks_per_field;
+  int32_t index[8];
+} cudecompExtFieldMoveLaunch_t;
+cudecompResult_t cudecompExtRunFieldMoveList(const cudecompExtMove_t* moves, const int64_t* work_steps, int32_t n,
+                                             void* const* inputs, void* const* outputs, int32_t n_fields, void* work, int32_t es,
+                                             int32_t force, hipStream_t stream, int32_t* n_launches);
+cudecompResult_t cudecompExtDescribeFieldMoveList(const cudecompExtMove_t* moves, const int64_t* work_steps, int32_t n,
+                                                  const uint64_t* input_addresses, const uint64_t* output_addresses,
+                                                  int32_t n_fields, uint64_t work_address, int32_t es, int32_t force,
+                                                  cudecompExtFieldMoveLaunch_t* launches, int32_t max_launches,
+                                                  int32_t* n_launches);
+
+/* Data-movement kernel launches this process has made so far through the kernel layer (launchMoves, launchFieldMoves and
+ * launchFieldMoveList; the signal / wait kernels and the copy-engine copies of the transports are not counted -- the chunk copies the
+ * one-sided transport makes with the row-copy kernel between ranks that share a GPU go through launchMoves and are).  Tests take
+ * the difference around a call. */
 cudecompResult_t cudecompExtDataLaunchCount(int64_t* launches);
 
 /* The orbit walk of the in-place rotation kernel (csrc/rotate_walk.h; no launch, works without a GPU): for an array of nb
