@@ -65,13 +65,15 @@ def main():
     ap.add_argument("--fields", type=int, default=0, metavar="N",
                     help="also time cudecompAmdUpdateFieldHalosX on N pencils (periodic; one launch for all of them), after the other "
                          "passes, and compare every field on the device with a clone updated by single calls")
+    ap.add_argument("--gdims", type=int, nargs=3, default=[2048, 1024, 256], metavar="N",
+                    help="the pencil (default: config 5's per-rank X pencil; 64 64 64: a pencil on which fixed cost dominates)")
     ap.add_argument("--json", metavar="FILE", default=None, help="also write the result line to FILE")
     a = ap.parse_args()
     import torch
 
     import cudecomp_amd as cd
     torch.cuda.set_device(0)
-    gdims, halo = (2048, 1024, 256), (a.halo,) * 3
+    gdims, halo = tuple(a.gdims), (a.halo,) * 3
     h = cd.cudecompInit()
     res = {}
     gd = cd.cudecompGridDescCreate(h, cd.make_config(gdims, (1, 1)))
@@ -210,13 +212,13 @@ def main():
         cd.cudecompFree(h, gd, fwork)
     cd.cudecompFree(h, gd, work)
     cd.cudecompGridDescDestroy(h, gd)
-    line = json.dumps(dict({"workload": "X pencil 2048x1024x256 fp64 + halo %d, periodic single rank, per dim: update (self copy), "
+    line = json.dumps(dict({"workload": "X pencil %dx%dx%d fp64 + halo %d, periodic single rank, per dim: update (self copy), "
                                         "accumulation (self add)%s; %d repetitions of %d calls"
-                                        % (a.halo, (" and fill (zero)" if a.fill else "") + (" and accumulate-and-clear" if a.accumulate_clear else "")
+                                        % (gdims + (a.halo,) + ((" and fill (zero)" if a.fill else "") + (" and accumulate-and-clear" if a.accumulate_clear else "")
                                            + (" and reflection (non-periodic, odd mirror, centering 0)" if a.reflect else "")
                                            + (" and fold (non-periodic, parity -1, centering 0)" if a.fold else "")
                                            + (" and fold with clear" if a.fold_clear else "")
-                                           + (" and the update of %d pencils in one call" % a.fields if a.fields else ""), a.reps, a.calls),
+                                           + (" and the update of %d pencils in one call" % a.fields if a.fields else ""), a.reps, a.calls)),
                             "device": torch.cuda.get_device_name(0), "result": res}, **extra))
     print(line)
     if a.json:

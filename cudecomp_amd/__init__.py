@@ -848,8 +848,9 @@ def cudecompExtDescribeMoves(moves, buf_addresses, es, mode=MOVES_COPY, dtype=0,
 
 
 def cudecompExtRunFieldMoves(moves, fields, work, work_field_stride, es, force=0, stream=None):
-    """One or two moves for every buffer of `fields` (device pointers) in one launch (cudecomp_ext.h): an end of a move in buffer 2
-    lies in `work` at its offset + f * work_field_stride, any other end in fields[f].  Returns the number of launches (0 or 1)."""
+    """One or two moves for every buffer of `fields` (device pointers) in one launch with one kernel choice (cudecomp_ext.h; the
+    list launcher of cudecompExtRunFieldMoveList in its one-choice mode): an end of a move in buffer 2 lies in `work` at its offset +
+    f * work_field_stride, any other end in fields[f].  Returns the number of launches (0 or 1)."""
     f = (C.c_void_p * max(1, len(fields)))(*[p or None for p in fields])
     total = C.c_int32(-1)
     _check(lib().cudecompExtRunFieldMoves(_move_list(moves), len(moves), f, len(fields), work or None, int(work_field_stride), es,
@@ -898,8 +899,8 @@ def cudecompExtRunFieldMoveList(moves, work_steps, inputs, outputs, work, es, fo
 
 
 def cudecompExtDescribeFieldMoveList(moves, work_steps, input_addresses, output_addresses, work_address, es, force=0):
-    """Which launches cudecompExtRunFieldMoveList would make (no launch, no GPU): a list of dicts (kind 24 transposing, 25 rows, 26
-    element-wise; es, vec, ti, tj, access, guard, blocks, blocks_per_field, index)."""
+    """Which launches cudecompExtRunFieldMoveList would make (no launch, no GPU): a list of dicts (kind 22 rows, 23 element-wise, 24
+    transposing; es, vec, ti, tj, access, guard, blocks, blocks_per_field, index)."""
     fi = (C.c_uint64 * max(1, len(input_addresses)))(*[int(p) for p in input_addresses])
     fo = None if output_addresses is None else (C.c_uint64 * max(1, len(output_addresses)))(*[int(p) for p in output_addresses])
     cap = max(1, len(moves))

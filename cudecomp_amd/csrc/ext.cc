@@ -924,9 +924,12 @@ cudecompResult_t cudecompExtFold3D(const void* src, void* dst, cudecompDataType_
   return CUDECOMP_RESULT_SUCCESS;
 }
 
-static std::vector<Move3D> importFieldMoves(const cudecompExtMove_t* moves, int32_t n, int32_t n_fields, int32_t es) {
-  if (n < 0 || n > 2 || (n > 0 && !moves)) CD_INVALID_USAGE("a field launch takes at most two moves");
-  if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_HALO_FIELDS) CD_INVALID_USAGE("n_fields out of range");
+// the moves of a field launch (at most 2, CUDECOMP_AMD_MAX_HALO_FIELDS fields) or of a field-move list (at most
+// CUDECOMP_EXT_MAX_MEMBERS, CUDECOMP_AMD_MAX_TRANSPOSE_FIELDS fields)
+static std::vector<Move3D> importFieldMoves(const cudecompExtMove_t* moves, int32_t n, int32_t max_moves, int32_t n_fields,
+                                            int32_t max_fields, int32_t es) {
+  if (n < 0 || n > max_moves || (n > 0 && !moves)) CD_INVALID_USAGE("number of moves out of range");
+  if (n_fields < 1 || n_fields > max_fields) CD_INVALID_USAGE("n_fields out of range");
   if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
   std::vector<Move3D> list(n);
   for (int32_t i = 0; i < n; ++i) {
@@ -988,9 +991,10 @@ cudecompResult_t cudecompExtRunFieldMoves(const cudecompExtMove_t* moves, int32_
                                          int32_t* n_launches) {
   try {
     if (!fields) CD_INVALID_USAGE("null argument");
-    const std::vector<Move3D> list = importFieldMoves(moves, n, n_fields, es);
+    const std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_FIELDS, es);
+    const std::vector<i64> steps(list.size(), work_field_stride);
     KernelStats st;
-    launchFieldMoves(list.data(), n, fields, n_fields, work, work_field_stride, es, stream, force, &st);
+    launchFieldMoveList(list.data(), steps.data(), n, fields, fields, n_fields, work, es, stream, force, &st, true);
     if (n_launches) {
       *n_launches = 0;
       for (int c = 0; c < MOVE_CLASS_COUNT; ++c) *n_launches += st.launches[c];
@@ -1008,12 +1012,15 @@ cudecompResult_t cudecompExtDescribeFieldMoves(const cudecompExtMove_t* moves, i
                                               int32_t force, int64_t out[5]) {
   try {
     if (!field_addresses || !out) CD_INVALID_USAGE("null argument");
-    const std::vector<Move3D> list = importFieldMoves(moves, n, n_fields, es);
+    const std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_FIELDS, es);
+    const std::vector<i64> steps(list.size(), work_field_stride);
     std::vector<void*> fields(n_fields);
     for (int32_t f = 0; f < n_fields; ++f) fields[f] = reinterpret_cast<void*>(field_addresses[f]);
-    const FieldLaunch l = planFieldLaunch(list.data(), n, fields.data(), n_fields, reinterpret_cast<void*>(work_address),
-                                          work_field_stride, es, force);
-    out[0] = l.blocks ? (int64_t)l.k.kind : -1;
+    const std::vector<FieldMoveLaunch> ls = planFieldMoveLaunches(list.data(), steps.data(), n, fields.data(), fields.data(), n_fields,
+                                                                  reinterpret_cast<void*>(work_address), es, force, true);
+    const FieldMoveLaunch none{};  // (every move is empty: nothing is launched)
+    const FieldMoveLaunch& l = ls.empty() ? none : ls[0];  // (one choice, at most two moves: never a second launch)
+    out[0] = ls.empty() ? -1 : (int64_t)l.k.kind;
     out[1] = l.k.vec;
     out[2] = l.k.access;
     out[3] = l.blocks_per_field;
@@ -1024,29 +1031,6 @@ cudecompResult_t cudecompExtDescribeFieldMoves(const cudecompExtMove_t* moves, i
     return CUDECOMP_RESULT_INTERNAL_ERROR;
   }
   return CUDECOMP_RESULT_SUCCESS;
-}
-
-static std::vector<Move3D> importFieldMoveList(const cudecompExtMove_t* moves, int32_t n, int32_t n_fields, int32_t es) {
-  if (n < 0 || n > CUDECOMP_EXT_MAX_MEMBERS || (n > 0 && !moves)) CD_INVALID_USAGE("a field-move list takes at most 64 moves");
-  if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_TRANSPOSE_FIELDS) CD_INVALID_USAGE("n_fields out of range");
-  if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
-  std::vector<Move3D> list(n);
-  for (int32_t i = 0; i < n; ++i) {
-    const cudecompExtMove_t& e = moves[i];
-    if (e.src_buf < 0 || e.src_buf > 2 || e.dst_buf < 0 || e.dst_buf > 2) CD_INVALID_USAGE("buffer number out of range");
-    Move3D& m = list[i];
-    m.src_buf = (BufId)e.src_buf;
-    m.dst_buf = (BufId)e.dst_buf;
-    m.src_off = e.src_off;
-    m.dst_off = e.dst_off;
-    for (int d = 0; d < 3; ++d) {
-      m.extent[d] = e.extent[d];
-      m.ss[d] = e.ss[d];
-      m.ds[d] = e.ds[d];
-    }
-    m.dst_row_pitch = e.row_pitch;
-  }
-  return list;
 }
 
 cudecompResult_t cudecompExtPlanTransposeFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t op, const int32_t in_halo[],
@@ -1088,7 +1072,7 @@ cudecompResult_t cudecompExtRunFieldMoveList(const cudecompExtMove_t* moves, con
                                              int32_t force, hipStream_t stream, int32_t* n_launches) {
   try {
     if (!inputs) CD_INVALID_USAGE("null argument");
-    const std::vector<Move3D> list = importFieldMoveList(moves, n, n_fields, es);
+    const std::vector<Move3D> list = importFieldMoves(moves, n, CUDECOMP_EXT_MAX_MEMBERS, n_fields, CUDECOMP_AMD_MAX_TRANSPOSE_FIELDS, es);
     KernelStats st;
     launchFieldMoveList(list.data(), work_steps, n, inputs, outputs, n_fields, work, es, stream, force, &st);
     if (n_launches) {
@@ -1110,7 +1094,7 @@ cudecompResult_t cudecompExtDescribeFieldMoveList(const cudecompExtMove_t* moves
                                                   int32_t* n_launches) {
   try {
     if (!input_addresses || !n_launches || (max_launches > 0 && !launches)) CD_INVALID_USAGE("null argument");
-    const std::vector<Move3D> list = importFieldMoveList(moves, n, n_fields, es);
+    const std::vector<Move3D> list = importFieldMoves(moves, n, CUDECOMP_EXT_MAX_MEMBERS, n_fields, CUDECOMP_AMD_MAX_TRANSPOSE_FIELDS, es);
     std::vector<void*> in(n_fields), out(n_fields);
     for (int32_t f = 0; f < n_fields; ++f) {
       in[f] = reinterpret_cast<void*>(input_addresses[f]);

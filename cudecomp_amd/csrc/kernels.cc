@@ -8,8 +8,9 @@
 // batching key, the launcher's instantiation and the kernel's name all come from that one record.  The kernels live in
 // kernels_rows.hip, kernels_transpose.hip (one code object per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip and kernels_fold.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
-// transpose.cc; kernels_fields.hip (field-moves: the moves of a halo phase for several pencils in one launch) has an entry of its
-// own at the end of this file, launchFieldMoves.  kernels_batch.h says why they are separate code objects.
+// transpose.cc; kernels_field_transpose.hip (lists of field-moves: the moves of a halo or transpose phase for several pencils in
+// one launch) has an entry of its own at the end of this file, launchFieldMoveList.  kernels_batch.h says why they are separate
+// code objects.
 //
 // 2-byte elements (fp16, bf16) take the row copy (plain kernel), the LDS-tiled transposition (128 x 128 tiles with 16-byte
 // lanes, 64 x 64 element-wise) and the generic kernel only: never the window, lines, row-lines, shifted-rows, dense-rows or
@@ -50,8 +51,7 @@ constexpr long long kDenseMaxGapBytes = 512;  // widest gap between rows the den
 
 MoveClass classOf(KernelKind kind) {
   if (kind == K_GENERIC || kind == K_GENERIC_ADD || kind == K_GENERIC_FILL || kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE ||
-      kind == K_GENERIC_REFLECT || kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE || kind == K_GENERIC_FIELDS ||
-      kind == K_GENERIC_FIELDMOVES)
+      kind == K_GENERIC_REFLECT || kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE || kind == K_GENERIC_FIELDS)
     return MOVE_GENERIC;
   return (kind >= K_TRANSPOSE && kind <= K_TRANSPOSE_ROWLINES) || kind == K_TRANSPOSE_FIELDS ? MOVE_TRANSPOSE : MOVE_ROWS_VEC;
 }
@@ -70,11 +70,11 @@ bool halfMisaligned(const DevMove& dm, int es, long long strides) {
   return es == 2 && ((reinterpret_cast<uintptr_t>(dm.src) | reinterpret_cast<uintptr_t>(dm.dst) | (uintptr_t)(strides * es)) & 3) != 0;
 }
 
-// Rows contiguous on both sides (also the all-extents-1 case), copied or added.  Widest vector that divides the row length;
-// addresses only need the element's natural alignment (see GlobalBytes).
-void rowVectors(Classified& c, const Move3D& m) {
+// Rows contiguous on both sides (also the all-extents-1 case), copied or added.  Widest vector, of at most `widest` bytes, that
+// divides the row length; addresses only need the element's natural alignment (see GlobalBytes).
+void rowVectors(Classified& c, const Move3D& m, int widest = 16) {
   const int es = c.k.es;
-  int vb = 16;
+  int vb = widest;
   while (vb > es && (m.extent[0] * es) % vb != 0) vb >>= 1;
   if (halfMisaligned(c.dm, es, m.ss[1] | m.ss[2] | m.ds[1] | m.ds[2])) vb = 2;
   c.k.vec = vb;
@@ -321,8 +321,8 @@ bool offerRowLines(Classified& c, i64 planned_row, i64 row_pitch) {
   return true;
 }
 
-// LDS-tiled transposition: dim t of the normalised move is the destination's unit-stride dim
-void classifyTranspose(Classified& c, const Move3D& in, const Move3D& m, int t, const KernelTuning& tuning, bool remote) {
+// Dims (i, j, k) of a transposition: i the source's unit-stride dim (0 of the normalised move), j the destination's (t), k the other
+void transposeGeometry(Classified& c, const Move3D& m, int t) {
   const int k = 3 - t;
   c.dm.e[0] = m.extent[0];
   c.dm.e[1] = m.extent[t];
@@ -333,6 +333,11 @@ void classifyTranspose(Classified& c, const Move3D& in, const Move3D& m, int t, 
   c.dm.ds[0] = m.ds[0];
   c.dm.ds[1] = 1;
   c.dm.ds[2] = m.ds[k];
+}
+
+// LDS-tiled transposition: dim t of the normalised move is the destination's unit-stride dim
+void classifyTranspose(Classified& c, const Move3D& in, const Move3D& m, int t, const KernelTuning& tuning, bool remote) {
+  transposeGeometry(c, m, t);
   bool j_first, aligned;
   chooseTranspose(c, tuning, j_first, aligned);
   c.p0 = 0;
@@ -578,8 +583,6 @@ void spellKernelName(const KernelChoice& k) {
     case K_TRANSPOSE_FIELDS:
       snprintf(out, n, "transpose_fields_kernel<%d,%d,%d,%d,%d,%s>", k.es, k.vec, k.ti, k.tj, s, k.guard ? "true" : "false");
       break;
-    case K_ROWS_FIELDMOVES: snprintf(out, n, "rows_fieldmoves_kernel<%d,%d>", k.vec, s); break;
-    case K_GENERIC_FIELDMOVES: snprintf(out, n, "generic_fieldmoves_kernel<%d>", k.es); break;
   }
 }
 
@@ -632,10 +635,8 @@ void launchBatch(const KernelChoice& k, const Batch& b, const void* fill_value, 
     case K_ROWS_FOLD_TAKE:
     case K_GENERIC_FOLD_TAKE: launchFoldBatch(k, b, blocks, stream); break;
     case K_ROWS_FIELDS:
-    case K_GENERIC_FIELDS: CD_INTERNAL_ERROR("field-moves are launched by launchFieldMoves");
-    case K_TRANSPOSE_FIELDS:
-    case K_ROWS_FIELDMOVES:
-    case K_GENERIC_FIELDMOVES: CD_INTERNAL_ERROR("lists of field-moves are launched by launchFieldMoveList");
+    case K_GENERIC_FIELDS:
+    case K_TRANSPOSE_FIELDS: CD_INTERNAL_ERROR("lists of field-moves are launched by launchFieldMoveList");
   }
 }
 
@@ -736,123 +737,11 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
 }
 
 // ---------------------------------------------------------------------------------------------
-// field-moves (kernels.h; kernels_fields.hip)
-// ---------------------------------------------------------------------------------------------
-FieldLaunch planFieldLaunch(const Move3D* moves, int n, void* const* fields, int n_fields, void* work, i64 work_field_stride,
-                            int es, int force) {
-  if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
-  if (n < 0 || n > 2) CD_INTERNAL_ERROR("a field launch serves at most two moves");
-  if (n_fields < 1 || n_fields > kMaxFields || !fields) CD_INTERNAL_ERROR("field count out of range");
-  for (int f = 0; f < n_fields; ++f)
-    if (!fields[f]) CD_INTERNAL_ERROR("null field buffer");
-  FieldLaunch l{};
-  FieldBatch& b = l.b;
-  b.n_fields = n_fields;
-  b.work = static_cast<char*>(work);
-  for (int f = 0; f < n_fields; ++f) b.field[f] = static_cast<char*>(fields[f]);
-  l.k.es = es;
-  const bool force_generic = (force & 1) != 0;
-
-  // the shared geometry, normalised, and every address a lane's first element can have, or-ed together (the 2-byte rule)
-  Move3D norm[2];
-  uintptr_t address_bits = 0;
-  bool rows = !force_generic;
-  i64 largest = 0;
-  for (int i = 0; i < n; ++i) {
-    const Move3D& in = moves[i];
-    if (in.add || in.fill || in.take || in.reflect || in.negate || in.dst_row_pitch != 0)
-      CD_INTERNAL_ERROR("field-moves are plain copies of exactly their cells");
-    if ((in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK) && !work) CD_INTERNAL_ERROR("field-move through a workspace that was not given");
-    for (int d = 0; d < 3; ++d)
-      if (in.ss[d] < 0 || in.ds[d] < 0 || in.extent[d] < 0) CD_INTERNAL_ERROR("negative stride or extent in a field-move");
-    if (in.elements() == 0) continue;
-    Move3D m = in;
-    normalizeMove(m);
-    rows = rows && m.ss[0] <= 1 && m.ds[0] <= 1;
-    largest = std::max(largest, m.elements());
-    FieldSide& s = b.side[b.n_sides];
-    s.src_work = in.src_buf == BUF_WORK;
-    s.dst_work = in.dst_buf == BUF_WORK;
-    s.src_off = in.src_off * es;
-    s.dst_off = in.dst_off * es;
-    s.src_step = s.src_work ? work_field_stride * es : 0;
-    s.dst_step = s.dst_work ? work_field_stride * es : 0;
-    for (int f = 0; f < n_fields; ++f) {
-      address_bits |= reinterpret_cast<uintptr_t>(s.src_work ? b.work + f * s.src_step : b.field[f]) + (uintptr_t)s.src_off;
-      address_bits |= reinterpret_cast<uintptr_t>(s.dst_work ? b.work + f * s.dst_step : b.field[f]) + (uintptr_t)s.dst_off;
-    }
-    norm[b.n_sides++] = m;
-  }
-  if (b.n_sides == 0) return l;
-
-  const bool streaming = (largest * es >= kStreamBytes || (force & 2)) && !(force & 4);
-  Classified c[2] = {};
-  int vb = 16;
-  for (int i = 0; i < b.n_sides; ++i) {
-    c[i].k.es = es;
-    c[i].elements = norm[i].elements();
-    c[i].dm.src = reinterpret_cast<const char*>(address_bits);  // (only its alignment is read)
-    c[i].dm.dst = reinterpret_cast<char*>(address_bits);
-    if (rows) {
-      rowVectors(c[i], norm[i]);
-      vb = std::min(vb, c[i].k.vec);
-    } else {
-      genericGeometry(c[i], norm[i]);
-    }
-  }
-  l.k.kind = rows ? K_ROWS_FIELDS : K_GENERIC_FIELDS;
-  l.k.vec = rows ? vb : es;
-  l.k.access = rows && streaming ? 1 : 0;
-  l.k.arith = ARITH_NONE;
-  l.cls = classOf(l.k.kind);
-  if (rows && vb < es) CD_INTERNAL_ERROR("field-move narrower than one element");
-  unsigned long long per_field = 0;
-  for (int i = 0; i < b.n_sides; ++i) {
-    if (rows) {  // one lane width for the launch: the narrowest (a power of two, so it divides every row)
-      c[i].k.vec = vb;
-      c[i].dm.e[0] = norm[i].extent[0] * es / vb;
-      rowTiles(c[i]);
-    }
-    if (c[i].blocks == 0 || c[i].blocks > 0x7fffffffULL) CD_NOT_SUPPORTED("single block move too large for one launch");
-    FieldSide& s = b.side[i];
-    for (int d = 0; d < 3; ++d) {
-      s.e[d] = c[i].dm.e[d];
-      s.ss[d] = c[i].dm.ss[d];
-      s.ds[d] = c[i].dm.ds[d];
-    }
-    s.p0 = c[i].p0;
-    s.t0 = c[i].t0;
-    s.t1 = c[i].t1;
-    s.blocks = (unsigned int)c[i].blocks;
-    per_field += c[i].blocks;
-    l.elements += c[i].elements * n_fields;
-  }
-  const unsigned long long total = per_field * (unsigned long long)n_fields;
-  if (total > 0x7fffffffULL) CD_NOT_SUPPORTED("field-moves too large for one launch");
-  b.side1_first = (unsigned int)((unsigned long long)b.side[0].blocks * n_fields);
-  l.blocks_per_field = (unsigned int)per_field;
-  l.blocks = (unsigned int)total;
-  return l;
-}
-
-void launchFieldMoves(const Move3D* moves, int n, void* const* fields, int n_fields, void* work, i64 work_field_stride, int es,
-                      hipStream_t stream, int force, KernelStats* stats) {
-  const FieldLaunch l = planFieldLaunch(moves, n, fields, n_fields, work, work_field_stride, es, force);
-  if (l.blocks == 0) return;
-  spellKernelName(l.k);
-  ++g_data_launches;
-  launchFieldsBatch(l.k, l.b, l.blocks, stream);
-  if (stats) {
-    stats->launches[l.cls] += 1;
-    stats->elements[l.cls] += l.elements;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // lists of field-moves (kernels.h; kernels_field_transpose.hip)
 // ---------------------------------------------------------------------------------------------
 std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i64* work_steps, int n, void* const* inputs,
-                                                   void* const* outputs, int n_fields, void* work, int es, int force) {
+                                                   void* const* outputs, int n_fields, void* work, int es, int force,
+                                                   bool one_choice) {
   if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
   if (n < 0 || (n > 0 && !moves)) CD_INTERNAL_ERROR("field-move list without moves");
   if (n_fields < 1 || n_fields > kMaxFields || !inputs) CD_INTERNAL_ERROR("field count out of range");
@@ -861,8 +750,9 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
   const bool force_generic = (force & 1) != 0;
   char* const w = static_cast<char*>(work);
 
-  // classify each move's shared geometry once; the addresses every field's first element can have are or-ed together (the
+  // each move's shared geometry, normalised, its ends, and the addresses every field's first element can have or-ed together (the
   // 2-byte rule: all fields' pencils and all workspace pieces)
+  std::vector<Move3D> norm;
   std::vector<Classified> cs;
   std::vector<FieldMove> fms;
   std::vector<int> index;
@@ -899,33 +789,46 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     c.elements = m.elements();
     c.dm.src = reinterpret_cast<const char*>(address_bits);  // (only its alignment is read)
     c.dm.dst = reinterpret_cast<char*>(address_bits);
+    norm.push_back(m);
+    cs.push_back(c);
+    fms.push_back(fm);
+    index.push_back(i);
+  }
+  // one_choice: rows only if every move has contiguous rows, then the narrowest of their lane widths; the largest move decides
+  // the access mode
+  bool all_rows = !force_generic;
+  int lanes = 16;
+  i64 largest = 0;
+  for (size_t i = 0; one_choice && i < cs.size(); ++i) {
+    all_rows = all_rows && norm[i].ss[0] <= 1 && norm[i].ds[0] <= 1;
+    largest = std::max(largest, cs[i].elements);
+    if (!all_rows) continue;
+    Classified c = cs[i];
+    rowVectors(c, norm[i]);
+    lanes = std::min(lanes, c.k.vec);
+  }
+  for (size_t i = 0; i < cs.size(); ++i) {
+    const Move3D& m = norm[i];
+    Classified& c = cs[i];
+    FieldMove& fm = fms[i];
     // Access: cached while the move is below kStreamBytes PER FIELD, non-temporal loads and stores from there -- the project's
     // rule for copies, unmeasured for these kernels; the element-wise kernel always caches.
-    const bool streaming = (c.elements * es >= kStreamBytes || (force & 2)) && !(force & 4);
+    const bool streaming = ((one_choice ? largest : c.elements) * es >= kStreamBytes || (force & 2)) && !(force & 4);
     int t = -1;
-    if (!force_generic && m.ss[0] == 1) {
+    if (!force_generic && !one_choice && m.ss[0] == 1) {
       if (m.ds[1] == 1) t = 1;
       if (m.ds[2] == 1) t = 2;
     }
-    if (!force_generic && m.ss[0] <= 1 && m.ds[0] <= 1) {
-      c.k.kind = K_ROWS_FIELDMOVES;
+    if (one_choice ? all_rows : (!force_generic && m.ss[0] <= 1 && m.ds[0] <= 1)) {
+      c.k.kind = K_ROWS_FIELDS;
       c.k.access = streaming ? 1 : 0;
-      rowVectors(c, m);
+      rowVectors(c, m, lanes);
       if (c.k.vec < es) CD_INTERNAL_ERROR("field-move narrower than one element");
       rowTiles(c);
     } else if (t > 0 && m.extent[0] >= 4 && m.extent[t] >= 4) {
-      const int k = 3 - t;
       c.k.kind = K_TRANSPOSE_FIELDS;
       c.k.access = streaming ? 2 : 0;
-      c.dm.e[0] = m.extent[0];
-      c.dm.e[1] = m.extent[t];
-      c.dm.e[2] = m.extent[k];
-      c.dm.ss[0] = 1;
-      c.dm.ss[1] = m.ss[t];
-      c.dm.ss[2] = m.ss[k];
-      c.dm.ds[0] = m.ds[0];
-      c.dm.ds[1] = 1;
-      c.dm.ds[2] = m.ds[k];
+      transposeGeometry(c, m, t);
       // one tile per element size and lane width: 2-byte 128 x 128 with 16-byte lanes, 64 x 64 element-wise; 4-byte 64 x 128 /
       // 64 x 64; 8-byte 64 x 64; 16-byte 32 x 32
       const int vw = transposeLaneWidth(c);
@@ -937,7 +840,7 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
       c.t1 = (unsigned int)((c.dm.e[1] + c.k.tj - 1) / c.k.tj);
       c.blocks = (unsigned long long)c.t0 * c.t1 * (unsigned long long)c.dm.e[2];
     } else {
-      c.k.kind = K_GENERIC_FIELDMOVES;
+      c.k.kind = K_GENERIC_FIELDS;
       c.k.access = 0;
       genericGeometry(c, m);
     }
@@ -952,9 +855,6 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     fm.t0 = c.t0;
     fm.t1 = c.t1;
     fm.blocks = (unsigned int)c.blocks;
-    cs.push_back(c);
-    fms.push_back(fm);
-    index.push_back(i);
   }
   // moves of one phase are independent: regrouped by equal kernel choice in the order of first appearance, cut at kMaxBatch
   std::vector<FieldMoveLaunch> launches;
@@ -975,7 +875,10 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     for (size_t j = i; j < cs.size() && b.n < kMaxBatch; ++j) {
       if (done[j] || !(cs[j].k == cs[i].k)) continue;
       const unsigned long long mine = cs[j].blocks * (unsigned long long)n_fields;
-      if (blocks + mine > 0x7fffffffULL) break;  // (never the first of a group: checked per move above)
+      if (blocks + mine > 0x7fffffffULL) {  // (never the first of a group: checked per move above)
+        if (one_choice) CD_NOT_SUPPORTED("field-moves too large for one launch");
+        break;
+      }
       b.first_block[b.n] = (unsigned int)blocks;
       b.m[b.n] = fms[j];
       blocks += mine;
@@ -993,8 +896,8 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
 }
 
 void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void* const* inputs, void* const* outputs, int n_fields,
-                         void* work, int es, hipStream_t stream, int force, KernelStats* stats) {
-  for (const FieldMoveLaunch& l : planFieldMoveLaunches(moves, work_steps, n, inputs, outputs, n_fields, work, es, force)) {
+                         void* work, int es, hipStream_t stream, int force, KernelStats* stats, bool one_choice) {
+  for (const FieldMoveLaunch& l : planFieldMoveLaunches(moves, work_steps, n, inputs, outputs, n_fields, work, es, force, one_choice)) {
     spellKernelName(l.k);
     ++g_data_launches;
     launchFieldMoveBatch(l.k, l.b, l.blocks, stream);

@@ -77,35 +77,11 @@ std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3]
 // 4 runs over batch planes, 8 transpose_lines_kernel, 16 transpose_rowlines_kernel), access mode}.  (Tests of the planning logic: tests/test_kernel_plan.py.)
 void describeMove(const Move3D& m, const void* src, void* dst, int es, const KernelTuning* tuning, long long out[10]);
 
-// ---- field-moves: the same one or two copy moves for several buffers in ONE launch (kernels_fields.hip) ---------------------
-// The moves of one phase of a multi-field halo update (include/cudecomp_halo_fields.h): moves[0 .. n - 1], n <= 2, share their
-// geometry among `n_fields` (1 .. kern::kMaxFields) fields.  An end of a move whose buffer is BUF_WORK lies in the workspace, at
-// work + (offset + f * work_field_stride) elements for field f; any other end lies in field f's own buffer, fields[f] + offset.
-// The kernels copy exactly the cells of the moves -- rows (rowVectors' rule) or element by element (genericGeometry's), never a
-// transposing, shifted or dense form -- and ONE kernel choice serves the launch: rows only when every move has contiguous rows,
-// the narrowest of the moves' lane widths, and for 2-byte elements 2-byte lanes as soon as ANY field's address or any stride is
-// 2 mod 4.  Access: cached while every move is below kStreamBytes PER FIELD, non-temporal loads and stores from there; the
-// element-wise kernel always caches.  force: bit 0 the element-wise kernel, bit 1 non-temporal access regardless of the size, bit 2
-// cached access regardless of the size.  A move with add, fill, take, reflect, negate or dst_row_pitch, and a workspace end
-// without a workspace, are internal errors before anything is launched; more than 2^31 - 1 workgroups is NOT_SUPPORTED.
-struct FieldLaunch {
-  KernelChoice k;
-  kern::FieldBatch b;
-  unsigned int blocks;            // 0: every move is empty, nothing is launched
-  unsigned int blocks_per_field;  // of all its sides
-  MoveClass cls;
-  i64 elements;                   // of all moves and fields
-};
-// WHICH launch launchFieldMoves makes (pure host code, no device needed; `fields` and `work` are only looked at as addresses)
-FieldLaunch planFieldLaunch(const Move3D* moves, int n, void* const* fields, int n_fields, void* work, i64 work_field_stride,
-                            int es, int force = 0);
-void launchFieldMoves(const Move3D* moves, int n, void* const* fields, int n_fields, void* work, i64 work_field_stride, int es,
-                      hipStream_t stream, int force = 0, KernelStats* stats = nullptr);
-
 // ---- lists of field-moves: a list of copy moves, each for several (input, output) pairs of buffers (kernels_field_transpose.hip) --
-// The moves of one phase of a multi-field transpose (include/cudecomp_transpose_fields.h): moves[0 .. n - 1] share their geometry
-// among `n_fields` (1 .. kern::kMaxFields) fields.  An end of a move in BUF_IN lies in inputs[f] + offset, an end in BUF_OUT in
-// outputs[f] + offset, an end in BUF_WORK at work + (offset + f * work_steps[i]) elements (work_steps == nullptr: all zero).
+// The moves of one phase of a multi-field transpose (include/cudecomp_transpose_fields.h) or of a multi-field halo update
+// (include/cudecomp_halo_fields.h): moves[0 .. n - 1] share their geometry among `n_fields` (1 .. kern::kMaxFields) fields.  An end
+// of a move in BUF_IN lies in inputs[f] + offset, an end in BUF_OUT in outputs[f] + offset, an end in BUF_WORK at
+// work + (offset + f * work_steps[i]) elements (work_steps == nullptr: all zero).
 // Each move's shared geometry is classified once: rows (rowVectors' rule) when its fastest dim is contiguous on both sides, the
 // LDS-tiled transposition (chooseTranspose's lane-width rule, one tile per element size and lane width) when source and
 // destination rows run along different dims of at least 4 elements, element by element (genericGeometry's) otherwise.  For
@@ -113,9 +89,14 @@ void launchFieldMoves(const Move3D* moves, int n, void* const* fields, int n_fie
 // KernelChoice share a launch, in the order of first appearance, cut at kMaxBatch moves (and before 2^31 - 1 workgroups).  The
 // kernels copy exactly the cells of the moves -- never a window, lines, shifted or dense form.  Access: cached while a move is
 // below kStreamBytes PER FIELD, non-temporal loads and stores from there (unmeasured for these kernels); the element-wise kernel
-// always caches.  force: as for launchFieldMoves.  A move with add, fill, take, reflect, negate or dst_row_pitch, a workspace end
-// without a workspace and an output end without `outputs` are internal errors before anything is launched; a move of more than
-// 2^31 - 1 workgroups is NOT_SUPPORTED.
+// always caches.  force: bit 0 the element-wise kernel, bit 1 non-temporal access regardless of the size, bit 2 cached access
+// regardless of the size.
+// one_choice (the phases of a halo update: its one or two sides): ONE kernel choice serves the list, hence one launch -- rows only
+// when every move has contiguous rows, then the narrowest of the moves' lane widths; never the transposition; non-temporal access
+// when the LARGEST move reaches kStreamBytes per field.  More than 2^31 - 1 workgroups in all are then NOT_SUPPORTED, not a
+// second launch.
+// A move with add, fill, take, reflect, negate or dst_row_pitch, a workspace end without a workspace and an output end without
+// `outputs` are internal errors before anything is launched; a move of more than 2^31 - 1 workgroups is NOT_SUPPORTED.
 struct FieldMoveLaunch {
   KernelChoice k;
   kern::FieldMoveBatch b;
@@ -127,11 +108,12 @@ struct FieldMoveLaunch {
 };
 // WHICH launches launchFieldMoveList makes, in order (pure host code, no device needed; buffers are only looked at as addresses)
 std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i64* work_steps, int n, void* const* inputs,
-                                                   void* const* outputs, int n_fields, void* work, int es, int force = 0);
+                                                   void* const* outputs, int n_fields, void* work, int es, int force = 0,
+                                                   bool one_choice = false);
 void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void* const* inputs, void* const* outputs, int n_fields,
-                         void* work, int es, hipStream_t stream, int force = 0, KernelStats* stats = nullptr);
+                         void* work, int es, hipStream_t stream, int force = 0, KernelStats* stats = nullptr, bool one_choice = false);
 
-// data-movement launches this process has made so far (launchMoves, launchFieldMoves and launchFieldMoveList; tests count launches per call with it)
+// data-movement launches this process has made so far (launchMoves and launchFieldMoveList; tests count launches per call with it)
 long long dataLaunchCount();
 
 // name (template spelling) of the data-movement kernel launched last by this process, "" before the first launch

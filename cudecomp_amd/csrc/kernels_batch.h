@@ -2,8 +2,8 @@
 // kernel choice (KernelChoice), the launch descriptor (Batch) and the launchers.  The code objects the classifier dispatches
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip;
-// kernels_fields.hip is reached through launchFieldMoves (kernels.h); kernels_rotate.hip and sync.hip are launched by the
-// executor; kernels_field_transpose.hip is reached through launchFieldMoveList (kernels.h).  Seventeen code objects in all.
+// kernels_rotate.hip and sync.hip are launched by the executor; kernels_field_transpose.hip (lists of field-moves: multi-field
+// halo phases and transposes) is reached through launchFieldMoveList (kernels.h).  Sixteen code objects in all.
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
 // code object beyond roughly 0.6-0.7 MB puts the whole process into a regime where every small synchronous operation costs
@@ -66,49 +66,23 @@ struct Batch {
   DevMove m[kMaxBatch];
 };
 
-// ---- field-moves: the same one or two moves for up to kMaxFields buffers, in ONE launch (kernels_fields.hip) ------------------
-// A phase of a multi-field halo update has at most two sides (low, high) whose geometry is the same for every field: only the
-// base pointers differ.  A side therefore carries byte OFFSETS in the place of DevMove's pointers; each end of it is either
-// "field f's pencil" (base = field[f]) or "the workspace" (base = work + f * step bytes: the fields' pieces of one slot lie one
-// behind the other).  Workgroup b serves side 0 while b < side1_first, side 1 from there; inside a side, field b / blocks and
-// that field's workgroup b % blocks -- one decode per workgroup.
-constexpr int kMaxFields = 32;  // one 256-byte table of pointers in the kernel arguments (include/cudecomp_halo_fields.h)
-
-struct FieldSide {
-  long long src_off, dst_off;    // bytes from the base of that end
-  long long src_step, dst_step;  // workspace ends: bytes between the pieces of consecutive fields (unused for pencil ends)
-  long long e[3];                // as DevMove: rows_fields_kernel vectors per row / rows / planes, strides in BYTES;
-  long long ss[3];               // generic_fields_kernel extents and strides in ELEMENTS
-  long long ds[3];
-  int src_work, dst_work;        // 1: that end is the workspace, 0: field f's pencil
-  int p0;                        // rows: log2 of the lanes per row; element-wise: the dim the lanes run along
-  unsigned int t0, t1;           // rows: tile columns / tile rows per plane
-  unsigned int blocks;           // workgroups PER FIELD
-};
-
-struct FieldBatch {
-  int n_sides, n_fields;
-  unsigned int side1_first;  // n_fields * side[0].blocks
-  char* work;
-  FieldSide side[2];
-  char* field[kMaxFields];
-};
-
 // ---- lists of field-moves: up to kMaxBatch moves, each for up to kMaxFields (input, output) pairs of buffers, in ONE launch
-// (kernels_field_transpose.hip; multi-field transposes, include/cudecomp_transpose_fields.h) ------------------------------------
+// (kernels_field_transpose.hip; multi-field halo updates and transposes, include/cudecomp_halo_fields.h and
+// include/cudecomp_transpose_fields.h) ------------------------------------------------------------------------------------------
 // The geometry is held once per move, with byte OFFSETS in the place of DevMove's pointers.  Each end of a move names its base:
 // kEndInput "field f's entry of the input table", kEndOutput "field f's entry of the output table", kEndWork "the workspace at
 // f * a per-move byte step" (the fields' pieces of one peer's chunk lie one behind the other).  Workgroup b serves the move
 // whose [first_block[i], first_block[i + 1]) holds it; inside the move, field rel / blocks and that field's workgroup
 // rel % blocks -- one decode per workgroup.  The struct travels in the kernel arguments and stays under their 4 KB (1.7 KB).
+constexpr int kMaxFields = 32;  // two 256-byte tables of pointers in the kernel arguments
 constexpr int kEndInput = 0, kEndOutput = 1, kEndWork = 2;
 
 struct FieldMove {
   long long src_off, dst_off;    // bytes from the base of that end
   long long src_step, dst_step;  // kEndWork ends: bytes between the pieces of consecutive fields (0 for table ends)
   long long e[3];                // transpose_fields_kernel: {ei, ej, ek}, ss = {1, sj, sk}, ds = {di, 1, dk} in ELEMENTS;
-  long long ss[3];               // rows_fieldmoves_kernel: vectors per row / rows / planes, strides in BYTES;
-  long long ds[3];               // generic_fieldmoves_kernel: extents and strides in ELEMENTS
+  long long ss[3];               // rows_fields_kernel: vectors per row / rows / planes, strides in BYTES;
+  long long ds[3];               // generic_fields_kernel: extents and strides in ELEMENTS
   int src_end, dst_end;          // kEnd*
   int p0;                        // rows: log2 of the lanes per row; element-wise: the dim the lanes run along
   unsigned int t0, t1;           // transposes: tiles along i / j; rows: tile columns / tile rows per plane
@@ -152,11 +126,9 @@ enum KernelKind {
   K_GENERIC_FOLD,        // generic_fold_kernel = 19
   K_ROWS_FOLD_TAKE,      // rows_fold_kernel with TAKE (... ; src = 0) = 20
   K_GENERIC_FOLD_TAKE,   // generic_fold_kernel with TAKE = 21
-  K_ROWS_FIELDS,         // rows_fields_kernel (dst = src, the same move for every field of a FieldBatch) = 22
+  K_ROWS_FIELDS,         // rows_fields_kernel (dst = src, one move of a FieldMoveBatch for every field) = 22
   K_GENERIC_FIELDS,      // generic_fields_kernel = 23
-  K_TRANSPOSE_FIELDS,    // transpose_fields_kernel (LDS-tiled, one move of a FieldMoveBatch for every field) = 24
-  K_ROWS_FIELDMOVES,     // rows_fieldmoves_kernel = 25
-  K_GENERIC_FIELDMOVES   // generic_fieldmoves_kernel = 26
+  K_TRANSPOSE_FIELDS     // transpose_fields_kernel (LDS-tiled) = 24
 };
 struct KernelChoice {
   KernelKind kind;
@@ -190,9 +162,8 @@ inline int streamArgOf(KernelKind kind, int access) {
   if (kind == K_GENERIC_REFLECT) return 0;
   if (kind == K_ROWS_FOLD || kind == K_ROWS_FOLD_TAKE) return access;
   if (kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE) return 0;
-  if (kind == K_ROWS_FIELDS) return access;
-  if (kind == K_GENERIC_FIELDS || kind == K_GENERIC_FIELDMOVES) return 0;
-  if (kind == K_ROWS_FIELDMOVES || kind == K_TRANSPOSE_FIELDS) return access;
+  if (kind == K_ROWS_FIELDS || kind == K_TRANSPOSE_FIELDS) return access;
+  if (kind == K_GENERIC_FIELDS) return 0;
   if (kind == K_TRANSPOSE_WINDOW || kind == K_TRANSPOSE_LINES || kind == K_TRANSPOSE_ROWLINES)
     return access == 2 ? 4 : access;  // always cached loads: the overlap rows of neighbouring windows hit in L2
   return access == 3 ? 3 : (access >= 1 ? 1 : 0);  // row copies: loads and stores stream together
@@ -235,8 +206,6 @@ void launchReflectBatch(const KernelChoice& k, const kern::Batch& b, unsigned in
 // signed strides in elements.  k.arith: the real type of the addition; k.neg: the sign mask of that type travels as a 16-byte
 // kernel argument of its own, all zero otherwise.  Local buffers only.
 void launchFoldBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
-// kernels_fields.hip: field-moves (plain copies of exactly the cells of the moves; local buffers only)
-void launchFieldsBatch(const KernelChoice& k, const kern::FieldBatch& b, unsigned int blocks, hipStream_t stream);
 // kernels_field_transpose.hip: lists of field-moves (plain copies of exactly the cells of the moves; local buffers only)
 void launchFieldMoveBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, unsigned int blocks, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)

@@ -1,20 +1,24 @@
 // kernels_field_transpose.hip -- lists of field-moves: up to kMaxBatch moves, each carried out for up to kMaxFields (input,
-// output) pairs of pencils, in ONE launch (multi-field transposes, include/cudecomp_transpose_fields.h).  Hand-written gfx950
-// (CDNA4 / MI355X) data-movement kernels, one code object (see kernels_batch.h for why there are several).
+// output) pairs of pencils, in ONE launch (multi-field transposes, include/cudecomp_transpose_fields.h, and multi-field halo
+// updates, include/cudecomp_halo_fields.h).  Hand-written gfx950 (CDNA4 / MI355X) data-movement kernels, one code object (see
+// kernels_batch.h for why there are several).
 //
-// The pack (or unpack) phase of a multi-field transpose is the single transpose's list of moves -- one per peer -- whose geometry
-// is the same for every field: only the base pointers differ.  The descriptor (kern::FieldMoveBatch, kernels_batch.h) holds the
-// geometry once per move, with byte offsets in the place of pointers, two tables of the fields' pencils (inputs, outputs) and
-// the workspace; each end of a move is "field f's input", "field f's output" or "the workspace at f * a per-move byte step".
+// The pack (or unpack) phase of a multi-field transpose is the single transpose's list of moves -- one per peer -- and a phase of
+// a multi-field halo update the update's one or two sides; their geometry is the same for every field: only the base pointers
+// differ.  The descriptor (kern::FieldMoveBatch, kernels_batch.h) holds the geometry once per move, with byte offsets in the
+// place of pointers, two tables of the fields' pencils (inputs, outputs; a halo update names the same pencils in both) and the
+// workspace; each end of a move is "field f's input", "field f's output" or "the workspace at f * a per-move byte step".
 //   transpose_fields_kernel<ES,VW,TI,TJ,STREAM,GUARD>
 //                                    fastest source dim != fastest destination dim: the LDS-tiled transposition of
 //                                    kernels_tile.h (transposeTile: XOR-swizzled LDS rows, 16-byte lanes when the tile edges
 //                                    hold whole vectors; transposeTilePadded for 16-byte elements).  Workgroup -> (move, field,
 //                                    plane, tile): one decode per WORKGROUP; tiles are walked along i first, with no XCD or run
 //                                    walk.  GUARD = false when every move of the launch consists of whole tiles.
-//   rows_fieldmoves_kernel<VB,STREAM>  fastest dim contiguous on both sides: the lane layout of rows_fields_kernel
-//                                    (kernels_fields.hip) -- VB = 16 (8, 4, 2) bytes per lane, kRowsUnroll vectors in flight.
-//   generic_fieldmoves_kernel<ES>    element-wise with a grid-stride loop per field: everything else, and the forced case.
+//   rows_fields_kernel<VB,STREAM>    fastest dim contiguous on both sides: the lane layout of rows_kernel (kernels_rows.hip) --
+//                                    each lane moves VB = 16 (8, 4, 2) bytes, kRowsUnroll vectors per lane in flight, lanes along
+//                                    the row; one decode per WORKGROUP, no per-element index math.
+//   generic_fields_kernel<ES>        element-wise with a grid-stride loop per field, lanes along the destination-fast dim: faces
+//                                    one element thick along the fastest memory axis, everything else, and the forced case.
 // Exactly the cells of the moves are read and written: no window, lines, shifted or dense form (the cells between rows belong
 // to the fields' pencils and are not the move's to rewrite), no remote destination.
 // Pure data movement: no MFMA; the bound is HBM (8 TB/s spec, ~6.3 TB/s achievable copy rate).
@@ -80,12 +84,12 @@ __global__ __launch_bounds__(kThreads) void transpose_fields_kernel(const FieldM
 }
 
 // ---------------------------------------------------------------------------------------------
-// rows_fieldmoves_kernel: e[0] = vectors per row, e[1] = rows, e[2] = planes; ss/ds[1], [2] in BYTES.
+// rows_fields_kernel: e[0] = vectors per row, e[1] = rows, e[2] = planes; ss/ds[1], [2] in BYTES.
 // p0 = log2(lanes per row).  A workgroup covers (256 >> p0) * kRowsUnroll rows x (1 << p0) vectors of one field.
 // STREAM: 0 default caching, 1 non-temporal loads and stores.
 // ---------------------------------------------------------------------------------------------
 template <int VB, int STREAM>
-__global__ __launch_bounds__(kThreads) void rows_fieldmoves_kernel(const FieldMoveBatch b) {
+__global__ __launch_bounds__(kThreads) void rows_fields_kernel(const FieldMoveBatch b) {
   using V = Bytes<VB>;
   int mi;
   unsigned int f, lb;
@@ -121,11 +125,11 @@ __global__ __launch_bounds__(kThreads) void rows_fieldmoves_kernel(const FieldMo
 }
 
 // ---------------------------------------------------------------------------------------------
-// generic_fieldmoves_kernel: element-wise, lanes along dim p0 (the destination-fast dim when there is one); extents and strides
+// generic_fields_kernel: element-wise, lanes along dim p0 (the destination-fast dim when there is one); extents and strides
 // in elements; a field's `blocks` workgroups stride over its move.
 // ---------------------------------------------------------------------------------------------
 template <int ES>
-__global__ __launch_bounds__(kThreads) void generic_fieldmoves_kernel(const FieldMoveBatch b) {
+__global__ __launch_bounds__(kThreads) void generic_fields_kernel(const FieldMoveBatch b) {
   using E = Bytes<ES>;
   int mi;
   unsigned int fi, lb;
@@ -179,23 +183,23 @@ void launchFieldMoveBatch(const KernelChoice& k, const FieldMoveBatch& b, unsign
     CD_CHECK_HIP(hipGetLastError());
     return;
   }
-  const bool rows = k.kind == K_ROWS_FIELDMOVES, generic = k.kind == K_GENERIC_FIELDMOVES;
-#define CD_ROWS_FIELDMOVES(VB)                                                \
-  do {                                                                        \
-    if (s == 1) rows_fieldmoves_kernel<VB, 1><<<grid, block, 0, stream>>>(b); \
-    else rows_fieldmoves_kernel<VB, 0><<<grid, block, 0, stream>>>(b);        \
+  const bool rows = k.kind == K_ROWS_FIELDS, generic = k.kind == K_GENERIC_FIELDS;
+#define CD_ROWS_FIELDS(VB)                                                \
+  do {                                                                    \
+    if (s == 1) rows_fields_kernel<VB, 1><<<grid, block, 0, stream>>>(b); \
+    else rows_fields_kernel<VB, 0><<<grid, block, 0, stream>>>(b);        \
   } while (0)
   if (rows && s != 0 && s != 1) CD_INTERNAL_ERROR("no field-move row kernel for this access mode");
-  if (rows && vb == 16) CD_ROWS_FIELDMOVES(16);
-  else if (rows && vb == 8) CD_ROWS_FIELDMOVES(8);
-  else if (rows && vb == 4) CD_ROWS_FIELDMOVES(4);
-  else if (rows && vb == 2) CD_ROWS_FIELDMOVES(2);
-  else if (generic && k.es == 2) generic_fieldmoves_kernel<2><<<grid, block, 0, stream>>>(b);
-  else if (generic && k.es == 4) generic_fieldmoves_kernel<4><<<grid, block, 0, stream>>>(b);
-  else if (generic && k.es == 8) generic_fieldmoves_kernel<8><<<grid, block, 0, stream>>>(b);
-  else if (generic && k.es == 16) generic_fieldmoves_kernel<16><<<grid, block, 0, stream>>>(b);
+  if (rows && vb == 16) CD_ROWS_FIELDS(16);
+  else if (rows && vb == 8) CD_ROWS_FIELDS(8);
+  else if (rows && vb == 4) CD_ROWS_FIELDS(4);
+  else if (rows && vb == 2) CD_ROWS_FIELDS(2);
+  else if (generic && k.es == 2) generic_fields_kernel<2><<<grid, block, 0, stream>>>(b);
+  else if (generic && k.es == 4) generic_fields_kernel<4><<<grid, block, 0, stream>>>(b);
+  else if (generic && k.es == 8) generic_fields_kernel<8><<<grid, block, 0, stream>>>(b);
+  else if (generic && k.es == 16) generic_fields_kernel<16><<<grid, block, 0, stream>>>(b);
   else CD_INTERNAL_ERROR("no field-move kernel for this lane width");
-#undef CD_ROWS_FIELDMOVES
+#undef CD_ROWS_FIELDS
   CD_CHECK_HIP(hipGetLastError());
 }
 

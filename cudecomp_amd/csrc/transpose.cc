@@ -574,13 +574,19 @@ void runHaloFields(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* co
 
   ensureDevice(h);
   const int force = (h->tuning.force_class == MOVE_GENERIC ? 1 : 0) | (h->tuning.force_streaming ? 2 : 0) | (h->tuning.no_streaming ? 4 : 0);
-  launchFieldMoves(plan.pre.data(), (int)plan.pre.size(), inputs, n_fields, work, plan.face_elements, es, stream, force);
+  // the one or two sides of a phase in ONE launch (one_choice): either end of a move in a pencil is field f's, the fields' pieces of
+  // the workspace lie one face apart
+  auto launch = [&](const std::vector<Move3D>& moves) {
+    const std::vector<i64> steps(moves.size(), plan.face_elements);
+    launchFieldMoveList(moves.data(), steps.data(), (int)moves.size(), inputs, inputs, n_fields, work, es, stream, force, nullptr, true);
+  };
+  launch(plan.pre);
   if (plan.kind == HaloPlan::SELF_PERIODIC) return;
   void* bufs[3] = {nullptr, nullptr, work};
   HaloExchange x = haloExchangeOf(plan, bufs, es);
   x.bytes = (i64)n_fields * plan.face_elements * es;
   haloExchange(h, gd, x, backend, stream);
-  launchFieldMoves(plan.post.data(), (int)plan.post.size(), inputs, n_fields, work, plan.face_elements, es, stream, force);
+  launch(plan.post);
 }
 
 // Halo accumulation (cudecompAmdAccumulateHalos*): the plain sequence pack my halos -> exchange -> add what arrived onto my

@@ -382,10 +382,11 @@ cudecompResult_t cudecompExtDescribeMoves(const cudecompExtMove_t* moves, int32_
                                          int32_t mode, cudecompDataType_t dtype, int32_t flags, const uint64_t* dst_base_addresses,
                                          cudecompExtLaunch_t* launches, int32_t max_launches, int32_t* n_launches);
 
-/* Field-moves (csrc/kernels.h launchFieldMoves; kernels_fields.hip): moves[0 .. n - 1], n <= 2, carried out for n_fields (1 .. 32)
- * buffers in ONE launch.  The two buffer numbers of a move are its direction flags: an end in buffer 2 lies in the workspace, at
+/* Field-moves (csrc/kernels.h launchFieldMoveList with one_choice, inputs = outputs = fields and every workspace step
+ * work_field_stride; kernels_field_transpose.hip): moves[0 .. n - 1], n <= 2, carried out for n_fields (1 .. 32) buffers in ONE
+ * launch with ONE kernel choice for both moves.  The two buffer numbers of a move are its direction flags: an end in buffer 2 lies in the workspace, at
  * work + (offset + f * work_field_stride) elements for field f; an end in buffer 0 or 1 lies in field f's own buffer, fields[f] +
- * offset (elements of `es` bytes; peer and row_pitch must be 0 / are refused as launchFieldMoves refuses them).  Destinations
+ * offset (elements of `es` bytes; peer and row_pitch must be 0 / are refused as launchFieldMoveList refuses them).  Destinations
  * must be disjoint from each other and from all sources.  force: bit 0 the element-wise kernel, bit 1 non-temporal access
  * regardless of the size, bit 2 cached access regardless of the size (as for cudecompExtFill3D).  *n_launches (optional): 1, or
  * 0 when every move is empty.
@@ -424,7 +425,7 @@ cudecompResult_t cudecompExtPlanTransposeFields(const cudecompExtGridSpec_t* gri
  *
  * cudecompExtDescribeFieldMoveList answers which launches that call would make, without a device: the same arguments with
  * addresses as integers; at most max_launches records are written, *n_launches is the full count.  kind: csrc/kernels_batch.h
- * KernelKind -- 24 transpose_fields_kernel, 25 rows_fieldmoves_kernel, 26 generic_fieldmoves_kernel; vec: rows and element-wise
+ * KernelKind -- 22 rows_fields_kernel, 23 generic_fields_kernel, 24 transpose_fields_kernel; vec: rows and element-wise
  * bytes per lane, transposes elements per lane; ti, tj: the tile of a transposing launch; access: 0 cached, 1 (rows) / 2
  * (transposes) non-temporal loads and stores; guard: the transposing kernel tests the tile edges; index[j]: the list entry its
  * j-th move is; blocks_per_field: workgroups of all its moves for one field; blocks = n_fields * blocks_per_field. */
@@ -442,7 +443,7 @@ cudecompResult_t cudecompExtDescribeFieldMoveList(const cudecompExtMove_t* moves
                                                   cudecompExtFieldMoveLaunch_t* launches, int32_t max_launches,
                                                   int32_t* n_launches);
 
-/* Data-movement kernel launches this process has made so far through the kernel layer (launchMoves, launchFieldMoves and
+/* Data-movement kernel launches this process has made so far through the kernel layer (launchMoves and
  * launchFieldMoveList; the signal / wait kernels and the copy-engine copies of the transports are not counted -- the chunk copies the
  * one-sided transport makes with the row-copy kernel between ranks that share a GPU go through launchMoves and are).  Tests take
  * the difference around a call. */

@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-/* the most fields one call takes: one 256-byte table of pointers in the kernel arguments (a D3Q27 lattice fits) */
+/* the most fields one call takes: a 256-byte table of pointers in the kernel arguments (a D3Q27 lattice fits) */
 #define CUDECOMP_AMD_MAX_HALO_FIELDS 32
 
 /*

@@ -48,14 +48,17 @@ class _Arena:
         self.init = torch.randint(0, 256, (nbytes,), dtype=torch.uint8, device="cuda", generator=g)
         self.buf = torch.empty_like(self.init)
 
-    def run(self, es, extent, pitch_strides, n_fields, direction, sides, force, offsets, work_offset, expect_rows=None):
+    def run(self, es, extent, pitch_strides, n_fields, direction, sides, force, offsets, work_offset, expect_rows=None, shifts=(0, 0)):
         """`sides` moves of the geometry (extent, pencil strides `pitch_strides`; dense in the workspace) for n_fields fields whose
-        bases lie offsets[f] elements into their regions, the workspace work_offset elements into its own.  Returns the kernel."""
+        bases lie offsets[f] elements into their regions, the workspace work_offset elements into its own.  A geometry PER SIDE: lists
+        of `sides` extents and strides; shifts[s]: elements side s lies further into the pencils.  Returns the kernel."""
         import torch
         dev = self.buf.device
-        dense = (1, int(extent[0]), int(extent[0]) * int(extent[1]))
-        face = int(extent[0]) * int(extent[1]) * int(extent[2])
-        span = _span(extent, pitch_strides)
+        extents = list(extent) if isinstance(extent[0], (tuple, list)) else [extent] * sides
+        strides = list(pitch_strides) if isinstance(pitch_strides[0], (tuple, list)) else [pitch_strides] * sides
+        assert len(extents) == len(strides) == sides
+        face = max(int(e[0]) * int(e[1]) * int(e[2]) for e in extents)  # between the fields' pieces of the workspace
+        span = max(_span(e, st) for e, st in zip(extents, strides)) + max(shifts)
         # a field's region: [side 0 source | side 0 destination | side 1 source | side 1 destination], each `span + 3` apart
         part = span + 3 + (span + 3) % 2  # (even: the 2-byte cases decide their alignment by the fields' offsets alone)
         region = (max(offsets) + 4 * part) * es + SLACK
@@ -74,9 +77,11 @@ class _Arena:
         E, I = expected.view(-1, es), init.view(-1, es)
         base_el = torch.tensor([b // es for b in bases], dtype=torch.int64, device=dev)[:, None]
         f_el = torch.arange(n_fields, dtype=torch.int64, device=dev)[:, None]
-        kp, kd = _cells(extent, pitch_strides, dev)[None, :], _cells(extent, dense, dev)[None, :]
         for s in range(sides):
-            src_pencil, dst_pencil = (2 * s) * part, (2 * s + 1) * part
+            extent, pitch_strides = extents[s], strides[s]
+            dense = (1, int(extent[0]), int(extent[0]) * int(extent[1]))
+            kp, kd = _cells(extent, pitch_strides, dev)[None, :], _cells(extent, dense, dev)[None, :]
+            src_pencil, dst_pencil = (2 * s) * part + shifts[s], (2 * s + 1) * part + shifts[s]
             if direction == FIELD_TO_WORK:
                 m = cd.make_move(extent, pitch_strides, dense, src_off=src_pencil, dst_off=s * slot, src_buf=0, dst_buf=2)
                 src, dst = base_el + src_pencil + kp, work // es + s * slot + f_el * face + kd
@@ -95,7 +100,7 @@ class _Arena:
         n = cd.cudecompExtRunFieldMoves(moves, fields, ptr + work, face, es, force, torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         name = cd.cudecompExtLastKernelName()
-        what = (es, tuple(extent), tuple(pitch_strides), n_fields, direction, sides, force, offsets, work_offset, name)
+        what = (es, extents, strides, n_fields, direction, sides, force, offsets, work_offset, shifts, name)
         assert n == 1 and name == _spell(desc, es), what + (desc,)
         assert desc["blocks"] == n_fields * desc["blocks_per_field"], what + (desc,)
         if not torch.equal(buf, expected):
@@ -158,6 +163,19 @@ def test_kernel_parity_two_byte_lanes_follow_every_field():
         assert name == "rows_fields_kernel<16,0>", (direction, name)
         name, desc = arena.run(2, extent, strides, 9, direction, 2, 0, [0, 2, 4, 6, 8, 0, 3, 4, 6], 2, expect_rows=True)
         assert name == "rows_fields_kernel<2,0>", (direction, name)
+
+
+def test_kernel_parity_two_sides_that_differ():
+    """ONE kernel choice for the launch when the two sides are not alike: the narrower side's lanes (24-byte rows beside 256-byte
+    ones), the element-wise kernel as soon as one side is a face one element thick, 2-byte lanes as soon as one side of 2-byte
+    elements lies at 2 mod 4; three fields, every direction, one launch each, every byte compared"""
+    arena = _Arena(1 << 20)
+    row, short, thin = ((64, 5, 3), (1, 66, 66 * 5 + 6)), ((6, 5, 3), (1, 66, 66 * 5 + 6)), ((1, 9, 7), (1, 13, 13 * 11))
+    for es, (a, b), shifts, kernel in ((4, (row, short), (0, 0), "rows_fields_kernel<8,0>"), (8, (row, thin), (0, 0), "generic_fields_kernel<8>"),
+                                       (2, (row, row), (0, 0), "rows_fields_kernel<16,0>"), (2, (row, row), (2, 1), "rows_fields_kernel<2,0>")):
+        for direction in (FIELD_TO_WORK, WORK_TO_FIELD, FIELD_TO_FIELD):
+            name, _ = arena.run(es, (a[0], b[0]), (a[1], b[1]), 3, direction, 2, 0, [0, 0, 0], 0, shifts=shifts)
+            assert name == kernel, (es, a, b, shifts, direction, name)
 
 
 @pytest.mark.parametrize("es", [2, 4, 8, 16])

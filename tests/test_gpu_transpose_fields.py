@@ -25,7 +25,7 @@ SELF = {"CUDECOMP_TEST_SELF_EXCHANGE": "1"}
 ENGINES = {"CUDECOMP_PEER_COPY_ENGINE": "sdma"}
 SHIM_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "shim")
 SHIM = os.path.join(SHIM_DIR, "libfake_rccl.so")
-K_TRANSPOSE, K_ROWS, K_GENERIC = 24, 25, 26
+K_TRANSPOSE, K_ROWS, K_GENERIC = 24, 22, 23
 
 
 # ---- kernel parity ---------------------------------------------------------------------------------------------------------
@@ -43,8 +43,8 @@ def _spell(d):
     if d["kind"] == K_TRANSPOSE:
         return "transpose_fields_kernel<%d,%d,%d,%d,%d,%s>" % (d["es"], d["vec"], d["ti"], d["tj"], d["access"], "true" if d["guard"] else "false")
     if d["kind"] == K_ROWS:
-        return "rows_fieldmoves_kernel<%d,%d>" % (d["vec"], d["access"])
-    return "generic_fieldmoves_kernel<%d>" % d["es"]
+        return "rows_fields_kernel<%d,%d>" % (d["vec"], d["access"])
+    return "generic_fields_kernel<%d>" % d["es"]
 
 
 class _Arena:
@@ -220,7 +220,7 @@ def test_kernel_parity_rows_and_generic(es):
         extent, st = (1, h, d_), (1, pitch, pitch * (h + 3))
         desc, name = arena.run(es, _three_directions(extent, st, st), 2 + c % 2, (0, 2)[c % 2])
         c += 1
-        assert [d["kind"] for d in desc] == [K_GENERIC] and name == "generic_fieldmoves_kernel<%d>" % es, desc
+        assert [d["kind"] for d in desc] == [K_GENERIC] and name == "generic_fields_kernel<%d>" % es, desc
     desc, name = arena.run(es, _three_directions(*_transposing(3, 50, 2)), 3, 0)
     assert [d["kind"] for d in desc] == [K_GENERIC], desc
     assert kinds == {K_ROWS, K_GENERIC} and {(K_ROWS, 0), (K_ROWS, 1), (K_GENERIC, 0)} <= access, (kinds, access)

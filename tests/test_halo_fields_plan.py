@@ -4,21 +4,25 @@ stateless plan (cudecompExtPlanHaloFields) against the single-field plan over ra
 and a real exchange over gloo on four ranks, and the classifier of the field-move kernels (cudecompExtDescribeFieldMoves)."""
 import ctypes as C
 import itertools
+import json
 import os
 import re
 import shutil
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 from hypothesis import HealthCheck, given, settings
 from hypothesis import strategies as st
 
-import cudecomp_amd as cd
-from tests.mp import run_ranks
-from tests.test_plan_sim import _cells, decompositions, small3
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+import cudecomp_amd as cd  # noqa: E402
+from tests.mp import run_ranks  # noqa: E402
+from tests.test_plan_sim import _cells, decompositions, small3  # noqa: E402
+
 HEADER = "cudecomp_halo_fields.h"
 NAMES = ["cudecompAmdUpdateFieldHalos" + a for a in "XYZ"]
 EXT = ["cudecompExtPlanHaloFields", "cudecompExtRunFieldMoves", "cudecompExtDescribeFieldMoves", "cudecompExtDataLaunchCount"]
@@ -303,3 +307,83 @@ def test_the_documents_name_the_kernels_and_say_what_is_unmeasured():
     assert para and any("unmeasured" in p or "not measured" in p or "nobody has measured" in p.lower() for p in para)
     integration = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert "cudecompAmdUpdateFieldHalos" in integration and "Not covered" in integration
+
+
+# ---- the launch of two sides that DIFFER, pinned -------------------------------------------------------------------------------
+PINS = os.path.join(ROOT, "tests", "golden", "field_launch_pins.json")
+PENCIL = (1, 66, 66 * 11 + 6)  # strides of the sides inside a field's pencil
+ROW, SHORT, THIN, NONE = (64, 5, 3), (6, 5, 3), (1, 9, 7), (0, 5, 3)
+
+
+def _pairs(es):
+    """(name, [(extent, pencil strides, pencil offset) per side]): what the cases above never give one launch"""
+    big = ((32 << 20) // es, 1, 1)
+    return [("lanes differ", [(ROW, PENCIL, 0), (SHORT, PENCIL, 4000)]), ("lanes differ, narrow first", [(SHORT, PENCIL, 0), (ROW, PENCIL, 4000)]),
+            ("rows with a thin face", [(ROW, PENCIL, 0), (THIN, PENCIL, 4000)]), ("thin faces", [(THIN, PENCIL, 0), ((1, 40, 1), PENCIL, 4000)]),
+            ("one side at an odd offset", [(ROW, PENCIL, 0), (ROW, PENCIL, 4001)]), ("one side empty", [(NONE, PENCIL, 0), (ROW, PENCIL, 4000)]),
+            ("both sides empty", [(NONE, PENCIL, 0), (NONE, PENCIL, 4000)]), ("large with small", [(ROW, PENCIL, 0), (big, (1, 0, 0), 4000)]),
+            ("just below large with small", [((big[0] - 1, 1, 1), (1, 0, 0), 0), (ROW, PENCIL, 1 << 26)]),
+            ("one workgroup per plane", [((2, 3, 1 << 25), (1, 5, 17), 0), ((2, 3, 1 << 25), (1, 5, 17), 1 << 30)])]
+
+
+def _pin_cases():
+    """element size x side pair x direction x force, the field count and the workspace stride (the faces' size, or the next odd
+    number above it) drawn with a fixed seed: 480 cases"""
+    rng = np.random.RandomState(2223)
+    for es, direction, force in itertools.product((2, 4, 8, 16), ("field to work", "work to field", "field to field"), (0, 1, 2, 4)):
+        for name, sides in _pairs(es):
+            n, odd = (2, 3, 32)[rng.randint(3)], int(rng.randint(2))
+            faces = [int(np.prod(extent)) for extent, _, _ in sides]
+            stride = max(faces) if not odd else max(faces) + 1 + max(faces) % 2
+            moves = []
+            for s, (extent, strides, off) in enumerate(sides):
+                dense, slot = (1, extent[0], extent[0] * extent[1]), s * (n * stride + 6)
+                if direction == "field to work":
+                    moves.append(cd.make_move(extent, strides, dense, src_off=off, dst_off=slot, src_buf=0, dst_buf=2))
+                elif direction == "work to field":
+                    moves.append(cd.make_move(extent, dense, strides, src_off=slot, dst_off=off, src_buf=2, dst_buf=0))
+                else:
+                    moves.append(cd.make_move(extent, strides, strides, src_off=off, dst_off=off + 2000, src_buf=0, dst_buf=1))
+            key = "es %d, %s, %s, force %d, %d fields, stride %d" % (es, name, direction, force, n, stride)
+            yield key, moves, [(f + 1) << 36 for f in range(n)], stride, es, force
+
+
+def field_launches():
+    table = {}
+    for key, moves, bases, stride, es, force in _pin_cases():
+        try:
+            d = cd.cudecompExtDescribeFieldMoves(moves, bases, 1 << 44, stride, es, force)
+            table[key] = [d[k] for k in ("kind", "vec", "access", "blocks_per_field", "blocks")]
+        except cd.CudecompError as e:
+            table[key] = {"error": e.code}
+    return table
+
+
+def test_launches_of_differing_sides_are_the_pinned_ones():
+    """tests/golden/field_launch_pins.json: [kind, lane bytes, access, workgroups per field, workgroups] (or the error code) of the
+    ONE launch cudecompExtDescribeFieldMoves answers for two sides that differ in lane width, in kernel, in alignment, in size, or
+    of which one or both are empty.  Recorded from the two-sided planner this path had before it moved onto the list planner; a
+    mismatch is a finding about the planner's one-choice mode, not a reason to regenerate (python tests/test_halo_fields_plan.py
+    --regen rewrites the file from whatever library is built)."""
+    with open(PINS) as f:
+        pinned = json.load(f)
+    now = field_launches()
+    assert sorted(now) == sorted(pinned) and len(now) == 480
+    diffs = ["%s: pinned %s, now %s" % (k, pinned[k], now[k]) for k in sorted(now) if now[k] != pinned[k]]
+    assert not diffs, "field launches differ from tests/golden/field_launch_pins.json:\n" + "\n".join(diffs[:40])
+    # a few readable facts of the table
+    rows = {k: v for k, v in pinned.items() if ", force 0," in k or ", force 4," in k}
+    assert all(v[:2] == [22, 8] for k, v in rows.items() if "es 4, lanes differ" in k)
+    assert all(v[:3] == [23, 8, 0] for k, v in rows.items() if "es 8, rows with a thin face" in k)
+    assert all(v[:2] == [22, 2] for k, v in rows.items() if "es 2, one side at an odd offset" in k)
+    assert all(v[0] == -1 for k, v in pinned.items() if "both sides empty" in k)
+    assert all(v[2] == (0 if ", force 4," in k else 1) for k, v in rows.items() if ", large with small" in k)
+    assert all(v == {"error": cd.RESULT_NOT_SUPPORTED} for k, v in rows.items() if "one workgroup per plane" in k and "32 fields" in k)
+    assert all(v[4] == v[3] * 3 == 3 << 26 for k, v in rows.items() if "one workgroup per plane" in k and " 3 fields" in k)
+
+
+if __name__ == "__main__" and "--regen" in sys.argv:
+    with open(PINS, "w") as f:
+        table = field_launches()
+        f.write("{\n" + ",\n".join(" %s: %s" % (json.dumps(k), json.dumps(table[k])) for k in sorted(table)) + "\n}\n")
+    print("wrote", PINS)
