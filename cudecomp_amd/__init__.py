@@ -166,7 +166,7 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtPlanHaloAccumulateClear", "cudecompExtPlanHaloReflect", "cudecompExtReflect3D",
                "cudecompExtPlanHaloFold", "cudecompExtFold3D", "cudecompExtPlanHaloFields", "cudecompExtRunFieldMoves",
                "cudecompExtDescribeFieldMoves", "cudecompExtDataLaunchCount", "cudecompExtPlanTransposeFields",
-               "cudecompExtRunFieldMoveList", "cudecompExtDescribeFieldMoveList"]
+               "cudecompExtRunFieldMoveList", "cudecompExtDescribeFieldMoveList", "cudecompExtDescribeResidency"]
 # include/cudecomp_amd.h: extensions of the API a solver may use
 AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
 # include/cudecomp_amd_fill.h: halo fill
@@ -314,6 +314,7 @@ def lib():
                                           C.POINTER(i64), pi32]
         L.cudecompExtDescribeMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, i32, i32, i32,
                                                C.POINTER(C.c_uint64), C.POINTER(ExtLaunch), i32, pi32]
+        L.cudecompExtDescribeResidency.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, i32, pi32, i32, pi32]
         _lib = L
     return _lib
 
@@ -845,6 +846,16 @@ def cudecompExtDescribeMoves(moves, buf_addresses, es, mode=MOVES_COPY, dtype=0,
         d["index"] = [int(x) for x in l.index[:l.n]]
         res.append(d)
     return res
+
+
+def cudecompExtDescribeResidency(moves, buf_addresses, es, flags=0):
+    """The dynamic LDS (bytes) each launch cudecompExtDescribeMoves lists for a copy list would ask for (no launch, no GPU)."""
+    b = (C.c_uint64 * 3)(*[int(p or 0) for p in buf_addresses])
+    cap = len(moves) + 1
+    out, n = (C.c_int32 * cap)(), C.c_int32(-1)
+    _check(lib().cudecompExtDescribeResidency(_move_list(moves), len(moves), b, es, int(flags), out, cap, C.byref(n)),
+           "cudecompExtDescribeResidency")
+    return [int(x) for x in out[:n.value]]
 
 
 def cudecompExtRunFieldMoves(moves, fields, work, work_field_stride, es, force=0, stream=None):

@@ -1177,6 +1177,27 @@ cudecompResult_t cudecompExtDescribeMoves(const cudecompExtMove_t* moves, int32_
   return CUDECOMP_RESULT_SUCCESS;
 }
 
+cudecompResult_t cudecompExtDescribeResidency(const cudecompExtMove_t* moves, int32_t n, const uint64_t buf_addresses[3], int32_t es,
+                                             int32_t flags, int32_t* pad_bytes, int32_t max_launches, int32_t* n_launches) {
+  try {
+    if (!buf_addresses || !n_launches || max_launches < 0 || (max_launches > 0 && !pad_bytes)) CD_INVALID_USAGE("bad argument");
+    ArithType arith;
+    const std::vector<Move3D> list = importMoves(moves, n, es, 0, (cudecompDataType_t)0, &arith);
+    const KernelTuning t = tuningOfFlags(flags);
+    void* bufs[3];
+    for (int i = 0; i < 3; ++i) bufs[i] = reinterpret_cast<void*>(buf_addresses[i]);
+    const std::vector<Launch> ls = planLaunches(list.data(), n, bufs, es, &t, nullptr, arith);
+    *n_launches = (int32_t)ls.size();
+    if ((int32_t)ls.size() > max_launches) CD_INVALID_USAGE("more launches than the output array holds");
+    for (size_t i = 0; i < ls.size(); ++i) pad_bytes[i] = residencyPadBytes(ls[i].k, ls[i].b);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
 cudecompResult_t cudecompExtRunMoves(const cudecompExtMove_t* moves, int32_t n, void* const bufs[3], int32_t es, int32_t mode,
                                     cudecompDataType_t dtype, const void* fill_value, int32_t flags, void* const* dst_bases,
                                     hipStream_t stream, int32_t launches[3], int64_t elements[3], int32_t* n_launches) {

@@ -644,6 +644,29 @@ const KernelTuning kDefaultTuning;
 
 }  // namespace
 
+// Residency of the large far-strided transposes: fewer workgroups per CU than their tiles leave room for.  The workgroups in
+// flight then hold fewer, shorter-lived fronts on the far-strided rows (the reading of the run walk, offerRunWalk).  Measured on
+// the 8-GiB cycles, settings alternating inside one process on one set of buffers and as whole bench runs against the parent
+// commit (profiles/transpose_residency.json):
+//   fp64 forward hops (64 x 64 tile, 32 KiB, run walk over tiles): 3 per CU instead of 5, 2.83-2.84 -> 2.82 ms; 4 per CU
+//     changes nothing, 2 per CU costs 0.14 ms
+//   fp64 inverse hops (64 x 128 tile, 64 KiB): 1 per CU instead of 2, 2.67 -> 2.62-2.63 ms.  (The same tile staged through 32
+//     KiB in two halves, which would allow 3 and 4 per CU, measured 0.03 / 0.07 / 0.09 ms per hop SLOWER at 2 / 3 / 4 per CU.)
+//   complex128 forward hops (32 x 32 tile, padded rows: 16.5 KiB, run walk): 4 per CU instead of 8, 2.86-2.87 -> 2.75 ms;
+//     3, 5 and 6 per CU lie between
+//   fp32 forward hops (64 x 128 tile): 3 and 4 per CU within the noise of 5; they launch as before
+// The rule reads only what the launch knows: the kernel choice, and for the forward hops that EVERY move of the launch walks in
+// runs of tiles along j.
+int residencyPadBytes(const KernelChoice& k, const Batch& b) {
+  if (k.kind != K_TRANSPOSE || k.access != 2) return 0;
+  if (k.es == 8 && k.vec == 2 && k.ti == 64 && k.tj == 128) return 32 << 10;  // far-strided source: 64 + 32 KiB, one per CU
+  const bool f64 = k.es == 8 && k.vec == 2 && k.ti == 64 && k.tj == 64, c128 = k.es == 16 && k.vec == 1 && k.ti == 32 && k.tj == 32;
+  if (!f64 && !c128) return 0;
+  for (int i = 0; i < b.n; ++i)  // far-strided destination, runs of tiles (offerRunWalk)
+    if (b.p0[i] <= 1 || !(b.p1[i] & kWalkJFirst) || (b.p1[i] & kWalkRunOverPlanes)) return 0;
+  return f64 ? 16 << 10 : 23 << 10;  // 32 + 16 KiB: three per CU; 16.5 + 23 KiB: four
+}
+
 const char* lastKernelName() { return g_last_kernel; }
 long long dataLaunchCount() { return g_data_launches; }
 

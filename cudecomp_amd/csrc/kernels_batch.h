@@ -150,6 +150,12 @@ struct KernelChoice {
 };
 constexpr int kLinesUnitBytes = 128;  // alignment unit of the lines and row-lines kernels
 
+// Residency of the LDS-tiled transposes: the dynamic LDS (bytes) a launch asks for on top of its kernel's static tile.  No kernel
+// references that memory; it only limits how many workgroups share a CU (160 KiB of LDS).  Pure host code (csrc/kernels.cc, where
+// the rule and its measurements are); 0 for everything but the streaming transposes with a far-strided side it names.
+int residencyPadBytes(const KernelChoice& k, const kern::Batch& b);
+inline int residencyPadBytes(const KernelChoice&, const kern::FieldMoveBatch&) { return 0; }  // lists of field-moves: never
+
 // the STREAM template argument (kernels_dev.h, storePolicyOf) with which a kind of kernel serves an access mode
 inline int streamArgOf(KernelKind kind, int access) {
   if (kind == K_TRANSPOSE || kind == K_ROWS_ADD) return access;

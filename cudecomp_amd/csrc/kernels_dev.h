@@ -128,10 +128,11 @@ template <int STREAM> constexpr int storePolicyOf() {
 template <int STREAM> constexpr bool loadsStream() { return STREAM >= 1 && STREAM <= 3; }
 
 // Host side of the LDS-tiled kernels: launch KERNEL<ES, VW, TI, TJ, ...> and return true if that is the element size, lane width
-// and tile the record `k` asks for.  (Window, lines and row lines exist in the same five shapes.)
+// and tile the record `k` asks for.  (Window, lines and row lines exist in the same five shapes.)  The dynamic LDS of the launch
+// is residencyPadBytes (kernels_batch.h): memory no kernel references, it only sets how many workgroups share a CU.
 #define CD_TILED_SHAPE(KERNEL, ES, VW, TI, TJ, ...)                      \
   if (k.es == ES && k.vec == VW && k.ti == TI && k.tj == TJ)             \
-    return KERNEL<ES, VW, TI, TJ, __VA_ARGS__><<<dim3(blocks), dim3(kThreads), 0, stream>>>(b), true;
+    return KERNEL<ES, VW, TI, TJ, __VA_ARGS__><<<dim3(blocks), dim3(kThreads), residencyPadBytes(k, b), stream>>>(b), true;
 #define CD_WINDOW_SHAPES(KERNEL, ...)                     \
   CD_TILED_SHAPE(KERNEL, 4, 4, 64, 128, __VA_ARGS__)      \
   CD_TILED_SHAPE(KERNEL, 4, 1, 64, 128, __VA_ARGS__)      \

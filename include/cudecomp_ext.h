@@ -381,6 +381,12 @@ cudecompResult_t cudecompExtRunMoves(const cudecompExtMove_t* moves, int32_t n, 
 cudecompResult_t cudecompExtDescribeMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t buf_addresses[3], int32_t es,
                                          int32_t mode, cudecompDataType_t dtype, int32_t flags, const uint64_t* dst_base_addresses,
                                          cudecompExtLaunch_t* launches, int32_t max_launches, int32_t* n_launches);
+/* Residency of the same launches (csrc/kernels.cc residencyPadBytes), without a device: pad_bytes[i] = the dynamic LDS launch i of
+ * cudecompExtDescribeMoves asks for on top of its kernel's static tile -- memory no kernel references, it only sets how many
+ * workgroups share a CU; 0 for everything but the streaming transposes with a far-strided side that the rule names.  Copy lists (mode 0) without
+ * destination bases; the other arguments and result codes as for cudecompExtDescribeMoves. */
+cudecompResult_t cudecompExtDescribeResidency(const cudecompExtMove_t* moves, int32_t n, const uint64_t buf_addresses[3], int32_t es,
+                                             int32_t flags, int32_t* pad_bytes, int32_t max_launches, int32_t* n_launches);
 
 /* Field-moves (csrc/kernels.h launchFieldMoveList with one_choice, inputs = outputs = fields and every workspace step
  * work_field_stride; kernels_field_transpose.hip): moves[0 .. n - 1], n <= 2, carried out for n_fields (1 .. 32) buffers in ONE
