@@ -10,7 +10,9 @@ per dim the cells the periodic update writes, as many cells read, the same two s
 --fold / --fold-clear, cudecompAmdFoldHalosX (cudecomp_halo_fold.h), the reflection's transpose, on the same non-periodic single rank
 with parity -1, centering 0 and clear 0 / 1: the reflection's two sibling moves the other way round, the destinations read as well
 (6 * face bytes), the ghost cells zeroed as well (8 * face bytes) and, with --fields N, cudecompAmdUpdateFieldHalosX
-(cudecomp_halo_fields.h) on N such pencils, periodic: the update's two wrap copies for all N in one launch (N * 4 * face bytes).
+(cudecomp_halo_fields.h) on N such pencils, periodic: the update's two wrap copies for all N in one launch (N * 4 * face bytes) and,
+with --accumulate --fields N / --accumulate-clear --fields N, cudecompAmdAccumulateFieldHalosX (cudecomp_halo_accumulate_fields.h) with
+clear 0 / 1 on N such pencils: the two wrap additions for all N in one launch (N * 6 / N * 8 * face bytes).
 Per dim: `--reps` repetitions of `--calls` back-to-back calls each, ms per call of every repetition, their
 min / median / max, and GB/s of the median against the algorithmic bytes (update: 2 faces read + written,
 4 * face bytes; accumulation: 2 faces read, 2 destinations read and written, 6 * face bytes; fill: 2 halos written, 2 * face
@@ -65,6 +67,9 @@ def main():
     ap.add_argument("--fields", type=int, default=0, metavar="N",
                     help="also time cudecompAmdUpdateFieldHalosX on N pencils (periodic; one launch for all of them), after the other "
                          "passes, and compare every field on the device with a clone updated by single calls")
+    ap.add_argument("--accumulate", action="store_true",
+                    help="with --fields N: also time cudecompAmdAccumulateFieldHalosX (clear 0) on the N pencils and compare every field "
+                         "on the device with a clone accumulated by single calls; with --accumulate-clear --fields N: the same with clear 1")
     ap.add_argument("--gdims", type=int, nargs=3, default=[2048, 1024, 256], metavar="N",
                     help="the pencil (default: config 5's per-rank X pencil; 64 64 64: a pencil on which fixed cost dominates)")
     ap.add_argument("--json", metavar="FILE", default=None, help="also write the result line to FILE")
@@ -209,6 +214,33 @@ def main():
             differ += int(torch.count_nonzero(t.view(torch.int64) != c.view(torch.int64)))
         extra["n_fields"] = n
         extra["field_cells_that_differ_from_single_calls"] = differ
+        # the accumulation of the N pencils in one call; the figure to hold against is N times the single call's median of the same dim
+        for clear, wanted in ((0, a.accumulate), (1, a.accumulate_clear)):
+            if not wanted:
+                continue
+            name, single = ("accumulate_clear", cd.cudecompAccumulateAndClearHalos) if clear else ("accumulate", cd.cudecompAccumulateHalos)
+            for t in fields:
+                t.normal_()
+            for dim in range(3):
+                rec = res["dim%d" % dim]
+                ms = _time(lambda: cd.cudecompAccumulateFieldHalos(0, h, gd, ptrs, fwork, cd.DOUBLE, halo, (1, 1, 1), dim, None, clear, st),
+                           a.reps, a.calls)
+                rec[name + "_fields"] = _record(ms, n * (8 if clear else 6) * faces[dim] * 8)
+                rec[name + "_fields_kernel"] = cd.cudecompExtLastKernelName()
+                rec[name + "_fields_over_n_singles"] = round(rec[name + "_fields"]["median_ms"] / (n * rec[name]["median_ms"]), 3)
+            # after the timing: fresh payloads, dims 2, 1, 0 by the fields call against single calls on clones, on the device
+            differ = 0
+            for t in fields:
+                t.normal_()
+            clones = [t.clone() for t in fields]
+            for dim in (2, 1, 0):
+                cd.cudecompAccumulateFieldHalos(0, h, gd, ptrs, fwork, cd.DOUBLE, halo, (1, 1, 1), dim, None, clear, st)
+                for c in clones:
+                    single(0, h, gd, c.data_ptr(), work, cd.DOUBLE, halo, (1, 1, 1), dim, stream=st)
+            torch.cuda.synchronize()
+            for t, c in zip(fields, clones):
+                differ += int(torch.count_nonzero(t.view(torch.int64) != c.view(torch.int64)))
+            extra[name + "_field_cells_that_differ_from_single_calls"] = differ
         cd.cudecompFree(h, gd, fwork)
     cd.cudecompFree(h, gd, work)
     cd.cudecompGridDescDestroy(h, gd)
@@ -218,7 +250,10 @@ def main():
                                            + (" and reflection (non-periodic, odd mirror, centering 0)" if a.reflect else "")
                                            + (" and fold (non-periodic, parity -1, centering 0)" if a.fold else "")
                                            + (" and fold with clear" if a.fold_clear else "")
-                                           + (" and the update of %d pencils in one call" % a.fields if a.fields else ""), a.reps, a.calls)),
+                                           + (" and the update of %d pencils in one call" % a.fields if a.fields else "")
+                                           + (" and their accumulation in one call" if a.fields and a.accumulate else "")
+                                           + (" and their accumulate-and-clear in one call" if a.fields and a.accumulate_clear else ""),
+                                           a.reps, a.calls)),
                             "device": torch.cuda.get_device_name(0), "result": res}, **extra))
     print(line)
     if a.json:
@@ -230,6 +265,10 @@ def main():
                  % (extra["ghost_cells_not_zero_after_accumulate_clear"], extra["interior_sum_after_accumulate_clear"], extra["cells"]))
     if extra.get("field_cells_that_differ_from_single_calls"):
         sys.exit("halo_bench.py: after the fields call along 0, 1, 2 %d cells differ from single calls on clones" % extra["field_cells_that_differ_from_single_calls"])
+    for name in ("accumulate", "accumulate_clear"):
+        if extra.get(name + "_field_cells_that_differ_from_single_calls"):
+            sys.exit("halo_bench.py: after the %s fields call along 2, 1, 0 %d cells differ from single calls on clones"
+                     % (name, extra[name + "_field_cells_that_differ_from_single_calls"]))
     for name in ("fold", "fold_clear"):
         if extra.get("interior_cells_with_another_count_after_" + name) or extra.get("ghost_cells_not_zero_after_" + name):
             sys.exit("halo_bench.py: after folding a pencil of ones along 2, 1, 0 (%s pass) %d interior cells do not hold their count and %d "

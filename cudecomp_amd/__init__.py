@@ -166,7 +166,8 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtPlanHaloAccumulateClear", "cudecompExtPlanHaloReflect", "cudecompExtReflect3D",
                "cudecompExtPlanHaloFold", "cudecompExtFold3D", "cudecompExtPlanHaloFields", "cudecompExtRunFieldMoves",
                "cudecompExtDescribeFieldMoves", "cudecompExtDataLaunchCount", "cudecompExtPlanTransposeFields",
-               "cudecompExtRunFieldMoveList", "cudecompExtDescribeFieldMoveList", "cudecompExtDescribeResidency"]
+               "cudecompExtRunFieldMoveList", "cudecompExtDescribeFieldMoveList", "cudecompExtDescribeResidency",
+               "cudecompExtPlanHaloAccumulateFields", "cudecompExtRunFieldMovesOp", "cudecompExtDescribeFieldMovesOp"]
 # include/cudecomp_amd.h: extensions of the API a solver may use
 AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
 # include/cudecomp_amd_fill.h: halo fill
@@ -181,6 +182,10 @@ AMD_FOLD_SYMBOLS = ["cudecompAmdFoldHalosX", "cudecompAmdFoldHalosY", "cudecompA
 # include/cudecomp_halo_fields.h: multi-field halo updates (several pencils in one exchange)
 AMD_FIELDS_SYMBOLS = ["cudecompAmdUpdateFieldHalosX", "cudecompAmdUpdateFieldHalosY", "cudecompAmdUpdateFieldHalosZ"]
 MAX_HALO_FIELDS = 32  # CUDECOMP_AMD_MAX_HALO_FIELDS
+# include/cudecomp_halo_accumulate_fields.h: multi-field halo accumulation (several pencils in one exchange)
+AMD_ACCUMULATE_FIELDS_SYMBOLS = ["cudecompAmdAccumulateFieldHalosX", "cudecompAmdAccumulateFieldHalosY",
+                                 "cudecompAmdAccumulateFieldHalosZ"]
+MAX_HALO_ACCUMULATE_FIELDS = 32  # CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS
 # include/cudecomp_transpose_fields.h: multi-field transposes (several pencils in one exchange)
 TRANSPOSE_FIELDS_SYMBOLS = ["cudecompAmdTransposeFieldsXToY", "cudecompAmdTransposeFieldsYToZ", "cudecompAmdTransposeFieldsZToY",
                             "cudecompAmdTransposeFieldsYToX"]
@@ -261,6 +266,13 @@ def lib():
         L.cudecompExtDescribeFieldMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, C.c_uint64, i64, i32, i32,
                                                     C.POINTER(i64)]
         L.cudecompExtDataLaunchCount.argtypes = [C.POINTER(i64)]
+        for name in AMD_ACCUMULATE_FIELDS_SYMBOLS:  # (the multi-field update's arguments with `clear` before the stream)
+            getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, vp]
+        L.cudecompExtPlanHaloAccumulateFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32,
+                                                          i32, C.POINTER(ExtHaloFieldsPlan)]
+        L.cudecompExtRunFieldMovesOp.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(vp), i32, vp, i64, i32, i32, i32, i32, vp, pi32]
+        L.cudecompExtDescribeFieldMovesOp.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, C.c_uint64, i64, i32, i32,
+                                                      i32, i32, C.POINTER(i64)]
         for name in TRANSPOSE_FIELDS_SYMBOLS:  # (the transpose's arguments with the two lists and their length in the place of `input`, `output`)
             getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), i32, vp, i32, pi32, pi32, pi32, pi32, vp]
         L.cudecompExtPlanTransposeFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, pi32, pi32, pi32, C.c_bool, i32, i32, i32,
@@ -514,6 +526,17 @@ def cudecompUpdateFieldHalos(axis, handle, gd, ptrs, work, dtype, halo_extents, 
                                 dim, _i3(padding), stream), name)
 
 
+def cudecompAccumulateFieldHalos(axis, handle, gd, ptrs, work, dtype, halo_extents, halo_periods, dim, padding=None, clear=False,
+                                 stream=None):
+    """cudecompAmdAccumulateFieldHalos{X,Y,Z} (cudecomp_halo_accumulate_fields.h): the halo accumulation along `dim` of every pencil
+    in `ptrs` (device pointers) with one pack launch, one exchange and one addition launch; with `clear` the ghost cells that were
+    read hold zero bytes afterwards; `work` holds len(ptrs) single workspaces."""
+    name = "cudecompAmdAccumulateFieldHalos" + "XYZ"[axis]
+    arr = None if ptrs is None else (C.c_void_p * max(1, len(ptrs)))(*[p or None for p in ptrs])
+    _check(getattr(lib(), name)(handle, gd, arr, 0 if ptrs is None else len(ptrs), work, dtype, _i3(halo_extents), _b3(halo_periods),
+                                dim, _i3(padding), int(clear), stream), name)
+
+
 def cudecompTransposeFields(op, handle, gd, inputs, outputs, work, dtype, in_halo=None, out_halo=None, in_pad=None, out_pad=None,
                             stream=None):
     """cudecompAmdTransposeFields{XToY,YToZ,ZToY,YToX} (cudecomp_transpose_fields.h): op in OPS; the transpose of every pencil in
@@ -641,6 +664,17 @@ def cudecompExtPlanHaloFields(grid, rank, axis, halo_extents, halo_periods, dim,
     p = ExtHaloFieldsPlan()
     _check(lib().cudecompExtPlanHaloFields(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding),
                                            int(n_fields), int(force_packed), C.byref(p)), "cudecompExtPlanHaloFields")
+    return p
+
+
+def cudecompExtPlanHaloAccumulateFields(grid, rank, axis, halo_extents, halo_periods, dim, padding=None, n_fields=1, clear=False,
+                                        self_exchange=False):
+    """Stateless planner of cudecompAmdAccumulateFieldHalos*: the moves of field 0, the slot layout and the offsets, with the flag
+    bits of the single accumulation plans in `reserved` (cudecomp_ext.h)."""
+    p = ExtHaloFieldsPlan()
+    _check(lib().cudecompExtPlanHaloAccumulateFields(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding),
+                                                     int(n_fields), int(clear), int(self_exchange), C.byref(p)),
+           "cudecompExtPlanHaloAccumulateFields")
     return p
 
 
@@ -876,6 +910,27 @@ def cudecompExtDescribeFieldMoves(moves, field_addresses, work_address, work_fie
     out = (C.c_int64 * 5)()
     _check(lib().cudecompExtDescribeFieldMoves(_move_list(moves), len(moves), f, len(field_addresses), int(work_address or 0),
                                                int(work_field_stride), es, int(force), out), "cudecompExtDescribeFieldMoves")
+    return dict(zip(("kind", "vec", "access", "blocks_per_field", "blocks"), [int(x) for x in out]))
+
+
+def cudecompExtRunFieldMovesOp(moves, fields, work, work_field_stride, es, mode, dtype, force=0, stream=None):
+    """cudecompExtRunFieldMoves with an operation: mode 0 copy, 1 add, 3 take, 4 add and take (the values of cudecompExtRunMoves);
+    `dtype` names the arithmetic of the additions.  Returns the number of launches (0 or 1)."""
+    f = (C.c_void_p * max(1, len(fields)))(*[p or None for p in fields])
+    total = C.c_int32(-1)
+    _check(lib().cudecompExtRunFieldMovesOp(_move_list(moves), len(moves), f, len(fields), work or None, int(work_field_stride), es,
+                                            int(force), int(mode), int(dtype), stream, C.byref(total)), "cudecompExtRunFieldMovesOp")
+    return total.value
+
+
+def cudecompExtDescribeFieldMovesOp(moves, field_addresses, work_address, work_field_stride, es, mode, dtype, force=0):
+    """How cudecompExtRunFieldMovesOp would run (no launch, no GPU): a dict of kind (22 / 23 copies, 25 / 26 additions, 27 / 28
+    takes, 29 / 30 additions that take; -1 nothing), lane bytes, access mode, workgroups per field and workgroups in all."""
+    f = (C.c_uint64 * max(1, len(field_addresses)))(*[int(p) for p in field_addresses])
+    out = (C.c_int64 * 5)()
+    _check(lib().cudecompExtDescribeFieldMovesOp(_move_list(moves), len(moves), f, len(field_addresses), int(work_address or 0),
+                                                 int(work_field_stride), es, int(force), int(mode), int(dtype), out),
+           "cudecompExtDescribeFieldMovesOp")
     return dict(zip(("kind", "vec", "access", "blocks_per_field", "blocks"), [int(x) for x in out]))
 
 

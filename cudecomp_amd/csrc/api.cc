@@ -628,6 +628,7 @@ cudecompResult_t cudecompGridDescCreateVersioned(cudecompHandle_t handle, cudeco
     gd->halo_accumulate_clear_plans.clear();
     gd->halo_reflect_plans.clear();
     gd->halo_fold_plans.clear();
+    gd->halo_accumulate_fields_plans.clear();
     perfReset(gd);  // autotuning trials are not part of the user's performance report
 
     *grid_desc_out = gd;
@@ -1009,6 +1010,47 @@ static cudecompResult_t haloFieldsEntry(int axis, cudecompHandle_t handle, cudec
 CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosX, 0)
 CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosY, 1)
 CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosZ, 2)
+
+// cudecomp_halo_accumulate_fields.h: the accumulation of several pencils with one exchange.  The checks of haloEntry, in its order,
+// with `clear` after halo_extents (also when every halo is zero) and the list of fields checked where the accumulation checks
+// `input`; all of it on the host, before anything is launched.
+static cudecompResult_t haloAccumulateFieldsEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const inputs[],
+                                                  int32_t n_fields, void* work, cudecompDataType_t dtype, const int32_t halo_extents[],
+                                                  const bool halo_periods[], int32_t dim, const int32_t padding[], int32_t clear,
+                                                  hipStream_t stream) {
+  try {
+    checkHandle(handle);
+    checkGridDesc(handle, grid_desc);
+    checkDataType(dtype);
+    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
+    if (clear != 0 && clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
+    if (halo_extents[0] == 0 && halo_extents[1] == 0 && halo_extents[2] == 0) return CUDECOMP_RESULT_SUCCESS;
+    if (!inputs) CD_INVALID_USAGE("inputs argument cannot be null");
+    if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS) CD_INVALID_USAGE("n_fields argument out of range");
+    for (int32_t i = 0; i < n_fields; ++i) {
+      if (!inputs[i]) CD_INVALID_USAGE("inputs argument cannot hold a null entry");
+      for (int32_t j = 0; j < i; ++j)
+        if (inputs[j] == inputs[i]) CD_INVALID_USAGE("inputs argument cannot hold the same field twice");
+    }
+    if (!work) CD_INVALID_USAGE("work argument cannot be null");
+    if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
+    runHaloAccumulateFields(handle, grid_desc, axis, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, padding, clear != 0,
+                            stream);
+  }
+  CD_API_CATCH()
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+#define CD_DEFINE_HALO_ACCUMULATE_FIELDS(NAME, AXIS)                                                                           \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const inputs[], int32_t n_fields,         \
+                        void* work, cudecompDataType_t dtype, const int32_t halo_extents[], const bool halo_periods[],         \
+                        int32_t dim, const int32_t padding[], int32_t clear, hipStream_t stream) {                             \
+    return haloAccumulateFieldsEntry(AXIS, handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim,  \
+                                     padding, clear, stream);                                                                  \
+  }
+CD_DEFINE_HALO_ACCUMULATE_FIELDS(cudecompAmdAccumulateFieldHalosX, 0)
+CD_DEFINE_HALO_ACCUMULATE_FIELDS(cudecompAmdAccumulateFieldHalosY, 1)
+CD_DEFINE_HALO_ACCUMULATE_FIELDS(cudecompAmdAccumulateFieldHalosZ, 2)
 
 // cudecomp_transpose_fields.h: the transpose of several pencils with one exchange.  The checks of transposeEntry, in its order,
 // with the lists checked where the transpose checks `input` and `output`; all of it on the host, before anything is launched.

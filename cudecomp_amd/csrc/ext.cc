@@ -7,6 +7,7 @@
 
 #include "cudecomp_ext.h"
 #include "cudecomp_halo_fields.h"
+#include "cudecomp_halo_accumulate_fields.h"
 #include "cudecomp_transpose_fields.h"
 #include "errors.h"
 #include "internal.h"
@@ -978,6 +979,110 @@ cudecompResult_t cudecompExtPlanHaloFields(const cudecompExtGridSpec_t* grid, in
     out->n_post = (int32_t)p.post.size();
     for (size_t i = 0; i < p.pre.size(); ++i) exportMove(p.pre[i], &out->pre[i]);
     for (size_t i = 0; i < p.post.size(); ++i) exportMove(p.post[i], &out->post[i]);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtPlanHaloAccumulateFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
+                                                     const bool periods[], int32_t dim, const int32_t pad[], int32_t n_fields,
+                                                     int32_t clear, int32_t self_exchange, cudecompExtHaloFieldsPlan_t* out) {
+  try {
+    const GridShape g = shapeFromSpec(grid);
+    if (!out || !halo) CD_INVALID_USAGE("null argument");
+    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
+    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
+    if (clear != 0 && clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
+    const int32_t zero[3] = {0, 0, 0};
+    const bool none[3] = {false, false, false};
+    const HaloFieldsPlan fp = buildHaloAccumulateFieldsPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero,
+                                                            n_fields, clear != 0, self_exchange != 0);
+    cudecompExtHaloPlan_t single;  // (the flags of the single plans: cudecompExtHaloPlan_t::reserved)
+    exportHaloPlan(fp.base, &single);
+    std::memset(out, 0, sizeof(*out));
+    out->kind = single.kind;
+    out->comm_axis = single.comm_axis;
+    out->n_fields = fp.n_fields;
+    out->reserved = single.reserved;
+    out->face_elements = single.face_elements;
+    out->slot_elements = fp.slot_elements;
+    for (int i = 0; i < 2; ++i) {
+      out->neighbor[i] = single.neighbor[i];
+      out->send_off[i] = single.send_off[i];
+      out->recv_off[i] = single.recv_off[i];
+      out->pre[i] = single.pre[i];
+      out->post[i] = single.post[i];
+    }
+    out->n_pre = single.n_pre;
+    out->n_post = single.n_post;
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+// the operation of cudecompExtRunFieldMovesOp / cudecompExtDescribeFieldMovesOp onto an imported list; *arith as importMoves sets it
+static void applyFieldMoveMode(std::vector<Move3D>& list, int32_t mode, cudecompDataType_t dtype, int32_t es, ArithType* arith) {
+  if (mode != 0 && mode != 1 && mode != 3 && mode != 4) CD_INVALID_USAGE("mode must be 0 (copy), 1 (add), 3 (take) or 4 (add and take)");
+  *arith = ARITH_NONE;
+  if (mode == 1 || mode == 4) {
+    if (elementSize(dtype) != es) CD_INVALID_USAGE("element size does not match the data type of the arithmetic");
+    *arith = arithOf(dtype);
+  }
+  for (Move3D& m : list) {
+    m.add = mode == 1 || mode == 4;
+    m.take = mode == 3 || mode == 4;
+  }
+}
+
+cudecompResult_t cudecompExtRunFieldMovesOp(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
+                                           void* work, int64_t work_field_stride, int32_t es, int32_t force, int32_t mode,
+                                           cudecompDataType_t dtype, hipStream_t stream, int32_t* n_launches) {
+  try {
+    if (!fields) CD_INVALID_USAGE("null argument");
+    std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS, es);
+    ArithType arith;
+    applyFieldMoveMode(list, mode, dtype, es, &arith);
+    const std::vector<i64> steps(list.size(), work_field_stride);
+    KernelStats st;
+    launchFieldMoveList(list.data(), steps.data(), n, fields, fields, n_fields, work, es, stream, force, &st, true, arith);
+    if (n_launches) {
+      *n_launches = 0;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c) *n_launches += st.launches[c];
+    }
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtDescribeFieldMovesOp(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
+                                                int32_t n_fields, uint64_t work_address, int64_t work_field_stride, int32_t es,
+                                                int32_t force, int32_t mode, cudecompDataType_t dtype, int64_t out[5]) {
+  try {
+    if (!field_addresses || !out) CD_INVALID_USAGE("null argument");
+    std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS, es);
+    ArithType arith;
+    applyFieldMoveMode(list, mode, dtype, es, &arith);
+    const std::vector<i64> steps(list.size(), work_field_stride);
+    std::vector<void*> fields(n_fields);
+    for (int32_t f = 0; f < n_fields; ++f) fields[f] = reinterpret_cast<void*>(field_addresses[f]);
+    const std::vector<FieldMoveLaunch> ls = planFieldMoveLaunches(list.data(), steps.data(), n, fields.data(), fields.data(), n_fields,
+                                                                  reinterpret_cast<void*>(work_address), es, force, true, arith);
+    const FieldMoveLaunch none{};  // (every move is empty: nothing is launched)
+    const FieldMoveLaunch& l = ls.empty() ? none : ls[0];  // (one choice, at most two moves: never a second launch)
+    out[0] = ls.empty() ? -1 : (int64_t)l.k.kind;
+    out[1] = l.k.vec;
+    out[2] = l.k.access;
+    out[3] = l.blocks_per_field;
+    out[4] = l.blocks;
   } catch (const Error& e) {
     return fail(e);
   } catch (...) {

@@ -17,6 +17,7 @@
 #include "cudecomp_amd_reflect.h"
 #include "cudecomp_halo_fold.h"
 #include "cudecomp_halo_fields.h"
+#include "cudecomp_halo_accumulate_fields.h"
 #include "cudecomp_transpose_fields.h"
 #include "decomp.h"
 #include "errors.h"
@@ -148,6 +149,8 @@ struct cudecompGridDesc {
   std::map<std::tuple<HaloKey, int, bool, bool>, cudecomp::HaloPlan> halo_fold_plans;
   // cudecompAmdUpdateFieldHalos* with two fields or more: the same key plus n_fields
   std::map<std::tuple<HaloKey, int>, cudecomp::HaloFieldsPlan> halo_fields_plans;
+  // cudecompAmdAccumulateFieldHalos*: the key, the number of fields and `clear`
+  std::map<std::tuple<HaloKey, int, bool>, cudecomp::HaloFieldsPlan> halo_accumulate_fields_plans;
   // cudecompAmdTransposeFields* with two fields or more: TransposeKey (never pipelined) plus n_fields
   std::map<std::tuple<TransposeKey, int>, cudecomp::TransposeFieldsPlan> transpose_fields_plans;
 
@@ -287,6 +290,10 @@ void runHaloFold(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void*
 void runHaloFields(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* const* inputs, int n_fields, void* work,
                    cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
                    hipStream_t stream);
+// cudecompAmdAccumulateFieldHalos*: n_fields pencils, one exchange (n_fields == 1 IS runHaloAccumulate / runHaloAccumulateClear)
+void runHaloAccumulateFields(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* const* inputs, int n_fields, void* work,
+                             cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
+                             bool clear, hipStream_t stream);
 
 // cudecompAmdTransposeFields*: n_fields pencils, one exchange (n_fields == 1 IS runTranspose)
 void runTransposeFields(cudecompHandle_t handle, cudecompGridDesc_t gd, TransposeOp op, void* const* inputs, void* const* outputs,

@@ -9,7 +9,8 @@
 // kernels_rows.hip, kernels_transpose.hip (one code object per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip and kernels_fold.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
 // transpose.cc; kernels_field_transpose.hip (lists of field-moves: the moves of a halo or transpose phase for several pencils in
-// one launch) has an entry of its own at the end of this file, launchFieldMoveList.  kernels_batch.h says why they are separate
+// one launch) and kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) have an entry of their
+// own at the end of this file, launchFieldMoveList.  kernels_batch.h says why they are separate
 // code objects.
 //
 // 2-byte elements (fp16, bf16) take the row copy (plain kernel), the LDS-tiled transposition (128 x 128 tiles with 16-byte
@@ -51,7 +52,8 @@ constexpr long long kDenseMaxGapBytes = 512;  // widest gap between rows the den
 
 MoveClass classOf(KernelKind kind) {
   if (kind == K_GENERIC || kind == K_GENERIC_ADD || kind == K_GENERIC_FILL || kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE ||
-      kind == K_GENERIC_REFLECT || kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE || kind == K_GENERIC_FIELDS)
+      kind == K_GENERIC_REFLECT || kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE || kind == K_GENERIC_FIELDS || kind == K_GENERIC_FIELDS_ADD || kind == K_GENERIC_FIELDS_TAKE ||
+      kind == K_GENERIC_FIELDS_ADD_TAKE)
     return MOVE_GENERIC;
   return (kind >= K_TRANSPOSE && kind <= K_TRANSPOSE_ROWLINES) || kind == K_TRANSPOSE_FIELDS ? MOVE_TRANSPOSE : MOVE_ROWS_VEC;
 }
@@ -583,6 +585,18 @@ void spellKernelName(const KernelChoice& k) {
     case K_TRANSPOSE_FIELDS:
       snprintf(out, n, "transpose_fields_kernel<%d,%d,%d,%d,%d,%s>", k.es, k.vec, k.ti, k.tj, s, k.guard ? "true" : "false");
       break;
+    case K_ROWS_FIELDS_ADD:
+    case K_ROWS_FIELDS_ADD_TAKE:
+      snprintf(out, n, "rows_fields_accumulate_kernel<%s,%d,%d,%s>", arithName(k.arith), k.vec, s,
+               k.kind == K_ROWS_FIELDS_ADD_TAKE ? "true" : "false");
+      break;
+    case K_GENERIC_FIELDS_ADD:
+    case K_GENERIC_FIELDS_ADD_TAKE:
+      snprintf(out, n, "generic_fields_accumulate_kernel<%s,%d,%s>", arithName(k.arith), k.es / arithBytes(k.arith),
+               k.kind == K_GENERIC_FIELDS_ADD_TAKE ? "true" : "false");
+      break;
+    case K_ROWS_FIELDS_TAKE: snprintf(out, n, "rows_fields_take_kernel<%d,%d>", k.vec, s); break;
+    case K_GENERIC_FIELDS_TAKE: snprintf(out, n, "generic_fields_take_kernel<%d>", k.es); break;
   }
 }
 
@@ -636,7 +650,13 @@ void launchBatch(const KernelChoice& k, const Batch& b, const void* fill_value, 
     case K_GENERIC_FOLD_TAKE: launchFoldBatch(k, b, blocks, stream); break;
     case K_ROWS_FIELDS:
     case K_GENERIC_FIELDS:
-    case K_TRANSPOSE_FIELDS: CD_INTERNAL_ERROR("lists of field-moves are launched by launchFieldMoveList");
+    case K_TRANSPOSE_FIELDS:
+    case K_ROWS_FIELDS_ADD:
+    case K_GENERIC_FIELDS_ADD:
+    case K_ROWS_FIELDS_TAKE:
+    case K_GENERIC_FIELDS_TAKE:
+    case K_ROWS_FIELDS_ADD_TAKE:
+    case K_GENERIC_FIELDS_ADD_TAKE: CD_INTERNAL_ERROR("lists of field-moves are launched by launchFieldMoveList");
   }
 }
 
@@ -764,7 +784,7 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
 // ---------------------------------------------------------------------------------------------
 std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i64* work_steps, int n, void* const* inputs,
                                                    void* const* outputs, int n_fields, void* work, int es, int force,
-                                                   bool one_choice) {
+                                                   bool one_choice, ArithType arith) {
   if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
   if (n < 0 || (n > 0 && !moves)) CD_INTERNAL_ERROR("field-move list without moves");
   if (n_fields < 1 || n_fields > kMaxFields || !inputs) CD_INTERNAL_ERROR("field count out of range");
@@ -772,6 +792,16 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     if (!inputs[f] || (outputs && !outputs[f])) CD_INTERNAL_ERROR("null field buffer");
   const bool force_generic = (force & 1) != 0;
   char* const w = static_cast<char*>(work);
+  // the operation of the list: every move carries the same one
+  bool add = false, take = false;
+  for (int i = 0; i < n; ++i) {
+    if (i == 0) add = moves[i].add, take = moves[i].take;
+    else if (moves[i].add != add || moves[i].take != take) CD_INTERNAL_ERROR("the field-moves of one list carry different operations");
+  }
+  if (add) {
+    if (arith == ARITH_NONE) CD_INTERNAL_ERROR("adding field-move without an arithmetic type");
+    if (es % arithBytes(arith) != 0 || es / arithBytes(arith) > 2) CD_INTERNAL_ERROR("element size does not fit the arithmetic type");
+  }
 
   // each move's shared geometry, normalised, its ends, and the addresses every field's first element can have or-ed together (the
   // 2-byte rule: all fields' pencils and all workspace pieces)
@@ -781,8 +811,10 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
   std::vector<int> index;
   for (int i = 0; i < n; ++i) {
     const Move3D& in = moves[i];
-    if (in.add || in.fill || in.take || in.reflect || in.negate || in.dst_row_pitch != 0)
-      CD_INTERNAL_ERROR("field-moves are plain copies of exactly their cells");
+    if (in.fill || in.reflect || in.negate || in.dst_row_pitch != 0)
+      CD_INTERNAL_ERROR("field-moves copy, add or take exactly their cells");
+    if (add && in.dst_buf == BUF_WORK) CD_INTERNAL_ERROR("adding field-moves never add onto the workspace");
+    if (take && in.src_buf == BUF_WORK) CD_INTERNAL_ERROR("taking field-moves never clear the workspace");
     if ((in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK) && !work) CD_INTERNAL_ERROR("field-move through a workspace that was not given");
     if ((in.src_buf == BUF_OUT || in.dst_buf == BUF_OUT) && !outputs) CD_INTERNAL_ERROR("field-move onto an output list that was not given");
     for (int d = 0; d < 3; ++d)
@@ -808,7 +840,7 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     }
     Classified c{};
     c.k.es = es;
-    c.k.arith = ARITH_NONE;
+    c.k.arith = add ? arith : ARITH_NONE;
     c.elements = m.elements();
     c.dm.src = reinterpret_cast<const char*>(address_bits);  // (only its alignment is read)
     c.dm.dst = reinterpret_cast<char*>(address_bits);
@@ -835,15 +867,17 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     Classified& c = cs[i];
     FieldMove& fm = fms[i];
     // Access: cached while the move is below kStreamBytes PER FIELD, non-temporal loads and stores from there -- the project's
-    // rule for copies, unmeasured for these kernels; the element-wise kernel always caches.
+    // rule for copies, unmeasured for these kernels; the element-wise kernel always caches.  Additions and
+    // takes: the accumulation's rule by the same size -- access 1 = non-temporal source loads and (take) zero stores, the destination
+    // of an addition always cached, the plain take streaming all of it; unmeasured for these kernels too.
     const bool streaming = ((one_choice ? largest : c.elements) * es >= kStreamBytes || (force & 2)) && !(force & 4);
     int t = -1;
-    if (!force_generic && !one_choice && m.ss[0] == 1) {
+    if (!force_generic && !one_choice && !add && !take && m.ss[0] == 1) {  // (additions and takes never transpose)
       if (m.ds[1] == 1) t = 1;
       if (m.ds[2] == 1) t = 2;
     }
     if (one_choice ? all_rows : (!force_generic && m.ss[0] <= 1 && m.ds[0] <= 1)) {
-      c.k.kind = K_ROWS_FIELDS;
+      c.k.kind = take ? (add ? K_ROWS_FIELDS_ADD_TAKE : K_ROWS_FIELDS_TAKE) : (add ? K_ROWS_FIELDS_ADD : K_ROWS_FIELDS);
       c.k.access = streaming ? 1 : 0;
       rowVectors(c, m, lanes);
       if (c.k.vec < es) CD_INTERNAL_ERROR("field-move narrower than one element");
@@ -863,7 +897,7 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
       c.t1 = (unsigned int)((c.dm.e[1] + c.k.tj - 1) / c.k.tj);
       c.blocks = (unsigned long long)c.t0 * c.t1 * (unsigned long long)c.dm.e[2];
     } else {
-      c.k.kind = K_GENERIC_FIELDS;
+      c.k.kind = take ? (add ? K_GENERIC_FIELDS_ADD_TAKE : K_GENERIC_FIELDS_TAKE) : (add ? K_GENERIC_FIELDS_ADD : K_GENERIC_FIELDS);
       c.k.access = 0;
       genericGeometry(c, m);
     }
@@ -919,11 +953,13 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
 }
 
 void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void* const* inputs, void* const* outputs, int n_fields,
-                         void* work, int es, hipStream_t stream, int force, KernelStats* stats, bool one_choice) {
-  for (const FieldMoveLaunch& l : planFieldMoveLaunches(moves, work_steps, n, inputs, outputs, n_fields, work, es, force, one_choice)) {
+                         void* work, int es, hipStream_t stream, int force, KernelStats* stats, bool one_choice, ArithType arith) {
+  for (const FieldMoveLaunch& l :
+       planFieldMoveLaunches(moves, work_steps, n, inputs, outputs, n_fields, work, es, force, one_choice, arith)) {
     spellKernelName(l.k);
     ++g_data_launches;
-    launchFieldMoveBatch(l.k, l.b, l.blocks, stream);
+    if (l.k.kind >= K_ROWS_FIELDS_ADD) launchFieldAccumulateBatch(l.k, l.b, l.blocks, stream);
+    else launchFieldMoveBatch(l.k, l.b, l.blocks, stream);
     if (stats) {
       stats->launches[l.cls] += 1;
       stats->elements[l.cls] += l.elements;

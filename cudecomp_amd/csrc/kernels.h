@@ -77,7 +77,8 @@ std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3]
 // 4 runs over batch planes, 8 transpose_lines_kernel, 16 transpose_rowlines_kernel), access mode}.  (Tests of the planning logic: tests/test_kernel_plan.py.)
 void describeMove(const Move3D& m, const void* src, void* dst, int es, const KernelTuning* tuning, long long out[10]);
 
-// ---- lists of field-moves: a list of copy moves, each for several (input, output) pairs of buffers (kernels_field_transpose.hip) --
+// ---- lists of field-moves: a list of moves, each for several (input, output) pairs of buffers (kernels_field_transpose.hip,
+// kernels_field_accumulate.hip) ----
 // The moves of one phase of a multi-field transpose (include/cudecomp_transpose_fields.h) or of a multi-field halo update
 // (include/cudecomp_halo_fields.h): moves[0 .. n - 1] share their geometry among `n_fields` (1 .. kern::kMaxFields) fields.  An end
 // of a move in BUF_IN lies in inputs[f] + offset, an end in BUF_OUT in outputs[f] + offset, an end in BUF_WORK at
@@ -95,8 +96,16 @@ void describeMove(const Move3D& m, const void* src, void* dst, int es, const Ker
 // when every move has contiguous rows, then the narrowest of the moves' lane widths; never the transposition; non-temporal access
 // when the LARGEST move reaches kStreamBytes per field.  More than 2^31 - 1 workgroups in all are then NOT_SUPPORTED, not a
 // second launch.
-// A move with add, fill, take, reflect, negate or dst_row_pitch, a workspace end without a workspace and an output end without
-// `outputs` are internal errors before anything is launched; a move of more than 2^31 - 1 workgroups is NOT_SUPPORTED.
+// The OPERATION of a list (kernels_field_accumulate.hip) is what its moves carry, the same on every move: copy (neither flag), add
+// (Move3D::add: dst += src in `arith`, the real type the elements consist of, with the operand order of the single accumulation),
+// take (Move3D::take: dst = src; src = 0) or add-take (both).  Adding and taking lists run as rows or element by element, never
+// transposed, over exactly the cells of their moves; sources are disjoint from all destinations.  Access: the accumulation's rule by
+// the size of one field's move -- cached below kStreamBytes, from there non-temporal source loads and, with take, non-temporal zero
+// stores (the plain take: all of it); the destination of an add is always cached (unmeasured for these kernels).
+// A move with fill, reflect, negate or dst_row_pitch, moves of one list with different operations, an add without an arithmetic
+// type (or one the element size does not fit), an add whose destination is the workspace, a take whose source is the workspace, a
+// workspace end without a workspace and an output end without `outputs` are internal errors before anything is launched; a move
+// of more than 2^31 - 1 workgroups is NOT_SUPPORTED.
 struct FieldMoveLaunch {
   KernelChoice k;
   kern::FieldMoveBatch b;
@@ -109,9 +118,10 @@ struct FieldMoveLaunch {
 // WHICH launches launchFieldMoveList makes, in order (pure host code, no device needed; buffers are only looked at as addresses)
 std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i64* work_steps, int n, void* const* inputs,
                                                    void* const* outputs, int n_fields, void* work, int es, int force = 0,
-                                                   bool one_choice = false);
+                                                   bool one_choice = false, ArithType arith = ARITH_NONE);
 void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void* const* inputs, void* const* outputs, int n_fields,
-                         void* work, int es, hipStream_t stream, int force = 0, KernelStats* stats = nullptr, bool one_choice = false);
+                         void* work, int es, hipStream_t stream, int force = 0, KernelStats* stats = nullptr, bool one_choice = false,
+                         ArithType arith = ARITH_NONE);
 
 // data-movement launches this process has made so far (launchMoves and launchFieldMoveList; tests count launches per call with it)
 long long dataLaunchCount();

@@ -3,7 +3,8 @@
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip;
 // kernels_rotate.hip and sync.hip are launched by the executor; kernels_field_transpose.hip (lists of field-moves: multi-field
-// halo phases and transposes) is reached through launchFieldMoveList (kernels.h).  Sixteen code objects in all.
+// halo phases and transposes) and kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) are
+// reached through launchFieldMoveList (kernels.h).  Seventeen code objects in all.
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
 // code object beyond roughly 0.6-0.7 MB puts the whole process into a regime where every small synchronous operation costs
@@ -128,7 +129,13 @@ enum KernelKind {
   K_GENERIC_FOLD_TAKE,   // generic_fold_kernel with TAKE = 21
   K_ROWS_FIELDS,         // rows_fields_kernel (dst = src, one move of a FieldMoveBatch for every field) = 22
   K_GENERIC_FIELDS,      // generic_fields_kernel = 23
-  K_TRANSPOSE_FIELDS     // transpose_fields_kernel (LDS-tiled) = 24
+  K_TRANSPOSE_FIELDS,    // transpose_fields_kernel (LDS-tiled) = 24
+  K_ROWS_FIELDS_ADD,          // rows_fields_accumulate_kernel (dst += src, one move of a FieldMoveBatch for every field) = 25
+  K_GENERIC_FIELDS_ADD,       // generic_fields_accumulate_kernel = 26
+  K_ROWS_FIELDS_TAKE,         // rows_fields_take_kernel (dst = src; src = 0) = 27
+  K_GENERIC_FIELDS_TAKE,      // generic_fields_take_kernel = 28
+  K_ROWS_FIELDS_ADD_TAKE,     // rows_fields_accumulate_kernel with TAKE (dst += src; src = 0) = 29
+  K_GENERIC_FIELDS_ADD_TAKE   // generic_fields_accumulate_kernel with TAKE = 30
 };
 struct KernelChoice {
   KernelKind kind;
@@ -139,7 +146,8 @@ struct KernelChoice {
                     // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads;
                     // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it);
                     // reflections: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores;
-                    // field-moves: 0, 1 non-temporal loads and stores; transpose_fields_kernel: 0, 2
+                    // field-moves: 0, 1 non-temporal loads and stores; transpose_fields_kernel: 0, 2; adding / taking
+                    // field-moves: as additions / takes
   ArithType arith;  // additions, folds, reflections that flip the sign bits: the real type the elements consist of; ARITH_NONE otherwise
   bool neg;         // folds: the sign bits of the source are flipped before the addition (one sign mask per launch)
   bool guard;       // transpose_fields_kernel: some tile of the move ends inside the move (the GUARD template argument); false otherwise
@@ -170,6 +178,8 @@ inline int streamArgOf(KernelKind kind, int access) {
   if (kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE) return 0;
   if (kind == K_ROWS_FIELDS || kind == K_TRANSPOSE_FIELDS) return access;
   if (kind == K_GENERIC_FIELDS) return 0;
+  if (kind == K_ROWS_FIELDS_ADD || kind == K_ROWS_FIELDS_TAKE || kind == K_ROWS_FIELDS_ADD_TAKE) return access;
+  if (kind == K_GENERIC_FIELDS_ADD || kind == K_GENERIC_FIELDS_TAKE || kind == K_GENERIC_FIELDS_ADD_TAKE) return 0;
   if (kind == K_TRANSPOSE_WINDOW || kind == K_TRANSPOSE_LINES || kind == K_TRANSPOSE_ROWLINES)
     return access == 2 ? 4 : access;  // always cached loads: the overlap rows of neighbouring windows hit in L2
   return access == 3 ? 3 : (access >= 1 ? 1 : 0);  // row copies: loads and stores stream together
@@ -214,6 +224,8 @@ void launchReflectBatch(const KernelChoice& k, const kern::Batch& b, unsigned in
 void launchFoldBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // kernels_field_transpose.hip: lists of field-moves (plain copies of exactly the cells of the moves; local buffers only)
 void launchFieldMoveBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, unsigned int blocks, hipStream_t stream);
+// kernels_field_accumulate.hip: lists of field-moves that add (k.arith: the real type), take or both; local buffers only
+void launchFieldAccumulateBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, unsigned int blocks, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

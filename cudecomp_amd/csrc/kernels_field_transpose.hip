@@ -22,6 +22,7 @@
 // Exactly the cells of the moves are read and written: no window, lines, shifted or dense form (the cells between rows belong
 // to the fields' pencils and are not the move's to rewrite), no remote destination.
 // Pure data movement: no MFMA; the bound is HBM (8 TB/s spec, ~6.3 TB/s achievable copy rate).
+#include "kernels_field_list.h"
 #include "kernels_tile.h"
 
 #include "errors.h"
@@ -29,27 +30,6 @@
 namespace cudecomp {
 namespace kern {
 namespace {
-
-// workgroup -> (move, field, workgroup index inside that field's move)
-__device__ __forceinline__ void locateFieldMove(const FieldMoveBatch& b, unsigned int block, int& mi, unsigned int& f, unsigned int& lb) {
-  mi = 0;
-#pragma unroll
-  for (int i = 1; i < kMaxBatch; ++i)
-    if (i < b.n && block >= b.first_block[i]) mi = i;
-  const unsigned int rel = block - b.first_block[mi];
-  const unsigned int per = b.m[mi].blocks;
-  f = rel / per;
-  lb = rel - f * per;
-}
-
-__device__ __forceinline__ const char* sourceOf(const FieldMoveBatch& b, const FieldMove& m, unsigned int f) {
-  const char* base = m.src_end == kEndWork ? b.work + (long long)f * m.src_step : (m.src_end == kEndOutput ? b.out[f] : b.in[f]);
-  return base + m.src_off;
-}
-__device__ __forceinline__ char* destinationOf(const FieldMoveBatch& b, const FieldMove& m, unsigned int f) {
-  char* base = m.dst_end == kEndWork ? b.work + (long long)f * m.dst_step : (m.dst_end == kEndOutput ? b.out[f] : b.in[f]);
-  return base + m.dst_off;
-}
 
 // ---------------------------------------------------------------------------------------------
 // transpose_fields_kernel: dims (i, j, k) as transpose_kernel (kernels_tile.h): i unit-stride in the source, j unit-stride in the

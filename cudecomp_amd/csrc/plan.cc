@@ -601,19 +601,13 @@ HaloPlan buildHaloFoldPlan(const GridShape& g, int rank, int axis, int dim, cons
   return p;
 }
 
-HaloFieldsPlan buildHaloFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
-                                   const int32_t* pad, int n_fields, bool force_packed, bool self_exchange) {
-  if (n_fields < 1) CD_INVALID_USAGE("n_fields argument out of range");
-  HaloFieldsPlan fp;
-  fp.n_fields = n_fields;
-  fp.base = buildHaloPlan(g, rank, axis, dim, halo, periods, pad, force_packed || n_fields >= 2, self_exchange);
+// the slots of a packed single plan are alignElements(face) apart: move them alignElements(n_fields * face) apart
+static void relayFieldSlots(HaloFieldsPlan& fp) {
   HaloPlan& p = fp.base;
-  if (p.kind == HaloPlan::DIRECT && n_fields >= 2) CD_INTERNAL_ERROR("a multi-field halo plan came out direct");
-  if (p.kind != HaloPlan::PACKED) return fp;
+  const int n_fields = fp.n_fields;
   const i64 single = alignElements(p.face_elements);
   fp.slot_elements = n_fields == 1 ? single : alignElements((i64)n_fields * p.face_elements);
-  if (n_fields == 1) return fp;
-  // the slots of buildHaloPlan are `single` apart: move them `slot_elements` apart
+  if (n_fields == 1) return;
   auto moved = [&](i64 off) {
     if (off % single != 0 || off / single > 3) CD_INTERNAL_ERROR("a packed halo plan with an unexpected workspace layout");
     return off / single * fp.slot_elements;
@@ -630,6 +624,29 @@ HaloFieldsPlan buildHaloFieldsPlan(const GridShape& g, int rank, int axis, int d
     if (m.src_buf != BUF_WORK || m.dst_buf != BUF_IN) CD_INTERNAL_ERROR("a halo unpack that does not run workspace -> pencil");
     m.src_off = moved(m.src_off);
   }
+}
+
+HaloFieldsPlan buildHaloFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                   const int32_t* pad, int n_fields, bool force_packed, bool self_exchange) {
+  if (n_fields < 1) CD_INVALID_USAGE("n_fields argument out of range");
+  HaloFieldsPlan fp;
+  fp.n_fields = n_fields;
+  fp.base = buildHaloPlan(g, rank, axis, dim, halo, periods, pad, force_packed || n_fields >= 2, self_exchange);
+  HaloPlan& p = fp.base;
+  if (p.kind == HaloPlan::DIRECT && n_fields >= 2) CD_INTERNAL_ERROR("a multi-field halo plan came out direct");
+  if (p.kind != HaloPlan::PACKED) return fp;
+  relayFieldSlots(fp);
+  return fp;
+}
+
+HaloFieldsPlan buildHaloAccumulateFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                             const int32_t* pad, int n_fields, bool clear, bool self_exchange) {
+  if (n_fields < 1) CD_INVALID_USAGE("n_fields argument out of range");
+  HaloFieldsPlan fp;
+  fp.n_fields = n_fields;
+  fp.base = (clear ? buildHaloAccumulateClearPlan : buildHaloAccumulatePlan)(g, rank, axis, dim, halo, periods, pad, true, self_exchange);
+  if (fp.base.kind == HaloPlan::DIRECT) CD_INTERNAL_ERROR("a halo accumulation plan came out direct");
+  if (fp.base.kind == HaloPlan::PACKED) relayFieldSlots(fp);
   return fp;
 }
 

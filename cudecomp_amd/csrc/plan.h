@@ -278,6 +278,18 @@ struct HaloFieldsPlan {
 HaloFieldsPlan buildHaloFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
                                    const int32_t* pad, int n_fields, bool force_packed, bool self_exchange = false);
 
+// Multi-field halo ACCUMULATION along `dim` (include/cudecomp_halo_accumulate_fields.h has the contract): `n_fields` pencils of one
+// descriptor, axis, halos and padding accumulated by one exchange, with (`clear`) or without the clearing of the ghost cells read.
+// Derived from buildHaloAccumulatePlan / buildHaloAccumulateClearPlan: refusals, neighbours, slabs, `ordered` and the add / take
+// flags of the moves are the single call's by construction.  Kinds: NONE, SELF_PERIODIC (the two wrap additions, pencil -> pencil,
+// carried out for every field) or PACKED.  The moves in `base` are those of field 0 under the slot layout of buildHaloFieldsPlan:
+// an end in BUF_IN is "field f's pencil" at the same offset, an end in BUF_WORK lies at its offset + f * face_elements; workspace
+// [send low | send high | recv low | recv high], each slot slot_elements = alignElements(n_fields * face_elements) long; the
+// exchange moves n_fields * face_elements elements per direction, from send_off[i] to the neighbour's recv_off[1 - i].
+// n_fields == 1: the single plan, unchanged.
+HaloFieldsPlan buildHaloAccumulateFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                             const int32_t* pad, int n_fields, bool clear, bool self_exchange = false);
+
 // Number of stages every member of the communicator arrives at without talking: at most `wanted`, at most the smallest
 // chunk extent, at most 14 (flag steps), and no stage smaller than `min_stage_bytes` of the largest pencil (below that the extra
 // launches cost more than the overlap gains).

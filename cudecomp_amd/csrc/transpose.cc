@@ -647,6 +647,53 @@ void runHaloAccumulateClear(cudecompHandle_t h, cudecompGridDesc_t gd, int axis,
   runHaloAccumulateOf(true, h, gd, axis, input, work, dtype, halo, periods, dim, pad, stream);
 }
 
+// Multi-field halo accumulation (cudecompAmdAccumulateFieldHalos*): pack all fields' halos (one launch; with `clear` the pack zeroes
+// what it has read) -> one exchange of n_fields slabs per direction -> add what arrived onto all fields' faces (one launch; one per
+// side, low side first, where the plan is `ordered`).  Self-periodic: the wrap additions of all fields in one launch (two when
+// ordered).  Not sampled by the performance report.  One field: the single call itself.
+void runHaloAccumulateFields(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* const* inputs, int n_fields, void* work,
+                             cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, bool clear,
+                             hipStream_t stream) {
+  if (n_fields == 1) return runHaloAccumulateOf(clear, h, gd, axis, inputs[0], work, dtype, halo, periods, dim, pad, stream);
+  const int es = elementSize(dtype);
+  const ArithType arith = arithOf(dtype);
+  const auto backend = gd->config.halo_comm_backend;
+
+  const auto hh = arr3(halo), pp = arr3(pad);
+  std::array<bool, 3> per{false, false, false};
+  if (periods)
+    for (int i = 0; i < 3; ++i) per[i] = periods[i];
+  const cudecompGridDesc::HaloKey hkey{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, true};
+  const std::tuple<cudecompGridDesc::HaloKey, int, bool> key{hkey, n_fields, clear};
+  auto it = gd->halo_accumulate_fields_plans.find(key);
+  if (it == gd->halo_accumulate_fields_plans.end()) {
+    HaloFieldsPlan p = buildHaloAccumulateFieldsPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), n_fields, clear,
+                                                     h->self_exchange);
+    it = gd->halo_accumulate_fields_plans.emplace(key, std::move(p)).first;
+  }
+  const HaloPlan& plan = it->second.base;
+  if (plan.kind == HaloPlan::NONE) return;
+
+  ensureDevice(h);
+  const int force = (h->tuning.force_class == MOVE_GENERIC ? 1 : 0) | (h->tuning.force_streaming ? 2 : 0) | (h->tuning.no_streaming ? 4 : 0);
+  // the one or two sides of a phase in ONE launch (one_choice) unless they add onto overlapping cells (interior narrower than two
+  // halos): then one launch per side, low face first
+  auto launch = [&](const std::vector<Move3D>& moves) {
+    if (moves.empty()) return;
+    const std::vector<i64> steps(moves.size(), plan.face_elements);
+    const int each = plan.ordered && moves[0].add ? 1 : (int)moves.size();
+    for (int i = 0; i < (int)moves.size(); i += each)
+      launchFieldMoveList(moves.data() + i, steps.data() + i, each, inputs, inputs, n_fields, work, es, stream, force, nullptr, true, arith);
+  };
+  launch(plan.pre);
+  if (plan.kind == HaloPlan::SELF_PERIODIC) return;
+  void* bufs[3] = {nullptr, nullptr, work};
+  HaloExchange x = haloExchangeOf(plan, bufs, es);
+  x.bytes = (i64)n_fields * plan.face_elements * es;
+  haloExchange(h, gd, x, backend, stream);
+  launch(plan.post);
+}
+
 // Halo fill (cudecompAmdFillHalos*): the cells the update would write receive `value`, both sides in one launch.  Local: no
 // workspace, no exchange.  The key carries force_packed because the destinations are taken from the update's own plan.
 void runHaloFill(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, const void* value,

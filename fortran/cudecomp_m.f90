@@ -688,6 +688,60 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompAmdUpdateFieldHalosZ_C
 
+    function cudecompAmdAccumulateFieldHalosX_C(handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, &
+                                                padding, clear, stream) bind(C, name="cudecompAmdAccumulateFieldHalosX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      integer(c_int32_t), value :: n_fields
+      type(c_ptr) :: inputs(*)
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_int32_t), value :: clear
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdAccumulateFieldHalosX_C
+
+    function cudecompAmdAccumulateFieldHalosY_C(handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, &
+                                                padding, clear, stream) bind(C, name="cudecompAmdAccumulateFieldHalosY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      integer(c_int32_t), value :: n_fields
+      type(c_ptr) :: inputs(*)
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_int32_t), value :: clear
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdAccumulateFieldHalosY_C
+
+    function cudecompAmdAccumulateFieldHalosZ_C(handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, &
+                                                padding, clear, stream) bind(C, name="cudecompAmdAccumulateFieldHalosZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      integer(c_int32_t), value :: n_fields
+      type(c_ptr) :: inputs(*)
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_int32_t), value :: clear
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdAccumulateFieldHalosZ_C
+
     function cudecompAmdTransposeFieldsXToY_C(handle, grid_desc, inputs, outputs, n_fields, work, dtype, ihalo, ohalo, ipad, opad, &
                                                 stream) bind(C, name="cudecompAmdTransposeFieldsXToY") result(res)
       import
@@ -1558,6 +1612,79 @@ contains
     res = cudecompAmdUpdateFieldHalosZ_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), c_loc(work), int(dtype, c_int), h, per, &
                                          int(dim - 1, c_int32_t), p, s)
   end function cudecompAmdUpdateFieldHalosZ
+
+
+  ! ---- multi-field halo accumulation (include/cudecomp_halo_accumulate_fields.h): n_fields pencils, one exchange ------------
+  ! the arguments of cudecompAmdUpdateFieldHalosX with `clear` (0 / 1: zero bytes into the ghost cells that were read) after `dim`,
+  ! before the optional ones
+  function cudecompAmdAccumulateFieldHalosX(handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, clear, &
+                                            padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    type(*), dimension(..), target :: work
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer :: clear  ! 0 / 1
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdAccumulateFieldHalosX_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), c_loc(work), int(dtype, c_int), h, &
+                                             per, int(dim - 1, c_int32_t), p, int(clear, c_int32_t), s)
+  end function cudecompAmdAccumulateFieldHalosX
+
+  function cudecompAmdAccumulateFieldHalosY(handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, clear, &
+                                            padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    type(*), dimension(..), target :: work
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer :: clear  ! 0 / 1
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdAccumulateFieldHalosY_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), c_loc(work), int(dtype, c_int), h, &
+                                             per, int(dim - 1, c_int32_t), p, int(clear, c_int32_t), s)
+  end function cudecompAmdAccumulateFieldHalosY
+
+  function cudecompAmdAccumulateFieldHalosZ(handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, clear, &
+                                            padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    type(*), dimension(..), target :: work
+    integer :: dtype
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer :: clear  ! 0 / 1
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    res = cudecompAmdAccumulateFieldHalosZ_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), c_loc(work), int(dtype, c_int), h, &
+                                             per, int(dim - 1, c_int32_t), p, int(clear, c_int32_t), s)
+  end function cudecompAmdAccumulateFieldHalosZ
 
 
   ! ---- multi-field transposes (include/cudecomp_transpose_fields.h): n_fields pencils, one exchange ------------------------

@@ -183,6 +183,18 @@ cudecompResult_t cudecompExtPlanHaloFields(const cudecompExtGridSpec_t* grid, in
                                            const int32_t padding[], int32_t n_fields, int32_t force_packed,
                                            cudecompExtHaloFieldsPlan_t* plan);
 
+/* The plan cudecompAmdAccumulateFieldHalos{X,Y,Z} (cudecomp_halo_accumulate_fields.h) would run on `rank` for n_fields fields and
+ * `clear` (csrc/plan.h buildHaloAccumulateFieldsPlan), in the structure of cudecompExtPlanHaloFields: kind 0, 1 or 2; pre / post are
+ * the moves of FIELD 0 under the same rule for their ends; the slots, slot_elements and the exchange as described there.
+ * `reserved` holds the bits cudecompExtHaloPlan_t::reserved has for the single accumulation (clear == 0) or accumulate-and-clear
+ * (clear == 1) plan.  self_exchange != 0: the plan of a run with CUDECOMP_TEST_SELF_EXCHANGE=1.  n_fields == 1: the single plan,
+ * unchanged.  The refusals are those of cudecompExtPlanHaloAccumulate, then CUDECOMP_RESULT_INVALID_USAGE for n_fields < 1 and for
+ * a `clear` that is not 0 / 1. */
+cudecompResult_t cudecompExtPlanHaloAccumulateFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
+                                                     const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
+                                                     const int32_t padding[], int32_t n_fields, int32_t clear, int32_t self_exchange,
+                                                     cudecompExtHaloFieldsPlan_t* plan);
+
 /* Stateless geometry queries on a grid spec (no handle, no communicator): what cudecompGetPencilInfo,
  * cudecompGetShiftedRank, cudecompGetTransposeWorkspaceSize and cudecompGetHaloWorkspaceSize would answer on `rank`. */
 cudecompResult_t cudecompExtPencilInfo(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
@@ -406,6 +418,21 @@ cudecompResult_t cudecompExtRunFieldMoves(const cudecompExtMove_t* moves, int32_
 cudecompResult_t cudecompExtDescribeFieldMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
                                               int32_t n_fields, uint64_t work_address, int64_t work_field_stride, int32_t es,
                                               int32_t force, int64_t out[5]);
+
+/* The pair above with an OPERATION (kernels_field_accumulate.hip): the same arguments plus `mode` -- 0 copy, 1 add (dst += src), 3
+ * take (dst = src; src = 0), 4 add and take, the values cudecompExtRunMoves uses; every other value is INVALID_USAGE -- and `dtype`,
+ * whose arithmetic the additions use (its element size must be `es`; ignored for modes 0 and 3).  Every move of the list carries
+ * the operation.  An add whose destination is the workspace and a take whose source is the workspace are internal errors before
+ * any launch; sources must be disjoint from all destinations.  kinds (csrc/kernels_batch.h KernelKind): 22 / 23 copy, 25
+ * rows_fields_accumulate_kernel, 26 generic_fields_accumulate_kernel, 27 rows_fields_take_kernel, 28 generic_fields_take_kernel,
+ * 29 / 30 the accumulating kernels with TAKE.  Access mode of the adding and taking kinds: 0 cached, 1 non-temporal source loads
+ * and (take) zero stores, the plain take's destination stores too; the destination of an add is always cached. */
+cudecompResult_t cudecompExtRunFieldMovesOp(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
+                                           void* work, int64_t work_field_stride, int32_t es, int32_t force, int32_t mode,
+                                           cudecompDataType_t dtype, hipStream_t stream, int32_t* n_launches);
+cudecompResult_t cudecompExtDescribeFieldMovesOp(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
+                                                int32_t n_fields, uint64_t work_address, int64_t work_field_stride, int32_t es,
+                                                int32_t force, int32_t mode, cudecompDataType_t dtype, int64_t out[5]);
 
 /* The plan cudecompAmdTransposeFields{XToY,YToZ,ZToY,YToX} (cudecomp_transpose_fields.h) would run on `rank` for n_fields fields
  * (csrc/plan.h buildTransposeFieldsPlan), stateless like cudecompExtPlanTranspose and with its arguments.  pack / unpack are the
