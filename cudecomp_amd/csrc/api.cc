@@ -623,12 +623,6 @@ cudecompResult_t cudecompGridDescCreateVersioned(cudecompHandle_t handle, cudeco
     gd->transpose_plans.clear();
     gd->relay_plans.clear();
     gd->halo_plans.clear();
-    gd->halo_accumulate_plans.clear();
-    gd->halo_fill_plans.clear();
-    gd->halo_accumulate_clear_plans.clear();
-    gd->halo_reflect_plans.clear();
-    gd->halo_fold_plans.clear();
-    gd->halo_accumulate_fields_plans.clear();
     perfReset(gd);  // autotuning trials are not part of the user's performance report
 
     *grid_desc_out = gd;
@@ -837,216 +831,158 @@ CD_DEFINE_TRANSPOSE(cudecompTransposeYToZ, OP_Y_TO_Z)
 CD_DEFINE_TRANSPOSE(cudecompTransposeZToY, OP_Z_TO_Y)
 CD_DEFINE_TRANSPOSE(cudecompTransposeYToX, OP_Y_TO_X)
 
-// accumulate: 0 the update, 1 accumulation, 2 accumulation that clears the ghost cells it has read (cudecomp_amd_fill.h)
-static cudecompResult_t haloEntry(int accumulate, int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
-                                  void* work, cudecompDataType_t dtype, const int32_t halo_extents[],
-                                  const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {
+// Every halo family (cudecomp.h, cudecomp_amd.h, cudecomp_amd_fill.h, cudecomp_amd_reflect.h, cudecomp_halo_fold.h,
+// cudecomp_halo_fields.h, cudecomp_halo_accumulate_fields.h) checks its arguments here, in one order: handle, descriptor, data type,
+// halo_extents, the return when every halo is zero, input, work, dim; all of it on the host, before anything is launched.  What differs:
+//  - max_fields > 0: a multi-field family -- the list of fields is checked where the single calls check `input`;
+//  - clear_first: `clear` is checked right after halo_extents, also when every halo is zero (cudecompAmdAccumulateFieldHalos*);
+//  - reflection and folding check parity, centering and `clear` when every halo is zero and otherwise leave them to the runner,
+//    which puts the plan's own refusals in the contract's place (halo.cc);
+//  - the local families (fill, reflection, folding) take no workspace.
+static cudecompResult_t haloApiEntry(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, const HaloCall& c, int max_fields = 0,
+                                     bool clear_first = false) {
   try {
+    const HaloOp::Kind kind = c.op.kind;
     checkHandle(handle);
     checkGridDesc(handle, grid_desc);
-    checkDataType(dtype);
-    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
-    if (halo_extents[0] == 0 && halo_extents[1] == 0 && halo_extents[2] == 0) return CUDECOMP_RESULT_SUCCESS;
-    if (!input) CD_INVALID_USAGE("input argument cannot be null");
-    if (!work) CD_INVALID_USAGE("work argument cannot be null");
-    if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
-    if (accumulate == 2) runHaloAccumulateClear(handle, grid_desc, axis, input, work, dtype, halo_extents, halo_periods, dim, padding, stream);
-    else if (accumulate) runHaloAccumulate(handle, grid_desc, axis, input, work, dtype, halo_extents, halo_periods, dim, padding, stream);
-    else runHalo(handle, grid_desc, axis, input, work, dtype, halo_extents, halo_periods, dim, padding, stream);
+    checkDataType(c.dtype);
+    if (!c.halo) CD_INVALID_USAGE("halo_extents argument cannot be null");
+    if (clear_first && c.clear != 0 && c.clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
+    if (c.halo[0] == 0 && c.halo[1] == 0 && c.halo[2] == 0) {
+      if (kind == HaloOp::REFLECT || kind == HaloOp::FOLD) {
+        if (c.parity != 1 && c.parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
+        if (c.op.centering != 0 && c.op.centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
+        if (c.clear != 0 && c.clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
+      }
+      return CUDECOMP_RESULT_SUCCESS;
+    }
+    if (max_fields == 0) {
+      if (!c.fields[0]) CD_INVALID_USAGE("input argument cannot be null");
+    } else {
+      const int32_t n_fields = c.op.n_fields;
+      if (!c.fields) CD_INVALID_USAGE("inputs argument cannot be null");
+      if (n_fields < 1 || n_fields > max_fields) CD_INVALID_USAGE("n_fields argument out of range");
+      for (int32_t i = 0; i < n_fields; ++i) {
+        if (!c.fields[i]) CD_INVALID_USAGE("inputs argument cannot hold a null entry");
+        for (int32_t j = 0; j < i; ++j)
+          if (c.fields[j] == c.fields[i]) CD_INVALID_USAGE("inputs argument cannot hold the same field twice");
+      }
+    }
+    if ((kind == HaloOp::UPDATE || kind == HaloOp::ACCUMULATE) && !c.work) CD_INVALID_USAGE("work argument cannot be null");
+    if (c.dim < 0 || c.dim > 2) CD_INVALID_USAGE("dim argument out of range");
+    runHaloOp(handle, grid_desc, c);
   }
   CD_API_CATCH()
   return CUDECOMP_RESULT_SUCCESS;
 }
 
-#define CD_DEFINE_HALO(NAME, ACCUMULATE, AXIS)                                                                              \
-  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, void* work,           \
-                        cudecompDataType_t dtype, const int32_t halo_extents[], const bool halo_periods[],        \
-                        int32_t dim, const int32_t padding[], hipStream_t stream) {                               \
-    return haloEntry(ACCUMULATE, AXIS, handle, grid_desc, input, work, dtype, halo_extents, halo_periods, dim, padding, stream); \
+// the arguments every family passes
+static HaloCall haloCall(HaloOp::Kind kind, int axis, void* const* fields, void* work, cudecompDataType_t dtype, const int32_t halo_extents[],
+                         const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {
+  HaloCall c;
+  c.op.kind = kind;
+  c.axis = axis;
+  c.dim = dim;
+  c.fields = fields;
+  c.work = work;
+  c.dtype = dtype;
+  c.halo = halo_extents;
+  c.periods = halo_periods;
+  c.pad = padding;
+  c.stream = stream;
+  return c;
+}
+
+// CLEAR: the accumulation also stores zero bytes to the ghost cells it has read (cudecomp_amd_fill.h)
+#define CD_DEFINE_HALO(NAME, KIND, CLEAR, AXIS)                                                                             \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, void* work,                     \
+                        cudecompDataType_t dtype, const int32_t halo_extents[], const bool halo_periods[],                  \
+                        int32_t dim, const int32_t padding[], hipStream_t stream) {                                         \
+    HaloCall c = haloCall(HaloOp::KIND, AXIS, &input, work, dtype, halo_extents, halo_periods, dim, padding, stream);       \
+    c.clear = CLEAR;                                                                                                        \
+    c.op.clear = CLEAR != 0;                                                                                                \
+    return haloApiEntry(handle, grid_desc, c);                                                                              \
   }
-CD_DEFINE_HALO(cudecompUpdateHalosX, 0, 0)
-CD_DEFINE_HALO(cudecompUpdateHalosY, 0, 1)
-CD_DEFINE_HALO(cudecompUpdateHalosZ, 0, 2)
+CD_DEFINE_HALO(cudecompUpdateHalosX, UPDATE, 0, 0)
+CD_DEFINE_HALO(cudecompUpdateHalosY, UPDATE, 0, 1)
+CD_DEFINE_HALO(cudecompUpdateHalosZ, UPDATE, 0, 2)
 // cudecomp_amd.h: the transpose of the updates (ghost cells summed into their owners)
-CD_DEFINE_HALO(cudecompAmdAccumulateHalosX, 1, 0)
-CD_DEFINE_HALO(cudecompAmdAccumulateHalosY, 1, 1)
-CD_DEFINE_HALO(cudecompAmdAccumulateHalosZ, 1, 2)
+CD_DEFINE_HALO(cudecompAmdAccumulateHalosX, ACCUMULATE, 0, 0)
+CD_DEFINE_HALO(cudecompAmdAccumulateHalosY, ACCUMULATE, 0, 1)
+CD_DEFINE_HALO(cudecompAmdAccumulateHalosZ, ACCUMULATE, 0, 2)
 // cudecomp_amd_fill.h: accumulation and the fill with zero bytes of the same ghost cells, in the accumulation's launches
-CD_DEFINE_HALO(cudecompAmdAccumulateAndClearHalosX, 2, 0)
-CD_DEFINE_HALO(cudecompAmdAccumulateAndClearHalosY, 2, 1)
-CD_DEFINE_HALO(cudecompAmdAccumulateAndClearHalosZ, 2, 2)
+CD_DEFINE_HALO(cudecompAmdAccumulateAndClearHalosX, ACCUMULATE, 1, 0)
+CD_DEFINE_HALO(cudecompAmdAccumulateAndClearHalosY, ACCUMULATE, 1, 1)
+CD_DEFINE_HALO(cudecompAmdAccumulateAndClearHalosZ, ACCUMULATE, 1, 2)
 
-// cudecomp_amd_fill.h: the ghost cells an update would write receive one value.  The checks of haloEntry, in its order, without `work`.
-static cudecompResult_t haloFillEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
-                                      cudecompDataType_t dtype, const void* value, const int32_t halo_extents[],
-                                      const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {
-  try {
-    checkHandle(handle);
-    checkGridDesc(handle, grid_desc);
-    checkDataType(dtype);
-    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
-    if (halo_extents[0] == 0 && halo_extents[1] == 0 && halo_extents[2] == 0) return CUDECOMP_RESULT_SUCCESS;
-    if (!input) CD_INVALID_USAGE("input argument cannot be null");
-    if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
-    runHaloFill(handle, grid_desc, axis, input, dtype, value, halo_extents, halo_periods, dim, padding, stream);
-  }
-  CD_API_CATCH()
-  return CUDECOMP_RESULT_SUCCESS;
-}
-
-#define CD_DEFINE_HALO_FILL(NAME, AXIS)                                                                                   \
-  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,     \
-                        const void* value, const int32_t halo_extents[], const bool halo_periods[], int32_t dim,          \
-                        const int32_t padding[], hipStream_t stream) {                                                    \
-    return haloFillEntry(AXIS, handle, grid_desc, input, dtype, value, halo_extents, halo_periods, dim, padding, stream); \
+// cudecomp_amd_fill.h: the ghost cells an update would write receive one value
+#define CD_DEFINE_HALO_FILL(NAME, AXIS)                                                                                     \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,       \
+                        const void* value, const int32_t halo_extents[], const bool halo_periods[], int32_t dim,            \
+                        const int32_t padding[], hipStream_t stream) {                                                      \
+    HaloCall c = haloCall(HaloOp::FILL, AXIS, &input, nullptr, dtype, halo_extents, halo_periods, dim, padding, stream);    \
+    c.value = value;                                                                                                        \
+    return haloApiEntry(handle, grid_desc, c);                                                                              \
   }
 CD_DEFINE_HALO_FILL(cudecompAmdFillHalosX, 0)
 CD_DEFINE_HALO_FILL(cudecompAmdFillHalosY, 1)
 CD_DEFINE_HALO_FILL(cudecompAmdFillHalosZ, 2)
 
-// cudecomp_amd_reflect.h: the ghost cells at a non-periodic edge of the domain receive the mirror image of the interior.  The
-// checks of haloFillEntry, in its order; then parity and centering (also when every halo is zero); then the plan's own.
-static cudecompResult_t haloReflectEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
-                                         cudecompDataType_t dtype, int32_t parity, int32_t centering, const int32_t halo_extents[],
-                                         const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {
-  try {
-    checkHandle(handle);
-    checkGridDesc(handle, grid_desc);
-    checkDataType(dtype);
-    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
-    if (halo_extents[0] == 0 && halo_extents[1] == 0 && halo_extents[2] == 0) {
-      if (parity != 1 && parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
-      if (centering != 0 && centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
-      return CUDECOMP_RESULT_SUCCESS;
-    }
-    if (!input) CD_INVALID_USAGE("input argument cannot be null");
-    if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
-    runHaloReflect(handle, grid_desc, axis, input, dtype, parity, centering, halo_extents, halo_periods, dim, padding, stream);
-  }
-  CD_API_CATCH()
-  return CUDECOMP_RESULT_SUCCESS;
-}
-
-#define CD_DEFINE_HALO_REFLECT(NAME, AXIS)                                                                                \
-  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,     \
-                        int32_t parity, int32_t centering, const int32_t halo_extents[], const bool halo_periods[],       \
-                        int32_t dim, const int32_t padding[], hipStream_t stream) {                                       \
-    return haloReflectEntry(AXIS, handle, grid_desc, input, dtype, parity, centering, halo_extents, halo_periods, dim,    \
-                            padding, stream);                                                                            \
+// cudecomp_amd_reflect.h: the ghost cells at a non-periodic edge of the domain receive the mirror image of the interior
+#define CD_DEFINE_HALO_REFLECT(NAME, AXIS)                                                                                  \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,       \
+                        int32_t parity, int32_t centering, const int32_t halo_extents[], const bool halo_periods[],         \
+                        int32_t dim, const int32_t padding[], hipStream_t stream) {                                         \
+    HaloCall c = haloCall(HaloOp::REFLECT, AXIS, &input, nullptr, dtype, halo_extents, halo_periods, dim, padding, stream); \
+    c.parity = parity;                                                                                                      \
+    c.op.negate = parity == -1;                                                                                             \
+    c.op.centering = centering;                                                                                             \
+    return haloApiEntry(handle, grid_desc, c);                                                                              \
   }
 CD_DEFINE_HALO_REFLECT(cudecompAmdReflectHalosX, 0)
 CD_DEFINE_HALO_REFLECT(cudecompAmdReflectHalosY, 1)
 CD_DEFINE_HALO_REFLECT(cudecompAmdReflectHalosZ, 2)
 
-// cudecomp_halo_fold.h: the ghost cells the reflection writes are added onto their mirror images.  The checks of haloReflectEntry,
-// in its order, with `clear` after centering (also when every halo is zero); then the plan's own.
-static cudecompResult_t haloFoldEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
-                                      cudecompDataType_t dtype, int32_t parity, int32_t centering, int32_t clear,
-                                      const int32_t halo_extents[], const bool halo_periods[], int32_t dim, const int32_t padding[],
-                                      hipStream_t stream) {
-  try {
-    checkHandle(handle);
-    checkGridDesc(handle, grid_desc);
-    checkDataType(dtype);
-    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
-    if (halo_extents[0] == 0 && halo_extents[1] == 0 && halo_extents[2] == 0) {
-      if (parity != 1 && parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
-      if (centering != 0 && centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
-      if (clear != 0 && clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
-      return CUDECOMP_RESULT_SUCCESS;
-    }
-    if (!input) CD_INVALID_USAGE("input argument cannot be null");
-    if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
-    runHaloFold(handle, grid_desc, axis, input, dtype, parity, centering, clear, halo_extents, halo_periods, dim, padding, stream);
-  }
-  CD_API_CATCH()
-  return CUDECOMP_RESULT_SUCCESS;
-}
-
-#define CD_DEFINE_HALO_FOLD(NAME, AXIS)                                                                                   \
-  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,     \
-                        int32_t parity, int32_t centering, int32_t clear, const int32_t halo_extents[],                   \
-                        const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {            \
-    return haloFoldEntry(AXIS, handle, grid_desc, input, dtype, parity, centering, clear, halo_extents, halo_periods,     \
-                         dim, padding, stream);                                                                           \
+// cudecomp_halo_fold.h: the ghost cells the reflection writes are added onto their mirror images
+#define CD_DEFINE_HALO_FOLD(NAME, AXIS)                                                                                     \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,       \
+                        int32_t parity, int32_t centering, int32_t clear, const int32_t halo_extents[],                     \
+                        const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {              \
+    HaloCall c = haloCall(HaloOp::FOLD, AXIS, &input, nullptr, dtype, halo_extents, halo_periods, dim, padding, stream);    \
+    c.parity = parity;                                                                                                      \
+    c.clear = clear;                                                                                                        \
+    c.op.negate = parity == -1;                                                                                             \
+    c.op.centering = centering;                                                                                             \
+    c.op.clear = clear == 1;                                                                                                \
+    return haloApiEntry(handle, grid_desc, c);                                                                              \
   }
 CD_DEFINE_HALO_FOLD(cudecompAmdFoldHalosX, 0)
 CD_DEFINE_HALO_FOLD(cudecompAmdFoldHalosY, 1)
 CD_DEFINE_HALO_FOLD(cudecompAmdFoldHalosZ, 2)
 
-// cudecomp_halo_fields.h: the update of several pencils with one exchange.  The checks of haloEntry, in its order, with the list
-// of fields checked where the update checks `input`; all of it on the host, before anything is launched.
-static cudecompResult_t haloFieldsEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const inputs[],
-                                        int32_t n_fields, void* work, cudecompDataType_t dtype, const int32_t halo_extents[],
-                                        const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {
-  try {
-    checkHandle(handle);
-    checkGridDesc(handle, grid_desc);
-    checkDataType(dtype);
-    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
-    if (halo_extents[0] == 0 && halo_extents[1] == 0 && halo_extents[2] == 0) return CUDECOMP_RESULT_SUCCESS;
-    if (!inputs) CD_INVALID_USAGE("inputs argument cannot be null");
-    if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_HALO_FIELDS) CD_INVALID_USAGE("n_fields argument out of range");
-    for (int32_t i = 0; i < n_fields; ++i) {
-      if (!inputs[i]) CD_INVALID_USAGE("inputs argument cannot hold a null entry");
-      for (int32_t j = 0; j < i; ++j)
-        if (inputs[j] == inputs[i]) CD_INVALID_USAGE("inputs argument cannot hold the same field twice");
-    }
-    if (!work) CD_INVALID_USAGE("work argument cannot be null");
-    if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
-    runHaloFields(handle, grid_desc, axis, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, padding, stream);
-  }
-  CD_API_CATCH()
-  return CUDECOMP_RESULT_SUCCESS;
-}
-
+// cudecomp_halo_fields.h: the update of several pencils with one exchange
 #define CD_DEFINE_HALO_FIELDS(NAME, AXIS)                                                                                      \
   cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const inputs[], int32_t n_fields,         \
                         void* work, cudecompDataType_t dtype, const int32_t halo_extents[], const bool halo_periods[],         \
                         int32_t dim, const int32_t padding[], hipStream_t stream) {                                            \
-    return haloFieldsEntry(AXIS, handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, padding,   \
-                           stream);                                                                                            \
+    HaloCall c = haloCall(HaloOp::UPDATE, AXIS, inputs, work, dtype, halo_extents, halo_periods, dim, padding, stream);        \
+    c.op.n_fields = n_fields;                                                                                                  \
+    return haloApiEntry(handle, grid_desc, c, CUDECOMP_AMD_MAX_HALO_FIELDS);                                                   \
   }
 CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosX, 0)
 CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosY, 1)
 CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosZ, 2)
 
-// cudecomp_halo_accumulate_fields.h: the accumulation of several pencils with one exchange.  The checks of haloEntry, in its order,
-// with `clear` after halo_extents (also when every halo is zero) and the list of fields checked where the accumulation checks
-// `input`; all of it on the host, before anything is launched.
-static cudecompResult_t haloAccumulateFieldsEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const inputs[],
-                                                  int32_t n_fields, void* work, cudecompDataType_t dtype, const int32_t halo_extents[],
-                                                  const bool halo_periods[], int32_t dim, const int32_t padding[], int32_t clear,
-                                                  hipStream_t stream) {
-  try {
-    checkHandle(handle);
-    checkGridDesc(handle, grid_desc);
-    checkDataType(dtype);
-    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
-    if (clear != 0 && clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
-    if (halo_extents[0] == 0 && halo_extents[1] == 0 && halo_extents[2] == 0) return CUDECOMP_RESULT_SUCCESS;
-    if (!inputs) CD_INVALID_USAGE("inputs argument cannot be null");
-    if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS) CD_INVALID_USAGE("n_fields argument out of range");
-    for (int32_t i = 0; i < n_fields; ++i) {
-      if (!inputs[i]) CD_INVALID_USAGE("inputs argument cannot hold a null entry");
-      for (int32_t j = 0; j < i; ++j)
-        if (inputs[j] == inputs[i]) CD_INVALID_USAGE("inputs argument cannot hold the same field twice");
-    }
-    if (!work) CD_INVALID_USAGE("work argument cannot be null");
-    if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
-    runHaloAccumulateFields(handle, grid_desc, axis, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim, padding, clear != 0,
-                            stream);
-  }
-  CD_API_CATCH()
-  return CUDECOMP_RESULT_SUCCESS;
-}
-
+// cudecomp_halo_accumulate_fields.h: the accumulation of several pencils with one exchange
 #define CD_DEFINE_HALO_ACCUMULATE_FIELDS(NAME, AXIS)                                                                           \
   cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const inputs[], int32_t n_fields,         \
                         void* work, cudecompDataType_t dtype, const int32_t halo_extents[], const bool halo_periods[],         \
                         int32_t dim, const int32_t padding[], int32_t clear, hipStream_t stream) {                             \
-    return haloAccumulateFieldsEntry(AXIS, handle, grid_desc, inputs, n_fields, work, dtype, halo_extents, halo_periods, dim,  \
-                                     padding, clear, stream);                                                                  \
+    HaloCall c = haloCall(HaloOp::ACCUMULATE, AXIS, inputs, work, dtype, halo_extents, halo_periods, dim, padding, stream);    \
+    c.op.n_fields = n_fields;                                                                                                  \
+    c.clear = clear;                                                                                                           \
+    c.op.clear = clear != 0;                                                                                                   \
+    return haloApiEntry(handle, grid_desc, c, CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS, true);                                  \
   }
 CD_DEFINE_HALO_ACCUMULATE_FIELDS(cudecompAmdAccumulateFieldHalosX, 0)
 CD_DEFINE_HALO_ACCUMULATE_FIELDS(cudecompAmdAccumulateFieldHalosY, 1)

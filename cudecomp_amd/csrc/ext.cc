@@ -99,23 +99,46 @@ void exportHaloPlan(const HaloPlan& p, cudecompExtHaloPlan_t* out) {
     out->n_post = (int32_t)p.post.size();
     for (size_t i = 0; i < p.pre.size(); ++i) exportMove(p.pre[i], &out->pre[i]);
     for (size_t i = 0; i < p.post.size(); ++i) exportMove(p.post[i], &out->post[i]);
-    if (p.accumulate) {
+    const HaloOp& op = p.op;  // (cudecomp_ext.h: cudecompExtHaloPlan_t::reserved)
+    if (op.kind == HaloOp::ACCUMULATE) {
       out->reserved = 1 | (p.ordered ? 2 : 0);
       for (size_t i = 0; i < p.pre.size(); ++i)
         if (p.pre[i].add) out->reserved |= 16 << i;
       for (size_t i = 0; i < p.post.size(); ++i)
         if (p.post[i].add) out->reserved |= 64 << i;
     }
-    if (p.fill) out->reserved = 256;
-    if (p.reflect) out->reserved = 4096 | (p.negate ? 8192 : 0);
-    if (p.fold) out->reserved = 16384 | (p.negate ? 8192 : 0) | (p.ordered ? 2 : 0);
-    if (p.clear) {
+    if (op.kind == HaloOp::FILL) out->reserved = 256;
+    if (op.kind == HaloOp::REFLECT) out->reserved = 4096 | (op.negate ? 8192 : 0);
+    if (op.kind == HaloOp::FOLD) out->reserved = 16384 | (op.negate ? 8192 : 0) | (p.ordered ? 2 : 0);
+    if (op.clear) {
       out->reserved |= 512;
       for (size_t i = 0; i < p.pre.size(); ++i)
         if (p.pre[i].take) out->reserved |= 1024 << i;
       for (size_t i = 0; i < p.post.size(); ++i)
         if (p.post[i].take) CD_INTERNAL_ERROR("a move after the exchange clears its source");
     }
+}
+
+// the multi-field form: the single plan's fields (its flags included: 0 for an update), the number of fields and the slot length
+void exportHaloPlan(const HaloPlan& p, cudecompExtHaloFieldsPlan_t* out) {
+  cudecompExtHaloPlan_t single;
+  exportHaloPlan(p, &single);
+  std::memset(out, 0, sizeof(*out));
+  out->kind = single.kind;
+  out->comm_axis = single.comm_axis;
+  out->n_fields = p.op.n_fields;
+  out->reserved = single.reserved;
+  out->face_elements = single.face_elements;
+  out->slot_elements = p.slot_elements;
+  for (int i = 0; i < 2; ++i) {
+    out->neighbor[i] = single.neighbor[i];
+    out->send_off[i] = single.send_off[i];
+    out->recv_off[i] = single.recv_off[i];
+    out->pre[i] = single.pre[i];
+    out->post[i] = single.post[i];
+  }
+  out->n_pre = single.n_pre;
+  out->n_post = single.n_post;
 }
 
 GridShape shapeFromSpec(const cudecompExtGridSpec_t* spec) {
@@ -191,6 +214,42 @@ std::vector<Move3D> importMoves(const cudecompExtMove_t* moves, int32_t n, int32
     }
   }
   return out;
+}
+
+// Every cudecompExtPlanHalo* function: the grid given by value, the common checks, the defaults for periods and padding, the plan
+// of `op`, its export.  `clear` is the caller's number behind op.clear: refused before the plan is built (clear_first) or after
+// the plan's own refusals.
+template <typename Out>
+cudecompResult_t planHaloOp(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[], const bool periods[],
+                                   int32_t dim, const int32_t pad[], const HaloOp& op, bool force_packed, Out* out, int32_t clear = 0,
+                                   bool clear_first = false, bool self_exchange = false) {
+  try {
+    const GridShape g = shapeFromSpec(grid);
+    if (!out || !halo) CD_INVALID_USAGE("null argument");
+    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
+    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
+    if (clear_first && clear != 0 && clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
+    const int32_t zero[3] = {0, 0, 0};
+    const bool none[3] = {false, false, false};
+    const HaloPlan p = buildHaloOpPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, op, force_packed, self_exchange);
+    if (clear != 0 && clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
+    exportHaloPlan(p, out);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+HaloOp haloOp(HaloOp::Kind kind, bool clear = false, int centering = 0, bool negate = false, int n_fields = 1) {
+  HaloOp op;
+  op.kind = kind;
+  op.clear = clear;
+  op.centering = centering;
+  op.negate = negate;
+  op.n_fields = n_fields;
+  return op;
 }
 
 }  // namespace
@@ -358,125 +417,38 @@ cudecompResult_t cudecompExtPlanRelay(const cudecompExtGridSpec_t* grid, int32_t
 cudecompResult_t cudecompExtPlanHalo(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                      const bool periods[], int32_t dim, const int32_t pad[], int32_t force_packed,
                                      cudecompExtHaloPlan_t* out) {
-  try {
-    const GridShape g = shapeFromSpec(grid);
-    if (!out || !halo) CD_INVALID_USAGE("null argument");
-    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
-    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
-    const int32_t zero[3] = {0, 0, 0};
-    const bool none[3] = {false, false, false};
-    const HaloPlan p = buildHaloPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, force_packed != 0);
-    exportHaloPlan(p, out);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  return planHaloOp(grid, rank, axis, halo, periods, dim, pad, haloOp(HaloOp::UPDATE), force_packed != 0, out);
 }
 
 cudecompResult_t cudecompExtPlanHaloAccumulate(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
                                                const int32_t halo[], const bool periods[], int32_t dim, const int32_t pad[],
                                                int32_t force_packed, cudecompExtHaloPlan_t* out) {
-  try {
-    const GridShape g = shapeFromSpec(grid);
-    if (!out || !halo) CD_INVALID_USAGE("null argument");
-    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
-    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
-    const int32_t zero[3] = {0, 0, 0};
-    const bool none[3] = {false, false, false};
-    const HaloPlan p =
-        buildHaloAccumulatePlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, force_packed != 0);
-    exportHaloPlan(p, out);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  return planHaloOp(grid, rank, axis, halo, periods, dim, pad, haloOp(HaloOp::ACCUMULATE), force_packed != 0, out);
 }
 
 cudecompResult_t cudecompExtPlanHaloAccumulateClear(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
                                                     const int32_t halo[], const bool periods[], int32_t dim, const int32_t pad[],
                                                     int32_t force_packed, cudecompExtHaloPlan_t* out) {
-  try {
-    const GridShape g = shapeFromSpec(grid);
-    if (!out || !halo) CD_INVALID_USAGE("null argument");
-    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
-    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
-    const int32_t zero[3] = {0, 0, 0};
-    const bool none[3] = {false, false, false};
-    const HaloPlan p =
-        buildHaloAccumulateClearPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, force_packed != 0);
-    exportHaloPlan(p, out);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  return planHaloOp(grid, rank, axis, halo, periods, dim, pad, haloOp(HaloOp::ACCUMULATE, true), force_packed != 0, out);
 }
 
 cudecompResult_t cudecompExtPlanHaloFill(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                          const bool periods[], int32_t dim, const int32_t pad[], int32_t force_packed,
                                          cudecompExtHaloPlan_t* out) {
-  try {
-    const GridShape g = shapeFromSpec(grid);
-    if (!out || !halo) CD_INVALID_USAGE("null argument");
-    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
-    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
-    const int32_t zero[3] = {0, 0, 0};
-    const bool none[3] = {false, false, false};
-    const HaloPlan p = buildHaloFillPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, force_packed != 0);
-    exportHaloPlan(p, out);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  return planHaloOp(grid, rank, axis, halo, periods, dim, pad, haloOp(HaloOp::FILL), force_packed != 0, out);
 }
 
 cudecompResult_t cudecompExtPlanHaloReflect(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                             const bool periods[], int32_t dim, const int32_t pad[], int32_t centering,
                                             int32_t negate, cudecompExtHaloPlan_t* out) {
-  try {
-    const GridShape g = shapeFromSpec(grid);
-    if (!out || !halo) CD_INVALID_USAGE("null argument");
-    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
-    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
-    const int32_t zero[3] = {0, 0, 0};
-    const bool none[3] = {false, false, false};
-    const HaloPlan p = buildHaloReflectPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, centering, negate != 0);
-    exportHaloPlan(p, out);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  return planHaloOp(grid, rank, axis, halo, periods, dim, pad, haloOp(HaloOp::REFLECT, false, centering, negate != 0), false, out);
 }
 
 cudecompResult_t cudecompExtPlanHaloFold(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                          const bool periods[], int32_t dim, const int32_t pad[], int32_t centering, int32_t negate,
                                          int32_t clear, cudecompExtHaloPlan_t* out) {
-  try {
-    const GridShape g = shapeFromSpec(grid);
-    if (!out || !halo) CD_INVALID_USAGE("null argument");
-    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
-    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
-    const int32_t zero[3] = {0, 0, 0};
-    const bool none[3] = {false, false, false};
-    const HaloPlan p = buildHaloFoldPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, centering, negate != 0,
-                                         clear == 1);
-    if (clear != 0 && clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");  // (after the reflection's refusals)
-    exportHaloPlan(p, out);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  // (a bad `clear` is refused after the reflection's refusals)
+  return planHaloOp(grid, rank, axis, halo, periods, dim, pad, haloOp(HaloOp::FOLD, clear == 1, centering, negate != 0), false, out, clear);
 }
 
 cudecompResult_t cudecompExtPencilInfo(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
@@ -954,76 +926,14 @@ static std::vector<Move3D> importFieldMoves(const cudecompExtMove_t* moves, int3
 cudecompResult_t cudecompExtPlanHaloFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                            const bool periods[], int32_t dim, const int32_t pad[], int32_t n_fields,
                                            int32_t force_packed, cudecompExtHaloFieldsPlan_t* out) {
-  try {
-    const GridShape g = shapeFromSpec(grid);
-    if (!out || !halo) CD_INVALID_USAGE("null argument");
-    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
-    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
-    const int32_t zero[3] = {0, 0, 0};
-    const bool none[3] = {false, false, false};
-    const HaloFieldsPlan fp = buildHaloFieldsPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, n_fields,
-                                                  force_packed != 0);
-    const HaloPlan& p = fp.base;
-    std::memset(out, 0, sizeof(*out));
-    out->kind = (int32_t)p.kind;
-    out->comm_axis = p.comm_axis;
-    out->n_fields = fp.n_fields;
-    out->face_elements = p.face_elements;
-    out->slot_elements = fp.slot_elements;
-    for (int i = 0; i < 2; ++i) {
-      out->neighbor[i] = p.neighbor[i];
-      out->send_off[i] = p.send_off[i];
-      out->recv_off[i] = p.recv_off[i];
-    }
-    out->n_pre = (int32_t)p.pre.size();
-    out->n_post = (int32_t)p.post.size();
-    for (size_t i = 0; i < p.pre.size(); ++i) exportMove(p.pre[i], &out->pre[i]);
-    for (size_t i = 0; i < p.post.size(); ++i) exportMove(p.post[i], &out->post[i]);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  return planHaloOp(grid, rank, axis, halo, periods, dim, pad, haloOp(HaloOp::UPDATE, false, 0, false, n_fields), force_packed != 0, out);
 }
 
 cudecompResult_t cudecompExtPlanHaloAccumulateFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                                      const bool periods[], int32_t dim, const int32_t pad[], int32_t n_fields,
                                                      int32_t clear, int32_t self_exchange, cudecompExtHaloFieldsPlan_t* out) {
-  try {
-    const GridShape g = shapeFromSpec(grid);
-    if (!out || !halo) CD_INVALID_USAGE("null argument");
-    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
-    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
-    if (clear != 0 && clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
-    const int32_t zero[3] = {0, 0, 0};
-    const bool none[3] = {false, false, false};
-    const HaloFieldsPlan fp = buildHaloAccumulateFieldsPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero,
-                                                            n_fields, clear != 0, self_exchange != 0);
-    cudecompExtHaloPlan_t single;  // (the flags of the single plans: cudecompExtHaloPlan_t::reserved)
-    exportHaloPlan(fp.base, &single);
-    std::memset(out, 0, sizeof(*out));
-    out->kind = single.kind;
-    out->comm_axis = single.comm_axis;
-    out->n_fields = fp.n_fields;
-    out->reserved = single.reserved;
-    out->face_elements = single.face_elements;
-    out->slot_elements = fp.slot_elements;
-    for (int i = 0; i < 2; ++i) {
-      out->neighbor[i] = single.neighbor[i];
-      out->send_off[i] = single.send_off[i];
-      out->recv_off[i] = single.recv_off[i];
-      out->pre[i] = single.pre[i];
-      out->post[i] = single.post[i];
-    }
-    out->n_pre = single.n_pre;
-    out->n_post = single.n_post;
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  return planHaloOp(grid, rank, axis, halo, periods, dim, pad, haloOp(HaloOp::ACCUMULATE, clear != 0, 0, false, n_fields), true, out, clear,
+                    true, self_exchange != 0);
 }
 
 // the operation of cudecompExtRunFieldMovesOp / cudecompExtDescribeFieldMovesOp onto an imported list; *arith as importMoves sets it

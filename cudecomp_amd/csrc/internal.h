@@ -139,18 +139,9 @@ struct cudecompGridDesc {
   using TransposeKey = std::tuple<int, std::array<int32_t, 12>, bool, bool, bool>;
   std::map<TransposeKey, cudecomp::TransposePlan> transpose_plans;
   using HaloKey = std::tuple<int, int, std::array<int32_t, 6>, std::array<bool, 3>, bool>;
-  std::map<HaloKey, cudecomp::HaloPlan> halo_plans;
-  std::map<HaloKey, cudecomp::HaloPlan> halo_accumulate_plans;  // cudecompAmdAccumulateHalos*: the same key, the other operation
-  std::map<HaloKey, cudecomp::HaloPlan> halo_fill_plans;        // cudecompAmdFillHalos*: likewise
-  std::map<HaloKey, cudecomp::HaloPlan> halo_accumulate_clear_plans;  // cudecompAmdAccumulateAndClearHalos*: likewise
-  // cudecompAmdReflectHalos*: the same key (its last entry unused: always false) plus (centering, sign flip)
-  std::map<std::tuple<HaloKey, int, bool>, cudecomp::HaloPlan> halo_reflect_plans;
-  // cudecompAmdFoldHalos*: the same key plus (centering, sign flip, clear)
-  std::map<std::tuple<HaloKey, int, bool, bool>, cudecomp::HaloPlan> halo_fold_plans;
-  // cudecompAmdUpdateFieldHalos* with two fields or more: the same key plus n_fields
-  std::map<std::tuple<HaloKey, int>, cudecomp::HaloFieldsPlan> halo_fields_plans;
-  // cudecompAmdAccumulateFieldHalos*: the key, the number of fields and `clear`
-  std::map<std::tuple<HaloKey, int, bool>, cudecomp::HaloFieldsPlan> halo_accumulate_fields_plans;
+  // every halo family in one map: HaloKey plus the operation.  The last entry of HaloKey (force_packed) is the family's own: update,
+  // accumulation and fill usesPeerTransport(...), reflection and folding false, two fields or more true (halo.cc)
+  std::map<std::pair<HaloKey, cudecomp::HaloOp>, cudecomp::HaloPlan> halo_plans;
   // cudecompAmdTransposeFields* with two fields or more: TransposeKey (never pipelined) plus n_fields
   std::map<std::tuple<TransposeKey, int>, cudecomp::TransposeFieldsPlan> transpose_fields_plans;
 
@@ -270,30 +261,22 @@ inline bool usesPeerTransport(cudecompHandle_t h, cudecompHaloCommBackend_t b) {
 void runTranspose(cudecompHandle_t handle, cudecompGridDesc_t gd, TransposeOp op, void* input, void* output, void* work,
                   cudecompDataType_t dtype, const int32_t* in_halo, const int32_t* out_halo, const int32_t* in_pad,
                   const int32_t* out_pad, hipStream_t stream);
-void runHalo(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, void* work,
-             cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
-             hipStream_t stream);
-void runHaloAccumulate(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, void* work,
-                       cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
-                       hipStream_t stream);
-// ... and zero bytes into the ghost cells it has read (cudecompAmdAccumulateAndClearHalos*): the same sequence, launch grouping and exchange
-void runHaloAccumulateClear(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, void* work,
-                            cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
-                            hipStream_t stream);
-void runHaloFill(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, const void* value,
-                 const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream);
-void runHaloReflect(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, int parity,
-                    int centering, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream);
-void runHaloFold(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, int parity,
-                 int centering, int clear, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream);
-// cudecompAmdUpdateFieldHalos*: n_fields pencils, one exchange (n_fields == 1 IS runHalo)
-void runHaloFields(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* const* inputs, int n_fields, void* work,
-                   cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
-                   hipStream_t stream);
-// cudecompAmdAccumulateFieldHalos*: n_fields pencils, one exchange (n_fields == 1 IS runHaloAccumulate / runHaloAccumulateClear)
-void runHaloAccumulateFields(cudecompHandle_t handle, cudecompGridDesc_t gd, int axis, void* const* inputs, int n_fields, void* work,
-                             cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
-                             bool clear, hipStream_t stream);
+// halo.cc: everything a halo call passes.  `op.centering` and `op.n_fields` are the caller's numbers as they came; `parity` and
+// `clear` are the raw arguments behind op.negate and op.clear (REFLECT, FOLD: checked late, by the runner)
+struct HaloCall {
+  HaloOp op;
+  int axis = 0, dim = 0;
+  void* const* fields = nullptr;  // op.n_fields pencils (one entry for the single calls)
+  void* work = nullptr;
+  cudecompDataType_t dtype = CUDECOMP_FLOAT;
+  const void* value = nullptr;  // FILL
+  int parity = 1, clear = 0;
+  const int32_t* halo = nullptr;
+  const bool* periods = nullptr;
+  const int32_t* pad = nullptr;
+  hipStream_t stream = nullptr;
+};
+void runHaloOp(cudecompHandle_t handle, cudecompGridDesc_t gd, const HaloCall& call);
 
 // cudecompAmdTransposeFields*: n_fields pencils, one exchange (n_fields == 1 IS runTranspose)
 void runTransposeFields(cudecompHandle_t handle, cudecompGridDesc_t gd, TransposeOp op, void* const* inputs, void* const* outputs,

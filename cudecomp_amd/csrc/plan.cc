@@ -403,7 +403,7 @@ HaloPlan buildHaloAccumulatePlan(const GridShape& g, int rank, int axis, int dim
   HaloPlan p;
   p.axis = axis;
   p.dim = dim;
-  p.accumulate = true;
+  p.op.kind = HaloOp::ACCUMULATE;
   const auto pidx = gridIndexOfRank(g, rank);
   const Pencil h = makePencil(g, pidx, axis, halo, nullptr);  // extents of what is exchanged
   const Pencil hp = makePencil(g, pidx, axis, halo, pad);     // strides of the user's buffer
@@ -469,7 +469,7 @@ HaloPlan buildHaloAccumulatePlan(const GridShape& g, int rank, int axis, int dim
 HaloPlan buildHaloAccumulateClearPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
                                       const int32_t* pad, bool force_packed, bool self_exchange) {
   HaloPlan p = buildHaloAccumulatePlan(g, rank, axis, dim, halo, periods, pad, force_packed, self_exchange);
-  p.clear = true;
+  p.op.clear = true;
   for (Move3D& m : p.pre) {  // (SELF_PERIODIC: the wrap additions; PACKED: the packs -- the moves that read the pencil)
     if (m.src_buf != BUF_IN) CD_INTERNAL_ERROR("the first phase of a halo accumulation reads something other than the pencil");
     m.take = true;
@@ -485,7 +485,7 @@ HaloPlan buildHaloFillPlan(const GridShape& g, int rank, int axis, int dim, cons
   HaloPlan p;
   p.axis = axis;
   p.dim = dim;
-  p.fill = true;
+  p.op.kind = HaloOp::FILL;
   p.comm_axis = u.comm_axis;
   p.neighbor[0] = u.neighbor[0];
   p.neighbor[1] = u.neighbor[1];
@@ -531,8 +531,9 @@ HaloPlan buildHaloReflectPlan(const GridShape& g, int rank, int axis, int dim, c
   HaloPlan p;
   p.axis = axis;
   p.dim = dim;
-  p.reflect = true;
-  p.negate = negate;
+  p.op.kind = HaloOp::REFLECT;
+  p.op.centering = centering;
+  p.op.negate = negate;
   p.comm_axis = commAxisOfDim(axis, dim);
   p.neighbor[0] = u.neighbor[0];
   p.neighbor[1] = u.neighbor[1];
@@ -573,9 +574,10 @@ HaloPlan buildHaloFoldPlan(const GridShape& g, int rank, int axis, int dim, cons
   HaloPlan p;
   p.axis = axis;
   p.dim = dim;
-  p.fold = true;
-  p.negate = negate;
-  p.clear = clear;
+  p.op.kind = HaloOp::FOLD;
+  p.op.centering = centering;
+  p.op.negate = negate;
+  p.op.clear = clear;
   p.comm_axis = r.comm_axis;
   p.neighbor[0] = r.neighbor[0];
   p.neighbor[1] = r.neighbor[1];
@@ -602,15 +604,14 @@ HaloPlan buildHaloFoldPlan(const GridShape& g, int rank, int axis, int dim, cons
 }
 
 // the slots of a packed single plan are alignElements(face) apart: move them alignElements(n_fields * face) apart
-static void relayFieldSlots(HaloFieldsPlan& fp) {
-  HaloPlan& p = fp.base;
-  const int n_fields = fp.n_fields;
+static void relayFieldSlots(HaloPlan& p) {
+  const int n_fields = p.op.n_fields;
   const i64 single = alignElements(p.face_elements);
-  fp.slot_elements = n_fields == 1 ? single : alignElements((i64)n_fields * p.face_elements);
+  p.slot_elements = n_fields == 1 ? single : alignElements((i64)n_fields * p.face_elements);
   if (n_fields == 1) return;
   auto moved = [&](i64 off) {
     if (off % single != 0 || off / single > 3) CD_INTERNAL_ERROR("a packed halo plan with an unexpected workspace layout");
-    return off / single * fp.slot_elements;
+    return off / single * p.slot_elements;
   };
   for (int i = 0; i < 2; ++i) {
     p.send_off[i] = moved(p.send_off[i]);
@@ -626,28 +627,36 @@ static void relayFieldSlots(HaloFieldsPlan& fp) {
   }
 }
 
-HaloFieldsPlan buildHaloFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
-                                   const int32_t* pad, int n_fields, bool force_packed, bool self_exchange) {
+HaloPlan buildHaloFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                             const int32_t* pad, int n_fields, bool force_packed, bool self_exchange) {
   if (n_fields < 1) CD_INVALID_USAGE("n_fields argument out of range");
-  HaloFieldsPlan fp;
-  fp.n_fields = n_fields;
-  fp.base = buildHaloPlan(g, rank, axis, dim, halo, periods, pad, force_packed || n_fields >= 2, self_exchange);
-  HaloPlan& p = fp.base;
+  HaloPlan p = buildHaloPlan(g, rank, axis, dim, halo, periods, pad, force_packed || n_fields >= 2, self_exchange);
+  p.op.n_fields = n_fields;
   if (p.kind == HaloPlan::DIRECT && n_fields >= 2) CD_INTERNAL_ERROR("a multi-field halo plan came out direct");
-  if (p.kind != HaloPlan::PACKED) return fp;
-  relayFieldSlots(fp);
-  return fp;
+  if (p.kind == HaloPlan::PACKED) relayFieldSlots(p);
+  return p;
 }
 
-HaloFieldsPlan buildHaloAccumulateFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
-                                             const int32_t* pad, int n_fields, bool clear, bool self_exchange) {
+HaloPlan buildHaloAccumulateFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                       const int32_t* pad, int n_fields, bool clear, bool self_exchange) {
   if (n_fields < 1) CD_INVALID_USAGE("n_fields argument out of range");
-  HaloFieldsPlan fp;
-  fp.n_fields = n_fields;
-  fp.base = (clear ? buildHaloAccumulateClearPlan : buildHaloAccumulatePlan)(g, rank, axis, dim, halo, periods, pad, true, self_exchange);
-  if (fp.base.kind == HaloPlan::DIRECT) CD_INTERNAL_ERROR("a halo accumulation plan came out direct");
-  if (fp.base.kind == HaloPlan::PACKED) relayFieldSlots(fp);
-  return fp;
+  HaloPlan p = (clear ? buildHaloAccumulateClearPlan : buildHaloAccumulatePlan)(g, rank, axis, dim, halo, periods, pad, true, self_exchange);
+  p.op.n_fields = n_fields;
+  if (p.kind == HaloPlan::DIRECT) CD_INTERNAL_ERROR("a halo accumulation plan came out direct");
+  if (p.kind == HaloPlan::PACKED) relayFieldSlots(p);
+  return p;
+}
+
+HaloPlan buildHaloOpPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods, const int32_t* pad,
+                         const HaloOp& op, bool force_packed, bool self_exchange) {
+  switch (op.kind) {
+    case HaloOp::UPDATE: return buildHaloFieldsPlan(g, rank, axis, dim, halo, periods, pad, op.n_fields, force_packed, self_exchange);
+    case HaloOp::ACCUMULATE: return buildHaloAccumulateFieldsPlan(g, rank, axis, dim, halo, periods, pad, op.n_fields, op.clear, self_exchange);
+    case HaloOp::FILL: return buildHaloFillPlan(g, rank, axis, dim, halo, periods, pad, force_packed, self_exchange);
+    case HaloOp::REFLECT: return buildHaloReflectPlan(g, rank, axis, dim, halo, periods, pad, op.centering, op.negate, self_exchange);
+    case HaloOp::FOLD: return buildHaloFoldPlan(g, rank, axis, dim, halo, periods, pad, op.centering, op.negate, op.clear, self_exchange);
+  }
+  CD_INTERNAL_ERROR("unknown halo operation");
 }
 
 int normalizeMove(Move3D& m) {

@@ -12,6 +12,7 @@
 // include/internal/transpose.h:196-905, include/internal/halo.h:41-315).  The plan is derived from
 // the decomposition itself rather than transcribed from that code: see DESIGN.md "Plan".
 #pragma once
+#include <tuple>
 #include <vector>
 
 #include "decomp.h"
@@ -186,6 +187,19 @@ RelayPlan buildRelayPlan(const GridShape& g, int nranks, int rank, TransposeOp o
                          const int32_t* out_halo, const int32_t* in_pad, const int32_t* out_pad, bool inplace,
                          const TransportTraits& traits, int npergroup);
 
+// What a halo call is: the operation and the arguments that change its plan.  Every builder below writes the record of its plan;
+// buildHaloOpPlan goes the other way.  Ordered, so that it can be part of the key of the plan cache (internal.h).
+struct HaloOp {
+  enum Kind { UPDATE, ACCUMULATE, FILL, REFLECT, FOLD } kind = UPDATE;
+  bool clear = false;  // ACCUMULATE, FOLD: the ghost cells read are cleared
+  int centering = 0;   // REFLECT, FOLD
+  bool negate = false; // REFLECT, FOLD: parity -1
+  int n_fields = 1;    // UPDATE, ACCUMULATE (1 otherwise)
+  bool operator<(const HaloOp& o) const {
+    return std::tie(kind, clear, centering, negate, n_fields) < std::tie(o.kind, o.clear, o.centering, o.negate, o.n_fields);
+  }
+};
+
 struct HaloPlan {
   int axis = 0, dim = 0;
   enum Kind { NONE, SELF_PERIODIC, PACKED, DIRECT } kind = NONE;
@@ -198,14 +212,10 @@ struct HaloPlan {
   i64 face_elements = 0;
   BufId xbuf = BUF_WORK;
   i64 send_off[2] = {0, 0}, recv_off[2] = {0, 0};
-  // accumulation plans (buildHaloAccumulatePlan) only
-  bool accumulate = false;
-  bool ordered = false;  // the destinations of the two add-moves overlap (interior narrower than two halos): one launch each, in order
-  bool fill = false;     // fill plans (buildHaloFillPlan) only
-  bool clear = false;    // fused accumulate-and-clear plans (buildHaloAccumulateClearPlan) only
-  bool reflect = false;  // reflection plans (buildHaloReflectPlan) only
-  bool negate = false;   // ... whose moves flip the sign bits (parity -1); fold plans likewise
-  bool fold = false;     // fold plans (buildHaloFoldPlan) only; `ordered` and `clear` as for accumulation plans
+  HaloOp op;             // the operation the plan was built for
+  bool ordered = false;  // accumulation and fold plans: the destinations of the two add-moves overlap (interior narrower than two
+                         // halos; fold: n < 4h + 2c): one launch each, in order
+  i64 slot_elements = 0; // multi-field builders, PACKED: the length of one workspace slot (buildHaloFieldsPlan)
 };
 
 HaloPlan buildHaloPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
@@ -263,32 +273,32 @@ HaloPlan buildHaloFoldPlan(const GridShape& g, int rank, int axis, int dim, cons
 // halos and padding updated by one exchange.  Derived from buildHaloPlan(..., force_packed = true for n_fields >= 2): its refusals,
 // neighbours, faces and "which cells" hold by construction.  Kinds: NONE, SELF_PERIODIC (the two wrap copies, pencil -> pencil,
 // carried out for every field) or PACKED -- never DIRECT for n_fields >= 2: one message per direction is the point, and the
-// exchange describes one contiguous piece per direction.  The moves in `base` are those of field 0: an end in BUF_IN is "field
-// f's pencil" at the same offset, an end in BUF_WORK lies at its offset + f * face_elements.  Workspace: [send low | send high |
+// exchange describes one contiguous piece per direction.  The moves are those of field 0 (HaloOp::n_fields says of how many): an end
+// in BUF_IN is "field f's pencil" at the same offset, an end in BUF_WORK lies at its offset + f * face_elements.  Workspace: [send low | send high |
 // recv low | recv high], each slot slot_elements = alignElements(n_fields * face_elements) long -- never more than n_fields times
 // haloWorkspaceElements.  Neighbours along `dim` share the extents of the other two dims, so the slot size and the offsets are the
 // same on both ends of every exchange (the one-sided transport needs that).  The exchange moves n_fields * face_elements elements
 // per direction, from send_off[i] to the neighbour's recv_off[1 - i].  n_fields == 1: the plan of buildHaloPlan with the caller's
 // force_packed, unchanged.
-struct HaloFieldsPlan {
-  HaloPlan base;
-  int n_fields = 1;
-  i64 slot_elements = 0;
-};
-HaloFieldsPlan buildHaloFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
-                                   const int32_t* pad, int n_fields, bool force_packed, bool self_exchange = false);
+HaloPlan buildHaloFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                             const int32_t* pad, int n_fields, bool force_packed, bool self_exchange = false);
 
 // Multi-field halo ACCUMULATION along `dim` (include/cudecomp_halo_accumulate_fields.h has the contract): `n_fields` pencils of one
 // descriptor, axis, halos and padding accumulated by one exchange, with (`clear`) or without the clearing of the ghost cells read.
 // Derived from buildHaloAccumulatePlan / buildHaloAccumulateClearPlan: refusals, neighbours, slabs, `ordered` and the add / take
 // flags of the moves are the single call's by construction.  Kinds: NONE, SELF_PERIODIC (the two wrap additions, pencil -> pencil,
-// carried out for every field) or PACKED.  The moves in `base` are those of field 0 under the slot layout of buildHaloFieldsPlan:
+// carried out for every field) or PACKED.  The moves are those of field 0 under the slot layout of buildHaloFieldsPlan:
 // an end in BUF_IN is "field f's pencil" at the same offset, an end in BUF_WORK lies at its offset + f * face_elements; workspace
 // [send low | send high | recv low | recv high], each slot slot_elements = alignElements(n_fields * face_elements) long; the
 // exchange moves n_fields * face_elements elements per direction, from send_off[i] to the neighbour's recv_off[1 - i].
 // n_fields == 1: the single plan, unchanged.
-HaloFieldsPlan buildHaloAccumulateFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
-                                             const int32_t* pad, int n_fields, bool clear, bool self_exchange = false);
+HaloPlan buildHaloAccumulateFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                       const int32_t* pad, int n_fields, bool clear, bool self_exchange = false);
+
+// The plan of the halo call `op`, by the builder of its family: UPDATE buildHaloFieldsPlan, ACCUMULATE buildHaloAccumulateFieldsPlan
+// (one field: the single plans, unchanged), FILL, REFLECT and FOLD their own.  `force_packed` reaches the builders that take it.
+HaloPlan buildHaloOpPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods, const int32_t* pad,
+                         const HaloOp& op, bool force_packed, bool self_exchange = false);
 
 // Number of stages every member of the communicator arrives at without talking: at most `wanted`, at most the smallest
 // chunk extent, at most 14 (flag steps), and no stage smaller than `min_stage_bytes` of the largest pencil (below that the extra

@@ -1919,7 +1919,7 @@ void haloExchange(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloExchange&
 #ifdef CUDECOMP_WITH_MPI
   if (haloBackendIsMpi(backend) && h->boot->nativeComm()) return mpiHaloExchange(h, x, stream);
 #endif
-  // The one-sided transport only runs packed plans (runHalo: force_packed), whose faces were packed on `stream`
+  // The one-sided transport only runs packed plans (runHaloOp: force_packed), whose faces were packed on `stream`
   // before this call; the epoch starts here, i.e. "my halo slots are free" is published after the packs -- harmless,
   // the overlapped variant below publishes it before them.
   const PeerCall call = haloBegin(h, gd, x, backend, stream);

@@ -1,4 +1,4 @@
-// transpose.cc -- executes transpose and halo plans: bind pointers, launch the move kernels, run the
+// transpose.cc -- executes transpose plans (halo plans: halo.cc): bind pointers, launch the move kernels, run the
 // exchange.  The algorithmic content lives in plan.cc (what moves where) and kernels.cc / kernels_*.hip (how).
 #include <cstdio>
 
@@ -476,317 +476,5 @@ void executeTranspose(cudecompHandle_t h, cudecompGridDesc_t gd, const Transpose
 }
 
 }  // namespace
-
-// the exchange of a halo plan (update or accumulation): send slot / face i travels to neighbour i and lands in ITS receive slot
-// 1 - i (update: my low face fills the low neighbour's HIGH halo; accumulation: my low halo is the addend of its HIGH face)
-static HaloExchange haloExchangeOf(const HaloPlan& plan, void* const bufs[3], int es) {
-  HaloExchange x;
-  x.send = x.recv = static_cast<char*>(bufs[plan.xbuf]);
-  for (int i = 0; i < 2; ++i) {
-    x.send_off[i] = plan.send_off[i] * es;
-    x.recv_off[i] = plan.recv_off[i] * es;
-    x.remote_off[i] = plan.recv_off[1 - i] * es;
-    x.neighbor[i] = plan.neighbor[i];
-  }
-  x.bytes = plan.face_elements * es;
-  x.comm_axis = plan.comm_axis;
-  return x;
-}
-
-void runHalo(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, void* work, cudecompDataType_t dtype,
-             const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
-  const int es = elementSize(dtype);
-  const auto backend = gd->config.halo_comm_backend;
-  const bool force_packed = usesPeerTransport(h, backend);
-
-  const auto hh = arr3(halo), pp = arr3(pad);
-  std::array<bool, 3> per{false, false, false};
-  if (periods)
-    for (int i = 0; i < 3; ++i) per[i] = periods[i];
-  const cudecompGridDesc::HaloKey key{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, force_packed};
-  auto it = gd->halo_plans.find(key);
-  if (it == gd->halo_plans.end()) {
-    HaloPlan p = buildHaloPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), force_packed, h->self_exchange);
-    it = gd->halo_plans.emplace(key, std::move(p)).first;
-  }
-  const HaloPlan& plan = it->second;
-  if (plan.kind == HaloPlan::NONE) return;
-
-  ensureDevice(h);
-  void* bufs[3] = {input, input, work};
-  int64_t wire_bytes = 0;
-  if (plan.kind != HaloPlan::SELF_PERIODIC)
-    for (int i = 0; i < 2; ++i)
-      if (plan.neighbor[i] >= 0) wire_bytes += plan.face_elements * es;
-  hipEvent_t* pev = perfBeginHalo(h, gd, axis, dim, dtype, hh, per, pp, wire_bytes, stream);
-  if (plan.kind == HaloPlan::SELF_PERIODIC) {
-    launchMoves(plan.pre.data(), (int)plan.pre.size(), bufs, es, stream, &h->tuning);
-    perfMark(pev, 1, stream);
-    perfMark(pev, 2, stream);
-    perfMark(pev, 3, stream);
-    return;
-  }
-  const HaloExchange x = haloExchangeOf(plan, bufs, es);
-  // packed faces: pack, exchange and unpack overlap face by face (env CUDECOMP_DISABLE_HALO_OVERLAP=1 restores the
-  // plain pack -> exchange -> unpack sequence of the reference, halo.h:200-260)
-  if (plan.kind == HaloPlan::PACKED && !h->halo_overlap_disable) {
-    perfMark(pev, 1, stream);
-    if (haloExchangePackedOverlapped(h, gd, x, plan, bufs, es, backend, stream)) {
-      perfMark(pev, 2, stream);
-      perfMark(pev, 3, stream);
-      return;
-    }
-  }
-  if (plan.kind == HaloPlan::PACKED) launchMoves(plan.pre.data(), (int)plan.pre.size(), bufs, es, stream, &h->tuning);
-  perfMark(pev, 1, stream);
-  haloExchange(h, gd, x, backend, stream);
-  perfMark(pev, 2, stream);
-  if (plan.kind == HaloPlan::PACKED) launchMoves(plan.post.data(), (int)plan.post.size(), bufs, es, stream, &h->tuning);
-  perfMark(pev, 3, stream);
-}
-
-// Multi-field halo update (cudecompAmdUpdateFieldHalos*): the plain sequence pack all fields (one launch) -> one exchange of
-// n_fields faces per direction -> unpack all fields (one launch); self-periodic: the wrap copies of all fields in one launch.
-// The overlapped path of runHalo (haloExchangePackedOverlapped) is not used: it runs the plan's moves itself through bufs[3].
-// Not sampled by the performance report.  One field: runHalo itself.
-void runHaloFields(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* const* inputs, int n_fields, void* work,
-                   cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
-  if (n_fields == 1) return runHalo(h, gd, axis, inputs[0], work, dtype, halo, periods, dim, pad, stream);
-  const int es = elementSize(dtype);
-  const auto backend = gd->config.halo_comm_backend;
-  const bool force_packed = true;  // (always, for two fields or more)
-
-  const auto hh = arr3(halo), pp = arr3(pad);
-  std::array<bool, 3> per{false, false, false};
-  if (periods)
-    for (int i = 0; i < 3; ++i) per[i] = periods[i];
-  const cudecompGridDesc::HaloKey hkey{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, force_packed};
-  const std::tuple<cudecompGridDesc::HaloKey, int> key{hkey, n_fields};
-  auto it = gd->halo_fields_plans.find(key);
-  if (it == gd->halo_fields_plans.end()) {
-    HaloFieldsPlan p = buildHaloFieldsPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), n_fields, force_packed,
-                                           h->self_exchange);
-    it = gd->halo_fields_plans.emplace(key, std::move(p)).first;
-  }
-  const HaloFieldsPlan& fp = it->second;
-  const HaloPlan& plan = fp.base;
-  if (plan.kind == HaloPlan::NONE) return;
-
-  ensureDevice(h);
-  const int force = (h->tuning.force_class == MOVE_GENERIC ? 1 : 0) | (h->tuning.force_streaming ? 2 : 0) | (h->tuning.no_streaming ? 4 : 0);
-  // the one or two sides of a phase in ONE launch (one_choice): either end of a move in a pencil is field f's, the fields' pieces of
-  // the workspace lie one face apart
-  auto launch = [&](const std::vector<Move3D>& moves) {
-    const std::vector<i64> steps(moves.size(), plan.face_elements);
-    launchFieldMoveList(moves.data(), steps.data(), (int)moves.size(), inputs, inputs, n_fields, work, es, stream, force, nullptr, true);
-  };
-  launch(plan.pre);
-  if (plan.kind == HaloPlan::SELF_PERIODIC) return;
-  void* bufs[3] = {nullptr, nullptr, work};
-  HaloExchange x = haloExchangeOf(plan, bufs, es);
-  x.bytes = (i64)n_fields * plan.face_elements * es;
-  haloExchange(h, gd, x, backend, stream);
-  launch(plan.post);
-}
-
-// Halo accumulation (cudecompAmdAccumulateHalos*): the plain sequence pack my halos -> exchange -> add what arrived onto my
-// faces, with the exchange of the updates (haloExchange: same routing, same transports, same stream ordering).  Not sampled
-// by the performance report.  `clear`: the fused accumulate-and-clear (cudecompAmdAccumulateAndClearHalos*) -- the plan of
-// buildHaloAccumulateClearPlan, whose moves out of the pencil zero what they have read; everything else is the same.
-static void runHaloAccumulateOf(bool clear, cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, void* work,
-                                cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad,
-                                hipStream_t stream) {
-  const int es = elementSize(dtype);
-  const ArithType arith = arithOf(dtype);
-  const auto backend = gd->config.halo_comm_backend;
-  const bool force_packed = usesPeerTransport(h, backend);
-
-  const auto hh = arr3(halo), pp = arr3(pad);
-  std::array<bool, 3> per{false, false, false};
-  if (periods)
-    for (int i = 0; i < 3; ++i) per[i] = periods[i];
-  const cudecompGridDesc::HaloKey key{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, force_packed};
-  // (force_packed stays in the key because it is HaloKey's: accumulation plans never take the direct form, so a descriptor whose
-  // backend changes between peer and non-peer transports would cache the same plan twice -- harmless)
-  auto& plans = clear ? gd->halo_accumulate_clear_plans : gd->halo_accumulate_plans;
-  auto it = plans.find(key);
-  if (it == plans.end()) {
-    HaloPlan p = (clear ? buildHaloAccumulateClearPlan : buildHaloAccumulatePlan)(gd->shape, h->rank, axis, dim, hh.data(), per.data(),
-                                                                                  pp.data(), force_packed, h->self_exchange);
-    it = plans.emplace(key, std::move(p)).first;
-  }
-  const HaloPlan& plan = it->second;
-  if (plan.kind == HaloPlan::NONE) return;
-
-  ensureDevice(h);
-  void* bufs[3] = {input, input, work};
-  // the two additions of a phase go into one launch unless their destinations overlap (interior narrower than two halos):
-  // then one after the other, low face first
-  auto launch = [&](const std::vector<Move3D>& moves) {
-    if (moves.empty()) return;
-    if (plan.ordered && moves[0].add) {
-      for (const Move3D& m : moves) launchMoves(&m, 1, bufs, es, stream, &h->tuning, nullptr, nullptr, arith);
-    } else {
-      launchMoves(moves.data(), (int)moves.size(), bufs, es, stream, &h->tuning, nullptr, nullptr, arith);
-    }
-  };
-  launch(plan.pre);
-  if (plan.kind == HaloPlan::SELF_PERIODIC) return;
-  const HaloExchange x = haloExchangeOf(plan, bufs, es);
-  haloExchange(h, gd, x, backend, stream);
-  launch(plan.post);
-}
-
-void runHaloAccumulate(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, void* work, cudecompDataType_t dtype,
-                       const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
-  runHaloAccumulateOf(false, h, gd, axis, input, work, dtype, halo, periods, dim, pad, stream);
-}
-
-void runHaloAccumulateClear(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, void* work, cudecompDataType_t dtype,
-                            const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
-  runHaloAccumulateOf(true, h, gd, axis, input, work, dtype, halo, periods, dim, pad, stream);
-}
-
-// Multi-field halo accumulation (cudecompAmdAccumulateFieldHalos*): pack all fields' halos (one launch; with `clear` the pack zeroes
-// what it has read) -> one exchange of n_fields slabs per direction -> add what arrived onto all fields' faces (one launch; one per
-// side, low side first, where the plan is `ordered`).  Self-periodic: the wrap additions of all fields in one launch (two when
-// ordered).  Not sampled by the performance report.  One field: the single call itself.
-void runHaloAccumulateFields(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* const* inputs, int n_fields, void* work,
-                             cudecompDataType_t dtype, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, bool clear,
-                             hipStream_t stream) {
-  if (n_fields == 1) return runHaloAccumulateOf(clear, h, gd, axis, inputs[0], work, dtype, halo, periods, dim, pad, stream);
-  const int es = elementSize(dtype);
-  const ArithType arith = arithOf(dtype);
-  const auto backend = gd->config.halo_comm_backend;
-
-  const auto hh = arr3(halo), pp = arr3(pad);
-  std::array<bool, 3> per{false, false, false};
-  if (periods)
-    for (int i = 0; i < 3; ++i) per[i] = periods[i];
-  const cudecompGridDesc::HaloKey hkey{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, true};
-  const std::tuple<cudecompGridDesc::HaloKey, int, bool> key{hkey, n_fields, clear};
-  auto it = gd->halo_accumulate_fields_plans.find(key);
-  if (it == gd->halo_accumulate_fields_plans.end()) {
-    HaloFieldsPlan p = buildHaloAccumulateFieldsPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), n_fields, clear,
-                                                     h->self_exchange);
-    it = gd->halo_accumulate_fields_plans.emplace(key, std::move(p)).first;
-  }
-  const HaloPlan& plan = it->second.base;
-  if (plan.kind == HaloPlan::NONE) return;
-
-  ensureDevice(h);
-  const int force = (h->tuning.force_class == MOVE_GENERIC ? 1 : 0) | (h->tuning.force_streaming ? 2 : 0) | (h->tuning.no_streaming ? 4 : 0);
-  // the one or two sides of a phase in ONE launch (one_choice) unless they add onto overlapping cells (interior narrower than two
-  // halos): then one launch per side, low face first
-  auto launch = [&](const std::vector<Move3D>& moves) {
-    if (moves.empty()) return;
-    const std::vector<i64> steps(moves.size(), plan.face_elements);
-    const int each = plan.ordered && moves[0].add ? 1 : (int)moves.size();
-    for (int i = 0; i < (int)moves.size(); i += each)
-      launchFieldMoveList(moves.data() + i, steps.data() + i, each, inputs, inputs, n_fields, work, es, stream, force, nullptr, true, arith);
-  };
-  launch(plan.pre);
-  if (plan.kind == HaloPlan::SELF_PERIODIC) return;
-  void* bufs[3] = {nullptr, nullptr, work};
-  HaloExchange x = haloExchangeOf(plan, bufs, es);
-  x.bytes = (i64)n_fields * plan.face_elements * es;
-  haloExchange(h, gd, x, backend, stream);
-  launch(plan.post);
-}
-
-// Halo fill (cudecompAmdFillHalos*): the cells the update would write receive `value`, both sides in one launch.  Local: no
-// workspace, no exchange.  The key carries force_packed because the destinations are taken from the update's own plan.
-void runHaloFill(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, const void* value,
-                 const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
-  const int es = elementSize(dtype);
-  const bool force_packed = usesPeerTransport(h, gd->config.halo_comm_backend);
-
-  const auto hh = arr3(halo), pp = arr3(pad);
-  std::array<bool, 3> per{false, false, false};
-  if (periods)
-    for (int i = 0; i < 3; ++i) per[i] = periods[i];
-  const cudecompGridDesc::HaloKey key{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, force_packed};
-  auto it = gd->halo_fill_plans.find(key);
-  if (it == gd->halo_fill_plans.end()) {
-    HaloPlan p = buildHaloFillPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), force_packed, h->self_exchange);
-    it = gd->halo_fill_plans.emplace(key, std::move(p)).first;
-  }
-  const HaloPlan& plan = it->second;
-  if (plan.kind == HaloPlan::NONE) return;
-
-  ensureDevice(h);
-  void* bufs[3] = {input, input, nullptr};
-  launchMoves(plan.pre.data(), (int)plan.pre.size(), bufs, es, stream, &h->tuning, nullptr, nullptr, ARITH_NONE, value);
-}
-
-// Halo reflection (cudecompAmdReflectHalos*): the ghost cells the update does NOT write -- those at a non-periodic edge of the
-// domain -- receive the mirror image of the interior, both sides in one launch.  Local: no workspace, no exchange.  The checks
-// come in the contract's order: what the fill refuses, then parity / centering, then a mirror that reaches beyond the interior.
-void runHaloReflect(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, int parity,
-                    int centering, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
-  const int es = elementSize(dtype);
-  const auto hh = arr3(halo), pp = arr3(pad);
-  std::array<bool, 3> per{false, false, false};
-  if (periods)
-    for (int i = 0; i < 3; ++i) per[i] = periods[i];
-  if ((parity != 1 && parity != -1) || (centering != 0 && centering != 1)) {
-    buildHaloPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), false, h->self_exchange);  // (the fill's refusals)
-    if (parity != 1 && parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
-    CD_INVALID_USAGE("centering argument must be 0 or 1");
-  }
-  const bool negate = parity == -1;
-  const cudecompGridDesc::HaloKey hkey{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, false};
-  const auto key = std::make_tuple(hkey, centering, negate);
-  auto it = gd->halo_reflect_plans.find(key);
-  if (it == gd->halo_reflect_plans.end()) {
-    HaloPlan p = buildHaloReflectPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), centering, negate, h->self_exchange);
-    it = gd->halo_reflect_plans.emplace(key, std::move(p)).first;
-  }
-  const HaloPlan& plan = it->second;
-  if (plan.kind == HaloPlan::NONE) return;
-
-  ensureDevice(h);
-  void* bufs[3] = {input, input, nullptr};
-  launchMoves(plan.pre.data(), (int)plan.pre.size(), bufs, es, stream, &h->tuning, nullptr, nullptr, negate ? arithOf(dtype) : ARITH_NONE);
-}
-
-// Halo folding (cudecompAmdFoldHalos*), the transpose of the reflection: the ghost cells the reflection writes are added onto the
-// interior cells it reads them from, and cleared in the same launches with `clear`.  Local: no workspace, no exchange.  The
-// checks come in the reflection's order, then `clear`.  Both sides go into one launch unless their destinations overlap (a rank
-// alone along the dim with n < 4h + 2c): then one after the other, low side first, as for accumulation plans.
-void runHaloFold(cudecompHandle_t h, cudecompGridDesc_t gd, int axis, void* input, cudecompDataType_t dtype, int parity, int centering,
-                 int clear, const int32_t* halo, const bool* periods, int dim, const int32_t* pad, hipStream_t stream) {
-  const int es = elementSize(dtype);
-  const auto hh = arr3(halo), pp = arr3(pad);
-  std::array<bool, 3> per{false, false, false};
-  if (periods)
-    for (int i = 0; i < 3; ++i) per[i] = periods[i];
-  if ((parity != 1 && parity != -1) || (centering != 0 && centering != 1) || (clear != 0 && clear != 1)) {
-    buildHaloPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), false, h->self_exchange);  // (the fill's refusals)
-    if (parity != 1 && parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
-    if (centering != 0 && centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
-    CD_INVALID_USAGE("clear argument must be 0 or 1");
-  }
-  const bool negate = parity == -1;
-  const cudecompGridDesc::HaloKey hkey{axis, dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, false};
-  const auto key = std::make_tuple(hkey, centering, negate, clear == 1);
-  auto it = gd->halo_fold_plans.find(key);
-  if (it == gd->halo_fold_plans.end()) {
-    HaloPlan p = buildHaloFoldPlan(gd->shape, h->rank, axis, dim, hh.data(), per.data(), pp.data(), centering, negate, clear == 1,
-                                   h->self_exchange);
-    it = gd->halo_fold_plans.emplace(key, std::move(p)).first;
-  }
-  const HaloPlan& plan = it->second;
-  if (plan.kind == HaloPlan::NONE) return;
-
-  ensureDevice(h);
-  void* bufs[3] = {input, input, nullptr};
-  const ArithType arith = arithOf(dtype);
-  if (plan.ordered) {
-    for (const Move3D& m : plan.pre) launchMoves(&m, 1, bufs, es, stream, &h->tuning, nullptr, nullptr, arith);
-  } else {
-    launchMoves(plan.pre.data(), (int)plan.pre.size(), bufs, es, stream, &h->tuning, nullptr, nullptr, arith);
-  }
-}
 
 }  // namespace cudecomp

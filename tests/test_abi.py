@@ -422,3 +422,8 @@ def test_every_code_object_stays_small():
     sizes = _code_objects(os.path.join(ROOT, "cudecomp_amd", "lib", "libcudecomp.so"))
     assert len(sizes) >= 5, sizes
     assert max(sizes) < 400_000, "a code object grew to %d bytes: split its translation unit" % max(sizes)
+
+
+def test_arguments_are_checked_in_the_stated_order(capfd):
+    from tests import halo_check_order
+    halo_check_order.check("update", capfd)

@@ -371,3 +371,8 @@ def test_headers_declare_and_library_exports_the_symbols():
         assert hasattr(L, name), name
     assert "cudecompExtPlanHaloAccumulateClear" in _declared("cudecomp_ext.h")
     assert callable(cd.cudecompAccumulateAndClearHalos)
+
+
+def test_arguments_are_checked_in_the_stated_order(capfd):
+    from tests import halo_check_order
+    halo_check_order.check("accumulate_clear", capfd)

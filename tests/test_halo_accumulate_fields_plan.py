@@ -456,3 +456,8 @@ def test_the_documents_name_the_kernels_and_say_what_is_unmeasured():
     assert "Not covered" in section
     readme = open(os.path.join(ROOT, "README.md")).read()
     assert "cudecomp_halo_accumulate_fields.h" in readme and "kernels_field_accumulate.hip" in readme
+
+
+def test_arguments_are_checked_in_the_stated_order(capfd):
+    from tests import halo_check_order
+    halo_check_order.check("accumulate_fields", capfd)

@@ -321,3 +321,8 @@ def test_header_declares_and_library_exports_the_symbols():
         assert hasattr(L, name), name
     ext = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "cudecomp_ext.h")).read(), flags=re.S)
     assert "cudecompExtPlanHaloAccumulate" in ext and "cudecompExtAccumulate3D" in ext
+
+
+def test_arguments_are_checked_in_the_stated_order(capfd):
+    from tests import halo_check_order
+    halo_check_order.check("accumulate", capfd)

@@ -387,3 +387,8 @@ if __name__ == "__main__" and "--regen" in sys.argv:
         table = field_launches()
         f.write("{\n" + ",\n".join(" %s: %s" % (json.dumps(k), json.dumps(table[k])) for k in sorted(table)) + "\n}\n")
     print("wrote", PINS)
+
+
+def test_arguments_are_checked_in_the_stated_order(capfd):
+    from tests import halo_check_order
+    halo_check_order.check("fields", capfd)

@@ -282,3 +282,8 @@ def test_header_declares_and_library_exports_the_symbols():
     assert cd.AMD_SYMBOLS == ["cudecompAmdAccumulateHalos" + a for a in "XYZ"]
     digest = hashlib.sha256(open(os.path.join(ROOT, "include", "cudecomp_amd.h"), "rb").read()).hexdigest()
     assert digest == "59ee86fb255c4ec48c5ce5a29a8a2ae32ec4a8ac2de41de07cb8cd1134d170e8"
+
+
+def test_arguments_are_checked_in_the_stated_order(capfd):
+    from tests import halo_check_order
+    halo_check_order.check("fill", capfd)

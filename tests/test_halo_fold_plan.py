@@ -309,3 +309,8 @@ def test_what_a_fold_move_never_carries():
     assert ML.describe([plain], ML.FAKE, 8, cd.MOVES_COPY)[0]["kind"] == 0
     assert ML.describe([plain], ML.FAKE, 8, cd.MOVES_ADD, cd.DOUBLE)[0]["kind"] == 8
     assert ML.describe([m], ML.FAKE, 8, cd.MOVES_REFLECT)[0]["kind"] == 16
+
+
+def test_arguments_are_checked_in_the_stated_order(capfd):
+    from tests import halo_check_order
+    halo_check_order.check("fold", capfd)

@@ -396,3 +396,8 @@ def test_header_declares_and_library_exports_the_symbols():
     # the older headers stay as they were: the reflection lives in a header of its own
     assert _declared("cudecomp_amd_fill.h") == set(cd.AMD_FILL_SYMBOLS)
     assert "Reflect" not in open(os.path.join(ROOT, "include", "cudecomp_amd.h")).read()
+
+
+def test_arguments_are_checked_in_the_stated_order(capfd):
+    from tests import halo_check_order
+    halo_check_order.check("reflect", capfd)
