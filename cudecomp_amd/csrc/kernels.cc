@@ -50,14 +50,6 @@ struct Classified {
 
 constexpr long long kDenseMaxGapBytes = 512;  // widest gap between rows the dense row copy rewrites (halo + padding cells)
 
-MoveClass classOf(KernelKind kind) {
-  if (kind == K_GENERIC || kind == K_GENERIC_ADD || kind == K_GENERIC_FILL || kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE ||
-      kind == K_GENERIC_REFLECT || kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE || kind == K_GENERIC_FIELDS || kind == K_GENERIC_FIELDS_ADD || kind == K_GENERIC_FIELDS_TAKE ||
-      kind == K_GENERIC_FIELDS_ADD_TAKE)
-    return MOVE_GENERIC;
-  return (kind >= K_TRANSPOSE && kind <= K_TRANSPOSE_ROWLINES) || kind == K_TRANSPOSE_FIELDS ? MOVE_TRANSPOSE : MOVE_ROWS_VEC;
-}
-
 int arithBytes(int arith) { return arith == ARITH_F64 ? 8 : (arith == ARITH_F32 ? 4 : 2); }
 
 int ilog2ceil(long long x) {
@@ -98,15 +90,21 @@ void rowTiles(Classified& c) {
   c.blocks = (unsigned long long)c.t0 * c.t1 * (unsigned long long)c.dm.e[2];
 }
 
-// element-wise, copied or added: lanes along the destination-fast dim when there is one
-void genericGeometry(Classified& c, const Move3D& m) {
+// element-wise, copied or added: lanes along the destination-fast dim when there is one; without one along dim 0, or
+// (along_longest: reflections and folds, whose mirrored dim never sits in slot 0) along the longest dim
+void genericGeometry(Classified& c, const Move3D& m, bool along_longest = false) {
   c.k.vec = c.k.es;
-  c.p0 = 0;
+  c.p0 = -1;
   for (int i = 0; i < 3; ++i) {
     c.dm.e[i] = m.extent[i];
     c.dm.ss[i] = m.ss[i];
     c.dm.ds[i] = m.ds[i];
     if (m.ds[i] == 1 && m.extent[i] > 1) c.p0 = i;
+  }
+  if (c.p0 < 0) {
+    c.p0 = 0;
+    for (int i = 1; along_longest && i < 3; ++i)
+      if (m.extent[i] > m.extent[c.p0]) c.p0 = i;
   }
   const unsigned long long want = ((unsigned long long)c.elements + kThreads - 1) / kThreads;
   c.blocks = std::min<unsigned long long>(std::max<unsigned long long>(want, 1), 8192);
@@ -445,21 +443,7 @@ Classified classifyReflect(const Move3D& in, void* const bufs[3], int es, const 
   }
   c.k.kind = fold ? (in.take ? K_GENERIC_FOLD_TAKE : K_GENERIC_FOLD) : K_GENERIC_REFLECT;
   c.k.access = 0;
-  c.k.vec = es;
-  c.p0 = -1;
-  for (int i = 0; i < 3; ++i) {
-    c.dm.e[i] = m.extent[i];
-    c.dm.ss[i] = m.ss[i];
-    c.dm.ds[i] = m.ds[i];
-    if (m.ds[i] == 1 && m.extent[i] > 1) c.p0 = i;
-  }
-  if (c.p0 < 0) {  // no destination-fast dim: along the longest
-    c.p0 = 0;
-    for (int i = 1; i < 3; ++i)
-      if (m.extent[i] > m.extent[c.p0]) c.p0 = i;
-  }
-  const unsigned long long want = ((unsigned long long)c.elements + kThreads - 1) / kThreads;
-  c.blocks = std::min<unsigned long long>(std::max<unsigned long long>(want, 1), 8192);
+  genericGeometry(c, m, true);  // no destination-fast dim: along the longest
   return c;
 }
 

@@ -10,14 +10,7 @@
 
 namespace cudecomp {
 
-// How a normalized move is executed on the GPU: the three families KernelStats counts; KernelKind (kernels_batch.h) names the kernel.
-enum MoveClass {
-  MOVE_ROWS_VEC = 0,   // rows contiguous on both sides: row copy or addition, 2 ... 16 B/lane (the widest the row length allows)
-  MOVE_TRANSPOSE = 1,  // source rows along another dim than destination rows, both extents >= 4: LDS-tiled transposition
-  MOVE_GENERIC = 2,    // anything else (no unit stride, 1-element rows, forced): element-wise
-  MOVE_CLASS_COUNT = 3
-};
-
+// (MoveClass, the three families KernelStats counts: kernels_batch.h, beside the table that gives every KernelKind its class)
 struct KernelStats {  // filled per launch when requested (tests, bench bookkeeping)
   int launches[MOVE_CLASS_COUNT] = {0, 0, 0};
   i64 elements[MOVE_CLASS_COUNT] = {0, 0, 0};

@@ -4,7 +4,8 @@
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip;
 // kernels_rotate.hip and sync.hip are launched by the executor; kernels_field_transpose.hip (lists of field-moves: multi-field
 // halo phases and transposes) and kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) are
-// reached through launchFieldMoveList (kernels.h).  Seventeen code objects in all.
+// reached through launchFieldMoveList (kernels.h).  Seventeen code objects in all.  The row and element-wise kernels of all of
+// them share one workgroup decode (kernels_walk.h) and their launchers one dispatch (kernels_dispatch.h).
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
 // code object beyond roughly 0.6-0.7 MB puts the whole process into a regime where every small synchronous operation costs
@@ -16,6 +17,8 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+
+#include "errors.h"
 
 namespace cudecomp {
 
@@ -164,25 +167,79 @@ constexpr int kLinesUnitBytes = 128;  // alignment unit of the lines and row-lin
 int residencyPadBytes(const KernelChoice& k, const kern::Batch& b);
 inline int residencyPadBytes(const KernelChoice&, const kern::FieldMoveBatch&) { return 0; }  // lists of field-moves: never
 
-// the STREAM template argument (kernels_dev.h, storePolicyOf) with which a kind of kernel serves an access mode
+// How a normalized move is executed on the GPU: the three families KernelStats (kernels.h) counts; KernelKind names the kernel.
+enum MoveClass {
+  MOVE_ROWS_VEC = 0,   // rows contiguous on both sides: row copy or addition, 2 ... 16 B/lane (the widest the row length allows)
+  MOVE_TRANSPOSE = 1,  // source rows along another dim than destination rows, both extents >= 4: LDS-tiled transposition
+  MOVE_GENERIC = 2,    // anything else (no unit stride, 1-element rows, forced): element-wise
+  MOVE_CLASS_COUNT = 3
+};
+
+// One row per KernelKind, in the order of the enum: the class of the kind and the rule by which it turns an access mode into the
+// STREAM template argument of its kernels (kernels_dev.h, storePolicyOf).
+enum StreamRule {
+  STREAM_AS_ACCESS,    // the access mode itself
+  STREAM_CACHED,       // always 0: the element-wise kernels of the local families
+  STREAM_REMOTE_ONLY,  // 3 for remote destinations, else 0: the element-wise copy and addition
+  STREAM_ROW_COPY,     // 3 remote, 1 any streaming mode, else 0: row copies stream loads and stores together
+  STREAM_WINDOW        // 2 -> 4, else the mode: always cached loads, the overlap rows of neighbouring windows hit in L2
+};
+struct KindTraits {
+  MoveClass cls;
+  StreamRule stream;
+};
+constexpr KindTraits kKindTraits[] = {
+    {MOVE_ROWS_VEC, STREAM_ROW_COPY},      // K_ROWS
+    {MOVE_ROWS_VEC, STREAM_ROW_COPY},      // K_ROWS_SHIFTED
+    {MOVE_ROWS_VEC, STREAM_ROW_COPY},      // K_ROWS_DENSE
+    {MOVE_TRANSPOSE, STREAM_AS_ACCESS},    // K_TRANSPOSE
+    {MOVE_TRANSPOSE, STREAM_WINDOW},       // K_TRANSPOSE_WINDOW
+    {MOVE_TRANSPOSE, STREAM_WINDOW},       // K_TRANSPOSE_LINES
+    {MOVE_TRANSPOSE, STREAM_WINDOW},       // K_TRANSPOSE_ROWLINES
+    {MOVE_GENERIC, STREAM_REMOTE_ONLY},    // K_GENERIC
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_ADD
+    {MOVE_GENERIC, STREAM_REMOTE_ONLY},    // K_GENERIC_ADD
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FILL
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FILL
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_TAKE
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_TAKE
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_ADD_TAKE
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_ADD_TAKE
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_REFLECT
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_REFLECT
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FOLD
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FOLD
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FOLD_TAKE
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FOLD_TAKE
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FIELDS
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS
+    {MOVE_TRANSPOSE, STREAM_AS_ACCESS},    // K_TRANSPOSE_FIELDS
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FIELDS_ADD
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_ADD
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FIELDS_TAKE
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_TAKE
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FIELDS_ADD_TAKE
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_ADD_TAKE
+};
+static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_FIELDS_ADD_TAKE + 1, "one row per KernelKind");
+
+// the row of a kind; a value outside the enum is an internal error, never a read past the table
+inline const KindTraits& kindTraits(KernelKind kind) {
+  if (kind < K_ROWS || kind > K_GENERIC_FIELDS_ADD_TAKE) CD_INTERNAL_ERROR("kernel kind out of range");
+  return kKindTraits[kind];
+}
+inline MoveClass classOf(KernelKind kind) { return kindTraits(kind).cls; }
+
+// the STREAM template argument with which a kind of kernel serves an access mode
 inline int streamArgOf(KernelKind kind, int access) {
-  if (kind == K_TRANSPOSE || kind == K_ROWS_ADD) return access;
-  if (kind == K_GENERIC || kind == K_GENERIC_ADD) return access == 3 ? 3 : 0;
-  if (kind == K_ROWS_FILL) return access;
-  if (kind == K_GENERIC_FILL) return 0;
-  if (kind == K_ROWS_TAKE || kind == K_ROWS_ADD_TAKE) return access;
-  if (kind == K_GENERIC_TAKE || kind == K_GENERIC_ADD_TAKE) return 0;
-  if (kind == K_ROWS_REFLECT) return access;
-  if (kind == K_GENERIC_REFLECT) return 0;
-  if (kind == K_ROWS_FOLD || kind == K_ROWS_FOLD_TAKE) return access;
-  if (kind == K_GENERIC_FOLD || kind == K_GENERIC_FOLD_TAKE) return 0;
-  if (kind == K_ROWS_FIELDS || kind == K_TRANSPOSE_FIELDS) return access;
-  if (kind == K_GENERIC_FIELDS) return 0;
-  if (kind == K_ROWS_FIELDS_ADD || kind == K_ROWS_FIELDS_TAKE || kind == K_ROWS_FIELDS_ADD_TAKE) return access;
-  if (kind == K_GENERIC_FIELDS_ADD || kind == K_GENERIC_FIELDS_TAKE || kind == K_GENERIC_FIELDS_ADD_TAKE) return 0;
-  if (kind == K_TRANSPOSE_WINDOW || kind == K_TRANSPOSE_LINES || kind == K_TRANSPOSE_ROWLINES)
-    return access == 2 ? 4 : access;  // always cached loads: the overlap rows of neighbouring windows hit in L2
-  return access == 3 ? 3 : (access >= 1 ? 1 : 0);  // row copies: loads and stores stream together
+  switch (kindTraits(kind).stream) {
+    case STREAM_AS_ACCESS: return access;
+    case STREAM_CACHED: return 0;
+    case STREAM_REMOTE_ONLY: return access == 3 ? 3 : 0;
+    case STREAM_WINDOW: return access == 2 ? 4 : access;
+    case STREAM_ROW_COPY: break;
+  }
+  return access == 3 ? 3 : (access >= 1 ? 1 : 0);
 }
 
 // ---- launchers, one per code object (host side; csrc/kernels.cc decides what runs): each selects its instantiation from the
@@ -216,6 +273,17 @@ void launchTakeBatch(const KernelChoice& k, const kern::Batch& b, unsigned int b
 struct SignMask {
   unsigned int w[4];
 };
+// the sign bit of every real of `arith` in 16 bytes (little endian): 2-byte reals 0x8000 in every half word, 4-byte reals the top
+// bit of every word, 8-byte reals the top bit of every second word; all zero without a real type
+inline SignMask signMaskOf(ArithType arith) {
+  switch (arith) {
+    case ARITH_F16:
+    case ARITH_BF16: return {{0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u}};
+    case ARITH_F32: return {{0x80000000u, 0x80000000u, 0x80000000u, 0x80000000u}};
+    case ARITH_F64: return {{0u, 0x80000000u, 0u, 0x80000000u}};
+    default: return {{0, 0, 0, 0}};
+  }
+}
 void launchReflectBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
 // kernels_fold.hip: fold-moves (dst += src or dst += -src with the source running backwards along one dim; the TAKE kinds then
 // store zero bytes to the source cells).  The Batch of the reflections: rows with SIGNED byte strides ss[1], ss[2], generic with

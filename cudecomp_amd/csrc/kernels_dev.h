@@ -1,5 +1,7 @@
 // kernels_dev.h -- device-side helpers shared by the data-movement kernels: lane payload types, access policies, the
-// workgroup -> (move, block) decode.  (kernels_batch.h: the launch descriptor, and why the kernels live in several code objects.)
+// workgroup -> (move, block) decode.  (kernels_batch.h: the launch descriptor, and why the kernels live in several code objects;
+// kernels_walk.h: how a workgroup of the row and element-wise kernels walks its move; kernels_dispatch.h: the host's way from a
+// KernelChoice to an instantiation.)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -16,14 +16,18 @@
 //                                    walk.  GUARD = false when every move of the launch consists of whole tiles.
 //   rows_fields_kernel<VB,STREAM>    fastest dim contiguous on both sides: the lane layout of rows_kernel (kernels_rows.hip) --
 //                                    each lane moves VB = 16 (8, 4, 2) bytes, kRowsUnroll vectors per lane in flight, lanes along
-//                                    the row; one decode per WORKGROUP, no per-element index math.
+//                                    the row; one decode per WORKGROUP (rowLane and forRows, kernels_walk.h), no per-element
+//                                    index math.
 //   generic_fields_kernel<ES>        element-wise with a grid-stride loop per field, lanes along the destination-fast dim: faces
-//                                    one element thick along the fastest memory axis, everything else, and the forced case.
+//                                    one element thick along the fastest memory axis, everything else, and the forced case
+//                                    (forEachElement, kernels_walk.h).
 // Exactly the cells of the moves are read and written: no window, lines, shifted or dense form (the cells between rows belong
 // to the fields' pencils and are not the move's to rewrite), no remote destination.
 // Pure data movement: no MFMA; the bound is HBM (8 TB/s spec, ~6.3 TB/s achievable copy rate).
+#include "kernels_dispatch.h"
 #include "kernels_field_list.h"
 #include "kernels_tile.h"
+#include "kernels_walk.h"
 
 #include "errors.h"
 
@@ -76,32 +80,14 @@ __global__ __launch_bounds__(kThreads) void rows_fields_kernel(const FieldMoveBa
   locateFieldMove(b, blockIdx.x, mi, f, lb);
   if (f >= (unsigned int)b.n_fields) return;
   const FieldMove& m = b.m[mi];
-  const int lg = m.p0;
-  const int lpr = 1 << lg;
-  const int rb = kThreads >> lg;
-  const unsigned int tc = m.t0, tr = m.t1;
-  const unsigned int bc = lb % tc;
-  const unsigned int rest = lb / tc;
-  const unsigned int br = rest % tr;
-  const long long plane = rest / tr;
-
-  const long long col = (long long)bc * lpr + (threadIdx.x & (lpr - 1));
-  const long long r0 = (long long)br * rb * kRowsUnroll + (threadIdx.x >> lg);
-  if (col >= m.e[0]) return;
-  const char* __restrict__ s = sourceOf(b, m, f) + plane * m.ss[2] + col * VB;
-  char* __restrict__ d = destinationOf(b, m, f) + plane * m.ds[2] + col * VB;
+  const RowLane l = rowLane(m.p0, m.t0, m.t1, lb);
+  if (l.col >= m.e[0]) return;
+  const char* __restrict__ s = sourceOf(b, m, f) + l.plane * m.ss[2] + l.col * VB;
+  char* __restrict__ d = destinationOf(b, m, f) + l.plane * m.ds[2] + l.col * VB;
 
   V v[kRowsUnroll];
-#pragma unroll
-  for (int u = 0; u < kRowsUnroll; ++u) {
-    const long long r = r0 + (long long)u * rb;
-    if (r < m.e[1]) v[u] = loadVec<(STREAM >= 1), VB>(s + r * m.ss[1]);
-  }
-#pragma unroll
-  for (int u = 0; u < kRowsUnroll; ++u) {
-    const long long r = r0 + (long long)u * rb;
-    if (r < m.e[1]) storeVec<(STREAM >= 1 ? ST_STREAM : ST_CACHED), VB>(d + r * m.ds[1], v[u]);
-  }
+  forRows(l, m.e[1], [&](int u, long long r) CD_INLINED { v[u] = loadVec<(STREAM >= 1), VB>(s + r * m.ss[1]); });
+  forRows(l, m.e[1], [&](int u, long long r) CD_INLINED { storeVec<(STREAM >= 1 ? ST_STREAM : ST_CACHED), VB>(d + r * m.ds[1], v[u]); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -116,18 +102,12 @@ __global__ __launch_bounds__(kThreads) void generic_fields_kernel(const FieldMov
   locateFieldMove(b, blockIdx.x, mi, fi, lb);
   if (fi >= (unsigned int)b.n_fields) return;
   const FieldMove& m = b.m[mi];
-  const unsigned int nb = m.blocks;
-  const int f = m.p0, g = (f + 1) % 3, h = (f + 2) % 3;
-  const unsigned long long ef = m.e[f], eg = m.e[g];
-  const unsigned long long total = ef * eg * (unsigned long long)m.e[h];
+  const ElementWalk w = elementWalk(m.e, m.p0, lb, m.blocks);
   const E* __restrict__ src = reinterpret_cast<const E*>(sourceOf(b, m, fi));
   E* __restrict__ dst = reinterpret_cast<E*>(destinationOf(b, m, fi));
-  for (unsigned long long n = (unsigned long long)lb * kThreads + threadIdx.x; n < total;
-       n += (unsigned long long)nb * kThreads) {
-    const unsigned long long kf = n % ef, t = n / ef;
-    const unsigned long long kg = t % eg, kh = t / eg;
-    storeVec<ST_CACHED, ES>(dst + (kf * m.ds[f] + kg * m.ds[g] + kh * m.ds[h]), src[kf * m.ss[f] + kg * m.ss[g] + kh * m.ss[h]]);
-  }
+  forEachElement(w, [&](unsigned long long kf, unsigned long long kg, unsigned long long kh) CD_INLINED {
+    storeVec<ST_CACHED, ES>(dst + (kf * m.ds[w.f] + kg * m.ds[w.g] + kh * m.ds[w.h]), src[kf * m.ss[w.f] + kg * m.ss[w.g] + kh * m.ss[w.h]]);
+  });
 }
 
 // one tile per element size and lane width (the shapes of kernels_transpose.hip without the longer tiles).  The unguarded form
@@ -164,22 +144,15 @@ void launchFieldMoveBatch(const KernelChoice& k, const FieldMoveBatch& b, unsign
     return;
   }
   const bool rows = k.kind == K_ROWS_FIELDS, generic = k.kind == K_GENERIC_FIELDS;
-#define CD_ROWS_FIELDS(VB)                                                \
-  do {                                                                    \
-    if (s == 1) rows_fields_kernel<VB, 1><<<grid, block, 0, stream>>>(b); \
-    else rows_fields_kernel<VB, 0><<<grid, block, 0, stream>>>(b);        \
-  } while (0)
   if (rows && s != 0 && s != 1) CD_INTERNAL_ERROR("no field-move row kernel for this access mode");
-  if (rows && vb == 16) CD_ROWS_FIELDS(16);
-  else if (rows && vb == 8) CD_ROWS_FIELDS(8);
-  else if (rows && vb == 4) CD_ROWS_FIELDS(4);
-  else if (rows && vb == 2) CD_ROWS_FIELDS(2);
-  else if (generic && k.es == 2) generic_fields_kernel<2><<<grid, block, 0, stream>>>(b);
-  else if (generic && k.es == 4) generic_fields_kernel<4><<<grid, block, 0, stream>>>(b);
-  else if (generic && k.es == 8) generic_fields_kernel<8><<<grid, block, 0, stream>>>(b);
-  else if (generic && k.es == 16) generic_fields_kernel<16><<<grid, block, 0, stream>>>(b);
-  else CD_INTERNAL_ERROR("no field-move kernel for this lane width");
-#undef CD_ROWS_FIELDS
+  bool ok = false;
+  if (rows)
+    ok = dispatchLaneWidth<unsigned short>(vb, [&](auto w) {
+      dispatchAccess(s, [&](auto a) { rows_fields_kernel<decltype(w)::value, decltype(a)::value><<<grid, block, 0, stream>>>(b); });
+    });
+  else if (generic)
+    ok = dispatchElementSize(k.es, [&](auto es) { generic_fields_kernel<decltype(es)::value><<<grid, block, 0, stream>>>(b); });
+  if (!ok) CD_INTERNAL_ERROR("no field-move kernel for this lane width");
   CD_CHECK_HIP(hipGetLastError());
 }
 

@@ -5,21 +5,23 @@
 // A pure store stream: the kernels issue NO loads from the destination, so a solver may write the neighbouring cells from
 // another stream meanwhile -- no dense / shifted / window forms (those read and rewrite gap cells), no remote destinations.
 //   rows_fill_kernel<VB, STREAM>  fastest dim contiguous in the destination.  Workgroup decode and batching of rows_kernel
-//                                 (kernels_rows.hip): one (row, plane) decode per WORKGROUP, kRowsUnroll stores per lane in
-//                                 flight.  A fill has no source alignment to respect, so the lanes lie on the destination's
-//                                 VB = 16-byte grid, from the boundary below each row's start: the body of every row is stored
-//                                 as whole, naturally aligned 16-byte vectors whatever the row's base (2-byte elements at 2 mod 4
-//                                 included), only a row's head and tail take narrower, naturally aligned pieces.  What costs a
-//                                 store stream is the partly written 128-byte line (profiles/r05_tuning.md section 3); whole
-//                                 aligned vectors leave one at each row end at most, and none inside a slab that is contiguous
-//                                 in memory (normalizeMove has fused it into one long row: a plain streaming fill).
+//                                 (kernels_rows.hip; rowLane, kernels_walk.h): one (row, plane) decode per WORKGROUP, kRowsUnroll
+//                                 stores per lane in flight.  A fill has no source alignment to respect, so the lanes lie on the
+//                                 destination's VB = 16-byte grid, from the boundary below each row's start: the body of every
+//                                 row is stored as whole, naturally aligned 16-byte vectors whatever the row's base (2-byte
+//                                 elements at 2 mod 4 included), only a row's head and tail take narrower, naturally aligned
+//                                 pieces.  What costs a store stream is the partly written 128-byte line (profiles/r05_tuning.md
+//                                 section 3); whole aligned vectors leave one at each row end at most, and none inside a slab
+//                                 that is contiguous in memory (normalizeMove has fused it into one long row: a plain streaming
+//                                 fill).
 //   generic_fill_kernel<ES>       element-wise, for everything else: faces one element thick along the fastest memory axis (cells
 //                                 a row pitch apart), degenerate shapes.
 // The value arrives as FillPattern, a kernel argument of its own: the 16 bytes of ANY 16-byte-aligned slot of the destination
 // (the element replicated, at the phase the destination's address gives it; kernels.cc fillPatternOf).  Every store takes its
 // bytes from the pattern at the offset of its address inside the slot, so no store ever depends on which row it belongs to.
 // No store of 4 bytes or more is issued at an address that is not a multiple of its size.
-#include "kernels_dev.h"
+#include "kernels_dispatch.h"
+#include "kernels_walk.h"
 
 #include "errors.h"
 
@@ -71,24 +73,14 @@ __global__ __launch_bounds__(kThreads) void rows_fill_kernel(const Batch b, cons
   unsigned int lb;
   if (!locate(b, blockIdx.x, mi, lb)) return;
   const DevMove& m = b.m[mi];
-  const int lg = b.p0[mi];
-  const int lpr = 1 << lg;
-  const int rb = kThreads >> lg;
-  const unsigned int tc = b.t0[mi], tr = b.t1[mi];
-  const unsigned int bc = lb % tc;
-  const unsigned int rest = lb / tc;
-  const unsigned int br = rest % tr;
-  const long long plane = rest / tr;
-
-  const long long col = (long long)bc * lpr + (threadIdx.x & (lpr - 1));
-  const long long r0 = (long long)br * rb * kRowsUnroll + (threadIdx.x >> lg);
-  if (col >= m.e[0]) return;
+  const RowLane l = rowLane(b.p0[mi], b.t0[mi], b.t1[mi], lb);
+  if (l.col >= m.e[0]) return;
   const u32x4 pat = {pattern.w[0], pattern.w[1], pattern.w[2], pattern.w[3]};
-  char* const d = m.dst + plane * m.ds[2];
-  const long long row_bytes = m.ss[0], lo = col * VB;
+  char* const d = m.dst + l.plane * m.ds[2];
+  const long long row_bytes = m.ss[0], lo = l.col * VB;
 #pragma unroll
   for (int u = 0; u < kRowsUnroll; ++u) {
-    const long long r = r0 + (long long)u * rb;
+    const long long r = l.r0 + (long long)u * l.rb;
     if (r >= m.e[1]) continue;
     char* const row = d + r * m.ds[1];
     const long long ph = (long long)(reinterpret_cast<uintptr_t>(row) & (VB - 1));  // the row is bytes [ph, ph + row_bytes) of its slots
@@ -109,6 +101,8 @@ __global__ __launch_bounds__(kThreads) void generic_fill_kernel(const Batch b, c
   unsigned int lb;
   if (!locate(b, blockIdx.x, mi, lb)) return;
   const DevMove& m = b.m[mi];
+  // (the element walk of kernels_walk.h, written out: through forEachElement the 2-byte form compiles to 52 instructions more
+  // than this loop -- other branches around storeSlot -- profiles/kernel_walk_refactor.md)
   const unsigned int nb = b.first_block[mi + 1] - b.first_block[mi];
   const int f = b.p0[mi], g = (f + 1) % 3, h = (f + 2) % 3;
   const unsigned long long ef = m.e[f], eg = m.e[g];
@@ -133,18 +127,15 @@ using namespace kern;
 
 void launchFillBatch(const KernelChoice& k, const Batch& b, const FillPattern& pattern, unsigned int blocks, hipStream_t stream) {
   const dim3 grid(blocks), block(kThreads);
-  bool ok = true;
-  if (k.kind == K_ROWS_FILL && k.vec == 16) {
-    if (streamArgOf(k.kind, k.access) == 1) rows_fill_kernel<16, 1><<<grid, block, 0, stream>>>(b, pattern);
-    else rows_fill_kernel<16, 0><<<grid, block, 0, stream>>>(b, pattern);
+  bool ok = false;
+  if (k.kind == K_ROWS_FILL) {
+    ok = dispatchInt<16>(k.vec, [&](auto w) {
+      dispatchAccess(streamArgOf(k.kind, k.access), [&](auto a) {
+        rows_fill_kernel<decltype(w)::value, decltype(a)::value><<<grid, block, 0, stream>>>(b, pattern);
+      });
+    });
   } else if (k.kind == K_GENERIC_FILL) {
-    if (k.es == 2) generic_fill_kernel<2><<<grid, block, 0, stream>>>(b, pattern);
-    else if (k.es == 4) generic_fill_kernel<4><<<grid, block, 0, stream>>>(b, pattern);
-    else if (k.es == 8) generic_fill_kernel<8><<<grid, block, 0, stream>>>(b, pattern);
-    else if (k.es == 16) generic_fill_kernel<16><<<grid, block, 0, stream>>>(b, pattern);
-    else ok = false;
-  } else {
-    ok = false;
+    ok = dispatchElementSize(k.es, [&](auto es) { generic_fill_kernel<decltype(es)::value><<<grid, block, 0, stream>>>(b, pattern); });
   }
   if (!ok) CD_INTERNAL_ERROR("no fill kernel for this lane width and element size");
   CD_CHECK_HIP(hipGetLastError());

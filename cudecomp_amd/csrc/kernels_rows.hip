@@ -10,8 +10,11 @@
 //   rows_dense_kernel     the same when, in addition, the cells between consecutive destination rows belong to the move
 //                         (whole interior rows of a halo-carrying pencil): whole cache lines across the row ends.
 //   generic_kernel<ES>    degenerate shapes (no unit stride on one side, 1-element rows); ES = 2, 4, 8, 16.
+// The workgroup decode of the row kernels (rowLane, forRows) and the element walk (forEachElement) are those of every family:
+// kernels_walk.h; rows_dense_kernel walks the destination's linear address space and has a decode of its own.
 // Pure data movement: no MFMA; the bound is HBM (8 TB/s spec, ~6.3 TB/s achievable copy rate).
-#include "kernels_dev.h"
+#include "kernels_dispatch.h"
+#include "kernels_walk.h"
 
 #include "errors.h"
 
@@ -21,7 +24,7 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------
 // rows_kernel: e[0] = vectors per row, e[1] = rows, e[2] = planes; ss/ds[1], [2] in BYTES.
-// p0 = log2(lanes per row).  A workgroup covers (256 >> p0) * kRowsUnroll rows x (1 << p0) vectors.
+// p0 = log2(lanes per row).  A workgroup covers (256 >> p0) * kRowsUnroll rows x (1 << p0) vectors (rowLane, kernels_walk.h).
 // ---------------------------------------------------------------------------------------------
 template <int VB, int STREAM>
 __global__ __launch_bounds__(kThreads) void rows_kernel(const Batch b) {
@@ -30,32 +33,16 @@ __global__ __launch_bounds__(kThreads) void rows_kernel(const Batch b) {
   unsigned int lb;
   if (!locate(b, blockIdx.x, mi, lb)) return;
   const DevMove& m = b.m[mi];
-  const int lg = b.p0[mi];
-  const int lpr = 1 << lg;
-  const int rb = kThreads >> lg;
-  const unsigned int tc = b.t0[mi], tr = b.t1[mi];
-  const unsigned int bc = lb % tc;
-  const unsigned int rest = lb / tc;
-  const unsigned int br = rest % tr;
-  const long long plane = rest / tr;
-
-  const long long col = (long long)bc * lpr + (threadIdx.x & (lpr - 1));
-  const long long r0 = (long long)br * rb * kRowsUnroll + (threadIdx.x >> lg);
-  if (col >= m.e[0]) return;
-  const char* __restrict__ s = m.src + plane * m.ss[2] + col * VB;
-  char* __restrict__ d = m.dst + plane * m.ds[2] + col * VB;
+  const RowLane l = rowLane(b.p0[mi], b.t0[mi], b.t1[mi], lb);
+  if (l.col >= m.e[0]) return;
+  const char* __restrict__ s = m.src + l.plane * m.ss[2] + l.col * VB;
+  char* __restrict__ d = m.dst + l.plane * m.ds[2] + l.col * VB;
 
   V v[kRowsUnroll];
-#pragma unroll
-  for (int u = 0; u < kRowsUnroll; ++u) {
-    const long long r = r0 + (long long)u * rb;
-    if (r < m.e[1]) v[u] = loadVec<(STREAM >= 1), VB>(s + r * m.ss[1]);
-  }
-#pragma unroll
-  for (int u = 0; u < kRowsUnroll; ++u) {
-    const long long r = r0 + (long long)u * rb;
-    if (r < m.e[1]) storeVec<(STREAM == 3 ? ST_REMOTE : (STREAM >= 1 ? ST_STREAM : ST_CACHED)), VB>(d + r * m.ds[1], v[u]);
-  }
+  forRows(l, m.e[1], [&](int u, long long r) CD_INLINED { v[u] = loadVec<(STREAM >= 1), VB>(s + r * m.ss[1]); });
+  forRows(l, m.e[1], [&](int u, long long r) CD_INLINED {
+    storeVec<(STREAM == 3 ? ST_REMOTE : (STREAM >= 1 ? ST_STREAM : ST_CACHED)), VB>(d + r * m.ds[1], v[u]);
+  });
   if constexpr (STREAM == 3) remoteStoresDone();
 }
 
@@ -87,24 +74,17 @@ __global__ __launch_bounds__(kThreads) void rows_shifted_kernel(const Batch b) {
   unsigned int lb;
   if (!locate(b, blockIdx.x, mi, lb)) return;
   const DevMove& m = b.m[mi];
-  const int lg = b.p0[mi];
-  const int lpr = 1 << lg;
-  const int rb = kThreads >> lg;
-  const unsigned int tc = b.t0[mi], tr = b.t1[mi];
-  const unsigned int bc = lb % tc;
-  const unsigned int rest = lb / tc;
-  const unsigned int br = rest % tr;
-  const long long plane = rest / tr;
-  const long long row_bytes = b.p1[mi];
   // e[0] = vectors of a row + one 64-byte unit of slack (the shift moves up to a unit's worth past the row's own
   // vectors).  When the slack needs a tile column of its own that column is almost empty; letting the first lanes of
   // the last full column take it in a second step instead was measured and is far worse (3.0 -> 4.2 ms on 8 GiB: those
   // workgroups pay two memory round trips).
-  const long long col = (long long)bc * lpr + (threadIdx.x & (lpr - 1));
-  const long long r0 = (long long)br * rb * kRowsUnroll + (threadIdx.x >> lg);
+  const RowLane l = rowLane(b.p0[mi], b.t0[mi], b.t1[mi], lb);
+  const long long row_bytes = b.p1[mi];
+  const long long col = l.col, r0 = l.r0;
+  const int rb = l.rb;
   if (col >= m.e[0]) return;
-  const char* __restrict__ s = m.src + plane * m.ss[2];
-  char* __restrict__ d = m.dst + plane * m.ds[2];
+  const char* __restrict__ s = m.src + l.plane * m.ss[2];
+  char* __restrict__ d = m.dst + l.plane * m.ds[2];
 
   V v[kRowsUnroll] = {};
   long long off[kRowsUnroll];
@@ -242,19 +222,13 @@ __global__ __launch_bounds__(kThreads) void generic_kernel(const Batch b) {
   unsigned int lb;
   if (!locate(b, blockIdx.x, mi, lb)) return;
   const DevMove& m = b.m[mi];
-  const unsigned int nb = b.first_block[mi + 1] - b.first_block[mi];
-  const int f = b.p0[mi], g = (f + 1) % 3, h = (f + 2) % 3;
-  const unsigned long long ef = m.e[f], eg = m.e[g];
-  const unsigned long long total = ef * eg * (unsigned long long)m.e[h];
+  const ElementWalk w = elementWalk(m.e, b.p0[mi], lb, b.first_block[mi + 1] - b.first_block[mi]);
   const E* __restrict__ src = reinterpret_cast<const E*>(m.src);
   E* __restrict__ dst = reinterpret_cast<E*>(m.dst);
-  for (unsigned long long n = (unsigned long long)lb * kThreads + threadIdx.x; n < total;
-       n += (unsigned long long)nb * kThreads) {
-    const unsigned long long kf = n % ef, t = n / ef;
-    const unsigned long long kg = t % eg, kh = t / eg;
-    storeVec<(REMOTE ? ST_REMOTE : ST_CACHED), ES>(dst + (kf * m.ds[f] + kg * m.ds[g] + kh * m.ds[h]),
-                                                     src[kf * m.ss[f] + kg * m.ss[g] + kh * m.ss[h]]);
-  }
+  forEachElement(w, [&](unsigned long long kf, unsigned long long kg, unsigned long long kh) CD_INLINED {
+    storeVec<(REMOTE ? ST_REMOTE : ST_CACHED), ES>(dst + (kf * m.ds[w.f] + kg * m.ds[w.g] + kh * m.ds[w.h]),
+                                                     src[kf * m.ss[w.f] + kg * m.ss[w.g] + kh * m.ss[w.h]]);
+  });
   if constexpr (REMOTE) remoteStoresDone();
 }
 
@@ -276,32 +250,22 @@ void launchRowsBatch(const KernelChoice& k, const Batch& b, unsigned int blocks,
     CD_CHECK_HIP(hipGetLastError());
     return;
   }
-#define CD_ROWS(K, VB)                                                    \
-  do {                                                                    \
-    if (rs == 3) K<VB, 3><<<grid, block, 0, stream>>>(b);                 \
-    else if (rs == 1) K<VB, 1><<<grid, block, 0, stream>>>(b);            \
-    else K<VB, 0><<<grid, block, 0, stream>>>(b);                         \
-  } while (0)
-#define CD_GENERIC(ES)                                                           \
-  do {                                                                           \
-    if (rs == 3) generic_kernel<ES, true><<<grid, block, 0, stream>>>(b);        \
-    else generic_kernel<ES, false><<<grid, block, 0, stream>>>(b);               \
-  } while (0)
+  const auto access = [&](auto&& f) { dispatchInt<0, 1, 3>(rs == 3 || rs == 1 ? rs : 0, f); };  // cached, streaming, remote stores
+  bool ok = false;
   // (2-byte rows: plain kernel only -- the shifted one copies the row ends in 4-byte pieces, kernels.cc classify())
-  if (shifted && vb == 16) CD_ROWS(rows_shifted_kernel, 16);
-  else if (shifted && vb == 8) CD_ROWS(rows_shifted_kernel, 8);
-  else if (shifted && vb == 4) CD_ROWS(rows_shifted_kernel, 4);
-  else if (plain && vb == 16) CD_ROWS(rows_kernel, 16);
-  else if (plain && vb == 8) CD_ROWS(rows_kernel, 8);
-  else if (plain && vb == 4) CD_ROWS(rows_kernel, 4);
-  else if (plain && vb == 2) CD_ROWS(rows_kernel, 2);
-  else if (generic && k.es == 2) CD_GENERIC(2);
-  else if (generic && k.es == 4) CD_GENERIC(4);
-  else if (generic && k.es == 8) CD_GENERIC(8);
-  else if (generic && k.es == 16) CD_GENERIC(16);
-  else CD_INTERNAL_ERROR("no row copy or element-wise kernel for this lane width");
-#undef CD_ROWS
-#undef CD_GENERIC
+  if (shifted)
+    ok = dispatchInt<16, 8, 4>(vb, [&](auto w) {
+      access([&](auto a) { rows_shifted_kernel<decltype(w)::value, decltype(a)::value><<<grid, block, 0, stream>>>(b); });
+    });
+  else if (plain)
+    ok = dispatchInt<16, 8, 4, 2>(vb, [&](auto w) {
+      access([&](auto a) { rows_kernel<decltype(w)::value, decltype(a)::value><<<grid, block, 0, stream>>>(b); });
+    });
+  else if (generic)
+    ok = dispatchElementSize(k.es, [&](auto es) {
+      dispatchBool(rs == 3, [&](auto remote) { generic_kernel<decltype(es)::value, decltype(remote)::value><<<grid, block, 0, stream>>>(b); });
+    });
+  if (!ok) CD_INTERNAL_ERROR("no row copy or element-wise kernel for this lane width");
   CD_CHECK_HIP(hipGetLastError());
 }
 

@@ -5,8 +5,10 @@
 // buildHaloAccumulateClearPlan): the ghost cells an accumulation reads are the cells a fill would clear afterwards, so the lane
 // that loads them clears them.  Nothing like them exists in NVIDIA/cuDecomp.
 //   rows_take_kernel<VB, STREAM>                dst = src; src = 0.  Fastest dim contiguous on both sides: lane layout, workgroup
-//                                               decode and batching of rows_kernel (kernels_rows.hip).
-//   generic_take_kernel<ES>                     the same, element-wise (faces one element thick along the fastest memory axis).
+//                                               decode and batching of rows_kernel (kernels_rows.hip) -- rowLane of kernels_walk.h,
+//                                               shared in code by every family.
+//   generic_take_kernel<ES>                     the same, element-wise (faces one element thick along the fastest memory axis):
+//                                               the element walk of kernels_walk.h.
 //   rows_accumulate_take_kernel<T, VB, STREAM>  dst += src; src = 0.  Layout of rows_accumulate_kernel (kernels_accumulate.hip),
 //                                               arithmetic of kernels_arith.h.
 //   generic_accumulate_take_kernel<T, NC>       the same, element-wise (NC reals per element).
@@ -16,21 +18,20 @@
 // bytes and keeps their order; the hardware keeps a wave's accesses to one address in order.  Source and destination cells of a
 // list are disjoint (the planner's and the harness's contract), so no lane clears what another still has to read.  Local
 // buffers only: no remote stores.
+// The two row kernels keep their two unrolled loops written out (all loads, then all stores, into arrays of the kernel's own):
+// through forRows some of their instantiations compile to other register counts and waits than these loops do
+// (profiles/kernel_walk_refactor.md).
 // Bound: HBM.  Algorithmic bytes per byte of the move: 3 for a take (source read, destination written, source written), 4 for
 // an add-take (the destination is read as well).
 #include "kernels_arith.h"
-#include "kernels_dev.h"
+#include "kernels_dispatch.h"
+#include "kernels_walk.h"
 
 #include "errors.h"
 
 namespace cudecomp {
 namespace kern {
 namespace {
-
-template <int N> __device__ __forceinline__ Bytes<N> zeroBytes() {
-  Bytes<N> z = {};
-  return z;
-}
 
 // ---------------------------------------------------------------------------------------------
 // rows_take_kernel / rows_accumulate_take_kernel: e[0] = vectors per row, e[1] = rows, e[2] = planes; ss/ds[1], [2] in BYTES.
@@ -47,30 +48,20 @@ __global__ __launch_bounds__(kThreads) void rows_take_kernel(const Batch b) {
   unsigned int lb;
   if (!locate(b, blockIdx.x, mi, lb)) return;
   const DevMove& m = b.m[mi];
-  const int lg = b.p0[mi];
-  const int lpr = 1 << lg;
-  const int rb = kThreads >> lg;
-  const unsigned int tc = b.t0[mi], tr = b.t1[mi];
-  const unsigned int bc = lb % tc;
-  const unsigned int rest = lb / tc;
-  const unsigned int br = rest % tr;
-  const long long plane = rest / tr;
-
-  const long long col = (long long)bc * lpr + (threadIdx.x & (lpr - 1));
-  const long long r0 = (long long)br * rb * kRowsUnroll + (threadIdx.x >> lg);
-  if (col >= m.e[0]) return;
-  char* s = const_cast<char*>(m.src) + plane * m.ss[2] + col * VB;  // (written too: the zeroes)
-  char* d = m.dst + plane * m.ds[2] + col * VB;
+  const RowLane l = rowLane(b.p0[mi], b.t0[mi], b.t1[mi], lb);
+  if (l.col >= m.e[0]) return;
+  char* s = const_cast<char*>(m.src) + l.plane * m.ss[2] + l.col * VB;  // (written too: the zeroes)
+  char* d = m.dst + l.plane * m.ds[2] + l.col * VB;
 
   V v[kRowsUnroll];
 #pragma unroll
   for (int u = 0; u < kRowsUnroll; ++u) {
-    const long long r = r0 + (long long)u * rb;
+    const long long r = l.r0 + (long long)u * l.rb;
     if (r < m.e[1]) v[u] = loadVec<(STREAM >= 1), VB>(s + r * m.ss[1]);
   }
 #pragma unroll
   for (int u = 0; u < kRowsUnroll; ++u) {
-    const long long r = r0 + (long long)u * rb;
+    const long long r = l.r0 + (long long)u * l.rb;
     if (r < m.e[1]) {
       storeVec<POLICY, VB>(d + r * m.ds[1], v[u]);
       storeVec<POLICY, VB>(s + r * m.ss[1], zeroBytes<VB>());
@@ -85,25 +76,15 @@ __global__ __launch_bounds__(kThreads) void rows_accumulate_take_kernel(const Ba
   unsigned int lb;
   if (!locate(b, blockIdx.x, mi, lb)) return;
   const DevMove& m = b.m[mi];
-  const int lg = b.p0[mi];
-  const int lpr = 1 << lg;
-  const int rb = kThreads >> lg;
-  const unsigned int tc = b.t0[mi], tr = b.t1[mi];
-  const unsigned int bc = lb % tc;
-  const unsigned int rest = lb / tc;
-  const unsigned int br = rest % tr;
-  const long long plane = rest / tr;
-
-  const long long col = (long long)bc * lpr + (threadIdx.x & (lpr - 1));
-  const long long r0 = (long long)br * rb * kRowsUnroll + (threadIdx.x >> lg);
-  if (col >= m.e[0]) return;
-  char* s = const_cast<char*>(m.src) + plane * m.ss[2] + col * VB;  // (a wrap onto myself: both sides are slabs of one pencil)
-  char* d = m.dst + plane * m.ds[2] + col * VB;
+  const RowLane l = rowLane(b.p0[mi], b.t0[mi], b.t1[mi], lb);
+  if (l.col >= m.e[0]) return;
+  char* s = const_cast<char*>(m.src) + l.plane * m.ss[2] + l.col * VB;  // (a wrap onto myself: both sides are slabs of one pencil)
+  char* d = m.dst + l.plane * m.ds[2] + l.col * VB;
 
   V x[kRowsUnroll], y[kRowsUnroll];
 #pragma unroll
   for (int u = 0; u < kRowsUnroll; ++u) {
-    const long long r = r0 + (long long)u * rb;
+    const long long r = l.r0 + (long long)u * l.rb;
     if (r < m.e[1]) {
       x[u] = loadVec<(STREAM >= 1), VB>(s + r * m.ss[1]);
       y[u] = loadVec<false, VB>(d + r * m.ds[1]);
@@ -111,7 +92,7 @@ __global__ __launch_bounds__(kThreads) void rows_accumulate_take_kernel(const Ba
   }
 #pragma unroll
   for (int u = 0; u < kRowsUnroll; ++u) {
-    const long long r = r0 + (long long)u * rb;
+    const long long r = l.r0 + (long long)u * l.rb;
     if (r < m.e[1]) {
       storeVec<ST_CACHED, VB>(d + r * m.ds[1], addPayload<T, VB>(y[u], x[u]));
       storeVec<(STREAM >= 1 ? ST_STREAM : ST_CACHED), VB>(s + r * m.ss[1], zeroBytes<VB>());
@@ -130,21 +111,15 @@ __global__ __launch_bounds__(kThreads) void generic_take_kernel(const Batch b) {
   unsigned int lb;
   if (!locate(b, blockIdx.x, mi, lb)) return;
   const DevMove& m = b.m[mi];
-  const unsigned int nb = b.first_block[mi + 1] - b.first_block[mi];
-  const int f = b.p0[mi], g = (f + 1) % 3, h = (f + 2) % 3;
-  const unsigned long long ef = m.e[f], eg = m.e[g];
-  const unsigned long long total = ef * eg * (unsigned long long)m.e[h];
+  const ElementWalk w = elementWalk(m.e, b.p0[mi], lb, b.first_block[mi + 1] - b.first_block[mi]);
   char* src = const_cast<char*>(m.src);
   char* dst = m.dst;
-  for (unsigned long long n = (unsigned long long)lb * kThreads + threadIdx.x; n < total;
-       n += (unsigned long long)nb * kThreads) {
-    const unsigned long long kf = n % ef, t = n / ef;
-    const unsigned long long kg = t % eg, kh = t / eg;
-    char* s = src + (long long)(kf * m.ss[f] + kg * m.ss[g] + kh * m.ss[h]) * ES;
+  forEachElement(w, [&](unsigned long long kf, unsigned long long kg, unsigned long long kh) CD_INLINED {
+    char* s = src + (long long)(kf * m.ss[w.f] + kg * m.ss[w.g] + kh * m.ss[w.h]) * ES;
     const E x = loadVec<false, ES>(s);
-    storeVec<ST_CACHED, ES>(dst + (long long)(kf * m.ds[f] + kg * m.ds[g] + kh * m.ds[h]) * ES, x);
+    storeVec<ST_CACHED, ES>(dst + (long long)(kf * m.ds[w.f] + kg * m.ds[w.g] + kh * m.ds[w.h]) * ES, x);
     storeVec<ST_CACHED, ES>(s, zeroBytes<ES>());
-  }
+  });
 }
 
 template <typename T, int NC>
@@ -155,68 +130,17 @@ __global__ __launch_bounds__(kThreads) void generic_accumulate_take_kernel(const
   unsigned int lb;
   if (!locate(b, blockIdx.x, mi, lb)) return;
   const DevMove& m = b.m[mi];
-  const unsigned int nb = b.first_block[mi + 1] - b.first_block[mi];
-  const int f = b.p0[mi], g = (f + 1) % 3, h = (f + 2) % 3;
-  const unsigned long long ef = m.e[f], eg = m.e[g];
-  const unsigned long long total = ef * eg * (unsigned long long)m.e[h];
+  const ElementWalk w = elementWalk(m.e, b.p0[mi], lb, b.first_block[mi + 1] - b.first_block[mi]);
   char* src = const_cast<char*>(m.src);
   char* dst = m.dst;
-  for (unsigned long long n = (unsigned long long)lb * kThreads + threadIdx.x; n < total;
-       n += (unsigned long long)nb * kThreads) {
-    const unsigned long long kf = n % ef, t = n / ef;
-    const unsigned long long kg = t % eg, kh = t / eg;
-    char* s = src + (long long)(kf * m.ss[f] + kg * m.ss[g] + kh * m.ss[h]) * ES;
-    char* d = dst + (long long)(kf * m.ds[f] + kg * m.ds[g] + kh * m.ds[h]) * ES;
+  forEachElement(w, [&](unsigned long long kf, unsigned long long kg, unsigned long long kh) CD_INLINED {
+    char* s = src + (long long)(kf * m.ss[w.f] + kg * m.ss[w.g] + kh * m.ss[w.h]) * ES;
+    char* d = dst + (long long)(kf * m.ds[w.f] + kg * m.ds[w.g] + kh * m.ds[w.h]) * ES;
     const E x = loadVec<false, ES>(s);
     const E y = loadVec<false, ES>(d);
     storeVec<ST_CACHED, ES>(d, addPayload<T, ES>(y, x));
     storeVec<ST_CACHED, ES>(s, zeroBytes<ES>());
-  }
-}
-
-template <int VB>
-void launchTakeRowsOf(int stream_access, const Batch& b, const dim3& grid, const dim3& block, hipStream_t stream) {
-  if (stream_access == 1) rows_take_kernel<VB, 1><<<grid, block, 0, stream>>>(b);
-  else rows_take_kernel<VB, 0><<<grid, block, 0, stream>>>(b);
-}
-
-template <typename T, int VB>
-void launchAddTakeRowsOf(int stream_access, const Batch& b, const dim3& grid, const dim3& block, hipStream_t stream) {
-  if (stream_access == 1) rows_accumulate_take_kernel<T, VB, 1><<<grid, block, 0, stream>>>(b);
-  else rows_accumulate_take_kernel<T, VB, 0><<<grid, block, 0, stream>>>(b);
-}
-
-template <typename T>
-bool launchAddTakeRowsOfType(int vb, int stream_access, const Batch& b, const dim3& grid, const dim3& block, hipStream_t stream) {
-  if (vb == 16) {
-    launchAddTakeRowsOf<T, 16>(stream_access, b, grid, block, stream);
-    return true;
-  }
-  if (vb == 8) {
-    launchAddTakeRowsOf<T, 8>(stream_access, b, grid, block, stream);
-    return true;
-  }
-  if constexpr (sizeof(T) <= 4) {
-    if (vb == 4) {
-      launchAddTakeRowsOf<T, 4>(stream_access, b, grid, block, stream);
-      return true;
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
-    if (vb == 2) {
-      launchAddTakeRowsOf<T, 2>(stream_access, b, grid, block, stream);
-      return true;
-    }
-  }
-  return false;
-}
-
-template <typename T>
-bool launchAddTakeGenericOfType(int nc, const Batch& b, const dim3& grid, const dim3& block, hipStream_t stream) {
-  if (nc == 1) generic_accumulate_take_kernel<T, 1><<<grid, block, 0, stream>>>(b);
-  else if (nc == 2) generic_accumulate_take_kernel<T, 2><<<grid, block, 0, stream>>>(b);
-  else return false;
-  return true;
+  });
 }
 
 }  // namespace
@@ -226,38 +150,28 @@ using namespace kern;
 
 void launchTakeBatch(const KernelChoice& k, const Batch& b, unsigned int blocks, hipStream_t stream) {
   const dim3 grid(blocks), block(kThreads);
-  const int vb = k.vec, s = streamArgOf(k.kind, k.access), es = k.es;
-  bool ok = true;
+  const int s = streamArgOf(k.kind, k.access);
+  bool ok = false;
   if (k.kind == K_ROWS_TAKE) {
-    if (vb == 16) launchTakeRowsOf<16>(s, b, grid, block, stream);
-    else if (vb == 8) launchTakeRowsOf<8>(s, b, grid, block, stream);
-    else if (vb == 4) launchTakeRowsOf<4>(s, b, grid, block, stream);
-    else if (vb == 2) launchTakeRowsOf<2>(s, b, grid, block, stream);
-    else ok = false;
+    ok = dispatchLaneWidth<unsigned short>(k.vec, [&](auto w) {
+      dispatchAccess(s, [&](auto a) { rows_take_kernel<decltype(w)::value, decltype(a)::value><<<grid, block, 0, stream>>>(b); });
+    });
   } else if (k.kind == K_GENERIC_TAKE) {
-    if (es == 2) generic_take_kernel<2><<<grid, block, 0, stream>>>(b);
-    else if (es == 4) generic_take_kernel<4><<<grid, block, 0, stream>>>(b);
-    else if (es == 8) generic_take_kernel<8><<<grid, block, 0, stream>>>(b);
-    else if (es == 16) generic_take_kernel<16><<<grid, block, 0, stream>>>(b);
-    else ok = false;
-  } else if (k.kind == K_ROWS_ADD_TAKE) {
-    switch (k.arith) {
-      case ARITH_F16: ok = launchAddTakeRowsOfType<_Float16>(vb, s, b, grid, block, stream); break;
-      case ARITH_BF16: ok = launchAddTakeRowsOfType<__bf16>(vb, s, b, grid, block, stream); break;
-      case ARITH_F32: ok = launchAddTakeRowsOfType<float>(vb, s, b, grid, block, stream); break;
-      case ARITH_F64: ok = launchAddTakeRowsOfType<double>(vb, s, b, grid, block, stream); break;
-      default: ok = false; break;
-    }
-  } else if (k.kind == K_GENERIC_ADD_TAKE) {
-    switch (k.arith) {
-      case ARITH_F16: ok = launchAddTakeGenericOfType<_Float16>(es / 2, b, grid, block, stream); break;
-      case ARITH_BF16: ok = es == 2 && launchAddTakeGenericOfType<__bf16>(1, b, grid, block, stream); break;
-      case ARITH_F32: ok = launchAddTakeGenericOfType<float>(es / 4, b, grid, block, stream); break;
-      case ARITH_F64: ok = launchAddTakeGenericOfType<double>(es / 8, b, grid, block, stream); break;
-      default: ok = false; break;
-    }
-  } else {
-    ok = false;
+    ok = dispatchElementSize(k.es, [&](auto es) { generic_take_kernel<decltype(es)::value><<<grid, block, 0, stream>>>(b); });
+  } else if (k.kind == K_ROWS_ADD_TAKE || k.kind == K_GENERIC_ADD_TAKE) {
+    ok = dispatchArith(k.arith, [&](auto t) {
+      using T = typename decltype(t)::type;
+      if (k.kind == K_ROWS_ADD_TAKE)
+        return dispatchLaneWidth<T>(k.vec, [&](auto w) {
+          dispatchAccess(s, [&](auto a) {
+            rows_accumulate_take_kernel<T, decltype(w)::value, decltype(a)::value><<<grid, block, 0, stream>>>(b);
+          });
+        });
+      // (there is no complex bf16 type: the two-real form of bf16 is compiled here and never launched)
+      return (!std::is_same<T, __bf16>::value || k.es == 2) && dispatchInt<1, 2>(k.es / (int)sizeof(T), [&](auto nc) {
+               generic_accumulate_take_kernel<T, decltype(nc)::value><<<grid, block, 0, stream>>>(b);
+             });
+    });
   }
   if (!ok) CD_INTERNAL_ERROR("no take kernel for this kind, arithmetic type, lane width and element size");
   CD_CHECK_HIP(hipGetLastError());
