@@ -330,7 +330,7 @@ void cudecompCommInfo::release() {
     (void)hipDeviceSynchronize();
     unsigned long long v = 0;
     if (hipMemcpy(&v, dev_epoch, sizeof(v), hipMemcpyDeviceToHost) == hipSuccess) high = std::max<uint64_t>(high, v);
-    // (the cell belongs to the handle's slab of epoch cells, transport.cc devEpoch: nothing to free here)
+    // (the cell belongs to the handle's slab of epoch cells, peer_context.cc devEpoch: nothing to free here)
     (void)hipGetLastError();
     dev_epoch = nullptr;
   }
@@ -642,7 +642,7 @@ cudecompResult_t cudecompGridDescDestroy(cudecompHandle_t handle, cudecompGridDe
     delete grid_desc;  // (drains the device if the descriptor ran one-sided exchanges)
     // the LAST exchange of a descriptor has no later call that would report a wait kernel that gave up: do it here
     if (one_sided) peerCheckStatus(handle);
-    // mappings of user buffers their owners have re-created since are kept open on purpose (transport.cc map()); bound them
+    // mappings of user buffers their owners have re-created since are kept open on purpose (peer_context.cc map()); bound them
     peerTrimRetiredImports(handle, 32);
 
   }
@@ -792,7 +792,7 @@ cudecompResult_t cudecompFree(cudecompHandle_t handle, cudecompGridDesc_t grid_d
   try {
     checkHandle(handle);
     checkGridDesc(handle, grid_desc);
-    if (buffer) workspaceFree(handle, grid_desc, buffer);
+    if (buffer) workspaceFree(handle, buffer);
   }
   CD_API_CATCH()
   return CUDECOMP_RESULT_SUCCESS;

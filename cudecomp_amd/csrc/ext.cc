@@ -637,7 +637,7 @@ cudecompResult_t cudecompExtRunLocalPhases(const cudecompExtGridSpec_t* grid, in
     const TransposePlan p = buildTransposePlan(g, rank, (TransposeOp)op, zero, zero, zero, zero, input == output, traits, P);
     void* bufs[3] = {input, output, work};
     // the launches of the executor: one batched launch per phase; pipelined: one launch per STAGE with all peers in it
-    // for the one-sided transport (transport.cc: peerStagedExchange), one launch per PEER for RCCL / MPI (the reference's
+    // for the one-sided transport (peer_exchange.cc: peerStagedExchange), one launch per PEER for RCCL / MPI (the reference's
     // pipeline, transpose.h:470-513, 683-744)
     int stages = 4;
     if (const char* v = std::getenv("CUDECOMP_PIPELINE_STAGES")) stages = (int)std::strtol(v, nullptr, 10);

@@ -26,8 +26,8 @@
 
 namespace cudecomp {
 enum ExecPath { PATH_LOCAL = 0, PATH_RCCL, PATH_MPI, PATH_PEER_BARRIER, PATH_PEER_FUSED, PATH_PEER_PIPELINED };
-class RcclContext;  // transport.cc
-class PeerContext;  // transport.cc
+class RcclContext;  // peer_context.h
+class PeerContext;  // peer_context.h
 }  // namespace cudecomp
 
 // One row or column of the process grid as seen by this rank.
@@ -85,7 +85,7 @@ struct cudecompHandle {
   void* relay_buf = nullptr;          // my relay region (a library region mapped into every rank), grown on demand
   size_t relay_bytes = 0;
   hipEvent_t relay_last_call = nullptr;  // end of the handle's last relayed transpose (relayed calls run one after the other)
-  int census_compute_queues = -1, census_queue_slots = 0;  // last census of the device's compute queues (transport.cc)
+  int census_compute_queues = -1, census_queue_slots = 0;  // last census of the device's compute queues (peer_diag.cc)
   bool queue_warned = false;          // the "hardware queues oversubscribed" note (ranks sharing a device) was printed
   bool halo_overlap_disable = false;  // CUDECOMP_DISABLE_HALO_OVERLAP=1
   bool halo_overlap_force = false;    // CUDECOMP_FORCE_HALO_OVERLAP=1: also for faces below the size threshold (tests)

@@ -153,7 +153,7 @@ TransposeFieldsPlan buildTransposeFieldsPlan(const GridShape& g, int rank, Trans
                                              const int32_t* out_halo, const int32_t* in_pad, const int32_t* out_pad, bool inplace,
                                              const TransportTraits& traits, int npergroup, int n_fields);
 
-// ---- two-hop relay of a low-fan-out exchange over the whole node (transport.cc: peerRelayAlltoall) ----------------------
+// ---- two-hop relay of a low-fan-out exchange over the whole node (peer_exchange.cc: peerRelayAlltoall) ----------------------
 // On a full xGMI mesh an exchange among P members drives P - 1 of a GPU's links.  On a pencil grid P is small -- the
 // X<->Y exchange of a 2 x 4 grid has P = 2: half a pencil through ONE link while six links idle.  Here every outgoing chunk
 // is cut into `nranks` equal slices (nranks = all ranks of the node); slice q travels source -> rank q -> destination, the

@@ -19,7 +19,11 @@
 //         buffers from cudecompMalloc are mapped once at allocation (NVSHMEM enums require them, as the
 //         reference does); the MPI enums take any device buffer and exchange descriptors per call.
 //
-// A build with MPI=1 adds the ROCm-aware-MPI implementation of the MPI_* enums (transport_mpi.cc).
+// A build with MPI=1 adds the ROCm-aware-MPI implementation of the MPI_* enums (bootstrap_mpi.cc).
+//
+// This is the one header the rest of the library includes.  Behind it: transport.cc (world bootstrap, RCCL, the dispatchers that
+// pick RCCL, MPI or PEER), peer_exchange.cc (the one-sided exchanges), peer_context.cc (IPC regions, pool, board, flags,
+// rendezvous), workspace.cc (cudecompMalloc / cudecompFree), peer_diag.cc (census, probes, verifier); they share peer_context.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -60,7 +64,7 @@ void workspaceFreeRaw(cudecompHandle_t h, void* ptr);
 void workspaceTrimPool(cudecompHandle_t h);
 // mappings of re-created user buffers that are kept open (see PeerContext::map): close all but the newest `keep`
 void peerTrimRetiredImports(cudecompHandle_t h, size_t keep);
-void workspaceFree(cudecompHandle_t h, cudecompGridDesc_t gd, void* ptr);       // collective
+void workspaceFree(cudecompHandle_t h, void* ptr);                              // collective
 
 struct ExchangeBuffers {
   char* send;  // base of the send area (device pointer)
@@ -88,8 +92,7 @@ PeerCall peerBegin(cudecompHandle_t h, cudecompCommInfo& ci, bool rendezvous, co
 // Two-hop relay of a low-fan-out exchange (plan.h RelayPlan): `world` is the descriptor's communicator of all ranks, `call`
 // the call state begun on IT (peerBegin with the symmetric workspace).  Grows the handle's relay region when needed
 // (collective).  Ordered on `stream`, nothing blocks the host.
-bool peerRelayApplies(cudecompHandle_t h, cudecompGridDesc_t gd, const TransposePlan& plan, cudecompTransposeCommBackend_t backend,
-                      bool inplace);
+bool peerRelayApplies(cudecompHandle_t h, cudecompGridDesc_t gd, const TransposePlan& plan, cudecompTransposeCommBackend_t backend);
 bool peerRelayEnsureRegion(cudecompHandle_t h, const RelayPlan& rp, int es);
 void peerRelayAlltoall(cudecompHandle_t h, cudecompCommInfo& world, const TransposePlan& plan, const RelayPlan& rp,
                        const ExchangeBuffers& b, int es, const PeerCall& call, hipStream_t stream);
@@ -97,9 +100,8 @@ void peerRelayAlltoall(cudecompHandle_t h, cudecompCommInfo& world, const Transp
 // All-to-all of the plan's chunks among the members of `ci`.  `stream` carries the pack kernels before and
 // the unpack kernels after; on return the exchange is ordered on `stream`.  `call` = peerBegin's result for the
 // one-sided transport (nullptr for RCCL / MPI).
-void alltoallExchange(cudecompHandle_t h, cudecompGridDesc_t gd, cudecompCommInfo& ci, const TransposePlan& plan,
-                      const ExchangeBuffers& b, int es, cudecompTransposeCommBackend_t backend, const PeerCall* call,
-                      hipStream_t stream);
+void alltoallExchange(cudecompHandle_t h, cudecompCommInfo& ci, const TransposePlan& plan, const ExchangeBuffers& b, int es,
+                      cudecompTransposeCommBackend_t backend, const PeerCall* call, hipStream_t stream);
 
 // Fused pack + put (NVSHMEM_SM enum): runs the plan's pack moves with the peers' receive areas -- or, with
 // call.direct, their output pencils -- as destinations.
@@ -109,8 +111,8 @@ void peerPutExchange(cudecompHandle_t h, cudecompCommInfo& ci, const TransposePl
 // Staged pipeline of the one-sided transport (pack / send / unpack overlapped stage by stage, all peers in every
 // stage).  Runs the plan's pack and unpack moves itself.
 bool peerPipelineAvailable(cudecompHandle_t h, const cudecompCommInfo& ci);
-void peerStagedExchange(cudecompHandle_t h, cudecompGridDesc_t gd, cudecompCommInfo& ci, const TransposePlan& plan,
-                        void* const bufs[3], const ExchangeBuffers& b, int es, const PeerCall& call, hipStream_t stream);
+void peerStagedExchange(cudecompHandle_t h, cudecompCommInfo& ci, const TransposePlan& plan, void* const bufs[3],
+                        const ExchangeBuffers& b, int es, const PeerCall& call, hipStream_t stream);
 
 // debugging aid (CUDECOMP_DEBUG_VERIFY_EXCHANGE=1): host-synchronous check of what a one-sided exchange delivered
 void peerVerifyExchange(cudecompHandle_t h, cudecompCommInfo& ci, const TransposePlan& plan, const ExchangeBuffers& b, int es,

@@ -102,7 +102,7 @@ bool runAsGraph(cudecompHandle_t h, cudecompGridDesc_t gd, const TransposePlan& 
                 hipStream_t stream) {
   if (!h->graphs_enable || gd->graphs_failed || !plan.exchange) return false;
   if (!(backend == CUDECOMP_TRANSPOSE_COMM_NVSHMEM || backend == CUDECOMP_TRANSPOSE_COMM_NVSHMEM_PL)) return false;
-  if (peerRelayApplies(h, gd, plan, backend, inplace)) return false;  // (the relay allocates on first use; it runs eagerly)
+  if (peerRelayApplies(h, gd, plan, backend)) return false;  // (the relay allocates on first use; it runs eagerly)
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
     (void)hipGetLastError();
@@ -294,7 +294,7 @@ void runTransposeFields(cudecompHandle_t h, cudecompGridDesc_t gd, TransposeOp o
   }
   gd->path_count[xpath]++;
   launch(plan.pack, fp.pack_step);
-  alltoallExchange(h, gd, ci, plan, xb, es, backend, one_sided ? &call : nullptr, stream);
+  alltoallExchange(h, ci, plan, xb, es, backend, one_sided ? &call : nullptr, stream);
   launch(plan.unpack, fp.unpack_step);
 }
 
@@ -342,7 +342,7 @@ void executeTranspose(cudecompHandle_t h, cudecompGridDesc_t gd, const Transpose
   PeerCall call;
   // Two-hop relay (opt-in, CUDECOMP_TWO_HOP_RELAY=1): a low-fan-out exchange of the NVSHMEM enum travels through ALL ranks
   // of the node, ordered by the flags of the descriptor's communicator of all ranks (plan.h RelayPlan).
-  if (!pipelined && !in_capture && xpath == PATH_PEER_BARRIER && peerRelayApplies(h, gd, plan, backend, inplace)) {
+  if (!pipelined && !in_capture && xpath == PATH_PEER_BARRIER && peerRelayApplies(h, gd, plan, backend)) {
     auto rit = gd->relay_plans.find(key);
     if (rit == gd->relay_plans.end()) {
       TransportTraits traits;
@@ -409,7 +409,7 @@ void executeTranspose(cudecompHandle_t h, cudecompGridDesc_t gd, const Transpose
     gd->path_count[xpath]++;
     launchMoves(plan.pack.data(), (int)plan.pack.size(), bufs, es, stream, &h->tuning);
     perfMark(pev, 1, stream);
-    alltoallExchange(h, gd, ci, plan, xb, es, backend, one_sided ? &call : nullptr, stream);
+    alltoallExchange(h, ci, plan, xb, es, backend, one_sided ? &call : nullptr, stream);
     perfMark(pev, 2, stream);
     launchMoves(plan.unpack.data(), (int)plan.unpack.size(), bufs, es, stream, &h->tuning);
     perfMark(pev, 3, stream);
@@ -417,10 +417,10 @@ void executeTranspose(cudecompHandle_t h, cudecompGridDesc_t gd, const Transpose
   }
 
   if (one_sided) {
-    // staged pipeline: pack / send / unpack overlap stage by stage with all peers in every stage (transport.cc)
+    // staged pipeline: pack / send / unpack overlap stage by stage with all peers in every stage (peer_exchange.cc)
     gd->path_count[PATH_PEER_PIPELINED]++;
     perfMark(pev, 1, stream);
-    peerStagedExchange(h, gd, ci, plan, bufs, xb, es, call, stream);
+    peerStagedExchange(h, ci, plan, bufs, xb, es, call, stream);
     perfMark(pev, 2, stream);
     perfMark(pev, 3, stream);
     return;

@@ -102,7 +102,7 @@ def stage_of_move(m, axis, k, K):
 
 
 def staged_exchange_gloo(plan, bufs, stages, rank, itemsize, dt):
-    """The staged pipeline of the one-sided pipelined transports (csrc/transport.cc peerStagedExchange) with a real
+    """The staged pipeline of the one-sided pipelined transports (csrc/peer_exchange.cc peerStagedExchange) with a real
     multi-process exchange: all pack stages, then per stage the contiguous sub-chunks travel over gloo and the stage's
     range of every source is unpacked.  The receive area is poisoned first."""
     import torch
@@ -145,7 +145,7 @@ def staged_exchange_gloo(plan, bufs, stages, rank, itemsize, dt):
 
 
 def relayed_exchange_gloo(plan, relays, bufs, rank, nranks, itemsize, dt):
-    """The two-hop relay (csrc/plan.h RelayPlan, csrc/transport.cc peerRelayAlltoall) with a real multi-process exchange: every
+    """The two-hop relay (csrc/plan.h RelayPlan, csrc/peer_exchange.cc peerRelayAlltoall) with a real multi-process exchange: every
     rank derives the relay moves of ALL ranks from the stateless planner (as the library does), so a receiver knows what
     each sender will send it in either step and in which order.  Step 1 scatters my slices (relay slots of the other ranks /
     two direct slices per chunk), step 2 forwards what landed in MY relay region; relay region and receive area start

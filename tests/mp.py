@@ -320,7 +320,7 @@ def _pool_run(nranks, module, func, args, timeout, extra_env):
 # ("hipIpcGetMemHandle failed: invalid argument"; on the importing ranks "a peer rank could not export its buffer over IPC").  Seen
 # twice in about twenty suite runs of round 6, both times with eight processes on the one GPU creating and releasing shared workspaces
 # (gpurun_out/r06_sixth: subcomm_test; profiles/r06_ipc_export_refused.log: the CUDECOMP_WORKSPACE_POOL_MIB=0 arm of the switch sweep);
-# the library had already tried four allocations at other addresses (csrc/transport.cc workspaceAllocRaw) and goes on without the
+# the library had already tried four allocations at other addresses (csrc/workspace.cc workspaceAllocRaw) and goes on without the
 # one-sided transport, which the backends under test need.  Not a property of the kernels, plans or transports.
 IPC_EXPORT_REFUSED = ("could not export its buffer over IPC", "hipIpcGetMemHandle failed")
 

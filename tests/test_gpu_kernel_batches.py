@@ -331,7 +331,7 @@ def test_nine_transposes(es):
 
 
 # ---- destination bases: the calling form of the one-sided transports, on local memory ----------------------------------------------
-# csrc/transport.cc gives EVERY move of an exchange the receive area (or output pencil) of the member it feeds as its destination
+# csrc/peer_exchange.cc gives EVERY move of an exchange the receive area (or output pencil) of the member it feeds as its destination
 # base, the rank's own slot included (remote_recv[own rank] is its own buffer): a local buffer behind a base pointer is what the
 # library itself passes.
 @pytest.mark.parametrize("what", ["rows", "generic", "transposes"])

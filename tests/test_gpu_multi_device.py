@@ -135,7 +135,7 @@ def test_native_programs_across_devices(n):
 
 
 def test_link_probe_reports_cross_device_rates():
-    """The start-up link probe (transport.cc peerMeasureLink) must see different devices and measure both engines."""
+    """The start-up link probe (peer_diag.cc peerMeasureLink) must see different devices and measure both engines."""
     _need(2)
     res = run_ranks(2, "tests.gpu_bodies", "link_info", {}, timeout=300, extra_env=ENV)
     for r in res:

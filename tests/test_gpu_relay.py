@@ -1,4 +1,4 @@
-"""Two-hop relay of low-fan-out exchanges (CUDECOMP_TWO_HOP_RELAY=1; csrc/plan.h RelayPlan, csrc/transport.cc
+"""Two-hop relay of low-fan-out exchanges (CUDECOMP_TWO_HOP_RELAY=1; csrc/plan.h RelayPlan, csrc/peer_exchange.cc
 peerRelayAlltoall): on a pencil grid whose X<->Y or Y<->Z exchange has two members, every chunk is cut into one slice per
 rank of the node and travels source -> relay -> destination, so that all links carry data instead of one.  Ranks share the
 test box's GPU here, so this checks the protocol (flags of the communicator of all ranks, relay slots, forwarding) and the

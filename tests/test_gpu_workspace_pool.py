@@ -1,5 +1,5 @@
 """cudecompMalloc / cudecompFree on a multi-rank job: released workspaces are parked WITH the peers' IPC mappings and
-handed out again (csrc/transport.cc: takeFromPool / park), new mappings are verified by page tags.  Reference contract:
+handed out again (csrc/peer_context.cc: takeFromPool / park), new mappings are verified by page tags.  Reference contract:
 cudecompMalloc / cudecompFree are collective (include/cudecomp.h:433-455); what they do underneath is the library's
 business."""
 import pytest

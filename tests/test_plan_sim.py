@@ -185,7 +185,7 @@ from tests.bodies import stage_of_move as _stage_of  # noqa: E402
 
 
 def simulate_staged_transpose(d, op, halos, pads, inplace, stages, npergroup):
-    """The staged pipeline of the one-sided pipelined transports (csrc/transport.cc peerStagedExchange) on host arrays:
+    """The staged pipeline of the one-sided pipelined transports (csrc/peer_exchange.cc peerStagedExchange) on host arrays:
     stage by stage, pack the stage's range of every chunk, deliver ONLY the matching contiguous sub-chunks, unpack the
     stage's range from every source.  The receive areas start poisoned, so an unpack stage that touched a range
     belonging to a later stage would spoil the output."""
@@ -422,7 +422,7 @@ def test_index_maps_reject_bad_arguments():
         cd.cudecompExtPencilInfo(bad, 0, 0)
 
 
-# ---- two-hop relay of low-fan-out exchanges (csrc/plan.h RelayPlan, csrc/transport.cc peerRelayAlltoall) --------------------
+# ---- two-hop relay of low-fan-out exchanges (csrc/plan.h RelayPlan, csrc/peer_exchange.cc peerRelayAlltoall) --------------------
 def simulate_relayed_transpose(d, op, halos, pads, inplace):
     """The relayed exchange on host arrays, rank by rank as the executor orders it: pack; step 1 -- every rank scatters the
     slices of its chunks into the relay regions of all ranks (two slices per chunk straight into the destination's
