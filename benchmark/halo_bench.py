@@ -12,7 +12,10 @@ with parity -1, centering 0 and clear 0 / 1: the reflection's two sibling moves 
 (6 * face bytes), the ghost cells zeroed as well (8 * face bytes) and, with --fields N, cudecompAmdUpdateFieldHalosX
 (cudecomp_halo_fields.h) on N such pencils, periodic: the update's two wrap copies for all N in one launch (N * 4 * face bytes) and,
 with --accumulate --fields N / --accumulate-clear --fields N, cudecompAmdAccumulateFieldHalosX (cudecomp_halo_accumulate_fields.h) with
-clear 0 / 1 on N such pencils: the two wrap additions for all N in one launch (N * 6 / N * 8 * face bytes).
+clear 0 / 1 on N such pencils: the two wrap additions for all N in one launch (N * 6 / N * 8 * face bytes) and, with --wall-fields N,
+cudecompAmdReflectFieldHalosX and cudecompAmdFoldFieldHalosX (cudecomp_halo_wall_fields.h; centering 0, clear 0, parities -1, +1, -1, ...)
+on N such pencils as a NON-periodic single rank: one call for all N against N single calls with the same parities, the two arms
+timed alternately in both orders (fields first, then singles; singles first, then fields) with every shape warmed up before.
 Per dim: `--reps` repetitions of `--calls` back-to-back calls each, ms per call of every repetition, their
 min / median / max, and GB/s of the median against the algorithmic bytes (update: 2 faces read + written,
 4 * face bytes; accumulation: 2 faces read, 2 destinations read and written, 6 * face bytes; fill: 2 halos written, 2 * face
@@ -70,6 +73,9 @@ def main():
     ap.add_argument("--accumulate", action="store_true",
                     help="with --fields N: also time cudecompAmdAccumulateFieldHalosX (clear 0) on the N pencils and compare every field "
                          "on the device with a clone accumulated by single calls; with --accumulate-clear --fields N: the same with clear 1")
+    ap.add_argument("--wall-fields", type=int, default=0, metavar="N",
+                    help="also time cudecompAmdReflectFieldHalosX / cudecompAmdFoldFieldHalosX on N pencils (non-periodic) against N single "
+                         "calls, both orders of the two arms, and compare every field on the device with a clone served by single calls")
     ap.add_argument("--gdims", type=int, nargs=3, default=[2048, 1024, 256], metavar="N",
                     help="the pencil (default: config 5's per-rank X pencil; 64 64 64: a pencil on which fixed cost dominates)")
     ap.add_argument("--json", metavar="FILE", default=None, help="also write the result line to FILE")
@@ -242,9 +248,67 @@ def main():
                 differ += int(torch.count_nonzero(t.view(torch.int64) != c.view(torch.int64)))
             extra[name + "_field_cells_that_differ_from_single_calls"] = differ
         cd.cudecompFree(h, gd, fwork)
+    if a.wall_fields:
+        n = a.wall_fields
+        wall = [torch.randn(p.size, dtype=torch.float64, device="cuda") for _ in range(n)]
+        wptrs = [t.data_ptr() for t in wall]
+        parities = [1 if f % 3 == 1 else -1 for f in range(n)]
+        none = (0, 0, 0)
+
+        def arms(op, dim):
+            if op == "reflect":
+                def many():
+                    cd.cudecompReflectFieldHalos(0, h, gd, wptrs, cd.DOUBLE, parities, 0, halo, none, dim, stream=st)
+
+                def singles():
+                    for q, s in zip(wptrs, parities):
+                        cd.cudecompReflectHalos(0, h, gd, q, cd.DOUBLE, s, 0, halo, none, dim, stream=st)
+            else:
+                def many():
+                    cd.cudecompFoldFieldHalos(0, h, gd, wptrs, cd.DOUBLE, parities, 0, 0, halo, none, dim, stream=st)
+
+                def singles():
+                    for q, s in zip(wptrs, parities):
+                        cd.cudecompFoldHalos(0, h, gd, q, cd.DOUBLE, s, 0, 0, halo, none, dim, stream=st)
+            return many, singles
+
+        for op, per_byte in (("reflect", 4), ("fold", 6)):
+            for dim in range(3):
+                rec = res["dim%d" % dim]
+                many, singles = arms(op, dim)
+                for t in wall:
+                    t.normal_()
+                out = {}
+                for order in ("fields_first", "singles_first"):  # (_time warms every arm up before it times it)
+                    pair = [("fields", many), ("singles", singles)]
+                    for arm, fn in (pair if order == "fields_first" else pair[::-1]):
+                        out[order + "_" + arm] = _record(_time(fn, a.reps, a.calls), n * per_byte * faces[dim] * 8)
+                many()
+                out["kernel"] = cd.cudecompExtLastKernelName()
+                out["fields_over_singles"] = [round(out[o + "_fields"]["median_ms"] / out[o + "_singles"]["median_ms"], 3)
+                                              for o in ("fields_first", "singles_first")]
+                rec[op + "_wall_fields"] = out
+        # after the timing: fresh payloads, reflection along dims 0, 1, 2 and fold along 2, 1, 0 by the field calls against single calls
+        # on clones, on the device
+        for t in wall:
+            t.normal_()
+        clones = [t.clone() for t in wall]
+        for op, dims in (("reflect", (0, 1, 2)), ("fold", (2, 1, 0))):
+            for dim in dims:
+                many, _ = arms(op, dim)
+                many()
+                for c, s in zip(clones, parities):
+                    if op == "reflect":
+                        cd.cudecompReflectHalos(0, h, gd, c.data_ptr(), cd.DOUBLE, s, 0, halo, none, dim, stream=st)
+                    else:
+                        cd.cudecompFoldHalos(0, h, gd, c.data_ptr(), cd.DOUBLE, s, 0, 0, halo, none, dim, stream=st)
+        torch.cuda.synchronize()
+        extra["n_wall_fields"] = n
+        extra["wall_field_cells_that_differ_from_single_calls"] = sum(
+            int(torch.count_nonzero(t.view(torch.int64) != c.view(torch.int64))) for t, c in zip(wall, clones))
     cd.cudecompFree(h, gd, work)
     cd.cudecompGridDescDestroy(h, gd)
-    line = json.dumps(dict({"workload": "X pencil %dx%dx%d fp64 + halo %d, periodic single rank, per dim: update (self copy), "
+    line = json.dumps(dict({"workload": "X pencil %dx%dx%d fp64 + halo %d, single rank, periodic where not said otherwise, per dim: update (self copy), "
                                         "accumulation (self add)%s; %d repetitions of %d calls"
                                         % (gdims + (a.halo,) + ((" and fill (zero)" if a.fill else "") + (" and accumulate-and-clear" if a.accumulate_clear else "")
                                            + (" and reflection (non-periodic, odd mirror, centering 0)" if a.reflect else "")
@@ -252,7 +316,9 @@ def main():
                                            + (" and fold with clear" if a.fold_clear else "")
                                            + (" and the update of %d pencils in one call" % a.fields if a.fields else "")
                                            + (" and their accumulation in one call" if a.fields and a.accumulate else "")
-                                           + (" and their accumulate-and-clear in one call" if a.fields and a.accumulate_clear else ""),
+                                           + (" and their accumulate-and-clear in one call" if a.fields and a.accumulate_clear else "")
+                                           + (" and the reflection and the fold of %d pencils in one call (non-periodic)" % a.wall_fields
+                                              if a.wall_fields else ""),
                                            a.reps, a.calls)),
                             "device": torch.cuda.get_device_name(0), "result": res}, **extra))
     print(line)
@@ -269,6 +335,9 @@ def main():
         if extra.get(name + "_field_cells_that_differ_from_single_calls"):
             sys.exit("halo_bench.py: after the %s fields call along 2, 1, 0 %d cells differ from single calls on clones"
                      % (name, extra[name + "_field_cells_that_differ_from_single_calls"]))
+    if extra.get("wall_field_cells_that_differ_from_single_calls"):
+        sys.exit("halo_bench.py: after the wall field calls %d cells differ from single calls on clones"
+                 % extra["wall_field_cells_that_differ_from_single_calls"])
     for name in ("fold", "fold_clear"):
         if extra.get("interior_cells_with_another_count_after_" + name) or extra.get("ghost_cells_not_zero_after_" + name):
             sys.exit("halo_bench.py: after folding a pencil of ones along 2, 1, 0 (%s pass) %d interior cells do not hold their count and %d "

@@ -167,7 +167,8 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtPlanHaloFold", "cudecompExtFold3D", "cudecompExtPlanHaloFields", "cudecompExtRunFieldMoves",
                "cudecompExtDescribeFieldMoves", "cudecompExtDataLaunchCount", "cudecompExtPlanTransposeFields",
                "cudecompExtRunFieldMoveList", "cudecompExtDescribeFieldMoveList", "cudecompExtDescribeResidency",
-               "cudecompExtPlanHaloAccumulateFields", "cudecompExtRunFieldMovesOp", "cudecompExtDescribeFieldMovesOp"]
+               "cudecompExtPlanHaloAccumulateFields", "cudecompExtRunFieldMovesOp", "cudecompExtDescribeFieldMovesOp",
+               "cudecompExtRunMirroredFieldMoves", "cudecompExtDescribeMirroredFieldMoves", "cudecompExtHaloPlanCount"]
 # include/cudecomp_amd.h: extensions of the API a solver may use
 AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
 # include/cudecomp_amd_fill.h: halo fill
@@ -186,6 +187,11 @@ MAX_HALO_FIELDS = 32  # CUDECOMP_AMD_MAX_HALO_FIELDS
 AMD_ACCUMULATE_FIELDS_SYMBOLS = ["cudecompAmdAccumulateFieldHalosX", "cudecompAmdAccumulateFieldHalosY",
                                  "cudecompAmdAccumulateFieldHalosZ"]
 MAX_HALO_ACCUMULATE_FIELDS = 32  # CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS
+# include/cudecomp_halo_wall_fields.h: multi-field wall halos (reflection and fold of several pencils, a parity per field, one launch)
+AMD_REFLECT_FIELDS_SYMBOLS = ["cudecompAmdReflectFieldHalosX", "cudecompAmdReflectFieldHalosY", "cudecompAmdReflectFieldHalosZ"]
+AMD_FOLD_FIELDS_SYMBOLS = ["cudecompAmdFoldFieldHalosX", "cudecompAmdFoldFieldHalosY", "cudecompAmdFoldFieldHalosZ"]
+AMD_WALL_FIELDS_SYMBOLS = AMD_REFLECT_FIELDS_SYMBOLS + AMD_FOLD_FIELDS_SYMBOLS
+MAX_HALO_WALL_FIELDS = 32  # CUDECOMP_AMD_MAX_HALO_WALL_FIELDS
 # include/cudecomp_transpose_fields.h: multi-field transposes (several pencils in one exchange)
 TRANSPOSE_FIELDS_SYMBOLS = ["cudecompAmdTransposeFieldsXToY", "cudecompAmdTransposeFieldsYToZ", "cudecompAmdTransposeFieldsZToY",
                             "cudecompAmdTransposeFieldsYToX"]
@@ -266,6 +272,7 @@ def lib():
         L.cudecompExtDescribeFieldMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, C.c_uint64, i64, i32, i32,
                                                     C.POINTER(i64)]
         L.cudecompExtDataLaunchCount.argtypes = [C.POINTER(i64)]
+        L.cudecompExtHaloPlanCount.argtypes = [vp, vp, C.POINTER(i64)]
         for name in AMD_ACCUMULATE_FIELDS_SYMBOLS:  # (the multi-field update's arguments with `clear` before the stream)
             getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, vp]
         L.cudecompExtPlanHaloAccumulateFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32,
@@ -273,6 +280,13 @@ def lib():
         L.cudecompExtRunFieldMovesOp.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(vp), i32, vp, i64, i32, i32, i32, i32, vp, pi32]
         L.cudecompExtDescribeFieldMovesOp.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, C.c_uint64, i64, i32, i32,
                                                       i32, i32, C.POINTER(i64)]
+        for name in AMD_REFLECT_FIELDS_SYMBOLS:  # (the reflection's arguments with the lists of fields and parities and their length)
+            getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, i32, pi32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
+        for name in AMD_FOLD_FIELDS_SYMBOLS:  # (... with `clear` after the centering)
+            getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, i32, pi32, i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
+        L.cudecompExtRunMirroredFieldMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(vp), i32, i32, i32, i32, i32, C.c_uint32, vp, pi32]
+        L.cudecompExtDescribeMirroredFieldMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, i32, i32, i32, i32,
+                                                            C.c_uint32, C.POINTER(i64)]
         for name in TRANSPOSE_FIELDS_SYMBOLS:  # (the transpose's arguments with the two lists and their length in the place of `input`, `output`)
             getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), i32, vp, i32, pi32, pi32, pi32, pi32, vp]
         L.cudecompExtPlanTransposeFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, pi32, pi32, pi32, C.c_bool, i32, i32, i32,
@@ -535,6 +549,34 @@ def cudecompAccumulateFieldHalos(axis, handle, gd, ptrs, work, dtype, halo_exten
     arr = None if ptrs is None else (C.c_void_p * max(1, len(ptrs)))(*[p or None for p in ptrs])
     _check(getattr(lib(), name)(handle, gd, arr, 0 if ptrs is None else len(ptrs), work, dtype, _i3(halo_extents), _b3(halo_periods),
                                 dim, _i3(padding), int(clear), stream), name)
+
+
+def _wall_field_tables(ptrs, parities):
+    arr = None if ptrs is None else (C.c_void_p * max(1, len(ptrs)))(*[p or None for p in ptrs])
+    par = None if parities is None else (C.c_int32 * max(1, len(parities)))(*[int(p) for p in parities])
+    return arr, par, (len(ptrs) if ptrs is not None else (len(parities) if parities is not None else 0))
+
+
+def cudecompReflectFieldHalos(axis, handle, gd, ptrs, dtype, parities, centering, halo_extents, halo_periods, dim, padding=None,
+                              stream=None, n_fields=None):
+    """cudecompAmdReflectFieldHalos{X,Y,Z} (cudecomp_halo_wall_fields.h): the reflection along `dim` of every pencil in `ptrs` (device
+    pointers), field f with parity parities[f] (+1 or -1), in one launch.  Nothing is checked here: the library refuses what the
+    header says it refuses.  n_fields: the count passed, when it shall differ from len(ptrs)."""
+    name = "cudecompAmdReflectFieldHalos" + "XYZ"[axis]
+    arr, par, n = _wall_field_tables(ptrs, parities)
+    _check(getattr(lib(), name)(handle, gd, arr, n if n_fields is None else n_fields, dtype, par, int(centering), _i3(halo_extents),
+                                _b3(halo_periods), dim, _i3(padding), stream), name)
+
+
+def cudecompFoldFieldHalos(axis, handle, gd, ptrs, dtype, parities, centering, clear, halo_extents, halo_periods, dim, padding=None,
+                           stream=None, n_fields=None):
+    """cudecompAmdFoldFieldHalos{X,Y,Z} (cudecomp_halo_wall_fields.h): the fold along `dim` of every pencil in `ptrs` (device
+    pointers), field f with parity parities[f], in one launch (one per side where the two sides add onto the same cells); with
+    clear = 1 the ghost cells that were read hold zero bytes afterwards.  Nothing is checked here."""
+    name = "cudecompAmdFoldFieldHalos" + "XYZ"[axis]
+    arr, par, n = _wall_field_tables(ptrs, parities)
+    _check(getattr(lib(), name)(handle, gd, arr, n if n_fields is None else n_fields, dtype, par, int(centering), int(clear),
+                                _i3(halo_extents), _b3(halo_periods), dim, _i3(padding), stream), name)
 
 
 def cudecompTransposeFields(op, handle, gd, inputs, outputs, work, dtype, in_halo=None, out_halo=None, in_pad=None, out_pad=None,
@@ -934,6 +976,30 @@ def cudecompExtDescribeFieldMovesOp(moves, field_addresses, work_address, work_f
     return dict(zip(("kind", "vec", "access", "blocks_per_field", "blocks"), [int(x) for x in out]))
 
 
+MIRROR_REFLECT, MIRROR_FOLD, MIRROR_FOLD_TAKE = 0, 1, 4  # modes of the mirrored field-move pair
+
+
+def cudecompExtRunMirroredFieldMoves(moves, fields, es, mode, dtype, fields_neg=0, force=0, stream=None):
+    """One or two reflect-moves (one dim with a negative source stride) for every buffer of `fields` (device pointers) in one launch:
+    mode 0 reflect, 1 fold, 4 fold and take; bit f of fields_neg flips the sign bits of field f's source on the way; `dtype` names
+    the real type.  Returns the number of launches (0 or 1)."""
+    f = (C.c_void_p * max(1, len(fields)))(*[p or None for p in fields])
+    total = C.c_int32(-1)
+    _check(lib().cudecompExtRunMirroredFieldMoves(_move_list(moves), len(moves), f, len(fields), es, int(force), int(mode), int(dtype),
+                                                  int(fields_neg), stream, C.byref(total)), "cudecompExtRunMirroredFieldMoves")
+    return total.value
+
+
+def cudecompExtDescribeMirroredFieldMoves(moves, field_addresses, es, mode, dtype, fields_neg=0, force=0):
+    """How cudecompExtRunMirroredFieldMoves would run (no launch, no GPU): a dict of kind (31 / 32 reflections, 33 / 34 folds, 35 / 36
+    folds that take; -1 nothing), lane bytes, access mode, workgroups per field and workgroups in all."""
+    f = (C.c_uint64 * max(1, len(field_addresses)))(*[int(p) for p in field_addresses])
+    out = (C.c_int64 * 5)()
+    _check(lib().cudecompExtDescribeMirroredFieldMoves(_move_list(moves), len(moves), f, len(field_addresses), es, int(force), int(mode),
+                                                       int(dtype), int(fields_neg), out), "cudecompExtDescribeMirroredFieldMoves")
+    return dict(zip(("kind", "vec", "access", "blocks_per_field", "blocks"), [int(x) for x in out]))
+
+
 def cudecompExtPlanTransposeFields(grid, rank, op, in_halo=None, out_halo=None, in_pad=None, out_pad=None, inplace=False,
                                    pipelined=False, symmetric_recv=False, npergroup=0, n_fields=1, no_elide=False):
     """Stateless planner of cudecompAmdTransposeFields*: (plan of field 0 with the scaled exchange, pack steps, unpack steps); an end
@@ -988,6 +1054,13 @@ def cudecompExtDataLaunchCount():
     """Data-movement kernel launches of this process so far (cudecomp_ext.h)."""
     n = C.c_int64(-1)
     _check(lib().cudecompExtDataLaunchCount(C.byref(n)), "cudecompExtDataLaunchCount")
+    return n.value
+
+
+def cudecompExtHaloPlanCount(handle, gd):
+    """Halo plans the descriptor has cached so far (cudecomp_ext.h)."""
+    n = C.c_int64(-1)
+    _check(lib().cudecompExtHaloPlanCount(handle, gd, C.byref(n)), "cudecompExtHaloPlanCount")
     return n.value
 
 

@@ -832,23 +832,57 @@ CD_DEFINE_TRANSPOSE(cudecompTransposeZToY, OP_Z_TO_Y)
 CD_DEFINE_TRANSPOSE(cudecompTransposeYToX, OP_Y_TO_X)
 
 // Every halo family (cudecomp.h, cudecomp_amd.h, cudecomp_amd_fill.h, cudecomp_amd_reflect.h, cudecomp_halo_fold.h,
-// cudecomp_halo_fields.h, cudecomp_halo_accumulate_fields.h) checks its arguments here, in one order: handle, descriptor, data type,
-// halo_extents, the return when every halo is zero, input, work, dim; all of it on the host, before anything is launched.  What differs:
+// cudecomp_halo_fields.h, cudecomp_halo_accumulate_fields.h, cudecomp_halo_wall_fields.h) checks its arguments here, in one order:
+// handle, descriptor, data type, halo_extents, the return when every halo is zero, input, work, dim; all of it on the host, before anything is launched.  What differs:
 //  - max_fields > 0: a multi-field family -- the list of fields is checked where the single calls check `input`;
 //  - clear_first: `clear` is checked right after halo_extents, also when every halo is zero (cudecompAmdAccumulateFieldHalos*);
 //  - reflection and folding check parity, centering and `clear` when every halo is zero and otherwise leave them to the runner,
 //    which puts the plan's own refusals in the contract's place (halo.cc);
+//  - wall_fields: reflection and folding of several fields (cudecompAmdReflectFieldHalos*, cudecompAmdFoldFieldHalos*) -- `parities`
+//    is checked for NULL right after the list of fields, and its entries are read where the single calls read `parity`: when every
+//    halo is zero (there the list of fields is not looked at, but `parities` and the n_fields that says how many to read are),
+//    otherwise by the runner.  One field: the single call with parities[0].  Several: the signs travel as a mask of fields;
 //  - the local families (fill, reflection, folding) take no workspace.
-static cudecompResult_t haloApiEntry(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, const HaloCall& c, int max_fields = 0,
-                                     bool clear_first = false) {
+struct HaloEntryOptions {
+  int max_fields = 0;                 // > 0: a multi-field family and the most fields it takes
+  bool clear_first = false;           // `clear` is checked right after halo_extents
+  bool wall_fields = false;           // reflection / folding of several fields: `parities` below is the caller's list (may be NULL)
+  const int32_t* parities = nullptr;
+};
+
+// the caller's parities into the call: one field -- the single call's parity and sign; several -- the mask of the fields with parity
+// -1, and in `parity` the first entry that is neither +1 nor -1 (the runner refuses it where it refuses the single call's).
+// n_fields is in range here.
+static void readWallParities(HaloCall& c, const int32_t* parities) {
+  if (!parities) CD_INVALID_USAGE("parities argument cannot be null");
+  if (c.op.n_fields == 1) {
+    c.parity = parities[0];
+    c.op.negate = parities[0] == -1;
+    return;
+  }
+  for (int32_t f = c.op.n_fields - 1; f >= 0; --f) {
+    if (parities[f] == -1) c.fields_neg |= 1u << f;
+    else if (parities[f] != 1) c.parity = parities[f];
+  }
+}
+
+static cudecompResult_t haloApiEntry(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, const HaloCall& call,
+                                     const HaloEntryOptions& opt = HaloEntryOptions()) {
   try {
+    HaloCall c = call;  // (a multi-field wall call fills in its parities)
     const HaloOp::Kind kind = c.op.kind;
+    const int max_fields = opt.max_fields;
     checkHandle(handle);
     checkGridDesc(handle, grid_desc);
     checkDataType(c.dtype);
     if (!c.halo) CD_INVALID_USAGE("halo_extents argument cannot be null");
-    if (clear_first && c.clear != 0 && c.clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
+    if (opt.clear_first && c.clear != 0 && c.clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
     if (c.halo[0] == 0 && c.halo[1] == 0 && c.halo[2] == 0) {
+      if (opt.wall_fields) {
+        if (!opt.parities) CD_INVALID_USAGE("parities argument cannot be null");
+        if (c.op.n_fields < 1 || c.op.n_fields > max_fields) CD_INVALID_USAGE("n_fields argument out of range");
+        readWallParities(c, opt.parities);
+      }
       if (kind == HaloOp::REFLECT || kind == HaloOp::FOLD) {
         if (c.parity != 1 && c.parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
         if (c.op.centering != 0 && c.op.centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
@@ -867,6 +901,7 @@ static cudecompResult_t haloApiEntry(cudecompHandle_t handle, cudecompGridDesc_t
         for (int32_t j = 0; j < i; ++j)
           if (c.fields[j] == c.fields[i]) CD_INVALID_USAGE("inputs argument cannot hold the same field twice");
       }
+      if (opt.wall_fields) readWallParities(c, opt.parities);
     }
     if ((kind == HaloOp::UPDATE || kind == HaloOp::ACCUMULATE) && !c.work) CD_INVALID_USAGE("work argument cannot be null");
     if (c.dim < 0 || c.dim > 2) CD_INVALID_USAGE("dim argument out of range");
@@ -967,7 +1002,9 @@ CD_DEFINE_HALO_FOLD(cudecompAmdFoldHalosZ, 2)
                         int32_t dim, const int32_t padding[], hipStream_t stream) {                                            \
     HaloCall c = haloCall(HaloOp::UPDATE, AXIS, inputs, work, dtype, halo_extents, halo_periods, dim, padding, stream);        \
     c.op.n_fields = n_fields;                                                                                                  \
-    return haloApiEntry(handle, grid_desc, c, CUDECOMP_AMD_MAX_HALO_FIELDS);                                                   \
+    HaloEntryOptions opt;                                                                                                      \
+    opt.max_fields = CUDECOMP_AMD_MAX_HALO_FIELDS;                                                                             \
+    return haloApiEntry(handle, grid_desc, c, opt);                                                                            \
   }
 CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosX, 0)
 CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosY, 1)
@@ -982,11 +1019,40 @@ CD_DEFINE_HALO_FIELDS(cudecompAmdUpdateFieldHalosZ, 2)
     c.op.n_fields = n_fields;                                                                                                  \
     c.clear = clear;                                                                                                           \
     c.op.clear = clear != 0;                                                                                                   \
-    return haloApiEntry(handle, grid_desc, c, CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS, true);                                  \
+    HaloEntryOptions opt;                                                                                                      \
+    opt.max_fields = CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS;                                                                  \
+    opt.clear_first = true;                                                                                                    \
+    return haloApiEntry(handle, grid_desc, c, opt);                                                                            \
   }
 CD_DEFINE_HALO_ACCUMULATE_FIELDS(cudecompAmdAccumulateFieldHalosX, 0)
 CD_DEFINE_HALO_ACCUMULATE_FIELDS(cudecompAmdAccumulateFieldHalosY, 1)
 CD_DEFINE_HALO_ACCUMULATE_FIELDS(cudecompAmdAccumulateFieldHalosZ, 2)
+
+// cudecomp_halo_wall_fields.h: the reflection and the fold of several pencils, each with a parity of its own, in one launch
+#define CD_DEFINE_HALO_WALL_FIELDS(NAME, KIND, AXIS, CLEAR_PARAM, CLEAR)                                                       \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const inputs[], int32_t n_fields,         \
+                        cudecompDataType_t dtype, const int32_t parities[], int32_t centering CLEAR_PARAM,                     \
+                        const int32_t halo_extents[], const bool halo_periods[], int32_t dim, const int32_t padding[],         \
+                        hipStream_t stream) {                                                                                  \
+    HaloCall c = haloCall(HaloOp::KIND, AXIS, inputs, nullptr, dtype, halo_extents, halo_periods, dim, padding, stream);       \
+    c.op.n_fields = n_fields;                                                                                                  \
+    c.op.centering = centering;                                                                                                \
+    c.clear = CLEAR;                                                                                                           \
+    c.op.clear = CLEAR == 1;                                                                                                   \
+    HaloEntryOptions opt;                                                                                                      \
+    opt.max_fields = CUDECOMP_AMD_MAX_HALO_WALL_FIELDS;                                                                        \
+    opt.wall_fields = true;                                                                                                    \
+    opt.parities = parities;                                                                                                   \
+    return haloApiEntry(handle, grid_desc, c, opt);                                                                            \
+  }
+#define CD_NO_CLEAR_PARAM
+#define CD_CLEAR_PARAM , int32_t clear
+CD_DEFINE_HALO_WALL_FIELDS(cudecompAmdReflectFieldHalosX, REFLECT, 0, CD_NO_CLEAR_PARAM, 0)
+CD_DEFINE_HALO_WALL_FIELDS(cudecompAmdReflectFieldHalosY, REFLECT, 1, CD_NO_CLEAR_PARAM, 0)
+CD_DEFINE_HALO_WALL_FIELDS(cudecompAmdReflectFieldHalosZ, REFLECT, 2, CD_NO_CLEAR_PARAM, 0)
+CD_DEFINE_HALO_WALL_FIELDS(cudecompAmdFoldFieldHalosX, FOLD, 0, CD_CLEAR_PARAM, clear)
+CD_DEFINE_HALO_WALL_FIELDS(cudecompAmdFoldFieldHalosY, FOLD, 1, CD_CLEAR_PARAM, clear)
+CD_DEFINE_HALO_WALL_FIELDS(cudecompAmdFoldFieldHalosZ, FOLD, 2, CD_CLEAR_PARAM, clear)
 
 // cudecomp_transpose_fields.h: the transpose of several pencils with one exchange.  The checks of transposeEntry, in its order,
 // with the lists checked where the transpose checks `input` and `output`; all of it on the host, before anything is launched.

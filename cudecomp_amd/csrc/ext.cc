@@ -8,6 +8,7 @@
 #include "cudecomp_ext.h"
 #include "cudecomp_halo_fields.h"
 #include "cudecomp_halo_accumulate_fields.h"
+#include "cudecomp_halo_wall_fields.h"
 #include "cudecomp_transpose_fields.h"
 #include "errors.h"
 #include "internal.h"
@@ -1001,6 +1002,67 @@ cudecompResult_t cudecompExtDescribeFieldMovesOp(const cudecompExtMove_t* moves,
   return CUDECOMP_RESULT_SUCCESS;
 }
 
+// the operation of the mirrored pair onto an imported list: every move a reflect-move, with add (and take) as the mode says
+static ArithType applyMirroredFieldMoveMode(std::vector<Move3D>& list, int32_t mode, cudecompDataType_t dtype, int32_t es) {
+  if (mode != 0 && mode != 1 && mode != 4) CD_INVALID_USAGE("mode must be 0 (reflect), 1 (fold) or 4 (fold and take)");
+  if (elementSize(dtype) != es) CD_INVALID_USAGE("element size does not match the data type");
+  for (Move3D& m : list) {
+    m.reflect = true;
+    m.add = mode != 0;
+    m.take = mode == 4;
+  }
+  return arithOf(dtype);
+}
+
+cudecompResult_t cudecompExtRunMirroredFieldMoves(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
+                                                 int32_t es, int32_t force, int32_t mode, cudecompDataType_t dtype,
+                                                 uint32_t fields_neg, hipStream_t stream, int32_t* n_launches) {
+  try {
+    if (!fields) CD_INVALID_USAGE("null argument");
+    std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_WALL_FIELDS, es);
+    const ArithType arith = applyMirroredFieldMoveMode(list, mode, dtype, es);
+    if (n_fields < 32 && (fields_neg >> n_fields) != 0) CD_INVALID_USAGE("sign bit of a field the list does not have");
+    KernelStats st;
+    launchFieldMoveList(list.data(), nullptr, n, fields, fields, n_fields, nullptr, es, stream, force, &st, true, arith, true, fields_neg);
+    if (n_launches) {
+      *n_launches = 0;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c) *n_launches += st.launches[c];
+    }
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtDescribeMirroredFieldMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
+                                                      int32_t n_fields, int32_t es, int32_t force, int32_t mode,
+                                                      cudecompDataType_t dtype, uint32_t fields_neg, int64_t out[5]) {
+  try {
+    if (!field_addresses || !out) CD_INVALID_USAGE("null argument");
+    std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_WALL_FIELDS, es);
+    const ArithType arith = applyMirroredFieldMoveMode(list, mode, dtype, es);
+    if (n_fields < 32 && (fields_neg >> n_fields) != 0) CD_INVALID_USAGE("sign bit of a field the list does not have");
+    std::vector<void*> fields(n_fields);
+    for (int32_t f = 0; f < n_fields; ++f) fields[f] = reinterpret_cast<void*>(field_addresses[f]);
+    const std::vector<FieldMoveLaunch> ls =
+        planFieldMoveLaunches(list.data(), nullptr, n, fields.data(), fields.data(), n_fields, nullptr, es, force, true, arith, true, fields_neg);
+    const FieldMoveLaunch none{};  // (every move is empty: nothing is launched)
+    const FieldMoveLaunch& l = ls.empty() ? none : ls[0];  // (one choice, at most two moves: never a second launch)
+    out[0] = ls.empty() ? -1 : (int64_t)l.k.kind;
+    out[1] = l.k.vec;
+    out[2] = l.k.access;
+    out[3] = l.blocks_per_field;
+    out[4] = l.blocks;
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
 cudecompResult_t cudecompExtRunFieldMoves(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
                                          void* work, int64_t work_field_stride, int32_t es, int32_t force, hipStream_t stream,
                                          int32_t* n_launches) {
@@ -1145,6 +1207,12 @@ cudecompResult_t cudecompExtDescribeFieldMoveList(const cudecompExtMove_t* moves
 cudecompResult_t cudecompExtDataLaunchCount(int64_t* launches) {
   if (!launches) return CUDECOMP_RESULT_INVALID_USAGE;
   *launches = dataLaunchCount();
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtHaloPlanCount(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, int64_t* plans) {
+  if (!handle || !grid_desc || !plans) return CUDECOMP_RESULT_INVALID_USAGE;
+  *plans = (int64_t)grid_desc->halo_plans.size();
   return CUDECOMP_RESULT_SUCCESS;
 }
 

@@ -37,7 +37,7 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
   // The key carries force_packed also where the plan never takes the direct form (accumulation) or only takes its destinations
   // from the update's plan (fill): a descriptor whose backend changes between peer and non-peer transports caches such a plan
   // twice -- harmless.  Two fields or more are always packed: one message per direction.
-  const bool force_packed = op.n_fields >= 2 || (!mirrored && usesPeerTransport(h, backend));
+  const bool force_packed = !mirrored && (op.n_fields >= 2 || usesPeerTransport(h, backend));
 
   std::array<int32_t, 3> hh{0, 0, 0}, pp{0, 0, 0};
   std::array<bool, 3> per{false, false, false};
@@ -69,13 +69,15 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
 
   ensureDevice(h);
   void* bufs[3] = {c.fields[0], c.fields[0], c.work};
-  // the arithmetic of the moves that add (accumulation, folding) or flip sign bits (reflection with parity -1)
-  const bool computes = op.kind == HaloOp::ACCUMULATE || op.kind == HaloOp::FOLD || (op.kind == HaloOp::REFLECT && op.negate);
+  // the arithmetic of the moves that add (accumulation, folding) or flip sign bits (reflection with parity -1; the reflection of
+  // several fields always names its real type: its signs are a mask of fields, one kernel whatever they are)
+  const bool computes = op.kind == HaloOp::ACCUMULATE || op.kind == HaloOp::FOLD ||
+                        (op.kind == HaloOp::REFLECT && (op.negate || op.n_fields >= 2));
   const ArithType arith = computes ? arithOf(c.dtype) : ARITH_NONE;
   const int force = (h->tuning.force_class == MOVE_GENERIC ? 1 : 0) | (h->tuning.force_streaming ? 2 : 0) | (h->tuning.no_streaming ? 4 : 0);
   // The one or two sides of a phase go into ONE launch, unless they add onto overlapping cells (`ordered`): then one launch per
   // side, low side first.  Several fields: the list kernels (one_choice); either end of a move in a pencil is field f's, the fields'
-  // pieces of the workspace lie one face apart.
+  // pieces of the workspace lie one face apart; reflection and folding go as mirrored lists with the call's mask of signs.
   auto launch = [&](const std::vector<Move3D>& moves) {
     if (moves.empty()) return;
     const int n = (int)moves.size(), each = plan.ordered && moves[0].add ? 1 : n;
@@ -86,7 +88,7 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
       const std::vector<i64> steps(n, plan.face_elements);
       for (int i = 0; i < n; i += each)
         launchFieldMoveList(moves.data() + i, steps.data() + i, each, c.fields, c.fields, op.n_fields, c.work, es, c.stream, force, nullptr,
-                            true, arith);
+                            true, arith, mirrored, c.fields_neg);
     }
   };
 

@@ -18,6 +18,7 @@
 #include "cudecomp_halo_fold.h"
 #include "cudecomp_halo_fields.h"
 #include "cudecomp_halo_accumulate_fields.h"
+#include "cudecomp_halo_wall_fields.h"
 #include "cudecomp_transpose_fields.h"
 #include "decomp.h"
 #include "errors.h"
@@ -262,7 +263,9 @@ void runTranspose(cudecompHandle_t handle, cudecompGridDesc_t gd, TransposeOp op
                   cudecompDataType_t dtype, const int32_t* in_halo, const int32_t* out_halo, const int32_t* in_pad,
                   const int32_t* out_pad, hipStream_t stream);
 // halo.cc: everything a halo call passes.  `op.centering` and `op.n_fields` are the caller's numbers as they came; `parity` and
-// `clear` are the raw arguments behind op.negate and op.clear (REFLECT, FOLD: checked late, by the runner)
+// `clear` are the raw arguments behind op.negate and op.clear (REFLECT, FOLD: checked late, by the runner).  REFLECT and FOLD of
+// several fields: op.negate is false, `parity` is the first of the caller's parities that is neither +1 nor -1 (+1 when all are
+// fine) and `fields_neg` has bit f set where field f's parity is -1 -- the signs reach the launcher with the call, not with the plan
 struct HaloCall {
   HaloOp op;
   int axis = 0, dim = 0;
@@ -271,6 +274,7 @@ struct HaloCall {
   cudecompDataType_t dtype = CUDECOMP_FLOAT;
   const void* value = nullptr;  // FILL
   int parity = 1, clear = 0;
+  uint32_t fields_neg = 0;
   const int32_t* halo = nullptr;
   const bool* periods = nullptr;
   const int32_t* pad = nullptr;

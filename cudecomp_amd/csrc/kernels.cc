@@ -9,8 +9,9 @@
 // kernels_rows.hip, kernels_transpose.hip (one code object per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip and kernels_fold.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
 // transpose.cc; kernels_field_transpose.hip (lists of field-moves: the moves of a halo or transpose phase for several pencils in
-// one launch) and kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) have an entry of their
-// own at the end of this file, launchFieldMoveList.  kernels_batch.h says why they are separate
+// one launch), kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) and
+// kernels_field_mirror.hip (the same lists mirrored, with a sign per field: multi-field wall halos) have an entry of their own at
+// the end of this file, launchFieldMoveList.  kernels_batch.h says why they are separate
 // code objects.
 //
 // 2-byte elements (fp16, bf16) take the row copy (plain kernel), the LDS-tiled transposition (128 x 128 tiles with 16-byte
@@ -377,12 +378,45 @@ void classifyFill(Classified& c, const Move3D& m, const KernelTuning& tuning, bo
   genericGeometry(c, m);
 }
 
+// The geometry of a reflect- or fold-move as the kernels take it.  Such a move never passes normalizeMove as a whole: the mirrored
+// dim (the one with the negative source stride) is set aside, the other two are normalised (and fused) as those of a copy, and the
+// mirrored dim comes back as the row or plane index, slower than the row.  mirrored_fastest: it is the fastest memory axis of
+// either side -- rows reversed in themselves, which only the element-wise kernels serve.
+Move3D mirrorGeometry(const Move3D& in, bool& mirrored_fastest) {
+  int mirrored = -1;
+  for (int i = 0; i < 3; ++i) {
+    if (in.ds[i] < 0) CD_INTERNAL_ERROR("negative destination stride");
+    if (in.ss[i] >= 0) continue;
+    if (mirrored >= 0) CD_INTERNAL_ERROR("reflect-move with more than one mirrored dim");
+    mirrored = i;
+  }
+  Move3D m = in;
+  const bool live = mirrored >= 0 && in.extent[mirrored] > 1;  // (a mirrored dim one cell thick has no direction)
+  if (mirrored >= 0) {
+    m.extent[mirrored] = 1;
+    m.ss[mirrored] = m.ds[mirrored] = 0;
+  }
+  normalizeMove(m);  // at most two dims remain, in slots 0 and 1
+  if (live) {  // back in, slower than the row: slot 1 or 2, ordered by the size of the source stride
+    const int at = (m.extent[1] > 1 && m.ss[1] < -in.ss[mirrored]) ? 2 : 1;
+    if (at == 1) {
+      m.extent[2] = m.extent[1];
+      m.ss[2] = m.ss[1];
+      m.ds[2] = m.ds[1];
+    }
+    m.extent[at] = in.extent[mirrored];
+    m.ss[at] = in.ss[mirrored];
+    m.ds[at] = in.ds[mirrored];
+  }
+  mirrored_fastest = live && (in.ss[mirrored] == -1 || in.ds[mirrored] <= 1);
+  return m;
+}
+
 // Reflect-moves (Move3D::reflect; `arith` the real type when the sign bits are flipped): the row geometry of the copy when the
 // fastest dim is contiguous on both sides and is not the mirrored one -- the mirror then is the sign of the source's row or plane
-// stride -- or the element-wise one; nothing else (only the cells of the move are touched).  They never pass normalizeMove as a
-// whole: the mirrored dim is set aside, the other two are normalised (and fused) as those of a copy, and the mirrored dim comes
-// back as the row or plane index.  Access mode: the project's rule, cached below kStreamBytes, non-temporal loads and stores from
-// there (unmeasured for this kernel); the element-wise kernel always caches.
+// stride -- or the element-wise one; nothing else (only the cells of the move are touched); mirrorGeometry above.  Access mode:
+// the project's rule, cached below kStreamBytes, non-temporal loads and stores from there (unmeasured for this kernel, DESIGN.md
+// section 4); the element-wise kernel always caches.
 // Fold-moves (Move3D::reflect with Move3D::add, `arith` their real type; Move3D::take as well when they clear their source) come
 // the same way and are offered the same two geometries and nothing else.  Access mode: the accumulation's rule, cached below
 // kStreamBytes, from there non-temporal source loads and zero stores, the destination always cached (unmeasured for these
@@ -399,20 +433,8 @@ Classified classifyReflect(const Move3D& in, void* const bufs[3], int es, const 
     if (in.negate && (arith == ARITH_NONE || es % arithBytes(arith) != 0 || es / arithBytes(arith) > 2))
       CD_INTERNAL_ERROR("reflect-move that flips sign bits without a real type that fits the element size");
   }
-  int mirrored = -1;
-  for (int i = 0; i < 3; ++i) {
-    if (in.ds[i] < 0) CD_INTERNAL_ERROR("negative destination stride");
-    if (in.ss[i] >= 0) continue;
-    if (mirrored >= 0) CD_INTERNAL_ERROR("reflect-move with more than one mirrored dim");
-    mirrored = i;
-  }
-  Move3D m = in;
-  const bool live = mirrored >= 0 && in.extent[mirrored] > 1;  // (a mirrored dim one cell thick has no direction)
-  if (mirrored >= 0) {
-    m.extent[mirrored] = 1;
-    m.ss[mirrored] = m.ds[mirrored] = 0;
-  }
-  normalizeMove(m);  // at most two dims remain, in slots 0 and 1
+  bool mirrored_fastest;
+  const Move3D m = mirrorGeometry(in, mirrored_fastest);
   Classified c{};
   c.k.es = es;
   c.k.arith = (fold || in.negate) ? arith : ARITH_NONE;
@@ -421,18 +443,6 @@ Classified classifyReflect(const Move3D& in, void* const bufs[3], int es, const 
   const bool streaming = (c.elements * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming;
   c.dm.src = static_cast<const char*>(bufs[in.src_buf]) + in.src_off * es;
   c.dm.dst = static_cast<char*>(bufs[in.dst_buf]) + in.dst_off * es;
-  if (live) {  // back in, slower than the row: slot 1 or 2, ordered by the size of the source stride
-    const int at = (m.extent[1] > 1 && m.ss[1] < -in.ss[mirrored]) ? 2 : 1;
-    if (at == 1) {
-      m.extent[2] = m.extent[1];
-      m.ss[2] = m.ss[1];
-      m.ds[2] = m.ds[1];
-    }
-    m.extent[at] = in.extent[mirrored];
-    m.ss[at] = in.ss[mirrored];
-    m.ds[at] = in.ds[mirrored];
-  }
-  const bool mirrored_fastest = live && (in.ss[mirrored] == -1 || in.ds[mirrored] <= 1);
   if (tuning.force_class != MOVE_GENERIC && m.ss[0] <= 1 && m.ds[0] <= 1 && !mirrored_fastest) {
     c.k.kind = fold ? (in.take ? K_ROWS_FOLD_TAKE : K_ROWS_FOLD) : K_ROWS_REFLECT;
     c.k.access = streaming ? 1 : 0;
@@ -581,6 +591,18 @@ void spellKernelName(const KernelChoice& k) {
       break;
     case K_ROWS_FIELDS_TAKE: snprintf(out, n, "rows_fields_take_kernel<%d,%d>", k.vec, s); break;
     case K_GENERIC_FIELDS_TAKE: snprintf(out, n, "generic_fields_take_kernel<%d>", k.es); break;
+    case K_ROWS_FIELDS_REFLECT: snprintf(out, n, "rows_fields_reflect_kernel<%d,%d>", k.vec, s); break;
+    case K_GENERIC_FIELDS_REFLECT: snprintf(out, n, "generic_fields_reflect_kernel<%d>", k.es); break;
+    case K_ROWS_FIELDS_FOLD:
+    case K_ROWS_FIELDS_FOLD_TAKE:
+      snprintf(out, n, "rows_fields_fold_kernel<%s,%d,%d,%s>", arithName(k.arith), k.vec, s,
+               k.kind == K_ROWS_FIELDS_FOLD_TAKE ? "true" : "false");
+      break;
+    case K_GENERIC_FIELDS_FOLD:
+    case K_GENERIC_FIELDS_FOLD_TAKE:
+      snprintf(out, n, "generic_fields_fold_kernel<%s,%d,%s>", arithName(k.arith), k.es / arithBytes(k.arith),
+               k.kind == K_GENERIC_FIELDS_FOLD_TAKE ? "true" : "false");
+      break;
   }
 }
 
@@ -640,7 +662,13 @@ void launchBatch(const KernelChoice& k, const Batch& b, const void* fill_value, 
     case K_ROWS_FIELDS_TAKE:
     case K_GENERIC_FIELDS_TAKE:
     case K_ROWS_FIELDS_ADD_TAKE:
-    case K_GENERIC_FIELDS_ADD_TAKE: CD_INTERNAL_ERROR("lists of field-moves are launched by launchFieldMoveList");
+    case K_GENERIC_FIELDS_ADD_TAKE:
+    case K_ROWS_FIELDS_REFLECT:
+    case K_GENERIC_FIELDS_REFLECT:
+    case K_ROWS_FIELDS_FOLD:
+    case K_GENERIC_FIELDS_FOLD:
+    case K_ROWS_FIELDS_FOLD_TAKE:
+    case K_GENERIC_FIELDS_FOLD_TAKE: CD_INTERNAL_ERROR("lists of field-moves are launched by launchFieldMoveList");
   }
 }
 
@@ -768,7 +796,7 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
 // ---------------------------------------------------------------------------------------------
 std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i64* work_steps, int n, void* const* inputs,
                                                    void* const* outputs, int n_fields, void* work, int es, int force,
-                                                   bool one_choice, ArithType arith) {
+                                                   bool one_choice, ArithType arith, bool mirrored, unsigned int fields_neg) {
   if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
   if (n < 0 || (n > 0 && !moves)) CD_INTERNAL_ERROR("field-move list without moves");
   if (n_fields < 1 || n_fields > kMaxFields || !inputs) CD_INTERNAL_ERROR("field count out of range");
@@ -782,10 +810,13 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     if (i == 0) add = moves[i].add, take = moves[i].take;
     else if (moves[i].add != add || moves[i].take != take) CD_INTERNAL_ERROR("the field-moves of one list carry different operations");
   }
-  if (add) {
-    if (arith == ARITH_NONE) CD_INTERNAL_ERROR("adding field-move without an arithmetic type");
+  if (add || mirrored) {  // (a mirrored list always: the sign mask is that of its real type)
+    if (arith == ARITH_NONE) CD_INTERNAL_ERROR(mirrored ? "mirrored field-move without a real type" : "adding field-move without an arithmetic type");
     if (es % arithBytes(arith) != 0 || es / arithBytes(arith) > 2) CD_INTERNAL_ERROR("element size does not fit the arithmetic type");
   }
+  if (!mirrored && fields_neg != 0) CD_INTERNAL_ERROR("only mirrored field-moves carry signs");
+  if (mirrored && n_fields < kMaxFields && (fields_neg >> n_fields) != 0) CD_INTERNAL_ERROR("sign bit of a field the list does not have");
+  if (mirrored && take && !add) CD_INTERNAL_ERROR("a mirrored field-move that clears its source must add (fold)");
 
   // each move's shared geometry, normalised, its ends, and the addresses every field's first element can have or-ed together (the
   // 2-byte rule: all fields' pencils and all workspace pieces)
@@ -793,21 +824,30 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
   std::vector<Classified> cs;
   std::vector<FieldMove> fms;
   std::vector<int> index;
+  std::vector<bool> rows_fit;  // the move's fastest dim is contiguous on both sides (and not the mirrored one)
   for (int i = 0; i < n; ++i) {
     const Move3D& in = moves[i];
-    if (in.fill || in.reflect || in.negate || in.dst_row_pitch != 0)
+    if (mirrored) {
+      // the moves of kernels_field_mirror.hip: reflect- or fold-moves between cells of the fields' own buffers; their signs travel
+      // in fields_neg, never in the move
+      if (!in.reflect || in.negate || in.fill || in.dst_row_pitch != 0 || in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK)
+        CD_INTERNAL_ERROR("mirrored field-moves reflect or fold exactly their cells of the fields' buffers, unsigned");
+    } else if (in.fill || in.reflect || in.negate || in.dst_row_pitch != 0) {
       CD_INTERNAL_ERROR("field-moves copy, add or take exactly their cells");
+    }
     if (add && in.dst_buf == BUF_WORK) CD_INTERNAL_ERROR("adding field-moves never add onto the workspace");
     if (take && in.src_buf == BUF_WORK) CD_INTERNAL_ERROR("taking field-moves never clear the workspace");
     if ((in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK) && !work) CD_INTERNAL_ERROR("field-move through a workspace that was not given");
     if ((in.src_buf == BUF_OUT || in.dst_buf == BUF_OUT) && !outputs) CD_INTERNAL_ERROR("field-move onto an output list that was not given");
     for (int d = 0; d < 3; ++d)
-      if (in.ss[d] < 0 || in.ds[d] < 0 || in.extent[d] < 0) CD_INTERNAL_ERROR("negative stride or extent in a field-move");
+      if ((in.ss[d] < 0 && !mirrored) || in.ds[d] < 0 || in.extent[d] < 0) CD_INTERNAL_ERROR("negative stride or extent in a field-move");
     if (in.elements() == 0) continue;
     const i64 step = work_steps ? work_steps[i] : 0;
     if (step < 0) CD_INTERNAL_ERROR("negative workspace step in a field-move");
     Move3D m = in;
-    normalizeMove(m);
+    bool mirrored_fastest = false;
+    if (mirrored) m = mirrorGeometry(in, mirrored_fastest);  // (the mirrored dim back in as the row or plane index)
+    else normalizeMove(m);
     FieldMove fm{};
     fm.src_end = in.src_buf == BUF_WORK ? kEndWork : (in.src_buf == BUF_OUT ? kEndOutput : kEndInput);
     fm.dst_end = in.dst_buf == BUF_WORK ? kEndWork : (in.dst_buf == BUF_OUT ? kEndOutput : kEndInput);
@@ -824,7 +864,7 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     }
     Classified c{};
     c.k.es = es;
-    c.k.arith = add ? arith : ARITH_NONE;
+    c.k.arith = (add || mirrored) ? arith : ARITH_NONE;
     c.elements = m.elements();
     c.dm.src = reinterpret_cast<const char*>(address_bits);  // (only its alignment is read)
     c.dm.dst = reinterpret_cast<char*>(address_bits);
@@ -832,6 +872,7 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     cs.push_back(c);
     fms.push_back(fm);
     index.push_back(i);
+    rows_fit.push_back(m.ss[0] <= 1 && m.ds[0] <= 1 && !mirrored_fastest);
   }
   // one_choice: rows only if every move has contiguous rows, then the narrowest of their lane widths; the largest move decides
   // the access mode
@@ -839,7 +880,7 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
   int lanes = 16;
   i64 largest = 0;
   for (size_t i = 0; one_choice && i < cs.size(); ++i) {
-    all_rows = all_rows && norm[i].ss[0] <= 1 && norm[i].ds[0] <= 1;
+    all_rows = all_rows && rows_fit[i];
     largest = std::max(largest, cs[i].elements);
     if (!all_rows) continue;
     Classified c = cs[i];
@@ -856,12 +897,13 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     // of an addition always cached, the plain take streaming all of it; unmeasured for these kernels too.
     const bool streaming = ((one_choice ? largest : c.elements) * es >= kStreamBytes || (force & 2)) && !(force & 4);
     int t = -1;
-    if (!force_generic && !one_choice && !add && !take && m.ss[0] == 1) {  // (additions and takes never transpose)
+    if (!force_generic && !one_choice && !add && !take && !mirrored && m.ss[0] == 1) {  // (additions, takes and mirrors never transpose)
       if (m.ds[1] == 1) t = 1;
       if (m.ds[2] == 1) t = 2;
     }
-    if (one_choice ? all_rows : (!force_generic && m.ss[0] <= 1 && m.ds[0] <= 1)) {
-      c.k.kind = take ? (add ? K_ROWS_FIELDS_ADD_TAKE : K_ROWS_FIELDS_TAKE) : (add ? K_ROWS_FIELDS_ADD : K_ROWS_FIELDS);
+    if (one_choice ? all_rows : (!force_generic && rows_fit[i])) {
+      if (mirrored) c.k.kind = add ? (take ? K_ROWS_FIELDS_FOLD_TAKE : K_ROWS_FIELDS_FOLD) : K_ROWS_FIELDS_REFLECT;
+      else c.k.kind = take ? (add ? K_ROWS_FIELDS_ADD_TAKE : K_ROWS_FIELDS_TAKE) : (add ? K_ROWS_FIELDS_ADD : K_ROWS_FIELDS);
       c.k.access = streaming ? 1 : 0;
       rowVectors(c, m, lanes);
       if (c.k.vec < es) CD_INTERNAL_ERROR("field-move narrower than one element");
@@ -881,9 +923,10 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
       c.t1 = (unsigned int)((c.dm.e[1] + c.k.tj - 1) / c.k.tj);
       c.blocks = (unsigned long long)c.t0 * c.t1 * (unsigned long long)c.dm.e[2];
     } else {
-      c.k.kind = take ? (add ? K_GENERIC_FIELDS_ADD_TAKE : K_GENERIC_FIELDS_TAKE) : (add ? K_GENERIC_FIELDS_ADD : K_GENERIC_FIELDS);
+      if (mirrored) c.k.kind = add ? (take ? K_GENERIC_FIELDS_FOLD_TAKE : K_GENERIC_FIELDS_FOLD) : K_GENERIC_FIELDS_REFLECT;
+      else c.k.kind = take ? (add ? K_GENERIC_FIELDS_ADD_TAKE : K_GENERIC_FIELDS_TAKE) : (add ? K_GENERIC_FIELDS_ADD : K_GENERIC_FIELDS);
       c.k.access = 0;
-      genericGeometry(c, m);
+      genericGeometry(c, m, mirrored);  // (mirrored, without a destination-fast dim: along the longest, as the single calls)
     }
     if (c.blocks == 0 || c.blocks * (unsigned long long)n_fields > 0x7fffffffULL)
       CD_NOT_SUPPORTED("single block move too large for one launch");
@@ -906,6 +949,7 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     FieldMoveBatch& b = l.b;
     l.k = cs[i].k;
     l.cls = classOf(cs[i].k.kind);
+    l.fields_neg = fields_neg;
     b.n_fields = n_fields;
     b.work = w;
     for (int f = 0; f < n_fields; ++f) {
@@ -937,12 +981,14 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
 }
 
 void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void* const* inputs, void* const* outputs, int n_fields,
-                         void* work, int es, hipStream_t stream, int force, KernelStats* stats, bool one_choice, ArithType arith) {
+                         void* work, int es, hipStream_t stream, int force, KernelStats* stats, bool one_choice, ArithType arith,
+                         bool mirrored, unsigned int fields_neg) {
   for (const FieldMoveLaunch& l :
-       planFieldMoveLaunches(moves, work_steps, n, inputs, outputs, n_fields, work, es, force, one_choice, arith)) {
+       planFieldMoveLaunches(moves, work_steps, n, inputs, outputs, n_fields, work, es, force, one_choice, arith, mirrored, fields_neg)) {
     spellKernelName(l.k);
     ++g_data_launches;
-    if (l.k.kind >= K_ROWS_FIELDS_ADD) launchFieldAccumulateBatch(l.k, l.b, l.blocks, stream);
+    if (l.k.kind >= K_ROWS_FIELDS_REFLECT) launchFieldMirrorBatch(l.k, l.b, l.fields_neg, l.blocks, stream);
+    else if (l.k.kind >= K_ROWS_FIELDS_ADD) launchFieldAccumulateBatch(l.k, l.b, l.blocks, stream);
     else launchFieldMoveBatch(l.k, l.b, l.blocks, stream);
     if (stats) {
       stats->launches[l.cls] += 1;

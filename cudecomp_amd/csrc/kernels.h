@@ -71,7 +71,7 @@ std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3]
 void describeMove(const Move3D& m, const void* src, void* dst, int es, const KernelTuning* tuning, long long out[10]);
 
 // ---- lists of field-moves: a list of moves, each for several (input, output) pairs of buffers (kernels_field_transpose.hip,
-// kernels_field_accumulate.hip) ----
+// kernels_field_accumulate.hip, kernels_field_mirror.hip) ----
 // The moves of one phase of a multi-field transpose (include/cudecomp_transpose_fields.h) or of a multi-field halo update
 // (include/cudecomp_halo_fields.h): moves[0 .. n - 1] share their geometry among `n_fields` (1 .. kern::kMaxFields) fields.  An end
 // of a move in BUF_IN lies in inputs[f] + offset, an end in BUF_OUT in outputs[f] + offset, an end in BUF_WORK at
@@ -99,11 +99,23 @@ void describeMove(const Move3D& m, const void* src, void* dst, int es, const Ker
 // type (or one the element size does not fit), an add whose destination is the workspace, a take whose source is the workspace, a
 // workspace end without a workspace and an output end without `outputs` are internal errors before anything is launched; a move
 // of more than 2^31 - 1 workgroups is NOT_SUPPORTED.
+// MIRRORED lists (`mirrored`; kernels_field_mirror.hip: the one or two sides of a multi-field reflection or fold,
+// include/cudecomp_halo_wall_fields.h): every move is a reflect-move (Move3D::reflect: one dim with a negative source stride,
+// src_off at the source cell of its index 0) or a fold-move (with Move3D::add, and Move3D::take when it clears its source), both
+// ends in the fields' own buffers.  `arith`, the real type of the elements, is always needed; bit f of `fields_neg` says that the
+// sign bits of field f's source are flipped on the way (parity -1) -- Move3D::negate is NOT used: the signs are no part of the
+// kernel choice, so one plan and one kernel serve every combination of parities.  Each move is classified as the single calls
+// classify it (rows when the fastest dim is contiguous on both sides and not the mirrored one, element by element otherwise --
+// lanes along the longest dim when there is no destination-fast one -- never transposed); one_choice as above.  Access: the
+// reflection's / the fold's rule by the size of one field's move (unmeasured for these kernels); the element-wise kernels always
+// cache.  Without `mirrored` a reflect-move, a sign or a negative stride stays the internal error it was; with it a move that is
+// no reflect-move, carries negate, fill or dst_row_pitch, touches the workspace or takes without adding is one.
 struct FieldMoveLaunch {
   KernelChoice k;
   kern::FieldMoveBatch b;
   unsigned int blocks;            // of all its moves and fields
   unsigned int blocks_per_field;  // of all its moves
+  unsigned int fields_neg;        // mirrored lists: the fields whose sign bits are flipped (0 otherwise)
   MoveClass cls;
   i64 elements;                   // of all its moves and fields
   int index[kern::kMaxBatch];     // index[i]: the list entry b.m[i] is
@@ -111,10 +123,11 @@ struct FieldMoveLaunch {
 // WHICH launches launchFieldMoveList makes, in order (pure host code, no device needed; buffers are only looked at as addresses)
 std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i64* work_steps, int n, void* const* inputs,
                                                    void* const* outputs, int n_fields, void* work, int es, int force = 0,
-                                                   bool one_choice = false, ArithType arith = ARITH_NONE);
+                                                   bool one_choice = false, ArithType arith = ARITH_NONE, bool mirrored = false,
+                                                   unsigned int fields_neg = 0);
 void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void* const* inputs, void* const* outputs, int n_fields,
                          void* work, int es, hipStream_t stream, int force = 0, KernelStats* stats = nullptr, bool one_choice = false,
-                         ArithType arith = ARITH_NONE);
+                         ArithType arith = ARITH_NONE, bool mirrored = false, unsigned int fields_neg = 0);
 
 // data-movement launches this process has made so far (launchMoves and launchFieldMoveList; tests count launches per call with it)
 long long dataLaunchCount();

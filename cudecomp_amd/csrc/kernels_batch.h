@@ -2,9 +2,10 @@
 // kernel choice (KernelChoice), the launch descriptor (Batch) and the launchers.  The code objects the classifier dispatches
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip;
-// kernels_rotate.hip and sync.hip are launched by the executor; kernels_field_transpose.hip (lists of field-moves: multi-field
-// halo phases and transposes) and kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) are
-// reached through launchFieldMoveList (kernels.h).  Seventeen code objects in all.  The row and element-wise kernels of all of
+// kernels_rotate.hip and sync.hip are launched by the executor (and compiled as one unit, kernels_executor.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
+// halo phases and transposes), kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) and
+// kernels_field_mirror.hip (the same lists mirrored, with a sign per field: multi-field wall halos) are reached through
+// launchFieldMoveList (kernels.h).  Seventeen code objects in all.  The row and element-wise kernels of all of
 // them share one workgroup decode (kernels_walk.h) and their launchers one dispatch (kernels_dispatch.h).
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
@@ -138,7 +139,13 @@ enum KernelKind {
   K_ROWS_FIELDS_TAKE,         // rows_fields_take_kernel (dst = src; src = 0) = 27
   K_GENERIC_FIELDS_TAKE,      // generic_fields_take_kernel = 28
   K_ROWS_FIELDS_ADD_TAKE,     // rows_fields_accumulate_kernel with TAKE (dst += src; src = 0) = 29
-  K_GENERIC_FIELDS_ADD_TAKE   // generic_fields_accumulate_kernel with TAKE = 30
+  K_GENERIC_FIELDS_ADD_TAKE,  // generic_fields_accumulate_kernel with TAKE = 30
+  K_ROWS_FIELDS_REFLECT,      // rows_fields_reflect_kernel (dst = +-src per field, the source backwards along the row or plane index) = 31
+  K_GENERIC_FIELDS_REFLECT,   // generic_fields_reflect_kernel = 32
+  K_ROWS_FIELDS_FOLD,         // rows_fields_fold_kernel (dst += +-src per field, the source backwards) = 33
+  K_GENERIC_FIELDS_FOLD,      // generic_fields_fold_kernel = 34
+  K_ROWS_FIELDS_FOLD_TAKE,    // rows_fields_fold_kernel with TAKE (... ; src = 0) = 35
+  K_GENERIC_FIELDS_FOLD_TAKE  // generic_fields_fold_kernel with TAKE = 36
 };
 struct KernelChoice {
   KernelKind kind;
@@ -150,8 +157,9 @@ struct KernelChoice {
                     // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it);
                     // reflections: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores;
                     // field-moves: 0, 1 non-temporal loads and stores; transpose_fields_kernel: 0, 2; adding / taking
-                    // field-moves: as additions / takes
-  ArithType arith;  // additions, folds, reflections that flip the sign bits: the real type the elements consist of; ARITH_NONE otherwise
+                    // field-moves: as additions / takes; mirrored field-moves: as reflections / folds
+  ArithType arith;  // additions, folds, reflections that flip the sign bits, mirrored field-moves (whatever their signs): the real
+                    // type the elements consist of; ARITH_NONE otherwise
   bool neg;         // folds: the sign bits of the source are flipped before the addition (one sign mask per launch)
   bool guard;       // transpose_fields_kernel: some tile of the move ends inside the move (the GUARD template argument); false otherwise
   bool operator==(const KernelChoice& o) const {
@@ -220,12 +228,18 @@ constexpr KindTraits kKindTraits[] = {
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_TAKE
     {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FIELDS_ADD_TAKE
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_ADD_TAKE
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FIELDS_REFLECT
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_REFLECT
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FIELDS_FOLD
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_FOLD
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FIELDS_FOLD_TAKE
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_FOLD_TAKE
 };
-static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_FIELDS_ADD_TAKE + 1, "one row per KernelKind");
+static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_FIELDS_FOLD_TAKE + 1, "one row per KernelKind");
 
 // the row of a kind; a value outside the enum is an internal error, never a read past the table
 inline const KindTraits& kindTraits(KernelKind kind) {
-  if (kind < K_ROWS || kind > K_GENERIC_FIELDS_ADD_TAKE) CD_INTERNAL_ERROR("kernel kind out of range");
+  if (kind < K_ROWS || kind > K_GENERIC_FIELDS_FOLD_TAKE) CD_INTERNAL_ERROR("kernel kind out of range");
   return kKindTraits[kind];
 }
 inline MoveClass classOf(KernelKind kind) { return kindTraits(kind).cls; }
@@ -294,6 +308,11 @@ void launchFoldBatch(const KernelChoice& k, const kern::Batch& b, unsigned int b
 void launchFieldMoveBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, unsigned int blocks, hipStream_t stream);
 // kernels_field_accumulate.hip: lists of field-moves that add (k.arith: the real type), take or both; local buffers only
 void launchFieldAccumulateBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, unsigned int blocks, hipStream_t stream);
+// kernels_field_mirror.hip: lists of mirrored field-moves (reflect- or fold-moves: SIGNED source strides, rows in bytes, generic in
+// elements).  k.arith: the real type of the elements, always; bit f of fields_neg: the sign bits of field f's source are flipped on
+// the way (the mask of that type and fields_neg travel as kernel arguments of their own).  Local buffers only.
+void launchFieldMirrorBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, unsigned int fields_neg, unsigned int blocks,
+                            hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

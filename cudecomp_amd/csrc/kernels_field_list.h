@@ -1,5 +1,6 @@
 // kernels_field_list.h -- the workgroup decode of the lists of field-moves (kern::FieldMoveBatch, kernels_batch.h), shared by the
-// code objects that serve them: kernels_field_transpose.hip (copies) and kernels_field_accumulate.hip (additions and takes).
+// code objects that serve them: kernels_field_transpose.hip (copies), kernels_field_accumulate.hip (additions and takes) and
+// kernels_field_mirror.hip (reflections and folds with a sign per field).
 #pragma once
 #include "kernels_dev.h"
 

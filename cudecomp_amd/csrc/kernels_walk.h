@@ -2,7 +2,8 @@
 // kernels, the unrolled loop over a lane's rows, the grid-stride element walk, and the two small payload helpers (zero bytes, sign
 // bits) the taking, reflecting and folding families share.  Device code, included by the kernel code objects only; one
 // definition each, so a change to the decode reaches every family (kernels_rows.hip, kernels_accumulate.hip, kernels_take.hip,
-// kernels_reflect.hip, kernels_fold.hip, kernels_fill.hip, kernels_field_transpose.hip, kernels_field_accumulate.hip).
+// kernels_reflect.hip, kernels_fold.hip, kernels_fill.hip, kernels_field_transpose.hip, kernels_field_accumulate.hip,
+// kernels_field_mirror.hip).
 //
 // What is NOT here, on purpose: the payload arrays and the two phases of a row kernel (all loads, then all stores).  They stay in
 // each kernel's body, as do its pointer qualifiers.  Moved into a shared function together with the loops, the compiler treats a

@@ -647,8 +647,24 @@ HaloPlan buildHaloAccumulateFieldsPlan(const GridShape& g, int rank, int axis, i
   return p;
 }
 
+HaloPlan buildHaloWallFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                 const int32_t* pad, bool fold, int centering, bool clear, int n_fields, bool self_exchange) {
+  if (n_fields < 2) CD_INTERNAL_ERROR("a multi-field wall plan for fewer than two fields");
+  HaloPlan p = fold ? buildHaloFoldPlan(g, rank, axis, dim, halo, periods, pad, centering, false, clear, self_exchange)
+                    : buildHaloReflectPlan(g, rank, axis, dim, halo, periods, pad, centering, false, self_exchange);
+  p.op.n_fields = n_fields;
+  for (const Move3D& m : p.pre)
+    if (!m.reflect || m.negate || m.src_buf != BUF_IN || m.dst_buf != BUF_IN) CD_INTERNAL_ERROR("a wall plan whose moves are not unsigned mirrors of the pencil");
+  return p;
+}
+
 HaloPlan buildHaloOpPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods, const int32_t* pad,
                          const HaloOp& op, bool force_packed, bool self_exchange) {
+  if ((op.kind == HaloOp::REFLECT || op.kind == HaloOp::FOLD) && op.n_fields != 1) {
+    if (op.negate) CD_INTERNAL_ERROR("the parities of a multi-field wall call are no part of its plan");
+    return buildHaloWallFieldsPlan(g, rank, axis, dim, halo, periods, pad, op.kind == HaloOp::FOLD, op.centering, op.clear, op.n_fields,
+                                   self_exchange);
+  }
   switch (op.kind) {
     case HaloOp::UPDATE: return buildHaloFieldsPlan(g, rank, axis, dim, halo, periods, pad, op.n_fields, force_packed, self_exchange);
     case HaloOp::ACCUMULATE: return buildHaloAccumulateFieldsPlan(g, rank, axis, dim, halo, periods, pad, op.n_fields, op.clear, self_exchange);

@@ -193,8 +193,8 @@ struct HaloOp {
   enum Kind { UPDATE, ACCUMULATE, FILL, REFLECT, FOLD } kind = UPDATE;
   bool clear = false;  // ACCUMULATE, FOLD: the ghost cells read are cleared
   int centering = 0;   // REFLECT, FOLD
-  bool negate = false; // REFLECT, FOLD: parity -1
-  int n_fields = 1;    // UPDATE, ACCUMULATE (1 otherwise)
+  bool negate = false; // REFLECT, FOLD of ONE field: parity -1 (several fields: false; their parities travel with the call)
+  int n_fields = 1;    // UPDATE, ACCUMULATE, REFLECT, FOLD (1 for FILL)
   bool operator<(const HaloOp& o) const {
     return std::tie(kind, clear, centering, negate, n_fields) < std::tie(o.kind, o.clear, o.centering, o.negate, o.n_fields);
   }
@@ -295,8 +295,19 @@ HaloPlan buildHaloFieldsPlan(const GridShape& g, int rank, int axis, int dim, co
 HaloPlan buildHaloAccumulateFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
                                        const int32_t* pad, int n_fields, bool clear, bool self_exchange = false);
 
+// Multi-field wall halos along `dim` (include/cudecomp_halo_wall_fields.h has the contract): the REFLECTION (`fold` false) or the
+// FOLD of `n_fields` pencils of one descriptor, axis, halos, padding and centering, each with a parity of its own.  Derived from
+// buildHaloReflectPlan / buildHaloFoldPlan: refusals, sides, "which cells" and `ordered` are the single call's by construction.
+// Kinds: NONE or SELF_PERIODIC ("local").  The moves in `pre` are those of FIELD 0 -- an end in BUF_IN is "field f's pencil" at the
+// same offset -- and carry NO sign (Move3D::negate false, HaloOp::negate false): the parities are no part of the plan, they reach
+// the launcher with the call as a mask of the fields with parity -1 (HaloCall::fields_neg), so that one plan serves every
+// combination of them.  n_fields == 1: not this builder -- the single plans, which carry their sign.
+HaloPlan buildHaloWallFieldsPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                 const int32_t* pad, bool fold, int centering, bool clear, int n_fields, bool self_exchange = false);
+
 // The plan of the halo call `op`, by the builder of its family: UPDATE buildHaloFieldsPlan, ACCUMULATE buildHaloAccumulateFieldsPlan
-// (one field: the single plans, unchanged), FILL, REFLECT and FOLD their own.  `force_packed` reaches the builders that take it.
+// (one field: the single plans, unchanged), REFLECT and FOLD their own for one field and buildHaloWallFieldsPlan for several, FILL
+// its own.  `force_packed` reaches the builders that take it.
 HaloPlan buildHaloOpPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods, const int32_t* pad,
                          const HaloOp& op, bool force_packed, bool self_exchange = false);
 

@@ -742,6 +742,115 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompAmdAccumulateFieldHalosZ_C
 
+    ! cudecomp_halo_wall_fields.h: reflection and fold of several pencils, each with a parity of its own
+    function cudecompAmdReflectFieldHalosX_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, halo_extents, halo_periods, &
+                                            dim, padding, stream) bind(C, name="cudecompAmdReflectFieldHalosX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*)
+      integer(c_int32_t), value :: n_fields
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: parities(*)
+      integer(c_int32_t), value :: centering
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdReflectFieldHalosX_C
+
+    function cudecompAmdReflectFieldHalosY_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, halo_extents, halo_periods, &
+                                            dim, padding, stream) bind(C, name="cudecompAmdReflectFieldHalosY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*)
+      integer(c_int32_t), value :: n_fields
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: parities(*)
+      integer(c_int32_t), value :: centering
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdReflectFieldHalosY_C
+
+    function cudecompAmdReflectFieldHalosZ_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, halo_extents, halo_periods, &
+                                            dim, padding, stream) bind(C, name="cudecompAmdReflectFieldHalosZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*)
+      integer(c_int32_t), value :: n_fields
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: parities(*)
+      integer(c_int32_t), value :: centering
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdReflectFieldHalosZ_C
+
+    function cudecompAmdFoldFieldHalosX_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, clear, halo_extents, halo_periods, &
+                                            dim, padding, stream) bind(C, name="cudecompAmdFoldFieldHalosX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*)
+      integer(c_int32_t), value :: n_fields
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: parities(*)
+      integer(c_int32_t), value :: centering, clear
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdFoldFieldHalosX_C
+
+    function cudecompAmdFoldFieldHalosY_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, clear, halo_extents, halo_periods, &
+                                            dim, padding, stream) bind(C, name="cudecompAmdFoldFieldHalosY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*)
+      integer(c_int32_t), value :: n_fields
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: parities(*)
+      integer(c_int32_t), value :: centering, clear
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdFoldFieldHalosY_C
+
+    function cudecompAmdFoldFieldHalosZ_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, clear, halo_extents, halo_periods, &
+                                            dim, padding, stream) bind(C, name="cudecompAmdFoldFieldHalosZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*)
+      integer(c_int32_t), value :: n_fields
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: parities(*)
+      integer(c_int32_t), value :: centering, clear
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdFoldFieldHalosZ_C
+
     function cudecompAmdTransposeFieldsXToY_C(handle, grid_desc, inputs, outputs, n_fields, work, dtype, ihalo, ohalo, ipad, opad, &
                                                 stream) bind(C, name="cudecompAmdTransposeFieldsXToY") result(res)
       import
@@ -1685,6 +1794,163 @@ contains
     res = cudecompAmdAccumulateFieldHalosZ_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), c_loc(work), int(dtype, c_int), h, &
                                              per, int(dim - 1, c_int32_t), p, int(clear, c_int32_t), s)
   end function cudecompAmdAccumulateFieldHalosZ
+
+
+  ! ---- multi-field wall halos (include/cudecomp_halo_wall_fields.h): n_fields pencils, a parity per field, one launch ---------
+  ! the arguments of cudecompAmdReflectHalosX / cudecompAmdFoldHalosX with the list of fields and its length in the place of `input`
+  ! and the list of parities (+1 / -1 per field) in the place of `parity`
+  function cudecompAmdReflectFieldHalosX(handle, grid_desc, inputs, n_fields, dtype, parities, centering, halo_extents, halo_periods, dim, &
+                                         padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    integer :: dtype
+    integer, intent(in) :: parities(n_fields)  ! per field, +1: mirrored as it is; -1: with the sign bits flipped
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3), par(max(n_fields, 1))
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    par = 0
+    if (n_fields >= 1) par(1:n_fields) = int(parities, c_int32_t)
+    res = cudecompAmdReflectFieldHalosX_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), int(dtype, c_int), par, &
+                                           int(centering, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdReflectFieldHalosX
+
+  function cudecompAmdReflectFieldHalosY(handle, grid_desc, inputs, n_fields, dtype, parities, centering, halo_extents, halo_periods, dim, &
+                                         padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    integer :: dtype
+    integer, intent(in) :: parities(n_fields)  ! per field, +1: mirrored as it is; -1: with the sign bits flipped
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3), par(max(n_fields, 1))
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    par = 0
+    if (n_fields >= 1) par(1:n_fields) = int(parities, c_int32_t)
+    res = cudecompAmdReflectFieldHalosY_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), int(dtype, c_int), par, &
+                                           int(centering, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdReflectFieldHalosY
+
+  function cudecompAmdReflectFieldHalosZ(handle, grid_desc, inputs, n_fields, dtype, parities, centering, halo_extents, halo_periods, dim, &
+                                         padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    integer :: dtype
+    integer, intent(in) :: parities(n_fields)  ! per field, +1: mirrored as it is; -1: with the sign bits flipped
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3), par(max(n_fields, 1))
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    par = 0
+    if (n_fields >= 1) par(1:n_fields) = int(parities, c_int32_t)
+    res = cudecompAmdReflectFieldHalosZ_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), int(dtype, c_int), par, &
+                                           int(centering, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdReflectFieldHalosZ
+
+  function cudecompAmdFoldFieldHalosX(handle, grid_desc, inputs, n_fields, dtype, parities, centering, clear, halo_extents, halo_periods, dim, &
+                                         padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    integer :: dtype
+    integer, intent(in) :: parities(n_fields)  ! per field, +1: mirrored as it is; -1: with the sign bits flipped
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: clear      ! 1: the ghost cells that were read hold zero bytes afterwards; 0: they are only read
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3), par(max(n_fields, 1))
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    par = 0
+    if (n_fields >= 1) par(1:n_fields) = int(parities, c_int32_t)
+    res = cudecompAmdFoldFieldHalosX_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), int(dtype, c_int), par, &
+                                           int(centering, c_int32_t), int(clear, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdFoldFieldHalosX
+
+  function cudecompAmdFoldFieldHalosY(handle, grid_desc, inputs, n_fields, dtype, parities, centering, clear, halo_extents, halo_periods, dim, &
+                                         padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    integer :: dtype
+    integer, intent(in) :: parities(n_fields)  ! per field, +1: mirrored as it is; -1: with the sign bits flipped
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: clear      ! 1: the ghost cells that were read hold zero bytes afterwards; 0: they are only read
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3), par(max(n_fields, 1))
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    par = 0
+    if (n_fields >= 1) par(1:n_fields) = int(parities, c_int32_t)
+    res = cudecompAmdFoldFieldHalosY_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), int(dtype, c_int), par, &
+                                           int(centering, c_int32_t), int(clear, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdFoldFieldHalosY
+
+  function cudecompAmdFoldFieldHalosZ(handle, grid_desc, inputs, n_fields, dtype, parities, centering, clear, halo_extents, halo_periods, dim, &
+                                         padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    integer :: dtype
+    integer, intent(in) :: parities(n_fields)  ! per field, +1: mirrored as it is; -1: with the sign bits flipped
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: clear      ! 1: the ghost cells that were read hold zero bytes afterwards; 0: they are only read
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3), par(max(n_fields, 1))
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    par = 0
+    if (n_fields >= 1) par(1:n_fields) = int(parities, c_int32_t)
+    res = cudecompAmdFoldFieldHalosZ_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), int(dtype, c_int), par, &
+                                           int(centering, c_int32_t), int(clear, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdFoldFieldHalosZ
 
 
   ! ---- multi-field transposes (include/cudecomp_transpose_fields.h): n_fields pencils, one exchange ------------------------

@@ -434,6 +434,24 @@ cudecompResult_t cudecompExtDescribeFieldMovesOp(const cudecompExtMove_t* moves,
                                                 int32_t n_fields, uint64_t work_address, int64_t work_field_stride, int32_t es,
                                                 int32_t force, int32_t mode, cudecompDataType_t dtype, int64_t out[5]);
 
+/* The pair once more for MIRRORED lists with a sign per field (kernels_field_mirror.hip; csrc/kernels.h launchFieldMoveList with
+ * one_choice and `mirrored`): moves[0 .. n - 1], n <= 2, are reflect-moves -- one dim of a move has a NEGATIVE source stride and
+ * src_off names the source cell of its index 0 -- carried out for n_fields (1 .. 32) buffers in ONE launch.  Both ends of a move
+ * lie in field f's own buffer (buffer numbers 0 or 1; the workspace, peer and row_pitch are refused).  mode: 0 reflect (dst = src),
+ * 1 fold (dst += src), 4 fold and take (dst += src; src = 0); every other value is INVALID_USAGE.  `dtype` names the real type of
+ * the elements, always (its element size must be `es`): bit f of `fields_neg` says that the sign bits of field f's source are
+ * flipped on the way (a fold flips first and adds then); a bit at or beyond n_fields is INVALID_USAGE.  force as above.  Sources
+ * must be disjoint from all destinations.  kinds (csrc/kernels_batch.h KernelKind): 31 rows_fields_reflect_kernel, 32
+ * generic_fields_reflect_kernel, 33 rows_fields_fold_kernel, 34 generic_fields_fold_kernel, 35 / 36 the folding kernels with TAKE;
+ * -1 nothing to launch.  Access mode: 0 cached; 1 the reflection's non-temporal loads and stores, the fold's non-temporal source
+ * loads and (take) zero stores -- the destination of a fold is always cached.  The kind does not depend on fields_neg. */
+cudecompResult_t cudecompExtRunMirroredFieldMoves(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
+                                                 int32_t es, int32_t force, int32_t mode, cudecompDataType_t dtype,
+                                                 uint32_t fields_neg, hipStream_t stream, int32_t* n_launches);
+cudecompResult_t cudecompExtDescribeMirroredFieldMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
+                                                      int32_t n_fields, int32_t es, int32_t force, int32_t mode,
+                                                      cudecompDataType_t dtype, uint32_t fields_neg, int64_t out[5]);
+
 /* The plan cudecompAmdTransposeFields{XToY,YToZ,ZToY,YToX} (cudecomp_transpose_fields.h) would run on `rank` for n_fields fields
  * (csrc/plan.h buildTransposeFieldsPlan), stateless like cudecompExtPlanTranspose and with its arguments.  pack / unpack are the
  * moves of FIELD 0: an end in buffer 0 / 1 is field f's input / output pencil at the same offset, an end in buffer 2 (the
@@ -481,6 +499,11 @@ cudecompResult_t cudecompExtDescribeFieldMoveList(const cudecompExtMove_t* moves
  * one-sided transport makes with the row-copy kernel between ranks that share a GPU go through launchMoves and are).  Tests take
  * the difference around a call. */
 cudecompResult_t cudecompExtDataLaunchCount(int64_t* launches);
+
+/* Halo plans the descriptor has cached so far: one per distinct (axis, dim, halos, padding, periods, packed, operation) of the
+ * halo calls made on it -- the parities of a multi-field wall call (cudecomp_halo_wall_fields.h) are no part of the operation.
+ * Tests take the difference around a call. */
+cudecompResult_t cudecompExtHaloPlanCount(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, int64_t* plans);
 
 /* The orbit walk of the in-place rotation kernel (csrc/rotate_walk.h; no launch, works without a GPU): for an array of nb
  * blocks per edge and walk (-1 = the default), *grid = the workgroups a launch has, and for workgroups first .. first + count - 1
