@@ -15,7 +15,11 @@ with --accumulate --fields N / --accumulate-clear --fields N, cudecompAmdAccumul
 clear 0 / 1 on N such pencils: the two wrap additions for all N in one launch (N * 6 / N * 8 * face bytes) and, with --wall-fields N,
 cudecompAmdReflectFieldHalosX and cudecompAmdFoldFieldHalosX (cudecomp_halo_wall_fields.h; centering 0, clear 0, parities -1, +1, -1, ...)
 on N such pencils as a NON-periodic single rank: one call for all N against N single calls with the same parities, the two arms
-timed alternately in both orders (fields first, then singles; singles first, then fields) with every shape warmed up before.
+timed alternately in both orders (fields first, then singles; singles first, then fields) with every shape warmed up before and, with
+--wall-values, cudecompAmdSetWallHalosX (cudecomp_halo_wall_values.h; parity -1, centering 0, both sides, one addend per layer) next to
+cudecompAmdReflectHalosX with parity -1 on the same pencil, walls along dims 1 and 2 (dim 0 periodic), for fp64 and for fp16: the
+reflection's two sibling moves plus one addition per element (4 * face bytes), the two calls timed in the order reflection, wall
+values, wall values, reflection.
 Per dim: `--reps` repetitions of `--calls` back-to-back calls each, ms per call of every repetition, their
 min / median / max, and GB/s of the median against the algorithmic bytes (update: 2 faces read + written,
 4 * face bytes; accumulation: 2 faces read, 2 destinations read and written, 6 * face bytes; fill: 2 halos written, 2 * face
@@ -76,6 +80,9 @@ def main():
     ap.add_argument("--wall-fields", type=int, default=0, metavar="N",
                     help="also time cudecompAmdReflectFieldHalosX / cudecompAmdFoldFieldHalosX on N pencils (non-periodic) against N single "
                          "calls, both orders of the two arms, and compare every field on the device with a clone served by single calls")
+    ap.add_argument("--wall-values", action="store_true",
+                    help="also time cudecompAmdSetWallHalosX (parity -1, centering 0, both sides) next to cudecompAmdReflectHalosX with "
+                         "parity -1, walls along dims 1 and 2, fp64 and fp16, after the other passes")
     ap.add_argument("--gdims", type=int, nargs=3, default=[2048, 1024, 256], metavar="N",
                     help="the pencil (default: config 5's per-rank X pencil; 64 64 64: a pencil on which fixed cost dominates)")
     ap.add_argument("--json", metavar="FILE", default=None, help="also write the result line to FILE")
@@ -165,6 +172,30 @@ def main():
         for dim in range(3):
             cd.cudecompReflectHalos(0, h, gd, data.data_ptr(), cd.DOUBLE, 1, 0, halo, (0, 0, 0), dim, stream=st)
         extra["cells_not_one_after_reflect"] = int(cells.numel()) - int(torch.count_nonzero(cells == 1.0))
+    if a.wall_values:
+        periods = (1, 0, 0)
+        for dtype, tdtype, es, label in ((cd.DOUBLE, torch.float64, 8, "fp64"), (cd.HALF, torch.float16, 2, "fp16")):
+            pencil = torch.ones(p.size, dtype=tdtype, device="cuda")
+            low, high = [0.5 * (k + 1) for k in range(a.halo)], [-0.25 * (k + 1) for k in range(a.halo)]
+            reflect = lambda: cd.cudecompReflectHalos(0, h, gd, pencil.data_ptr(), dtype, -1, 0, halo, periods, dim, stream=st)
+            wall = lambda: cd.cudecompAmdSetWallHalos(0, h, gd, pencil.data_ptr(), dtype, -1, 0, 3, low, high, halo, periods, dim, stream=st)
+            for dim in (1, 2):
+                rec = res["dim%d" % dim].setdefault("wall_values", {})
+                runs, kernels = {"reflect": [], "wall_values": []}, {}
+                for name, fn in (("reflect", reflect), ("wall_values", wall), ("wall_values", wall), ("reflect", reflect)):
+                    runs[name] += _time(fn, a.reps, a.calls)
+                    kernels[name] = cd.cudecompExtLastKernelName()
+                out = {name: _record(ms, 4 * faces[dim] * es) for name, ms in runs.items()}
+                out["reflect_kernel"], out["wall_values_kernel"] = kernels["reflect"], kernels["wall_values"]
+                out["wall_values_over_reflect"] = round(out["wall_values"]["median_ms"] / out["reflect"]["median_ms"], 3)
+                rec[label] = out
+            # what the call wrote: from an interior of ones, parity -1 and a_k leave -1 + a_k in ghost layer k of the low wall of dim 1
+            pencil.fill_(1.0)
+            cd.cudecompAmdSetWallHalos(0, h, gd, pencil.data_ptr(), dtype, -1, 0, 3, low, high, halo, periods, 1, stream=st)
+            cells = pencil.view(shape[2], shape[1], shape[0])
+            want = torch.tensor([low[a.halo - 1 - j] - 1.0 for j in range(a.halo)], dtype=tdtype, device="cuda")
+            got = cells[a.halo, :a.halo, a.halo]
+            extra["wall_values_wrong_cells_" + label] = int(torch.count_nonzero(got != want))
     for clear, wanted in ((0, a.fold), (1, a.fold_clear)):
         if not wanted:
             continue
@@ -318,7 +349,8 @@ def main():
                                            + (" and their accumulation in one call" if a.fields and a.accumulate else "")
                                            + (" and their accumulate-and-clear in one call" if a.fields and a.accumulate_clear else "")
                                            + (" and the reflection and the fold of %d pencils in one call (non-periodic)" % a.wall_fields
-                                              if a.wall_fields else ""),
+                                              if a.wall_fields else "")
+                                           + (" and wall values next to the reflection (walls along dims 1 and 2, fp64 and fp16)" if a.wall_values else ""),
                                            a.reps, a.calls)),
                             "device": torch.cuda.get_device_name(0), "result": res}, **extra))
     print(line)
@@ -343,6 +375,10 @@ def main():
             sys.exit("halo_bench.py: after folding a pencil of ones along 2, 1, 0 (%s pass) %d interior cells do not hold their count and %d "
                      "ghost cells are not zero" % (name, extra["interior_cells_with_another_count_after_" + name],
                                                    extra["ghost_cells_not_zero_after_" + name]))
+    for label in ("fp64", "fp16"):
+        if extra.get("wall_values_wrong_cells_" + label):
+            sys.exit("halo_bench.py: %d ghost cells of the low wall do not hold -1 + a_k after the wall values (%s)"
+                     % (extra["wall_values_wrong_cells_" + label], label))
     if extra.get("cells_not_one_after_reflect"):
         sys.exit("halo_bench.py: after the even mirror along 0, 1, 2 %d cells do not hold the interior's value" % extra["cells_not_one_after_reflect"])
     if extra.get("ghost_cells_not_zero") or extra.get("interior_cells_changed"):

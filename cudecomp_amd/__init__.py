@@ -168,7 +168,8 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtDescribeFieldMoves", "cudecompExtDataLaunchCount", "cudecompExtPlanTransposeFields",
                "cudecompExtRunFieldMoveList", "cudecompExtDescribeFieldMoveList", "cudecompExtDescribeResidency",
                "cudecompExtPlanHaloAccumulateFields", "cudecompExtRunFieldMovesOp", "cudecompExtDescribeFieldMovesOp",
-               "cudecompExtRunMirroredFieldMoves", "cudecompExtDescribeMirroredFieldMoves", "cudecompExtHaloPlanCount"]
+               "cudecompExtRunMirroredFieldMoves", "cudecompExtDescribeMirroredFieldMoves", "cudecompExtHaloPlanCount",
+               "cudecompExtPlanHaloWallValues", "cudecompExtWall3D"]
 # include/cudecomp_amd.h: extensions of the API a solver may use
 AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
 # include/cudecomp_amd_fill.h: halo fill
@@ -192,6 +193,9 @@ AMD_REFLECT_FIELDS_SYMBOLS = ["cudecompAmdReflectFieldHalosX", "cudecompAmdRefle
 AMD_FOLD_FIELDS_SYMBOLS = ["cudecompAmdFoldFieldHalosX", "cudecompAmdFoldFieldHalosY", "cudecompAmdFoldFieldHalosZ"]
 AMD_WALL_FIELDS_SYMBOLS = AMD_REFLECT_FIELDS_SYMBOLS + AMD_FOLD_FIELDS_SYMBOLS
 MAX_HALO_WALL_FIELDS = 32  # CUDECOMP_AMD_MAX_HALO_WALL_FIELDS
+# include/cudecomp_halo_wall_values.h: wall values (the reflection with one addend per ghost layer and side: Dirichlet / Neumann data)
+AMD_WALL_VALUES_SYMBOLS = ["cudecompAmdSetWallHalosX", "cudecompAmdSetWallHalosY", "cudecompAmdSetWallHalosZ"]
+MAX_WALL_HALO = 8  # CUDECOMP_AMD_MAX_WALL_HALO
 # include/cudecomp_transpose_fields.h: multi-field transposes (several pencils in one exchange)
 TRANSPOSE_FIELDS_SYMBOLS = ["cudecompAmdTransposeFieldsXToY", "cudecompAmdTransposeFieldsYToZ", "cudecompAmdTransposeFieldsZToY",
                             "cudecompAmdTransposeFieldsYToX"]
@@ -264,6 +268,12 @@ def lib():
             getattr(L, name).argtypes = [vp, vp, vp, i32, i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         for name in AMD_FOLD_SYMBOLS:  # (the reflection's arguments with `clear` after the centering)
             getattr(L, name).argtypes = [vp, vp, vp, i32, i32, i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
+        pf64 = C.POINTER(C.c_double)
+        for name in AMD_WALL_VALUES_SYMBOLS:  # (the reflection's arguments with `sides` and the two host arrays after the centering)
+            getattr(L, name).argtypes = [vp, vp, vp, i32, i32, i32, i32, pf64, pf64, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
+        L.cudecompExtPlanHaloWallValues.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32, i32,
+                                                    i32, pf64, pf64, C.POINTER(ExtHaloPlan), C.POINTER(C.c_uint8)]
+        L.cudecompExtWall3D.argtypes = [vp, vp, i32, i32, i32, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, pi32, vp]
         for name in AMD_FIELDS_SYMBOLS:  # (the update's arguments with the list of fields and its length in the place of `input`)
             getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         L.cudecompExtPlanHaloFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32,
@@ -515,6 +525,31 @@ def cudecompReflectHalos(axis, handle, gd, inp, dtype, parity, centering, halo_e
                                 _i3(padding), stream), name)
 
 
+def _f64(values):
+    """a host array of doubles for ctypes (None stays NULL)"""
+    if values is None:
+        return None
+    v = [float(x) for x in values]
+    return (C.c_double * max(1, len(v)))(*v)
+
+
+def cudecompAmdSetWallHalos(axis, handle, gd, inp, dtype, parity, centering, sides, values_low, values_high, halo_extents,
+                            halo_periods, dim, padding=None, stream=None):
+    """cudecompAmdSetWallHalos{X,Y,Z} (cudecomp_halo_wall_values.h): the ghost cells the reflection along `dim` writes receive
+    parity * mirror + addend, one addend per ghost layer k (counted from the wall outward) and side; `sides` bit 0 the low halo, bit 1
+    the high halo.  values_low / values_high: sequences of halo_extents[dim] floats (complex types: twice as many, re and im
+    interleaved), converted once on the host; the one of a side not named may be None."""
+    if parity not in (1, -1):
+        raise ValueError("parity must be +1 or -1, not %r" % (parity,))
+    if centering not in (0, 1):
+        raise ValueError("centering must be 0 or 1, not %r" % (centering,))
+    if sides not in (1, 2, 3):
+        raise ValueError("sides must be 1, 2 or 3, not %r" % (sides,))
+    name = "cudecompAmdSetWallHalos" + "XYZ"[axis]
+    _check(getattr(lib(), name)(handle, gd, inp, dtype, int(parity), int(centering), int(sides), _f64(values_low), _f64(values_high),
+                                _i3(halo_extents), _b3(halo_periods), dim, _i3(padding), stream), name)
+
+
 def cudecompFoldHalos(axis, handle, gd, inp, dtype, parity, centering, clear, halo_extents, halo_periods, dim, padding=None,
                       stream=None):
     """cudecompAmdFoldHalos{X,Y,Z} (cudecomp_halo_fold.h), the transpose of the reflection: the ghost cells along `dim` that have
@@ -701,6 +736,21 @@ def cudecompExtPlanHaloFold(grid, rank, axis, halo_extents, halo_periods, dim, p
     return p
 
 
+def cudecompExtPlanHaloWallValues(grid, rank, axis, halo_extents, halo_periods, dim, dtype, parity, centering, sides, values_low,
+                                  values_high, padding=None):
+    """Stateless planner of cudecompAmdSetWallHalos*: (plan, table) -- the plan's moves are the reflection's for the sides kept, with
+    ExtMove.peer the side; ExtHaloPlan.reserved bit 15 marks the plan, bit 13 the sign flip, bits 16 / 17 the sides; table is a uint8
+    array of shape (2, MAX_WALL_HALO, 16): per side the converted addends in DESTINATION order, replicated to 16 bytes
+    (cudecomp_ext.h).  Arguments are passed as they are: the library makes the checks."""
+    import numpy as np
+    p = ExtHaloPlan()
+    table = np.zeros((2, MAX_WALL_HALO, 16), dtype=np.uint8)
+    _check(lib().cudecompExtPlanHaloWallValues(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding),
+                                               int(dtype), int(parity), int(centering), int(sides), _f64(values_low), _f64(values_high),
+                                               C.byref(p), table.ctypes.data_as(C.POINTER(C.c_uint8))), "cudecompExtPlanHaloWallValues")
+    return p, table
+
+
 def cudecompExtPlanHaloFields(grid, rank, axis, halo_extents, halo_periods, dim, padding=None, n_fields=1, force_packed=False):
     """Stateless planner of cudecompAmdUpdateFieldHalos*: the moves of field 0, the slot layout and the offsets (cudecomp_ext.h)."""
     p = ExtHaloFieldsPlan()
@@ -843,6 +893,18 @@ def cudecompExtFold3D(src, dst, dtype, negate, take, extent, ss, ds, force=0, st
     return cls.value
 
 
+def cudecompExtWall3D(src, dst, dtype, negate, side, addends, extent, ss, ds, force=0, stream=None):
+    """One wall-value move (dst = +-src + addend of the destination's layer; the negative entry of `ss` names the mirrored dim; side
+    0 low / 1 high; `addends`: bytes or a numpy array of one element of `dtype` per layer, counted from the wall outward) through the
+    kernel layer; returns the kernel class (0 rows, 2 generic)."""
+    cls = C.c_int32(-1)
+    a = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
+    raw = addends if isinstance(addends, (bytes, bytearray)) else addends.tobytes()
+    _check(lib().cudecompExtWall3D(src, dst, dtype, int(bool(negate)), int(side), bytes(raw), a(extent), a(ss), a(ds), int(force),
+                                   C.byref(cls), stream), "cudecompExtWall3D")
+    return cls.value
+
+
 def cudecompExtRotateWalk(nb, walk=-1):
     """The in-place rotation kernel's orbit walk for nb blocks per edge (no launch, no GPU): (grid, blocks) with blocks an
     int32 array of shape (grid, 3): the block triple of every workgroup, -1 -1 -1 for the ones that map to none."""
@@ -874,6 +936,9 @@ MOVES_REFLECT, MOVES_REFLECT_NEGATE = 5, 6  # ... mirror copies (a negative `ss`
 # ... folds (additions whose source runs backwards along the dim its negative `ss` entry names): plain / sign bits flipped first /
 # then zero bytes into the source cells / both
 MOVES_FOLD, MOVES_FOLD_NEGATE, MOVES_FOLD_TAKE, MOVES_FOLD_NEGATE_TAKE = 7, 8, 9, 10
+# ... wall values (mirror copies that add the addend of the destination's layer; ExtMove.peer names the side, `value` holds the
+# 2 x MAX_WALL_HALO addends as bytes), plain / sign bits flipped first
+MOVES_WALL, MOVES_WALL_NEGATE = 11, 12
 
 
 def make_move(extent, ss, ds, src_off=0, dst_off=0, src_buf=0, dst_buf=1, row_pitch=0):
@@ -896,8 +961,9 @@ def cudecompExtRunMoves(moves, bufs, es, mode=MOVES_COPY, dtype=0, value=None, f
     """A list of moves through the kernel layer's batching (cudecomp_ext.h): bufs = three device pointers (ints or None),
     dst_bases = None or one device pointer per move.  Returns (launches per class, elements per class, launches in all)."""
     v = _value_bytes(value)
-    if v is not None and len(v) != es:
-        raise ValueError("value holds %d bytes, the element size is %d" % (len(v), es))
+    want = es * (2 * MAX_WALL_HALO if mode in (MOVES_WALL, MOVES_WALL_NEGATE) else 1)
+    if v is not None and len(v) != want:
+        raise ValueError("value holds %d bytes, this mode takes %d" % (len(v), want))
     b = (C.c_void_p * 3)(*[p or None for p in bufs])
     bases = None if dst_bases is None else (C.c_void_p * max(1, len(moves)))(*[p or None for p in dst_bases])
     launches, elements, total = (C.c_int32 * 3)(), (C.c_int64 * 3)(), C.c_int32(-1)

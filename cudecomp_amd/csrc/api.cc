@@ -842,7 +842,9 @@ CD_DEFINE_TRANSPOSE(cudecompTransposeYToX, OP_Y_TO_X)
 //    is checked for NULL right after the list of fields, and its entries are read where the single calls read `parity`: when every
 //    halo is zero (there the list of fields is not looked at, but `parities` and the n_fields that says how many to read are),
 //    otherwise by the runner.  One field: the single call with parities[0].  Several: the signs travel as a mask of fields;
-//  - the local families (fill, reflection, folding) take no workspace.
+//  - wall values (cudecompAmdSetWallHalos*) check parity, centering, sides and the value arrays where the reflection checks parity
+//    and centering;
+//  - the local families (fill, reflection, folding, wall values) take no workspace.
 struct HaloEntryOptions {
   int max_fields = 0;                 // > 0: a multi-field family and the most fields it takes
   bool clear_first = false;           // `clear` is checked right after halo_extents
@@ -887,6 +889,12 @@ static cudecompResult_t haloApiEntry(cudecompHandle_t handle, cudecompGridDesc_t
         if (c.parity != 1 && c.parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
         if (c.op.centering != 0 && c.op.centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
         if (c.clear != 0 && c.clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
+      }
+      if (kind == HaloOp::WALL_VALUES) {
+        if (c.parity != 1 && c.parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
+        if (c.op.centering != 0 && c.op.centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
+        const int refusal = wallValueRefusal(c.op.sides, c.values_low != nullptr, c.values_high != nullptr, 0);
+        if (refusal != 0) refuseWallValues(refusal);
       }
       return CUDECOMP_RESULT_SUCCESS;
     }
@@ -977,6 +985,26 @@ CD_DEFINE_HALO_FILL(cudecompAmdFillHalosZ, 2)
 CD_DEFINE_HALO_REFLECT(cudecompAmdReflectHalosX, 0)
 CD_DEFINE_HALO_REFLECT(cudecompAmdReflectHalosY, 1)
 CD_DEFINE_HALO_REFLECT(cudecompAmdReflectHalosZ, 2)
+
+// cudecomp_halo_wall_values.h: the reflection with one addend per ghost layer and side (Dirichlet and Neumann data at a wall)
+#define CD_DEFINE_HALO_WALL_VALUES(NAME, AXIS)                                                                              \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,       \
+                        int32_t parity, int32_t centering, int32_t sides, const double values_low[],                        \
+                        const double values_high[], const int32_t halo_extents[], const bool halo_periods[], int32_t dim,   \
+                        const int32_t padding[], hipStream_t stream) {                                                      \
+    HaloCall c = haloCall(HaloOp::WALL_VALUES, AXIS, &input, nullptr, dtype, halo_extents, halo_periods, dim, padding,      \
+                          stream);                                                                                          \
+    c.parity = parity;                                                                                                      \
+    c.op.negate = parity == -1;                                                                                             \
+    c.op.centering = centering;                                                                                             \
+    c.op.sides = sides;                                                                                                     \
+    c.values_low = values_low;                                                                                              \
+    c.values_high = values_high;                                                                                            \
+    return haloApiEntry(handle, grid_desc, c);                                                                              \
+  }
+CD_DEFINE_HALO_WALL_VALUES(cudecompAmdSetWallHalosX, 0)
+CD_DEFINE_HALO_WALL_VALUES(cudecompAmdSetWallHalosY, 1)
+CD_DEFINE_HALO_WALL_VALUES(cudecompAmdSetWallHalosZ, 2)
 
 // cudecomp_halo_fold.h: the ghost cells the reflection writes are added onto their mirror images
 #define CD_DEFINE_HALO_FOLD(NAME, AXIS)                                                                                     \

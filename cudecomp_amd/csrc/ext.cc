@@ -9,6 +9,7 @@
 #include "cudecomp_halo_fields.h"
 #include "cudecomp_halo_accumulate_fields.h"
 #include "cudecomp_halo_wall_fields.h"
+#include "cudecomp_halo_wall_values.h"
 #include "cudecomp_transpose_fields.h"
 #include "errors.h"
 #include "internal.h"
@@ -111,6 +112,7 @@ void exportHaloPlan(const HaloPlan& p, cudecompExtHaloPlan_t* out) {
     if (op.kind == HaloOp::FILL) out->reserved = 256;
     if (op.kind == HaloOp::REFLECT) out->reserved = 4096 | (op.negate ? 8192 : 0);
     if (op.kind == HaloOp::FOLD) out->reserved = 16384 | (op.negate ? 8192 : 0) | (p.ordered ? 2 : 0);
+    if (op.kind == HaloOp::WALL_VALUES) out->reserved = 32768 | (op.negate ? 8192 : 0) | (op.sides << 16);
     if (op.clear) {
       out->reserved |= 512;
       for (size_t i = 0; i < p.pre.size(); ++i)
@@ -179,9 +181,9 @@ std::vector<Move3D> importMoves(const cudecompExtMove_t* moves, int32_t n, int32
                                 ArithType* arith) {
   if (n < 0 || (n > 0 && !moves)) CD_INVALID_USAGE("bad move list");
   if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
-  if (mode < 0 || mode > 10)
-    CD_INVALID_USAGE("mode must be 0 (copy), 1 (add), 2 (fill), 3 (take), 4 (add and take), 5 (mirror copy), 6 (mirror copy with sign flip) "
-                     "or 7 ... 10 (fold: plain, with sign flip, with take, with both)");
+  if (mode < 0 || mode > 12)
+    CD_INVALID_USAGE("mode must be 0 (copy), 1 (add), 2 (fill), 3 (take), 4 (add and take), 5 (mirror copy), 6 (mirror copy with sign flip), "
+                     "7 ... 10 (fold: plain, with sign flip, with take, with both) or 11 / 12 (wall values: plain, with sign flip)");
   *arith = ARITH_NONE;
   if (mode == 1 || mode == 4 || mode >= 6) {
     if (elementSize(dtype) != es) CD_INVALID_USAGE("element size does not match the data type of the arithmetic");
@@ -203,13 +205,19 @@ std::vector<Move3D> importMoves(const cudecompExtMove_t* moves, int32_t n, int32
       m.ds[d] = e.ds[d];
     }
     m.dst_row_pitch = e.row_pitch;
-    m.add = mode == 1 || mode == 4 || mode >= 7;
+    const bool wall = mode == 11 || mode == 12;
+    m.add = mode == 1 || mode == 4 || (mode >= 7 && !wall);
     m.fill = mode == 2;
     m.take = mode == 3 || mode == 4 || mode == 9 || mode == 10;
     m.reflect = mode >= 5;
-    m.negate = mode == 6 || mode == 8 || mode == 10;
+    m.negate = mode == 6 || mode == 8 || mode == 10 || mode == 12;
+    if (wall) {  // the move's `peer` names the side whose addends it takes
+      if (e.peer != 0 && e.peer != 1) CD_INVALID_USAGE("a wall-value move (mode 11 / 12) names its side in `peer`: 0 low, 1 high");
+      m.affine = e.peer + 1;
+    }
     // a mirror copy says which dim it mirrors: without a negative source stride the entry is a plain copy in the wrong mode
     if (m.reflect && e.ss[0] >= 0 && e.ss[1] >= 0 && e.ss[2] >= 0) {
+      if (wall) CD_INVALID_USAGE("a wall-value move (mode 11 / 12) names its mirrored dim with a negative source stride");
       if (mode >= 7) CD_INVALID_USAGE("a fold (mode 7 ... 10) names its mirrored dim with a negative source stride");
       CD_INVALID_USAGE("a mirror copy (mode 5 / 6) names its mirrored dim with a negative source stride");
     }
@@ -898,6 +906,86 @@ cudecompResult_t cudecompExtFold3D(const void* src, void* dst, cudecompDataType_
   return CUDECOMP_RESULT_SUCCESS;
 }
 
+cudecompResult_t cudecompExtWall3D(const void* src, void* dst, cudecompDataType_t dtype, int32_t negate, int32_t side,
+                                   const void* addends, const int64_t extent[3], const int64_t ss[3], const int64_t ds[3],
+                                   int32_t force, int32_t* kernel_class, hipStream_t stream) {
+  try {
+    if (!src || !dst || !addends || !extent || !ss || !ds) CD_INVALID_USAGE("null argument");
+    if (side != 0 && side != 1) CD_INVALID_USAGE("side must be 0 (low) or 1 (high)");
+    const int es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
+    Move3D m;
+    m.src_buf = BUF_IN;
+    m.dst_buf = BUF_OUT;
+    m.reflect = true;
+    m.negate = negate != 0;
+    m.affine = side + 1;
+    int layers = -1;
+    for (int i = 0; i < 3; ++i) {
+      m.extent[i] = extent[i];
+      m.ss[i] = ss[i];
+      m.ds[i] = ds[i];
+      if (ss[i] < 0) layers = layers < 0 ? (int)std::min<int64_t>(extent[i], CUDECOMP_AMD_MAX_WALL_HALO + 1) : CUDECOMP_AMD_MAX_WALL_HALO + 1;
+    }
+    if (layers < 0) CD_INVALID_USAGE("a wall-value move names its mirrored dim with a negative source stride");
+    if (layers > CUDECOMP_AMD_MAX_WALL_HALO) CD_INVALID_USAGE("one mirrored dim of at most CUDECOMP_AMD_MAX_WALL_HALO layers");
+    WallAddends a;
+    std::memset(&a, 0, sizeof(a));
+    for (int k = 0; k < layers; ++k) std::memcpy(a.v[side][k], static_cast<const char*>(addends) + (size_t)k * es, es);
+    void* bufs[3] = {const_cast<void*>(src), dst, nullptr};
+    KernelTuning t;
+    if (force & 1) t.force_class = MOVE_GENERIC;
+    if (force & 2) t.force_streaming = true;
+    if (force & 4) t.no_streaming = true;
+    KernelStats st;
+    launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, arithOf(dtype), nullptr, &a);
+    if (kernel_class) {
+      *kernel_class = -1;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
+        if (st.launches[c]) *kernel_class = c;
+    }
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtPlanHaloWallValues(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
+                                               const bool periods[], int32_t dim, const int32_t pad[], cudecompDataType_t dtype,
+                                               int32_t parity, int32_t centering, int32_t sides, const double values_low[],
+                                               const double values_high[], cudecompExtHaloPlan_t* out, uint8_t* table) {
+  try {
+    const GridShape g = shapeFromSpec(grid);
+    if (!out || !halo || !table) CD_INVALID_USAGE("null argument");
+    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
+    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
+    const int es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
+    const int32_t zero[3] = {0, 0, 0};
+    const bool none[3] = {false, false, false};
+    const bool* per = periods ? periods : none;
+    const int32_t* pp = pad ? pad : zero;
+    // the call's checks in the call's order: what the fill refuses, parity, centering, sides, value arrays, width, then the plan's
+    buildHaloPlan(g, rank, axis, dim, halo, per, pp, false, false);
+    if (parity != 1 && parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
+    if (centering != 0 && centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
+    const int refusal = wallValueRefusal(sides, values_low != nullptr, values_high != nullptr, halo[dim]);
+    if (refusal != 0) refuseWallValues(refusal);
+    HaloOp op = haloOp(HaloOp::WALL_VALUES, false, centering, parity == -1);
+    op.sides = sides;
+    const HaloPlan p = buildHaloOpPlan(g, rank, axis, dim, halo, per, pp, op, false, false);
+    exportHaloPlan(p, out);
+    const WallAddends a = wallAddendsOf(dtype, halo[dim], sides, values_low, values_high);
+    for (int side = 0; side < 2; ++side)
+      wallTableRow(a, side, (sides & (1 << side)) ? halo[dim] : 0, es, table + side * CUDECOMP_AMD_MAX_WALL_HALO * 16);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
 // the moves of a field launch (at most 2, CUDECOMP_AMD_MAX_HALO_FIELDS fields) or of a field-move list (at most
 // CUDECOMP_EXT_MAX_MEMBERS, CUDECOMP_AMD_MAX_TRANSPOSE_FIELDS fields)
 static std::vector<Move3D> importFieldMoves(const cudecompExtMove_t* moves, int32_t n, int32_t max_moves, int32_t n_fields,
@@ -1290,7 +1378,16 @@ cudecompResult_t cudecompExtRunMoves(const cudecompExtMove_t* moves, int32_t n, 
     const std::vector<Move3D> list = importMoves(moves, n, es, mode, dtype, &arith);
     const KernelTuning t = tuningOfFlags(flags);
     KernelStats st;
-    launchMoves(list.data(), n, bufs, es, stream, &t, &st, dst_bases, arith, mode == 2 ? fill_value : nullptr);
+    WallAddends addends;
+    const bool wall = mode == 11 || mode == 12;
+    if (wall) {  // fill_value: 2 x CUDECOMP_AMD_MAX_WALL_HALO elements of `es` bytes, the low side's layers then the high side's
+      if (!fill_value) CD_INVALID_USAGE("wall-value moves (mode 11 / 12) take their addends through fill_value");
+      std::memset(&addends, 0, sizeof(addends));
+      for (int side = 0; side < 2; ++side)
+        for (int k = 0; k < CUDECOMP_AMD_MAX_WALL_HALO; ++k)
+          std::memcpy(addends.v[side][k], static_cast<const char*>(fill_value) + (size_t)(side * CUDECOMP_AMD_MAX_WALL_HALO + k) * es, es);
+    }
+    launchMoves(list.data(), n, bufs, es, stream, &t, &st, dst_bases, arith, mode == 2 ? fill_value : nullptr, wall ? &addends : nullptr);
     int total = 0;
     for (int c = 0; c < MOVE_CLASS_COUNT; ++c) {
       if (launches) launches[c] = st.launches[c];

@@ -6,7 +6,69 @@
 #include "transport.h"
 #include "kernels_batch.h"
 
+#include <cstring>
+
 namespace cudecomp {
+
+static_assert(CUDECOMP_AMD_MAX_WALL_HALO == kern::kMaxWallHalo && kMaxWallLayers == kern::kMaxWallHalo,
+              "the header's limit, the planner's and the addend table's length are one number");
+
+// a double rounded to nearest even, in one step, to a 16-bit format of 1 sign, `ebits` exponent and `mbits` mantissa bits (binary16:
+// 5, 10; bfloat16: 8, 7); overflow gives infinity, what lies below half the smallest subnormal gives zero, a NaN stays one (quiet)
+static uint16_t narrowFromDouble(double x, int ebits, int mbits) {
+  uint64_t u;
+  std::memcpy(&u, &x, 8);
+  const uint16_t sign = (uint16_t)((u >> 63) << 15);
+  const int exp = (int)((u >> 52) & 0x7ff);
+  const uint64_t man = u & ((1ull << 52) - 1);
+  const int emax = (1 << ebits) - 1, bias = (1 << (ebits - 1)) - 1;
+  const uint16_t inf = (uint16_t)(emax << mbits);
+  if (exp == 0x7ff) return man ? (uint16_t)(sign | inf | (1u << (mbits - 1)) | (uint16_t)(man >> (52 - mbits))) : (uint16_t)(sign | inf);
+  if (exp == 0) return sign;  // (zero, or a double subnormal: far below either format's smallest subnormal)
+  int e = exp - 1023 + bias;  // the biased exponent of a normal result
+  if (e >= emax) return (uint16_t)(sign | inf);
+  const uint64_t sig = man | (1ull << 52);
+  int shift = 52 - mbits;
+  if (e <= 0) {  // subnormal result: the significand moves further down, the exponent field is 0
+    shift += 1 - e;
+    e = 0;
+  }
+  if (shift > 60) return sign;
+  uint64_t q = sig >> shift;
+  const uint64_t rem = sig & ((1ull << shift) - 1), half = 1ull << (shift - 1);
+  if (rem > half || (rem == half && (q & 1))) ++q;
+  // normal: q holds the implicit bit, and a carry out of the mantissa lands in the exponent; subnormal: q is the field
+  const uint64_t bits = e > 0 ? ((uint64_t)(e - 1) << mbits) + q : q;
+  return bits >= inf ? (uint16_t)(sign | inf) : (uint16_t)(sign | bits);
+}
+
+WallAddends wallAddendsOf(cudecompDataType_t dtype, int layers, int sides, const double* values_low, const double* values_high) {
+  if (layers < 0 || layers > kern::kMaxWallHalo) CD_INTERNAL_ERROR("more ghost layers than the addend table holds");
+  const ArithType arith = arithOf(dtype);
+  const int rs = arith == ARITH_F64 ? 8 : (arith == ARITH_F32 ? 4 : 2), nc = elementSize(dtype) / rs;
+  WallAddends a;
+  std::memset(&a, 0, sizeof(a));
+  for (int side = 0; side < 2; ++side) {
+    const double* in = side == 0 ? values_low : values_high;
+    if (!(sides & (1 << side))) continue;
+    if (!in && layers > 0) CD_INTERNAL_ERROR("the value array of a side to write is missing");
+    for (int k = 0; k < layers; ++k)
+      for (int c = 0; c < nc; ++c) {
+        const double x = in[k * nc + c];
+        unsigned char* out = a.v[side][k] + c * rs;
+        if (arith == ARITH_F64) {
+          std::memcpy(out, &x, 8);
+        } else if (arith == ARITH_F32) {
+          const float f = (float)x;  // (IEEE: one rounding to nearest even, overflow to infinity)
+          std::memcpy(out, &f, 4);
+        } else {
+          const uint16_t v = arith == ARITH_F16 ? narrowFromDouble(x, 5, 10) : narrowFromDouble(x, 8, 7);
+          std::memcpy(out, &v, 2);
+        }
+      }
+  }
+  return a;
+}
 
 // the exchange of a halo plan (update or accumulation): send slot / face i travels to neighbour i and lands in ITS receive slot
 // 1 - i (update: my low face fills the low neighbour's HIGH halo; accumulation: my low halo is the addend of its HIGH face)
@@ -24,7 +86,7 @@ static HaloExchange haloExchangeOf(const HaloPlan& plan, void* const bufs[3], in
   return x;
 }
 
-// The sequence of every halo call.  Local kinds (fill, reflection, folding) and self-periodic plans end after `pre`; the others pack
+// The sequence of every halo call.  Local kinds (fill, reflection, folding, wall values) and self-periodic plans end after `pre`; the others pack
 // (`pre`), exchange op.n_fields faces per direction with the exchange of the updates (haloExchange: same routing, transports and
 // stream ordering for all of them) and unpack or add what arrived (`post`).  Only the update of ONE pencil is sampled by the
 // performance report and overlaps pack, exchange and unpack face by face; a one-field call of the multi-field entry points IS the
@@ -33,7 +95,8 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
   const HaloOp& op = c.op;
   const int es = elementSize(c.dtype);
   const auto backend = gd->config.halo_comm_backend;
-  const bool mirrored = op.kind == HaloOp::REFLECT || op.kind == HaloOp::FOLD;
+  const bool wall = op.kind == HaloOp::WALL_VALUES;
+  const bool mirrored = op.kind == HaloOp::REFLECT || op.kind == HaloOp::FOLD || wall;
   // The key carries force_packed also where the plan never takes the direct form (accumulation) or only takes its destinations
   // from the update's plan (fill): a descriptor whose backend changes between peer and non-peer transports caches such a plan
   // twice -- harmless.  Two fields or more are always packed: one message per direction.
@@ -47,14 +110,17 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
     if (c.periods) per[i] = c.periods[i];
   }
   // reflection and folding check their own arguments here, in the contract's order: what the fill refuses, then parity,
-  // centering and `clear`, then (the plan's) a mirror that reaches beyond the interior
+  // centering and `clear`, then (wall values: sides, value arrays, width -- on every rank, whatever its place and the periods) then
+  // (the plan's) a mirror that reaches beyond the interior
   const bool bad_parity = c.parity != 1 && c.parity != -1, bad_centering = op.centering != 0 && op.centering != 1,
              bad_clear = c.clear != 0 && c.clear != 1;
-  if (mirrored && (bad_parity || bad_centering || bad_clear)) {
+  const int bad_wall = wall ? wallValueRefusal(op.sides, c.values_low != nullptr, c.values_high != nullptr, hh[c.dim]) : 0;
+  if (mirrored && (bad_parity || bad_centering || bad_clear || bad_wall != 0)) {
     buildHaloPlan(gd->shape, h->rank, c.axis, c.dim, hh.data(), per.data(), pp.data(), false, h->self_exchange);  // (the fill's refusals)
     if (bad_parity) CD_INVALID_USAGE("parity argument must be +1 or -1");
     if (bad_centering) CD_INVALID_USAGE("centering argument must be 0 or 1");
-    CD_INVALID_USAGE("clear argument must be 0 or 1");
+    if (bad_clear) CD_INVALID_USAGE("clear argument must be 0 or 1");
+    refuseWallValues(bad_wall);
   }
 
   const cudecompGridDesc::HaloKey hkey{c.axis, c.dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, force_packed};
@@ -71,9 +137,12 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
   void* bufs[3] = {c.fields[0], c.fields[0], c.work};
   // the arithmetic of the moves that add (accumulation, folding) or flip sign bits (reflection with parity -1; the reflection of
   // several fields always names its real type: its signs are a mask of fields, one kernel whatever they are)
-  const bool computes = op.kind == HaloOp::ACCUMULATE || op.kind == HaloOp::FOLD ||
+  const bool computes = op.kind == HaloOp::ACCUMULATE || op.kind == HaloOp::FOLD || wall ||
                         (op.kind == HaloOp::REFLECT && (op.negate || op.n_fields >= 2));
   const ArithType arith = computes ? arithOf(c.dtype) : ARITH_NONE;
+  // wall values: the addends are converted here, once per call, and travel to the launch by value -- read before the call returns
+  WallAddends addends;
+  if (wall) addends = wallAddendsOf(c.dtype, hh[c.dim], op.sides, c.values_low, c.values_high);
   const int force = (h->tuning.force_class == MOVE_GENERIC ? 1 : 0) | (h->tuning.force_streaming ? 2 : 0) | (h->tuning.no_streaming ? 4 : 0);
   // The one or two sides of a phase go into ONE launch, unless they add onto overlapping cells (`ordered`): then one launch per
   // side, low side first.  Several fields: the list kernels (one_choice); either end of a move in a pencil is field f's, the fields'
@@ -83,7 +152,7 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
     const int n = (int)moves.size(), each = plan.ordered && moves[0].add ? 1 : n;
     if (op.n_fields == 1) {
       for (int i = 0; i < n; i += each)
-        launchMoves(moves.data() + i, each, bufs, es, c.stream, &h->tuning, nullptr, nullptr, arith, c.value);
+        launchMoves(moves.data() + i, each, bufs, es, c.stream, &h->tuning, nullptr, nullptr, arith, c.value, wall ? &addends : nullptr);
     } else {
       const std::vector<i64> steps(n, plan.face_elements);
       for (int i = 0; i < n; i += each)

@@ -15,6 +15,7 @@
 #include "cudecomp_amd.h"
 #include "cudecomp_amd_fill.h"
 #include "cudecomp_amd_reflect.h"
+#include "cudecomp_halo_wall_values.h"
 #include "cudecomp_halo_fold.h"
 #include "cudecomp_halo_fields.h"
 #include "cudecomp_halo_accumulate_fields.h"
@@ -141,7 +142,7 @@ struct cudecompGridDesc {
   std::map<TransposeKey, cudecomp::TransposePlan> transpose_plans;
   using HaloKey = std::tuple<int, int, std::array<int32_t, 6>, std::array<bool, 3>, bool>;
   // every halo family in one map: HaloKey plus the operation.  The last entry of HaloKey (force_packed) is the family's own: update,
-  // accumulation and fill usesPeerTransport(...), reflection and folding false, two fields or more true (halo.cc)
+  // accumulation and fill usesPeerTransport(...), reflection, folding and wall values false, two fields or more true (halo.cc)
   std::map<std::pair<HaloKey, cudecomp::HaloOp>, cudecomp::HaloPlan> halo_plans;
   // cudecompAmdTransposeFields* with two fields or more: TransposeKey (never pipelined) plus n_fields
   std::map<std::tuple<TransposeKey, int>, cudecomp::TransposeFieldsPlan> transpose_fields_plans;
@@ -275,12 +276,20 @@ struct HaloCall {
   const void* value = nullptr;  // FILL
   int parity = 1, clear = 0;
   uint32_t fields_neg = 0;
+  // WALL_VALUES: the caller's host arrays (op.sides is the caller's number as it came; the runner checks all three after the centering)
+  const double* values_low = nullptr;
+  const double* values_high = nullptr;
   const int32_t* halo = nullptr;
   const bool* periods = nullptr;
   const int32_t* pad = nullptr;
   hipStream_t stream = nullptr;
 };
 void runHaloOp(cudecompHandle_t handle, cudecompGridDesc_t gd, const HaloCall& call);
+// halo.cc: the addends of a wall-value call as the kernel layer takes them -- for every side named in `sides` (bit 0 low, bit 1 high)
+// and every ghost layer k < layers the element of `dtype`: each double (one per real type, re and im interleaved per complex one)
+// rounded ONCE to the real type, to nearest even directly from the double (never through fp32), overflow to infinity.  The
+// array of a side that is not named is not looked at.  Pure host code.
+WallAddends wallAddendsOf(cudecompDataType_t dtype, int layers, int sides, const double* values_low, const double* values_high);
 
 // cudecompAmdTransposeFields*: n_fields pencils, one exchange (n_fields == 1 IS runTranspose)
 void runTransposeFields(cudecompHandle_t handle, cudecompGridDesc_t gd, TransposeOp op, void* const* inputs, void* const* outputs,

@@ -2,12 +2,12 @@
 //
 // A move is normalised (unit dims dropped, contiguous dims fused, dims sorted by source stride) and classified: classify()
 // writes WHAT runs into one KernelChoice (kernels_batch.h: the kind of kernel -- row copy plain / shifted / dense, LDS-tiled
-// transposition plain / window / lines / row lines, element-wise, the two additions, the two fills, the four takes, the two reflections, the four folds -- element size, lane width,
+// transposition plain / window / lines / row lines, element-wise, the two additions, the two fills, the four takes, the two reflections, the four folds, the two wall-moves -- element size, lane width,
 // tile, access mode) and HOW it walks into the Batch fields beside it.  Moves with equal choices are batched (up to kMaxBatch moves, e.g.
 // the per-peer pack copies of one transpose, share one launch; the descriptors travel in the kernel argument segment).  The
 // batching key, the launcher's instantiation and the kernel's name all come from that one record.  The kernels live in
 // kernels_rows.hip, kernels_transpose.hip (one code object per element size), kernels_window.hip, kernels_lines.hip,
-// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip and kernels_fold.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
+// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip and kernels_wall.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
 // transpose.cc; kernels_field_transpose.hip (lists of field-moves: the moves of a halo or transpose phase for several pencils in
 // one launch), kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) and
 // kernels_field_mirror.hip (the same lists mirrored, with a sign per field: multi-field wall halos) have an entry of their own at
@@ -378,6 +378,19 @@ void classifyFill(Classified& c, const Move3D& m, const KernelTuning& tuning, bo
   genericGeometry(c, m);
 }
 
+// layers of a wall-move (Move3D::affine): the extent of its one mirrored dim; -1 when it has none, several, or more layers than
+// the addend table holds
+int wallLayers(const Move3D& in) {
+  int mirrored = -1;
+  for (int i = 0; i < 3; ++i) {
+    if (in.ss[i] >= 0) continue;
+    if (mirrored >= 0) return -1;
+    mirrored = i;
+  }
+  if (mirrored < 0 || in.extent[mirrored] < 1 || in.extent[mirrored] > kMaxWallHalo) return -1;
+  return (int)in.extent[mirrored];
+}
+
 // The geometry of a reflect- or fold-move as the kernels take it.  Such a move never passes normalizeMove as a whole: the mirrored
 // dim (the one with the negative source stride) is set aside, the other two are normalised (and fused) as those of a copy, and the
 // mirrored dim comes back as the row or plane index, slower than the row.  mirrored_fastest: it is the fastest memory axis of
@@ -421,9 +434,20 @@ Move3D mirrorGeometry(const Move3D& in, bool& mirrored_fastest) {
 // the same way and are offered the same two geometries and nothing else.  Access mode: the accumulation's rule, cached below
 // kStreamBytes, from there non-temporal source loads and zero stores, the destination always cached (unmeasured for these
 // kernels too); the element-wise kernel always caches.
+// Wall-moves (Move3D::affine: reflect-moves that add the addend of the destination's layer along the mirrored dim) come the same
+// way once more: the two geometries of the reflection and nothing else, its access rule (unmeasured here too), lanes never narrower
+// than one element -- and Batch::p1 names the entry of the kernel's e[] that is the mirrored dim (-1 when it is one cell thick).
 Classified classifyReflect(const Move3D& in, void* const bufs[3], int es, const KernelTuning& tuning, bool remote, ArithType arith) {
-  const bool fold = in.add;
-  if (fold) {
+  const bool wall = in.affine != 0;
+  const bool fold = in.add && !wall;
+  if (wall) {
+    if (in.fill || in.take || in.add || in.dst_row_pitch != 0 || remote)
+      CD_INTERNAL_ERROR("wall-moves only reflect the cells of a local buffer and add their layer's value");
+    if (in.affine != 1 && in.affine != 2) CD_INTERNAL_ERROR("wall-move without a side");
+    if (arith == ARITH_NONE) CD_INTERNAL_ERROR("wall-move without an arithmetic type");
+    if (es % arithBytes(arith) != 0 || es / arithBytes(arith) > 2) CD_INTERNAL_ERROR("element size does not fit the arithmetic type");
+    if (wallLayers(in) < 0) CD_INTERNAL_ERROR("wall-move without a mirrored dim, or with more layers than the addend table holds");
+  } else if (fold) {
     if (in.fill || in.dst_row_pitch != 0 || remote) CD_INTERNAL_ERROR("fold-moves only add onto the cells of a local buffer");
     if (arith == ARITH_NONE) CD_INTERNAL_ERROR("fold-move without an arithmetic type");
     if (es % arithBytes(arith) != 0 || es / arithBytes(arith) > 2) CD_INTERNAL_ERROR("element size does not fit the arithmetic type");
@@ -437,23 +461,28 @@ Classified classifyReflect(const Move3D& in, void* const bufs[3], int es, const 
   const Move3D m = mirrorGeometry(in, mirrored_fastest);
   Classified c{};
   c.k.es = es;
-  c.k.arith = (fold || in.negate) ? arith : ARITH_NONE;
-  c.k.neg = fold && in.negate;
+  c.k.arith = (fold || wall || in.negate) ? arith : ARITH_NONE;
+  c.k.neg = (fold || wall) && in.negate;
+  int along = -1;  // wall-moves: the entry of the kernel's e[] whose index is the layer
+  for (int i = 0; wall && i < 3; ++i)
+    if (m.ss[i] < 0) along = i;
   c.elements = in.elements();
   const bool streaming = (c.elements * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming;
   c.dm.src = static_cast<const char*>(bufs[in.src_buf]) + in.src_off * es;
   c.dm.dst = static_cast<char*>(bufs[in.dst_buf]) + in.dst_off * es;
   if (tuning.force_class != MOVE_GENERIC && m.ss[0] <= 1 && m.ds[0] <= 1 && !mirrored_fastest) {
-    c.k.kind = fold ? (in.take ? K_ROWS_FOLD_TAKE : K_ROWS_FOLD) : K_ROWS_REFLECT;
+    c.k.kind = wall ? K_ROWS_WALL : (fold ? (in.take ? K_ROWS_FOLD_TAKE : K_ROWS_FOLD) : K_ROWS_REFLECT);
     c.k.access = streaming ? 1 : 0;
     rowVectors(c, m);
     if (c.k.vec < es) CD_INTERNAL_ERROR("reflect-move narrower than one element");
     rowTiles(c);
+    if (wall) c.p1 = along;
     return c;
   }
-  c.k.kind = fold ? (in.take ? K_GENERIC_FOLD_TAKE : K_GENERIC_FOLD) : K_GENERIC_REFLECT;
+  c.k.kind = wall ? K_GENERIC_WALL : (fold ? (in.take ? K_GENERIC_FOLD_TAKE : K_GENERIC_FOLD) : K_GENERIC_REFLECT);
   c.k.access = 0;
   genericGeometry(c, m, true);  // no destination-fast dim: along the longest
+  if (wall) c.p1 = along;
   return c;
 }
 
@@ -465,6 +494,7 @@ Classified classifyReflect(const Move3D& in, void* const bufs[3], int es, const 
 Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelTuning& tuning, void* dst_base, bool remote,
                     ArithType arith) {
   if (in.negate && !in.reflect) CD_INTERNAL_ERROR("only reflect- and fold-moves flip sign bits");
+  if (in.affine != 0 && !in.reflect) CD_INTERNAL_ERROR("only reflect-moves add a wall's values");
   if (in.reflect && in.take && !in.add) CD_INTERNAL_ERROR("a reflect-move that clears its source must be a fold-move (add)");
   if (in.reflect) return classifyReflect(in, bufs, es, tuning, remote || dst_base != nullptr, arith);
   Move3D m = in;
@@ -574,6 +604,10 @@ void spellKernelName(const KernelChoice& k) {
       snprintf(out, n, "generic_fold_kernel<%s,%d,%s>", arithName(k.arith), k.es / arithBytes(k.arith),
                k.kind == K_GENERIC_FOLD_TAKE ? "true" : "false");
       break;
+    case K_ROWS_WALL:
+      snprintf(out, n, "rows_wall_kernel<%s,%d,%d,%s>", arithName(k.arith), k.vec, s, k.neg ? "true" : "false");
+      break;
+    case K_GENERIC_WALL: snprintf(out, n, "generic_wall_kernel<%s,%d,%s>", arithName(k.arith), k.es, k.neg ? "true" : "false"); break;
     case K_ROWS_FIELDS: snprintf(out, n, "rows_fields_kernel<%d,%d>", k.vec, s); break;
     case K_GENERIC_FIELDS: snprintf(out, n, "generic_fields_kernel<%d>", k.es); break;
     case K_TRANSPOSE_FIELDS:
@@ -623,7 +657,27 @@ FillPattern fillPatternOf(const void* value, int es, const void* cell) {
 
 long long g_data_launches = 0;
 
-void launchBatch(const KernelChoice& k, const Batch& b, const void* fill_value, unsigned int blocks, hipStream_t stream) {
+// The addend table of a launch of wall-moves: row i for move i of the Batch, in DESTINATION order along the mirrored dim.  The high
+// side's ghost layer k is destination index k; the low side's is extent - 1 - k, so the low side is reversed here and the kernels
+// index by destination layer.  Every entry is the element replicated to 16 bytes.
+WallTable wallTableOf(const Launch& l, const Move3D* moves, const WallAddends* addends) {
+  if (!addends) CD_INTERNAL_ERROR("wall-moves without the call's addends");
+  const int es = l.k.es;
+  WallTable t;
+  std::memset(&t, 0, sizeof(t));
+  for (int i = 0; i < l.b.n; ++i) {
+    const Move3D& m = moves[l.index[i]];
+    const int layers = wallLayers(m), side = m.affine - 1;
+    if (layers < 0 || side < 0 || side > 1) CD_INTERNAL_ERROR("a launch of wall-moves holds a move that is none");
+    wallTableRow(*addends, side, layers, es, reinterpret_cast<unsigned char*>(t.w[i]));
+  }
+  return t;
+}
+
+void launchBatch(const Launch& l, const Move3D* moves, const void* fill_value, const WallAddends* addends, hipStream_t stream) {
+  const KernelChoice& k = l.k;
+  const Batch& b = l.b;
+  const unsigned int blocks = l.blocks;
   spellKernelName(k);
   ++g_data_launches;
   switch (k.kind) {
@@ -654,6 +708,8 @@ void launchBatch(const KernelChoice& k, const Batch& b, const void* fill_value, 
     case K_GENERIC_FOLD:
     case K_ROWS_FOLD_TAKE:
     case K_GENERIC_FOLD_TAKE: launchFoldBatch(k, b, blocks, stream); break;
+    case K_ROWS_WALL:
+    case K_GENERIC_WALL: launchWallBatch(k, b, wallTableOf(l, moves, addends), blocks, stream); break;
     case K_ROWS_FIELDS:
     case K_GENERIC_FIELDS:
     case K_TRANSPOSE_FIELDS:
@@ -697,6 +753,16 @@ int residencyPadBytes(const KernelChoice& k, const Batch& b) {
   for (int i = 0; i < b.n; ++i)  // far-strided destination, runs of tiles (offerRunWalk)
     if (b.p0[i] <= 1 || !(b.p1[i] & kWalkJFirst) || (b.p1[i] & kWalkRunOverPlanes)) return 0;
   return f64 ? 16 << 10 : 23 << 10;  // 32 + 16 KiB: three per CU; 16.5 + 23 KiB: four
+}
+
+void wallTableRow(const WallAddends& addends, int side, int layers, int es, unsigned char out[kern::kMaxWallHalo * 16]) {
+  if (side < 0 || side > 1 || layers < 0 || layers > kMaxWallHalo || (es != 2 && es != 4 && es != 8 && es != 16))
+    CD_INTERNAL_ERROR("addend table row out of range");
+  std::memset(out, 0, kMaxWallHalo * 16);
+  for (int j = 0; j < layers; ++j) {
+    const unsigned char* v = addends.v[side][side == 0 ? layers - 1 - j : j];
+    for (int k = 0; k < 16; ++k) out[16 * j + k] = v[k % es];
+  }
 }
 
 const char* lastKernelName() { return g_last_kernel; }
@@ -781,9 +847,9 @@ std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3]
 
 void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
                  const KernelTuning* tuning, KernelStats* stats, void* const* dst_base_override, ArithType arith,
-                 const void* fill_value) {
+                 const void* fill_value, const WallAddends* wall_addends) {
   for (const Launch& l : planLaunches(moves, n, bufs, es, tuning, dst_base_override, arith)) {
-    launchBatch(l.k, l.b, fill_value, l.blocks, stream);
+    launchBatch(l, moves, fill_value, wall_addends, stream);
     if (stats) {
       stats->launches[l.cls] += 1;
       stats->elements[l.cls] += l.elements;
@@ -830,9 +896,9 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     if (mirrored) {
       // the moves of kernels_field_mirror.hip: reflect- or fold-moves between cells of the fields' own buffers; their signs travel
       // in fields_neg, never in the move
-      if (!in.reflect || in.negate || in.fill || in.dst_row_pitch != 0 || in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK)
+      if (!in.reflect || in.negate || in.affine != 0 || in.fill || in.dst_row_pitch != 0 || in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK)
         CD_INTERNAL_ERROR("mirrored field-moves reflect or fold exactly their cells of the fields' buffers, unsigned");
-    } else if (in.fill || in.reflect || in.negate || in.dst_row_pitch != 0) {
+    } else if (in.fill || in.reflect || in.negate || in.affine != 0 || in.dst_row_pitch != 0) {
       CD_INTERNAL_ERROR("field-moves copy, add or take exactly their cells");
     }
     if (add && in.dst_buf == BUF_WORK) CD_INTERNAL_ERROR("adding field-moves never add onto the workspace");

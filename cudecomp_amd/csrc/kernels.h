@@ -43,10 +43,19 @@ struct KernelTuning {
 // Fold-moves (Move3D::reflect with Move3D::add; kernels_fold.hip) add the source, running backwards along one dim, onto disjoint
 // cells of the same local buffer, with its sign bits flipped first under Move3D::negate, and clear it under Move3D::take; they
 // always need `arith`.
+// Wall-moves (Move3D::affine on a reflect-move; kernels_wall.hip) add the addend of the destination's layer along the mirrored dim
+// after the optional sign flip, in `arith`, which they always need.  `wall_addends` holds the converted addends of the call per
+// side and ghost layer (kernels_batch.h WallAddends), read before the call returns; a move names its side.  At most
+// kern::kMaxWallHalo layers; anything else on such a move is an internal error before any launch.
 void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
                  const KernelTuning* tuning = nullptr, KernelStats* stats = nullptr,
                  void* const* dst_base_override = nullptr,  // per-move destination base (remote buffers)
-                 ArithType arith = ARITH_NONE, const void* fill_value = nullptr);
+                 ArithType arith = ARITH_NONE, const void* fill_value = nullptr, const WallAddends* wall_addends = nullptr);
+
+// One row of the addend table a launch of wall-moves carries (kern::WallTable): `layers` entries of 16 bytes in DESTINATION order
+// along the mirrored dim -- the high side's (side 1) ghost layer k at index k, the low side's (side 0) at layers - 1 - k -- each the
+// `es`-byte element replicated; the rest zero.  Pure host code.
+void wallTableRow(const WallAddends& addends, int side, int layers, int es, unsigned char out[kern::kMaxWallHalo * 16]);
 
 // One kernel launch of a list of moves: what runs, its descriptor, its workgroups (the padded count of an interleaved launch)
 // and which entries of the list it serves.

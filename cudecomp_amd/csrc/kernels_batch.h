@@ -1,8 +1,8 @@
 // kernels_batch.h -- what csrc/kernels.cc (host: classification, batching) and the kernel code objects share: the record of a
 // kernel choice (KernelChoice), the launch descriptor (Batch) and the launchers.  The code objects the classifier dispatches
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
-// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip;
-// kernels_rotate.hip and sync.hip are launched by the executor (and compiled as one unit, kernels_executor.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
+// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip, kernels_wall.hip;
+// kernels_rotate.hip and sync.hip are launched by the executor (and compiled as one unit, kernels_executor.hip; kernels_fill.hip and kernels_reflect.hip likewise as kernels_edge.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
 // halo phases and transposes), kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) and
 // kernels_field_mirror.hip (the same lists mirrored, with a sign per field: multi-field wall halos) are reached through
 // launchFieldMoveList (kernels.h).  Seventeen code objects in all.  The row and element-wise kernels of all of
@@ -32,6 +32,7 @@ constexpr int kMaxBatch = 8;
 constexpr int kThreads = 256;
 constexpr int kRowsUnroll = 4;
 constexpr long long kStreamBytes = 32ll << 20;  // moves at least this large use non-temporal access
+constexpr int kMaxWallHalo = 8;                 // layers a wall-move's addend table holds (CUDECOMP_AMD_MAX_WALL_HALO)
 
 struct DevMove {
   const char* src;
@@ -63,6 +64,8 @@ struct Batch {
   //   takes                      p0 as for rows / element-wise; p1 unused
   //   reflections                p0 as for rows / element-wise; p1 unused
   //   folds                      p0 as for rows / element-wise; p1 unused
+  //   wall-moves                 p0 as for rows / element-wise; p1 = the entry of e[] that is the mirrored dim, whose index is the
+  //                              destination layer (rows: 1 the row, 2 the plane); -1: the mirrored dim is one cell thick, layer 0
   int p0[kMaxBatch];
   int p1[kMaxBatch];
   unsigned int first_block[kMaxBatch + 1];
@@ -70,6 +73,15 @@ struct Batch {
   unsigned int t1[kMaxBatch];             // tiles along dim 1
   DevMove m[kMaxBatch];
 };
+
+// The addends of a launch of wall-moves (kernels_wall.hip): a kernel argument of its own beside the Batch, which stays as it is.
+// Row i belongs to move i of the Batch; entry j is the addend of DESTINATION layer j along the mirrored dim -- the element, already
+// converted to the call's type, replicated to 16 bytes.  Lanes hold whole elements and start on an element's boundary, so the low
+// VB bytes of an entry serve every lane.
+struct WallTable {
+  unsigned int w[kMaxBatch][kMaxWallHalo][4];
+};
+static_assert(sizeof(Batch) + sizeof(WallTable) + 16 <= 2048, "Batch, sign mask and addend table stay well under the 4 KB of kernel arguments");
 
 // ---- lists of field-moves: up to kMaxBatch moves, each for up to kMaxFields (input, output) pairs of buffers, in ONE launch
 // (kernels_field_transpose.hip; multi-field halo updates and transposes, include/cudecomp_halo_fields.h and
@@ -145,7 +157,9 @@ enum KernelKind {
   K_ROWS_FIELDS_FOLD,         // rows_fields_fold_kernel (dst += +-src per field, the source backwards) = 33
   K_GENERIC_FIELDS_FOLD,      // generic_fields_fold_kernel = 34
   K_ROWS_FIELDS_FOLD_TAKE,    // rows_fields_fold_kernel with TAKE (... ; src = 0) = 35
-  K_GENERIC_FIELDS_FOLD_TAKE  // generic_fields_fold_kernel with TAKE = 36
+  K_GENERIC_FIELDS_FOLD_TAKE, // generic_fields_fold_kernel with TAKE = 36
+  K_ROWS_WALL,                // rows_wall_kernel (dst = +-src + addend of the destination layer, the source backwards along the row or plane index) = 37
+  K_GENERIC_WALL              // generic_wall_kernel = 38
 };
 struct KernelChoice {
   KernelKind kind;
@@ -155,12 +169,12 @@ struct KernelChoice {
   int access;       // copies: 0 default caching, 2 non-temporal loads + stores, 3 non-temporal loads + remote (system-scope
                     // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads;
                     // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it);
-                    // reflections: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores;
+                    // reflections and wall-moves: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores;
                     // field-moves: 0, 1 non-temporal loads and stores; transpose_fields_kernel: 0, 2; adding / taking
                     // field-moves: as additions / takes; mirrored field-moves: as reflections / folds
-  ArithType arith;  // additions, folds, reflections that flip the sign bits, mirrored field-moves (whatever their signs): the real
-                    // type the elements consist of; ARITH_NONE otherwise
-  bool neg;         // folds: the sign bits of the source are flipped before the addition (one sign mask per launch)
+  ArithType arith;  // additions, folds, wall-moves, reflections that flip the sign bits, mirrored field-moves (whatever their signs):
+                    // the real type the elements consist of; ARITH_NONE otherwise
+  bool neg;         // folds, wall-moves: the sign bits of the source are flipped before the addition (one sign mask per launch)
   bool guard;       // transpose_fields_kernel: some tile of the move ends inside the move (the GUARD template argument); false otherwise
   bool operator==(const KernelChoice& o) const {
     return kind == o.kind && es == o.es && vec == o.vec && ti == o.ti && tj == o.tj && access == o.access && arith == o.arith &&
@@ -234,12 +248,14 @@ constexpr KindTraits kKindTraits[] = {
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_FOLD
     {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FIELDS_FOLD_TAKE
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_FOLD_TAKE
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_WALL
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_WALL
 };
-static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_FIELDS_FOLD_TAKE + 1, "one row per KernelKind");
+static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_WALL + 1, "one row per KernelKind");
 
 // the row of a kind; a value outside the enum is an internal error, never a read past the table
 inline const KindTraits& kindTraits(KernelKind kind) {
-  if (kind < K_ROWS || kind > K_GENERIC_FIELDS_FOLD_TAKE) CD_INTERNAL_ERROR("kernel kind out of range");
+  if (kind < K_ROWS || kind > K_GENERIC_WALL) CD_INTERNAL_ERROR("kernel kind out of range");
   return kKindTraits[kind];
 }
 inline MoveClass classOf(KernelKind kind) { return kindTraits(kind).cls; }
@@ -304,6 +320,17 @@ void launchReflectBatch(const KernelChoice& k, const kern::Batch& b, unsigned in
 // signed strides in elements.  k.arith: the real type of the addition; k.neg: the sign mask of that type travels as a 16-byte
 // kernel argument of its own, all zero otherwise.  Local buffers only.
 void launchFoldBatch(const KernelChoice& k, const kern::Batch& b, unsigned int blocks, hipStream_t stream);
+// kernels_wall.hip: wall-moves (Move3D::affine: dst = src + a or dst = -src + a with the source running backwards along one dim, a the
+// addend of the destination's layer along that dim).  The Batch of the reflections (rows with SIGNED byte strides, generic with
+// signed strides in elements) with Batch::p1 naming the mirrored entry of e[]; k.arith: the real type of the addition, always;
+// k.neg: the sign bits of the source are flipped first.  `table`: the addends in destination order (kernels.cc wallTableOf reverses
+// the low side, so the kernels pay nothing for the mirror).  Lanes never narrower than one element.  Local buffers only.
+// WallAddends is what a caller of launchMoves hands over: per side (0 low, 1 high) the converted element of every ghost layer k,
+// counted from the wall outward, its `es` bytes at the start of a 16-byte slot.
+struct WallAddends {
+  unsigned char v[2][kern::kMaxWallHalo][16];
+};
+void launchWallBatch(const KernelChoice& k, const kern::Batch& b, const kern::WallTable& table, unsigned int blocks, hipStream_t stream);
 // kernels_field_transpose.hip: lists of field-moves (plain copies of exactly the cells of the moves; local buffers only)
 void launchFieldMoveBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, unsigned int blocks, hipStream_t stream);
 // kernels_field_accumulate.hip: lists of field-moves that add (k.arith: the real type), take or both; local buffers only

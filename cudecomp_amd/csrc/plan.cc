@@ -524,8 +524,10 @@ HaloPlan buildHaloFillPlan(const GridShape& g, int rank, int axis, int dim, cons
   return p;
 }
 
-HaloPlan buildHaloReflectPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
-                              const int32_t* pad, int centering, bool negate, bool self_exchange) {
+// the reflection's plan for the sides of `sides` (bit 0 low, bit 1 high): the reflection itself takes both, the wall values those
+// the caller names.  A side left out is neither written nor checked.
+static HaloPlan reflectSides(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                             const int32_t* pad, int centering, bool negate, int sides, bool self_exchange) {
   const HaloPlan u = buildHaloPlan(g, rank, axis, dim, halo, periods, pad, false, self_exchange);  // (its refusals, its neighbours)
   if (centering != 0 && centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
   HaloPlan p;
@@ -538,7 +540,8 @@ HaloPlan buildHaloReflectPlan(const GridShape& g, int rank, int axis, int dim, c
   p.neighbor[0] = u.neighbor[0];
   p.neighbor[1] = u.neighbor[1];
   const i64 he = halo[dim];
-  if (he == 0 || (p.neighbor[0] != -1 && p.neighbor[1] != -1)) return p;
+  const bool writes[2] = {p.neighbor[0] == -1 && (sides & 1) != 0, p.neighbor[1] == -1 && (sides & 2) != 0};
+  if (he == 0 || (!writes[0] && !writes[1])) return p;
 
   const auto pidx = gridIndexOfRank(g, rank);
   const Pencil h = makePencil(g, pidx, axis, halo, nullptr);
@@ -561,9 +564,47 @@ HaloPlan buildHaloReflectPlan(const GridShape& g, int rank, int axis, int dim, c
     m.negate = negate;
     return m;
   };
-  if (p.neighbor[0] == -1) p.pre.push_back(mirroring(2 * he - 1 + c, 0, 0));
-  if (p.neighbor[1] == -1) p.pre.push_back(mirroring(n - he - 1 - c, n - he, 1));
+  if (writes[0]) p.pre.push_back(mirroring(2 * he - 1 + c, 0, 0));
+  if (writes[1]) p.pre.push_back(mirroring(n - he - 1 - c, n - he, 1));
   p.kind = HaloPlan::SELF_PERIODIC;
+  return p;
+}
+
+HaloPlan buildHaloReflectPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                              const int32_t* pad, int centering, bool negate, bool self_exchange) {
+  return reflectSides(g, rank, axis, dim, halo, periods, pad, centering, negate, 3, self_exchange);
+}
+
+int wallValueRefusal(int sides, bool has_low, bool has_high, i64 halo_dim) {
+  if (sides < 1 || sides > 3) return 1;
+  if (((sides & 1) && !has_low) || ((sides & 2) && !has_high)) return 2;
+  return halo_dim > kMaxWallLayers ? 3 : 0;
+}
+
+void refuseWallValues(int refusal) {
+  if (refusal == 1) CD_INVALID_USAGE("sides argument must be 1, 2 or 3: the low halo, the high halo or both");
+  if (refusal == 2) CD_INVALID_USAGE("the value array of a side named in sides cannot be null");
+  if (refusal == 3) CD_NOT_SUPPORTED("halo_extents[dim] is wider than CUDECOMP_AMD_MAX_WALL_HALO");
+  CD_INTERNAL_ERROR("no wall-value refusal to make");
+}
+
+HaloPlan buildHaloWallValuesPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                 const int32_t* pad, int centering, bool negate, int sides, bool self_exchange) {
+  if (sides < 1 || sides > 3) {  // (callers check first, in the contract's place; here after the reflection's own argument checks)
+    reflectSides(g, rank, axis, dim, halo, periods, pad, centering, negate, 0, self_exchange);
+    refuseWallValues(1);
+  }
+  if (halo[dim] > kMaxWallLayers) {
+    reflectSides(g, rank, axis, dim, halo, periods, pad, centering, negate, 0, self_exchange);
+    refuseWallValues(3);
+  }
+  HaloPlan p = reflectSides(g, rank, axis, dim, halo, periods, pad, centering, negate, sides, self_exchange);
+  p.op.kind = HaloOp::WALL_VALUES;
+  p.op.sides = sides;
+  for (Move3D& m : p.pre) {
+    if (!m.reflect || (m.peer != 0 && m.peer != 1)) CD_INTERNAL_ERROR("a wall-value plan whose moves are not the reflection's");
+    m.affine = m.peer + 1;  // (blockMove's `peer` of a reflect-move is its side)
+  }
   return p;
 }
 
@@ -671,6 +712,7 @@ HaloPlan buildHaloOpPlan(const GridShape& g, int rank, int axis, int dim, const 
     case HaloOp::FILL: return buildHaloFillPlan(g, rank, axis, dim, halo, periods, pad, force_packed, self_exchange);
     case HaloOp::REFLECT: return buildHaloReflectPlan(g, rank, axis, dim, halo, periods, pad, op.centering, op.negate, self_exchange);
     case HaloOp::FOLD: return buildHaloFoldPlan(g, rank, axis, dim, halo, periods, pad, op.centering, op.negate, op.clear, self_exchange);
+    case HaloOp::WALL_VALUES: return buildHaloWallValuesPlan(g, rank, axis, dim, halo, periods, pad, op.centering, op.negate, op.sides, self_exchange);
   }
   CD_INTERNAL_ERROR("unknown halo operation");
 }

@@ -64,6 +64,13 @@ struct Move3D {
   // reflect- and fold-moves only: the sign bit of every real component is inverted on the way (one bit per real, two per complex
   // element); nothing else about the bytes changes.  A fold-move flips the bits first and adds then.
   bool negate = false;
+  // reflect-moves of cudecompAmdSetWallHalos* only (buildHaloWallValuesPlan): the move adds the call's per-layer addend,
+  // dst = +-src + a[layer], `layer` the destination's index along the mirrored dim.  1: the addends of the call's low side (ghost
+  // layer k, counted from the wall outward, is destination index extent - 1 - k), 2: those of the high side (destination index k);
+  // 0: none.  The addends travel with the call, not with the move (kernels.h launchMoves).  Such a move is a reflect-move with or
+  // without `negate` and nothing else: with dst_row_pitch, fill, take, add or a remote destination it is an internal error before
+  // any launch, and so is a mirrored dim thicker than the addend table (kern::kMaxWallHalo).
+  int affine = 0;
 
   i64 elements() const { return extent[0] * extent[1] * extent[2]; }
 };
@@ -190,13 +197,15 @@ RelayPlan buildRelayPlan(const GridShape& g, int nranks, int rank, TransposeOp o
 // What a halo call is: the operation and the arguments that change its plan.  Every builder below writes the record of its plan;
 // buildHaloOpPlan goes the other way.  Ordered, so that it can be part of the key of the plan cache (internal.h).
 struct HaloOp {
-  enum Kind { UPDATE, ACCUMULATE, FILL, REFLECT, FOLD } kind = UPDATE;
+  enum Kind { UPDATE, ACCUMULATE, FILL, REFLECT, FOLD, WALL_VALUES } kind = UPDATE;
   bool clear = false;  // ACCUMULATE, FOLD: the ghost cells read are cleared
-  int centering = 0;   // REFLECT, FOLD
-  bool negate = false; // REFLECT, FOLD of ONE field: parity -1 (several fields: false; their parities travel with the call)
-  int n_fields = 1;    // UPDATE, ACCUMULATE, REFLECT, FOLD (1 for FILL)
+  int centering = 0;   // REFLECT, FOLD, WALL_VALUES
+  bool negate = false; // REFLECT, FOLD of ONE field, WALL_VALUES: parity -1 (several fields: false; their parities travel with the call)
+  int n_fields = 1;    // UPDATE, ACCUMULATE, REFLECT, FOLD (1 for FILL and WALL_VALUES)
+  int sides = 3;       // WALL_VALUES: bit 0 the low halo, bit 1 the high halo (it changes the moves; the addends do not and are
+                       // no part of the record: calls that differ only in them share a plan)
   bool operator<(const HaloOp& o) const {
-    return std::tie(kind, clear, centering, negate, n_fields) < std::tie(o.kind, o.clear, o.centering, o.negate, o.n_fields);
+    return std::tie(kind, clear, centering, negate, n_fields, sides) < std::tie(o.kind, o.clear, o.centering, o.negate, o.n_fields, o.sides);
   }
 };
 
@@ -258,6 +267,20 @@ HaloPlan buildHaloFillPlan(const GridShape& g, int rank, int axis, int dim, cons
 HaloPlan buildHaloReflectPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
                               const int32_t* pad, int centering, bool negate, bool self_exchange = false);
 
+// Wall VALUES along `dim` (include/cudecomp_halo_wall_values.h has the contract): the reflection with one addend per ghost layer and
+// side, cell = s * mirror + a.  The moves are buildHaloReflectPlan's for the sides kept (`sides`: bit 0 low, bit 1 high, 1 .. 3) --
+// same cells, same `reflect` and `negate` -- and carry Move3D::affine = 1 (low) / 2 (high).  The refusals of buildHaloPlan first, then
+// the centering, then (wallValueRefusal below, for callers that hold the arguments) sides, value arrays and width; the reflection's
+// refusal h + c > n - 2h only for a side that would be written.  Kinds: NONE or SELF_PERIODIC ("local").
+HaloPlan buildHaloWallValuesPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                 const int32_t* pad, int centering, bool negate, int sides, bool self_exchange = false);
+// The three checks of the wall values that follow the centering check, in the contract's order: 0 fine, 1 `sides` outside 1 .. 3,
+// 2 a NULL value array of a side named in `sides`, 3 halo_extents[dim] beyond the addend table.  refuseWallValues throws what the
+// contract states for 1 .. 3 (INVALID_USAGE, INVALID_USAGE, NOT_SUPPORTED).
+constexpr int kMaxWallLayers = 8;  // CUDECOMP_AMD_MAX_WALL_HALO and kern::kMaxWallHalo (halo.cc asserts that the three are one number)
+int wallValueRefusal(int sides, bool has_low, bool has_high, i64 halo_dim);
+[[noreturn]] void refuseWallValues(int refusal);
+
 // Halo FOLDING along `dim` (include/cudecomp_halo_fold.h has the contract) -- the transpose of the reflection: the ghost cells the
 // reflection along `dim` writes are ADDED to the interior cells it reads them from: low side cell(h+k+c) += s * cell(h-1-k), then
 // high side cell(n-h-1-k-c) += s * cell(n-h+k), k in [0, h).  Refusals, neighbours and sides are buildHaloReflectPlan's, which is
@@ -307,7 +330,7 @@ HaloPlan buildHaloWallFieldsPlan(const GridShape& g, int rank, int axis, int dim
 
 // The plan of the halo call `op`, by the builder of its family: UPDATE buildHaloFieldsPlan, ACCUMULATE buildHaloAccumulateFieldsPlan
 // (one field: the single plans, unchanged), REFLECT and FOLD their own for one field and buildHaloWallFieldsPlan for several, FILL
-// its own.  `force_packed` reaches the builders that take it.
+// and WALL_VALUES their own.  `force_packed` reaches the builders that take it.
 HaloPlan buildHaloOpPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods, const int32_t* pad,
                          const HaloOp& op, bool force_packed, bool self_exchange = false);
 

@@ -588,6 +588,61 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompAmdReflectHalosZ_C
 
+    ! cudecomp_halo_wall_values.h: wall values (the reflection with one addend per ghost layer and side)
+    function cudecompAmdSetWallHalosX_C(handle, grid_desc, input, dtype, parity, centering, sides, values_low, values_high, &
+                                        halo_extents, halo_periods, dim, padding, stream) &
+      bind(C, name="cudecompAmdSetWallHalosX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      integer(c_int32_t), value :: parity, centering, sides
+      type(c_ptr), value :: values_low, values_high  ! host arrays of doubles (NULL for a side that `sides` does not name)
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdSetWallHalosX_C
+
+    function cudecompAmdSetWallHalosY_C(handle, grid_desc, input, dtype, parity, centering, sides, values_low, values_high, &
+                                        halo_extents, halo_periods, dim, padding, stream) &
+      bind(C, name="cudecompAmdSetWallHalosY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      integer(c_int32_t), value :: parity, centering, sides
+      type(c_ptr), value :: values_low, values_high  ! host arrays of doubles (NULL for a side that `sides` does not name)
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdSetWallHalosY_C
+
+    function cudecompAmdSetWallHalosZ_C(handle, grid_desc, input, dtype, parity, centering, sides, values_low, values_high, &
+                                        halo_extents, halo_periods, dim, padding, stream) &
+      bind(C, name="cudecompAmdSetWallHalosZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      integer(c_int32_t), value :: parity, centering, sides
+      type(c_ptr), value :: values_low, values_high  ! host arrays of doubles (NULL for a side that `sides` does not name)
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdSetWallHalosZ_C
+
     ! cudecomp_halo_fold.h: halo folding (the ghost cells the reflection writes, summed into their mirror images)
     function cudecompAmdFoldHalosX_C(handle, grid_desc, input, dtype, parity, centering, clear, halo_extents, halo_periods, dim, &
                                         padding, stream) bind(C, name="cudecompAmdFoldHalosX") result(res)
@@ -1581,6 +1636,101 @@ contains
     res = cudecompAmdReflectHalosZ_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
                                       int(centering, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
   end function cudecompAmdReflectHalosZ
+
+  ! ---- wall values (cudecomp_halo_wall_values.h): the arguments of the reflection with `sides` and the two host arrays of
+  ! addends after the centering ----
+  function cudecompAmdSetWallHalosX(handle, grid_desc, input, dtype, parity, centering, sides, values_low, values_high, &
+                                    halo_extents, halo_periods, dim, padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: parity     ! +1: even mirror; -1: odd mirror (sign bits flipped)
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: sides      ! 1: the low halo; 2: the high halo; 3: both
+    ! halo_extents(dim) doubles per side (complex types: twice as many, re and im interleaved), layer 1 next to the wall; host
+    ! arrays, read before the call returns; the one of a side that `sides` does not name may be left out
+    real(c_double), optional, target :: values_low(*), values_high(*)
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    type(c_ptr) :: lo, hi
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    lo = c_null_ptr
+    hi = c_null_ptr
+    if (present(values_low)) lo = c_loc(values_low)
+    if (present(values_high)) hi = c_loc(values_high)
+    res = cudecompAmdSetWallHalosX_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
+                                      int(centering, c_int32_t), int(sides, c_int32_t), lo, hi, h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdSetWallHalosX
+
+  function cudecompAmdSetWallHalosY(handle, grid_desc, input, dtype, parity, centering, sides, values_low, values_high, &
+                                    halo_extents, halo_periods, dim, padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: parity     ! +1: even mirror; -1: odd mirror (sign bits flipped)
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: sides      ! 1: the low halo; 2: the high halo; 3: both
+    ! halo_extents(dim) doubles per side (complex types: twice as many, re and im interleaved), layer 1 next to the wall; host
+    ! arrays, read before the call returns; the one of a side that `sides` does not name may be left out
+    real(c_double), optional, target :: values_low(*), values_high(*)
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    type(c_ptr) :: lo, hi
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    lo = c_null_ptr
+    hi = c_null_ptr
+    if (present(values_low)) lo = c_loc(values_low)
+    if (present(values_high)) hi = c_loc(values_high)
+    res = cudecompAmdSetWallHalosY_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
+                                      int(centering, c_int32_t), int(sides, c_int32_t), lo, hi, h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdSetWallHalosY
+
+  function cudecompAmdSetWallHalosZ(handle, grid_desc, input, dtype, parity, centering, sides, values_low, values_high, &
+                                    halo_extents, halo_periods, dim, padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: parity     ! +1: even mirror; -1: odd mirror (sign bits flipped)
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: sides      ! 1: the low halo; 2: the high halo; 3: both
+    ! halo_extents(dim) doubles per side (complex types: twice as many, re and im interleaved), layer 1 next to the wall; host
+    ! arrays, read before the call returns; the one of a side that `sides` does not name may be left out
+    real(c_double), optional, target :: values_low(*), values_high(*)
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    type(c_ptr) :: lo, hi
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    lo = c_null_ptr
+    hi = c_null_ptr
+    if (present(values_low)) lo = c_loc(values_low)
+    if (present(values_high)) hi = c_loc(values_high)
+    res = cudecompAmdSetWallHalosZ_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
+                                      int(centering, c_int32_t), int(sides, c_int32_t), lo, hi, h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdSetWallHalosZ
 
   ! ---- halo folding (cudecomp_halo_fold.h): the arguments of the reflection with `clear` after the centering ----
   function cudecompAmdFoldHalosX(handle, grid_desc, input, dtype, parity, centering, clear, halo_extents, halo_periods, dim, &

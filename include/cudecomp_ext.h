@@ -70,7 +70,9 @@ typedef struct {
    * bit 13: the moves flip the sign bits (parity -1), and nothing else; every move of `pre` is a reflect-move (its source stride
    * along the mirrored dim is negative).  Fold plans (cudecompExtPlanHaloFold): bit 14 set, bit 13: the moves flip the sign bits,
    * bit 1: the two destination ranges overlap (one launch per side, in order), and with `clear` bit 9 and bits 10, 11 as above;
-   * every move of `pre` is a fold-move (a reflect-move that adds). */
+   * every move of `pre` is a fold-move (a reflect-move that adds).  Wall-value plans (cudecompExtPlanHaloWallValues): bit 15 set, bit
+   * 13: the moves flip the sign bits, bits 16, 17: the call's `sides`; every move of `pre` is a reflect-move that adds the addends of
+   * the side its `peer` names (0 low, 1 high). */
   int32_t reserved;
   int64_t face_elements, send_off[2], recv_off[2];
   cudecompExtMove_t pre[2], post[2];
@@ -164,6 +166,23 @@ cudecompResult_t cudecompExtPlanHaloFold(const cudecompExtGridSpec_t* grid, int3
                                          const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
                                          const int32_t padding[], int32_t centering, int32_t negate, int32_t clear,
                                          cudecompExtHaloPlan_t* plan);
+
+/* The plan cudecompAmdSetWallHalos{X,Y,Z} (cudecomp_halo_wall_values.h) would run on `rank`, AND the addend table its launch would
+ * carry; needs no device.  The plan: kind 0 (nothing to do) or 1 (local); `pre` holds the reflect-moves of
+ * cudecompExtPlanHaloReflect for the sides kept -- the same cells, the same source strides -- each with `peer` = its side (0 low, 1
+ * high); n_post = 0; cudecompExtHaloPlan_t::reserved as described there.  table: 2 x CUDECOMP_AMD_MAX_WALL_HALO x 16 bytes, the low
+ * side's row then the high side's: entry j of a row is the addend of DESTINATION index j along `dim` inside the slab -- the high
+ * side's ghost layer k at j = k, the low side's at j = h - 1 - k (the low side is reversed, so that the kernels index by destination
+ * layer) -- as the element of `dtype` converted from the doubles (round to nearest even directly from the double, overflow to
+ * infinity) and replicated to 16 bytes; entries at or beyond h and the row of a side not named in `sides` are zero bytes.  The
+ * checks are the call's, in its order: those of cudecompExtPlanHalo and an unknown dtype, then INVALID_USAGE for parity, centering,
+ * sides, a NULL array of a named side, NOT_SUPPORTED for halo_extents[dim] > CUDECOMP_AMD_MAX_WALL_HALO, then INVALID_USAGE for a
+ * side to write whose mirror reaches beyond the rank's interior. */
+cudecompResult_t cudecompExtPlanHaloWallValues(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
+                                               const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
+                                               const int32_t padding[], cudecompDataType_t dtype, int32_t parity, int32_t centering,
+                                               int32_t sides, const double values_low[], const double values_high[],
+                                               cudecompExtHaloPlan_t* plan, uint8_t* table);
 
 /* The plan cudecompAmdUpdateFieldHalos{X,Y,Z} (cudecomp_halo_fields.h) would run on `rank` for n_fields fields (csrc/plan.h
  * buildHaloFieldsPlan).  kind as in cudecompExtHaloPlan_t; never 3 for n_fields >= 2, whatever force_packed says (n_fields == 1:
@@ -339,6 +358,17 @@ cudecompResult_t cudecompExtFold3D(const void* src, void* dst, cudecompDataType_
                                    const int64_t extent[3], const int64_t ss[3], const int64_t ds[3], int32_t force,
                                    int32_t* kernel_class, hipStream_t stream);
 
+/* One wall-value move on the GPU (kernels_wall.hip): dst[k0*ds[0] + k1*ds[1] + k2*ds[2]] = +-src[k0*ss[0] + k1*ss[1] + k2*ss[2]] +
+ * a[layer] in the arithmetic of `dtype`, 0 <= k_i < extent[i] (strides in elements of `dtype`), where exactly one entry of ss is
+ * negative: the mirrored dim, of at most CUDECOMP_AMD_MAX_WALL_HALO cells, src pointing at the source cell of its index 0.
+ * negate != 0: the sign bit of every real of the source is inverted before the addition.  addends: extent[mirrored dim] elements
+ * of `dtype` on the host, entry k for ghost layer k counted from the wall outward: side 1 (high) adds entry k at destination index
+ * k of the mirrored dim, side 0 (low) at destination index extent - 1 - k.  src and dst are disjoint cells, usually of one
+ * buffer.  force: the bits of cudecompExtReflect3D.  *kernel_class (optional): 0 rows, 2 generic. */
+cudecompResult_t cudecompExtWall3D(const void* src, void* dst, cudecompDataType_t dtype, int32_t negate, int32_t side,
+                                   const void* addends, const int64_t extent[3], const int64_t ss[3], const int64_t ds[3],
+                                   int32_t force, int32_t* kernel_class, hipStream_t stream);
+
 /* How the kernel layer WOULD execute a 3-D block move between buffers at the given addresses (no launch; works without a
  * GPU): out[10] = {class (0 rows, 1 LDS transpose, 2 generic), kernel variant, tile_i, tile_j, tiles_i, tiles_j, batch extent,
  * run length of the tile walk, walk bits (1 XCD-contiguous, 2 j first, 4 runs over batch planes), access mode}.  flags: 2 =
@@ -364,11 +394,16 @@ cudecompResult_t cudecompExtDescribeMove(uint64_t src_address, uint64_t dst_addr
  * 0; exactly one per move -- an entry without one is CUDECOMP_RESULT_INVALID_USAGE, two are an internal error); 6: mirror copies with the sign bit of every real of `dtype` inverted (its size must be `es`); 7: folds
  * (fold-moves: dst += src in the arithmetic of `dtype`, the source running backwards along the dim its negative `ss` entry names,
  * as for mode 5; an entry without one is CUDECOMP_RESULT_INVALID_USAGE); 8: folds with the sign bits of the source flipped
- * first; 9: folds that clear their source (src = 0 afterwards); 10: both.  The
+ * first; 9: folds that clear their source (src = 0 afterwards); 10: both; 11: wall values (reflect-moves that add the addend of the
+ * destination's layer along the mirrored dim, in the arithmetic of `dtype`, whose size must be `es`: the negative `ss` entry names
+ * the mirrored dim, of at most CUDECOMP_AMD_MAX_WALL_HALO cells, `peer` the side whose addends the move takes -- 0 low, ghost layer
+ * k at destination index extent - 1 - k; 1 high, at index k; any other value is CUDECOMP_RESULT_INVALID_USAGE -- and fill_value
+ * points at 2 x CUDECOMP_AMD_MAX_WALL_HALO elements of `es` bytes on the host, the low side's layers then the high side's); 12:
+ * wall values with the sign bits of the source flipped first.  The
  * sources of a list of mode 3, 4 or 7 ... 10 must be disjoint from all destinations and from each other.  flags: bits 1, 2, 4, 8, 64, 128
  * of cudecompExtMove3D, same meanings.  dst_bases (optional, n entries): moves[i] writes dst_bases[i] + dst_off instead, with
  * the system-scope stores of a peer's memory (access mode 3) -- the calling form of the one-sided transports; additions,
- * fills, both take modes, both mirror modes and the four fold modes refuse it (as they refuse a row_pitch) with CUDECOMP_RESULT_INTERNAL_ERROR before anything is launched.  launches[3] / elements[3] (optional): launches
+ * fills, both take modes, both mirror modes, the four fold modes and both wall-value modes refuse it (as they refuse a row_pitch) with CUDECOMP_RESULT_INTERNAL_ERROR before anything is launched.  launches[3] / elements[3] (optional): launches
  * and elements per class (0 rows, 1 LDS transpose, 2 generic); *n_launches (optional): launches in all.
  *
  * cudecompExtDescribeMoves answers which launches that call would make, without a device: the same arguments with addresses
@@ -377,7 +412,8 @@ cudecompResult_t cudecompExtDescribeMove(uint64_t src_address, uint64_t dst_addr
  * kind counts csrc/kernels_batch.h KernelKind: 0 rows, 1 rows shifted, 2 rows dense, 3 transpose, 4 transpose window, 5 transpose
  * lines, 6 transpose row lines, 7 generic, 8 rows addition, 9 generic addition, 10 rows fill, 11 generic fill, 12 rows take, 13 generic take, 14 rows addition
  * with take, 15 generic addition with take, 16 rows reflection, 17 generic reflection, 18 rows fold, 19 generic fold, 20 rows
- * fold with take, 21 generic fold with take. */
+ * fold with take, 21 generic fold with take, 37 rows wall values, 38 generic wall values (22 ... 36: the lists of field-moves,
+ * which this call never makes). */
 typedef struct {
   int32_t cls;                                      /* 0 rows, 1 LDS transpose, 2 generic */
   int32_t kind, es, vec, tile_i, tile_j, access, arith; /* csrc/kernels_batch.h KernelChoice */
