@@ -3,7 +3,9 @@ cudecompExtRunMoves (modes 0 ... 10), cudecompExtRunFieldMoves and cudecompExtRu
 every real type of the seven data types, every lane width that type reaches (16 / 8 / 4 / 2 bytes by the row length and, for
 2-byte elements, by a base at 2 mod 4), cached and streaming access, plain and TAKE, plain and sign-flipped, the mirror as the row
 index and as the plane index.  tests/test_gpu_kernel_names.py and the parity suites reach a sample of these; the kernels share one
-workgroup decode (csrc/kernels_walk.h), so every one of them is held to it here.
+workgroup decode (csrc/kernels_walk.h), so every one of them is held to it here.  (The remote-store forms of the copies --
+rows_kernel<VB,3>, rows_shifted_kernel<VB,3>, generic_kernel<ES,true> -- need no other process's memory: destination bases reach
+them on local buffers, tests/test_gpu_tiled_kernel_instantiations.py, beside every instantiation of the LDS-tiled kernels.)
 
 Shapes: the smallest at which every division of the row decode and both of its guards are live.
   wide rows   300 lane vectors x 9 rows x 3 planes, padded pitches on both sides: p0 = 8, two tile columns (the second partial),

@@ -6,8 +6,9 @@ kernel a single process can reach -- all four lane widths of the row copy, the s
 transposition in every element size and with the longer tiles, the window, lines and row-lines transpositions with cached and
 streaming access, the element-wise kernel, the two additions with a real and a complex type.
 
-Names with the remote-store policy (STREAM 3) need a destination in another process's memory and cannot be reached here; the
-multi-rank suites cover those launches by their results."""
+This table is a sample.  Every instantiation of the LDS-tiled kernels, and the names with the remote-store policy (STREAM 3:
+reached on local memory through cudecompExtRunMoves with destination bases), are launched by name in
+tests/test_gpu_tiled_kernel_instantiations.py; the multi-rank suites cover the remote launches by their results as well."""
 import numpy as np
 import pytest
 import torch
