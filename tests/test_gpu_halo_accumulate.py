@@ -26,6 +26,7 @@ import pytest
 
 import cudecomp_amd as cd
 from tests import accumulate_bodies as AB
+from tests import edge_arithmetic as EA
 from tests.mp import run_ranks
 
 pytestmark = pytest.mark.gpu
@@ -185,21 +186,9 @@ def _accumulate_bits(dtype, extent, ss, ds, so, do, a, b, modes=(0, 1, 2), seed=
     return ran
 
 
-def _pair_elements(dtype, a, b):
-    """reals -> elements: complex types take the real part from pair n and the imaginary part from pair 7 n + 5 (a bijection of
-    the 576 pairs: the two parts of an element come from different rows of the table, and both see every pair)"""
-    if AB.TYPES[dtype][1] == 1:
-        return a.reshape(-1, 1), b.reshape(-1, 1)
-    other = (np.arange(a.size) * 7 + 5) % a.size
-    return np.stack([a, a[other]], axis=1), np.stack([b, b[other]], axis=1)
-
-
-# (w, h, d) with w * h * d = 576 and the lane width each gives an element of 2 / 4 / 8 / 16 bytes
-EDGE_SHAPES = [(96, 3, 2), (36, 4, 4), (18, 8, 4), (9, 16, 4)]
-T16, TBF, T32, T64 = "_Float16", "__bf16", "float", "double"
-EDGE_KERNELS = {cd.HALF: (T16, 1, (16, 8, 4, 2)), cd.BFLOAT16: (TBF, 1, (16, 8, 4, 2)), cd.HALF_COMPLEX: (T16, 2, (16, 8, 4)),
-                cd.FLOAT: (T32, 1, (16, 8, 4)), cd.FLOAT_COMPLEX: (T32, 2, (16, 8)), cd.DOUBLE: (T64, 1, (16, 8)),
-                cd.DOUBLE_COMPLEX: (T64, 2, (16,))}
+# the pairs laid into elements, the (w, h, d) shapes of 576 elements and the (real type, reals per element, lane widths) table are
+# shared with the edge-value tests of the other adding kernels: tests/edge_arithmetic.py
+_pair_elements, EDGE_SHAPES, EDGE_KERNELS = EA.pair_elements, EA.SHAPES, EA.KERNELS
 
 
 @pytest.mark.parametrize("dtype", AB.ALL_TYPES, ids=[AB.NAMES[t] for t in AB.ALL_TYPES])

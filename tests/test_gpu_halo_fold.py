@@ -5,7 +5,9 @@ against the definition of tests/fold_bodies.py; the adjoint identity <S x, y> ==
 against clear = 0 and a zeroing; the sums against add-moves taken one by one; four ranks sharing the GPU on a ragged 2 x 2 grid;
 capture into a hipGraph; asynchrony; refusals.  Everything is compared byte for byte against numpy with the additions of
 tests/accumulate_bodies.py: there is no tolerance anywhere.  Buffers start as a poison byte; payloads are finite, with zeros of
-both signs and subnormals, without NaN."""
+both signs and subnormals, without NaN: these tests are about WHERE cells go.  NaNs, infinities, overflow, ties and exact
+cancellation through the fold kernels (every lane width, access, parity and TAKE) and through cudecompAmdFoldHalos* on whole pencils
+are in tests/test_gpu_halo_edge_arithmetic.py."""
 import itertools
 
 import numpy as np
