@@ -169,7 +169,9 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtRunFieldMoveList", "cudecompExtDescribeFieldMoveList", "cudecompExtDescribeResidency",
                "cudecompExtPlanHaloAccumulateFields", "cudecompExtRunFieldMovesOp", "cudecompExtDescribeFieldMovesOp",
                "cudecompExtRunMirroredFieldMoves", "cudecompExtDescribeMirroredFieldMoves", "cudecompExtHaloPlanCount",
-               "cudecompExtPlanHaloWallValues", "cudecompExtWall3D"]
+               "cudecompExtPlanHaloWallValues", "cudecompExtWall3D", "cudecompExtSyncEpochBegin", "cudecompExtSyncSignal",
+               "cudecompExtSyncWait", "cudecompExtTagPages", "cudecompExtCheckPages", "cudecompExtChecksum"]
+MAX_FLAGS, FLAG_SCALE = 64, 16  # csrc/kernels.h: kMaxFlags, kFlagScale
 # include/cudecomp_amd.h: extensions of the API a solver may use
 AMD_SYMBOLS = ["cudecompAmdAccumulateHalosX", "cudecompAmdAccumulateHalosY", "cudecompAmdAccumulateHalosZ"]
 # include/cudecomp_amd_fill.h: halo fill
@@ -346,6 +348,12 @@ def lib():
         L.cudecompExtDescribeMove.argtypes = [C.c_uint64, C.c_uint64, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32,
                                               C.POINTER(i64)]
         L.cudecompExtRotateWalk.argtypes = [i32, i32, i64, i64, pi32, C.POINTER(i64)]
+        L.cudecompExtSyncEpochBegin.argtypes = [vp, C.POINTER(vp), i32, vp]
+        L.cudecompExtSyncSignal.argtypes = [vp, C.POINTER(vp), i32, i32, vp]
+        L.cudecompExtSyncWait.argtypes = [vp, C.POINTER(vp), i32, i32, vp, C.c_double, vp]
+        L.cudecompExtTagPages.argtypes = [vp, C.c_size_t, C.c_uint64, vp]
+        L.cudecompExtCheckPages.argtypes = [vp, C.c_size_t, C.c_uint64, vp, vp]
+        L.cudecompExtChecksum.argtypes = [vp, C.c_size_t, vp, vp]
         L.cudecompExtRunMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(vp), i32, i32, i32, vp, i32, C.POINTER(vp), vp, pi32,
                                           C.POINTER(i64), pi32]
         L.cudecompExtDescribeMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, i32, i32, i32,
@@ -915,6 +923,44 @@ def cudecompExtRotateWalk(nb, walk=-1):
     _check(lib().cudecompExtRotateWalk(nb, walk, 0, grid.value, blocks.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(grid)),
            "cudecompExtRotateWalk")
     return grid.value, blocks
+
+
+def _flag_pointers(flags):
+    """(array of the flags' addresses or None, their number) for the cudecompExtSync* calls; `flags`: a sequence of addresses"""
+    n = len(flags)
+    return ((C.c_void_p * n)(*[int(f) for f in flags]) if n else None), n
+
+
+def cudecompExtSyncEpochBegin(epoch, flags, stream=None):
+    """epoch_begin_k: *epoch += 1, every flag = *epoch * FLAG_SCALE.  Addresses; asynchronous on `stream`."""
+    a, n = _flag_pointers(flags)
+    _check(lib().cudecompExtSyncEpochBegin(epoch, a, n, stream), "cudecompExtSyncEpochBegin")
+
+
+def cudecompExtSyncSignal(epoch, flags, step, stream=None):
+    """signal_k: every flag = *epoch * FLAG_SCALE + step"""
+    a, n = _flag_pointers(flags)
+    _check(lib().cudecompExtSyncSignal(epoch, a, n, step, stream), "cudecompExtSyncSignal")
+
+
+def cudecompExtSyncWait(epoch, flags, step, status, timeout_s, stream=None):
+    """wait_k: until every flag >= *epoch * FLAG_SCALE + step, or timeout_s (at most 1 s) have passed: *status = the code then"""
+    a, n = _flag_pointers(flags)
+    _check(lib().cudecompExtSyncWait(epoch, a, n, step, status, timeout_s, stream), "cudecompExtSyncWait")
+
+
+def cudecompExtTagPages(base, nbytes, seed, stream=None):
+    _check(lib().cudecompExtTagPages(base, nbytes, seed, stream), "cudecompExtTagPages")
+
+
+def cudecompExtCheckPages(base, nbytes, seed, bad, stream=None):
+    """check_pages_k: *bad (an address) += the pages whose tag does not read back"""
+    _check(lib().cudecompExtCheckPages(base, nbytes, seed, bad, stream), "cudecompExtCheckPages")
+
+
+def cudecompExtChecksum(ptr, nbytes, out2, stream=None):
+    """checksum_k: out2[0] += sum of the words, out2[1] += position-weighted sum (out2: the address of two 64-bit cells)"""
+    _check(lib().cudecompExtChecksum(ptr, nbytes, out2, stream), "cudecompExtChecksum")
 
 
 def cudecompExtDescribeMove(src_address, dst_address, es, extent, ss, ds, flags=0, row_pitch=0):

@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <string>
 #include <vector>
 
 #include "cudecomp_ext.h"
@@ -259,6 +260,23 @@ HaloOp haloOp(HaloOp::Kind kind, bool clear = false, int centering = 0, bool neg
   op.negate = negate;
   op.n_fields = n_fields;
   return op;
+}
+
+// cudecompExtSync*: the list of n flag pointers as the kernels take it; n in 0 .. kMaxFlags, every one of the n pointers set
+FlagList flagListOf(uint64_t* const* flags, int32_t n) {
+  if (n < 0 || n > kMaxFlags) CD_INVALID_USAGE("n must lie in 0 .. " + std::to_string(kMaxFlags));
+  if (n > 0 && !flags) CD_INVALID_USAGE("null flag list");
+  FlagList l;
+  l.n = n;
+  for (int i = 0; i < kMaxFlags; ++i) {
+    if (i < n && !flags[i]) CD_INVALID_USAGE("null flag");
+    l.f[i] = i < n ? reinterpret_cast<unsigned long long*>(flags[i]) : nullptr;
+  }
+  return l;
+}
+
+void checkFlagStep(int32_t step) {
+  if (step < 0 || step >= (int32_t)kFlagScale) CD_INVALID_USAGE("step must lie in 0 .. " + std::to_string(kFlagScale - 1));
 }
 
 }  // namespace
@@ -1395,6 +1413,88 @@ cudecompResult_t cudecompExtRunMoves(const cudecompExtMove_t* moves, int32_t n, 
       total += st.launches[c];
     }
     if (n_launches) *n_launches = total;
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+// ---- the flag, page-tag and checksum kernels of sync.hip, one launch each (tests/test_gpu_sync_kernels.py) ----------------------
+cudecompResult_t cudecompExtSyncEpochBegin(uint64_t* epoch, uint64_t* const* flags, int32_t n, hipStream_t stream) {
+  try {
+    const FlagList l = flagListOf(flags, n);
+    if (!epoch) CD_INVALID_USAGE("null epoch");
+    launchEpochBegin(reinterpret_cast<unsigned long long*>(epoch), l, stream);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtSyncSignal(const uint64_t* epoch, uint64_t* const* flags, int32_t n, int32_t step, hipStream_t stream) {
+  try {
+    const FlagList l = flagListOf(flags, n);
+    checkFlagStep(step);
+    if (n > 0 && !epoch) CD_INVALID_USAGE("null epoch");
+    launchSignal(reinterpret_cast<const unsigned long long*>(epoch), l, stream, step);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtSyncWait(const uint64_t* epoch, uint64_t* const* flags, int32_t n, int32_t step, uint64_t* status,
+                                     double timeout_s, hipStream_t stream) {
+  try {
+    const FlagList l = flagListOf(flags, n);
+    checkFlagStep(step);
+    // (the harness never parks a wave for longer than a second, whatever a test asks for; NaN fails both comparisons)
+    if (!(timeout_s > 0.0 && timeout_s <= 1.0)) CD_INVALID_USAGE("timeout_s must lie in (0, 1]");
+    if (n > 0 && (!epoch || !status)) CD_INVALID_USAGE("null epoch or status");
+    launchWait(reinterpret_cast<const unsigned long long*>(epoch), l, reinterpret_cast<unsigned long long*>(status), timeout_s, stream,
+               step);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtTagPages(void* base, size_t bytes, uint64_t seed, hipStream_t stream) {
+  try {
+    if (bytes >= 4096 && !base) CD_INVALID_USAGE("null buffer");
+    launchTagPages(base, bytes, seed, stream);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtCheckPages(const void* base, size_t bytes, uint64_t seed, uint64_t* bad, hipStream_t stream) {
+  try {
+    if (bytes >= 4096 && (!base || !bad)) CD_INVALID_USAGE("null argument");
+    launchCheckPages(base, bytes, seed, reinterpret_cast<unsigned long long*>(bad), stream);
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtChecksum(const void* ptr, size_t bytes, uint64_t* out2, hipStream_t stream) {
+  try {
+    if (bytes > 0 && (!ptr || !out2)) CD_INVALID_USAGE("null argument");
+    launchChecksum(ptr, bytes, reinterpret_cast<unsigned long long*>(out2), stream);
   } catch (const Error& e) {
     return fail(e);
   } catch (...) {

@@ -167,7 +167,8 @@ void launchWait(const unsigned long long* epoch, const FlagList& flags, unsigned
 // stamp / verify the first word of every 4-KiB page of a shared buffer (see sync.hip)
 void launchTagPages(void* base, size_t bytes, unsigned long long seed, hipStream_t stream);
 void launchCheckPages(const void* base, size_t bytes, unsigned long long seed, unsigned long long* bad, hipStream_t stream);
-// debug aid: out2[0] += sum of the 32-bit words of [p, p + bytes), out2[1] += position-weighted sum (mod 2^64)
+// debug aid: out2[0] += sum of the 32-bit words of [p, p + bytes), out2[1] += position-weighted sum (mod 2^64); a tail of 1 - 3
+// bytes counts as one more word, zero-extended, at index bytes / 4 (no byte past p + bytes is read); bytes == 0: no launch
 void launchChecksum(const void* p, size_t bytes, unsigned long long* out2, hipStream_t stream);
 
 }  // namespace cudecomp

@@ -264,13 +264,16 @@ void peerVerifyExchange(cudecompHandle_t h, cudecompCommInfo& ci, const Transpos
   // everybody's "what I sent to member d": [member][d][2]
   std::vector<unsigned long long> sent((size_t)2 * P * P);
   ci.boot->allgather(host.data() + (size_t)2 * 2 * P, sent.data(), sizeof(unsigned long long) * 2 * P);
+  int summed = 0, reported = 0;
   for (int s = 0; s < P; ++s) {
     if (p.recv_cnt[s] == 0) continue;
+    ++summed;
     const unsigned long long* r1 = &host[2 * (0 * P + s)];
     const unsigned long long* r2 = &host[2 * (1 * P + s)];
     const unsigned long long* ex = &sent[2 * ((size_t)s * P + me)];
     const bool late = r1[0] != r2[0] || r1[1] != r2[1];
     const bool wrong = sender_side_valid && (r2[0] != ex[0] || r2[1] != ex[1]);
+    if (late || wrong) ++reported;
     if (late || wrong)
       fprintf(stderr, "CUDECOMP:VERIFY rank %d %s: chunk from member %d (rank %d, %lld bytes at recv offset %lld): %s%s  "
                       "[at flag %016llx/%016llx, after barrier %016llx/%016llx, sender %016llx/%016llx]\n",
@@ -278,6 +281,10 @@ void peerVerifyExchange(cudecompHandle_t h, cudecompCommInfo& ci, const Transpos
               late ? "LATE (changed after the landed flag) " : "", wrong ? "NOT WHAT WAS SENT even after everyone drained" : "",
               r1[0], r1[1], r2[0], r2[1], ex[0], ex[1]);
   }
+  // (every rank says so: tests/test_gpu_sync_kernels.py counts these lines to know that the aid ran at all)
+  if (std::getenv("CUDECOMP_VERBOSE"))
+    fprintf(stderr, "CUDECOMP: exchange verification rank %d %s: %d chunks summed%s, %d reported\n", h->rank, what, summed,
+            sender_side_valid ? " and compared with their senders' sums" : "", reported);
 }
 
 }  // namespace cudecomp

@@ -63,12 +63,21 @@ __global__ void wait_k(const u64* epoch, const FlagList flags, u64* status, long
 }
 
 // position-weighted checksum of a byte range taken as 32-bit words: out[0] += sum(w_i), out[1] += sum(w_i * (i + 1))
-// (mod 2^64) -- a moved, missing or stale block changes it.  Debug aid of the one-sided exchanges
-// (CUDECOMP_DEBUG_VERIFY_EXCHANGE), not part of any data path.
-__global__ void checksum_k(const unsigned int* p, unsigned long long words, u64* out) {
+// (mod 2^64) -- a moved, missing or stale block changes it.  A tail of 1 - 3 bytes (`tail`) is one more word at index `words`,
+// zero-extended: the last element of an odd-length chunk of a 2-byte type counts, and it is read byte by byte so that nothing
+// behind the range is.  The base need not be a multiple of 4 (chunks of 2-byte elements start at 2 mod 4).  Debug aid of the
+// one-sided exchanges (CUDECOMP_DEBUG_VERIFY_EXCHANGE), not part of any data path.
+__global__ void checksum_k(const unsigned int* p, unsigned long long words, unsigned int tail, u64* out) {
   u64 s1 = 0, s2 = 0;
-  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < words; i += (u64)gridDim.x * blockDim.x) {
-    const u64 w = __builtin_nontemporal_load(p + i);
+  const u64 total = words + (tail ? 1 : 0);
+  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < total; i += (u64)gridDim.x * blockDim.x) {
+    u64 w = 0;
+    if (i < words) {
+      w = __builtin_nontemporal_load(p + i);
+    } else {
+      const unsigned char* b = reinterpret_cast<const unsigned char*>(p + words);
+      for (unsigned int k = 0; k < tail; ++k) w |= (u64)b[k] << (8 * k);
+    }
     s1 += w;
     s2 += w * (i + 1);
   }
@@ -121,10 +130,10 @@ void launchCheckPages(const void* base, size_t bytes, unsigned long long seed, u
 }
 
 void launchChecksum(const void* p, size_t bytes, unsigned long long* out2, hipStream_t stream) {
-  if (bytes < 4) return;
-  const unsigned long long words = bytes / 4;
-  const unsigned int blocks = (unsigned int)std::min<unsigned long long>((words + 1023) / 1024, 2048);
-  checksum_k<<<blocks, 256, 0, stream>>>(static_cast<const unsigned int*>(p), words, out2);
+  if (bytes == 0) return;
+  const unsigned long long words = bytes / 4, total = words + (bytes % 4 ? 1 : 0);
+  const unsigned int blocks = (unsigned int)std::min<unsigned long long>((total + 1023) / 1024, 2048);
+  checksum_k<<<blocks, 256, 0, stream>>>(static_cast<const unsigned int*>(p), words, (unsigned int)(bytes % 4), out2);
   CD_CHECK_HIP(hipGetLastError());
 }
 

@@ -547,6 +547,30 @@ cudecompResult_t cudecompExtHaloPlanCount(cudecompHandle_t handle, cudecompGridD
  * blocks may be NULL (count 0).  Harness-only (tests/test_kernel_plan.py: every walk visits every triple exactly once). */
 cudecompResult_t cudecompExtRotateWalk(int32_t nb, int32_t walk, int64_t first, int64_t count, int32_t* blocks, int64_t* grid);
 
+/* The six kernels that order and guard the one-sided exchanges (csrc/sync.hip), one launch each, asynchronous on `stream`, no
+ * handle (tests/test_gpu_sync_kernels.py holds each to tests/sync_reference.py).  Pointers are whatever the caller passes: device
+ * memory, or pinned host memory by its device address.  A flag holds  call * 16 + step;  flags[0 .. n-1] are n pointers, one cell each,
+ * n in 0 .. 64, step in 0 .. 15.  INVALID_USAGE, before any launch, for n or step out of range and for a null pointer where a launch
+ * would follow.  None of these is a data-movement launch: cudecompExtDataLaunchCount and cudecompExtLastKernelName do not change.
+ *   SyncEpochBegin  *epoch += 1, then every flag = *epoch * 16.  n == 0 still bumps the epoch.
+ *   SyncSignal      every flag = *epoch * 16 + step.  n == 0: no launch.
+ *   SyncWait        returns on the stream once every flag >= *epoch * 16 + step.  A flag still short after timeout_s seconds of the
+ *                   100 MHz wall clock: *status = (*epoch << 8) | (index of that flag + 1), of any one such flag; the kernel then
+ *                   ends and the stream goes on.  timeout_s outside (0, 1] is INVALID_USAGE -- the harness never parks a wave for
+ *                   longer than a second.  n == 0: no launch.
+ *   TagPages        word 0 (64 bits) of every whole 4-KiB page i of [base, base + bytes) = tag(seed, i); no other byte is written.
+ *   CheckPages      *bad += the number of whole pages whose word 0 is not tag(seed, i).  bytes < 4096: no launch for either.
+ *   Checksum        the range as little-endian 32-bit words w_0 .. w_(k-1), a tail of 1 - 3 bytes as one more word, zero-extended;
+ *                   out2[0] += sum w_i, out2[1] += sum w_i * (i + 1), both mod 2^64.  ptr need not be a multiple of 4; no byte
+ *                   past ptr + bytes is read.  bytes == 0: no launch. */
+cudecompResult_t cudecompExtSyncEpochBegin(uint64_t* epoch, uint64_t* const* flags, int32_t n, hipStream_t stream);
+cudecompResult_t cudecompExtSyncSignal(const uint64_t* epoch, uint64_t* const* flags, int32_t n, int32_t step, hipStream_t stream);
+cudecompResult_t cudecompExtSyncWait(const uint64_t* epoch, uint64_t* const* flags, int32_t n, int32_t step, uint64_t* status,
+                                     double timeout_s, hipStream_t stream);
+cudecompResult_t cudecompExtTagPages(void* base, size_t bytes, uint64_t seed, hipStream_t stream);
+cudecompResult_t cudecompExtCheckPages(const void* base, size_t bytes, uint64_t seed, uint64_t* bad, hipStream_t stream);
+cudecompResult_t cudecompExtChecksum(const void* ptr, size_t bytes, uint64_t* out2, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
