@@ -19,7 +19,10 @@ timed alternately in both orders (fields first, then singles; singles first, the
 --wall-values, cudecompAmdSetWallHalosX (cudecomp_halo_wall_values.h; parity -1, centering 0, both sides, one addend per layer) next to
 cudecompAmdReflectHalosX with parity -1 on the same pencil, walls along dims 1 and 2 (dim 0 periodic), for fp64 and for fp16: the
 reflection's two sibling moves plus one addition per element (4 * face bytes), the two calls timed in the order reflection, wall
-values, wall values, reflection.
+values, wall values, reflection and, with --wall-value-fields N, cudecompAmdSetWallFieldHalosX (cudecomp_halo_wall_value_fields.h;
+parities -1, +1, -1, ..., centering 0, both sides, addends of its own for every field) on N such pencils next to N single
+cudecompAmdSetWallHalosX calls with the same parities and addends, walls along dims 1 and 2, for fp64 and for fp16, timed in the order
+singles, fields, fields, singles; afterwards every cell of every field against the single calls on clones.
 Per dim: `--reps` repetitions of `--calls` back-to-back calls each, ms per call of every repetition, their
 min / median / max, and GB/s of the median against the algorithmic bytes (update: 2 faces read + written,
 4 * face bytes; accumulation: 2 faces read, 2 destinations read and written, 6 * face bytes; fill: 2 halos written, 2 * face
@@ -83,6 +86,10 @@ def main():
     ap.add_argument("--wall-values", action="store_true",
                     help="also time cudecompAmdSetWallHalosX (parity -1, centering 0, both sides) next to cudecompAmdReflectHalosX with "
                          "parity -1, walls along dims 1 and 2, fp64 and fp16, after the other passes")
+    ap.add_argument("--wall-value-fields", type=int, default=0, metavar="N",
+                    help="also time cudecompAmdSetWallFieldHalosX on N pencils (centering 0, both sides, a parity and addends per field) next "
+                         "to N single cudecompAmdSetWallHalosX calls, walls along dims 1 and 2, fp64 and fp16, in the order singles, fields, "
+                         "fields, singles, and compare every field on the device with a clone served by single calls")
     ap.add_argument("--gdims", type=int, nargs=3, default=[2048, 1024, 256], metavar="N",
                     help="the pencil (default: config 5's per-rank X pencil; 64 64 64: a pencil on which fixed cost dominates)")
     ap.add_argument("--json", metavar="FILE", default=None, help="also write the result line to FILE")
@@ -337,6 +344,51 @@ def main():
         extra["n_wall_fields"] = n
         extra["wall_field_cells_that_differ_from_single_calls"] = sum(
             int(torch.count_nonzero(t.view(torch.int64) != c.view(torch.int64))) for t, c in zip(wall, clones))
+    if a.wall_value_fields:
+        n = a.wall_value_fields
+        periods = (1, 0, 0)
+        parities = [1 if f % 3 == 1 else -1 for f in range(n)]
+        # field f, ghost layer k: multiples of 1/8 that differ from field to field and layer to layer, exact in fp16
+        low = [[0.5 * (k + 1) + 0.125 * f for k in range(a.halo)] for f in range(n)]
+        high = [[-0.25 * (k + 1) - 0.125 * f for k in range(a.halo)] for f in range(n)]
+        flat_low, flat_high = [x for v in low for x in v], [x for v in high for x in v]
+        extra["n_wall_value_fields"] = n
+        for dtype, tdtype, es, label in ((cd.DOUBLE, torch.float64, 8, "fp64"), (cd.HALF, torch.float16, 2, "fp16")):
+            pencils = [torch.randn(p.size, dtype=torch.float64, device="cuda").to(tdtype) for _ in range(n)]
+            wptrs = [t.data_ptr() for t in pencils]
+
+            def many(dim, ptrs=wptrs):
+                cd.cudecompAmdSetWallFieldHalos(0, h, gd, ptrs, dtype, parities, 0, 3, flat_low, flat_high, halo, periods, dim, stream=st)
+
+            def singles(dim, ptrs=wptrs):
+                for f, q in enumerate(ptrs):
+                    cd.cudecompAmdSetWallHalos(0, h, gd, q, dtype, parities[f], 0, 3, low[f], high[f], halo, periods, dim, stream=st)
+
+            for dim in (1, 2):
+                rec = res["dim%d" % dim].setdefault("wall_value_fields", {})
+                runs, kernels = {"singles": [], "fields": []}, {}
+                for name, fn in (("singles", singles), ("fields", many), ("fields", many), ("singles", singles)):
+                    runs[name].append(_time(lambda: fn(dim), a.reps, a.calls))
+                    kernels[name] = cd.cudecompExtLastKernelName()
+                out = {name: _record(ms[0] + ms[1], n * 4 * faces[dim] * es) for name, ms in runs.items()}
+                first, second = (sorted(ms)[len(ms) // 2] for ms in runs["singles"])
+                out["singles_kernel"], out["fields_kernel"] = kernels["singles"], kernels["fields"]
+                out["singles_first_run_median_ms"], out["singles_second_run_median_ms"] = round(first, 4), round(second, 4)
+                out["singles_spread"] = round(abs(first - second) / min(first, second), 3)  # between the two runs of the yardstick
+                out["fields_over_singles"] = round(out["fields"]["median_ms"] / out["singles"]["median_ms"], 3)
+                rec[label] = out
+            # after the timing: fresh payloads, dims 0, 1, 2 by the field call against single calls on clones, on the device
+            for t in pencils:
+                t.copy_(torch.randn(p.size, dtype=torch.float64, device="cuda").to(tdtype))
+            clones = [t.clone() for t in pencils]
+            for dim in range(3):
+                many(dim)
+                singles(dim, [c.data_ptr() for c in clones])
+            torch.cuda.synchronize()
+            bits = torch.int64 if es == 8 else torch.int16
+            extra["wall_value_field_cells_that_differ_from_single_calls_" + label] = sum(
+                int(torch.count_nonzero(t.view(bits) != c.view(bits))) for t, c in zip(pencils, clones))
+            del pencils, clones
     cd.cudecompFree(h, gd, work)
     cd.cudecompGridDescDestroy(h, gd)
     line = json.dumps(dict({"workload": "X pencil %dx%dx%d fp64 + halo %d, single rank, periodic where not said otherwise, per dim: update (self copy), "
@@ -350,7 +402,9 @@ def main():
                                            + (" and their accumulate-and-clear in one call" if a.fields and a.accumulate_clear else "")
                                            + (" and the reflection and the fold of %d pencils in one call (non-periodic)" % a.wall_fields
                                               if a.wall_fields else "")
-                                           + (" and wall values next to the reflection (walls along dims 1 and 2, fp64 and fp16)" if a.wall_values else ""),
+                                           + (" and wall values next to the reflection (walls along dims 1 and 2, fp64 and fp16)" if a.wall_values else "")
+                                           + (" and the wall values of %d pencils in one call next to %d single calls (walls along dims 1 and 2, fp64 "
+                                              "and fp16)" % (a.wall_value_fields, a.wall_value_fields) if a.wall_value_fields else ""),
                                            a.reps, a.calls)),
                             "device": torch.cuda.get_device_name(0), "result": res}, **extra))
     print(line)
@@ -370,6 +424,10 @@ def main():
     if extra.get("wall_field_cells_that_differ_from_single_calls"):
         sys.exit("halo_bench.py: after the wall field calls %d cells differ from single calls on clones"
                  % extra["wall_field_cells_that_differ_from_single_calls"])
+    for label in ("fp64", "fp16"):
+        if extra.get("wall_value_field_cells_that_differ_from_single_calls_" + label):
+            sys.exit("halo_bench.py: after the wall-value field calls along 0, 1, 2 %d cells differ from single calls on clones (%s)"
+                     % (extra["wall_value_field_cells_that_differ_from_single_calls_" + label], label))
     for name in ("fold", "fold_clear"):
         if extra.get("interior_cells_with_another_count_after_" + name) or extra.get("ghost_cells_not_zero_after_" + name):
             sys.exit("halo_bench.py: after folding a pencil of ones along 2, 1, 0 (%s pass) %d interior cells do not hold their count and %d "

@@ -169,6 +169,7 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtRunFieldMoveList", "cudecompExtDescribeFieldMoveList", "cudecompExtDescribeResidency",
                "cudecompExtPlanHaloAccumulateFields", "cudecompExtRunFieldMovesOp", "cudecompExtDescribeFieldMovesOp",
                "cudecompExtRunMirroredFieldMoves", "cudecompExtDescribeMirroredFieldMoves", "cudecompExtHaloPlanCount",
+               "cudecompExtRunWallFieldMoves", "cudecompExtDescribeWallFieldMoves", "cudecompExtPlanHaloWallValueFields",
                "cudecompExtPlanHaloWallValues", "cudecompExtWall3D", "cudecompExtSyncEpochBegin", "cudecompExtSyncSignal",
                "cudecompExtSyncWait", "cudecompExtTagPages", "cudecompExtCheckPages", "cudecompExtChecksum"]
 MAX_FLAGS, FLAG_SCALE = 64, 16  # csrc/kernels.h: kMaxFlags, kFlagScale
@@ -198,6 +199,10 @@ MAX_HALO_WALL_FIELDS = 32  # CUDECOMP_AMD_MAX_HALO_WALL_FIELDS
 # include/cudecomp_halo_wall_values.h: wall values (the reflection with one addend per ghost layer and side: Dirichlet / Neumann data)
 AMD_WALL_VALUES_SYMBOLS = ["cudecompAmdSetWallHalosX", "cudecompAmdSetWallHalosY", "cudecompAmdSetWallHalosZ"]
 MAX_WALL_HALO = 8  # CUDECOMP_AMD_MAX_WALL_HALO
+# include/cudecomp_halo_wall_value_fields.h: multi-field wall values (several pencils, a parity and addends per field)
+AMD_WALL_VALUE_FIELDS_SYMBOLS = ["cudecompAmdSetWallFieldHalosX", "cudecompAmdSetWallFieldHalosY", "cudecompAmdSetWallFieldHalosZ"]
+MAX_WALL_VALUE_FIELDS = 32  # CUDECOMP_AMD_MAX_WALL_VALUE_FIELDS
+WALL_FIELD_TABLE_BYTES = 2048  # CUDECOMP_EXT_WALL_FIELD_TABLE_BYTES
 # include/cudecomp_transpose_fields.h: multi-field transposes (several pencils in one exchange)
 TRANSPOSE_FIELDS_SYMBOLS = ["cudecompAmdTransposeFieldsXToY", "cudecompAmdTransposeFieldsYToZ", "cudecompAmdTransposeFieldsZToY",
                             "cudecompAmdTransposeFieldsYToX"]
@@ -299,6 +304,13 @@ def lib():
         L.cudecompExtRunMirroredFieldMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(vp), i32, i32, i32, i32, i32, C.c_uint32, vp, pi32]
         L.cudecompExtDescribeMirroredFieldMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, i32, i32, i32, i32,
                                                             C.c_uint32, C.POINTER(i64)]
+        for name in AMD_WALL_VALUE_FIELDS_SYMBOLS:  # (the wall values' arguments with the lists of fields and parities and their length)
+            getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, i32, pi32, i32, i32, pf64, pf64, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
+        L.cudecompExtPlanHaloWallValueFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32, i32,
+                                                         C.POINTER(ExtHaloPlan)]
+        L.cudecompExtRunWallFieldMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(vp), i32, i32, i32, C.c_uint32, vp, vp, pi32]
+        L.cudecompExtDescribeWallFieldMoves.argtypes = [C.POINTER(ExtMove), i32, C.POINTER(C.c_uint64), i32, i32, i32, C.c_uint32, vp, i32,
+                                                        C.POINTER(i64), C.POINTER(C.c_uint8), pi32]
         for name in TRANSPOSE_FIELDS_SYMBOLS:  # (the transpose's arguments with the two lists and their length in the place of `input`, `output`)
             getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), i32, vp, i32, pi32, pi32, pi32, pi32, vp]
         L.cudecompExtPlanTransposeFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, pi32, pi32, pi32, C.c_bool, i32, i32, i32,
@@ -611,6 +623,19 @@ def cudecompReflectFieldHalos(axis, handle, gd, ptrs, dtype, parities, centering
                                 _b3(halo_periods), dim, _i3(padding), stream), name)
 
 
+def cudecompAmdSetWallFieldHalos(axis, handle, gd, ptrs, dtype, parities, centering, sides, values_low, values_high, halo_extents,
+                                 halo_periods, dim, padding=None, stream=None, n_fields=None):
+    """cudecompAmdSetWallFieldHalos{X,Y,Z} (cudecomp_halo_wall_value_fields.h): the wall values along `dim` of every pencil in `ptrs`
+    (device pointers), field f with parity parities[f] and its own addends.  values_low / values_high: flat sequences, field-major --
+    halo_extents[dim] floats per field (complex types: twice as many, re and im interleaved) -- or None for a side not named.
+    Nothing is checked here: the library refuses what the header says it refuses.  n_fields: the count passed, when it shall differ
+    from len(ptrs)."""
+    name = "cudecompAmdSetWallFieldHalos" + "XYZ"[axis]
+    arr, par, n = _wall_field_tables(ptrs, parities)
+    _check(getattr(lib(), name)(handle, gd, arr, n if n_fields is None else n_fields, dtype, par, int(centering), int(sides),
+                                _f64(values_low), _f64(values_high), _i3(halo_extents), _b3(halo_periods), dim, _i3(padding), stream), name)
+
+
 def cudecompFoldFieldHalos(axis, handle, gd, ptrs, dtype, parities, centering, clear, halo_extents, halo_periods, dim, padding=None,
                            stream=None, n_fields=None):
     """cudecompAmdFoldFieldHalos{X,Y,Z} (cudecomp_halo_wall_fields.h): the fold along `dim` of every pencil in `ptrs` (device
@@ -757,6 +782,16 @@ def cudecompExtPlanHaloWallValues(grid, rank, axis, halo_extents, halo_periods, 
                                                int(dtype), int(parity), int(centering), int(sides), _f64(values_low), _f64(values_high),
                                                C.byref(p), table.ctypes.data_as(C.POINTER(C.c_uint8))), "cudecompExtPlanHaloWallValues")
     return p, table
+
+
+def cudecompExtPlanHaloWallValueFields(grid, rank, axis, halo_extents, halo_periods, dim, centering, sides, n_fields, padding=None):
+    """Stateless planner of cudecompAmdSetWallFieldHalos*: the plan whose moves -- the single call's for the sides kept, unsigned, with
+    ExtMove.peer the side -- are carried out for every field.  Arguments are passed as they are: the library makes the checks."""
+    p = ExtHaloPlan()
+    _check(lib().cudecompExtPlanHaloWallValueFields(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding),
+                                                    int(centering), int(sides), int(n_fields), C.byref(p)),
+           "cudecompExtPlanHaloWallValueFields")
+    return p
 
 
 def cudecompExtPlanHaloFields(grid, rank, axis, halo_extents, halo_periods, dim, padding=None, n_fields=1, force_packed=False):
@@ -1110,6 +1145,51 @@ def cudecompExtDescribeMirroredFieldMoves(moves, field_addresses, es, mode, dtyp
     _check(lib().cudecompExtDescribeMirroredFieldMoves(_move_list(moves), len(moves), f, len(field_addresses), es, int(force), int(mode),
                                                        int(dtype), int(fields_neg), out), "cudecompExtDescribeMirroredFieldMoves")
     return dict(zip(("kind", "vec", "access", "blocks_per_field", "blocks"), [int(x) for x in out]))
+
+
+def _wall_field_addends(addends, n_fields, es):
+    """the raw addends of the wall pair as bytes: (n_fields, 2, MAX_WALL_HALO) elements of `es` bytes"""
+    raw = bytes(addends)
+    if len(raw) != n_fields * 2 * MAX_WALL_HALO * es:
+        raise ValueError("addends hold %d bytes, %d fields x 2 sides x %d layers of %d bytes are %d"
+                         % (len(raw), n_fields, MAX_WALL_HALO, es, n_fields * 2 * MAX_WALL_HALO * es))
+    return raw
+
+
+def cudecompExtRunWallFieldMoves(moves, fields, dtype, addends, fields_neg=0, force=0, stream=None):
+    """One or two wall-moves (one dim with a negative source stride, `peer` the side: 0 low, 1 high) for every buffer of `fields`
+    (device pointers): dst = +-src + the field's addend of the destination's ghost layer; bit f of fields_neg flips the sign bits of
+    field f's source first.  addends: bytes of (len(fields), 2, MAX_WALL_HALO) raw elements of `dtype`, ghost layer k counted from the
+    wall outward.  Returns the number of launches."""
+    f = (C.c_void_p * max(1, len(fields)))(*[p or None for p in fields])
+    total = C.c_int32(-1)
+    raw = _wall_field_addends(addends, len(fields), cudecompGetDataTypeSize(dtype))
+    _check(lib().cudecompExtRunWallFieldMoves(_move_list(moves), len(moves), f, len(fields), int(force), int(dtype), int(fields_neg), raw,
+                                              stream, C.byref(total)), "cudecompExtRunWallFieldMoves")
+    return total.value
+
+
+def cudecompExtDescribeWallFieldMoves(moves, field_addresses, dtype, addends, fields_neg=0, force=0):
+    """How cudecompExtRunWallFieldMoves would run (no launch, no GPU): a list with one dict per launch of kind (37 / 38 the single
+    wall kernels for one field, 39 / 40 the field kernels), lane bytes, access mode, workgroups, workgroups per field, first field,
+    fields in the launch, and `table`, the launch's WALL_FIELD_TABLE_BYTES of addends as a numpy uint8 array."""
+    import numpy as np
+    f = (C.c_uint64 * max(1, len(field_addresses)))(*[int(p) for p in field_addresses])
+    raw = _wall_field_addends(addends, len(field_addresses), cudecompGetDataTypeSize(dtype))
+    cap = MAX_WALL_VALUE_FIELDS
+    out = (C.c_int64 * (7 * cap))()
+    tables = np.zeros((cap, WALL_FIELD_TABLE_BYTES), dtype=np.uint8)
+    made = C.c_int32(-1)
+    _check(lib().cudecompExtDescribeWallFieldMoves(_move_list(moves), len(moves), f, len(field_addresses), int(force), int(dtype),
+                                                   int(fields_neg), raw, cap, out, tables.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                   C.byref(made)), "cudecompExtDescribeWallFieldMoves")
+    keys = ("kind", "vec", "access", "blocks", "blocks_per_field", "first_field", "fields")
+    res = []
+    for l in range(min(made.value, cap)):
+        d = dict(zip(keys, [int(x) for x in out[7 * l:7 * l + 7]]))
+        d["table"] = tables[l].copy()
+        res.append(d)
+    return res
 
 
 def cudecompExtPlanTransposeFields(grid, rank, op, in_halo=None, out_halo=None, in_pad=None, out_pad=None, inplace=False,

@@ -848,7 +848,7 @@ CD_DEFINE_TRANSPOSE(cudecompTransposeYToX, OP_Y_TO_X)
 struct HaloEntryOptions {
   int max_fields = 0;                 // > 0: a multi-field family and the most fields it takes
   bool clear_first = false;           // `clear` is checked right after halo_extents
-  bool wall_fields = false;           // reflection / folding of several fields: `parities` below is the caller's list (may be NULL)
+  bool wall_fields = false;           // reflection / folding / wall values of several fields: `parities` below is the caller's list (may be NULL)
   const int32_t* parities = nullptr;
 };
 
@@ -1081,6 +1081,31 @@ CD_DEFINE_HALO_WALL_FIELDS(cudecompAmdReflectFieldHalosZ, REFLECT, 2, CD_NO_CLEA
 CD_DEFINE_HALO_WALL_FIELDS(cudecompAmdFoldFieldHalosX, FOLD, 0, CD_CLEAR_PARAM, clear)
 CD_DEFINE_HALO_WALL_FIELDS(cudecompAmdFoldFieldHalosY, FOLD, 1, CD_CLEAR_PARAM, clear)
 CD_DEFINE_HALO_WALL_FIELDS(cudecompAmdFoldFieldHalosZ, FOLD, 2, CD_CLEAR_PARAM, clear)
+
+// cudecomp_halo_wall_value_fields.h: the wall values of several pencils, each with a parity and addends of its own.  The lists are
+// checked where cudecompAmdReflectFieldHalos* checks them, the parities where the single call checks `parity`, then the single
+// call's checks; one field IS the single call with parities[0]
+#define CD_DEFINE_HALO_WALL_VALUE_FIELDS(NAME, AXIS)                                                                           \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const inputs[], int32_t n_fields,         \
+                        cudecompDataType_t dtype, const int32_t parities[], int32_t centering, int32_t sides,                  \
+                        const double values_low[], const double values_high[], const int32_t halo_extents[],                   \
+                        const bool halo_periods[], int32_t dim, const int32_t padding[], hipStream_t stream) {                 \
+    HaloCall c = haloCall(HaloOp::WALL_VALUES, AXIS, inputs, nullptr, dtype, halo_extents, halo_periods, dim, padding,         \
+                          stream);                                                                                             \
+    c.op.n_fields = n_fields;                                                                                                  \
+    c.op.centering = centering;                                                                                                \
+    c.op.sides = sides;                                                                                                        \
+    c.values_low = values_low;                                                                                                 \
+    c.values_high = values_high;                                                                                               \
+    HaloEntryOptions opt;                                                                                                      \
+    opt.max_fields = CUDECOMP_AMD_MAX_WALL_VALUE_FIELDS;                                                                       \
+    opt.wall_fields = true;                                                                                                    \
+    opt.parities = parities;                                                                                                   \
+    return haloApiEntry(handle, grid_desc, c, opt);                                                                            \
+  }
+CD_DEFINE_HALO_WALL_VALUE_FIELDS(cudecompAmdSetWallFieldHalosX, 0)
+CD_DEFINE_HALO_WALL_VALUE_FIELDS(cudecompAmdSetWallFieldHalosY, 1)
+CD_DEFINE_HALO_WALL_VALUE_FIELDS(cudecompAmdSetWallFieldHalosZ, 2)
 
 // cudecomp_transpose_fields.h: the transpose of several pencils with one exchange.  The checks of transposeEntry, in its order,
 // with the lists checked where the transpose checks `input` and `output`; all of it on the host, before anything is launched.

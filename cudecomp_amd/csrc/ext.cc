@@ -1169,6 +1169,146 @@ cudecompResult_t cudecompExtDescribeMirroredFieldMoves(const cudecompExtMove_t* 
   return CUDECOMP_RESULT_SUCCESS;
 }
 
+// the wall pair: the imported list as wall-moves (every move a reflect-move that names its side in `peer`), and the raw addends
+// ((f * 2 + side) * CUDECOMP_AMD_MAX_WALL_HALO + k elements) as the kernel layer takes them
+static std::vector<Move3D> importWallFieldMoves(const cudecompExtMove_t* moves, int32_t n, int32_t n_fields, int32_t es, uint32_t fields_neg,
+                                                const void* addends, std::vector<WallAddends>& converted) {
+  if (!addends) CD_INVALID_USAGE("null argument");
+  std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_WALL_VALUE_FIELDS, es);
+  if (n_fields < 32 && (fields_neg >> n_fields) != 0) CD_INVALID_USAGE("sign bit of a field the list does not have");
+  for (int32_t i = 0; i < n; ++i) {
+    Move3D& m = list[i];
+    if (moves[i].peer != 0 && moves[i].peer != 1) CD_INVALID_USAGE("a wall-value move names its side in `peer`: 0 low, 1 high");
+    if (m.src_buf == BUF_WORK || m.dst_buf == BUF_WORK || m.dst_row_pitch != 0) CD_INVALID_USAGE("wall-value moves lie in the fields' own buffers");
+    int mirrored = 0;
+    for (int d = 0; d < 3; ++d) {
+      if (m.extent[d] < 0) CD_INVALID_USAGE("negative extent");
+      if (m.ss[d] < 0) {
+        ++mirrored;
+        if (m.extent[d] > CUDECOMP_AMD_MAX_WALL_HALO) CD_INVALID_USAGE("one mirrored dim of at most CUDECOMP_AMD_MAX_WALL_HALO layers");
+      }
+    }
+    if (mirrored != 1) CD_INVALID_USAGE("a wall-value move names its one mirrored dim with a negative source stride");
+    m.reflect = true;
+    m.affine = moves[i].peer + 1;
+  }
+  converted.assign(n_fields, WallAddends());
+  for (int32_t f = 0; f < n_fields; ++f) {
+    std::memset(&converted[f], 0, sizeof(WallAddends));
+    for (int side = 0; side < 2; ++side)
+      for (int k = 0; k < CUDECOMP_AMD_MAX_WALL_HALO; ++k)
+        std::memcpy(converted[f].v[side][k],
+                    static_cast<const char*>(addends) + ((size_t)(f * 2 + side) * CUDECOMP_AMD_MAX_WALL_HALO + k) * es, es);
+  }
+  return list;
+}
+
+cudecompResult_t cudecompExtPlanHaloWallValueFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
+                                                    const bool periods[], int32_t dim, const int32_t pad[], int32_t centering,
+                                                    int32_t sides, int32_t n_fields, cudecompExtHaloPlan_t* out) {
+  try {
+    if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_WALL_VALUE_FIELDS) CD_INVALID_USAGE("n_fields argument out of range");
+  } catch (const Error& e) {
+    return fail(e);
+  }
+  HaloOp op = haloOp(HaloOp::WALL_VALUES, false, centering, false, n_fields);
+  op.sides = sides;
+  return planHaloOp(grid, rank, axis, halo, periods, dim, pad, op, false, out);
+}
+
+static KernelTuning tuningOfForce(int32_t force) {
+  KernelTuning t;
+  if (force & 1) t.force_class = MOVE_GENERIC;
+  if (force & 2) t.force_streaming = true;
+  if (force & 4) t.no_streaming = true;
+  return t;
+}
+
+cudecompResult_t cudecompExtRunWallFieldMoves(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
+                                             int32_t force, cudecompDataType_t dtype, uint32_t fields_neg, const void* addends,
+                                             hipStream_t stream, int32_t* n_launches) {
+  try {
+    if (!fields) CD_INVALID_USAGE("null argument");
+    const int es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
+    std::vector<WallAddends> converted;
+    std::vector<Move3D> list = importWallFieldMoves(moves, n, n_fields, es, fields_neg, addends, converted);
+    for (int32_t f = 0; f < n_fields; ++f)
+      if (!fields[f]) CD_INVALID_USAGE("null field buffer");
+    KernelStats st;
+    if (n_fields == 1) {  // the single call's path
+      for (Move3D& m : list) m.negate = (fields_neg & 1u) != 0;
+      void* bufs[3] = {fields[0], fields[0], nullptr};
+      const KernelTuning t = tuningOfForce(force);
+      launchMoves(list.data(), n, bufs, es, stream, &t, &st, nullptr, arithOf(dtype), nullptr, converted.data());
+    } else {
+      launchFieldWallList(list.data(), n, fields, n_fields, es, stream, force, &st, arithOf(dtype), fields_neg, converted.data());
+    }
+    if (n_launches) {
+      *n_launches = 0;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c) *n_launches += st.launches[c];
+    }
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+cudecompResult_t cudecompExtDescribeWallFieldMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
+                                                  int32_t n_fields, int32_t force, cudecompDataType_t dtype, uint32_t fields_neg,
+                                                  const void* addends, int32_t max_launches, int64_t* out, uint8_t* tables,
+                                                  int32_t* n_launches) {
+  try {
+    if (!field_addresses || !n_launches || max_launches < 0 || (max_launches > 0 && (!out || !tables))) CD_INVALID_USAGE("null argument");
+    const int es = elementSize(dtype);
+    std::vector<WallAddends> converted;
+    std::vector<Move3D> list = importWallFieldMoves(moves, n, n_fields, es, fields_neg, addends, converted);
+    std::vector<void*> fields(n_fields);
+    for (int32_t f = 0; f < n_fields; ++f) fields[f] = reinterpret_cast<void*>(field_addresses[f]);
+    int made = 0;
+    auto record = [&](const KernelChoice& k, int64_t blocks, int64_t per_field, int first, int count, const unsigned char* table) {
+      if (made < max_launches) {
+        const int64_t v[7] = {(int64_t)k.kind, k.vec, k.access, blocks, per_field, first, count};
+        std::memcpy(out + 7 * made, v, sizeof(v));
+        std::memcpy(tables + (size_t)CUDECOMP_EXT_WALL_FIELD_TABLE_BYTES * made, table, CUDECOMP_EXT_WALL_FIELD_TABLE_BYTES);
+      }
+      ++made;
+    };
+    if (n_fields == 1) {  // the single call's launches; their addends in the compact layout, h the most layers of the list
+      for (Move3D& m : list) m.negate = (fields_neg & 1u) != 0;
+      void* bufs[3] = {fields[0], fields[0], nullptr};
+      const KernelTuning t = tuningOfForce(force);
+      auto layersOf = [](const Move3D& m) {
+        for (int d = 0; d < 3; ++d)
+          if (m.ss[d] < 0) return (int)m.extent[d];
+        return 0;
+      };
+      int layers = 0;
+      for (const Move3D& m : list)
+        if (m.elements() != 0) layers = std::max(layers, layersOf(m));
+      for (const Launch& l : planLaunches(list.data(), n, bufs, es, &t, nullptr, arithOf(dtype))) {
+        unsigned char table[CUDECOMP_EXT_WALL_FIELD_TABLE_BYTES] = {0};
+        for (int i = 0; i < l.b.n; ++i) {
+          const Move3D& m = list[l.index[i]];
+          const int mine = layersOf(m), side = m.affine - 1;
+          for (int j = 0; j < mine; ++j) std::memcpy(table + ((size_t)i * layers + j) * es, converted[0].v[side][side == 0 ? mine - 1 - j : j], es);
+        }
+        record(l.k, l.blocks, l.blocks, 0, 1, table);
+      }
+    } else {
+      for (const FieldWallLaunch& w : planFieldWallLaunches(list.data(), n, fields.data(), n_fields, es, force, arithOf(dtype), fields_neg, converted.data()))
+        record(w.l.k, w.l.blocks, w.l.blocks_per_field, w.first_field, w.l.b.n_fields, reinterpret_cast<const unsigned char*>(w.table.w));
+    }
+    *n_launches = made;
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
 cudecompResult_t cudecompExtRunFieldMoves(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
                                          void* work, int64_t work_field_stride, int32_t es, int32_t force, hipStream_t stream,
                                          int32_t* n_launches) {

@@ -7,6 +7,7 @@
 #include "kernels_batch.h"
 
 #include <cstring>
+#include <vector>
 
 namespace cudecomp {
 
@@ -141,8 +142,14 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
                         (op.kind == HaloOp::REFLECT && (op.negate || op.n_fields >= 2));
   const ArithType arith = computes ? arithOf(c.dtype) : ARITH_NONE;
   // wall values: the addends are converted here, once per call, and travel to the launch by value -- read before the call returns
-  WallAddends addends;
-  if (wall) addends = wallAddendsOf(c.dtype, hh[c.dim], op.sides, c.values_low, c.values_high);
+  // (several fields: values_low / values_high are field-major, hh[dim] * nc doubles per field; each field's part by the single rule)
+  std::vector<WallAddends> addends(wall ? op.n_fields : 0);
+  if (wall) {
+    const size_t per_field = (size_t)hh[c.dim] * (size_t)(es / (arith == ARITH_F64 ? 8 : (arith == ARITH_F32 ? 4 : 2)));
+    for (int f = 0; f < op.n_fields; ++f)
+      addends[f] = wallAddendsOf(c.dtype, hh[c.dim], op.sides, c.values_low ? c.values_low + f * per_field : nullptr,
+                                 c.values_high ? c.values_high + f * per_field : nullptr);
+  }
   const int force = (h->tuning.force_class == MOVE_GENERIC ? 1 : 0) | (h->tuning.force_streaming ? 2 : 0) | (h->tuning.no_streaming ? 4 : 0);
   // The one or two sides of a phase go into ONE launch, unless they add onto overlapping cells (`ordered`): then one launch per
   // side, low side first.  Several fields: the list kernels (one_choice); either end of a move in a pencil is field f's, the fields'
@@ -152,7 +159,9 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
     const int n = (int)moves.size(), each = plan.ordered && moves[0].add ? 1 : n;
     if (op.n_fields == 1) {
       for (int i = 0; i < n; i += each)
-        launchMoves(moves.data() + i, each, bufs, es, c.stream, &h->tuning, nullptr, nullptr, arith, c.value, wall ? &addends : nullptr);
+        launchMoves(moves.data() + i, each, bufs, es, c.stream, &h->tuning, nullptr, nullptr, arith, c.value, wall ? addends.data() : nullptr);
+    } else if (wall) {  // one launch per run of fields whose addends fit the table (kernels.h launchFieldWallList)
+      launchFieldWallList(moves.data(), n, c.fields, op.n_fields, es, c.stream, force, nullptr, arith, c.fields_neg, addends.data());
     } else {
       const std::vector<i64> steps(n, plan.face_elements);
       for (int i = 0; i < n; i += each)

@@ -20,6 +20,7 @@
 #include "cudecomp_halo_fields.h"
 #include "cudecomp_halo_accumulate_fields.h"
 #include "cudecomp_halo_wall_fields.h"
+#include "cudecomp_halo_wall_value_fields.h"
 #include "cudecomp_transpose_fields.h"
 #include "decomp.h"
 #include "errors.h"
@@ -276,7 +277,8 @@ struct HaloCall {
   const void* value = nullptr;  // FILL
   int parity = 1, clear = 0;
   uint32_t fields_neg = 0;
-  // WALL_VALUES: the caller's host arrays (op.sides is the caller's number as it came; the runner checks all three after the centering)
+  // WALL_VALUES: the caller's host arrays (op.sides is the caller's number as it came; the runner checks all three after the centering);
+  // several fields: field-major, halo[dim] layers per field, and the parities travel as for REFLECT (`parity`, `fields_neg`)
   const double* values_low = nullptr;
   const double* values_high = nullptr;
   const int32_t* halo = nullptr;

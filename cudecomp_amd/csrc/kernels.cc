@@ -637,6 +637,8 @@ void spellKernelName(const KernelChoice& k) {
       snprintf(out, n, "generic_fields_fold_kernel<%s,%d,%s>", arithName(k.arith), k.es / arithBytes(k.arith),
                k.kind == K_GENERIC_FIELDS_FOLD_TAKE ? "true" : "false");
       break;
+    case K_ROWS_FIELDS_WALL: snprintf(out, n, "rows_fields_wall_kernel<%s,%d,%d>", arithName(k.arith), k.vec, s); break;
+    case K_GENERIC_FIELDS_WALL: snprintf(out, n, "generic_fields_wall_kernel<%s,%d>", arithName(k.arith), k.es); break;
   }
 }
 
@@ -724,7 +726,9 @@ void launchBatch(const Launch& l, const Move3D* moves, const void* fill_value, c
     case K_ROWS_FIELDS_FOLD:
     case K_GENERIC_FIELDS_FOLD:
     case K_ROWS_FIELDS_FOLD_TAKE:
-    case K_GENERIC_FIELDS_FOLD_TAKE: CD_INTERNAL_ERROR("lists of field-moves are launched by launchFieldMoveList");
+    case K_GENERIC_FIELDS_FOLD_TAKE:
+    case K_ROWS_FIELDS_WALL:
+    case K_GENERIC_FIELDS_WALL: CD_INTERNAL_ERROR("lists of field-moves are launched by launchFieldMoveList and launchFieldWallList");
   }
 }
 
@@ -883,6 +887,13 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
   if (!mirrored && fields_neg != 0) CD_INTERNAL_ERROR("only mirrored field-moves carry signs");
   if (mirrored && n_fields < kMaxFields && (fields_neg >> n_fields) != 0) CD_INTERNAL_ERROR("sign bit of a field the list does not have");
   if (mirrored && take && !add) CD_INTERNAL_ERROR("a mirrored field-move that clears its source must add (fold)");
+  // wall field-moves (kernels_field_wall.hip): a mirrored list whose moves all name a side (Move3D::affine); neither adds nor takes
+  bool wall = false;
+  for (int i = 0; i < n; ++i) {
+    if (i == 0) wall = moves[i].affine != 0;
+    else if ((moves[i].affine != 0) != wall) CD_INTERNAL_ERROR("the field-moves of one list carry different operations");
+  }
+  if (wall && (!mirrored || add || take)) CD_INTERNAL_ERROR("wall field-moves are mirrored and neither add onto their destination nor take");
 
   // each move's shared geometry, normalised, its ends, and the addresses every field's first element can have or-ed together (the
   // 2-byte rule: all fields' pencils and all workspace pieces)
@@ -896,8 +907,10 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     if (mirrored) {
       // the moves of kernels_field_mirror.hip: reflect- or fold-moves between cells of the fields' own buffers; their signs travel
       // in fields_neg, never in the move
-      if (!in.reflect || in.negate || in.affine != 0 || in.fill || in.dst_row_pitch != 0 || in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK)
+      if (!in.reflect || in.negate || in.fill || in.dst_row_pitch != 0 || in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK)
         CD_INTERNAL_ERROR("mirrored field-moves reflect or fold exactly their cells of the fields' buffers, unsigned");
+      if (wall && ((in.affine != 1 && in.affine != 2) || wallLayers(in) < 0))
+        CD_INTERNAL_ERROR("wall field-move without a side or a mirrored dim, or with more layers than the addend table holds");
     } else if (in.fill || in.reflect || in.negate || in.affine != 0 || in.dst_row_pitch != 0) {
       CD_INTERNAL_ERROR("field-moves copy, add or take exactly their cells");
     }
@@ -968,7 +981,8 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
       if (m.ds[2] == 1) t = 2;
     }
     if (one_choice ? all_rows : (!force_generic && rows_fit[i])) {
-      if (mirrored) c.k.kind = add ? (take ? K_ROWS_FIELDS_FOLD_TAKE : K_ROWS_FIELDS_FOLD) : K_ROWS_FIELDS_REFLECT;
+      if (wall) c.k.kind = K_ROWS_FIELDS_WALL;
+      else if (mirrored) c.k.kind = add ? (take ? K_ROWS_FIELDS_FOLD_TAKE : K_ROWS_FIELDS_FOLD) : K_ROWS_FIELDS_REFLECT;
       else c.k.kind = take ? (add ? K_ROWS_FIELDS_ADD_TAKE : K_ROWS_FIELDS_TAKE) : (add ? K_ROWS_FIELDS_ADD : K_ROWS_FIELDS);
       c.k.access = streaming ? 1 : 0;
       rowVectors(c, m, lanes);
@@ -989,7 +1003,8 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
       c.t1 = (unsigned int)((c.dm.e[1] + c.k.tj - 1) / c.k.tj);
       c.blocks = (unsigned long long)c.t0 * c.t1 * (unsigned long long)c.dm.e[2];
     } else {
-      if (mirrored) c.k.kind = add ? (take ? K_GENERIC_FIELDS_FOLD_TAKE : K_GENERIC_FIELDS_FOLD) : K_GENERIC_FIELDS_REFLECT;
+      if (wall) c.k.kind = K_GENERIC_FIELDS_WALL;
+      else if (mirrored) c.k.kind = add ? (take ? K_GENERIC_FIELDS_FOLD_TAKE : K_GENERIC_FIELDS_FOLD) : K_GENERIC_FIELDS_REFLECT;
       else c.k.kind = take ? (add ? K_GENERIC_FIELDS_ADD_TAKE : K_GENERIC_FIELDS_TAKE) : (add ? K_GENERIC_FIELDS_ADD : K_GENERIC_FIELDS);
       c.k.access = 0;
       genericGeometry(c, m, mirrored);  // (mirrored, without a destination-fast dim: along the longest, as the single calls)
@@ -1001,6 +1016,9 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
       fm.ss[d] = c.dm.ss[d];
       fm.ds[d] = c.dm.ds[d];
     }
+    c.p1 = -1;  // wall field-moves: the entry of the kernel's e[] whose index is the destination layer (the mirrored one)
+    for (int d = 0; wall && d < 3; ++d)
+      if (m.ss[d] < 0) c.p1 = d;
     fm.p0 = c.p0;
     fm.t0 = c.t0;
     fm.t1 = c.t1;
@@ -1036,6 +1054,7 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
       l.elements += cs[j].elements * n_fields;
       l.blocks_per_field += (unsigned int)cs[j].blocks;
       l.index[b.n] = index[j];
+      l.along[b.n] = cs[j].p1;
       ++b.n;
       done[j] = true;
     }
@@ -1051,6 +1070,7 @@ void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void
                          bool mirrored, unsigned int fields_neg) {
   for (const FieldMoveLaunch& l :
        planFieldMoveLaunches(moves, work_steps, n, inputs, outputs, n_fields, work, es, force, one_choice, arith, mirrored, fields_neg)) {
+    if (l.k.kind >= K_ROWS_FIELDS_WALL) CD_INTERNAL_ERROR("wall field-moves are launched by launchFieldWallList, with their addends");
     spellKernelName(l.k);
     ++g_data_launches;
     if (l.k.kind >= K_ROWS_FIELDS_REFLECT) launchFieldMirrorBatch(l.k, l.b, l.fields_neg, l.blocks, stream);
@@ -1059,6 +1079,71 @@ void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void
     if (stats) {
       stats->launches[l.cls] += 1;
       stats->elements[l.cls] += l.elements;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// lists of wall field-moves (kernels.h; kernels_field_wall.hip)
+// ---------------------------------------------------------------------------------------------
+int fieldsPerWallLaunch(int sides, int layers, int es) {
+  if (sides < 1 || sides > kMaxBatch || layers < 1 || layers > kMaxWallHalo || (es != 2 && es != 4 && es != 8 && es != 16))
+    CD_INTERNAL_ERROR("wall field-moves out of the addend table's range");
+  return std::min(kMaxFields, kFieldWallTableBytes / (sides * layers * es));
+}
+
+std::vector<FieldWallLaunch> planFieldWallLaunches(const Move3D* moves, int n, void* const* fields, int n_fields, int es, int force,
+                                                   ArithType arith, unsigned int fields_neg, const WallAddends* addends) {
+  if (n_fields < 1 || n_fields > kMaxFields || !fields) CD_INTERNAL_ERROR("field count out of range");
+  if (n < 0 || n > 2 || (n > 0 && !moves)) CD_INTERNAL_ERROR("wall field-moves: the one or two sides of a call");
+  if (n_fields < kMaxFields && (fields_neg >> n_fields) != 0) CD_INTERNAL_ERROR("sign bit of a field the list does not have");
+  if (!addends) CD_INTERNAL_ERROR("wall field-moves without the call's addends");
+  std::vector<FieldWallLaunch> out;
+  // S, the sides written, and h, the layers: those of the moves that have cells
+  int sides = 0, layers = 0;
+  for (int i = 0; i < n; ++i) {
+    if (moves[i].elements() == 0) continue;
+    const int mine = wallLayers(moves[i]);
+    if (mine < 0 || (moves[i].affine != 1 && moves[i].affine != 2))
+      CD_INTERNAL_ERROR("wall field-move without a side or a mirrored dim, or with more layers than the addend table holds");
+    layers = std::max(layers, mine);
+    ++sides;
+  }
+  if (sides == 0) return out;
+  const int per_launch = fieldsPerWallLaunch(sides, layers, es);
+  for (int f0 = 0; f0 < n_fields; f0 += per_launch) {
+    const int nf = std::min(per_launch, n_fields - f0);
+    const unsigned int neg = (fields_neg >> f0) & (nf == kMaxFields ? 0xffffffffu : ((1u << nf) - 1u));
+    std::vector<FieldMoveLaunch> ls = planFieldMoveLaunches(moves, nullptr, n, fields + f0, fields + f0, nf, nullptr, es, force, true, arith, true, neg);
+    if (ls.size() != 1 || ls[0].b.n != sides) CD_INTERNAL_ERROR("the sides of a wall-value call did not come out as one launch");
+    FieldWallLaunch w{};
+    w.l = ls[0];
+    w.first_field = f0;
+    w.walk.layers = layers;
+    w.walk.es = es;
+    unsigned char* bytes = reinterpret_cast<unsigned char*>(w.table.w);
+    for (int i = 0; i < w.l.b.n; ++i) {
+      const Move3D& m = moves[w.l.index[i]];
+      const int mine = wallLayers(m), side = m.affine - 1;
+      w.walk.along[i] = w.l.along[i];
+      for (int f = 0; f < nf; ++f)
+        for (int j = 0; j < mine; ++j)  // destination order: the low side reversed, as wallTableRow
+          std::memcpy(bytes + ((size_t)(i * nf + f) * layers + j) * es, addends[f0 + f].v[side][side == 0 ? mine - 1 - j : j], es);
+    }
+    out.push_back(w);
+  }
+  return out;
+}
+
+void launchFieldWallList(const Move3D* moves, int n, void* const* fields, int n_fields, int es, hipStream_t stream, int force,
+                         KernelStats* stats, ArithType arith, unsigned int fields_neg, const WallAddends* addends) {
+  for (const FieldWallLaunch& w : planFieldWallLaunches(moves, n, fields, n_fields, es, force, arith, fields_neg, addends)) {
+    spellKernelName(w.l.k);
+    ++g_data_launches;
+    launchFieldWallBatch(w.l.k, w.l.b, w.l.fields_neg, w.table, w.walk, w.l.blocks, stream);
+    if (stats) {
+      stats->launches[w.l.cls] += 1;
+      stats->elements[w.l.cls] += w.l.elements;
     }
   }
 }

@@ -128,6 +128,7 @@ struct FieldMoveLaunch {
   MoveClass cls;
   i64 elements;                   // of all its moves and fields
   int index[kern::kMaxBatch];     // index[i]: the list entry b.m[i] is
+  int along[kern::kMaxBatch];     // wall field-moves: the entry of b.m[i].e[] whose index is the destination layer (-1 otherwise)
 };
 // WHICH launches launchFieldMoveList makes, in order (pure host code, no device needed; buffers are only looked at as addresses)
 std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i64* work_steps, int n, void* const* inputs,
@@ -138,7 +139,30 @@ void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void
                          void* work, int es, hipStream_t stream, int force = 0, KernelStats* stats = nullptr, bool one_choice = false,
                          ArithType arith = ARITH_NONE, bool mirrored = false, unsigned int fields_neg = 0);
 
-// data-movement launches this process has made so far (launchMoves and launchFieldMoveList; tests count launches per call with it)
+// ---- lists of WALL field-moves (kernels_field_wall.hip): the one or two sides of a multi-field wall-value call
+// (include/cudecomp_halo_wall_value_fields.h) ----
+// moves[0 .. n - 1], n <= 2, are wall-moves (Move3D::reflect with Move3D::affine naming the side, no Move3D::negate) between cells of
+// the fields' own buffers; bit f of `fields_neg` flips the sign bits of field f's source first; addends[f] holds field f's converted
+// addends per side and ghost layer (WallAddends, kernels_batch.h), read before the call returns.  Classification is that of the
+// mirrored lists with one_choice (planFieldMoveLaunches above): one kernel choice for the sides, rows or element by element.
+// Launch rule: with S the moves that have cells, h the layers (the extent of the mirrored dim) and es the element size, one launch
+// serves F = min(kern::kMaxFields, kern::kFieldWallTableBytes / (S * h * es)) consecutive fields -- what its compact addend table
+// holds -- and the list makes ceil(n_fields / F) launches in field order.  Access: the reflection's rule by the size of one field's
+// move (unmeasured for these kernels); the element-wise kernel always caches.
+struct FieldWallLaunch {
+  FieldMoveLaunch l;           // its fields are fields[first_field .. first_field + l.b.n_fields)
+  kern::FieldWallTable table;  // entry (move i of the launch, field f of the launch, destination layer j) at ((i * nf + f) * h + j) * es
+  kern::FieldWallWalk walk;
+  int first_field;
+};
+int fieldsPerWallLaunch(int sides, int layers, int es);  // F of the rule above
+// WHICH launches launchFieldWallList makes, in order (pure host code, no device needed; buffers are only looked at as addresses)
+std::vector<FieldWallLaunch> planFieldWallLaunches(const Move3D* moves, int n, void* const* fields, int n_fields, int es, int force,
+                                                   ArithType arith, unsigned int fields_neg, const WallAddends* addends);
+void launchFieldWallList(const Move3D* moves, int n, void* const* fields, int n_fields, int es, hipStream_t stream, int force,
+                         KernelStats* stats, ArithType arith, unsigned int fields_neg, const WallAddends* addends);
+
+// data-movement launches this process has made so far (launchMoves, launchFieldMoveList and launchFieldWallList; tests count launches per call with it)
 long long dataLaunchCount();
 
 // name (template spelling) of the data-movement kernel launched last by this process, "" before the first launch

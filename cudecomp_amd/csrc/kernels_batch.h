@@ -5,7 +5,8 @@
 // kernels_rotate.hip and sync.hip are launched by the executor (and compiled as one unit, kernels_executor.hip; kernels_fill.hip and kernels_reflect.hip likewise as kernels_edge.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
 // halo phases and transposes), kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) and
 // kernels_field_mirror.hip (the same lists mirrored, with a sign per field: multi-field wall halos) are reached through
-// launchFieldMoveList (kernels.h).  Seventeen code objects in all.  The row and element-wise kernels of all of
+// launchFieldMoveList (kernels.h); kernels_field_wall.hip (the mirrored lists adding an addend per field and layer: multi-field wall
+// values, reached through launchFieldWallList) is compiled into the unit kernels_executor.hip.  Seventeen code objects in all.  The row and element-wise kernels of all of
 // them share one workgroup decode (kernels_walk.h) and their launchers one dispatch (kernels_dispatch.h).
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single
@@ -116,6 +117,26 @@ struct FieldMoveBatch {
 };
 static_assert(sizeof(FieldMoveBatch) < 4096, "FieldMoveBatch must fit the kernel arguments");
 
+// The addends of a launch of wall field-moves (kernels_field_wall.hip: multi-field wall values,
+// include/cudecomp_halo_wall_value_fields.h): a kernel argument of its own beside the FieldMoveBatch, which stays as it is.  Fields x
+// sides x layers entries of 16 bytes would be 8 KB, so the table is COMPACT: kFieldWallTableBytes of `es`-byte entries, each the
+// converted element once.  The entry of (move i of the launch, field f of the launch, DESTINATION layer j along the mirrored dim)
+// sits at byte ((i * n_fields + f) * layers + j) * es; the host has reversed the low side (kernels.cc fieldWallTableOf).  A lane
+// holds whole elements and starts on an element's boundary: it replicates the entry to its width in registers, no phase arises.
+constexpr int kFieldWallTableBytes = 2048;
+struct FieldWallTable {
+  unsigned int w[kFieldWallTableBytes / 4];
+};
+// ... and how the kernels find a lane's entry: `layers` of the formula above, the element size, and per move of the launch the entry
+// of the kernel's e[] whose index is the destination layer -- Batch::p1's meaning for wall-moves (rows: 1 the row, 2 the plane;
+// element-wise: the dim; -1: the mirrored dim is one cell thick, layer 0).
+struct FieldWallWalk {
+  int layers, es;
+  int along[kMaxBatch];
+};
+static_assert(sizeof(FieldMoveBatch) + sizeof(FieldWallTable) + sizeof(FieldWallWalk) + 16 + 8 <= 4096,
+              "FieldMoveBatch, addend table, walk, sign mask and the mask of fields stay under the 4 KB of kernel arguments");
+
 }  // namespace kern
 
 // ---- what runs: one record per kernel choice ----------------------------------------------------------------------------------
@@ -159,7 +180,9 @@ enum KernelKind {
   K_ROWS_FIELDS_FOLD_TAKE,    // rows_fields_fold_kernel with TAKE (... ; src = 0) = 35
   K_GENERIC_FIELDS_FOLD_TAKE, // generic_fields_fold_kernel with TAKE = 36
   K_ROWS_WALL,                // rows_wall_kernel (dst = +-src + addend of the destination layer, the source backwards along the row or plane index) = 37
-  K_GENERIC_WALL              // generic_wall_kernel = 38
+  K_GENERIC_WALL,             // generic_wall_kernel = 38
+  K_ROWS_FIELDS_WALL,         // rows_fields_wall_kernel (dst = +-src per field + the field's addend of the destination layer) = 39
+  K_GENERIC_FIELDS_WALL       // generic_fields_wall_kernel = 40
 };
 struct KernelChoice {
   KernelKind kind;
@@ -171,7 +194,7 @@ struct KernelChoice {
                     // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it);
                     // reflections and wall-moves: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores;
                     // field-moves: 0, 1 non-temporal loads and stores; transpose_fields_kernel: 0, 2; adding / taking
-                    // field-moves: as additions / takes; mirrored field-moves: as reflections / folds
+                    // field-moves: as additions / takes; mirrored field-moves: as reflections / folds; wall field-moves: as reflections
   ArithType arith;  // additions, folds, wall-moves, reflections that flip the sign bits, mirrored field-moves (whatever their signs):
                     // the real type the elements consist of; ARITH_NONE otherwise
   bool neg;         // folds, wall-moves: the sign bits of the source are flipped before the addition (one sign mask per launch)
@@ -250,12 +273,14 @@ constexpr KindTraits kKindTraits[] = {
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_FOLD_TAKE
     {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_WALL
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_WALL
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FIELDS_WALL
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_WALL
 };
-static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_WALL + 1, "one row per KernelKind");
+static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_FIELDS_WALL + 1, "one row per KernelKind");
 
 // the row of a kind; a value outside the enum is an internal error, never a read past the table
 inline const KindTraits& kindTraits(KernelKind kind) {
-  if (kind < K_ROWS || kind > K_GENERIC_WALL) CD_INTERNAL_ERROR("kernel kind out of range");
+  if (kind < K_ROWS || kind > K_GENERIC_FIELDS_WALL) CD_INTERNAL_ERROR("kernel kind out of range");
   return kKindTraits[kind];
 }
 inline MoveClass classOf(KernelKind kind) { return kindTraits(kind).cls; }
@@ -340,6 +365,11 @@ void launchFieldAccumulateBatch(const KernelChoice& k, const kern::FieldMoveBatc
 // the way (the mask of that type and fields_neg travel as kernel arguments of their own).  Local buffers only.
 void launchFieldMirrorBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, unsigned int fields_neg, unsigned int blocks,
                             hipStream_t stream);
+// kernels_field_wall.hip: lists of wall field-moves (reflect-moves with Move3D::affine: SIGNED source strides, rows in bytes, generic
+// in elements).  k.arith: the real type of the addition, always; bit f of fields_neg: the sign bits of field f's source are flipped
+// first; `table` and `walk` as above.  Lanes never narrower than one element.  Local buffers only.
+void launchFieldWallBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, unsigned int fields_neg, const kern::FieldWallTable& table,
+                          const kern::FieldWallWalk& walk, unsigned int blocks, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

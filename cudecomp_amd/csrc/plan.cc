@@ -712,7 +712,15 @@ HaloPlan buildHaloOpPlan(const GridShape& g, int rank, int axis, int dim, const 
     case HaloOp::FILL: return buildHaloFillPlan(g, rank, axis, dim, halo, periods, pad, force_packed, self_exchange);
     case HaloOp::REFLECT: return buildHaloReflectPlan(g, rank, axis, dim, halo, periods, pad, op.centering, op.negate, self_exchange);
     case HaloOp::FOLD: return buildHaloFoldPlan(g, rank, axis, dim, halo, periods, pad, op.centering, op.negate, op.clear, self_exchange);
-    case HaloOp::WALL_VALUES: return buildHaloWallValuesPlan(g, rank, axis, dim, halo, periods, pad, op.centering, op.negate, op.sides, self_exchange);
+    case HaloOp::WALL_VALUES: {
+      // several fields (cudecomp_halo_wall_value_fields.h): the single call's moves, one per side kept, unsigned -- parities and
+      // addends travel with the call and are no part of the plan
+      if (op.n_fields < 1) CD_INTERNAL_ERROR("a wall-value plan without a field");
+      if (op.n_fields != 1 && op.negate) CD_INTERNAL_ERROR("the parities of a multi-field wall call are no part of its plan");
+      HaloPlan p = buildHaloWallValuesPlan(g, rank, axis, dim, halo, periods, pad, op.centering, op.negate, op.sides, self_exchange);
+      p.op.n_fields = op.n_fields;
+      return p;
+    }
   }
   CD_INTERNAL_ERROR("unknown halo operation");
 }

@@ -200,8 +200,8 @@ struct HaloOp {
   enum Kind { UPDATE, ACCUMULATE, FILL, REFLECT, FOLD, WALL_VALUES } kind = UPDATE;
   bool clear = false;  // ACCUMULATE, FOLD: the ghost cells read are cleared
   int centering = 0;   // REFLECT, FOLD, WALL_VALUES
-  bool negate = false; // REFLECT, FOLD of ONE field, WALL_VALUES: parity -1 (several fields: false; their parities travel with the call)
-  int n_fields = 1;    // UPDATE, ACCUMULATE, REFLECT, FOLD (1 for FILL and WALL_VALUES)
+  bool negate = false; // REFLECT, FOLD, WALL_VALUES of ONE field: parity -1 (several fields: false; their parities travel with the call)
+  int n_fields = 1;    // UPDATE, ACCUMULATE, REFLECT, FOLD, WALL_VALUES (1 for FILL)
   int sides = 3;       // WALL_VALUES: bit 0 the low halo, bit 1 the high halo (it changes the moves; the addends do not and are
                        // no part of the record: calls that differ only in them share a plan)
   bool operator<(const HaloOp& o) const {

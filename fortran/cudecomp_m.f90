@@ -643,6 +643,67 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompAmdSetWallHalosZ_C
 
+    ! cudecomp_halo_wall_value_fields.h: wall values of several pencils, each with a parity and addends of its own
+    function cudecompAmdSetWallFieldHalosX_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, sides, values_low, &
+                                             values_high, halo_extents, halo_periods, dim, padding, stream) &
+      bind(C, name="cudecompAmdSetWallFieldHalosX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*)
+      integer(c_int32_t), value :: n_fields
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: parities(*)
+      integer(c_int32_t), value :: centering, sides
+      type(c_ptr), value :: values_low, values_high  ! host arrays of doubles, field-major (NULL for a side that `sides` does not name)
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdSetWallFieldHalosX_C
+
+    function cudecompAmdSetWallFieldHalosY_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, sides, values_low, &
+                                             values_high, halo_extents, halo_periods, dim, padding, stream) &
+      bind(C, name="cudecompAmdSetWallFieldHalosY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*)
+      integer(c_int32_t), value :: n_fields
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: parities(*)
+      integer(c_int32_t), value :: centering, sides
+      type(c_ptr), value :: values_low, values_high  ! host arrays of doubles, field-major (NULL for a side that `sides` does not name)
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdSetWallFieldHalosY_C
+
+    function cudecompAmdSetWallFieldHalosZ_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, sides, values_low, &
+                                             values_high, halo_extents, halo_periods, dim, padding, stream) &
+      bind(C, name="cudecompAmdSetWallFieldHalosZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: inputs(*)
+      integer(c_int32_t), value :: n_fields
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: parities(*)
+      integer(c_int32_t), value :: centering, sides
+      type(c_ptr), value :: values_low, values_high  ! host arrays of doubles, field-major (NULL for a side that `sides` does not name)
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdSetWallFieldHalosZ_C
+
     ! cudecomp_halo_fold.h: halo folding (the ghost cells the reflection writes, summed into their mirror images)
     function cudecompAmdFoldHalosX_C(handle, grid_desc, input, dtype, parity, centering, clear, halo_extents, halo_periods, dim, &
                                         padding, stream) bind(C, name="cudecompAmdFoldHalosX") result(res)
@@ -2101,6 +2162,110 @@ contains
     res = cudecompAmdFoldFieldHalosZ_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), int(dtype, c_int), par, &
                                            int(centering, c_int32_t), int(clear, c_int32_t), h, per, int(dim - 1, c_int32_t), p, s)
   end function cudecompAmdFoldFieldHalosZ
+
+
+  ! ---- multi-field wall values (include/cudecomp_halo_wall_value_fields.h): n_fields pencils, a parity and addends per field -----
+  ! the arguments of cudecompAmdSetWallHalosX with the list of fields and its length in the place of `input`, the list of parities
+  ! (+1 / -1 per field) in the place of `parity`, and values_low / values_high field-major: halo_extents(dim) doubles per field
+  ! (complex types: twice as many), field 1 first, layer 1 next to the wall
+  function cudecompAmdSetWallFieldHalosX(handle, grid_desc, inputs, n_fields, dtype, parities, centering, sides, values_low, values_high, &
+                                         halo_extents, halo_periods, dim, padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    integer :: dtype
+    integer, intent(in) :: parities(n_fields)  ! per field, +1: even mirror; -1: odd mirror (sign bits flipped)
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: sides      ! 1: the low halo; 2: the high halo; 3: both
+    ! host arrays, read before the call returns; the one of a side that `sides` does not name may be left out
+    real(c_double), optional, target :: values_low(*), values_high(*)
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3), par(max(n_fields, 1))
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    type(c_ptr) :: lo, hi
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    par = 0
+    if (n_fields >= 1) par(1:n_fields) = int(parities, c_int32_t)
+    lo = c_null_ptr
+    hi = c_null_ptr
+    if (present(values_low)) lo = c_loc(values_low)
+    if (present(values_high)) hi = c_loc(values_high)
+    res = cudecompAmdSetWallFieldHalosX_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), int(dtype, c_int), par, &
+                                           int(centering, c_int32_t), int(sides, c_int32_t), lo, hi, h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdSetWallFieldHalosX
+
+  function cudecompAmdSetWallFieldHalosY(handle, grid_desc, inputs, n_fields, dtype, parities, centering, sides, values_low, values_high, &
+                                         halo_extents, halo_periods, dim, padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    integer :: dtype
+    integer, intent(in) :: parities(n_fields)  ! per field, +1: even mirror; -1: odd mirror (sign bits flipped)
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: sides      ! 1: the low halo; 2: the high halo; 3: both
+    ! host arrays, read before the call returns; the one of a side that `sides` does not name may be left out
+    real(c_double), optional, target :: values_low(*), values_high(*)
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3), par(max(n_fields, 1))
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    type(c_ptr) :: lo, hi
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    par = 0
+    if (n_fields >= 1) par(1:n_fields) = int(parities, c_int32_t)
+    lo = c_null_ptr
+    hi = c_null_ptr
+    if (present(values_low)) lo = c_loc(values_low)
+    if (present(values_high)) hi = c_loc(values_high)
+    res = cudecompAmdSetWallFieldHalosY_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), int(dtype, c_int), par, &
+                                           int(centering, c_int32_t), int(sides, c_int32_t), lo, hi, h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdSetWallFieldHalosY
+
+  function cudecompAmdSetWallFieldHalosZ(handle, grid_desc, inputs, n_fields, dtype, parities, centering, sides, values_low, values_high, &
+                                         halo_extents, halo_periods, dim, padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    integer :: n_fields
+    type(c_ptr), intent(in) :: inputs(n_fields)
+    integer :: dtype
+    integer, intent(in) :: parities(n_fields)  ! per field, +1: even mirror; -1: odd mirror (sign bits flipped)
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: sides      ! 1: the low halo; 2: the high halo; 3: both
+    ! host arrays, read before the call returns; the one of a side that `sides` does not name may be left out
+    real(c_double), optional, target :: values_low(*), values_high(*)
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3), par(max(n_fields, 1))
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    type(c_ptr) :: lo, hi
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    par = 0
+    if (n_fields >= 1) par(1:n_fields) = int(parities, c_int32_t)
+    lo = c_null_ptr
+    hi = c_null_ptr
+    if (present(values_low)) lo = c_loc(values_low)
+    if (present(values_high)) hi = c_loc(values_high)
+    res = cudecompAmdSetWallFieldHalosZ_C(handle, grid_desc, inputs, int(n_fields, c_int32_t), int(dtype, c_int), par, &
+                                           int(centering, c_int32_t), int(sides, c_int32_t), lo, hi, h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdSetWallFieldHalosZ
 
 
   ! ---- multi-field transposes (include/cudecomp_transpose_fields.h): n_fields pencils, one exchange ------------------------

@@ -488,6 +488,38 @@ cudecompResult_t cudecompExtDescribeMirroredFieldMoves(const cudecompExtMove_t* 
                                                       int32_t n_fields, int32_t es, int32_t force, int32_t mode,
                                                       cudecompDataType_t dtype, uint32_t fields_neg, int64_t out[5]);
 
+/* ... and for WALL field-moves with a sign and addends per field (kernels_field_wall.hip; csrc/kernels.h launchFieldWallList, the
+ * runner of cudecompAmdSetWallFieldHalos*, cudecomp_halo_wall_value_fields.h): moves[0 .. n - 1], n <= 2, are reflect-moves as
+ * above whose `peer` names the side whose addends they take (0 low, 1 high) and whose mirrored dim has at most
+ * CUDECOMP_AMD_MAX_WALL_HALO layers; both ends in field f's own buffer.  `dtype` names the element type (its element size is the
+ * list's); bit f of `fields_neg` flips the sign bits of field f's source before the addition.  `addends` holds RAW elements, already
+ * of `dtype`: element ((f * 2 + side) * CUDECOMP_AMD_MAX_WALL_HALO + k) is the addend of ghost layer k, counted from the wall
+ * outward, of side `side` of field f.  n_fields == 1 runs as the single wall-moves do (kinds 37 / 38, csrc/kernels.h launchMoves);
+ * otherwise one launch serves F = min(32, 2048 / (S * h * es)) consecutive fields, S the moves that have cells and h the most
+ * layers among them.  Describe (no launch, no GPU) writes for each of the first `max_launches` launches seven numbers to
+ * out[7 * l ...] -- kind (37 rows_wall_kernel, 38 generic_wall_kernel, 39 rows_fields_wall_kernel, 40 generic_fields_wall_kernel),
+ * bytes per lane, access mode, workgroups, workgroups per field, first field, fields in the launch -- and the launch's
+ * CUDECOMP_EXT_WALL_FIELD_TABLE_BYTES of addend table to tables[2048 * l ...]: the entry of (move i of the launch, field f of the
+ * launch, DESTINATION layer j) at byte ((i * fields + f) * h + j) * es, the low side reversed; *n_launches is the number the list
+ * makes, whatever max_launches.
+ *
+ * cudecompExtPlanHaloWallValueFields: the plan cudecompAmdSetWallFieldHalos{X,Y,Z} would run on `rank` for n_fields fields, stateless
+ * like cudecompExtPlanHaloWallValues: its moves are the single call's for the sides kept, unsigned (parities and addends travel with
+ * the call and are no part of the plan), to be carried out for every field.  It makes the plan's own checks only: n_fields outside
+ * 1 .. CUDECOMP_AMD_MAX_WALL_VALUE_FIELDS (INVALID_USAGE), what the fill refuses, centering, sides, width, the mirror's reach. */
+#define CUDECOMP_EXT_WALL_FIELD_TABLE_BYTES 2048
+cudecompResult_t cudecompExtPlanHaloWallValueFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
+                                                    const int32_t halo_extents[], const bool halo_periods[], int32_t dim,
+                                                    const int32_t padding[], int32_t centering, int32_t sides, int32_t n_fields,
+                                                    cudecompExtHaloPlan_t* plan);
+cudecompResult_t cudecompExtRunWallFieldMoves(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
+                                             int32_t force, cudecompDataType_t dtype, uint32_t fields_neg, const void* addends,
+                                             hipStream_t stream, int32_t* n_launches);
+cudecompResult_t cudecompExtDescribeWallFieldMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
+                                                  int32_t n_fields, int32_t force, cudecompDataType_t dtype, uint32_t fields_neg,
+                                                  const void* addends, int32_t max_launches, int64_t* out, uint8_t* tables,
+                                                  int32_t* n_launches);
+
 /* The plan cudecompAmdTransposeFields{XToY,YToZ,ZToY,YToX} (cudecomp_transpose_fields.h) would run on `rank` for n_fields fields
  * (csrc/plan.h buildTransposeFieldsPlan), stateless like cudecompExtPlanTranspose and with its arguments.  pack / unpack are the
  * moves of FIELD 0: an end in buffer 0 / 1 is field f's input / output pencil at the same offset, an end in buffer 2 (the

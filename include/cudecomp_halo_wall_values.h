@@ -64,8 +64,11 @@ extern "C" {
  * side that would be written.  Otherwise the call succeeds; without a usable device the result is CUDECOMP_RESULT_CUDA_ERROR only
  * when there are cells to write.
  *
- * Out of scope: a multi-field form with addends per field; addends that vary along the wall (a plane of values); halos wider
- * than CUDECOMP_AMD_MAX_WALL_HALO; an adjoint ("fold") of the affine call; the performance report and the autotuner.
+ * Several fields at once, each with a parity and addends of its own: cudecompAmdSetWallFieldHalos{X,Y,Z},
+ * cudecomp_halo_wall_value_fields.h.
+ *
+ * Out of scope: addends that vary along the wall (a plane of values); halos wider than CUDECOMP_AMD_MAX_WALL_HALO; an adjoint
+ * ("fold") of the affine call; the performance report and the autotuner.
  */
 cudecompResult_t cudecompAmdSetWallHalosX(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
                                           cudecompDataType_t dtype, int32_t parity, int32_t centering, int32_t sides,
