@@ -26,6 +26,19 @@ cudecompResult_t fail(const Error& e) {
   return e.code();
 }
 
+// every entry point's body runs in here (api.cc: CD_API_CATCH): an Error is reported and becomes its result code
+template <typename Body>
+cudecompResult_t guarded(Body&& body) {
+  try {
+    body();
+  } catch (const Error& e) {
+    return fail(e);
+  } catch (...) {
+    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  }
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
 // tests: "the cells between consecutive destination rows are the move's to rewrite" -- the pitch of consecutive rows is the
 // smallest destination stride among the dims that are not the unit-stride one
 i64 wholeRowsPitchOf(const Move3D& m) {
@@ -178,6 +191,52 @@ KernelTuning tuningOfFlags(int32_t flags) {  // the bits of cudecompExtMove3D
   return t;
 }
 
+KernelTuning tuningOfForce(int32_t force) {  // the `force` bits of the entries that take nothing else: 1, 2, 4
+  KernelTuning t;
+  if (force & 1) t.force_class = MOVE_GENERIC;
+  if (force & 2) t.force_streaming = true;
+  if (force & 4) t.no_streaming = true;
+  return t;
+}
+
+std::vector<void*> pointersOf(const uint64_t* addresses, int32_t n) {
+  std::vector<void*> p(n);
+  for (int32_t i = 0; i < n; ++i) p[i] = reinterpret_cast<void*>(addresses[i]);
+  return p;
+}
+
+int launchesOf(const KernelStats& st) {
+  int total = 0;
+  for (int c = 0; c < MOVE_CLASS_COUNT; ++c) total += st.launches[c];
+  return total;
+}
+
+// the cudecompExt*3D entries: the geometry of their one move from BUF_IN to BUF_OUT (a fill has no source strides) ...
+Move3D move3DOf(const int64_t extent[3], const int64_t ss[3], const int64_t ds[3]) {
+  Move3D m;
+  m.src_buf = BUF_IN;
+  m.dst_buf = BUF_OUT;
+  for (int i = 0; i < 3; ++i) {
+    m.extent[i] = extent[i];
+    if (ss) m.ss[i] = ss[i];
+    m.ds[i] = ds[i];
+  }
+  return m;
+}
+
+// ... and its launch with what the entry honours of its `force` bits; *kernel_class: the class that ran, -1 when nothing did
+void launchMove3D(const Move3D& m, const void* src, void* dst, int es, const KernelTuning& t, int32_t* kernel_class, hipStream_t stream,
+                  ArithType arith = ARITH_NONE, const void* fill_value = nullptr, const WallAddends* addends = nullptr) {
+  void* bufs[3] = {const_cast<void*>(src), dst, nullptr};
+  KernelStats st;
+  launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, arith, fill_value, addends);
+  if (kernel_class) {
+    *kernel_class = -1;
+    for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
+      if (st.launches[c]) *kernel_class = c;
+  }
+}
+
 std::vector<Move3D> importMoves(const cudecompExtMove_t* moves, int32_t n, int32_t es, int32_t mode, cudecompDataType_t dtype,
                                 ArithType* arith) {
   if (n < 0 || (n > 0 && !moves)) CD_INVALID_USAGE("bad move list");
@@ -233,7 +292,7 @@ template <typename Out>
 cudecompResult_t planHaloOp(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[], const bool periods[],
                                    int32_t dim, const int32_t pad[], const HaloOp& op, bool force_packed, Out* out, int32_t clear = 0,
                                    bool clear_first = false, bool self_exchange = false) {
-  try {
+  return guarded([&] {
     const GridShape g = shapeFromSpec(grid);
     if (!out || !halo) CD_INVALID_USAGE("null argument");
     if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
@@ -244,12 +303,7 @@ cudecompResult_t planHaloOp(const cudecompExtGridSpec_t* grid, int32_t rank, int
     const HaloPlan p = buildHaloOpPlan(g, rank, axis, dim, halo, periods ? periods : none, pad ? pad : zero, op, force_packed, self_exchange);
     if (clear != 0 && clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
     exportHaloPlan(p, out);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 HaloOp haloOp(HaloOp::Kind kind, bool clear = false, int centering = 0, bool negate = false, int n_fields = 1) {
@@ -287,7 +341,7 @@ cudecompResult_t cudecompExtGetTransposePlan(cudecompHandle_t handle, cudecompGr
                                              const int32_t in_halo[], const int32_t out_halo[], const int32_t in_pad[],
                                              const int32_t out_pad[], bool inplace, int32_t backend_override,
                                              cudecompExtTransposePlan_t* out) {
-  try {
+  return guarded([&] {
     if (!handle || !handle->initialized) CD_INVALID_USAGE("invalid handle");
     if (!gd || !gd->initialized || gd->handle != handle) CD_INVALID_USAGE("invalid grid descriptor");
     if (!out) CD_INVALID_USAGE("plan argument cannot be null");
@@ -303,18 +357,13 @@ cudecompResult_t cudecompExtGetTransposePlan(cudecompHandle_t handle, cudecompGr
     const TransposePlan p = buildTransposePlan(gd->shape, handle->rank, (TransposeOp)op, in_halo, out_halo, in_pad,
                                                out_pad, inplace, traits, ci.npergroup);
     exportTransposePlan(p, ci.global_ranks, out);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtGetHaloPlan(cudecompHandle_t handle, cudecompGridDesc_t gd, int32_t axis,
                                         const int32_t halo[], const bool periods[], int32_t dim, const int32_t pad[],
                                         int32_t backend_override, cudecompExtHaloPlan_t* out) {
-  try {
+  return guarded([&] {
     if (!handle || !handle->initialized) CD_INVALID_USAGE("invalid handle");
     if (!gd || !gd->initialized || gd->handle != handle) CD_INVALID_USAGE("invalid grid descriptor");
     if (!out || !halo) CD_INVALID_USAGE("null argument");
@@ -324,17 +373,12 @@ cudecompResult_t cudecompExtGetHaloPlan(cudecompHandle_t handle, cudecompGridDes
     const HaloPlan p = buildHaloPlan(gd->shape, handle->rank, axis, dim, halo, periods, pad ? pad : zero,
                                      usesPeerTransport(handle, backend), handle->self_exchange);
     exportHaloPlan(p, out);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtGetTransposeTimings(cudecompHandle_t handle, cudecompGridDesc_t gd, int32_t op,
                                                 cudecompExtTransposeTimings_t* out) {
-  try {
+  return guarded([&] {
     if (!handle || !handle->initialized) CD_INVALID_USAGE("invalid handle");
     if (!gd || !gd->initialized || gd->handle != handle) CD_INVALID_USAGE("invalid grid descriptor");
     if (!out || op < 0 || op > 3) CD_INVALID_USAGE("bad argument");
@@ -346,17 +390,12 @@ cudecompResult_t cudecompExtGetTransposeTimings(cudecompHandle_t handle, cudecom
     out->exchange_ms = t.exchange_ms;
     out->unpack_ms = t.unpack_ms;
     out->pencil_bytes = t.pencil_bytes;
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtGetHaloTimings(cudecompHandle_t handle, cudecompGridDesc_t gd, int32_t axis, int32_t dim,
                                            cudecompExtTransposeTimings_t* out) {
-  try {
+  return guarded([&] {
     if (!handle || !handle->initialized) CD_INVALID_USAGE("invalid handle");
     if (!gd || !gd->initialized || gd->handle != handle) CD_INVALID_USAGE("invalid grid descriptor");
     if (!out || axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("bad argument");
@@ -368,19 +407,14 @@ cudecompResult_t cudecompExtGetHaloTimings(cudecompHandle_t handle, cudecompGrid
     out->exchange_ms = t.exchange_ms;
     out->unpack_ms = t.unpack_ms;
     out->pencil_bytes = t.pencil_bytes;
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtPlanTranspose(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t op,
                                           const int32_t in_halo[], const int32_t out_halo[], const int32_t in_pad[],
                                           const int32_t out_pad[], bool inplace, int32_t pipelined,
                                           int32_t symmetric_recv, int32_t npergroup, cudecompExtTransposePlan_t* out) {
-  try {
+  return guarded([&] {
     const GridShape g = shapeFromSpec(grid);
     if (!out) CD_INVALID_USAGE("plan argument cannot be null");
     if (op < 0 || op > 3) CD_INVALID_USAGE("op out of range");
@@ -396,18 +430,13 @@ cudecompResult_t cudecompExtPlanTranspose(const cudecompExtGridSpec_t* grid, int
     const auto pidx = gridIndexOfRank(g, rank);
     for (int i = 0; i < P; ++i) members[i] = globalRankOf(g, pidx, ca, i);
     exportTransposePlan(p, members, out);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtPlanRelay(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t op, const int32_t in_halo[],
                                       const int32_t out_halo[], const int32_t in_pad[], const int32_t out_pad[], bool inplace,
                                       cudecompExtRelayPlan_t* out) {
-  try {
+  return guarded([&] {
     const GridShape g = shapeFromSpec(grid);
     if (!out) CD_INVALID_USAGE("plan argument cannot be null");
     if (op < 0 || op > 3) CD_INVALID_USAGE("op out of range");
@@ -433,12 +462,7 @@ cudecompResult_t cudecompExtPlanRelay(const cudecompExtGridSpec_t* grid, int32_t
     out->n_forward = (int32_t)rp.forward.size();
     put(rp.scatter, out->scatter);
     put(rp.forward, out->forward);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtPlanHalo(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
@@ -480,7 +504,7 @@ cudecompResult_t cudecompExtPlanHaloFold(const cudecompExtGridSpec_t* grid, int3
 
 cudecompResult_t cudecompExtPencilInfo(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                        const int32_t pad[], cudecompPencilInfo_t* out) {
-  try {
+  return guarded([&] {
     const GridShape g = shapeFromSpec(grid);
     if (!out) CD_INVALID_USAGE("pencil_info argument cannot be null");
     if (axis < 0 || axis > 2) CD_INVALID_USAGE("axis argument out of range");
@@ -496,33 +520,23 @@ cudecompResult_t cudecompExtPencilInfo(const cudecompExtGridSpec_t* grid, int32_
       out->padding[i] = p.pad[i];
     }
     out->size = p.size;
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtShiftedRank(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, int32_t dim,
                                         int32_t displacement, bool periodic, int32_t* shifted_rank) {
-  try {
+  return guarded([&] {
     const GridShape g = shapeFromSpec(grid);
     if (!shifted_rank) CD_INVALID_USAGE("shifted_rank argument cannot be null");
     if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
     if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
     *shifted_rank = shiftedRank(g, rank, axis, dim, displacement, periodic);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtWorkspaceSizes(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis,
                                            const int32_t halo[], int64_t* transpose_ws, int64_t* halo_ws) {
-  try {
+  return guarded([&] {
     const GridShape g = shapeFromSpec(grid);
     if (axis < 0 || axis > 2) CD_INVALID_USAGE("axis argument out of range");
     if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
@@ -531,16 +545,11 @@ cudecompResult_t cudecompExtWorkspaceSizes(const cudecompExtGridSpec_t* grid, in
       if (!halo) CD_INVALID_USAGE("halo_extents argument cannot be null");
       *halo_ws = haloWorkspaceElements(g, gridIndexOfRank(g, rank), axis, halo);
     }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtGetCounters(cudecompHandle_t handle, cudecompGridDesc_t gd, cudecompExtCounters_t* out) {
-  try {
+  return guarded([&] {
     if (!handle || !handle->initialized) CD_INVALID_USAGE("invalid handle");
     if (!gd || !gd->initialized || gd->handle != handle) CD_INVALID_USAGE("invalid grid descriptor");
     if (!out) CD_INVALID_USAGE("null argument");
@@ -560,46 +569,31 @@ cudecompResult_t cudecompExtGetCounters(cudecompHandle_t handle, cudecompGridDes
     out->hardware_queue_slots = handle->census_queue_slots;
     out->relayed = gd->relayed;
     out->rotations = gd->rotations;
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtQueueCensus(cudecompHandle_t handle, int32_t* compute_queues, int32_t* slots) {
-  try {
+  return guarded([&] {
     if (!handle || !handle->initialized) CD_INVALID_USAGE("invalid handle");
     int s = 0;
     const int c = peerQueueCensus(handle, false, &s);
     if (compute_queues) *compute_queues = c;
     if (slots) *slots = s;
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtTrimWorkspacePool(cudecompHandle_t handle) {
-  try {
+  return guarded([&] {
     if (!handle || !handle->initialized) CD_INVALID_USAGE("invalid handle");
     workspaceTrimPool(handle);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 const char* cudecompExtLastKernelName(void) { return lastKernelName(); }
 
 cudecompResult_t cudecompExtEstimateCycleMs(cudecompHandle_t handle, const cudecompExtGridSpec_t* grid, int32_t es,
                                             int32_t backend, int32_t library_buffers, int32_t inplace, double* ms) {
-  try {
+  return guarded([&] {
     if (!handle || !handle->initialized) CD_INVALID_USAGE("invalid handle");
     if (!grid || !ms) CD_INVALID_USAGE("null argument");
     if (es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 4, 8 or 16");
@@ -607,16 +601,11 @@ cudecompResult_t cudecompExtEstimateCycleMs(cudecompHandle_t handle, const cudec
     const GridShape g = shapeFromSpec(grid);
     const bool ip[4] = {inplace != 0, inplace != 0, inplace != 0, inplace != 0};
     *ms = estimateTransposeCycleMs(handle, g, es, (cudecompTransposeCommBackend_t)backend, library_buffers != 0, ip);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtGetLinkInfo(cudecompHandle_t handle, cudecompExtLinkInfo_t* out) {
-  try {
+  return guarded([&] {
     if (!handle || !handle->initialized) CD_INVALID_USAGE("invalid handle");
     if (!out) CD_INVALID_USAGE("null argument");
     out->gbps_sdma = handle->link_gbps_sdma;
@@ -625,31 +614,21 @@ cudecompResult_t cudecompExtGetLinkInfo(cudecompHandle_t handle, cudecompExtLink
     out->crosses_devices = handle->link_crosses_devices ? 1 : 0;
     out->copy_engine = handle->peer_copy_engine;
     out->reserved = 0;
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtPeerProbe(cudecompHandle_t handle, void* buffer, size_t bytes, int32_t* mismatches) {
-  try {
+  return guarded([&] {
     if (!handle || !handle->initialized) CD_INVALID_USAGE("invalid handle");
     if (!buffer || !mismatches) CD_INVALID_USAGE("null argument");
     *mismatches = peerProbe(handle, buffer, bytes);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtRunLocalPhases(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t op, int32_t pipelined,
                                            int32_t symmetric_recv, int32_t phases, void* input, void* output, void* work,
                                            int32_t es, hipStream_t stream) {
-  try {
+  return guarded([&] {
     const GridShape g = shapeFromSpec(grid);
     if (op < 0 || op > 3) CD_INVALID_USAGE("op out of range");
     if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
@@ -688,16 +667,11 @@ cudecompResult_t cudecompExtRunLocalPhases(const cudecompExtGridSpec_t* grid, in
     };
     if (phases & 1) run(p.pack);
     if (phases & 2) run(p.unpack);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtRotateWalk(int32_t nb, int32_t walk, int64_t first, int64_t count, int32_t* blocks, int64_t* grid) {
-  try {
+  return guarded([&] {
     if (nb < 1 || nb > 1024 || !grid || first < 0 || count < 0 || (count > 0 && !blocks)) CD_INVALID_USAGE("bad argument");
     const int w = rotateWalkFor(walk, nb);
     *grid = rotateWalkGrid(nb, w);
@@ -707,17 +681,12 @@ cudecompResult_t cudecompExtRotateWalk(int32_t nb, int32_t walk, int64_t first, 
       if (!rotateWalkBlock((unsigned int)(first + i), (unsigned int)nb, w, &b0, &b1, &b2)) b0 = b1 = b2 = -1;
       blocks[3 * i] = b0, blocks[3 * i + 1] = b1, blocks[3 * i + 2] = b2;
     }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtDescribeMove(uint64_t src_address, uint64_t dst_address, int32_t es, const int64_t extent[3],
                                         const int64_t ss[3], const int64_t ds[3], int32_t flags, int64_t out[10]) {
-  try {
+  return guarded([&] {
     if (!extent || !ss || !ds || !out) CD_INVALID_USAGE("null argument");
     if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
     Move3D m;
@@ -737,243 +706,101 @@ cudecompResult_t cudecompExtDescribeMove(uint64_t src_address, uint64_t dst_addr
     long long o[10];
     describeMove(m, reinterpret_cast<const void*>(src_address), reinterpret_cast<void*>(dst_address), es, &t, o);
     for (int i = 0; i < 10; ++i) out[i] = o[i];
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtMove3D(const void* src, void* dst, int32_t es, const int64_t extent[3],
                                    const int64_t ss[3], const int64_t ds[3], int32_t force_generic,
                                    int32_t* kernel_class, hipStream_t stream) {
-  try {
+  return guarded([&] {
     if (!src || !dst || !extent || !ss || !ds) CD_INVALID_USAGE("null argument");
     if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
-    Move3D m;
-    m.src_buf = BUF_IN;
-    m.dst_buf = BUF_OUT;
-    for (int i = 0; i < 3; ++i) {
-      m.extent[i] = extent[i];
-      m.ss[i] = ss[i];
-      m.ds[i] = ds[i];
-    }
+    Move3D m = move3DOf(extent, ss, ds);
     if (force_generic & 256) m.dst_row_pitch = wholeRowsPitchOf(m);  // the cells between consecutive destination rows are the move's to rewrite
-    void* bufs[3] = {const_cast<void*>(src), dst, nullptr};
-    KernelTuning t;
-    if (force_generic & 1) t.force_class = MOVE_GENERIC;
-    if (force_generic & 2) t.force_streaming = true;
-    if (force_generic & 4) t.window_mode = 1;  // window kernel whenever the destination rows are off the 64-byte grid
-    if (force_generic & 8) t.window_mode = 0;  // never
-    if (force_generic & 64) t.walk_order = 0;  // transposes: i first
-    if (force_generic & 128) t.walk_order = 1;  // transposes: j first (no runs)
-    KernelStats st;
-    launchMoves(&m, 1, bufs, es, stream, &t, &st);
-    if (kernel_class) {
-      *kernel_class = -1;
-      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
-        if (st.launches[c]) *kernel_class = c;
-    }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+    // bits 1, 2, and its own way with 4 / 8 (the window kernel always / never) and 64 / 128 (transposes: i first / j first)
+    launchMove3D(m, src, dst, es, tuningOfFlags(force_generic), kernel_class, stream);
+  });
 }
 
 cudecompResult_t cudecompExtAccumulate3D(const void* src, void* dst, cudecompDataType_t dtype, const int64_t extent[3],
                                          const int64_t ss[3], const int64_t ds[3], int32_t force_generic,
                                          int32_t* kernel_class, hipStream_t stream) {
-  try {
+  return guarded([&] {
     if (!src || !dst || !extent || !ss || !ds) CD_INVALID_USAGE("null argument");
     const int es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
-    Move3D m;
-    m.src_buf = BUF_IN;
-    m.dst_buf = BUF_OUT;
+    Move3D m = move3DOf(extent, ss, ds);
     m.add = true;
-    for (int i = 0; i < 3; ++i) {
-      m.extent[i] = extent[i];
-      m.ss[i] = ss[i];
-      m.ds[i] = ds[i];
-    }
-    void* bufs[3] = {const_cast<void*>(src), dst, nullptr};
-    KernelTuning t;
-    if (force_generic & 1) t.force_class = MOVE_GENERIC;
-    if (force_generic & 2) t.force_streaming = true;
-    KernelStats st;
-    launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, arithOf(dtype));
-    if (kernel_class) {
-      *kernel_class = -1;
-      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
-        if (st.launches[c]) *kernel_class = c;
-    }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+    launchMove3D(m, src, dst, es, tuningOfForce(force_generic & 3), kernel_class, stream, arithOf(dtype));  // (bit 2 is not read)
+  });
 }
 
 cudecompResult_t cudecompExtFill3D(void* dst, int32_t es, const void* value, const int64_t extent[3], const int64_t ds[3],
                                    int32_t force, int32_t* kernel_class, hipStream_t stream) {
-  try {
+  return guarded([&] {
     if (!dst || !extent || !ds) CD_INVALID_USAGE("null argument");
     if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
-    Move3D m;
-    m.src_buf = BUF_IN;
-    m.dst_buf = BUF_OUT;
+    Move3D m = move3DOf(extent, nullptr, ds);
     m.fill = true;
-    for (int i = 0; i < 3; ++i) {
-      m.extent[i] = extent[i];
-      m.ds[i] = ds[i];
-    }
-    void* bufs[3] = {nullptr, dst, nullptr};
-    KernelTuning t;
-    if (force & 1) t.force_class = MOVE_GENERIC;
-    if (force & 2) t.force_streaming = true;
-    if (force & 4) t.no_streaming = true;
-    KernelStats st;
-    launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, ARITH_NONE, value);
-    if (kernel_class) {
-      *kernel_class = -1;
-      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
-        if (st.launches[c]) *kernel_class = c;
-    }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+    launchMove3D(m, nullptr, dst, es, tuningOfForce(force), kernel_class, stream, ARITH_NONE, value);
+  });
 }
 
 cudecompResult_t cudecompExtReflect3D(const void* src, void* dst, cudecompDataType_t dtype, int32_t negate, const int64_t extent[3],
                                       const int64_t ss[3], const int64_t ds[3], int32_t force, int32_t* kernel_class,
                                       hipStream_t stream) {
-  try {
+  return guarded([&] {
     if (!src || !dst || !extent || !ss || !ds) CD_INVALID_USAGE("null argument");
     const int es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
-    Move3D m;
-    m.src_buf = BUF_IN;
-    m.dst_buf = BUF_OUT;
+    Move3D m = move3DOf(extent, ss, ds);
     m.reflect = true;
     m.negate = negate != 0;
-    for (int i = 0; i < 3; ++i) {
-      m.extent[i] = extent[i];
-      m.ss[i] = ss[i];
-      m.ds[i] = ds[i];
-    }
-    void* bufs[3] = {const_cast<void*>(src), dst, nullptr};
-    KernelTuning t;
-    if (force & 1) t.force_class = MOVE_GENERIC;
-    if (force & 2) t.force_streaming = true;
-    if (force & 4) t.no_streaming = true;
-    KernelStats st;
-    launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, m.negate ? arithOf(dtype) : ARITH_NONE);
-    if (kernel_class) {
-      *kernel_class = -1;
-      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
-        if (st.launches[c]) *kernel_class = c;
-    }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+    launchMove3D(m, src, dst, es, tuningOfForce(force), kernel_class, stream, m.negate ? arithOf(dtype) : ARITH_NONE);
+  });
 }
 
 cudecompResult_t cudecompExtFold3D(const void* src, void* dst, cudecompDataType_t dtype, int32_t negate, int32_t take,
                                    const int64_t extent[3], const int64_t ss[3], const int64_t ds[3], int32_t force,
                                    int32_t* kernel_class, hipStream_t stream) {
-  try {
+  return guarded([&] {
     if (!src || !dst || !extent || !ss || !ds) CD_INVALID_USAGE("null argument");
     const int es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
-    Move3D m;
-    m.src_buf = BUF_IN;
-    m.dst_buf = BUF_OUT;
+    Move3D m = move3DOf(extent, ss, ds);
     m.reflect = true;
     m.add = true;
     m.negate = negate != 0;
     m.take = take != 0;
-    for (int i = 0; i < 3; ++i) {
-      m.extent[i] = extent[i];
-      m.ss[i] = ss[i];
-      m.ds[i] = ds[i];
-    }
-    void* bufs[3] = {const_cast<void*>(src), dst, nullptr};
-    KernelTuning t;
-    if (force & 1) t.force_class = MOVE_GENERIC;
-    if (force & 2) t.force_streaming = true;
-    if (force & 4) t.no_streaming = true;
-    KernelStats st;
-    launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, arithOf(dtype));
-    if (kernel_class) {
-      *kernel_class = -1;
-      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
-        if (st.launches[c]) *kernel_class = c;
-    }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+    launchMove3D(m, src, dst, es, tuningOfForce(force), kernel_class, stream, arithOf(dtype));
+  });
 }
 
 cudecompResult_t cudecompExtWall3D(const void* src, void* dst, cudecompDataType_t dtype, int32_t negate, int32_t side,
                                    const void* addends, const int64_t extent[3], const int64_t ss[3], const int64_t ds[3],
                                    int32_t force, int32_t* kernel_class, hipStream_t stream) {
-  try {
+  return guarded([&] {
     if (!src || !dst || !addends || !extent || !ss || !ds) CD_INVALID_USAGE("null argument");
     if (side != 0 && side != 1) CD_INVALID_USAGE("side must be 0 (low) or 1 (high)");
     const int es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
-    Move3D m;
-    m.src_buf = BUF_IN;
-    m.dst_buf = BUF_OUT;
+    Move3D m = move3DOf(extent, ss, ds);
     m.reflect = true;
     m.negate = negate != 0;
     m.affine = side + 1;
     int layers = -1;
-    for (int i = 0; i < 3; ++i) {
-      m.extent[i] = extent[i];
-      m.ss[i] = ss[i];
-      m.ds[i] = ds[i];
+    for (int i = 0; i < 3; ++i)
       if (ss[i] < 0) layers = layers < 0 ? (int)std::min<int64_t>(extent[i], CUDECOMP_AMD_MAX_WALL_HALO + 1) : CUDECOMP_AMD_MAX_WALL_HALO + 1;
-    }
     if (layers < 0) CD_INVALID_USAGE("a wall-value move names its mirrored dim with a negative source stride");
     if (layers > CUDECOMP_AMD_MAX_WALL_HALO) CD_INVALID_USAGE("one mirrored dim of at most CUDECOMP_AMD_MAX_WALL_HALO layers");
     WallAddends a;
     std::memset(&a, 0, sizeof(a));
     for (int k = 0; k < layers; ++k) std::memcpy(a.v[side][k], static_cast<const char*>(addends) + (size_t)k * es, es);
-    void* bufs[3] = {const_cast<void*>(src), dst, nullptr};
-    KernelTuning t;
-    if (force & 1) t.force_class = MOVE_GENERIC;
-    if (force & 2) t.force_streaming = true;
-    if (force & 4) t.no_streaming = true;
-    KernelStats st;
-    launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, arithOf(dtype), nullptr, &a);
-    if (kernel_class) {
-      *kernel_class = -1;
-      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
-        if (st.launches[c]) *kernel_class = c;
-    }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+    launchMove3D(m, src, dst, es, tuningOfForce(force), kernel_class, stream, arithOf(dtype), nullptr, &a);
+  });
 }
 
 cudecompResult_t cudecompExtPlanHaloWallValues(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                                const bool periods[], int32_t dim, const int32_t pad[], cudecompDataType_t dtype,
                                                int32_t parity, int32_t centering, int32_t sides, const double values_low[],
                                                const double values_high[], cudecompExtHaloPlan_t* out, uint8_t* table) {
-  try {
+  return guarded([&] {
     const GridShape g = shapeFromSpec(grid);
     if (!out || !halo || !table) CD_INVALID_USAGE("null argument");
     if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
@@ -996,12 +823,7 @@ cudecompResult_t cudecompExtPlanHaloWallValues(const cudecompExtGridSpec_t* grid
     const WallAddends a = wallAddendsOf(dtype, halo[dim], sides, values_low, values_high);
     for (int side = 0; side < 2; ++side)
       wallTableRow(a, side, (sides & (1 << side)) ? halo[dim] : 0, es, table + side * CUDECOMP_AMD_MAX_WALL_HALO * 16);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 // the moves of a field launch (at most 2, CUDECOMP_AMD_MAX_HALO_FIELDS fields) or of a field-move list (at most
@@ -1043,6 +865,53 @@ cudecompResult_t cudecompExtPlanHaloAccumulateFields(const cudecompExtGridSpec_t
                     true, self_exchange != 0);
 }
 
+// What a Run / Describe pair of the field-move entries shares: the imported list, what it points to and the request over them.  The
+// request points into this record, which is therefore never copied.
+struct ImportedFieldMoves {
+  std::vector<Move3D> moves;
+  std::vector<i64> steps;
+  std::vector<void*> inputs, outputs;  // Describe: the fields given as addresses
+  std::vector<WallAddends> addends;
+  KernelTuning tuning;
+  FieldMoveList list;
+  ImportedFieldMoves() = default;
+  ImportedFieldMoves(const ImportedFieldMoves&) = delete;
+};
+
+// the request over q.moves in the one-choice mode of the halo phases: the fields as device pointers (Run) or as addresses (Describe),
+// inputs and outputs alike; of `force` the bits 1, 2 and 4
+static void requestOver(ImportedFieldMoves& q, void* const* fields, const uint64_t* addresses, int32_t n_fields, int32_t es, int32_t force) {
+  if (!fields) {
+    q.inputs = pointersOf(addresses, n_fields);
+    fields = q.inputs.data();
+  }
+  q.tuning = tuningOfForce(force);
+  q.list.moves = q.moves.data();
+  q.list.n = (int)q.moves.size();
+  q.list.inputs = q.list.outputs = fields;
+  q.list.n_fields = n_fields;
+  q.list.es = es;
+  q.list.one_choice = true;
+  q.list.tuning = &q.tuning;
+}
+
+static void runFieldMoveList(const FieldMoveList& list, hipStream_t stream, int32_t* n_launches) {
+  KernelStats st;
+  launchFieldMoveList(list, stream, &st);
+  if (n_launches) *n_launches = launchesOf(st);
+}
+
+// out[5] of the Describe entries whose lists make one launch at most (one choice, at most two moves)
+static void exportFirstLaunch(const std::vector<FieldMoveLaunch>& ls, int64_t out[5]) {
+  const FieldMoveLaunch none{};  // (every move is empty: nothing is launched)
+  const FieldMoveLaunch& l = ls.empty() ? none : ls[0];
+  out[0] = ls.empty() ? -1 : (int64_t)l.k.kind;
+  out[1] = l.k.vec;
+  out[2] = l.k.access;
+  out[3] = l.blocks_per_field;
+  out[4] = l.blocks;
+}
+
 // the operation of cudecompExtRunFieldMovesOp / cudecompExtDescribeFieldMovesOp onto an imported list; *arith as importMoves sets it
 static void applyFieldMoveMode(std::vector<Move3D>& list, int32_t mode, cudecompDataType_t dtype, int32_t es, ArithType* arith) {
   if (mode != 0 && mode != 1 && mode != 3 && mode != 4) CD_INVALID_USAGE("mode must be 0 (copy), 1 (add), 3 (take) or 4 (add and take)");
@@ -1057,150 +926,103 @@ static void applyFieldMoveMode(std::vector<Move3D>& list, int32_t mode, cudecomp
   }
 }
 
+// cudecompExt{Run,Describe}FieldMoves (mode 0: plain copies) and cudecompExt{Run,Describe}FieldMovesOp
+static void importFieldMovesOp(ImportedFieldMoves& q, const cudecompExtMove_t* moves, int32_t n, void* const* fields, const uint64_t* addresses,
+                               int32_t n_fields, int32_t max_fields, void* work, int64_t work_field_stride, int32_t es, int32_t force,
+                               int32_t mode, cudecompDataType_t dtype) {
+  q.moves = importFieldMoves(moves, n, 2, n_fields, max_fields, es);
+  applyFieldMoveMode(q.moves, mode, dtype, es, &q.list.arith);
+  q.steps.assign(q.moves.size(), work_field_stride);
+  requestOver(q, fields, addresses, n_fields, es, force);
+  q.list.work_steps = q.steps.data();
+  q.list.work = work;
+}
+
+cudecompResult_t cudecompExtRunFieldMoves(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
+                                         void* work, int64_t work_field_stride, int32_t es, int32_t force, hipStream_t stream,
+                                         int32_t* n_launches) {
+  return guarded([&] {
+    if (!fields) CD_INVALID_USAGE("null argument");
+    ImportedFieldMoves q;
+    importFieldMovesOp(q, moves, n, fields, nullptr, n_fields, CUDECOMP_AMD_MAX_HALO_FIELDS, work, work_field_stride, es, force, 0, (cudecompDataType_t)0);
+    runFieldMoveList(q.list, stream, n_launches);
+  });
+}
+
+cudecompResult_t cudecompExtDescribeFieldMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
+                                              int32_t n_fields, uint64_t work_address, int64_t work_field_stride, int32_t es,
+                                              int32_t force, int64_t out[5]) {
+  return guarded([&] {
+    if (!field_addresses || !out) CD_INVALID_USAGE("null argument");
+    ImportedFieldMoves q;
+    importFieldMovesOp(q, moves, n, nullptr, field_addresses, n_fields, CUDECOMP_AMD_MAX_HALO_FIELDS, reinterpret_cast<void*>(work_address),
+                       work_field_stride, es, force, 0, (cudecompDataType_t)0);
+    exportFirstLaunch(planFieldMoveLaunches(q.list), out);
+  });
+}
+
 cudecompResult_t cudecompExtRunFieldMovesOp(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
                                            void* work, int64_t work_field_stride, int32_t es, int32_t force, int32_t mode,
                                            cudecompDataType_t dtype, hipStream_t stream, int32_t* n_launches) {
-  try {
+  return guarded([&] {
     if (!fields) CD_INVALID_USAGE("null argument");
-    std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS, es);
-    ArithType arith;
-    applyFieldMoveMode(list, mode, dtype, es, &arith);
-    const std::vector<i64> steps(list.size(), work_field_stride);
-    KernelStats st;
-    launchFieldMoveList(list.data(), steps.data(), n, fields, fields, n_fields, work, es, stream, force, &st, true, arith);
-    if (n_launches) {
-      *n_launches = 0;
-      for (int c = 0; c < MOVE_CLASS_COUNT; ++c) *n_launches += st.launches[c];
-    }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+    ImportedFieldMoves q;
+    importFieldMovesOp(q, moves, n, fields, nullptr, n_fields, CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS, work, work_field_stride, es, force, mode, dtype);
+    runFieldMoveList(q.list, stream, n_launches);
+  });
 }
 
 cudecompResult_t cudecompExtDescribeFieldMovesOp(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
                                                 int32_t n_fields, uint64_t work_address, int64_t work_field_stride, int32_t es,
                                                 int32_t force, int32_t mode, cudecompDataType_t dtype, int64_t out[5]) {
-  try {
+  return guarded([&] {
     if (!field_addresses || !out) CD_INVALID_USAGE("null argument");
-    std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS, es);
-    ArithType arith;
-    applyFieldMoveMode(list, mode, dtype, es, &arith);
-    const std::vector<i64> steps(list.size(), work_field_stride);
-    std::vector<void*> fields(n_fields);
-    for (int32_t f = 0; f < n_fields; ++f) fields[f] = reinterpret_cast<void*>(field_addresses[f]);
-    const std::vector<FieldMoveLaunch> ls = planFieldMoveLaunches(list.data(), steps.data(), n, fields.data(), fields.data(), n_fields,
-                                                                  reinterpret_cast<void*>(work_address), es, force, true, arith);
-    const FieldMoveLaunch none{};  // (every move is empty: nothing is launched)
-    const FieldMoveLaunch& l = ls.empty() ? none : ls[0];  // (one choice, at most two moves: never a second launch)
-    out[0] = ls.empty() ? -1 : (int64_t)l.k.kind;
-    out[1] = l.k.vec;
-    out[2] = l.k.access;
-    out[3] = l.blocks_per_field;
-    out[4] = l.blocks;
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+    ImportedFieldMoves q;
+    importFieldMovesOp(q, moves, n, nullptr, field_addresses, n_fields, CUDECOMP_AMD_MAX_HALO_ACCUMULATE_FIELDS,
+                       reinterpret_cast<void*>(work_address), work_field_stride, es, force, mode, dtype);
+    exportFirstLaunch(planFieldMoveLaunches(q.list), out);
+  });
 }
 
-// the operation of the mirrored pair onto an imported list: every move a reflect-move, with add (and take) as the mode says
-static ArithType applyMirroredFieldMoveMode(std::vector<Move3D>& list, int32_t mode, cudecompDataType_t dtype, int32_t es) {
+// cudecompExt{Run,Describe}MirroredFieldMoves: every move a reflect-move, with add (and take) as the mode says
+static void importMirroredFieldMoves(ImportedFieldMoves& q, const cudecompExtMove_t* moves, int32_t n, void* const* fields,
+                                     const uint64_t* addresses, int32_t n_fields, int32_t es, int32_t force, int32_t mode,
+                                     cudecompDataType_t dtype, uint32_t fields_neg) {
+  q.moves = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_WALL_FIELDS, es);
   if (mode != 0 && mode != 1 && mode != 4) CD_INVALID_USAGE("mode must be 0 (reflect), 1 (fold) or 4 (fold and take)");
   if (elementSize(dtype) != es) CD_INVALID_USAGE("element size does not match the data type");
-  for (Move3D& m : list) {
+  for (Move3D& m : q.moves) {
     m.reflect = true;
     m.add = mode != 0;
     m.take = mode == 4;
   }
-  return arithOf(dtype);
+  if (n_fields < 32 && (fields_neg >> n_fields) != 0) CD_INVALID_USAGE("sign bit of a field the list does not have");
+  requestOver(q, fields, addresses, n_fields, es, force);
+  q.list.arith = arithOf(dtype);
+  q.list.mirrored = true;
+  q.list.fields_neg = fields_neg;
 }
 
 cudecompResult_t cudecompExtRunMirroredFieldMoves(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
                                                  int32_t es, int32_t force, int32_t mode, cudecompDataType_t dtype,
                                                  uint32_t fields_neg, hipStream_t stream, int32_t* n_launches) {
-  try {
+  return guarded([&] {
     if (!fields) CD_INVALID_USAGE("null argument");
-    std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_WALL_FIELDS, es);
-    const ArithType arith = applyMirroredFieldMoveMode(list, mode, dtype, es);
-    if (n_fields < 32 && (fields_neg >> n_fields) != 0) CD_INVALID_USAGE("sign bit of a field the list does not have");
-    KernelStats st;
-    launchFieldMoveList(list.data(), nullptr, n, fields, fields, n_fields, nullptr, es, stream, force, &st, true, arith, true, fields_neg);
-    if (n_launches) {
-      *n_launches = 0;
-      for (int c = 0; c < MOVE_CLASS_COUNT; ++c) *n_launches += st.launches[c];
-    }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+    ImportedFieldMoves q;
+    importMirroredFieldMoves(q, moves, n, fields, nullptr, n_fields, es, force, mode, dtype, fields_neg);
+    runFieldMoveList(q.list, stream, n_launches);
+  });
 }
 
 cudecompResult_t cudecompExtDescribeMirroredFieldMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
                                                       int32_t n_fields, int32_t es, int32_t force, int32_t mode,
                                                       cudecompDataType_t dtype, uint32_t fields_neg, int64_t out[5]) {
-  try {
+  return guarded([&] {
     if (!field_addresses || !out) CD_INVALID_USAGE("null argument");
-    std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_WALL_FIELDS, es);
-    const ArithType arith = applyMirroredFieldMoveMode(list, mode, dtype, es);
-    if (n_fields < 32 && (fields_neg >> n_fields) != 0) CD_INVALID_USAGE("sign bit of a field the list does not have");
-    std::vector<void*> fields(n_fields);
-    for (int32_t f = 0; f < n_fields; ++f) fields[f] = reinterpret_cast<void*>(field_addresses[f]);
-    const std::vector<FieldMoveLaunch> ls =
-        planFieldMoveLaunches(list.data(), nullptr, n, fields.data(), fields.data(), n_fields, nullptr, es, force, true, arith, true, fields_neg);
-    const FieldMoveLaunch none{};  // (every move is empty: nothing is launched)
-    const FieldMoveLaunch& l = ls.empty() ? none : ls[0];  // (one choice, at most two moves: never a second launch)
-    out[0] = ls.empty() ? -1 : (int64_t)l.k.kind;
-    out[1] = l.k.vec;
-    out[2] = l.k.access;
-    out[3] = l.blocks_per_field;
-    out[4] = l.blocks;
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
-}
-
-// the wall pair: the imported list as wall-moves (every move a reflect-move that names its side in `peer`), and the raw addends
-// ((f * 2 + side) * CUDECOMP_AMD_MAX_WALL_HALO + k elements) as the kernel layer takes them
-static std::vector<Move3D> importWallFieldMoves(const cudecompExtMove_t* moves, int32_t n, int32_t n_fields, int32_t es, uint32_t fields_neg,
-                                                const void* addends, std::vector<WallAddends>& converted) {
-  if (!addends) CD_INVALID_USAGE("null argument");
-  std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_WALL_VALUE_FIELDS, es);
-  if (n_fields < 32 && (fields_neg >> n_fields) != 0) CD_INVALID_USAGE("sign bit of a field the list does not have");
-  for (int32_t i = 0; i < n; ++i) {
-    Move3D& m = list[i];
-    if (moves[i].peer != 0 && moves[i].peer != 1) CD_INVALID_USAGE("a wall-value move names its side in `peer`: 0 low, 1 high");
-    if (m.src_buf == BUF_WORK || m.dst_buf == BUF_WORK || m.dst_row_pitch != 0) CD_INVALID_USAGE("wall-value moves lie in the fields' own buffers");
-    int mirrored = 0;
-    for (int d = 0; d < 3; ++d) {
-      if (m.extent[d] < 0) CD_INVALID_USAGE("negative extent");
-      if (m.ss[d] < 0) {
-        ++mirrored;
-        if (m.extent[d] > CUDECOMP_AMD_MAX_WALL_HALO) CD_INVALID_USAGE("one mirrored dim of at most CUDECOMP_AMD_MAX_WALL_HALO layers");
-      }
-    }
-    if (mirrored != 1) CD_INVALID_USAGE("a wall-value move names its one mirrored dim with a negative source stride");
-    m.reflect = true;
-    m.affine = moves[i].peer + 1;
-  }
-  converted.assign(n_fields, WallAddends());
-  for (int32_t f = 0; f < n_fields; ++f) {
-    std::memset(&converted[f], 0, sizeof(WallAddends));
-    for (int side = 0; side < 2; ++side)
-      for (int k = 0; k < CUDECOMP_AMD_MAX_WALL_HALO; ++k)
-        std::memcpy(converted[f].v[side][k],
-                    static_cast<const char*>(addends) + ((size_t)(f * 2 + side) * CUDECOMP_AMD_MAX_WALL_HALO + k) * es, es);
-  }
-  return list;
+    ImportedFieldMoves q;
+    importMirroredFieldMoves(q, moves, n, nullptr, field_addresses, n_fields, es, force, mode, dtype, fields_neg);
+    exportFirstLaunch(planFieldMoveLaunches(q.list), out);
+  });
 }
 
 cudecompResult_t cudecompExtPlanHaloWallValueFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
@@ -1216,56 +1038,80 @@ cudecompResult_t cudecompExtPlanHaloWallValueFields(const cudecompExtGridSpec_t*
   return planHaloOp(grid, rank, axis, halo, periods, dim, pad, op, false, out);
 }
 
-static KernelTuning tuningOfForce(int32_t force) {
-  KernelTuning t;
-  if (force & 1) t.force_class = MOVE_GENERIC;
-  if (force & 2) t.force_streaming = true;
-  if (force & 4) t.no_streaming = true;
-  return t;
+// cudecompExt{Run,Describe}WallFieldMoves: the imported list as wall-moves (every move a reflect-move that names its side in `peer`),
+// the raw addends ((f * 2 + side) * CUDECOMP_AMD_MAX_WALL_HALO + k elements) as the kernel layer takes them, and the wall list over
+// both.  One field is the single call: *single_bufs then holds its buffers, the moves carry its sign, and launchMoves / planLaunches
+// take q.moves, q.tuning and q.addends.
+static void importWallFieldMoves(ImportedFieldMoves& q, const cudecompExtMove_t* moves, int32_t n, void* const* fields,
+                                 const uint64_t* addresses, int32_t n_fields, int32_t es, int32_t force, cudecompDataType_t dtype,
+                                 uint32_t fields_neg, const void* addends, void* single_bufs[3]) {
+  if (!addends) CD_INVALID_USAGE("null argument");
+  q.moves = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_WALL_VALUE_FIELDS, es);
+  if (n_fields < 32 && (fields_neg >> n_fields) != 0) CD_INVALID_USAGE("sign bit of a field the list does not have");
+  for (int32_t i = 0; i < n; ++i) {
+    Move3D& m = q.moves[i];
+    if (moves[i].peer != 0 && moves[i].peer != 1) CD_INVALID_USAGE("a wall-value move names its side in `peer`: 0 low, 1 high");
+    if (m.src_buf == BUF_WORK || m.dst_buf == BUF_WORK || m.dst_row_pitch != 0) CD_INVALID_USAGE("wall-value moves lie in the fields' own buffers");
+    int mirrored = 0;
+    for (int d = 0; d < 3; ++d) {
+      if (m.extent[d] < 0) CD_INVALID_USAGE("negative extent");
+      if (m.ss[d] < 0) {
+        ++mirrored;
+        if (m.extent[d] > CUDECOMP_AMD_MAX_WALL_HALO) CD_INVALID_USAGE("one mirrored dim of at most CUDECOMP_AMD_MAX_WALL_HALO layers");
+      }
+    }
+    if (mirrored != 1) CD_INVALID_USAGE("a wall-value move names its one mirrored dim with a negative source stride");
+    m.reflect = true;
+    m.affine = moves[i].peer + 1;
+    if (n_fields == 1) m.negate = (fields_neg & 1u) != 0;
+  }
+  q.addends.assign(n_fields, WallAddends());
+  for (int32_t f = 0; f < n_fields; ++f) {
+    std::memset(&q.addends[f], 0, sizeof(WallAddends));
+    for (int side = 0; side < 2; ++side)
+      for (int k = 0; k < CUDECOMP_AMD_MAX_WALL_HALO; ++k)
+        std::memcpy(q.addends[f].v[side][k], static_cast<const char*>(addends) + ((size_t)(f * 2 + side) * CUDECOMP_AMD_MAX_WALL_HALO + k) * es, es);
+  }
+  requestOver(q, fields, addresses, n_fields, es, force);
+  for (int32_t f = 0; fields && f < n_fields; ++f)
+    if (!fields[f]) CD_INVALID_USAGE("null field buffer");
+  q.list.arith = arithOf(dtype);
+  q.list.mirrored = true;
+  q.list.fields_neg = fields_neg;
+  q.list.addends = q.addends.data();
+  single_bufs[0] = single_bufs[1] = q.list.inputs[0];
+  single_bufs[2] = nullptr;
 }
 
 cudecompResult_t cudecompExtRunWallFieldMoves(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
                                              int32_t force, cudecompDataType_t dtype, uint32_t fields_neg, const void* addends,
                                              hipStream_t stream, int32_t* n_launches) {
-  try {
+  return guarded([&] {
     if (!fields) CD_INVALID_USAGE("null argument");
     const int es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
-    std::vector<WallAddends> converted;
-    std::vector<Move3D> list = importWallFieldMoves(moves, n, n_fields, es, fields_neg, addends, converted);
-    for (int32_t f = 0; f < n_fields; ++f)
-      if (!fields[f]) CD_INVALID_USAGE("null field buffer");
-    KernelStats st;
+    ImportedFieldMoves q;
+    void* bufs[3];
+    importWallFieldMoves(q, moves, n, fields, nullptr, n_fields, es, force, dtype, fields_neg, addends, bufs);
     if (n_fields == 1) {  // the single call's path
-      for (Move3D& m : list) m.negate = (fields_neg & 1u) != 0;
-      void* bufs[3] = {fields[0], fields[0], nullptr};
-      const KernelTuning t = tuningOfForce(force);
-      launchMoves(list.data(), n, bufs, es, stream, &t, &st, nullptr, arithOf(dtype), nullptr, converted.data());
+      KernelStats st;
+      launchMoves(q.moves.data(), n, bufs, es, stream, &q.tuning, &st, nullptr, arithOf(dtype), nullptr, q.addends.data());
+      if (n_launches) *n_launches = launchesOf(st);
     } else {
-      launchFieldWallList(list.data(), n, fields, n_fields, es, stream, force, &st, arithOf(dtype), fields_neg, converted.data());
+      runFieldMoveList(q.list, stream, n_launches);
     }
-    if (n_launches) {
-      *n_launches = 0;
-      for (int c = 0; c < MOVE_CLASS_COUNT; ++c) *n_launches += st.launches[c];
-    }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtDescribeWallFieldMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
                                                   int32_t n_fields, int32_t force, cudecompDataType_t dtype, uint32_t fields_neg,
                                                   const void* addends, int32_t max_launches, int64_t* out, uint8_t* tables,
                                                   int32_t* n_launches) {
-  try {
+  return guarded([&] {
     if (!field_addresses || !n_launches || max_launches < 0 || (max_launches > 0 && (!out || !tables))) CD_INVALID_USAGE("null argument");
     const int es = elementSize(dtype);
-    std::vector<WallAddends> converted;
-    std::vector<Move3D> list = importWallFieldMoves(moves, n, n_fields, es, fields_neg, addends, converted);
-    std::vector<void*> fields(n_fields);
-    for (int32_t f = 0; f < n_fields; ++f) fields[f] = reinterpret_cast<void*>(field_addresses[f]);
+    ImportedFieldMoves q;
+    void* bufs[3];
+    importWallFieldMoves(q, moves, n, nullptr, field_addresses, n_fields, es, force, dtype, fields_neg, addends, bufs);
     int made = 0;
     auto record = [&](const KernelChoice& k, int64_t blocks, int64_t per_field, int first, int count, const unsigned char* table) {
       if (made < max_launches) {
@@ -1276,84 +1122,29 @@ cudecompResult_t cudecompExtDescribeWallFieldMoves(const cudecompExtMove_t* move
       ++made;
     };
     if (n_fields == 1) {  // the single call's launches; their addends in the compact layout, h the most layers of the list
-      for (Move3D& m : list) m.negate = (fields_neg & 1u) != 0;
-      void* bufs[3] = {fields[0], fields[0], nullptr};
-      const KernelTuning t = tuningOfForce(force);
       auto layersOf = [](const Move3D& m) {
         for (int d = 0; d < 3; ++d)
           if (m.ss[d] < 0) return (int)m.extent[d];
         return 0;
       };
       int layers = 0;
-      for (const Move3D& m : list)
+      for (const Move3D& m : q.moves)
         if (m.elements() != 0) layers = std::max(layers, layersOf(m));
-      for (const Launch& l : planLaunches(list.data(), n, bufs, es, &t, nullptr, arithOf(dtype))) {
+      for (const Launch& l : planLaunches(q.moves.data(), n, bufs, es, &q.tuning, nullptr, arithOf(dtype))) {
         unsigned char table[CUDECOMP_EXT_WALL_FIELD_TABLE_BYTES] = {0};
         for (int i = 0; i < l.b.n; ++i) {
-          const Move3D& m = list[l.index[i]];
+          const Move3D& m = q.moves[l.index[i]];
           const int mine = layersOf(m), side = m.affine - 1;
-          for (int j = 0; j < mine; ++j) std::memcpy(table + ((size_t)i * layers + j) * es, converted[0].v[side][side == 0 ? mine - 1 - j : j], es);
+          for (int j = 0; j < mine; ++j) std::memcpy(table + ((size_t)i * layers + j) * es, q.addends[0].v[side][side == 0 ? mine - 1 - j : j], es);
         }
         record(l.k, l.blocks, l.blocks, 0, 1, table);
       }
     } else {
-      for (const FieldWallLaunch& w : planFieldWallLaunches(list.data(), n, fields.data(), n_fields, es, force, arithOf(dtype), fields_neg, converted.data()))
+      for (const FieldWallLaunch& w : planFieldWallLaunches(q.list))
         record(w.l.k, w.l.blocks, w.l.blocks_per_field, w.first_field, w.l.b.n_fields, reinterpret_cast<const unsigned char*>(w.table.w));
     }
     *n_launches = made;
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
-}
-
-cudecompResult_t cudecompExtRunFieldMoves(const cudecompExtMove_t* moves, int32_t n, void* const* fields, int32_t n_fields,
-                                         void* work, int64_t work_field_stride, int32_t es, int32_t force, hipStream_t stream,
-                                         int32_t* n_launches) {
-  try {
-    if (!fields) CD_INVALID_USAGE("null argument");
-    const std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_FIELDS, es);
-    const std::vector<i64> steps(list.size(), work_field_stride);
-    KernelStats st;
-    launchFieldMoveList(list.data(), steps.data(), n, fields, fields, n_fields, work, es, stream, force, &st, true);
-    if (n_launches) {
-      *n_launches = 0;
-      for (int c = 0; c < MOVE_CLASS_COUNT; ++c) *n_launches += st.launches[c];
-    }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
-}
-
-cudecompResult_t cudecompExtDescribeFieldMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t* field_addresses,
-                                              int32_t n_fields, uint64_t work_address, int64_t work_field_stride, int32_t es,
-                                              int32_t force, int64_t out[5]) {
-  try {
-    if (!field_addresses || !out) CD_INVALID_USAGE("null argument");
-    const std::vector<Move3D> list = importFieldMoves(moves, n, 2, n_fields, CUDECOMP_AMD_MAX_HALO_FIELDS, es);
-    const std::vector<i64> steps(list.size(), work_field_stride);
-    std::vector<void*> fields(n_fields);
-    for (int32_t f = 0; f < n_fields; ++f) fields[f] = reinterpret_cast<void*>(field_addresses[f]);
-    const std::vector<FieldMoveLaunch> ls = planFieldMoveLaunches(list.data(), steps.data(), n, fields.data(), fields.data(), n_fields,
-                                                                  reinterpret_cast<void*>(work_address), es, force, true);
-    const FieldMoveLaunch none{};  // (every move is empty: nothing is launched)
-    const FieldMoveLaunch& l = ls.empty() ? none : ls[0];  // (one choice, at most two moves: never a second launch)
-    out[0] = ls.empty() ? -1 : (int64_t)l.k.kind;
-    out[1] = l.k.vec;
-    out[2] = l.k.access;
-    out[3] = l.blocks_per_field;
-    out[4] = l.blocks;
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtPlanTransposeFields(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t op, const int32_t in_halo[],
@@ -1361,7 +1152,7 @@ cudecompResult_t cudecompExtPlanTransposeFields(const cudecompExtGridSpec_t* gri
                                                 bool inplace, int32_t pipelined, int32_t symmetric_recv, int32_t npergroup,
                                                 int32_t n_fields, cudecompExtTransposePlan_t* out, int64_t* pack_step,
                                                 int64_t* unpack_step) {
-  try {
+  return guarded([&] {
     const GridShape g = shapeFromSpec(grid);
     if (!out || !pack_step || !unpack_step) CD_INVALID_USAGE("plan argument cannot be null");
     if (op < 0 || op > 3) CD_INVALID_USAGE("op out of range");
@@ -1382,32 +1173,35 @@ cudecompResult_t cudecompExtPlanTransposeFields(const cudecompExtGridSpec_t* gri
       pack_step[i] = i < (int)fp.pack_step.size() ? fp.pack_step[i] : 0;
       unpack_step[i] = i < (int)fp.unpack_step.size() ? fp.unpack_step[i] : 0;
     }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
+  });
+}
+
+// cudecompExt{Run,Describe}FieldMoveList: the phases of a multi-field transpose -- inputs and outputs apart, the caller's workspace
+// steps, a kernel choice per move
+static void importFieldMoveList(ImportedFieldMoves& q, const cudecompExtMove_t* moves, const int64_t* work_steps, int32_t n,
+                                void* const* inputs, void* const* outputs, const uint64_t* input_addresses, const uint64_t* output_addresses,
+                                int32_t n_fields, void* work, int32_t es, int32_t force) {
+  q.moves = importFieldMoves(moves, n, CUDECOMP_EXT_MAX_MEMBERS, n_fields, CUDECOMP_AMD_MAX_TRANSPOSE_FIELDS, es);
+  requestOver(q, inputs, input_addresses, n_fields, es, force);
+  if (output_addresses) {
+    q.outputs = pointersOf(output_addresses, n_fields);
+    outputs = q.outputs.data();
   }
-  return CUDECOMP_RESULT_SUCCESS;
+  q.list.outputs = outputs;
+  q.list.work_steps = work_steps;
+  q.list.work = work;
+  q.list.one_choice = false;
 }
 
 cudecompResult_t cudecompExtRunFieldMoveList(const cudecompExtMove_t* moves, const int64_t* work_steps, int32_t n,
                                              void* const* inputs, void* const* outputs, int32_t n_fields, void* work, int32_t es,
                                              int32_t force, hipStream_t stream, int32_t* n_launches) {
-  try {
+  return guarded([&] {
     if (!inputs) CD_INVALID_USAGE("null argument");
-    const std::vector<Move3D> list = importFieldMoves(moves, n, CUDECOMP_EXT_MAX_MEMBERS, n_fields, CUDECOMP_AMD_MAX_TRANSPOSE_FIELDS, es);
-    KernelStats st;
-    launchFieldMoveList(list.data(), work_steps, n, inputs, outputs, n_fields, work, es, stream, force, &st);
-    if (n_launches) {
-      *n_launches = 0;
-      for (int c = 0; c < MOVE_CLASS_COUNT; ++c) *n_launches += st.launches[c];
-    }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+    ImportedFieldMoves q;
+    importFieldMoveList(q, moves, work_steps, n, inputs, outputs, nullptr, nullptr, n_fields, work, es, force);
+    runFieldMoveList(q.list, stream, n_launches);
+  });
 }
 
 cudecompResult_t cudecompExtDescribeFieldMoveList(const cudecompExtMove_t* moves, const int64_t* work_steps, int32_t n,
@@ -1415,16 +1209,12 @@ cudecompResult_t cudecompExtDescribeFieldMoveList(const cudecompExtMove_t* moves
                                                   int32_t n_fields, uint64_t work_address, int32_t es, int32_t force,
                                                   cudecompExtFieldMoveLaunch_t* launches, int32_t max_launches,
                                                   int32_t* n_launches) {
-  try {
+  return guarded([&] {
     if (!input_addresses || !n_launches || (max_launches > 0 && !launches)) CD_INVALID_USAGE("null argument");
-    const std::vector<Move3D> list = importFieldMoves(moves, n, CUDECOMP_EXT_MAX_MEMBERS, n_fields, CUDECOMP_AMD_MAX_TRANSPOSE_FIELDS, es);
-    std::vector<void*> in(n_fields), out(n_fields);
-    for (int32_t f = 0; f < n_fields; ++f) {
-      in[f] = reinterpret_cast<void*>(input_addresses[f]);
-      if (output_addresses) out[f] = reinterpret_cast<void*>(output_addresses[f]);
-    }
-    const std::vector<FieldMoveLaunch> ls = planFieldMoveLaunches(list.data(), work_steps, n, in.data(), output_addresses ? out.data() : nullptr,
-                                                                  n_fields, reinterpret_cast<void*>(work_address), es, force);
+    ImportedFieldMoves q;
+    importFieldMoveList(q, moves, work_steps, n, nullptr, nullptr, input_addresses, output_addresses, n_fields,
+                        reinterpret_cast<void*>(work_address), es, force);
+    const std::vector<FieldMoveLaunch> ls = planFieldMoveLaunches(q.list);
     *n_launches = (int32_t)ls.size();
     for (int32_t i = 0; i < (int32_t)ls.size() && i < max_launches; ++i) {
       const FieldMoveLaunch& l = ls[i];
@@ -1442,12 +1232,7 @@ cudecompResult_t cudecompExtDescribeFieldMoveList(const cudecompExtMove_t* moves
       o.blocks_per_field = l.blocks_per_field;
       for (int j = 0; j < l.b.n; ++j) o.index[j] = l.index[j];
     }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtDataLaunchCount(int64_t* launches) {
@@ -1465,7 +1250,7 @@ cudecompResult_t cudecompExtHaloPlanCount(cudecompHandle_t handle, cudecompGridD
 cudecompResult_t cudecompExtDescribeMoves(const cudecompExtMove_t* moves, int32_t n, const uint64_t buf_addresses[3], int32_t es,
                                          int32_t mode, cudecompDataType_t dtype, int32_t flags, const uint64_t* dst_base_addresses,
                                          cudecompExtLaunch_t* launches, int32_t max_launches, int32_t* n_launches) {
-  try {
+  return guarded([&] {
     if (!buf_addresses || !n_launches || max_launches < 0 || (max_launches > 0 && !launches)) CD_INVALID_USAGE("bad argument");
     ArithType arith;
     const std::vector<Move3D> list = importMoves(moves, n, es, mode, dtype, &arith);
@@ -1473,8 +1258,7 @@ cudecompResult_t cudecompExtDescribeMoves(const cudecompExtMove_t* moves, int32_
     void* bufs[3];
     for (int i = 0; i < 3; ++i) bufs[i] = reinterpret_cast<void*>(buf_addresses[i]);
     std::vector<void*> bases;
-    if (dst_base_addresses)
-      for (int32_t i = 0; i < n; ++i) bases.push_back(reinterpret_cast<void*>(dst_base_addresses[i]));
+    if (dst_base_addresses) bases = pointersOf(dst_base_addresses, n);
     if (dst_base_addresses && bases.empty()) bases.push_back(nullptr);  // (an empty list with bases is still a remote one)
     const std::vector<Launch> ls = planLaunches(list.data(), n, bufs, es, &t, dst_base_addresses ? bases.data() : nullptr, arith);
     *n_launches = (int32_t)ls.size();
@@ -1498,17 +1282,12 @@ cudecompResult_t cudecompExtDescribeMoves(const cudecompExtMove_t* moves, int32_
       for (int k = 0; k <= l.b.n; ++k) o.first_block[k] = l.b.first_block[k];
       for (int k = 0; k < 8; ++k) o.index[k] = k < l.b.n ? l.index[k] : -1;
     }
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtDescribeResidency(const cudecompExtMove_t* moves, int32_t n, const uint64_t buf_addresses[3], int32_t es,
                                              int32_t flags, int32_t* pad_bytes, int32_t max_launches, int32_t* n_launches) {
-  try {
+  return guarded([&] {
     if (!buf_addresses || !n_launches || max_launches < 0 || (max_launches > 0 && !pad_bytes)) CD_INVALID_USAGE("bad argument");
     ArithType arith;
     const std::vector<Move3D> list = importMoves(moves, n, es, 0, (cudecompDataType_t)0, &arith);
@@ -1519,18 +1298,13 @@ cudecompResult_t cudecompExtDescribeResidency(const cudecompExtMove_t* moves, in
     *n_launches = (int32_t)ls.size();
     if ((int32_t)ls.size() > max_launches) CD_INVALID_USAGE("more launches than the output array holds");
     for (size_t i = 0; i < ls.size(); ++i) pad_bytes[i] = residencyPadBytes(ls[i].k, ls[i].b);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtRunMoves(const cudecompExtMove_t* moves, int32_t n, void* const bufs[3], int32_t es, int32_t mode,
                                     cudecompDataType_t dtype, const void* fill_value, int32_t flags, void* const* dst_bases,
                                     hipStream_t stream, int32_t launches[3], int64_t elements[3], int32_t* n_launches) {
-  try {
+  return guarded([&] {
     if (!bufs) CD_INVALID_USAGE("null argument");
     ArithType arith;
     const std::vector<Move3D> list = importMoves(moves, n, es, mode, dtype, &arith);
@@ -1553,45 +1327,30 @@ cudecompResult_t cudecompExtRunMoves(const cudecompExtMove_t* moves, int32_t n, 
       total += st.launches[c];
     }
     if (n_launches) *n_launches = total;
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 // ---- the flag, page-tag and checksum kernels of sync.hip, one launch each (tests/test_gpu_sync_kernels.py) ----------------------
 cudecompResult_t cudecompExtSyncEpochBegin(uint64_t* epoch, uint64_t* const* flags, int32_t n, hipStream_t stream) {
-  try {
+  return guarded([&] {
     const FlagList l = flagListOf(flags, n);
     if (!epoch) CD_INVALID_USAGE("null epoch");
     launchEpochBegin(reinterpret_cast<unsigned long long*>(epoch), l, stream);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtSyncSignal(const uint64_t* epoch, uint64_t* const* flags, int32_t n, int32_t step, hipStream_t stream) {
-  try {
+  return guarded([&] {
     const FlagList l = flagListOf(flags, n);
     checkFlagStep(step);
     if (n > 0 && !epoch) CD_INVALID_USAGE("null epoch");
     launchSignal(reinterpret_cast<const unsigned long long*>(epoch), l, stream, step);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtSyncWait(const uint64_t* epoch, uint64_t* const* flags, int32_t n, int32_t step, uint64_t* status,
                                      double timeout_s, hipStream_t stream) {
-  try {
+  return guarded([&] {
     const FlagList l = flagListOf(flags, n);
     checkFlagStep(step);
     // (the harness never parks a wave for longer than a second, whatever a test asks for; NaN fails both comparisons)
@@ -1599,48 +1358,28 @@ cudecompResult_t cudecompExtSyncWait(const uint64_t* epoch, uint64_t* const* fla
     if (n > 0 && (!epoch || !status)) CD_INVALID_USAGE("null epoch or status");
     launchWait(reinterpret_cast<const unsigned long long*>(epoch), l, reinterpret_cast<unsigned long long*>(status), timeout_s, stream,
                step);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtTagPages(void* base, size_t bytes, uint64_t seed, hipStream_t stream) {
-  try {
+  return guarded([&] {
     if (bytes >= 4096 && !base) CD_INVALID_USAGE("null buffer");
     launchTagPages(base, bytes, seed, stream);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtCheckPages(const void* base, size_t bytes, uint64_t seed, uint64_t* bad, hipStream_t stream) {
-  try {
+  return guarded([&] {
     if (bytes >= 4096 && (!base || !bad)) CD_INVALID_USAGE("null argument");
     launchCheckPages(base, bytes, seed, reinterpret_cast<unsigned long long*>(bad), stream);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 cudecompResult_t cudecompExtChecksum(const void* ptr, size_t bytes, uint64_t* out2, hipStream_t stream) {
-  try {
+  return guarded([&] {
     if (bytes > 0 && (!ptr || !out2)) CD_INVALID_USAGE("null argument");
     launchChecksum(ptr, bytes, reinterpret_cast<unsigned long long*>(out2), stream);
-  } catch (const Error& e) {
-    return fail(e);
-  } catch (...) {
-    return CUDECOMP_RESULT_INTERNAL_ERROR;
-  }
-  return CUDECOMP_RESULT_SUCCESS;
+  });
 }
 
 }  // extern "C"

@@ -150,23 +150,35 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
       addends[f] = wallAddendsOf(c.dtype, hh[c.dim], op.sides, c.values_low ? c.values_low + f * per_field : nullptr,
                                  c.values_high ? c.values_high + f * per_field : nullptr);
   }
-  const int force = (h->tuning.force_class == MOVE_GENERIC ? 1 : 0) | (h->tuning.force_streaming ? 2 : 0) | (h->tuning.no_streaming ? 4 : 0);
   // The one or two sides of a phase go into ONE launch, unless they add onto overlapping cells (`ordered`): then one launch per
   // side, low side first.  Several fields: the list kernels (one_choice); either end of a move in a pencil is field f's, the fields'
-  // pieces of the workspace lie one face apart; reflection and folding go as mirrored lists with the call's mask of signs.
+  // pieces of the workspace lie one face apart; reflection and folding go as mirrored lists with the call's mask of signs, wall
+  // values as wall lists with every field's addends (one launch per run of fields whose addends fit the table).
+  FieldMoveList list;
+  list.inputs = list.outputs = c.fields;
+  list.n_fields = op.n_fields;
+  list.work = c.work;
+  list.es = es;
+  list.arith = arith;
+  list.one_choice = true;
+  list.mirrored = mirrored;
+  list.fields_neg = c.fields_neg;
+  list.addends = wall ? addends.data() : nullptr;
+  list.tuning = &h->tuning;
   auto launch = [&](const std::vector<Move3D>& moves) {
     if (moves.empty()) return;
     const int n = (int)moves.size(), each = plan.ordered && moves[0].add ? 1 : n;
     if (op.n_fields == 1) {
       for (int i = 0; i < n; i += each)
-        launchMoves(moves.data() + i, each, bufs, es, c.stream, &h->tuning, nullptr, nullptr, arith, c.value, wall ? addends.data() : nullptr);
-    } else if (wall) {  // one launch per run of fields whose addends fit the table (kernels.h launchFieldWallList)
-      launchFieldWallList(moves.data(), n, c.fields, op.n_fields, es, c.stream, force, nullptr, arith, c.fields_neg, addends.data());
-    } else {
-      const std::vector<i64> steps(n, plan.face_elements);
-      for (int i = 0; i < n; i += each)
-        launchFieldMoveList(moves.data() + i, steps.data() + i, each, c.fields, c.fields, op.n_fields, c.work, es, c.stream, force, nullptr,
-                            true, arith, mirrored, c.fields_neg);
+        launchMoves(moves.data() + i, each, bufs, es, c.stream, &h->tuning, nullptr, nullptr, arith, c.value, list.addends);
+      return;
+    }
+    const std::vector<i64> steps(n, plan.face_elements);
+    for (int i = 0; i < n; i += each) {
+      list.moves = moves.data() + i;
+      list.work_steps = steps.data() + i;
+      list.n = each;
+      launchFieldMoveList(list, c.stream);
     }
   };
 

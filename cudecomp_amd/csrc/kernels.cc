@@ -862,72 +862,101 @@ void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStr
 }
 
 // ---------------------------------------------------------------------------------------------
-// lists of field-moves (kernels.h; kernels_field_transpose.hip)
+// lists of field-moves (kernels.h FieldMoveList; kernels_field_transpose.hip and its siblings)
 // ---------------------------------------------------------------------------------------------
-std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i64* work_steps, int n, void* const* inputs,
-                                                   void* const* outputs, int n_fields, void* work, int es, int force,
-                                                   bool one_choice, ArithType arith, bool mirrored, unsigned int fields_neg) {
-  if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
-  if (n < 0 || (n > 0 && !moves)) CD_INTERNAL_ERROR("field-move list without moves");
-  if (n_fields < 1 || n_fields > kMaxFields || !inputs) CD_INTERNAL_ERROR("field count out of range");
-  for (int f = 0; f < n_fields; ++f)
-    if (!inputs[f] || (outputs && !outputs[f])) CD_INTERNAL_ERROR("null field buffer");
-  const bool force_generic = (force & 1) != 0;
-  char* const w = static_cast<char*>(work);
-  // the operation of the list: every move carries the same one
-  bool add = false, take = false;
-  for (int i = 0; i < n; ++i) {
-    if (i == 0) add = moves[i].add, take = moves[i].take;
-    else if (moves[i].add != add || moves[i].take != take) CD_INTERNAL_ERROR("the field-moves of one list carry different operations");
-  }
-  if (add || mirrored) {  // (a mirrored list always: the sign mask is that of its real type)
-    if (arith == ARITH_NONE) CD_INTERNAL_ERROR(mirrored ? "mirrored field-move without a real type" : "adding field-move without an arithmetic type");
-    if (es % arithBytes(arith) != 0 || es / arithBytes(arith) > 2) CD_INTERNAL_ERROR("element size does not fit the arithmetic type");
-  }
-  if (!mirrored && fields_neg != 0) CD_INTERNAL_ERROR("only mirrored field-moves carry signs");
-  if (mirrored && n_fields < kMaxFields && (fields_neg >> n_fields) != 0) CD_INTERNAL_ERROR("sign bit of a field the list does not have");
-  if (mirrored && take && !add) CD_INTERNAL_ERROR("a mirrored field-move that clears its source must add (fold)");
-  // wall field-moves (kernels_field_wall.hip): a mirrored list whose moves all name a side (Move3D::affine); neither adds nor takes
-  bool wall = false;
-  for (int i = 0; i < n; ++i) {
-    if (i == 0) wall = moves[i].affine != 0;
-    else if ((moves[i].affine != 0) != wall) CD_INTERNAL_ERROR("the field-moves of one list carry different operations");
-  }
-  if (wall && (!mirrored || add || take)) CD_INTERNAL_ERROR("wall field-moves are mirrored and neither add onto their destination nor take");
+namespace {
 
-  // each move's shared geometry, normalised, its ends, and the addresses every field's first element can have or-ed together (the
-  // 2-byte rule: all fields' pencils and all workspace pieces)
-  std::vector<Move3D> norm;
-  std::vector<Classified> cs;
-  std::vector<FieldMove> fms;
-  std::vector<int> index;
-  std::vector<bool> rows_fit;  // the move's fastest dim is contiguous on both sides (and not the mirrored one)
-  for (int i = 0; i < n; ++i) {
-    const Move3D& in = moves[i];
-    if (mirrored) {
-      // the moves of kernels_field_mirror.hip: reflect- or fold-moves between cells of the fields' own buffers; their signs travel
-      // in fields_neg, never in the move
-      if (!in.reflect || in.negate || in.fill || in.dst_row_pitch != 0 || in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK)
-        CD_INTERNAL_ERROR("mirrored field-moves reflect or fold exactly their cells of the fields' buffers, unsigned");
-      if (wall && ((in.affine != 1 && in.affine != 2) || wallLayers(in) < 0))
-        CD_INTERNAL_ERROR("wall field-move without a side or a mirrored dim, or with more layers than the addend table holds");
-    } else if (in.fill || in.reflect || in.negate || in.affine != 0 || in.dst_row_pitch != 0) {
-      CD_INTERNAL_ERROR("field-moves copy, add or take exactly their cells");
-    }
-    if (add && in.dst_buf == BUF_WORK) CD_INTERNAL_ERROR("adding field-moves never add onto the workspace");
-    if (take && in.src_buf == BUF_WORK) CD_INTERNAL_ERROR("taking field-moves never clear the workspace");
-    if ((in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK) && !work) CD_INTERNAL_ERROR("field-move through a workspace that was not given");
-    if ((in.src_buf == BUF_OUT || in.dst_buf == BUF_OUT) && !outputs) CD_INTERNAL_ERROR("field-move onto an output list that was not given");
-    for (int d = 0; d < 3; ++d)
-      if ((in.ss[d] < 0 && !mirrored) || in.ds[d] < 0 || in.extent[d] < 0) CD_INTERNAL_ERROR("negative stride or extent in a field-move");
+// the families of field-move kernels and the kinds of each: {rows, element-wise}
+enum FieldFamily { FIELDS_COPY, FIELDS_ADD, FIELDS_TAKE, FIELDS_ADD_TAKE, FIELDS_REFLECT, FIELDS_FOLD, FIELDS_FOLD_TAKE, FIELDS_WALL };
+constexpr KernelKind kFieldKinds[][2] = {
+    {K_ROWS_FIELDS, K_GENERIC_FIELDS},           {K_ROWS_FIELDS_ADD, K_GENERIC_FIELDS_ADD},
+    {K_ROWS_FIELDS_TAKE, K_GENERIC_FIELDS_TAKE}, {K_ROWS_FIELDS_ADD_TAKE, K_GENERIC_FIELDS_ADD_TAKE},
+    {K_ROWS_FIELDS_REFLECT, K_GENERIC_FIELDS_REFLECT}, {K_ROWS_FIELDS_FOLD, K_GENERIC_FIELDS_FOLD},
+    {K_ROWS_FIELDS_FOLD_TAKE, K_GENERIC_FIELDS_FOLD_TAKE}, {K_ROWS_FIELDS_WALL, K_GENERIC_FIELDS_WALL}};
+struct FieldListOp {  // the operation of a list: what every one of its moves carries
+  bool add, take, wall;
+  FieldFamily family;
+};
+struct FieldMoveItem {  // a move with cells on its way into a launch
+  Classified c;   // the kernel choice and the geometry in the kernel's units (of c.dm.src / dst only the alignment is read)
+  Move3D norm;    // the shared geometry, normalised (mirrored lists: the mirrored dim back in as the row or plane index)
+  FieldMove fm;
+  int index;      // the list entry it is
+  bool rows_fit;  // its fastest dim is contiguous on both sides (and not the mirrored one)
+  int along;      // wall lists: the entry of the kernel's e[] whose index is the destination layer (the mirrored one); -1 otherwise
+};
+
+// the rules of the list as a whole; "one operation per list" gives the operation
+FieldListOp checkFieldMoveList(const FieldMoveList& r) {
+  const int es = r.es;
+  if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
+  if (r.n < 0 || (r.n > 0 && !r.moves)) CD_INTERNAL_ERROR("field-move list without moves");
+  if (r.n_fields < 1 || r.n_fields > kMaxFields || !r.inputs) CD_INTERNAL_ERROR("field count out of range");
+  for (int f = 0; f < r.n_fields; ++f)
+    if (!r.inputs[f] || (r.outputs && !r.outputs[f])) CD_INTERNAL_ERROR("null field buffer");
+  FieldListOp op{};
+  for (int i = 0; i < r.n; ++i) {
+    if (i == 0) op.add = r.moves[i].add, op.take = r.moves[i].take;
+    else if (r.moves[i].add != op.add || r.moves[i].take != op.take) CD_INTERNAL_ERROR("the field-moves of one list carry different operations");
+  }
+  if (op.add || r.mirrored) {  // (a mirrored list always: the sign mask is that of its real type)
+    if (r.arith == ARITH_NONE) CD_INTERNAL_ERROR(r.mirrored ? "mirrored field-move without a real type" : "adding field-move without an arithmetic type");
+    if (es % arithBytes(r.arith) != 0 || es / arithBytes(r.arith) > 2) CD_INTERNAL_ERROR("element size does not fit the arithmetic type");
+  }
+  if (!r.mirrored && r.fields_neg != 0) CD_INTERNAL_ERROR("only mirrored field-moves carry signs");
+  if (r.mirrored && r.n_fields < kMaxFields && (r.fields_neg >> r.n_fields) != 0) CD_INTERNAL_ERROR("sign bit of a field the list does not have");
+  if (r.mirrored && op.take && !op.add) CD_INTERNAL_ERROR("a mirrored field-move that clears its source must add (fold)");
+  // wall field-moves (kernels_field_wall.hip): a mirrored list whose moves all name a side (Move3D::affine); neither adds nor takes
+  for (int i = 0; i < r.n; ++i) {
+    if (i == 0) op.wall = r.moves[i].affine != 0;
+    else if ((r.moves[i].affine != 0) != op.wall) CD_INTERNAL_ERROR("the field-moves of one list carry different operations");
+  }
+  if (op.wall && (!r.mirrored || op.add || op.take)) CD_INTERNAL_ERROR("wall field-moves are mirrored and neither add onto their destination nor take");
+  if (op.wall) op.family = FIELDS_WALL;
+  else if (r.mirrored) op.family = op.add ? (op.take ? FIELDS_FOLD_TAKE : FIELDS_FOLD) : FIELDS_REFLECT;
+  else op.family = op.take ? (op.add ? FIELDS_ADD_TAKE : FIELDS_TAKE) : (op.add ? FIELDS_ADD : FIELDS_COPY);
+  return op;
+}
+
+// the rules of one move (empty ones included)
+void checkFieldMove(const FieldMoveList& r, const FieldListOp& op, const Move3D& in) {
+  if (r.mirrored) {  // (reflect- or fold-moves between cells of the fields' own buffers; their signs travel in fields_neg)
+    if (!in.reflect || in.negate || in.fill || in.dst_row_pitch != 0 || in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK)
+      CD_INTERNAL_ERROR("mirrored field-moves reflect or fold exactly their cells of the fields' buffers, unsigned");
+    if (op.wall && ((in.affine != 1 && in.affine != 2) || wallLayers(in) < 0))
+      CD_INTERNAL_ERROR("wall field-move without a side or a mirrored dim, or with more layers than the addend table holds");
+  } else if (in.fill || in.reflect || in.negate || in.affine != 0 || in.dst_row_pitch != 0) {
+    CD_INTERNAL_ERROR("field-moves copy, add or take exactly their cells");
+  }
+  if (op.add && in.dst_buf == BUF_WORK) CD_INTERNAL_ERROR("adding field-moves never add onto the workspace");
+  if (op.take && in.src_buf == BUF_WORK) CD_INTERNAL_ERROR("taking field-moves never clear the workspace");
+  if ((in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK) && !r.work) CD_INTERNAL_ERROR("field-move through a workspace that was not given");
+  if ((in.src_buf == BUF_OUT || in.dst_buf == BUF_OUT) && !r.outputs) CD_INTERNAL_ERROR("field-move onto an output list that was not given");
+  for (int d = 0; d < 3; ++d)
+    if ((in.ss[d] < 0 && !r.mirrored) || in.ds[d] < 0 || in.extent[d] < 0) CD_INTERNAL_ERROR("negative stride or extent in a field-move");
+}
+
+// every move with cells, checked: first its shared geometry, normalised, its ends, and the addresses every field's first element can
+// have or-ed together (the 2-byte rule: all fields' pencils and all workspace pieces) ...
+std::vector<FieldMoveItem> classifyFieldMoves(const FieldMoveList& r, const FieldListOp& op) {
+  const int es = r.es;
+  const char* const w = static_cast<const char*>(r.work);
+  std::vector<FieldMoveItem> items;
+  items.reserve(r.n);
+  for (int i = 0; i < r.n; ++i) {
+    const Move3D& in = r.moves[i];
+    checkFieldMove(r, op, in);
     if (in.elements() == 0) continue;
-    const i64 step = work_steps ? work_steps[i] : 0;
+    const i64 step = r.work_steps ? r.work_steps[i] : 0;
     if (step < 0) CD_INTERNAL_ERROR("negative workspace step in a field-move");
-    Move3D m = in;
+    FieldMoveItem it{};
+    it.index = i;
+    it.along = -1;
+    it.norm = in;
     bool mirrored_fastest = false;
-    if (mirrored) m = mirrorGeometry(in, mirrored_fastest);  // (the mirrored dim back in as the row or plane index)
-    else normalizeMove(m);
-    FieldMove fm{};
+    if (r.mirrored) it.norm = mirrorGeometry(in, mirrored_fastest);
+    else normalizeMove(it.norm);
+    FieldMove& fm = it.fm;
     fm.src_end = in.src_buf == BUF_WORK ? kEndWork : (in.src_buf == BUF_OUT ? kEndOutput : kEndInput);
     fm.dst_end = in.dst_buf == BUF_WORK ? kEndWork : (in.dst_buf == BUF_OUT ? kEndOutput : kEndInput);
     fm.src_off = in.src_off * es;
@@ -935,55 +964,47 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
     fm.src_step = fm.src_end == kEndWork ? step * es : 0;
     fm.dst_step = fm.dst_end == kEndWork ? step * es : 0;
     uintptr_t address_bits = 0;
-    for (int f = 0; f < n_fields; ++f) {
-      const char* sb = fm.src_end == kEndWork ? w + f * fm.src_step : static_cast<const char*>(fm.src_end == kEndOutput ? outputs[f] : inputs[f]);
-      const char* db = fm.dst_end == kEndWork ? w + f * fm.dst_step : static_cast<const char*>(fm.dst_end == kEndOutput ? outputs[f] : inputs[f]);
+    for (int f = 0; f < r.n_fields; ++f) {
+      const char* sb = fm.src_end == kEndWork ? w + f * fm.src_step : static_cast<const char*>(fm.src_end == kEndOutput ? r.outputs[f] : r.inputs[f]);
+      const char* db = fm.dst_end == kEndWork ? w + f * fm.dst_step : static_cast<const char*>(fm.dst_end == kEndOutput ? r.outputs[f] : r.inputs[f]);
       address_bits |= reinterpret_cast<uintptr_t>(sb) + (uintptr_t)fm.src_off;
       address_bits |= reinterpret_cast<uintptr_t>(db) + (uintptr_t)fm.dst_off;
     }
-    Classified c{};
-    c.k.es = es;
-    c.k.arith = (add || mirrored) ? arith : ARITH_NONE;
-    c.elements = m.elements();
-    c.dm.src = reinterpret_cast<const char*>(address_bits);  // (only its alignment is read)
-    c.dm.dst = reinterpret_cast<char*>(address_bits);
-    norm.push_back(m);
-    cs.push_back(c);
-    fms.push_back(fm);
-    index.push_back(i);
-    rows_fit.push_back(m.ss[0] <= 1 && m.ds[0] <= 1 && !mirrored_fastest);
+    it.c.k.es = es;
+    it.c.k.arith = (op.add || r.mirrored) ? r.arith : ARITH_NONE;
+    it.c.elements = it.norm.elements();
+    it.c.dm.src = reinterpret_cast<const char*>(address_bits);
+    it.c.dm.dst = reinterpret_cast<char*>(address_bits);
+    it.rows_fit = it.norm.ss[0] <= 1 && it.norm.ds[0] <= 1 && !mirrored_fastest;
+    items.push_back(it);
   }
-  // one_choice: rows only if every move has contiguous rows, then the narrowest of their lane widths; the largest move decides
-  // the access mode
+  // ... then the kernel choice of each and its geometry in that kernel's units
+  const KernelTuning& tuning = r.tuning ? *r.tuning : kDefaultTuning;
+  const bool force_generic = tuning.force_class == MOVE_GENERIC;
+  // one_choice: rows only if every move has contiguous rows, then the narrowest of their lanes; the largest move decides the access
   bool all_rows = !force_generic;
   int lanes = 16;
   i64 largest = 0;
-  for (size_t i = 0; one_choice && i < cs.size(); ++i) {
-    all_rows = all_rows && rows_fit[i];
-    largest = std::max(largest, cs[i].elements);
+  for (size_t i = 0; r.one_choice && i < items.size(); ++i) {
+    all_rows = all_rows && items[i].rows_fit;
+    largest = std::max(largest, items[i].c.elements);
     if (!all_rows) continue;
-    Classified c = cs[i];
-    rowVectors(c, norm[i]);
+    Classified c = items[i].c;
+    rowVectors(c, items[i].norm);
     lanes = std::min(lanes, c.k.vec);
   }
-  for (size_t i = 0; i < cs.size(); ++i) {
-    const Move3D& m = norm[i];
-    Classified& c = cs[i];
-    FieldMove& fm = fms[i];
-    // Access: cached while the move is below kStreamBytes PER FIELD, non-temporal loads and stores from there -- the project's
-    // rule for copies, unmeasured for these kernels; the element-wise kernel always caches.  Additions and
-    // takes: the accumulation's rule by the same size -- access 1 = non-temporal source loads and (take) zero stores, the destination
-    // of an addition always cached, the plain take streaming all of it; unmeasured for these kernels too.
-    const bool streaming = ((one_choice ? largest : c.elements) * es >= kStreamBytes || (force & 2)) && !(force & 4);
+  for (FieldMoveItem& it : items) {
+    const Move3D& m = it.norm;
+    Classified& c = it.c;
+    // (the access rule, unmeasured for these kernels: kernels.h FieldMoveList::tuning)
+    const bool streaming = ((r.one_choice ? largest : c.elements) * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming;
     int t = -1;
-    if (!force_generic && !one_choice && !add && !take && !mirrored && m.ss[0] == 1) {  // (additions, takes and mirrors never transpose)
+    if (!force_generic && !r.one_choice && op.family == FIELDS_COPY && m.ss[0] == 1) {  // (additions, takes and mirrors never transpose)
       if (m.ds[1] == 1) t = 1;
       if (m.ds[2] == 1) t = 2;
     }
-    if (one_choice ? all_rows : (!force_generic && rows_fit[i])) {
-      if (wall) c.k.kind = K_ROWS_FIELDS_WALL;
-      else if (mirrored) c.k.kind = add ? (take ? K_ROWS_FIELDS_FOLD_TAKE : K_ROWS_FIELDS_FOLD) : K_ROWS_FIELDS_REFLECT;
-      else c.k.kind = take ? (add ? K_ROWS_FIELDS_ADD_TAKE : K_ROWS_FIELDS_TAKE) : (add ? K_ROWS_FIELDS_ADD : K_ROWS_FIELDS);
+    if (r.one_choice ? all_rows : (!force_generic && it.rows_fit)) {
+      c.k.kind = kFieldKinds[op.family][0];
       c.k.access = streaming ? 1 : 0;
       rowVectors(c, m, lanes);
       if (c.k.vec < es) CD_INTERNAL_ERROR("field-move narrower than one element");
@@ -1003,58 +1024,61 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
       c.t1 = (unsigned int)((c.dm.e[1] + c.k.tj - 1) / c.k.tj);
       c.blocks = (unsigned long long)c.t0 * c.t1 * (unsigned long long)c.dm.e[2];
     } else {
-      if (wall) c.k.kind = K_GENERIC_FIELDS_WALL;
-      else if (mirrored) c.k.kind = add ? (take ? K_GENERIC_FIELDS_FOLD_TAKE : K_GENERIC_FIELDS_FOLD) : K_GENERIC_FIELDS_REFLECT;
-      else c.k.kind = take ? (add ? K_GENERIC_FIELDS_ADD_TAKE : K_GENERIC_FIELDS_TAKE) : (add ? K_GENERIC_FIELDS_ADD : K_GENERIC_FIELDS);
+      c.k.kind = kFieldKinds[op.family][1];
       c.k.access = 0;
-      genericGeometry(c, m, mirrored);  // (mirrored, without a destination-fast dim: along the longest, as the single calls)
+      genericGeometry(c, m, r.mirrored);  // (mirrored, without a destination-fast dim: along the longest, as the single calls)
     }
-    if (c.blocks == 0 || c.blocks * (unsigned long long)n_fields > 0x7fffffffULL)
+    if (c.blocks == 0 || c.blocks * (unsigned long long)r.n_fields > 0x7fffffffULL)
       CD_NOT_SUPPORTED("single block move too large for one launch");
+    FieldMove& fm = it.fm;
     for (int d = 0; d < 3; ++d) {
       fm.e[d] = c.dm.e[d];
       fm.ss[d] = c.dm.ss[d];
       fm.ds[d] = c.dm.ds[d];
+      if (op.wall && m.ss[d] < 0) it.along = d;
     }
-    c.p1 = -1;  // wall field-moves: the entry of the kernel's e[] whose index is the destination layer (the mirrored one)
-    for (int d = 0; wall && d < 3; ++d)
-      if (m.ss[d] < 0) c.p1 = d;
     fm.p0 = c.p0;
     fm.t0 = c.t0;
     fm.t1 = c.t1;
     fm.blocks = (unsigned int)c.blocks;
   }
-  // moves of one phase are independent: regrouped by equal kernel choice in the order of first appearance, cut at kMaxBatch
+  return items;
+}
+
+// moves of one phase are independent: regrouped by equal kernel choice in the order of first appearance, cut at kMaxBatch
+std::vector<FieldMoveLaunch> groupFieldMoves(const FieldMoveList& r, const std::vector<FieldMoveItem>& items) {
+  const int n_fields = r.n_fields;
   std::vector<FieldMoveLaunch> launches;
-  std::vector<bool> done(cs.size(), false);
-  for (size_t i = 0; i < cs.size(); ++i) {
+  std::vector<bool> done(items.size(), false);
+  for (size_t i = 0; i < items.size(); ++i) {
     if (done[i]) continue;
     FieldMoveLaunch l{};
     FieldMoveBatch& b = l.b;
-    l.k = cs[i].k;
-    l.cls = classOf(cs[i].k.kind);
-    l.fields_neg = fields_neg;
+    l.k = items[i].c.k;
+    l.cls = classOf(l.k.kind);
+    l.fields_neg = r.fields_neg;
     b.n_fields = n_fields;
-    b.work = w;
+    b.work = static_cast<char*>(r.work);
     for (int f = 0; f < n_fields; ++f) {
-      b.in[f] = static_cast<char*>(inputs[f]);
-      b.out[f] = outputs ? static_cast<char*>(outputs[f]) : nullptr;
+      b.in[f] = static_cast<char*>(r.inputs[f]);
+      b.out[f] = r.outputs ? static_cast<char*>(r.outputs[f]) : nullptr;
     }
     unsigned long long blocks = 0;
-    for (size_t j = i; j < cs.size() && b.n < kMaxBatch; ++j) {
-      if (done[j] || !(cs[j].k == cs[i].k)) continue;
-      const unsigned long long mine = cs[j].blocks * (unsigned long long)n_fields;
+    for (size_t j = i; j < items.size() && b.n < kMaxBatch; ++j) {
+      const Classified& c = items[j].c;
+      if (done[j] || !(c.k == l.k)) continue;
+      const unsigned long long mine = c.blocks * (unsigned long long)n_fields;
       if (blocks + mine > 0x7fffffffULL) {  // (never the first of a group: checked per move above)
-        if (one_choice) CD_NOT_SUPPORTED("field-moves too large for one launch");
+        if (r.one_choice) CD_NOT_SUPPORTED("field-moves too large for one launch");
         break;
       }
       b.first_block[b.n] = (unsigned int)blocks;
-      b.m[b.n] = fms[j];
+      b.m[b.n] = items[j].fm;
       blocks += mine;
-      l.elements += cs[j].elements * n_fields;
-      l.blocks_per_field += (unsigned int)cs[j].blocks;
-      l.index[b.n] = index[j];
-      l.along[b.n] = cs[j].p1;
+      l.elements += c.elements * n_fields;
+      l.blocks_per_field += (unsigned int)c.blocks;
+      l.index[b.n] = items[j].index;
+      l.along[b.n] = items[j].along;
       ++b.n;
       done[j] = true;
     }
@@ -1065,39 +1089,38 @@ std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i6
   return launches;
 }
 
-void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void* const* inputs, void* const* outputs, int n_fields,
-                         void* work, int es, hipStream_t stream, int force, KernelStats* stats, bool one_choice, ArithType arith,
-                         bool mirrored, unsigned int fields_neg) {
-  for (const FieldMoveLaunch& l :
-       planFieldMoveLaunches(moves, work_steps, n, inputs, outputs, n_fields, work, es, force, one_choice, arith, mirrored, fields_neg)) {
-    if (l.k.kind >= K_ROWS_FIELDS_WALL) CD_INTERNAL_ERROR("wall field-moves are launched by launchFieldWallList, with their addends");
-    spellKernelName(l.k);
-    ++g_data_launches;
-    if (l.k.kind >= K_ROWS_FIELDS_REFLECT) launchFieldMirrorBatch(l.k, l.b, l.fields_neg, l.blocks, stream);
-    else if (l.k.kind >= K_ROWS_FIELDS_ADD) launchFieldAccumulateBatch(l.k, l.b, l.blocks, stream);
-    else launchFieldMoveBatch(l.k, l.b, l.blocks, stream);
-    if (stats) {
-      stats->launches[l.cls] += 1;
-      stats->elements[l.cls] += l.elements;
-    }
+// a launch of a list: named, counted, made, accounted
+template <typename Make>
+void runFieldLaunch(const FieldMoveLaunch& l, KernelStats* stats, Make make) {
+  spellKernelName(l.k);
+  ++g_data_launches;
+  make();
+  if (stats) {
+    stats->launches[l.cls] += 1;
+    stats->elements[l.cls] += l.elements;
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// lists of wall field-moves (kernels.h; kernels_field_wall.hip)
-// ---------------------------------------------------------------------------------------------
+}  // namespace
+
+std::vector<FieldMoveLaunch> planFieldMoveLaunches(const FieldMoveList& list) {
+  const FieldListOp op = checkFieldMoveList(list);
+  return groupFieldMoves(list, classifyFieldMoves(list, op));
+}
+
 int fieldsPerWallLaunch(int sides, int layers, int es) {
   if (sides < 1 || sides > kMaxBatch || layers < 1 || layers > kMaxWallHalo || (es != 2 && es != 4 && es != 8 && es != 16))
     CD_INTERNAL_ERROR("wall field-moves out of the addend table's range");
   return std::min(kMaxFields, kFieldWallTableBytes / (sides * layers * es));
 }
 
-std::vector<FieldWallLaunch> planFieldWallLaunches(const Move3D* moves, int n, void* const* fields, int n_fields, int es, int force,
-                                                   ArithType arith, unsigned int fields_neg, const WallAddends* addends) {
-  if (n_fields < 1 || n_fields > kMaxFields || !fields) CD_INTERNAL_ERROR("field count out of range");
+std::vector<FieldWallLaunch> planFieldWallLaunches(const FieldMoveList& list) {
+  const Move3D* moves = list.moves;
+  const int n = list.n, n_fields = list.n_fields, es = list.es;
+  if (n_fields < 1 || n_fields > kMaxFields || !list.inputs) CD_INTERNAL_ERROR("field count out of range");
   if (n < 0 || n > 2 || (n > 0 && !moves)) CD_INTERNAL_ERROR("wall field-moves: the one or two sides of a call");
-  if (n_fields < kMaxFields && (fields_neg >> n_fields) != 0) CD_INTERNAL_ERROR("sign bit of a field the list does not have");
-  if (!addends) CD_INTERNAL_ERROR("wall field-moves without the call's addends");
+  if (n_fields < kMaxFields && (list.fields_neg >> n_fields) != 0) CD_INTERNAL_ERROR("sign bit of a field the list does not have");
+  if (!list.addends) CD_INTERNAL_ERROR("wall field-moves without the call's addends");
   std::vector<FieldWallLaunch> out;
   // S, the sides written, and h, the layers: those of the moves that have cells
   int sides = 0, layers = 0;
@@ -1111,10 +1134,17 @@ std::vector<FieldWallLaunch> planFieldWallLaunches(const Move3D* moves, int n, v
   }
   if (sides == 0) return out;
   const int per_launch = fieldsPerWallLaunch(sides, layers, es);
+  // a run of fields: the sides as a mirrored list with one choice, both ends in the fields' own buffers
+  FieldMoveList run = list;
+  run.work_steps = nullptr;
+  run.work = nullptr;
+  run.one_choice = run.mirrored = true;
   for (int f0 = 0; f0 < n_fields; f0 += per_launch) {
     const int nf = std::min(per_launch, n_fields - f0);
-    const unsigned int neg = (fields_neg >> f0) & (nf == kMaxFields ? 0xffffffffu : ((1u << nf) - 1u));
-    std::vector<FieldMoveLaunch> ls = planFieldMoveLaunches(moves, nullptr, n, fields + f0, fields + f0, nf, nullptr, es, force, true, arith, true, neg);
+    run.inputs = run.outputs = list.inputs + f0;
+    run.n_fields = nf;
+    run.fields_neg = (list.fields_neg >> f0) & (nf == kMaxFields ? 0xffffffffu : ((1u << nf) - 1u));
+    std::vector<FieldMoveLaunch> ls = planFieldMoveLaunches(run);
     if (ls.size() != 1 || ls[0].b.n != sides) CD_INTERNAL_ERROR("the sides of a wall-value call did not come out as one launch");
     FieldWallLaunch w{};
     w.l = ls[0];
@@ -1128,23 +1158,26 @@ std::vector<FieldWallLaunch> planFieldWallLaunches(const Move3D* moves, int n, v
       w.walk.along[i] = w.l.along[i];
       for (int f = 0; f < nf; ++f)
         for (int j = 0; j < mine; ++j)  // destination order: the low side reversed, as wallTableRow
-          std::memcpy(bytes + ((size_t)(i * nf + f) * layers + j) * es, addends[f0 + f].v[side][side == 0 ? mine - 1 - j : j], es);
+          std::memcpy(bytes + ((size_t)(i * nf + f) * layers + j) * es, list.addends[f0 + f].v[side][side == 0 ? mine - 1 - j : j], es);
     }
     out.push_back(w);
   }
   return out;
 }
 
-void launchFieldWallList(const Move3D* moves, int n, void* const* fields, int n_fields, int es, hipStream_t stream, int force,
-                         KernelStats* stats, ArithType arith, unsigned int fields_neg, const WallAddends* addends) {
-  for (const FieldWallLaunch& w : planFieldWallLaunches(moves, n, fields, n_fields, es, force, arith, fields_neg, addends)) {
-    spellKernelName(w.l.k);
-    ++g_data_launches;
-    launchFieldWallBatch(w.l.k, w.l.b, w.l.fields_neg, w.table, w.walk, w.l.blocks, stream);
-    if (stats) {
-      stats->launches[w.l.cls] += 1;
-      stats->elements[w.l.cls] += w.l.elements;
-    }
+void launchFieldMoveList(const FieldMoveList& list, hipStream_t stream, KernelStats* stats) {
+  if (list.addends) {  // a wall list: one launch per run of fields whose addends fit the table
+    for (const FieldWallLaunch& w : planFieldWallLaunches(list))
+      runFieldLaunch(w.l, stats, [&] { launchFieldWallBatch(w.l.k, w.l.b, w.l.fields_neg, w.table, w.walk, w.l.blocks, stream); });
+    return;
+  }
+  for (const FieldMoveLaunch& l : planFieldMoveLaunches(list)) {
+    if (l.k.kind >= K_ROWS_FIELDS_WALL) CD_INTERNAL_ERROR("wall field-moves without the call's addends");
+    runFieldLaunch(l, stats, [&] {
+      if (l.k.kind >= K_ROWS_FIELDS_REFLECT) launchFieldMirrorBatch(l.k, l.b, l.fields_neg, l.blocks, stream);
+      else if (l.k.kind >= K_ROWS_FIELDS_ADD) launchFieldAccumulateBatch(l.k, l.b, l.blocks, stream);
+      else launchFieldMoveBatch(l.k, l.b, l.blocks, stream);
+    });
   }
 }
 

@@ -80,45 +80,74 @@ std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3]
 void describeMove(const Move3D& m, const void* src, void* dst, int es, const KernelTuning* tuning, long long out[10]);
 
 // ---- lists of field-moves: a list of moves, each for several (input, output) pairs of buffers (kernels_field_transpose.hip,
-// kernels_field_accumulate.hip, kernels_field_mirror.hip) ----
-// The moves of one phase of a multi-field transpose (include/cudecomp_transpose_fields.h) or of a multi-field halo update
-// (include/cudecomp_halo_fields.h): moves[0 .. n - 1] share their geometry among `n_fields` (1 .. kern::kMaxFields) fields.  An end
-// of a move in BUF_IN lies in inputs[f] + offset, an end in BUF_OUT in outputs[f] + offset, an end in BUF_WORK at
-// work + (offset + f * work_steps[i]) elements (work_steps == nullptr: all zero).
-// Each move's shared geometry is classified once: rows (rowVectors' rule) when its fastest dim is contiguous on both sides, the
-// LDS-tiled transposition (chooseTranspose's lane-width rule, one tile per element size and lane width) when source and
-// destination rows run along different dims of at least 4 elements, element by element (genericGeometry's) otherwise.  For
-// 2-byte elements the lanes narrow as soon as ANY field's address, any workspace piece or any stride is 2 mod 4.  Moves with equal
-// KernelChoice share a launch, in the order of first appearance, cut at kMaxBatch moves (and before 2^31 - 1 workgroups).  The
-// kernels copy exactly the cells of the moves -- never a window, lines, shifted or dense form.  Access: cached while a move is
-// below kStreamBytes PER FIELD, non-temporal loads and stores from there (unmeasured for these kernels); the element-wise kernel
-// always caches.  force: bit 0 the element-wise kernel, bit 1 non-temporal access regardless of the size, bit 2 cached access
-// regardless of the size.
-// one_choice (the phases of a halo update: its one or two sides): ONE kernel choice serves the list, hence one launch -- rows only
-// when every move has contiguous rows, then the narrowest of the moves' lane widths; never the transposition; non-temporal access
-// when the LARGEST move reaches kStreamBytes per field.  More than 2^31 - 1 workgroups in all are then NOT_SUPPORTED, not a
-// second launch.
-// The OPERATION of a list (kernels_field_accumulate.hip) is what its moves carry, the same on every move: copy (neither flag), add
-// (Move3D::add: dst += src in `arith`, the real type the elements consist of, with the operand order of the single accumulation),
-// take (Move3D::take: dst = src; src = 0) or add-take (both).  Adding and taking lists run as rows or element by element, never
-// transposed, over exactly the cells of their moves; sources are disjoint from all destinations.  Access: the accumulation's rule by
-// the size of one field's move -- cached below kStreamBytes, from there non-temporal source loads and, with take, non-temporal zero
-// stores (the plain take: all of it); the destination of an add is always cached (unmeasured for these kernels).
-// A move with fill, reflect, negate or dst_row_pitch, moves of one list with different operations, an add without an arithmetic
-// type (or one the element size does not fit), an add whose destination is the workspace, a take whose source is the workspace, a
-// workspace end without a workspace and an output end without `outputs` are internal errors before anything is launched; a move
-// of more than 2^31 - 1 workgroups is NOT_SUPPORTED.
-// MIRRORED lists (`mirrored`; kernels_field_mirror.hip: the one or two sides of a multi-field reflection or fold,
-// include/cudecomp_halo_wall_fields.h): every move is a reflect-move (Move3D::reflect: one dim with a negative source stride,
-// src_off at the source cell of its index 0) or a fold-move (with Move3D::add, and Move3D::take when it clears its source), both
-// ends in the fields' own buffers.  `arith`, the real type of the elements, is always needed; bit f of `fields_neg` says that the
-// sign bits of field f's source are flipped on the way (parity -1) -- Move3D::negate is NOT used: the signs are no part of the
-// kernel choice, so one plan and one kernel serve every combination of parities.  Each move is classified as the single calls
-// classify it (rows when the fastest dim is contiguous on both sides and not the mirrored one, element by element otherwise --
-// lanes along the longest dim when there is no destination-fast one -- never transposed); one_choice as above.  Access: the
-// reflection's / the fold's rule by the size of one field's move (unmeasured for these kernels); the element-wise kernels always
-// cache.  Without `mirrored` a reflect-move, a sign or a negative stride stays the internal error it was; with it a move that is
-// no reflect-move, carries negate, fill or dst_row_pitch, touches the workspace or takes without adding is one.
+// kernels_field_accumulate.hip, kernels_field_mirror.hip, kernels_field_wall.hip) ----
+// The request: the moves of one phase of a multi-field transpose (include/cudecomp_transpose_fields.h) or of a multi-field halo call
+// (include/cudecomp_halo_fields.h and its siblings), which share their geometry among the fields.  The planners and the launcher
+// below take nothing else.  A list that breaks a rule marked (internal error) is refused before anything is launched.
+struct FieldMoveList {
+  // moves[0 .. n - 1].  Each move's shared geometry is classified once: rows (rowVectors' rule) when its fastest dim is contiguous on
+  // both sides, the LDS-tiled transposition (chooseTranspose's lane-width rule, one tile per element size and lane width) when source
+  // and destination rows run along different dims of at least 4 elements, element by element (genericGeometry's) otherwise.  Moves
+  // with equal KernelChoice share a launch, in the order of first appearance, cut at kMaxBatch moves (and before 2^31 - 1
+  // workgroups).  The kernels copy exactly the cells of the moves -- never a window, lines, shifted or dense form: a move with fill,
+  // negate or dst_row_pitch is an internal error; a move of more than 2^31 - 1 workgroups is NOT_SUPPORTED.
+  // The OPERATION of a list (kernels_field_accumulate.hip) is what its moves carry, the same on every move (internal error): copy
+  // (neither flag), add (Move3D::add: dst += src in `arith`, with the operand order of the single accumulation), take (Move3D::take:
+  // dst = src; src = 0) or add-take (both).  Adding and taking lists run as rows or element by element, never transposed, over
+  // exactly the cells of their moves; sources are disjoint from all destinations.  An add whose destination is the workspace and a
+  // take whose source is the workspace are internal errors.
+  const Move3D* moves = nullptr;
+  int n = 0;
+  // the fields' pieces of a workspace end: an end of moves[i] in BUF_WORK lies at work + (offset + f * work_steps[i]) elements for
+  // field f (nullptr: all zero; a negative step is an internal error)
+  const i64* work_steps = nullptr;
+  // n_fields (1 .. kern::kMaxFields) fields: an end of a move in BUF_IN lies in inputs[f] + offset, an end in BUF_OUT in
+  // outputs[f] + offset.  No null entry; an output end without `outputs` is an internal error.  Buffers are only looked at as
+  // addresses by the planners.  For 2-byte elements the lanes narrow as soon as ANY field's address, any workspace piece or any
+  // stride is 2 mod 4.
+  void* const* inputs = nullptr;
+  void* const* outputs = nullptr;
+  int n_fields = 0;
+  void* work = nullptr;  // a workspace end without a workspace is an internal error
+  int es = 0;            // element size in bytes: 2, 4, 8 or 16
+  // the real type the elements consist of: needed by adding lists and, always, by mirrored ones (whose sign mask is that of the
+  // type); one the element size does not fit is an internal error
+  ArithType arith = ARITH_NONE;
+  // the phases of a halo call (their one or two sides): ONE kernel choice serves the list, hence one launch -- rows only when every
+  // move has contiguous rows, then the narrowest of the moves' lane widths; never the transposition; non-temporal access when the
+  // LARGEST move reaches kStreamBytes per field.  More than 2^31 - 1 workgroups in all are then NOT_SUPPORTED, not a second launch.
+  bool one_choice = false;
+  // MIRRORED lists (kernels_field_mirror.hip: the one or two sides of a multi-field reflection or fold,
+  // include/cudecomp_halo_wall_fields.h): every move is a reflect-move (Move3D::reflect: one dim with a negative source stride,
+  // src_off at the source cell of its index 0) or a fold-move (with Move3D::add, and Move3D::take when it clears its source), both
+  // ends in the fields' own buffers.  Move3D::negate is NOT used: the signs travel in fields_neg and are no part of the kernel
+  // choice, so one plan and one kernel serve every combination of parities.  Each move is classified as the single calls classify
+  // it (rows when the fastest dim is contiguous on both sides and not the mirrored one, element by element otherwise -- lanes along
+  // the longest dim when there is no destination-fast one -- never transposed).  Without `mirrored` a reflect-move, a sign or a
+  // negative stride is an internal error; with it a move that is no reflect-move, carries negate, fill or dst_row_pitch, touches
+  // the workspace or takes without adding is one.
+  bool mirrored = false;
+  // mirrored lists: bit f says that the sign bits of field f's source are flipped on the way (parity -1); a bit of a field the list
+  // does not have, or any bit of a list that is not mirrored, is an internal error
+  unsigned int fields_neg = 0;
+  // WALL lists (kernels_field_wall.hip: the one or two sides of a multi-field wall-value call,
+  // include/cudecomp_halo_wall_value_fields.h): non-null exactly for them.  moves[0 .. n - 1], n <= 2, are wall-moves (Move3D::reflect
+  // with Move3D::affine naming the side, no Move3D::negate) between cells of the fields' own buffers; addends[f] holds field f's
+  // converted addends per side and ghost layer (WallAddends, kernels_batch.h), read before the call returns.  Such a list is planned
+  // as a mirrored list with one_choice, whatever those two members say; its fields are `inputs`, and `outputs`, `work` and
+  // `work_steps` are not read.
+  // Launch rule: with S the moves that have cells, h the layers (the extent of the mirrored dim) and es the element size, one launch
+  // serves F = min(kern::kMaxFields, kern::kFieldWallTableBytes / (S * h * es)) consecutive fields -- what its compact addend table
+  // holds -- and the list makes ceil(n_fields / F) launches in field order.
+  const WallAddends* addends = nullptr;
+  // Of the tuning the lists read three switches (nullptr: none set): force_class == MOVE_GENERIC the element-wise kernel,
+  // force_streaming non-temporal access regardless of the size, no_streaming cached access regardless of the size (and of
+  // force_streaming).  Access otherwise, unmeasured for these kernels: copies are cached while a move is below kStreamBytes PER
+  // FIELD, non-temporal loads and stores from there; adding and taking lists follow the accumulation's rule by the same size --
+  // non-temporal source loads and, with take, non-temporal zero stores (the plain take: all of it), the destination of an add
+  // always cached; mirrored and wall lists the reflection's / the fold's rule.  The element-wise kernels always cache.
+  const KernelTuning* tuning = nullptr;
+};
 struct FieldMoveLaunch {
   KernelChoice k;
   kern::FieldMoveBatch b;
@@ -130,39 +159,25 @@ struct FieldMoveLaunch {
   int index[kern::kMaxBatch];     // index[i]: the list entry b.m[i] is
   int along[kern::kMaxBatch];     // wall field-moves: the entry of b.m[i].e[] whose index is the destination layer (-1 otherwise)
 };
-// WHICH launches launchFieldMoveList makes, in order (pure host code, no device needed; buffers are only looked at as addresses)
-std::vector<FieldMoveLaunch> planFieldMoveLaunches(const Move3D* moves, const i64* work_steps, int n, void* const* inputs,
-                                                   void* const* outputs, int n_fields, void* work, int es, int force = 0,
-                                                   bool one_choice = false, ArithType arith = ARITH_NONE, bool mirrored = false,
-                                                   unsigned int fields_neg = 0);
-void launchFieldMoveList(const Move3D* moves, const i64* work_steps, int n, void* const* inputs, void* const* outputs, int n_fields,
-                         void* work, int es, hipStream_t stream, int force = 0, KernelStats* stats = nullptr, bool one_choice = false,
-                         ArithType arith = ARITH_NONE, bool mirrored = false, unsigned int fields_neg = 0);
+// WHICH launches launchFieldMoveList makes for a list that is no wall list, in order (pure host code, no device needed; `addends` is
+// not read)
+std::vector<FieldMoveLaunch> planFieldMoveLaunches(const FieldMoveList& list);
 
-// ---- lists of WALL field-moves (kernels_field_wall.hip): the one or two sides of a multi-field wall-value call
-// (include/cudecomp_halo_wall_value_fields.h) ----
-// moves[0 .. n - 1], n <= 2, are wall-moves (Move3D::reflect with Move3D::affine naming the side, no Move3D::negate) between cells of
-// the fields' own buffers; bit f of `fields_neg` flips the sign bits of field f's source first; addends[f] holds field f's converted
-// addends per side and ghost layer (WallAddends, kernels_batch.h), read before the call returns.  Classification is that of the
-// mirrored lists with one_choice (planFieldMoveLaunches above): one kernel choice for the sides, rows or element by element.
-// Launch rule: with S the moves that have cells, h the layers (the extent of the mirrored dim) and es the element size, one launch
-// serves F = min(kern::kMaxFields, kern::kFieldWallTableBytes / (S * h * es)) consecutive fields -- what its compact addend table
-// holds -- and the list makes ceil(n_fields / F) launches in field order.  Access: the reflection's rule by the size of one field's
-// move (unmeasured for these kernels); the element-wise kernel always caches.
 struct FieldWallLaunch {
   FieldMoveLaunch l;           // its fields are fields[first_field .. first_field + l.b.n_fields)
   kern::FieldWallTable table;  // entry (move i of the launch, field f of the launch, destination layer j) at ((i * nf + f) * h + j) * es
   kern::FieldWallWalk walk;
   int first_field;
 };
-int fieldsPerWallLaunch(int sides, int layers, int es);  // F of the rule above
-// WHICH launches launchFieldWallList makes, in order (pure host code, no device needed; buffers are only looked at as addresses)
-std::vector<FieldWallLaunch> planFieldWallLaunches(const Move3D* moves, int n, void* const* fields, int n_fields, int es, int force,
-                                                   ArithType arith, unsigned int fields_neg, const WallAddends* addends);
-void launchFieldWallList(const Move3D* moves, int n, void* const* fields, int n_fields, int es, hipStream_t stream, int force,
-                         KernelStats* stats, ArithType arith, unsigned int fields_neg, const WallAddends* addends);
+int fieldsPerWallLaunch(int sides, int layers, int es);  // F of the wall lists' launch rule
+// WHICH launches launchFieldMoveList makes for a wall list, in order (pure host code, no device needed): per run of F fields the one
+// launch planFieldMoveLaunches gives the sides, with the run's addend table
+std::vector<FieldWallLaunch> planFieldWallLaunches(const FieldMoveList& list);
 
-// data-movement launches this process has made so far (launchMoves, launchFieldMoveList and launchFieldWallList; tests count launches per call with it)
+// Launch the list, asynchronous on `stream`: planFieldMoveLaunches' launches, or planFieldWallLaunches' for a wall list.
+void launchFieldMoveList(const FieldMoveList& list, hipStream_t stream, KernelStats* stats = nullptr);
+
+// data-movement launches this process has made so far (launchMoves and launchFieldMoveList; tests count launches per call with it)
 long long dataLaunchCount();
 
 // name (template spelling) of the data-movement kernel launched last by this process, "" before the first launch

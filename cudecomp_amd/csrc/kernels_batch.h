@@ -6,7 +6,7 @@
 // halo phases and transposes), kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) and
 // kernels_field_mirror.hip (the same lists mirrored, with a sign per field: multi-field wall halos) are reached through
 // launchFieldMoveList (kernels.h); kernels_field_wall.hip (the mirrored lists adding an addend per field and layer: multi-field wall
-// values, reached through launchFieldWallList) is compiled into the unit kernels_executor.hip.  Seventeen code objects in all.  The row and element-wise kernels of all of
+// values, reached through the same launcher as a wall list) is compiled into the unit kernels_executor.hip.  Seventeen code objects in all.  The row and element-wise kernels of all of
 // them share one workgroup decode (kernels_walk.h) and their launchers one dispatch (kernels_dispatch.h).
 //
 // Why several translation units: every .hip file becomes ONE code object inside the library's .hip_fatbin, and a single

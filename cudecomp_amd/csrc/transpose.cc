@@ -270,9 +270,18 @@ void runTransposeFields(cudecompHandle_t h, cudecompGridDesc_t gd, TransposeOp o
   if (plan.noop) return;
 
   ensureDevice(h);
-  const int force = (h->tuning.force_class == MOVE_GENERIC ? 1 : 0) | (h->tuning.force_streaming ? 2 : 0) | (h->tuning.no_streaming ? 4 : 0);
+  FieldMoveList list;
+  list.inputs = inputs;
+  list.outputs = outputs;
+  list.n_fields = n_fields;
+  list.work = work;
+  list.es = es;
+  list.tuning = &h->tuning;
   auto launch = [&](const std::vector<Move3D>& moves, const std::vector<i64>& steps) {
-    launchFieldMoveList(moves.data(), steps.data(), (int)moves.size(), inputs, outputs, n_fields, work, es, stream, force);
+    list.moves = moves.data();
+    list.work_steps = steps.data();
+    list.n = (int)moves.size();
+    launchFieldMoveList(list, stream);
   };
   if (!plan.exchange) {
     gd->path_count[PATH_LOCAL]++;

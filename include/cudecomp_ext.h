@@ -488,7 +488,7 @@ cudecompResult_t cudecompExtDescribeMirroredFieldMoves(const cudecompExtMove_t* 
                                                       int32_t n_fields, int32_t es, int32_t force, int32_t mode,
                                                       cudecompDataType_t dtype, uint32_t fields_neg, int64_t out[5]);
 
-/* ... and for WALL field-moves with a sign and addends per field (kernels_field_wall.hip; csrc/kernels.h launchFieldWallList, the
+/* ... and for WALL field-moves with a sign and addends per field (kernels_field_wall.hip; csrc/kernels.h launchFieldMoveList of a wall list, the
  * runner of cudecompAmdSetWallFieldHalos*, cudecomp_halo_wall_value_fields.h): moves[0 .. n - 1], n <= 2, are reflect-moves as
  * above whose `peer` names the side whose addends they take (0 low, 1 high) and whose mirrored dim has at most
  * CUDECOMP_AMD_MAX_WALL_HALO layers; both ends in field f's own buffer.  `dtype` names the element type (its element size is the
