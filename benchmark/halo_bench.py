@@ -22,7 +22,11 @@ reflection's two sibling moves plus one addition per element (4 * face bytes), t
 values, wall values, reflection and, with --wall-value-fields N, cudecompAmdSetWallFieldHalosX (cudecomp_halo_wall_value_fields.h;
 parities -1, +1, -1, ..., centering 0, both sides, addends of its own for every field) on N such pencils next to N single
 cudecompAmdSetWallHalosX calls with the same parities and addends, walls along dims 1 and 2, for fp64 and for fp16, timed in the order
-singles, fields, fields, singles; afterwards every cell of every field against the single calls on clones.
+singles, fields, fields, singles; afterwards every cell of every field against the single calls on clones and, with --wall-planes,
+cudecompAmdSetWallPlaneHalosX (cudecomp_halo_wall_planes.h; parity -1, centering 0, both sides, two device planes whose entries differ
+from cell to cell) next to cudecompAmdSetWallHalosX on the same non-periodic pencil, walls along dims 0, 1 and 2, for fp64 and for
+fp16: the wall values' two sibling moves plus one plane read per element (6 * face bytes against 4), timed in the order values,
+planes, planes, values; dim 0 is the fastest memory axis, where both calls run element by element.
 Per dim: `--reps` repetitions of `--calls` back-to-back calls each, ms per call of every repetition, their
 min / median / max, and GB/s of the median against the algorithmic bytes (update: 2 faces read + written,
 4 * face bytes; accumulation: 2 faces read, 2 destinations read and written, 6 * face bytes; fill: 2 halos written, 2 * face
@@ -86,6 +90,10 @@ def main():
     ap.add_argument("--wall-values", action="store_true",
                     help="also time cudecompAmdSetWallHalosX (parity -1, centering 0, both sides) next to cudecompAmdReflectHalosX with "
                          "parity -1, walls along dims 1 and 2, fp64 and fp16, after the other passes")
+    ap.add_argument("--wall-planes", action="store_true",
+                    help="also time cudecompAmdSetWallPlaneHalosX (parity -1, centering 0, both sides, planes whose entries differ from cell "
+                         "to cell) next to cudecompAmdSetWallHalosX at the same shapes, walls along dims 0, 1 and 2 (non-periodic), fp64 and "
+                         "fp16, in the order values, planes, planes, values; afterwards the low wall's ghost cells against the plane")
     ap.add_argument("--wall-value-fields", type=int, default=0, metavar="N",
                     help="also time cudecompAmdSetWallFieldHalosX on N pencils (centering 0, both sides, a parity and addends per field) next "
                          "to N single cudecompAmdSetWallHalosX calls, walls along dims 1 and 2, fp64 and fp16, in the order singles, fields, "
@@ -203,6 +211,44 @@ def main():
             want = torch.tensor([low[a.halo - 1 - j] - 1.0 for j in range(a.halo)], dtype=tdtype, device="cuda")
             got = cells[a.halo, :a.halo, a.halo]
             extra["wall_values_wrong_cells_" + label] = int(torch.count_nonzero(got != want))
+    if a.wall_planes:
+        periods = (0, 0, 0)
+        for dtype, tdtype, es, label in ((cd.DOUBLE, torch.float64, 8, "fp64"), (cd.HALF, torch.float16, 2, "fp16")):
+            pencil = torch.ones(p.size, dtype=tdtype, device="cuda")
+            low, high = [0.5 * (k + 1) for k in range(a.halo)], [-0.25 * (k + 1) for k in range(a.halo)]
+            for dim in range(3):
+                # the planes of this dim: the pencil's shape with the extent along `dim` replaced by the halo; entries that differ
+                # from cell to cell (multiples of 1/4 below 64: exact in fp16)
+                pshape, elements = cd.wall_plane_shape(p, dim, halo)
+                planes = [((torch.arange(elements, device="cuda") * (3 + side)) % 251).to(tdtype) * 0.25 for side in (0, 1)]
+                values = lambda: cd.cudecompAmdSetWallHalos(0, h, gd, pencil.data_ptr(), dtype, -1, 0, 3, low, high, halo, periods, dim, stream=st)
+                wall = lambda: cd.cudecompAmdSetWallPlaneHalos(0, h, gd, pencil.data_ptr(), dtype, -1, 0, 3, planes[0].data_ptr(),
+                                                               planes[1].data_ptr(), halo, periods, dim, stream=st)
+                rec = res["dim%d" % dim].setdefault("wall_planes", {})
+                runs, kernels = {"wall_values": [], "wall_planes": []}, {}
+                for name, fn in (("wall_values", values), ("wall_planes", wall), ("wall_planes", wall), ("wall_values", values)):
+                    runs[name] += _time(fn, a.reps, a.calls)
+                    kernels[name] = cd.cudecompExtLastKernelName()
+                out = {"wall_values": _record(runs["wall_values"], 4 * faces[dim] * es), "wall_planes": _record(runs["wall_planes"], 6 * faces[dim] * es)}
+                out["wall_values_kernel"], out["wall_planes_kernel"] = kernels["wall_values"], kernels["wall_planes"]
+                out["wall_planes_over_wall_values"] = round(out["wall_planes"]["median_ms"] / out["wall_values"]["median_ms"], 3)
+                out["fastest_memory_axis"] = int(p.order[0]) == dim
+                rec[label] = out
+                # what the call wrote: from an interior of ones, parity -1 leaves -1 + plane entry in every ghost cell of the low wall
+                pencil.fill_(1.0)
+                wall()
+                cells = pencil.view(shape[2], shape[1], shape[0])
+                plane = planes[0].view(pshape[2], pshape[1], pshape[0])
+                at = [slice(a.halo, shape[2] - a.halo), slice(a.halo, shape[1] - a.halo), slice(a.halo, shape[0] - a.halo)]
+                ax = 2 - [int(x) for x in p.order].index(dim)
+                wrong = 0
+                for k in range(a.halo):  # ghost layer k sits at index halo - 1 - k of the pencil, index k of the plane
+                    at[ax] = a.halo - 1 - k
+                    got = cells[tuple(at)]
+                    at[ax] = k
+                    wrong += int(torch.count_nonzero(got != plane[tuple(at)] - 1.0))
+                extra["wall_planes_wrong_cells_%s_dim%d" % (label, dim)] = wrong
+                pencil.fill_(1.0)
     for clear, wanted in ((0, a.fold), (1, a.fold_clear)):
         if not wanted:
             continue
@@ -404,7 +450,9 @@ def main():
                                               if a.wall_fields else "")
                                            + (" and wall values next to the reflection (walls along dims 1 and 2, fp64 and fp16)" if a.wall_values else "")
                                            + (" and the wall values of %d pencils in one call next to %d single calls (walls along dims 1 and 2, fp64 "
-                                              "and fp16)" % (a.wall_value_fields, a.wall_value_fields) if a.wall_value_fields else ""),
+                                              "and fp16)" % (a.wall_value_fields, a.wall_value_fields) if a.wall_value_fields else "")
+                                           + (" and wall planes next to the wall values (non-periodic, walls along dims 0, 1 and 2, fp64 and fp16)"
+                                              if a.wall_planes else ""),
                                            a.reps, a.calls)),
                             "device": torch.cuda.get_device_name(0), "result": res}, **extra))
     print(line)
@@ -434,6 +482,10 @@ def main():
                      "ghost cells are not zero" % (name, extra["interior_cells_with_another_count_after_" + name],
                                                    extra["ghost_cells_not_zero_after_" + name]))
     for label in ("fp64", "fp16"):
+        for dim in range(3):
+            if extra.get("wall_planes_wrong_cells_%s_dim%d" % (label, dim)):
+                sys.exit("halo_bench.py: %d ghost cells of the low wall of dim %d do not hold -1 + plane entry after the wall planes (%s)"
+                         % (extra["wall_planes_wrong_cells_%s_dim%d" % (label, dim)], dim, label))
         if extra.get("wall_values_wrong_cells_" + label):
             sys.exit("halo_bench.py: %d ghost cells of the low wall do not hold -1 + a_k after the wall values (%s)"
                      % (extra["wall_values_wrong_cells_" + label], label))

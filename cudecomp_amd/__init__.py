@@ -97,6 +97,12 @@ class ExtHaloPlan(C.Structure):
                 ("send_off", C.c_int64 * 2), ("recv_off", C.c_int64 * 2), ("pre", ExtMove * 2), ("post", ExtMove * 2)]
 
 
+class ExtPlaneOperand(C.Structure):
+    """cudecompExtPlaneOperand_t: the third operand of a wall-plane move -- the plane it reads (1 low, 2 high), the element offset of
+    the entry destination index (0, 0, 0) adds, three signed element strides"""
+    _fields_ = [("plane", C.c_int32), ("reserved", C.c_int32), ("off", C.c_int64), ("ps", C.c_int64 * 3)]
+
+
 class ExtHaloFieldsPlan(C.Structure):
     _fields_ = [("kind", C.c_int32), ("comm_axis", C.c_int32), ("neighbor", C.c_int32 * 2), ("n_fields", C.c_int32),
                 ("n_pre", C.c_int32), ("n_post", C.c_int32), ("reserved", C.c_int32), ("face_elements", C.c_int64),
@@ -170,7 +176,8 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtPlanHaloAccumulateFields", "cudecompExtRunFieldMovesOp", "cudecompExtDescribeFieldMovesOp",
                "cudecompExtRunMirroredFieldMoves", "cudecompExtDescribeMirroredFieldMoves", "cudecompExtHaloPlanCount",
                "cudecompExtRunWallFieldMoves", "cudecompExtDescribeWallFieldMoves", "cudecompExtPlanHaloWallValueFields",
-               "cudecompExtPlanHaloWallValues", "cudecompExtWall3D", "cudecompExtSyncEpochBegin", "cudecompExtSyncSignal",
+               "cudecompExtPlanHaloWallValues", "cudecompExtWall3D", "cudecompExtPlanHaloWallPlanes", "cudecompExtWallPlane3D",
+               "cudecompExtSyncEpochBegin", "cudecompExtSyncSignal",
                "cudecompExtSyncWait", "cudecompExtTagPages", "cudecompExtCheckPages", "cudecompExtChecksum"]
 MAX_FLAGS, FLAG_SCALE = 64, 16  # csrc/kernels.h: kMaxFlags, kFlagScale
 # include/cudecomp_amd.h: extensions of the API a solver may use
@@ -199,6 +206,8 @@ MAX_HALO_WALL_FIELDS = 32  # CUDECOMP_AMD_MAX_HALO_WALL_FIELDS
 # include/cudecomp_halo_wall_values.h: wall values (the reflection with one addend per ghost layer and side: Dirichlet / Neumann data)
 AMD_WALL_VALUES_SYMBOLS = ["cudecompAmdSetWallHalosX", "cudecompAmdSetWallHalosY", "cudecompAmdSetWallHalosZ"]
 MAX_WALL_HALO = 8  # CUDECOMP_AMD_MAX_WALL_HALO
+# include/cudecomp_halo_wall_planes.h: wall planes (the reflection with an addend per cell of the ghost slab, read from device arrays)
+AMD_WALL_PLANES_SYMBOLS = ["cudecompAmdSetWallPlaneHalosX", "cudecompAmdSetWallPlaneHalosY", "cudecompAmdSetWallPlaneHalosZ"]
 # include/cudecomp_halo_wall_value_fields.h: multi-field wall values (several pencils, a parity and addends per field)
 AMD_WALL_VALUE_FIELDS_SYMBOLS = ["cudecompAmdSetWallFieldHalosX", "cudecompAmdSetWallFieldHalosY", "cudecompAmdSetWallFieldHalosZ"]
 MAX_WALL_VALUE_FIELDS = 32  # CUDECOMP_AMD_MAX_WALL_VALUE_FIELDS
@@ -281,6 +290,13 @@ def lib():
         L.cudecompExtPlanHaloWallValues.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32, i32,
                                                     i32, pf64, pf64, C.POINTER(ExtHaloPlan), C.POINTER(C.c_uint8)]
         L.cudecompExtWall3D.argtypes = [vp, vp, i32, i32, i32, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32, pi32, vp]
+        for name in AMD_WALL_PLANES_SYMBOLS:  # (the wall values' arguments with two device arrays in the place of the host arrays)
+            getattr(L, name).argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
+        L.cudecompExtPlanHaloWallPlanes.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32, i32,
+                                                    i32, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(ExtHaloPlan),
+                                                    C.POINTER(ExtPlaneOperand)]
+        L.cudecompExtWallPlane3D.argtypes = [vp, vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32,
+                                             pi32, vp]
         for name in AMD_FIELDS_SYMBOLS:  # (the update's arguments with the list of fields and its length in the place of `input`)
             getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         L.cudecompExtPlanHaloFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32,
@@ -570,6 +586,28 @@ def cudecompAmdSetWallHalos(axis, handle, gd, inp, dtype, parity, centering, sid
                                 _i3(halo_extents), _b3(halo_periods), dim, _i3(padding), stream), name)
 
 
+def cudecompAmdSetWallPlaneHalos(axis, handle, gd, inp, dtype, parity, centering, sides, planes_low, planes_high, halo_extents,
+                                 halo_periods, dim, padding=None, stream=None):
+    """cudecompAmdSetWallPlaneHalos{X,Y,Z} (cudecomp_halo_wall_planes.h): the ghost cells the reflection along `dim` writes receive
+    parity * mirror + plane entry, the planes DEVICE arrays (addresses) shaped like a slab of the pencil (wall_plane_shape); `sides`
+    bit 0 the low halo, bit 1 the high halo; the plane of a side not named may be None.  Arguments are passed as they are: the
+    library makes the checks."""
+    name = "cudecompAmdSetWallPlaneHalos" + "XYZ"[axis]
+    _check(getattr(lib(), name)(handle, gd, inp, dtype, int(parity), int(centering), int(sides), planes_low or None, planes_high or None,
+                                _i3(halo_extents), _b3(halo_periods), dim, _i3(padding), stream), name)
+
+
+def wall_plane_shape(info, dim, halo_extents):
+    """(shape, elements) of a plane of cudecompAmdSetWallPlaneHalos* for the pencil `info` (a PencilInfo made with the call's
+    halo_extents and padding): the pencil's shape in MEMORY order, fastest first, with the entry of `dim` replaced by
+    halo_extents[dim]; stored densely in that order."""
+    order = [int(x) for x in info.order]
+    shape = [int(x) for x in info.shape]
+    a = order.index(int(dim))
+    shape[a] = int(halo_extents[dim])
+    return tuple(shape), shape[0] * shape[1] * shape[2]
+
+
 def cudecompFoldHalos(axis, handle, gd, inp, dtype, parity, centering, clear, halo_extents, halo_periods, dim, padding=None,
                       stream=None):
     """cudecompAmdFoldHalos{X,Y,Z} (cudecomp_halo_fold.h), the transpose of the reflection: the ghost cells along `dim` that have
@@ -784,6 +822,21 @@ def cudecompExtPlanHaloWallValues(grid, rank, axis, halo_extents, halo_periods, 
     return p, table
 
 
+def cudecompExtPlanHaloWallPlanes(grid, rank, axis, halo_extents, halo_periods, dim, dtype, parity, centering, sides, pencil_address,
+                                  plane_low_address, plane_high_address, padding=None):
+    """Stateless planner of cudecompAmdSetWallPlaneHalos*: (plan, operands) -- the plan's moves are the reflection's for the sides kept,
+    with ExtMove.peer the side; ExtHaloPlan.reserved bit 18 marks the plan, bit 13 the sign flip, bits 16 / 17 the sides; operands[i]
+    (ExtPlaneOperand) is the third operand of plan.pre[i].  The three addresses are only compared (0 / None = NULL).  Arguments are
+    passed as they are: the library makes the checks."""
+    p = ExtHaloPlan()
+    ops = (ExtPlaneOperand * 2)()
+    _check(lib().cudecompExtPlanHaloWallPlanes(C.byref(grid), rank, axis, _i3(halo_extents), _b3(halo_periods), dim, _i3(padding),
+                                               int(dtype), int(parity), int(centering), int(sides), int(pencil_address or 0),
+                                               int(plane_low_address or 0), int(plane_high_address or 0), C.byref(p), ops),
+           "cudecompExtPlanHaloWallPlanes")
+    return p, ops
+
+
 def cudecompExtPlanHaloWallValueFields(grid, rank, axis, halo_extents, halo_periods, dim, centering, sides, n_fields, padding=None):
     """Stateless planner of cudecompAmdSetWallFieldHalos*: the plan whose moves -- the single call's for the sides kept, unsigned, with
     ExtMove.peer the side -- are carried out for every field.  Arguments are passed as they are: the library makes the checks."""
@@ -948,6 +1001,17 @@ def cudecompExtWall3D(src, dst, dtype, negate, side, addends, extent, ss, ds, fo
     return cls.value
 
 
+def cudecompExtWallPlane3D(src, dst, plane, dtype, negate, extent, ss, ds, ps, force=0, stream=None):
+    """One wall-plane move (dst = +-src + plane entry of the destination cell; the negative entry of `ss` names the mirrored dim; `ps`
+    the plane's signed strides, `plane` the device address of the entry destination index (0, 0, 0) adds) through the kernel layer;
+    returns the kernel class (0 rows, 2 generic)."""
+    cls = C.c_int32(-1)
+    a = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
+    _check(lib().cudecompExtWallPlane3D(src, dst, plane, dtype, int(bool(negate)), a(extent), a(ss), a(ds), a(ps), int(force),
+                                        C.byref(cls), stream), "cudecompExtWallPlane3D")
+    return cls.value
+
+
 def cudecompExtRotateWalk(nb, walk=-1):
     """The in-place rotation kernel's orbit walk for nb blocks per edge (no launch, no GPU): (grid, blocks) with blocks an
     int32 array of shape (grid, 3): the block triple of every workgroup, -1 -1 -1 for the ones that map to none."""
@@ -1020,6 +1084,10 @@ MOVES_FOLD, MOVES_FOLD_NEGATE, MOVES_FOLD_TAKE, MOVES_FOLD_NEGATE_TAKE = 7, 8, 9
 # ... wall values (mirror copies that add the addend of the destination's layer; ExtMove.peer names the side, `value` holds the
 # 2 x MAX_WALL_HALO addends as bytes), plain / sign bits flipped first
 MOVES_WALL, MOVES_WALL_NEGATE = 11, 12
+# ... wall planes (mirror copies between cells of buffer 0 that add the entry of a device array at the destination cell; buffer 1 is
+# the low plane, buffer 2 the high plane, ExtMove.peer names the plane, `planes` holds (element offset, three signed strides) per
+# move), plain / sign bits flipped first
+MOVES_WALL_PLANE, MOVES_WALL_PLANE_NEGATE = 13, 14
 
 
 def make_move(extent, ss, ds, src_off=0, dst_off=0, src_buf=0, dst_buf=1, row_pitch=0):
@@ -1031,14 +1099,23 @@ def make_move(extent, ss, ds, src_off=0, dst_off=0, src_buf=0, dst_buf=1, row_pi
     return m
 
 
-def _move_list(moves):
-    arr = (ExtMove * max(1, len(moves)))()
+def _move_list(moves, planes=None):
+    """the C array of a move list; with `planes` (wall-plane modes: (element offset, three strides) per move) the operand entries
+    follow the moves, entry n + i for move i (cudecomp_ext.h)"""
+    n = len(moves)
+    if planes is not None and len(planes) != n:
+        raise ValueError("one plane operand per move")
+    arr = (ExtMove * max(1, n * (2 if planes is not None else 1)))()
     for i, m in enumerate(moves):
         C.memmove(C.byref(arr[i]), C.byref(m), C.sizeof(ExtMove))
+    for i, (off, ps) in enumerate(planes or []):
+        arr[n + i].dst_off = int(off)
+        for d in range(3):
+            arr[n + i].ds[d] = int(ps[d])
     return arr
 
 
-def cudecompExtRunMoves(moves, bufs, es, mode=MOVES_COPY, dtype=0, value=None, flags=0, dst_bases=None, stream=None):
+def cudecompExtRunMoves(moves, bufs, es, mode=MOVES_COPY, dtype=0, value=None, flags=0, dst_bases=None, stream=None, planes=None):
     """A list of moves through the kernel layer's batching (cudecomp_ext.h): bufs = three device pointers (ints or None),
     dst_bases = None or one device pointer per move.  Returns (launches per class, elements per class, launches in all)."""
     v = _value_bytes(value)
@@ -1048,19 +1125,23 @@ def cudecompExtRunMoves(moves, bufs, es, mode=MOVES_COPY, dtype=0, value=None, f
     b = (C.c_void_p * 3)(*[p or None for p in bufs])
     bases = None if dst_bases is None else (C.c_void_p * max(1, len(moves)))(*[p or None for p in dst_bases])
     launches, elements, total = (C.c_int32 * 3)(), (C.c_int64 * 3)(), C.c_int32(-1)
-    _check(lib().cudecompExtRunMoves(_move_list(moves), len(moves), b, es, int(mode), int(dtype), v, int(flags), bases, stream,
+    if (mode in (MOVES_WALL_PLANE, MOVES_WALL_PLANE_NEGATE)) != (planes is not None):
+        raise ValueError("the wall-plane modes, and only they, take `planes`")
+    _check(lib().cudecompExtRunMoves(_move_list(moves, planes), len(moves), b, es, int(mode), int(dtype), v, int(flags), bases, stream,
                                      launches, elements, C.byref(total)), "cudecompExtRunMoves")
     return [int(x) for x in launches], [int(x) for x in elements], total.value
 
 
-def cudecompExtDescribeMoves(moves, buf_addresses, es, mode=MOVES_COPY, dtype=0, flags=0, dst_base_addresses=None):
+def cudecompExtDescribeMoves(moves, buf_addresses, es, mode=MOVES_COPY, dtype=0, flags=0, dst_base_addresses=None, planes=None):
     """The launches cudecompExtRunMoves would make for the list (no launch, no GPU): a list of dicts in launch order, with
     the ExtLaunch fields; `first_block` and `index` cut to the launch's moves."""
     b = (C.c_uint64 * 3)(*[int(p or 0) for p in buf_addresses])
     bases = None if dst_base_addresses is None else (C.c_uint64 * max(1, len(moves)))(*[int(p or 0) for p in dst_base_addresses])
     cap = len(moves) + 1
     out, n = (ExtLaunch * cap)(), C.c_int32(-1)
-    _check(lib().cudecompExtDescribeMoves(_move_list(moves), len(moves), b, es, int(mode), int(dtype), int(flags), bases, out, cap,
+    if (mode in (MOVES_WALL_PLANE, MOVES_WALL_PLANE_NEGATE)) != (planes is not None):
+        raise ValueError("the wall-plane modes, and only they, take `planes`")
+    _check(lib().cudecompExtDescribeMoves(_move_list(moves, planes), len(moves), b, es, int(mode), int(dtype), int(flags), bases, out, cap,
                                           C.byref(n)), "cudecompExtDescribeMoves")
     res = []
     for l in out[:n.value]:

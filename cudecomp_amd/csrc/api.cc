@@ -890,6 +890,12 @@ static cudecompResult_t haloApiEntry(cudecompHandle_t handle, cudecompGridDesc_t
         if (c.op.centering != 0 && c.op.centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
         if (c.clear != 0 && c.clear != 1) CD_INVALID_USAGE("clear argument must be 0 or 1");
       }
+      if (kind == HaloOp::WALL_PLANES) {
+        if (c.parity != 1 && c.parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
+        if (c.op.centering != 0 && c.op.centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
+        const int refusal = wallPlaneRefusal(c.op.sides, c.planes_low, c.planes_high, nullptr, 0, 0);
+        if (refusal != 0) refuseWallPlanes(refusal);
+      }
       if (kind == HaloOp::WALL_VALUES) {
         if (c.parity != 1 && c.parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
         if (c.op.centering != 0 && c.op.centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
@@ -1005,6 +1011,26 @@ CD_DEFINE_HALO_REFLECT(cudecompAmdReflectHalosZ, 2)
 CD_DEFINE_HALO_WALL_VALUES(cudecompAmdSetWallHalosX, 0)
 CD_DEFINE_HALO_WALL_VALUES(cudecompAmdSetWallHalosY, 1)
 CD_DEFINE_HALO_WALL_VALUES(cudecompAmdSetWallHalosZ, 2)
+
+// cudecomp_halo_wall_planes.h: the reflection with an addend per cell of the ghost slab, read from device arrays when the kernel runs
+#define CD_DEFINE_HALO_WALL_PLANES(NAME, AXIS)                                                                              \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,       \
+                        int32_t parity, int32_t centering, int32_t sides, const void* planes_low, const void* planes_high,  \
+                        const int32_t halo_extents[], const bool halo_periods[], int32_t dim, const int32_t padding[],      \
+                        hipStream_t stream) {                                                                               \
+    HaloCall c = haloCall(HaloOp::WALL_PLANES, AXIS, &input, nullptr, dtype, halo_extents, halo_periods, dim, padding,      \
+                          stream);                                                                                          \
+    c.parity = parity;                                                                                                      \
+    c.op.negate = parity == -1;                                                                                             \
+    c.op.centering = centering;                                                                                             \
+    c.op.sides = sides;                                                                                                     \
+    c.planes_low = planes_low;                                                                                              \
+    c.planes_high = planes_high;                                                                                            \
+    return haloApiEntry(handle, grid_desc, c);                                                                              \
+  }
+CD_DEFINE_HALO_WALL_PLANES(cudecompAmdSetWallPlaneHalosX, 0)
+CD_DEFINE_HALO_WALL_PLANES(cudecompAmdSetWallPlaneHalosY, 1)
+CD_DEFINE_HALO_WALL_PLANES(cudecompAmdSetWallPlaneHalosZ, 2)
 
 // cudecomp_halo_fold.h: the ghost cells the reflection writes are added onto their mirror images
 #define CD_DEFINE_HALO_FOLD(NAME, AXIS)                                                                                     \

@@ -127,6 +127,7 @@ void exportHaloPlan(const HaloPlan& p, cudecompExtHaloPlan_t* out) {
     if (op.kind == HaloOp::REFLECT) out->reserved = 4096 | (op.negate ? 8192 : 0);
     if (op.kind == HaloOp::FOLD) out->reserved = 16384 | (op.negate ? 8192 : 0) | (p.ordered ? 2 : 0);
     if (op.kind == HaloOp::WALL_VALUES) out->reserved = 32768 | (op.negate ? 8192 : 0) | (op.sides << 16);
+    if (op.kind == HaloOp::WALL_PLANES) out->reserved = 262144 | (op.negate ? 8192 : 0) | (op.sides << 16);
     if (op.clear) {
       out->reserved |= 512;
       for (size_t i = 0; i < p.pre.size(); ++i)
@@ -241,9 +242,10 @@ std::vector<Move3D> importMoves(const cudecompExtMove_t* moves, int32_t n, int32
                                 ArithType* arith) {
   if (n < 0 || (n > 0 && !moves)) CD_INVALID_USAGE("bad move list");
   if (es != 2 && es != 4 && es != 8 && es != 16) CD_INVALID_USAGE("element size must be 2, 4, 8 or 16");
-  if (mode < 0 || mode > 12)
+  if (mode < 0 || mode > 14)
     CD_INVALID_USAGE("mode must be 0 (copy), 1 (add), 2 (fill), 3 (take), 4 (add and take), 5 (mirror copy), 6 (mirror copy with sign flip), "
-                     "7 ... 10 (fold: plain, with sign flip, with take, with both) or 11 / 12 (wall values: plain, with sign flip)");
+                     "7 ... 10 (fold: plain, with sign flip, with take, with both), 11 / 12 (wall values: plain, with sign flip) or "
+                     "13 / 14 (wall planes: plain, with sign flip)");
   *arith = ARITH_NONE;
   if (mode == 1 || mode == 4 || mode >= 6) {
     if (elementSize(dtype) != es) CD_INVALID_USAGE("element size does not match the data type of the arithmetic");
@@ -265,12 +267,20 @@ std::vector<Move3D> importMoves(const cudecompExtMove_t* moves, int32_t n, int32
       m.ds[d] = e.ds[d];
     }
     m.dst_row_pitch = e.row_pitch;
-    const bool wall = mode == 11 || mode == 12;
-    m.add = mode == 1 || mode == 4 || (mode >= 7 && !wall);
+    const bool wall = mode == 11 || mode == 12, wall_plane = mode == 13 || mode == 14;
+    m.add = mode == 1 || mode == 4 || (mode >= 7 && !wall && !wall_plane);
     m.fill = mode == 2;
     m.take = mode == 3 || mode == 4 || mode == 9 || mode == 10;
     m.reflect = mode >= 5;
-    m.negate = mode == 6 || mode == 8 || mode == 10 || mode == 12;
+    m.negate = mode == 6 || mode == 8 || mode == 10 || mode == 12 || mode == 14;
+    if (wall_plane) {  // the move's `peer` names the plane it reads; entry n + i of the list describes the operand
+      if (e.peer != 0 && e.peer != 1) CD_INVALID_USAGE("a wall-plane move (mode 13 / 14) names its plane in `peer`: 0 low, 1 high");
+      if (e.src_buf != 0 || e.dst_buf != 0) CD_INVALID_USAGE("a wall-plane move (mode 13 / 14) runs between cells of buffer 0: buffers 1 and 2 are the planes");
+      const cudecompExtMove_t& o = moves[n + i];
+      m.plane = e.peer + 1;
+      m.plane_off = o.dst_off;
+      for (int d = 0; d < 3; ++d) m.ps[d] = o.ds[d];
+    }
     if (wall) {  // the move's `peer` names the side whose addends it takes
       if (e.peer != 0 && e.peer != 1) CD_INVALID_USAGE("a wall-value move (mode 11 / 12) names its side in `peer`: 0 low, 1 high");
       m.affine = e.peer + 1;
@@ -278,6 +288,7 @@ std::vector<Move3D> importMoves(const cudecompExtMove_t* moves, int32_t n, int32
     // a mirror copy says which dim it mirrors: without a negative source stride the entry is a plain copy in the wrong mode
     if (m.reflect && e.ss[0] >= 0 && e.ss[1] >= 0 && e.ss[2] >= 0) {
       if (wall) CD_INVALID_USAGE("a wall-value move (mode 11 / 12) names its mirrored dim with a negative source stride");
+      if (wall_plane) CD_INVALID_USAGE("a wall-plane move (mode 13 / 14) names its mirrored dim with a negative source stride");
       if (mode >= 7) CD_INVALID_USAGE("a fold (mode 7 ... 10) names its mirrored dim with a negative source stride");
       CD_INVALID_USAGE("a mirror copy (mode 5 / 6) names its mirrored dim with a negative source stride");
     }
@@ -796,6 +807,78 @@ cudecompResult_t cudecompExtWall3D(const void* src, void* dst, cudecompDataType_
   });
 }
 
+cudecompResult_t cudecompExtWallPlane3D(const void* src, void* dst, const void* plane, cudecompDataType_t dtype, int32_t negate,
+                                        const int64_t extent[3], const int64_t ss[3], const int64_t ds[3], const int64_t ps[3],
+                                        int32_t force, int32_t* kernel_class, hipStream_t stream) {
+  return guarded([&] {
+    if (!src || !dst || !plane || !extent || !ss || !ds || !ps) CD_INVALID_USAGE("null argument");
+    const int es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
+    Move3D m = move3DOf(extent, ss, ds);
+    m.reflect = true;
+    m.negate = negate != 0;
+    m.plane = 1;
+    bool mirrored = false;
+    for (int i = 0; i < 3; ++i) {
+      m.ps[i] = ps[i];
+      mirrored = mirrored || ss[i] < 0;
+    }
+    if (!mirrored) CD_INVALID_USAGE("a wall-plane move names its mirrored dim with a negative source stride");
+    const WallPlanes planes{{plane, nullptr}};
+    void* bufs[3] = {const_cast<void*>(src), dst, nullptr};
+    KernelStats st;
+    const KernelTuning t = tuningOfForce(force);
+    launchMoves(&m, 1, bufs, es, stream, &t, &st, nullptr, arithOf(dtype), nullptr, nullptr, &planes);
+    if (kernel_class) {
+      *kernel_class = -1;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
+        if (st.launches[c]) *kernel_class = c;
+    }
+  });
+}
+
+cudecompResult_t cudecompExtPlanHaloWallPlanes(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
+                                               const bool periods[], int32_t dim, const int32_t pad[], cudecompDataType_t dtype,
+                                               int32_t parity, int32_t centering, int32_t sides, uint64_t pencil_address,
+                                               uint64_t plane_low_address, uint64_t plane_high_address, cudecompExtHaloPlan_t* out,
+                                               cudecompExtPlaneOperand_t operands[2]) {
+  return guarded([&] {
+    const GridShape g = shapeFromSpec(grid);
+    if (!out || !halo || !operands) CD_INVALID_USAGE("null argument");
+    if (axis < 0 || axis > 2 || dim < 0 || dim > 2) CD_INVALID_USAGE("axis/dim out of range");
+    if (rank < 0 || rank >= g.pdims[0] * g.pdims[1]) CD_INVALID_USAGE("rank out of range");
+    const int es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
+    const int32_t zero[3] = {0, 0, 0};
+    const bool none[3] = {false, false, false};
+    const bool* per = periods ? periods : none;
+    const int32_t* pp = pad ? pad : zero;
+    // the call's checks in the call's order: what the fill refuses, parity, centering, sides, NULL planes, overlap, then the plan's
+    buildHaloPlan(g, rank, axis, dim, halo, per, pp, false, false);
+    if (parity != 1 && parity != -1) CD_INVALID_USAGE("parity argument must be +1 or -1");
+    if (centering != 0 && centering != 1) CD_INVALID_USAGE("centering argument must be 0 or 1");
+    const void* low = reinterpret_cast<const void*>(plane_low_address);
+    const void* high = reinterpret_cast<const void*>(plane_high_address);
+    i64 pencil_bytes = 0, plane_bytes = 0;
+    if (halo[dim] > 0 && !per[dim]) {
+      const Pencil pencil = makePencil(g, gridIndexOfRank(g, rank), axis, halo, pp);
+      const i64 along = pencil.extentG(dim);
+      pencil_bytes = pencil.size * es;
+      plane_bytes = along > 0 ? pencil.size / along * halo[dim] * es : 0;
+    }
+    const int refusal = wallPlaneRefusal(sides, low, high, reinterpret_cast<const void*>(pencil_address), pencil_bytes, plane_bytes);
+    if (refusal != 0) refuseWallPlanes(refusal);
+    HaloOp op = haloOp(HaloOp::WALL_PLANES, false, centering, parity == -1);
+    op.sides = sides;
+    const HaloPlan p = buildHaloOpPlan(g, rank, axis, dim, halo, per, pp, op, false, false);
+    exportHaloPlan(p, out);
+    std::memset(operands, 0, 2 * sizeof(operands[0]));
+    for (size_t i = 0; i < p.pre.size() && i < 2; ++i) {
+      operands[i].plane = p.pre[i].plane;
+      operands[i].off = p.pre[i].plane_off;
+      for (int d = 0; d < 3; ++d) operands[i].ps[d] = p.pre[i].ps[d];
+    }
+  });
+}
+
 cudecompResult_t cudecompExtPlanHaloWallValues(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                                const bool periods[], int32_t dim, const int32_t pad[], cudecompDataType_t dtype,
                                                int32_t parity, int32_t centering, int32_t sides, const double values_low[],
@@ -1260,7 +1343,11 @@ cudecompResult_t cudecompExtDescribeMoves(const cudecompExtMove_t* moves, int32_
     std::vector<void*> bases;
     if (dst_base_addresses) bases = pointersOf(dst_base_addresses, n);
     if (dst_base_addresses && bases.empty()) bases.push_back(nullptr);  // (an empty list with bases is still a remote one)
-    const std::vector<Launch> ls = planLaunches(list.data(), n, bufs, es, &t, dst_base_addresses ? bases.data() : nullptr, arith);
+    // wall planes (mode 13 / 14): source and destination are buffer 0's cells, buffers 1 and 2 the low and the high plane
+    const bool wall_plane = mode == 13 || mode == 14;
+    const WallPlanes planes{{bufs[1], bufs[2]}};
+    const std::vector<Launch> ls = planLaunches(list.data(), n, bufs, es, &t, dst_base_addresses ? bases.data() : nullptr, arith,
+                                                wall_plane ? &planes : nullptr);
     *n_launches = (int32_t)ls.size();
     if ((int32_t)ls.size() > max_launches) CD_INVALID_USAGE("more launches than the output array holds");
     for (size_t i = 0; i < ls.size(); ++i) {
@@ -1319,7 +1406,11 @@ cudecompResult_t cudecompExtRunMoves(const cudecompExtMove_t* moves, int32_t n, 
         for (int k = 0; k < CUDECOMP_AMD_MAX_WALL_HALO; ++k)
           std::memcpy(addends.v[side][k], static_cast<const char*>(fill_value) + (size_t)(side * CUDECOMP_AMD_MAX_WALL_HALO + k) * es, es);
     }
-    launchMoves(list.data(), n, bufs, es, stream, &t, &st, dst_bases, arith, mode == 2 ? fill_value : nullptr, wall ? &addends : nullptr);
+    // wall planes (mode 13 / 14): source and destination are buffer 0's cells, buffers 1 and 2 the low and the high plane
+    const bool wall_plane = mode == 13 || mode == 14;
+    const WallPlanes planes{{bufs[1], bufs[2]}};
+    launchMoves(list.data(), n, bufs, es, stream, &t, &st, dst_bases, arith, mode == 2 ? fill_value : nullptr, wall ? &addends : nullptr,
+                wall_plane ? &planes : nullptr);
     int total = 0;
     for (int c = 0; c < MOVE_CLASS_COUNT; ++c) {
       if (launches) launches[c] = st.launches[c];

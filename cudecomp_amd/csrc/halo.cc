@@ -87,7 +87,7 @@ static HaloExchange haloExchangeOf(const HaloPlan& plan, void* const bufs[3], in
   return x;
 }
 
-// The sequence of every halo call.  Local kinds (fill, reflection, folding, wall values) and self-periodic plans end after `pre`; the others pack
+// The sequence of every halo call.  Local kinds (fill, reflection, folding, wall values, wall planes) and self-periodic plans end after `pre`; the others pack
 // (`pre`), exchange op.n_fields faces per direction with the exchange of the updates (haloExchange: same routing, transports and
 // stream ordering for all of them) and unpack or add what arrived (`post`).  Only the update of ONE pencil is sampled by the
 // performance report and overlaps pack, exchange and unpack face by face; a one-field call of the multi-field entry points IS the
@@ -97,7 +97,8 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
   const int es = elementSize(c.dtype);
   const auto backend = gd->config.halo_comm_backend;
   const bool wall = op.kind == HaloOp::WALL_VALUES;
-  const bool mirrored = op.kind == HaloOp::REFLECT || op.kind == HaloOp::FOLD || wall;
+  const bool wall_planes = op.kind == HaloOp::WALL_PLANES;
+  const bool mirrored = op.kind == HaloOp::REFLECT || op.kind == HaloOp::FOLD || wall || wall_planes;
   // The key carries force_packed also where the plan never takes the direct form (accumulation) or only takes its destinations
   // from the update's plan (fill): a descriptor whose backend changes between peer and non-peer transports caches such a plan
   // twice -- harmless.  Two fields or more are always packed: one message per direction.
@@ -116,16 +117,41 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
   const bool bad_parity = c.parity != 1 && c.parity != -1, bad_centering = op.centering != 0 && op.centering != 1,
              bad_clear = c.clear != 0 && c.clear != 1;
   const int bad_wall = wall ? wallValueRefusal(op.sides, c.values_low != nullptr, c.values_high != nullptr, hh[c.dim]) : 0;
-  if (mirrored && (bad_parity || bad_centering || bad_clear || bad_wall != 0)) {
+  const cudecompGridDesc::HaloKey hkey{c.axis, c.dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, force_packed};
+  const std::pair<cudecompGridDesc::HaloKey, HaloOp> key{hkey, op};
+  // wall planes: sides, NULL, then the overlap of a named plane with the pencil -- addresses only; a periodic dim or h == 0 has no
+  // plane to overlap with.  The sizes depend on the key alone: a call that finds its plan cached reads them there.  Only a call
+  // without a cached plan (the first, or one whose plan the builder refuses every time) works them out here -- from the pencil,
+  // which only valid halos and padding give: what the fill refuses comes first -- because the overlap is reported before the
+  // plan's own last refusal.
+  int bad_planes = 0;
+  if (wall_planes && !bad_parity && !bad_centering) {
+    bad_planes = wallPlaneRefusal(op.sides, c.planes_low, c.planes_high, nullptr, 0, 0);
+    if (bad_planes == 0 && hh[c.dim] > 0 && !per[c.dim]) {
+      i64 pencil_elements = 0, plane_elements = 0;
+      const auto cached = gd->halo_plans.find(key);
+      if (cached != gd->halo_plans.end()) {
+        pencil_elements = cached->second.pencil_elements;
+        plane_elements = cached->second.plane_elements;
+      } else {
+        buildHaloPlan(gd->shape, h->rank, c.axis, c.dim, hh.data(), per.data(), pp.data(), false, h->self_exchange);  // (the fill's refusals)
+        const Pencil pencil = makePencil(gd->shape, gridIndexOfRank(gd->shape, h->rank), c.axis, hh.data(), pp.data());
+        const i64 along = pencil.extentG(c.dim);
+        pencil_elements = pencil.size;
+        plane_elements = along > 0 ? pencil.size / along * hh[c.dim] : 0;
+      }
+      bad_planes = wallPlaneRefusal(op.sides, c.planes_low, c.planes_high, c.fields[0], pencil_elements * es, plane_elements * es);
+    }
+  }
+  if (mirrored && (bad_parity || bad_centering || bad_clear || bad_wall != 0 || bad_planes != 0)) {
     buildHaloPlan(gd->shape, h->rank, c.axis, c.dim, hh.data(), per.data(), pp.data(), false, h->self_exchange);  // (the fill's refusals)
     if (bad_parity) CD_INVALID_USAGE("parity argument must be +1 or -1");
     if (bad_centering) CD_INVALID_USAGE("centering argument must be 0 or 1");
     if (bad_clear) CD_INVALID_USAGE("clear argument must be 0 or 1");
+    if (bad_planes != 0) refuseWallPlanes(bad_planes);
     refuseWallValues(bad_wall);
   }
 
-  const cudecompGridDesc::HaloKey hkey{c.axis, c.dim, {hh[0], hh[1], hh[2], pp[0], pp[1], pp[2]}, per, force_packed};
-  const std::pair<cudecompGridDesc::HaloKey, HaloOp> key{hkey, op};
   auto it = gd->halo_plans.find(key);
   if (it == gd->halo_plans.end()) {
     HaloPlan p = buildHaloOpPlan(gd->shape, h->rank, c.axis, c.dim, hh.data(), per.data(), pp.data(), op, force_packed, h->self_exchange);
@@ -138,7 +164,7 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
   void* bufs[3] = {c.fields[0], c.fields[0], c.work};
   // the arithmetic of the moves that add (accumulation, folding) or flip sign bits (reflection with parity -1; the reflection of
   // several fields always names its real type: its signs are a mask of fields, one kernel whatever they are)
-  const bool computes = op.kind == HaloOp::ACCUMULATE || op.kind == HaloOp::FOLD || wall ||
+  const bool computes = op.kind == HaloOp::ACCUMULATE || op.kind == HaloOp::FOLD || wall || wall_planes ||
                         (op.kind == HaloOp::REFLECT && (op.negate || op.n_fields >= 2));
   const ArithType arith = computes ? arithOf(c.dtype) : ARITH_NONE;
   // wall values: the addends are converted here, once per call, and travel to the launch by value -- read before the call returns
@@ -165,12 +191,16 @@ void runHaloOp(cudecompHandle_t h, cudecompGridDesc_t gd, const HaloCall& c) {
   list.fields_neg = c.fields_neg;
   list.addends = wall ? addends.data() : nullptr;
   list.tuning = &h->tuning;
+  // wall planes: the two device pointers travel to the launch with the call, the route of the addends; their contents are read by
+  // the kernel, so a captured call applies what the planes hold at replay
+  const WallPlanes planes{{c.planes_low, c.planes_high}};
   auto launch = [&](const std::vector<Move3D>& moves) {
     if (moves.empty()) return;
     const int n = (int)moves.size(), each = plan.ordered && moves[0].add ? 1 : n;
     if (op.n_fields == 1) {
       for (int i = 0; i < n; i += each)
-        launchMoves(moves.data() + i, each, bufs, es, c.stream, &h->tuning, nullptr, nullptr, arith, c.value, list.addends);
+        launchMoves(moves.data() + i, each, bufs, es, c.stream, &h->tuning, nullptr, nullptr, arith, c.value, list.addends,
+                    wall_planes ? &planes : nullptr);
       return;
     }
     const std::vector<i64> steps(n, plan.face_elements);

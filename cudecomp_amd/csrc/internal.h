@@ -16,6 +16,7 @@
 #include "cudecomp_amd_fill.h"
 #include "cudecomp_amd_reflect.h"
 #include "cudecomp_halo_wall_values.h"
+#include "cudecomp_halo_wall_planes.h"
 #include "cudecomp_halo_fold.h"
 #include "cudecomp_halo_fields.h"
 #include "cudecomp_halo_accumulate_fields.h"
@@ -281,6 +282,10 @@ struct HaloCall {
   // several fields: field-major, halo[dim] layers per field, and the parities travel as for REFLECT (`parity`, `fields_neg`)
   const double* values_low = nullptr;
   const double* values_high = nullptr;
+  // WALL_PLANES: the caller's DEVICE arrays (cudecomp_halo_wall_planes.h); only the addresses are looked at on the host.  The runner
+  // checks op.sides, NULL and the overlap with the pencil after the centering
+  const void* planes_low = nullptr;
+  const void* planes_high = nullptr;
   const int32_t* halo = nullptr;
   const bool* periods = nullptr;
   const int32_t* pad = nullptr;

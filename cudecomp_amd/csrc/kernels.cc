@@ -2,12 +2,12 @@
 //
 // A move is normalised (unit dims dropped, contiguous dims fused, dims sorted by source stride) and classified: classify()
 // writes WHAT runs into one KernelChoice (kernels_batch.h: the kind of kernel -- row copy plain / shifted / dense, LDS-tiled
-// transposition plain / window / lines / row lines, element-wise, the two additions, the two fills, the four takes, the two reflections, the four folds, the two wall-moves -- element size, lane width,
+// transposition plain / window / lines / row lines, element-wise, the two additions, the two fills, the four takes, the two reflections, the four folds, the two wall-moves, the two wall-plane moves -- element size, lane width,
 // tile, access mode) and HOW it walks into the Batch fields beside it.  Moves with equal choices are batched (up to kMaxBatch moves, e.g.
 // the per-peer pack copies of one transpose, share one launch; the descriptors travel in the kernel argument segment).  The
 // batching key, the launcher's instantiation and the kernel's name all come from that one record.  The kernels live in
 // kernels_rows.hip, kernels_transpose.hip (one code object per element size), kernels_window.hip, kernels_lines.hip,
-// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip and kernels_wall.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
+// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip, kernels_wall.hip and kernels_wall_plane.hip; kernels_rotate.hip (the in-place rotation) is launched by the executor,
 // transpose.cc; kernels_field_transpose.hip (lists of field-moves: the moves of a halo or transpose phase for several pencils in
 // one launch), kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) and
 // kernels_field_mirror.hip (the same lists mirrored, with a sign per field: multi-field wall halos) have an entry of their own at
@@ -47,6 +47,7 @@ struct Classified {
   unsigned int t0, t1;
   unsigned long long blocks;
   i64 elements;
+  PlaneOperand po;  // wall-plane moves: the third operand in the kernel's units (zero otherwise)
 };
 
 constexpr long long kDenseMaxGapBytes = 512;  // widest gap between rows the dense row copy rewrites (halo + padding cells)
@@ -486,15 +487,117 @@ Classified classifyReflect(const Move3D& in, void* const bufs[3], int es, const 
   return c;
 }
 
+// Wall-plane moves (Move3D::plane: reflect-moves whose addend is the entry of a device array at the destination cell) have THREE
+// operands, and every rule of the reflection's classification takes all three into account:
+//  - the mirrored dim is set aside, the other two are ordered by source stride and merge into longer rows only if they are
+//    contiguous in source, destination AND plane; the mirrored dim comes back as the row or plane index (mirrorGeometry's slots);
+//  - rows when the fastest dim is contiguous on all three operands and is not the mirrored one, element by element otherwise;
+//  - the lane width is the widest of 16, 8, 4 and 2 bytes that is not below the element and divides the row length, all three byte
+//    bases and all three operands' row and plane strides -- which holds the 2-byte rule (4 bytes and more only at dword-aligned
+//    addresses, halfMisaligned) for the plane as well.
+// Access: the reflection's rule, and the plane, read once per call, streams with the payload (unmeasured).
+Classified classifyWallPlane(const Move3D& in, void* const bufs[3], int es, const KernelTuning& tuning, bool remote, ArithType arith,
+                             const WallPlanes* planes) {
+  if (in.fill || in.take || in.add || in.affine != 0 || in.dst_row_pitch != 0 || remote)
+    CD_INTERNAL_ERROR("wall-plane moves only reflect the cells of a local buffer and add their plane's entries");
+  if (in.plane != 1 && in.plane != 2) CD_INTERNAL_ERROR("wall-plane move without a side");
+  if (!planes || !planes->base[in.plane - 1]) CD_INTERNAL_ERROR("wall-plane moves without the call's planes");
+  if (arith == ARITH_NONE) CD_INTERNAL_ERROR("wall-plane move without an arithmetic type");
+  if (es % arithBytes(arith) != 0 || es / arithBytes(arith) > 2) CD_INTERNAL_ERROR("element size does not fit the arithmetic type");
+  int mirrored = -1;
+  for (int i = 0; i < 3; ++i) {
+    if (in.ds[i] < 0) CD_INTERNAL_ERROR("negative destination stride");
+    if (in.ss[i] >= 0) {
+      if (in.ps[i] < 0) CD_INTERNAL_ERROR("a plane runs backwards only along the mirrored dim");
+      continue;
+    }
+    if (mirrored >= 0) CD_INTERNAL_ERROR("reflect-move with more than one mirrored dim");
+    mirrored = i;
+  }
+  if (mirrored < 0) CD_INTERNAL_ERROR("wall-plane move without a mirrored dim");
+  // the two dims that are not mirrored, by source stride; fused when contiguous on all three operands
+  struct D {
+    i64 e, s, d, p;
+  };
+  D dims[3];
+  int n = 0;
+  for (int i = 0; i < 3; ++i)
+    if (i != mirrored && in.extent[i] != 1) dims[n++] = {in.extent[i], in.ss[i], in.ds[i], in.ps[i]};
+  if (n == 2 && (dims[1].s != dims[0].s ? dims[1].s < dims[0].s : dims[1].d < dims[0].d)) std::swap(dims[0], dims[1]);
+  if (n == 2) {
+    for (int i = 0; i < 2; ++i) {
+      const D &a = dims[i], &b = dims[1 - i];
+      if (b.s == a.s * a.e && b.d == a.d * a.e && b.p == a.p * a.e) {
+        dims[0] = {a.e * b.e, a.s, a.d, a.p};
+        n = 1;
+        break;
+      }
+    }
+  }
+  const bool live = in.extent[mirrored] > 1;  // (a mirrored dim one cell thick has no direction)
+  if (live) {  // back in, slower than the row: slot 1 or 2, ordered by the size of the source stride
+    const int at = (n == 2 && dims[1].s < -in.ss[mirrored]) ? 2 : 1;
+    for (int i = n; i < at; ++i) dims[i] = {1, 0, 0, 0};
+    if (at == 1) dims[2] = n == 2 ? dims[1] : D{1, 0, 0, 0};
+    dims[at] = {in.extent[mirrored], in.ss[mirrored], in.ds[mirrored], in.ps[mirrored]};
+    n = 3;
+  }
+  for (int i = n; i < 3; ++i) dims[i] = {1, 0, 0, 0};
+  const i64 plane_fastest = in.ps[mirrored] < 0 ? -in.ps[mirrored] : in.ps[mirrored];
+  const bool mirrored_fastest = live && (in.ss[mirrored] == -1 || in.ds[mirrored] <= 1 || plane_fastest <= 1);
+  const bool rows_fit = dims[0].e == 1 || (dims[0].s == 1 && dims[0].d == 1 && dims[0].p == 1);
+
+  Classified c{};
+  c.k.es = es;
+  c.k.arith = arith;
+  c.k.neg = in.negate;
+  c.elements = in.elements();
+  const bool streaming = (c.elements * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming;
+  c.dm.src = static_cast<const char*>(bufs[in.src_buf]) + in.src_off * es;
+  c.dm.dst = static_cast<char*>(bufs[in.dst_buf]) + in.dst_off * es;
+  c.po.p = static_cast<const char*>(planes->base[in.plane - 1]) + in.plane_off * es;
+  if (tuning.force_class != MOVE_GENERIC && rows_fit && !mirrored_fastest) {
+    c.k.kind = K_ROWS_WALL_PLANE;
+    c.k.access = streaming ? 1 : 0;
+    uintptr_t bits = reinterpret_cast<uintptr_t>(c.dm.src) | reinterpret_cast<uintptr_t>(c.dm.dst) | reinterpret_cast<uintptr_t>(c.po.p);
+    for (int i = 1; i < 3; ++i) {
+      c.dm.ss[i] = dims[i].s * es;
+      c.dm.ds[i] = dims[i].d * es;
+      c.po.s[i] = dims[i].p * es;
+      bits |= (uintptr_t)(dims[i].s < 0 ? -c.dm.ss[i] : c.dm.ss[i]) | (uintptr_t)c.dm.ds[i] | (uintptr_t)(dims[i].p < 0 ? -c.po.s[i] : c.po.s[i]);
+    }
+    int vb = 16;
+    while (vb > es && ((dims[0].e * es) % vb != 0 || (bits & (uintptr_t)(vb - 1)) != 0)) vb >>= 1;
+    c.k.vec = vb;
+    c.dm.e[0] = dims[0].e * es / vb;
+    c.dm.e[1] = dims[1].e;
+    c.dm.e[2] = dims[2].e;
+    rowTiles(c);
+    return c;
+  }
+  c.k.kind = K_GENERIC_WALL_PLANE;
+  c.k.access = 0;
+  Move3D m = in;
+  for (int i = 0; i < 3; ++i) {
+    m.extent[i] = dims[i].e;
+    m.ss[i] = dims[i].s;
+    m.ds[i] = dims[i].d;
+    c.po.s[i] = dims[i].p;
+  }
+  genericGeometry(c, m, true);  // no destination-fast dim: along the longest
+  return c;
+}
+
 // Copy moves take any kind of kernel.  Add-moves (Move3D::add, `arith` their real type) take the row geometry of the copy
 // (same extent / address / stride rule) or the element-wise one and nothing else: never shifted, dense or transposing forms
 // (only the cells of the move are touched), never a remote destination, never lanes narrower than one real.  Take-moves
 // (Move3D::take, with or without `add`: the copy or the addition, then zero bytes into the source cells) are offered the same two
 // geometries and nothing else, for the same reason -- and because the zero must go where the lane's load went, at its width.
 Classified classify(const Move3D& in, void* const bufs[3], int es, const KernelTuning& tuning, void* dst_base, bool remote,
-                    ArithType arith) {
+                    ArithType arith, const WallPlanes* planes = nullptr) {
   if (in.negate && !in.reflect) CD_INTERNAL_ERROR("only reflect- and fold-moves flip sign bits");
-  if (in.affine != 0 && !in.reflect) CD_INTERNAL_ERROR("only reflect-moves add a wall's values");
+  if ((in.affine != 0 || in.plane != 0) && !in.reflect) CD_INTERNAL_ERROR("only reflect-moves add a wall's values");
+  if (in.plane != 0) return classifyWallPlane(in, bufs, es, tuning, remote || dst_base != nullptr, arith, planes);
   if (in.reflect && in.take && !in.add) CD_INTERNAL_ERROR("a reflect-move that clears its source must be a fold-move (add)");
   if (in.reflect) return classifyReflect(in, bufs, es, tuning, remote || dst_base != nullptr, arith);
   Move3D m = in;
@@ -608,6 +711,12 @@ void spellKernelName(const KernelChoice& k) {
       snprintf(out, n, "rows_wall_kernel<%s,%d,%d,%s>", arithName(k.arith), k.vec, s, k.neg ? "true" : "false");
       break;
     case K_GENERIC_WALL: snprintf(out, n, "generic_wall_kernel<%s,%d,%s>", arithName(k.arith), k.es, k.neg ? "true" : "false"); break;
+    case K_ROWS_WALL_PLANE:
+      snprintf(out, n, "rows_wall_plane_kernel<%s,%d,%d,%s>", arithName(k.arith), k.vec, s, k.neg ? "true" : "false");
+      break;
+    case K_GENERIC_WALL_PLANE:
+      snprintf(out, n, "generic_wall_plane_kernel<%s,%d,%s>", arithName(k.arith), k.es, k.neg ? "true" : "false");
+      break;
     case K_ROWS_FIELDS: snprintf(out, n, "rows_fields_kernel<%d,%d>", k.vec, s); break;
     case K_GENERIC_FIELDS: snprintf(out, n, "generic_fields_kernel<%d>", k.es); break;
     case K_TRANSPOSE_FIELDS:
@@ -712,6 +821,8 @@ void launchBatch(const Launch& l, const Move3D* moves, const void* fill_value, c
     case K_GENERIC_FOLD_TAKE: launchFoldBatch(k, b, blocks, stream); break;
     case K_ROWS_WALL:
     case K_GENERIC_WALL: launchWallBatch(k, b, wallTableOf(l, moves, addends), blocks, stream); break;
+    case K_ROWS_WALL_PLANE:
+    case K_GENERIC_WALL_PLANE: launchWallPlaneBatch(k, b, l.planes, blocks, stream); break;
     case K_ROWS_FIELDS:
     case K_GENERIC_FIELDS:
     case K_TRANSPOSE_FIELDS:
@@ -789,7 +900,7 @@ void describeMove(const Move3D& m, const void* src, void* dst, int es, const Ker
 }
 
 std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3], int es, const KernelTuning* tuning,
-                                 void* const* dst_base_override, ArithType arith) {
+                                 void* const* dst_base_override, ArithType arith, const WallPlanes* wall_planes) {
   const bool remote = dst_base_override != nullptr;
   const KernelTuning& t = tuning ? *tuning : kDefaultTuning;
   if (es != 2 && es != 4 && es != 8 && es != 16) CD_INTERNAL_ERROR("unsupported element size");
@@ -799,7 +910,7 @@ std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3]
   index.reserve(n);
   for (int i = 0; i < n; ++i) {
     if (moves[i].elements() == 0) continue;
-    cs.push_back(classify(moves[i], bufs, es, t, dst_base_override ? dst_base_override[i] : nullptr, remote, arith));
+    cs.push_back(classify(moves[i], bufs, es, t, dst_base_override ? dst_base_override[i] : nullptr, remote, arith, wall_planes));
     index.push_back(i);
   }
   // moves of one phase are independent, so they may be regrouped by kernel flavour
@@ -824,6 +935,7 @@ std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3]
       b.p1[b.n] = cs[j].p1;
       b.t0[b.n] = cs[j].t0;
       b.t1[b.n] = cs[j].t1;
+      l.planes.m[b.n] = cs[j].po;
       blocks += cs[j].blocks;
       l.elements += cs[j].elements;
       l.index[b.n] = index[j];
@@ -851,8 +963,8 @@ std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3]
 
 void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
                  const KernelTuning* tuning, KernelStats* stats, void* const* dst_base_override, ArithType arith,
-                 const void* fill_value, const WallAddends* wall_addends) {
-  for (const Launch& l : planLaunches(moves, n, bufs, es, tuning, dst_base_override, arith)) {
+                 const void* fill_value, const WallAddends* wall_addends, const WallPlanes* wall_planes) {
+  for (const Launch& l : planLaunches(moves, n, bufs, es, tuning, dst_base_override, arith, wall_planes)) {
     launchBatch(l, moves, fill_value, wall_addends, stream);
     if (stats) {
       stats->launches[l.cls] += 1;
@@ -921,11 +1033,11 @@ FieldListOp checkFieldMoveList(const FieldMoveList& r) {
 // the rules of one move (empty ones included)
 void checkFieldMove(const FieldMoveList& r, const FieldListOp& op, const Move3D& in) {
   if (r.mirrored) {  // (reflect- or fold-moves between cells of the fields' own buffers; their signs travel in fields_neg)
-    if (!in.reflect || in.negate || in.fill || in.dst_row_pitch != 0 || in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK)
+    if (!in.reflect || in.negate || in.fill || in.plane != 0 || in.dst_row_pitch != 0 || in.src_buf == BUF_WORK || in.dst_buf == BUF_WORK)
       CD_INTERNAL_ERROR("mirrored field-moves reflect or fold exactly their cells of the fields' buffers, unsigned");
     if (op.wall && ((in.affine != 1 && in.affine != 2) || wallLayers(in) < 0))
       CD_INTERNAL_ERROR("wall field-move without a side or a mirrored dim, or with more layers than the addend table holds");
-  } else if (in.fill || in.reflect || in.negate || in.affine != 0 || in.dst_row_pitch != 0) {
+  } else if (in.fill || in.reflect || in.negate || in.affine != 0 || in.plane != 0 || in.dst_row_pitch != 0) {
     CD_INTERNAL_ERROR("field-moves copy, add or take exactly their cells");
   }
   if (op.add && in.dst_buf == BUF_WORK) CD_INTERNAL_ERROR("adding field-moves never add onto the workspace");

@@ -47,10 +47,15 @@ struct KernelTuning {
 // after the optional sign flip, in `arith`, which they always need.  `wall_addends` holds the converted addends of the call per
 // side and ghost layer (kernels_batch.h WallAddends), read before the call returns; a move names its side.  At most
 // kern::kMaxWallHalo layers; anything else on such a move is an internal error before any launch.
+// Wall-plane moves (Move3D::plane on a reflect-move; kernels_wall_plane.hip) add, after the optional sign flip and in `arith`, which
+// they always need, the entry of a device array that Move3D::plane_off and Move3D::ps name for the destination cell.  `wall_planes`
+// holds the bases of the call's low and high plane (kernels_batch.h WallPlanes); only the POINTERS are read here, the contents when
+// the kernel runs.  Any number of layers; anything else on such a move is an internal error before any launch.
 void launchMoves(const Move3D* moves, int n, void* const bufs[3], int es, hipStream_t stream,
                  const KernelTuning* tuning = nullptr, KernelStats* stats = nullptr,
                  void* const* dst_base_override = nullptr,  // per-move destination base (remote buffers)
-                 ArithType arith = ARITH_NONE, const void* fill_value = nullptr, const WallAddends* wall_addends = nullptr);
+                 ArithType arith = ARITH_NONE, const void* fill_value = nullptr, const WallAddends* wall_addends = nullptr,
+                 const WallPlanes* wall_planes = nullptr);
 
 // One row of the addend table a launch of wall-moves carries (kern::WallTable): `layers` entries of 16 bytes in DESTINATION order
 // along the mirrored dim -- the high side's (side 1) ghost layer k at index k, the low side's (side 0) at layers - 1 - k -- each the
@@ -62,6 +67,7 @@ void wallTableRow(const WallAddends& addends, int side, int layers, int es, unsi
 struct Launch {
   KernelChoice k;
   kern::Batch b;
+  kern::PlaneOperands planes;    // wall-plane moves: planes.m[i] is the third operand of b.m[i] (zero otherwise)
   unsigned int blocks;
   MoveClass cls;
   i64 elements;                  // of all its moves
@@ -72,7 +78,8 @@ struct Launch {
 // moves and before the move whose workgroups would take the sum past 2^31 - 1, interleaved when there are several moves that
 // are no local transposes.  Throws what launchMoves throws, before anything is launched.
 std::vector<Launch> planLaunches(const Move3D* moves, int n, void* const bufs[3], int es, const KernelTuning* tuning = nullptr,
-                                 void* const* dst_base_override = nullptr, ArithType arith = ARITH_NONE);
+                                 void* const* dst_base_override = nullptr, ArithType arith = ARITH_NONE,
+                                 const WallPlanes* wall_planes = nullptr);
 
 // How a move WOULD run (no launch, no device needed): class, kernel variant, tile, tile counts, walk parameters, access mode.
 // out[10] = {class, variant, tile_i (row copies: 0 plain / 1 shifted / 2 dense kernel), tile_j, tiles_i, tiles_j, batch, p0 (run length), p1 (walk bits: 1 XCD-contiguous, 2 j first,

@@ -1,8 +1,9 @@
 // kernels_batch.h -- what csrc/kernels.cc (host: classification, batching) and the kernel code objects share: the record of a
 // kernel choice (KernelChoice), the launch descriptor (Batch) and the launchers.  The code objects the classifier dispatches
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
-// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip, kernels_wall.hip;
-// kernels_rotate.hip and sync.hip are launched by the executor (and compiled as one unit, kernels_executor.hip; kernels_fill.hip and kernels_reflect.hip likewise as kernels_edge.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
+// kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip, kernels_wall.hip, kernels_wall_plane.hip;
+// kernels_rotate.hip and sync.hip are launched by the executor (and compiled as one unit, kernels_executor.hip; kernels_fill.hip and kernels_reflect.hip likewise as kernels_edge.hip,
+// kernels_accumulate.hip and kernels_take.hip as kernels_sum.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
 // halo phases and transposes), kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) and
 // kernels_field_mirror.hip (the same lists mirrored, with a sign per field: multi-field wall halos) are reached through
 // launchFieldMoveList (kernels.h); kernels_field_wall.hip (the mirrored lists adding an addend per field and layer: multi-field wall
@@ -14,7 +15,8 @@
 // 14 ms (bisected in round 5, profiles/r05_code_size.md: the same 0.74 MB of device code split over two code objects is
 // harmless, in one code object it is not).  The kernels therefore live in several small code objects -- row copies + generic,
 // the LDS-tiled transposes per element size (kernels_transpose.hip compiled four times), the window transposes, ... -- and
-// tests/test_abi.py guards the size of each.
+// tests/test_abi.py guards the size of each.  That guard (400,000 bytes per code object) is also why the wall-plane kernels are not
+// appended to kernels_wall.hip: 317 KB and 320 KB in one unit would exceed it; kernels_wall_plane.hip is a code object of its own.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -83,6 +85,21 @@ struct WallTable {
   unsigned int w[kMaxBatch][kMaxWallHalo][4];
 };
 static_assert(sizeof(Batch) + sizeof(WallTable) + 16 <= 2048, "Batch, sign mask and addend table stay well under the 4 KB of kernel arguments");
+
+// The third operand of a launch of wall-plane moves (kernels_wall_plane.hip; Move3D::plane): a kernel argument of its own beside the
+// Batch, which stays as it is.  Entry i belongs to move i of the Batch: the address of the plane entry that destination index
+// (0, 0, 0) adds, and three SIGNED strides in the units of that move's DevMove (rows: s[0] unused, s[1] and s[2] in bytes;
+// element-wise: elements) -- negative along the mirrored dim of a low side, and only there.  Not a table of values: the values stay
+// in device memory and are read when the kernel runs, so a replayed graph applies what the planes hold then.  8 x 32 bytes.
+struct PlaneOperand {
+  const char* p;
+  long long s[3];
+};
+struct PlaneOperands {
+  PlaneOperand m[kMaxBatch];
+};
+static_assert(sizeof(PlaneOperands) == kMaxBatch * 32, "one pointer and three strides per move of the launch");
+static_assert(sizeof(Batch) + sizeof(PlaneOperands) + 16 <= 2048, "Batch, sign mask and plane operands stay well under the 4 KB of kernel arguments");
 
 // ---- lists of field-moves: up to kMaxBatch moves, each for up to kMaxFields (input, output) pairs of buffers, in ONE launch
 // (kernels_field_transpose.hip; multi-field halo updates and transposes, include/cudecomp_halo_fields.h and
@@ -182,7 +199,9 @@ enum KernelKind {
   K_ROWS_WALL,                // rows_wall_kernel (dst = +-src + addend of the destination layer, the source backwards along the row or plane index) = 37
   K_GENERIC_WALL,             // generic_wall_kernel = 38
   K_ROWS_FIELDS_WALL,         // rows_fields_wall_kernel (dst = +-src per field + the field's addend of the destination layer) = 39
-  K_GENERIC_FIELDS_WALL       // generic_fields_wall_kernel = 40
+  K_GENERIC_FIELDS_WALL,      // generic_fields_wall_kernel = 40
+  K_ROWS_WALL_PLANE,          // rows_wall_plane_kernel (dst = +-src + the plane entry of the destination cell, the source backwards along the row or plane index) = 41
+  K_GENERIC_WALL_PLANE        // generic_wall_plane_kernel = 42
 };
 struct KernelChoice {
   KernelKind kind;
@@ -275,12 +294,14 @@ constexpr KindTraits kKindTraits[] = {
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_WALL
     {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_FIELDS_WALL
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_WALL
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_WALL_PLANE
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_WALL_PLANE
 };
-static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_FIELDS_WALL + 1, "one row per KernelKind");
+static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_WALL_PLANE + 1, "one row per KernelKind");
 
 // the row of a kind; a value outside the enum is an internal error, never a read past the table
 inline const KindTraits& kindTraits(KernelKind kind) {
-  if (kind < K_ROWS || kind > K_GENERIC_FIELDS_WALL) CD_INTERNAL_ERROR("kernel kind out of range");
+  if (kind < K_ROWS || kind > K_GENERIC_WALL_PLANE) CD_INTERNAL_ERROR("kernel kind out of range");
   return kKindTraits[kind];
 }
 inline MoveClass classOf(KernelKind kind) { return kindTraits(kind).cls; }
@@ -356,6 +377,16 @@ struct WallAddends {
   unsigned char v[2][kern::kMaxWallHalo][16];
 };
 void launchWallBatch(const KernelChoice& k, const kern::Batch& b, const kern::WallTable& table, unsigned int blocks, hipStream_t stream);
+// kernels_wall_plane.hip: wall-plane moves (Move3D::plane: dst = src + plane or dst = -src + plane with the source running backwards
+// along one dim, the plane entry that of the destination cell).  The Batch of the reflections (rows with SIGNED byte strides,
+// generic with signed strides in elements); `planes`: the third operand of every move in the same units.  k.arith: the real type of
+// the addition, always; k.neg: the sign bits of the source are flipped first.  Lanes never narrower than one element.  Local buffers
+// only.  WallPlanes is what a caller of launchMoves hands over: the base of the low and of the high plane (device memory).
+struct WallPlanes {
+  const void* base[2];
+};
+void launchWallPlaneBatch(const KernelChoice& k, const kern::Batch& b, const kern::PlaneOperands& planes, unsigned int blocks,
+                          hipStream_t stream);
 // kernels_field_transpose.hip: lists of field-moves (plain copies of exactly the cells of the moves; local buffers only)
 void launchFieldMoveBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, unsigned int blocks, hipStream_t stream);
 // kernels_field_accumulate.hip: lists of field-moves that add (k.arith: the real type), take or both; local buffers only

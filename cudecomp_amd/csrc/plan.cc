@@ -608,6 +608,60 @@ HaloPlan buildHaloWallValuesPlan(const GridShape& g, int rank, int axis, int dim
   return p;
 }
 
+int wallPlaneRefusal(int sides, const void* plane_low, const void* plane_high, const void* pencil, i64 pencil_bytes, i64 plane_bytes) {
+  if (sides < 1 || sides > 3) return 1;
+  if (((sides & 1) && !plane_low) || ((sides & 2) && !plane_high)) return 2;
+  const uintptr_t p0 = reinterpret_cast<uintptr_t>(pencil), p1 = p0 + (uintptr_t)pencil_bytes;
+  for (int side = 0; side < 2 && plane_bytes > 0 && pencil_bytes > 0; ++side) {
+    if (!(sides & (1 << side))) continue;
+    const uintptr_t q0 = reinterpret_cast<uintptr_t>(side == 0 ? plane_low : plane_high), q1 = q0 + (uintptr_t)plane_bytes;
+    if (q0 < p1 && p0 < q1) return 3;
+  }
+  return 0;
+}
+
+void refuseWallPlanes(int refusal) {
+  if (refusal == 1) CD_INVALID_USAGE("sides argument must be 1, 2 or 3: the low halo, the high halo or both");
+  if (refusal == 2) CD_INVALID_USAGE("the plane of a side named in sides cannot be null");
+  if (refusal == 3) CD_INVALID_USAGE("a plane named in sides cannot overlap the pencil");
+  CD_INTERNAL_ERROR("no wall-plane refusal to make");
+}
+
+HaloPlan buildHaloWallPlanesPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                 const int32_t* pad, int centering, bool negate, int sides, bool self_exchange) {
+  if (sides < 1 || sides > 3) {  // (callers check first, in the contract's place; here after the reflection's own argument checks)
+    reflectSides(g, rank, axis, dim, halo, periods, pad, centering, negate, 0, self_exchange);
+    refuseWallPlanes(1);
+  }
+  HaloPlan p = reflectSides(g, rank, axis, dim, halo, periods, pad, centering, negate, sides, self_exchange);
+  p.op.kind = HaloOp::WALL_PLANES;
+  p.op.sides = sides;
+  // the plane: the pencil's shape with the extent along `dim` replaced by h, dense in the pencil's memory order
+  const Pencil hp = makePencil(g, gridIndexOfRank(g, rank), axis, halo, pad);
+  const i64 he = halo[dim];
+  if (he > 0 && !(periods && periods[dim]) && hp.extentG(dim) > 0) {
+    p.pencil_elements = hp.size;
+    p.plane_elements = hp.size / hp.extentG(dim) * he;
+  }
+  if (p.pre.empty()) return p;
+  i64 pst[3], run = 1;
+  for (int i = 0; i < 3; ++i) {
+    pst[hp.order[i]] = run;
+    run *= hp.order[i] == dim ? he : (i64)hp.shape[i];
+  }
+  for (Move3D& m : p.pre) {
+    if (!m.reflect || (m.peer != 0 && m.peer != 1)) CD_INTERNAL_ERROR("a wall-plane plan whose moves are not the reflection's");
+    const bool low = m.peer == 0;  // (blockMove's `peer` of a reflect-move is its side)
+    m.plane = m.peer + 1;
+    for (int ga = 0; ga < 3; ++ga) m.ps[ga] = pst[ga];
+    // destination index j along `dim` is ghost layer h - 1 - j on the low side, layer j on the high side; the other two dims start
+    // at the pencil's index 0, as the slab does
+    m.plane_off = low ? (he - 1) * pst[dim] : 0;
+    if (low) m.ps[dim] = -pst[dim];
+  }
+  return p;
+}
+
 HaloPlan buildHaloFoldPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
                            const int32_t* pad, int centering, bool negate, bool clear, bool self_exchange) {
   // (its refusals, its neighbours, its sides: one fold-move per reflect-move, the same cells with source and destination swapped)
@@ -721,6 +775,9 @@ HaloPlan buildHaloOpPlan(const GridShape& g, int rank, int axis, int dim, const 
       p.op.n_fields = op.n_fields;
       return p;
     }
+    case HaloOp::WALL_PLANES:
+      if (op.n_fields != 1) CD_INTERNAL_ERROR("wall planes serve one field per call");
+      return buildHaloWallPlanesPlan(g, rank, axis, dim, halo, periods, pad, op.centering, op.negate, op.sides, self_exchange);
   }
   CD_INTERNAL_ERROR("unknown halo operation");
 }

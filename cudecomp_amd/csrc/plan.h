@@ -71,6 +71,16 @@ struct Move3D {
   // without `negate` and nothing else: with dst_row_pitch, fill, take, add or a remote destination it is an internal error before
   // any launch, and so is a mirrored dim thicker than the addend table (kern::kMaxWallHalo).
   int affine = 0;
+  // reflect-moves of cudecompAmdSetWallPlaneHalos* only (buildHaloWallPlanesPlan): the move has a THIRD operand in device memory,
+  // dst = +-src + plane[plane_off + k0*ps[0] + k1*ps[1] + k2*ps[2]], in elements.  1: it reads the call's low plane, 2: its high
+  // plane; 0: none.  The strides are SIGNED: along the mirrored dim ps is negative on the low side (destination index j is ghost
+  // layer h - 1 - j, and plane_off names the entry of index 0), so the kernels index the plane by destination, as they index the
+  // source.  The plane POINTERS travel with the call, not with the move (kernels.h launchMoves).  Such a move is a reflect-move with
+  // or without `negate` and nothing else: with dst_row_pitch, fill, take, add, affine or a remote destination it is an internal error
+  // before any launch.  It carries no layer limit.
+  int plane = 0;
+  i64 plane_off = 0;
+  i64 ps[3] = {0, 0, 0};
 
   i64 elements() const { return extent[0] * extent[1] * extent[2]; }
 };
@@ -197,13 +207,13 @@ RelayPlan buildRelayPlan(const GridShape& g, int nranks, int rank, TransposeOp o
 // What a halo call is: the operation and the arguments that change its plan.  Every builder below writes the record of its plan;
 // buildHaloOpPlan goes the other way.  Ordered, so that it can be part of the key of the plan cache (internal.h).
 struct HaloOp {
-  enum Kind { UPDATE, ACCUMULATE, FILL, REFLECT, FOLD, WALL_VALUES } kind = UPDATE;
+  enum Kind { UPDATE, ACCUMULATE, FILL, REFLECT, FOLD, WALL_VALUES, WALL_PLANES } kind = UPDATE;
   bool clear = false;  // ACCUMULATE, FOLD: the ghost cells read are cleared
-  int centering = 0;   // REFLECT, FOLD, WALL_VALUES
-  bool negate = false; // REFLECT, FOLD, WALL_VALUES of ONE field: parity -1 (several fields: false; their parities travel with the call)
+  int centering = 0;   // REFLECT, FOLD, WALL_VALUES, WALL_PLANES
+  bool negate = false; // REFLECT, FOLD, WALL_VALUES, WALL_PLANES of ONE field: parity -1 (several fields: false; their parities travel with the call)
   int n_fields = 1;    // UPDATE, ACCUMULATE, REFLECT, FOLD, WALL_VALUES (1 for FILL)
-  int sides = 3;       // WALL_VALUES: bit 0 the low halo, bit 1 the high halo (it changes the moves; the addends do not and are
-                       // no part of the record: calls that differ only in them share a plan)
+  int sides = 3;       // WALL_VALUES, WALL_PLANES: bit 0 the low halo, bit 1 the high halo (it changes the moves; the addends and the
+                       // plane pointers do not and are no part of the record: calls that differ only in them share a plan)
   bool operator<(const HaloOp& o) const {
     return std::tie(kind, clear, centering, negate, n_fields, sides) < std::tie(o.kind, o.clear, o.centering, o.negate, o.n_fields, o.sides);
   }
@@ -225,6 +235,9 @@ struct HaloPlan {
   bool ordered = false;  // accumulation and fold plans: the destinations of the two add-moves overlap (interior narrower than two
                          // halos; fold: n < 4h + 2c): one launch each, in order
   i64 slot_elements = 0; // multi-field builders, PACKED: the length of one workspace slot (buildHaloFieldsPlan)
+  // WALL_PLANES: the elements of the pencil and of one plane, for the runner's overlap check of a call that finds its plan cached;
+  // both 0 where the dim is periodic or has no halo (no plane to overlap with).  Set on every rank, whether or not it has moves.
+  i64 pencil_elements = 0, plane_elements = 0;
 };
 
 HaloPlan buildHaloPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
@@ -281,6 +294,24 @@ constexpr int kMaxWallLayers = 8;  // CUDECOMP_AMD_MAX_WALL_HALO and kern::kMaxW
 int wallValueRefusal(int sides, bool has_low, bool has_high, i64 halo_dim);
 [[noreturn]] void refuseWallValues(int refusal);
 
+// Wall PLANES along `dim` (include/cudecomp_halo_wall_planes.h has the contract): the reflection with an addend per CELL of the
+// ghost slab, read from a device array that is a slab of the pencil, cell = s * mirror + plane(k; p, q).  The moves are
+// buildHaloWallValuesPlan's for the sides kept -- same cells, same `reflect` and `negate`, no `affine` -- and each describes its third
+// operand (Move3D::plane, plane_off, ps): the plane has the pencil's shape (halos and padding included) with the extent along `dim`
+// replaced by h = halo[dim], dense in the pencil's memory order; the index along `dim` is the ghost layer k, counted from the wall
+// outward, so ps[dim] is negative on the low side; the other two indices are the pencil's own.  No layer limit.  The refusals of
+// buildHaloPlan first, then the centering, then `sides` outside 1 .. 3 (callers that hold the plane pointers check them in the
+// contract's place, wallPlaneRefusal below); the reflection's refusal h + c > n - 2h only for a side that would be written.  Kinds:
+// NONE or SELF_PERIODIC ("local").
+HaloPlan buildHaloWallPlanesPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods,
+                                 const int32_t* pad, int centering, bool negate, int sides, bool self_exchange = false);
+// The three checks of the wall planes that follow the centering check, in the contract's order: 0 fine, 1 `sides` outside 1 .. 3, 2 a
+// NULL plane of a side named in `sides`, 3 a named plane whose byte range [plane, plane + plane_bytes) overlaps the pencil's
+// [pencil, pencil + pencil_bytes) -- a comparison of addresses (plane_bytes == 0: periodic dim or h == 0, NULL check only).
+// refuseWallPlanes throws INVALID_USAGE for 1 .. 3.
+int wallPlaneRefusal(int sides, const void* plane_low, const void* plane_high, const void* pencil, i64 pencil_bytes, i64 plane_bytes);
+[[noreturn]] void refuseWallPlanes(int refusal);
+
 // Halo FOLDING along `dim` (include/cudecomp_halo_fold.h has the contract) -- the transpose of the reflection: the ghost cells the
 // reflection along `dim` writes are ADDED to the interior cells it reads them from: low side cell(h+k+c) += s * cell(h-1-k), then
 // high side cell(n-h-1-k-c) += s * cell(n-h+k), k in [0, h).  Refusals, neighbours and sides are buildHaloReflectPlan's, which is
@@ -329,8 +360,8 @@ HaloPlan buildHaloWallFieldsPlan(const GridShape& g, int rank, int axis, int dim
                                  const int32_t* pad, bool fold, int centering, bool clear, int n_fields, bool self_exchange = false);
 
 // The plan of the halo call `op`, by the builder of its family: UPDATE buildHaloFieldsPlan, ACCUMULATE buildHaloAccumulateFieldsPlan
-// (one field: the single plans, unchanged), REFLECT and FOLD their own for one field and buildHaloWallFieldsPlan for several, FILL
-// and WALL_VALUES their own.  `force_packed` reaches the builders that take it.
+// (one field: the single plans, unchanged), REFLECT and FOLD their own for one field and buildHaloWallFieldsPlan for several, FILL,
+// WALL_VALUES and WALL_PLANES their own.  `force_packed` reaches the builders that take it.
 HaloPlan buildHaloOpPlan(const GridShape& g, int rank, int axis, int dim, const int32_t* halo, const bool* periods, const int32_t* pad,
                          const HaloOp& op, bool force_packed, bool self_exchange = false);
 

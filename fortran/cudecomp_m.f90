@@ -643,6 +643,61 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompAmdSetWallHalosZ_C
 
+    ! cudecomp_halo_wall_planes.h: wall planes (the reflection with an addend per cell of the ghost slab, from device arrays)
+    function cudecompAmdSetWallPlaneHalosX_C(handle, grid_desc, input, dtype, parity, centering, sides, planes_low, planes_high, &
+                                             halo_extents, halo_periods, dim, padding, stream) &
+      bind(C, name="cudecompAmdSetWallPlaneHalosX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      integer(c_int32_t), value :: parity, centering, sides
+      type(c_ptr), value :: planes_low, planes_high  ! device arrays of `dtype` (NULL for a side that `sides` does not name)
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdSetWallPlaneHalosX_C
+
+    function cudecompAmdSetWallPlaneHalosY_C(handle, grid_desc, input, dtype, parity, centering, sides, planes_low, planes_high, &
+                                             halo_extents, halo_periods, dim, padding, stream) &
+      bind(C, name="cudecompAmdSetWallPlaneHalosY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      integer(c_int32_t), value :: parity, centering, sides
+      type(c_ptr), value :: planes_low, planes_high  ! device arrays of `dtype` (NULL for a side that `sides` does not name)
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdSetWallPlaneHalosY_C
+
+    function cudecompAmdSetWallPlaneHalosZ_C(handle, grid_desc, input, dtype, parity, centering, sides, planes_low, planes_high, &
+                                             halo_extents, halo_periods, dim, padding, stream) &
+      bind(C, name="cudecompAmdSetWallPlaneHalosZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr), value :: input
+      integer(c_int), value :: dtype
+      integer(c_int32_t), value :: parity, centering, sides
+      type(c_ptr), value :: planes_low, planes_high  ! device arrays of `dtype` (NULL for a side that `sides` does not name)
+      integer(c_int32_t) :: halo_extents(3)
+      logical(c_bool) :: halo_periods(3)
+      integer(c_int32_t), value :: dim
+      integer(c_int32_t) :: padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdSetWallPlaneHalosZ_C
+
     ! cudecomp_halo_wall_value_fields.h: wall values of several pencils, each with a parity and addends of its own
     function cudecompAmdSetWallFieldHalosX_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, sides, values_low, &
                                              values_high, halo_extents, halo_periods, dim, padding, stream) &
@@ -1792,6 +1847,104 @@ contains
     res = cudecompAmdSetWallHalosZ_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
                                       int(centering, c_int32_t), int(sides, c_int32_t), lo, hi, h, per, int(dim - 1, c_int32_t), p, s)
   end function cudecompAmdSetWallHalosZ
+
+  ! ---- wall planes (cudecomp_halo_wall_planes.h): the arguments of the wall values with two DEVICE arrays in the place of the host
+  ! arrays of addends ----
+  function cudecompAmdSetWallPlaneHalosX(handle, grid_desc, input, dtype, parity, centering, sides, planes_low, planes_high, &
+                                         halo_extents, halo_periods, dim, padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: parity     ! +1: even mirror; -1: odd mirror (sign bits flipped)
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: sides      ! 1: the low halo; 2: the high halo; 3: both
+    ! device arrays of `dtype`: the pencil's shape with the extent along `dim` replaced by halo_extents(dim), dense in the pencil's
+    ! memory order; along `dim` index 1 is the layer next to the wall.  Only read, when the kernel runs; the one of a side that
+    ! `sides` does not name may be left out
+    type(*), dimension(..), optional, target :: planes_low, planes_high
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    type(c_ptr) :: lo, hi
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    lo = c_null_ptr
+    hi = c_null_ptr
+    if (present(planes_low)) lo = c_loc(planes_low)
+    if (present(planes_high)) hi = c_loc(planes_high)
+    res = cudecompAmdSetWallPlaneHalosX_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
+                                           int(centering, c_int32_t), int(sides, c_int32_t), lo, hi, h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdSetWallPlaneHalosX
+
+  function cudecompAmdSetWallPlaneHalosY(handle, grid_desc, input, dtype, parity, centering, sides, planes_low, planes_high, &
+                                         halo_extents, halo_periods, dim, padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: parity     ! +1: even mirror; -1: odd mirror (sign bits flipped)
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: sides      ! 1: the low halo; 2: the high halo; 3: both
+    ! device arrays of `dtype`: the pencil's shape with the extent along `dim` replaced by halo_extents(dim), dense in the pencil's
+    ! memory order; along `dim` index 1 is the layer next to the wall.  Only read, when the kernel runs; the one of a side that
+    ! `sides` does not name may be left out
+    type(*), dimension(..), optional, target :: planes_low, planes_high
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    type(c_ptr) :: lo, hi
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    lo = c_null_ptr
+    hi = c_null_ptr
+    if (present(planes_low)) lo = c_loc(planes_low)
+    if (present(planes_high)) hi = c_loc(planes_high)
+    res = cudecompAmdSetWallPlaneHalosY_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
+                                           int(centering, c_int32_t), int(sides, c_int32_t), lo, hi, h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdSetWallPlaneHalosY
+
+  function cudecompAmdSetWallPlaneHalosZ(handle, grid_desc, input, dtype, parity, centering, sides, planes_low, planes_high, &
+                                         halo_extents, halo_periods, dim, padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(*), dimension(..), target :: input
+    integer :: dtype
+    integer :: parity     ! +1: even mirror; -1: odd mirror (sign bits flipped)
+    integer :: centering  ! 0: about the face between ghost and interior cells; 1: about the first / last interior cell
+    integer :: sides      ! 1: the low halo; 2: the high halo; 3: both
+    ! device arrays of `dtype`: the pencil's shape with the extent along `dim` replaced by halo_extents(dim), dense in the pencil's
+    ! memory order; along `dim` index 1 is the layer next to the wall.  Only read, when the kernel runs; the one of a side that
+    ! `sides` does not name may be left out
+    type(*), dimension(..), optional, target :: planes_low, planes_high
+    integer :: halo_extents(3)
+    logical :: halo_periods(3)
+    integer :: dim  ! 1/2/3 = x/y/z
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    logical(c_bool) :: per(3)
+    integer(c_intptr_t) :: s
+    type(c_ptr) :: lo, hi
+    call halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
+    lo = c_null_ptr
+    hi = c_null_ptr
+    if (present(planes_low)) lo = c_loc(planes_low)
+    if (present(planes_high)) hi = c_loc(planes_high)
+    res = cudecompAmdSetWallPlaneHalosZ_C(handle, grid_desc, c_loc(input), int(dtype, c_int), int(parity, c_int32_t), &
+                                           int(centering, c_int32_t), int(sides, c_int32_t), lo, hi, h, per, int(dim - 1, c_int32_t), p, s)
+  end function cudecompAmdSetWallPlaneHalosZ
 
   ! ---- halo folding (cudecomp_halo_fold.h): the arguments of the reflection with `clear` after the centering ----
   function cudecompAmdFoldHalosX(handle, grid_desc, input, dtype, parity, centering, clear, halo_extents, halo_periods, dim, &

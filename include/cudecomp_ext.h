@@ -369,6 +369,34 @@ cudecompResult_t cudecompExtWall3D(const void* src, void* dst, cudecompDataType_
                                    const void* addends, const int64_t extent[3], const int64_t ss[3], const int64_t ds[3],
                                    int32_t force, int32_t* kernel_class, hipStream_t stream);
 
+/* One wall-plane move on the GPU (kernels_wall_plane.hip): dst[k0*ds[0] + k1*ds[1] + k2*ds[2]] = +-src[k0*ss[0] + k1*ss[1] +
+ * k2*ss[2]] + plane[k0*ps[0] + k1*ps[1] + k2*ps[2]] in the arithmetic of `dtype`, 0 <= k_i < extent[i] (strides in elements of
+ * `dtype`), where exactly one entry of ss is negative: the mirrored dim, of any extent, src pointing at the source cell of its index
+ * 0.  ps is signed as well and may be negative along the mirrored dim only (a low side: plane then points at the entry of index 0).
+ * negate != 0: the sign bit of every real of the source is inverted before the addition.  src and dst are disjoint cells, usually
+ * of one buffer; plane is device memory that is only read.  force: the bits of cudecompExtReflect3D.  *kernel_class (optional): 0
+ * rows, 2 generic. */
+cudecompResult_t cudecompExtWallPlane3D(const void* src, void* dst, const void* plane, cudecompDataType_t dtype, int32_t negate,
+                                        const int64_t extent[3], const int64_t ss[3], const int64_t ds[3], const int64_t ps[3],
+                                        int32_t force, int32_t* kernel_class, hipStream_t stream);
+
+/* The stateless planner of cudecompAmdSetWallPlaneHalos{X,Y,Z} (cudecomp_halo_wall_planes.h; csrc/plan.h buildHaloWallPlanesPlan)
+ * with the call's checks in the call's order; the three addresses are only compared (0 = NULL).  The plan is that of
+ * cudecompExtPlanHaloWallValues for the sides kept, whatever the width of the halo; cudecompExtHaloPlan_t::reserved has bit 18 set,
+ * bit 13: the moves flip the sign bits, bits 16, 17: the call's `sides`.  operands[i] is the third operand of pre[i]: the plane it
+ * reads (1 low, 2 high; 0 beyond n_pre), the element offset into that plane of the entry destination index (0, 0, 0) adds, and the
+ * three SIGNED element strides by GLOBAL axis, like the move's own -- negative along `dim` on the low side. */
+typedef struct {
+  int32_t plane, reserved;
+  int64_t off;
+  int64_t ps[3];
+} cudecompExtPlaneOperand_t;
+cudecompResult_t cudecompExtPlanHaloWallPlanes(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo_extents[],
+                                               const bool halo_periods[], int32_t dim, const int32_t padding[], cudecompDataType_t dtype,
+                                               int32_t parity, int32_t centering, int32_t sides, uint64_t pencil_address,
+                                               uint64_t plane_low_address, uint64_t plane_high_address, cudecompExtHaloPlan_t* plan,
+                                               cudecompExtPlaneOperand_t operands[2]);
+
 /* How the kernel layer WOULD execute a 3-D block move between buffers at the given addresses (no launch; works without a
  * GPU): out[10] = {class (0 rows, 1 LDS transpose, 2 generic), kernel variant, tile_i, tile_j, tiles_i, tiles_j, batch extent,
  * run length of the tile walk, walk bits (1 XCD-contiguous, 2 j first, 4 runs over batch planes), access mode}.  flags: 2 =
@@ -399,7 +427,12 @@ cudecompResult_t cudecompExtDescribeMove(uint64_t src_address, uint64_t dst_addr
  * the mirrored dim, of at most CUDECOMP_AMD_MAX_WALL_HALO cells, `peer` the side whose addends the move takes -- 0 low, ghost layer
  * k at destination index extent - 1 - k; 1 high, at index k; any other value is CUDECOMP_RESULT_INVALID_USAGE -- and fill_value
  * points at 2 x CUDECOMP_AMD_MAX_WALL_HALO elements of `es` bytes on the host, the low side's layers then the high side's); 12:
- * wall values with the sign bits of the source flipped first.  The
+ * wall values with the sign bits of the source flipped first; 13: wall planes (reflect-moves that add the entry of a device array
+ * at the destination cell, in the arithmetic of `dtype`, whose size must be `es`: source and destination are cells of buffer 0,
+ * buffer 1 is the low plane and buffer 2 the high plane; the negative `ss` entry names the mirrored dim, of any extent, `peer` the
+ * plane the move reads -- 0 low, 1 high -- and the list is 2 n entries long: entry n + i describes the third operand of move i, its
+ * dst_off the element offset into the plane and its ds the three signed strides, its other fields unread); 14: wall planes with the
+ * sign bits of the source flipped first.  The
  * sources of a list of mode 3, 4 or 7 ... 10 must be disjoint from all destinations and from each other.  flags: bits 1, 2, 4, 8, 64, 128
  * of cudecompExtMove3D, same meanings.  dst_bases (optional, n entries): moves[i] writes dst_bases[i] + dst_off instead, with
  * the system-scope stores of a peer's memory (access mode 3) -- the calling form of the one-sided transports; additions,
@@ -412,8 +445,8 @@ cudecompResult_t cudecompExtDescribeMove(uint64_t src_address, uint64_t dst_addr
  * kind counts csrc/kernels_batch.h KernelKind: 0 rows, 1 rows shifted, 2 rows dense, 3 transpose, 4 transpose window, 5 transpose
  * lines, 6 transpose row lines, 7 generic, 8 rows addition, 9 generic addition, 10 rows fill, 11 generic fill, 12 rows take, 13 generic take, 14 rows addition
  * with take, 15 generic addition with take, 16 rows reflection, 17 generic reflection, 18 rows fold, 19 generic fold, 20 rows
- * fold with take, 21 generic fold with take, 37 rows wall values, 38 generic wall values (22 ... 36: the lists of field-moves,
- * which this call never makes). */
+ * fold with take, 21 generic fold with take, 37 rows wall values, 38 generic wall values, 41 rows wall planes, 42 generic wall planes (22 ... 36,
+ * 39 and 40: the lists of field-moves, which this call never makes). */
 typedef struct {
   int32_t cls;                                      /* 0 rows, 1 LDS transpose, 2 generic */
   int32_t kind, es, vec, tile_i, tile_j, access, arith; /* csrc/kernels_batch.h KernelChoice */

@@ -67,8 +67,10 @@ extern "C" {
  * Several fields at once, each with a parity and addends of its own: cudecompAmdSetWallFieldHalos{X,Y,Z},
  * cudecomp_halo_wall_value_fields.h.
  *
- * Out of scope: addends that vary along the wall (a plane of values); halos wider than CUDECOMP_AMD_MAX_WALL_HALO; an adjoint
- * ("fold") of the affine call; the performance report and the autotuner.
+ * Addends that vary along the wall (a plane of values in device memory) and halos wider than CUDECOMP_AMD_MAX_WALL_HALO:
+ * cudecompAmdSetWallPlaneHalos{X,Y,Z}, cudecomp_halo_wall_planes.h.
+ *
+ * Out of scope: an adjoint ("fold") of the affine call; the performance report and the autotuner.
  */
 cudecompResult_t cudecompAmdSetWallHalosX(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input,
                                           cudecompDataType_t dtype, int32_t parity, int32_t centering, int32_t sides,
