@@ -1,6 +1,7 @@
 """IEEE edge values for every kernel that adds: the operand tables, the expected sums and the launch shapes shared by
 tests/test_gpu_halo_accumulate.py (kernels_accumulate.hip) and tests/test_gpu_halo_edge_arithmetic.py (kernels_fold.hip,
-kernels_field_mirror.hip, kernels_field_accumulate.hip, kernels_wall.hip).  numpy only: nothing here touches the GPU.
+kernels_field_mirror.hip, kernels_field_accumulate.hip, kernels_wall.hip, kernels_field_wall.hip, kernels_wall_plane.hip).  numpy
+only: nothing here touches the GPU.
 tests/test_edge_arithmetic_table.py holds the tables to the conditions the GPU tests rely on (every class of result occurs, the
 NaN cells -- the only ones compared by class -- stay few, a wrong reference is told apart).
 
@@ -23,6 +24,23 @@ KERNELS = {cd.HALF: (T16, 1, (16, 8, 4, 2)), cd.BFLOAT16: (TBF, 1, (16, 8, 4, 2)
            cd.FLOAT: (T32, 1, (16, 8, 4)), cd.FLOAT_COMPLEX: (T32, 2, (16, 8)), cd.DOUBLE: (T64, 1, (16, 8)),
            cd.DOUBLE_COMPLEX: (T64, 2, (16,))}
 DRAW_SEED = 7
+TF = {False: "false", True: "true"}
+
+
+def wall_plane_names(dtype):
+    """every instantiation of kernels_wall_plane.hip for the type, as cudecompExtLastKernelName spells them (the element-wise
+    kernel carries the element size in bytes)"""
+    t, _, widths = KERNELS[dtype]
+    es = AB.element_bytes(dtype)
+    return {"rows_wall_plane_kernel<%s,%d,%d,%s>" % (t, vb, s, TF[neg]) for vb in widths for s in (0, 1) for neg in (False, True)} | \
+           {"generic_wall_plane_kernel<%s,%d,%s>" % (t, es, TF[neg]) for neg in (False, True)}
+
+
+def field_wall_names(dtype):
+    """every instantiation of kernels_field_wall.hip for the type (the sign is an argument of these kernels, not a template's)"""
+    t, _, widths = KERNELS[dtype]
+    return {"rows_fields_wall_kernel<%s,%d,%d>" % (t, vb, s) for vb in widths for s in (0, 1)} | \
+           {"generic_fields_wall_kernel<%s,%d>" % (t, AB.element_bytes(dtype))}
 
 
 def pair_elements(dtype, a, b):
@@ -74,6 +92,27 @@ def flip_after_the_addition(dtype, a, b):
 def flip_the_destination(dtype, a, b):
     """-a + b where a + -b is meant"""
     return AB.typed_add(dtype, flip(dtype, a), np.ascontiguousarray(b))
+
+
+def flip_the_addend(dtype, mirror, addend):
+    """the wall order of operands: mirror + -addend where -mirror + addend is meant (flip_after_the_addition, applied to (mirror,
+    addend), is the other wrong wall reference: -(mirror + addend))"""
+    return AB.typed_add(dtype, np.ascontiguousarray(mirror), flip(dtype, addend))
+
+
+def edge_doubles(dtype):
+    """(doubles, is_nan): the 24 entries of AB.edge_table of the type's real format as float64 -- what cudecompAmdSetWallHalos*
+    and cudecompAmdSetWallFieldHalos* take as addends.  Every fp16, bf16 and fp32 pattern that is not a NaN IS a double, and the
+    library's narrowing of that double gives the pattern back (tests/test_edge_arithmetic_table.py holds the round trip through
+    AB.to_bytes); the fp64 entries are themselves.  What becomes of a NaN's payload on the way is unspecified: NaN by class."""
+    kind = AB.kind_of(dtype)
+    table = AB.edge_table(kind)
+    with np.errstate(invalid="ignore"):  # (the signalling NaN of the table)
+        if kind == "bf16":
+            wide = (table.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+        else:
+            wide = table.view(AB._FLOAT_OF_KIND[kind]).astype(np.float64)
+    return wide, AB.classes(kind, table)["nan"]
 
 
 def flush_subnormal_results(dtype, want):

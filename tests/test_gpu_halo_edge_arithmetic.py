@@ -1,7 +1,10 @@
 """IEEE edge values through the adding kernels that tests/test_gpu_halo_accumulate.py and tests/test_gpu_halo_accumulate_clear.py
 do not reach: kernels_fold.hip (rows_fold_kernel, generic_fold_kernel), kernels_field_mirror.hip (rows_fields_fold_kernel,
-generic_fields_fold_kernel), kernels_field_accumulate.hip (rows_fields_accumulate_kernel, generic_fields_accumulate_kernel) and
-every lane width, the streaming access and the complex types of kernels_wall.hip (rows_wall_kernel, generic_wall_kernel).
+generic_fields_fold_kernel), kernels_field_accumulate.hip (rows_fields_accumulate_kernel, generic_fields_accumulate_kernel),
+every lane width, the streaming access and the complex types of kernels_wall.hip (rows_wall_kernel, generic_wall_kernel), and
+the same of kernels_field_wall.hip (rows_fields_wall_kernel, generic_fields_wall_kernel: per-field signs, the addend table up to
+its last entry and at its odd half-words) and kernels_wall_plane.hip (rows_wall_plane_kernel, generic_wall_plane_kernel: the plane
+a third operand with pitches of its own, eight plane operands in one launch).
 
 Operands: all 24 x 24 pairs of AB.edge_table per real format (signed zeros, subnormals, ties, overflow ties, infinities, two NaNs)
 and the three dense draws of AB.dense_draws at 2^16 reals, laid out by tests/edge_arithmetic.py.  Every launch places them by the cell
@@ -14,8 +17,12 @@ that ran are held to the spelled-out set of instantiations of the family: an ins
 tests/test_edge_arithmetic_table.py holds the operand tables to what these tests need of them (classes present, few NaN cells, a
 wrong reference is told apart) on the CPU; the two can-fail tests at the end show the same on the device's own results.
 
-The public calls (cudecompAmdFoldHalos*, cudecompAmdFoldFieldHalos*, cudecompAmdAccumulateFieldHalos*) on pencils filled with the
-same pairs, ghost cells included, run on a rank of the pool: tests/edge_arithmetic_bodies.py."""
+The wall kernels have no destination operand: the source cell holds a[n], the addend -- of the layer, or the plane entry of the
+destination cell -- b[n], and the destination holds EA.expected_wall, the flipped mirror first.
+
+The public calls (cudecompAmdFoldHalos*, cudecompAmdFoldFieldHalos*, cudecompAmdAccumulateFieldHalos*, cudecompAmdSetWallHalos*,
+cudecompAmdSetWallFieldHalos*, cudecompAmdSetWallPlaneHalos*) on pencils filled with the same pairs, ghost cells included, run on
+a rank of the pool: tests/edge_arithmetic_bodies.py."""
 import itertools
 
 import numpy as np
@@ -26,6 +33,7 @@ from tests import accumulate_bodies as AB
 from tests import edge_arithmetic as EA
 from tests import edge_arithmetic_bodies as EB
 from tests import move_lists as ML
+from tests import wall_planes_bodies as WPB
 from tests.mp import run_ranks
 
 pytestmark = pytest.mark.gpu
@@ -335,6 +343,287 @@ def test_wall_kernels_on_edge_values_every_lane_width(dtype):
     assert seen == names, sorted(seen ^ names)
 
 
+# ---- kernels_wall_plane.hip -----------------------------------------------------------------------------------------------------
+def _up8(n):
+    return -(-int(n) // 8) * 8
+
+
+def _plane_strides(w, h):
+    """(pencil source, pencil destination, plane): three different padded pitches, each a multiple of 8 elements -- the lanes of a
+    wall-plane move divide every base and stride of its three operands, so with these only the row length narrows them"""
+    sp, dp, pp = _up8(w) + 16, _up8(w) + 8, _up8(w) + 24
+    return (1, sp, sp * (h + 1)), (1, dp, dp * (h + 2)), (1, pp, pp * (h + 3))
+
+
+def _wall_plane(dtype, extent, ss, ds, ps, mirrored, soff, doff, poff, a, b, negate, side, force, seed=0, reference=None):
+    """one wall-plane move through cudecompExtWallPlane3D: source and destination in one buffer, the plane in a second one, mirrored
+    along `mirrored` on the low side (0) as the source always is.  Source cell n holds a[n], the plane entry of destination cell n
+    holds b[n]; dst = (flipped) a + b.  The plane buffer must stay as it is.  Returns (kernel name, device bit patterns of the
+    destination cells, expected ones); reference: as for _fold."""
+    import torch
+    u, nc, es = _format(dtype)
+    signed, first = _mirrored(extent, ss, mirrored)
+    psigned, pfirst = _mirrored(extent, ps, mirrored if side == 0 else None)
+    front = SLACK // es
+    src, dst = front + ML.cells(extent, signed, soff + first), front + ML.cells(extent, ds, doff)
+    pc = front + ML.cells(extent, psigned, poff + pfirst)
+    both = np.concatenate([src, dst])
+    assert src.min() >= front and np.unique(both).size == both.size and a.shape == b.shape == (dst.size, nc)
+    assert pc.min() >= front and np.unique(pc).size == pc.size
+    init = _random_cells(dtype, int(both.max()) + 1 - front, seed)
+    pinit = _random_cells(dtype, int(pc.max()) + 1 - front, seed + 1000)
+    init[src], pinit[pc] = a, b
+    exp = init.copy()
+    exp[dst] = EA.expected_wall(dtype, a, b, negate) if reference is None else reference(dtype, a, b)
+    dev, pdev = _upload(init), _upload(pinit)
+    base, pbase = dev.data_ptr() + SLACK, pdev.data_ptr() + SLACK
+    cls = cd.cudecompExtWallPlane3D(base + (soff + first) * es, base + doff * es, pbase + (poff + pfirst) * es, dtype, negate, extent,
+                                    signed, ds, psigned, force, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    name = cd.cudecompExtLastKernelName()
+    where = ("wall plane", AB.NAMES[dtype], extent, ss, ds, ps, mirrored, soff, doff, poff,
+             "side %d negate %d force %d" % (side, negate, force), cls, name)
+    assert np.array_equal(pdev.cpu().numpy().view(u).reshape(-1, nc), pinit), where + ("the plane buffer was written",)
+    if reference is not None:
+        got = dev.cpu().numpy().view(u).reshape(-1, nc)
+        return name, got[dst], exp[dst]
+    got = _compare(dtype, dev, exp, [(dst, a, b)], where)
+    return name, got[dst], exp[dst]
+
+
+@TYPES
+def test_wall_plane_kernels_on_edge_values(dtype):
+    """the four shapes of 576 elements -- the mirrored dim the row index for two of them, the plane index for the others -- through
+    the fast path, the forced element-wise and the forced streaming kernel, plain and sign-flipping, from a low and from a high
+    plane whose pitches are not the pencil's; 2-byte elements at odd bases of the pencil, and of the plane alone"""
+    a, b = EA.pairs(dtype)
+    t, nc, widths = EA.KERNELS[dtype]
+    es = AB.element_bytes(dtype)
+    seen = set()
+    for k, (w, h, d) in enumerate(EA.SHAPES):
+        ss, ds, ps = _plane_strides(w, h)
+        assert len({ss[1], ds[1], ps[1]}) == 3 and not (ss[1] | ds[1] | ps[1] | ss[2] | ds[2] | ps[2]) & 1
+        doff = _up8(8 + ML.span((w, h, d), ss) + 4)
+        vb = max(v for v in widths if (w * es) % v == 0)
+        for force, negate, side in itertools.product(FORCES, (False, True), (0, 1)):
+            name, _, _ = _wall_plane(dtype, (w, h, d), ss, ds, ps, 1 + k % 2, 8, doff, 16, a, b, negate, side, force, seed=k)
+            assert name == ("generic_wall_plane_kernel<%s,%d,%s>" % (t, es, TF[negate]) if force & 1 else
+                            "rows_wall_plane_kernel<%s,%d,%d,%s>" % (t, vb, force // 2, TF[negate])), (name, force)
+            seen.add(name)
+    assert seen == EA.wall_plane_names(dtype), sorted(seen ^ EA.wall_plane_names(dtype))
+    if es == 2:  # 2-byte lanes whatever the row length: (a) the pencil's bases odd, (b) ONLY the plane's base odd
+        ss, ds, ps = _plane_strides(96, 3)
+        doff = _up8(8 + ML.span((96, 3, 2), ss) + 4)
+        for (soff, at, poff), force, negate, side in itertools.product(((1, doff + 3, 16), (8, doff, 17)), (0, 2), (False, True), (0, 1)):
+            name, _, _ = _wall_plane(dtype, (96, 3, 2), ss, ds, ps, 1, soff, at, poff, a, b, negate, side, force, seed=9)
+            assert name == "rows_wall_plane_kernel<%s,2,%d,%s>" % (t, force // 2, TF[negate]), (name, soff, poff)
+    # the mirrored dim as the fastest one: the element-wise kernel without a force bit
+    for negate, side in itertools.product((False, True), (0, 1)):
+        name, _, _ = _wall_plane(dtype, (24, 6, 4), (1, 50, 50 * 7), (1, 50, 50 * 7), (1, 32, 32 * 8), 0, 0, 24, 2, a, b, negate, side, 0, seed=10)
+        assert name == "generic_wall_plane_kernel<%s,%d,%s>" % (t, es, TF[negate]), name
+
+
+@TYPES
+def test_wall_plane_lists_on_edge_values(dtype):
+    """eight wall-plane moves of one kernel choice in ONE launch of cudecompExtRunMoves, the PlaneOperands of all eight in use: move
+    i carries the pairs rotated by 25 i, the sides alternate, every move reads its plane at another offset, and every destination is
+    held to ITS plane entries; the fast path and the element-wise flag, plain and sign-flipping"""
+    import torch
+    u, nc, es = _format(dtype)
+    a, b = EA.pairs(dtype)
+    t = EA.KERNELS[dtype][0]
+    extent, front = (96, 3, 2), SLACK // es
+    ss, _, ps = _plane_strides(96, 3)
+    span, pspan = ML.span(extent, ss), ML.span(extent, ps)
+    pairs, at = [], 8
+    for i in range(8):
+        doff = _up8(at + span + 4)
+        pairs.append(WPB.plane_move(extent, ss, 1 + (i // 2) % 2, at, doff, i & 1, ps, poff=8 * (i + 1) + (i // 2) * _up8(pspan + 8)))
+        at = _up8(doff + span + 4)
+    moves, operands = [m for m, _ in pairs], [o for _, o in pairs]
+    src = [front + ML.cells(m.extent, m.ss, m.src_off) for m in moves]
+    dst = [front + ML.cells(m.extent, m.ds, m.dst_off) for m in moves]
+    pcs = [front + ML.cells(m.extent, pstr, poff) for m, (poff, pstr) in pairs]
+    everything = np.concatenate(src + dst)
+    assert everything.min() >= front and np.unique(everything).size == everything.size
+    assert len({poff for poff, _ in operands}) == 8 and [m.peer for m in moves] == [0, 1] * 4
+    for side in (0, 1):
+        mine = np.concatenate([c for m, c in zip(moves, pcs) if m.peer == side])
+        assert mine.min() >= front and np.unique(mine).size == mine.size
+    rotated = [_rotated(a, b, i) for i in range(8)]
+    for negate, flags in itertools.product((False, True), (0, 1)):
+        init = _random_cells(dtype, int(everything.max()) + 1 - front, 20 + flags)
+        pinit = [_random_cells(dtype, max(int(c.max()) for c in pcs) + 1 - front, 30 + side) for side in (0, 1)]
+        for m, s, c, (x, y) in zip(moves, src, pcs, rotated):
+            init[s], pinit[m.peer][c] = x, y
+        exp = init.copy()
+        for d, (x, y) in zip(dst, rotated):
+            exp[d] = EA.expected_wall(dtype, x, y, negate)
+        dev, pdev = _upload(init), [_upload(x) for x in pinit]
+        ptrs = [dev.data_ptr() + SLACK, pdev[0].data_ptr() + SLACK, pdev[1].data_ptr() + SLACK]
+        mode = cd.MOVES_WALL_PLANE_NEGATE if negate else cd.MOVES_WALL_PLANE
+        described = cd.cudecompExtDescribeMoves(moves, ptrs, es, mode, dtype, flags, planes=operands)
+        launches, elements, total = cd.cudecompExtRunMoves(moves, ptrs, es, mode, dtype, None, flags, None,
+                                                           torch.cuda.current_stream().cuda_stream, planes=operands)
+        torch.cuda.synchronize()
+        name = cd.cudecompExtLastKernelName()
+        where = ("wall plane list", AB.NAMES[dtype], "negate %d flags %d" % (negate, flags), name)
+        assert total == len(described) == 1 and described[0]["n"] == 8 and sorted(described[0]["index"]) == list(range(8)), where + (described,)
+        assert sum(elements) == 8 * 576 and launches[2 if flags else 0] == 1, where + (launches, elements)
+        assert name == ("generic_wall_plane_kernel<%s,%d,%s>" % (t, es, TF[negate]) if flags else
+                        "rows_wall_plane_kernel<%s,16,0,%s>" % (t, TF[negate])), where
+        _compare(dtype, dev, exp, [(d, x, y) for d, (x, y) in zip(dst, rotated)], where)
+        for side in (0, 1):
+            assert np.array_equal(pdev[side].cpu().numpy().view(u).reshape(-1, nc), pinit[side]), where + ("plane %d was written" % side,)
+
+
+# ---- kernels_field_wall.hip -------------------------------------------------------------------------------------------------------
+def _field_wall_launch(dtype, extent, strides, mirrored, offsets, mirrors, addends, mask, side_list, force, seed=0):
+    """ONE call of cudecompExtRunWallFieldMoves over len(offsets) fields: all fields in one arena with slack around each, field f
+    at offsets[f] elements into its region, which holds a source and a destination block per side of `side_list` (0 low, 1 high):
+    one move per side, for every field.  mirrors[f]: (elements, nc), what field f's source cells hold, in the order of the move's
+    cells, on every side; addends[f][side]: (layers, nc), ghost layer k counted from the wall outward -- destination index extent
+    - 1 - k along the mirrored dim on the low side, k on the high side; bit f of `mask` flips the signs of field f's source.
+    Returns (kernel name, the launches cudecompExtDescribeWallFieldMoves lists)."""
+    import torch
+    u, nc, es = _format(dtype)
+    n_fields, layers = len(offsets), int(extent[mirrored])
+    signed, first = _mirrored(extent, strides, mirrored)
+    front = SLACK // es
+    part = ML.span(extent, strides) + 4
+    part += part & 1  # (even: 2-byte fields decide their alignment by their offsets alone)
+    region = max(offsets) + 2 * len(side_list) * part
+    region += -region % 16 + front  # a field's region and the slack in front of the next one
+    bases = [front + f * region + offsets[f] for f in range(n_fields)]
+    j = np.indices([int(e) for e in extent][::-1]).reshape(3, -1)[::-1][mirrored]  # index along the mirrored dim, in the cells' order
+    rng = np.random.default_rng([seed, 5])
+    raw = rng.integers(0, 256, (n_fields, 2, cd.MAX_WALL_HALO, es), dtype=np.uint8)  # (a side or layer no move has: never read)
+    moves, blocks = [], []
+    for i, side in enumerate(side_list):
+        m = cd.make_move(extent, signed, strides, src_off=2 * i * part + first, dst_off=(2 * i + 1) * part, src_buf=0, dst_buf=0)
+        m.peer = side
+        moves.append(m)
+        blocks.append((side, ML.cells(extent, signed, 2 * i * part + first), ML.cells(extent, strides, (2 * i + 1) * part)))
+    init = _random_cells(dtype, n_fields * region - front, seed)
+    for f in range(n_fields):
+        assert mirrors[f].shape == (j.size, nc) and layers <= cd.MAX_WALL_HALO
+        for side, src, dst in blocks:
+            both = bases[f] + np.concatenate([src, dst])
+            assert both.min() >= bases[f] and both.max() < (f + 1) * region
+            init[bases[f] + src] = mirrors[f]
+            assert addends[f][side].shape == (layers, nc)
+            raw[f, side, :layers] = np.ascontiguousarray(addends[f][side]).view(np.uint8).reshape(layers, es)
+    everything = np.concatenate([bases[f] + c for f in range(n_fields) for _, s, d in blocks for c in (s, d)])
+    assert np.unique(everything).size == everything.size
+    exp, held = init.copy(), []
+    for f in range(n_fields):
+        for side, src, dst in blocks:
+            per_cell = addends[f][side][(layers - 1 - j) if side == 0 else j]
+            exp[bases[f] + dst] = EA.expected_wall(dtype, mirrors[f], per_cell, bool((mask >> f) & 1))
+            held.append((bases[f] + dst, mirrors[f], per_cell))
+    dev = _upload(init)
+    ptrs = [dev.data_ptr() + bases[f] * es for f in range(n_fields)]
+    desc = cd.cudecompExtDescribeWallFieldMoves(moves, ptrs, dtype, raw.tobytes(), mask, force)
+    launches = cd.cudecompExtRunWallFieldMoves(moves, ptrs, dtype, raw.tobytes(), mask, force, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    name = cd.cudecompExtLastKernelName()
+    where = ("field wall", AB.NAMES[dtype], extent, strides, mirrored, offsets, "mask %#x sides %s force %d" % (mask, side_list, force), name)
+    assert launches == len(desc), where + (launches, desc)
+    _compare(dtype, dev, exp, held, where)
+    return name, desc
+
+
+def _table_entry(desc, es, u, index):
+    """entry `index` of the addend table of a described launch, as the reals' bit patterns"""
+    return desc["table"][index * es:(index + 1) * es].view(u)
+
+
+def _field_wall_pass(dtype, length, as_rows, seen):
+    """the launches of one row length with the layers as the row index (extent (length, 4, 1)) or as the plane index ((length, 3, 4),
+    mirrored dim 2): three fields of which the middle one flips its signs, six launches that walk the table x FORCES x one side and
+    both sides.  Every (mirror, addend) pair of reals must have met in every field and part of an element, on a single side and in
+    the SECOND move of a launch of two"""
+    u, nc, es = _format(dtype)
+    table = AB.edge_table(AB.kind_of(dtype))
+    pitch = length + 2 + (length & 1)
+    if as_rows:
+        extent, strides, mirrored = (length, LAYERS, 1), (1, pitch, pitch * LAYERS), 1
+    else:
+        extent, strides, mirrored = (length, 3, LAYERS), (1, pitch, pitch * 4), 2
+    k = np.indices(extent[::-1]).reshape(3, -1)[::-1]  # the cells' order: dim 0 fastest
+    i, r = k[0] + 7 * k[3 - mirrored], k[mirrored]  # (layers as planes: the three rows of a plane begin at different entries)
+    mirrors = [np.stack([table[(i + 25 * f + 5 * r + 11 * c) % 24] for c in range(nc)], axis=1) for f in range(3)]
+    met = {(f, c, second): set() for f in range(3) for c in range(nc) for second in (False, True)}
+    for q, force, side_list in itertools.product(range(6), FORCES, (None, (0, 1))):
+        side_list = (q & 1,) if side_list is None else side_list
+        which = 4 * q + np.arange(LAYERS)
+        second = 12 * (len(side_list) - 1)  # (the high side of a launch of both takes other entries than the low side)
+        addends = [[np.stack([table[(which + 13 * c + 7 * f + second * side) % 24] for c in range(nc)], axis=1) for side in (0, 1)]
+                   for f in range(3)]
+        name, desc = _field_wall_launch(dtype, extent, strides, mirrored, [0, 2, 4], mirrors, addends, 0b010, side_list, force, seed=q)
+        assert name.startswith("generic_fields_wall_kernel<" if force & 1 else "rows_fields_wall_kernel<") and len(desc) == 1, (name, force, desc)
+        seen.add(name)
+        for n, side in enumerate(side_list):
+            layer = (LAYERS - 1 - r) if side == 0 else r
+            for f, c in itertools.product(range(3), range(nc)):
+                if len(side_list) == 1 or n == 1:
+                    met[(f, c, n == 1)] |= set(zip(mirrors[f][:, c].tolist(), addends[f][side][layer, c].tolist()))
+        if nc == 2:
+            assert all((addends[f][side][:, 0] != addends[f][side][:, 1]).all() for f in range(3) for side in (0, 1))
+    # every (mirror, addend) pair of reals: in the flipped field (1) and in the others, in both parts of a complex element
+    assert all(len(m) == 576 for m in met.values()), {key: len(m) for key, m in met.items()}
+    if nc == 2:
+        assert all((m[:, 0] != m[:, 1]).all() for m in mirrors)
+
+
+@TYPES
+def test_field_wall_kernels_on_edge_values(dtype):
+    """every lane width of the type (WALL_LENGTHS), the layers as rows and as planes, three fields with per-field signs and addends,
+    one and two moves per launch; 32 fields that fill the addend table; for 2-byte elements one field at 2 mod 4, and addends at the
+    odd half-words of the table"""
+    u, nc, es = _format(dtype)
+    t = EA.KERNELS[dtype][0]
+    table = AB.edge_table(AB.kind_of(dtype))
+    assert LAYERS <= cd.MAX_WALL_HALO
+    seen = set()
+    for length in WALL_LENGTHS[es]:
+        for as_rows in (True, False):
+            _field_wall_pass(dtype, length, as_rows, seen)
+    assert seen == EA.field_wall_names(dtype), sorted(seen ^ EA.field_wall_names(dtype))
+    # 32 fields, one side, only field 31 flipped: for 16-byte elements 32 x 4 entries are the whole table
+    length = WALL_LENGTHS[es][0]
+    pitch = length + 2
+    k = np.indices((length, LAYERS, 1)[::-1]).reshape(3, -1)[::-1]
+    mirrors = [np.stack([table[(k[0] + 25 * f + 5 * k[1] + 11 * c) % 24] for c in range(nc)], axis=1) for f in range(32)]
+    for q, force in itertools.product(range(6), FORCES):
+        which = 4 * q + np.arange(LAYERS)
+        addends = [[np.stack([table[(which + 13 * c + 7 * f) % 24] for c in range(nc)], axis=1)] * 2 for f in range(32)]
+        side = q & 1
+        name, desc = _field_wall_launch(dtype, (length, LAYERS, 1), (1, pitch, pitch * LAYERS), 1, [2 * (f % 5) for f in range(32)], mirrors,
+                                        addends, 1 << 31, (side,), force, seed=11)
+        assert len(desc) == 1 and desc[0]["fields"] == 32, desc  # (one launch for every element size: 32 x 4 x 16 bytes fit)
+        last = (31 * LAYERS + LAYERS - 1)
+        assert es < 16 or (last + 1) * es == cd.WALL_FIELD_TABLE_BYTES
+        # the table holds destination layers: the last entry is field 31's outermost ghost layer on the high side, its innermost on the low
+        assert np.array_equal(_table_entry(desc[0], es, u, last), addends[31][side][LAYERS - 1 if side else 0])
+    if es == 2:  # ONE field at 2 mod 4: 2-byte lanes for the whole launch; three layers, so that field 1's entries begin at an odd half-word
+        k = np.indices((24, 3, 1)[::-1]).reshape(3, -1)[::-1]
+        mirrors = [table[(k[0] + 25 * f + 5 * k[1]) % 24].reshape(-1, 1) for f in range(3)]
+        for q, force in itertools.product(range(8), (0, 2)):
+            which = 3 * q + np.arange(3)
+            addends = [[table[(which + 7 * f + 12 * side) % 24].reshape(-1, 1) for side in (0, 1)] for f in range(3)]
+            side_list = (0, 1) if q & 1 else (1,)
+            name, desc = _field_wall_launch(dtype, (24, 3, 1), (1, 26, 26 * 3), 1, [0, 3, 4], mirrors, addends, 0b010, side_list, force, seed=12)
+            assert name == "rows_fields_wall_kernel<%s,2,%d>" % (t, force // 2), name
+            odd = 0
+            for n, side in enumerate(side_list):
+                for f, j in itertools.product(range(3), range(3)):
+                    index = (n * 3 + f) * 3 + j  # (move, field, destination layer), in elements of 2 bytes
+                    assert np.array_equal(_table_entry(desc[0], es, u, index), addends[f][side][2 - j if side == 0 else j])
+                    odd += (index * es) & 2 != 0
+            assert odd == (9 if len(side_list) == 2 else 4)  # (entries 1, 3, ... of 18 or of 9: each an edge value, each checked)
+
+
 # ---- dense bit patterns -----------------------------------------------------------------------------------------------------------
 DENSE = 1 << 16  # reals per launch
 
@@ -345,7 +634,7 @@ def _dense_shapes(nc):
     return n, (512, rows, 2), (1, 520, 520 * (rows + 1)), (1, 516, 516 * (rows + 2))
 
 
-@pytest.mark.parametrize("family", ["fold", "field_fold", "field_accumulate", "wall"])
+@pytest.mark.parametrize("family", ["fold", "field_fold", "field_accumulate", "wall", "wall_plane", "field_wall"])
 @TYPES
 def test_dense_bit_patterns(dtype, family):
     """2^16 reals per launch of uniformly random patterns, of nearly cancelling pairs and of subnormal operands, as one move of 512-
@@ -353,7 +642,10 @@ def test_dense_bit_patterns(dtype, family):
     accumulation takes) and sign-flipping (fold and field fold take; the field accumulation does not).  The field families give each
     of two fields half of the move's rows (the launch as a whole carries the 2^16 reals); of the field fold's two fields one flips its
     signs, the other one in the other half.  The wall takes the a side as the mirror and two elements of the b side as the addends
-    of its two layers.  The draws contain what they are for: tests/test_edge_arithmetic_table.py."""
+    of its two layers.  The wall plane takes the a side as the mirror and the b side as the plane, pair by pair, so every pair of
+    the draw is an addition.  The field wall gives each of two fields half of the rows, one flipped and the other not, swapped in
+    the second half, the addends of the two layers from the b side.  The draws contain what they are for:
+    tests/test_edge_arithmetic_table.py."""
     u, nc, es = _format(dtype)
     n, extent, ss, ds = _dense_shapes(nc)
     doff = _behind(0, ML.span(extent, ss))
@@ -367,6 +659,20 @@ def test_dense_bit_patterns(dtype, family):
                 addends = (b_flipped if flipped else b)[[3, n // 2 + 5]]
                 kernel = _wall(dtype, extent, ss, ds, 2, 0, doff, a, addends, int(flipped), flipped, force)
                 assert kernel.startswith("generic_wall_" if force & 1 else "rows_wall_kernel<%s,16,%d," % (EA.KERNELS[dtype][0], force // 2)), kernel
+            elif family == "wall_plane":  # the mirror is the a side, the plane the b side, pair by pair: every pair an addition
+                ps = (1, 528, 528 * (extent[1] + 3))
+                kernel, _, _ = _wall_plane(dtype, extent, ss, ds, ps, 1 if flipped else 2, 0, doff, 8, a, b_flipped if flipped else b, flipped,
+                                           int(flipped), force)
+                assert kernel.startswith("generic_wall_plane_" if force & 1 else "rows_wall_plane_kernel<%s," % EA.KERNELS[dtype][0]), kernel
+                assert force & 1 or kernel.endswith(",%d,%s>" % (force // 2, TF[flipped])), kernel
+            elif family == "field_wall":  # two fields, half of the rows each, one of them flipped; both planes of a field are layers
+                half = (extent[0], extent[1] // 2, extent[2])
+                mask = 0b01 if flipped else 0b10
+                mirrors = [a[f * (n // 2):(f + 1) * (n // 2)] for f in range(2)]
+                addends = [[(b_flipped if (mask >> f) & 1 else b)[[f * (n // 2) + 3 + side, f * (n // 2) + n // 4 + 5 + side]] for side in (0, 1)]
+                           for f in range(2)]
+                kernel, _ = _field_wall_launch(dtype, half, ss, 2, [0, 2], mirrors, addends, mask, (int(flipped),), force)
+                assert kernel.startswith("generic_fields_wall_" if force & 1 else "rows_fields_wall_kernel<%s,16,%d>" % (EA.KERNELS[dtype][0], force // 2)), kernel
             else:  # two fields, half of the draw each
                 half = (extent[0], extent[1] // 2, extent[2])
                 if family == "field_fold":  # the flipped field changes with the half, and takes b with its sign bits flipped
@@ -397,6 +703,22 @@ def test_comparison_can_fail_flip_order():
         assert told == int(EA.wrong_outside_nan(dtype, want, mutated).sum()) > 0, wrong.__name__
 
 
+def test_comparison_can_fail_wall_plane_flip():
+    """one sign-flipping wall-plane move of the bf16 pairs: right against EA.expected_wall, and WRONG -- in reals that are not NaN --
+    against the restatements that flip the plane entry instead of the mirror, or the sum (only the numpy side is mutated)"""
+    dtype = cd.BFLOAT16
+    a, b = EA.pairs(dtype)
+    ss, ds, ps = _plane_strides(96, 3)
+    doff = _up8(8 + ML.span((96, 3, 2), ss) + 4)
+    _, got, want = _wall_plane(dtype, (96, 3, 2), ss, ds, ps, 1, 8, doff, 16, a, b, True, 0, 0)
+    assert not AB.mismatches("bf16", got, want).any()
+    for wrong in (EA.flip_the_addend, EA.flip_after_the_addition):
+        _, got, mutated = _wall_plane(dtype, (96, 3, 2), ss, ds, ps, 1, 8, doff, 16, a, b, True, 0, 0, reference=wrong)
+        told = int(EA.wrong_outside_nan(dtype, got, mutated).sum())
+        print(wrong.__name__, "reals told apart:", told)
+        assert told == int(EA.wrong_outside_nan(dtype, want, mutated).sum()) > 0, wrong.__name__
+
+
 def test_comparison_can_fail_flush():
     """one fold of the fp16 pairs against the expected sums with their subnormals flushed to zero: the 30 subnormal results differ"""
     dtype = cd.HALF
@@ -414,11 +736,12 @@ PENCILS, ORDERS = EB.PENCILS, EB.ORDERS
 
 
 @pytest.mark.parametrize("layout", list(ORDERS))
-@pytest.mark.parametrize("call", ["fold", "fold_fields", "accumulate_fields"])
+@pytest.mark.parametrize("call", ["fold", "fold_fields", "accumulate_fields", "wall_values", "wall_fields", "wall_planes"])
 def test_public_calls_on_edge_valued_pencils(call, layout):
-    """cudecompAmdFoldHalos*, cudecompAmdFoldFieldHalos* and cudecompAmdAccumulateFieldHalos* on pencils whose every cell, ghost
-    cells included, walks the 576 pairs: whole buffers with their slack against the numpy restatements; no NaN or infinity of a
-    ghost cell lands anywhere but where the contract adds it"""
+    """cudecompAmdFoldHalos*, cudecompAmdFoldFieldHalos*, cudecompAmdAccumulateFieldHalos*, cudecompAmdSetWallHalos*,
+    cudecompAmdSetWallFieldHalos* and cudecompAmdSetWallPlaneHalos* on pencils whose every cell, ghost cells included, walks the 576
+    pairs (the wall planes too; the wall values are table entries): whole buffers with their slack against the numpy restatements; no
+    NaN or infinity of a ghost cell, a mirror cell, an addend or a plane lands anywhere but where the contract puts it"""
     out = run_ranks(1, "tests.edge_arithmetic_bodies", call, dict(PENCILS, mem_order=ORDERS[layout]), timeout=300, fresh=False)[0]
     assert out["failures"] == [], out["failures"][:10]
     assert out["launching"] > 0 and out["compared"] >= out["launching"], out
