@@ -177,6 +177,7 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtRunMirroredFieldMoves", "cudecompExtDescribeMirroredFieldMoves", "cudecompExtHaloPlanCount",
                "cudecompExtRunWallFieldMoves", "cudecompExtDescribeWallFieldMoves", "cudecompExtPlanHaloWallValueFields",
                "cudecompExtPlanHaloWallValues", "cudecompExtWall3D", "cudecompExtPlanHaloWallPlanes", "cudecompExtWallPlane3D",
+               "cudecompExtReduce3D", "cudecompExtDescribeReduce3D",
                "cudecompExtSyncEpochBegin", "cudecompExtSyncSignal",
                "cudecompExtSyncWait", "cudecompExtTagPages", "cudecompExtCheckPages", "cudecompExtChecksum"]
 MAX_FLAGS, FLAG_SCALE = 64, 16  # csrc/kernels.h: kMaxFlags, kFlagScale
@@ -208,6 +209,12 @@ AMD_WALL_VALUES_SYMBOLS = ["cudecompAmdSetWallHalosX", "cudecompAmdSetWallHalosY
 MAX_WALL_HALO = 8  # CUDECOMP_AMD_MAX_WALL_HALO
 # include/cudecomp_halo_wall_planes.h: wall planes (the reflection with an addend per cell of the ghost slab, read from device arrays)
 AMD_WALL_PLANES_SYMBOLS = ["cudecompAmdSetWallPlaneHalosX", "cudecompAmdSetWallPlaneHalosY", "cudecompAmdSetWallPlaneHalosZ"]
+# include/cudecomp_interior_reduce.h: interior reductions (sum, dot product, largest magnitude over the cells a rank owns)
+INTERIOR_REDUCE_SYMBOLS = ["cudecompAmdReduceInteriorWorkspaceBytes", "cudecompAmdReduceInteriorX", "cudecompAmdReduceInteriorY",
+                           "cudecompAmdReduceInteriorZ"]
+MAX_REDUCE_FIELDS = 32  # CUDECOMP_AMD_MAX_REDUCE_FIELDS
+REDUCE_SUM, REDUCE_DOT, REDUCE_MAX_ABS = 0, 1, 2  # CUDECOMP_AMD_REDUCE_*
+REDUCE_MAX_BLOCKS = 2048  # csrc/kernels_batch.h kReduceMaxBlocks: stage-one workgroups per field at most
 # include/cudecomp_halo_wall_value_fields.h: multi-field wall values (several pencils, a parity and addends per field)
 AMD_WALL_VALUE_FIELDS_SYMBOLS = ["cudecompAmdSetWallFieldHalosX", "cudecompAmdSetWallFieldHalosY", "cudecompAmdSetWallFieldHalosZ"]
 MAX_WALL_VALUE_FIELDS = 32  # CUDECOMP_AMD_MAX_WALL_VALUE_FIELDS
@@ -297,6 +304,12 @@ def lib():
                                                     C.POINTER(ExtPlaneOperand)]
         L.cudecompExtWallPlane3D.argtypes = [vp, vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32,
                                              pi32, vp]
+        L.cudecompAmdReduceInteriorWorkspaceBytes.argtypes = [i32, C.POINTER(i64)]
+        for name in INTERIOR_REDUCE_SYMBOLS[1:]:
+            getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), i32, i32, pf64, vp, i32, pi32, pi32, vp]
+        L.cudecompExtReduce3D.argtypes = [vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, vp, vp, i32, pi32, vp]
+        L.cudecompExtDescribeReduce3D.argtypes = [C.c_uint64, C.c_uint64, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, i32,
+                                                  C.POINTER(i64)]
         for name in AMD_FIELDS_SYMBOLS:  # (the update's arguments with the list of fields and its length in the place of `input`)
             getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         L.cudecompExtPlanHaloFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32,
@@ -595,6 +608,26 @@ def cudecompAmdSetWallPlaneHalos(axis, handle, gd, inp, dtype, parity, centering
     name = "cudecompAmdSetWallPlaneHalos" + "XYZ"[axis]
     _check(getattr(lib(), name)(handle, gd, inp, dtype, int(parity), int(centering), int(sides), planes_low or None, planes_high or None,
                                 _i3(halo_extents), _b3(halo_periods), dim, _i3(padding), stream), name)
+
+
+def cudecompAmdReduceInteriorWorkspaceBytes(n_fields):
+    """Bytes of device workspace a reduction of n_fields fields needs (cudecomp_interior_reduce.h)."""
+    out = C.c_int64()
+    _check(lib().cudecompAmdReduceInteriorWorkspaceBytes(int(n_fields), C.byref(out)), "cudecompAmdReduceInteriorWorkspaceBytes")
+    return out.value
+
+
+def cudecompAmdReduceInterior(axis, handle, gd, a, b, op, results, work, dtype, halo_extents, padding=None, stream=None, n_fields=None):
+    """cudecompAmdReduceInterior{X,Y,Z} (cudecomp_interior_reduce.h): `op` (REDUCE_SUM, REDUCE_DOT, REDUCE_MAX_ABS) over the interior
+    cells of every field of `a` (device addresses; `b` the second operands of a dot product, else None), two doubles per field into
+    the DEVICE array at `results`; `work` device memory of cudecompAmdReduceInteriorWorkspaceBytes(len(a)) bytes.  Arguments are
+    passed as they are: the library makes the checks (a list entry of 0 or None is a NULL entry)."""
+    name = "cudecompAmdReduceInterior" + "XYZ"[axis]
+    ptrs = lambda v: None if v is None else (C.c_void_p * max(len(v), 1))(*[x or None for x in v])
+    n = n_fields if n_fields is not None else (len(a) if a is not None else 0)
+    res = C.cast(C.c_void_p(results or None), C.POINTER(C.c_double))
+    _check(getattr(lib(), name)(handle, gd, ptrs(a), ptrs(b), int(n), int(op), res, work or None, dtype, _i3(halo_extents),
+                                _i3(padding), stream), name)
 
 
 def wall_plane_shape(info, dim, halo_extents):
@@ -1010,6 +1043,27 @@ def cudecompExtWallPlane3D(src, dst, plane, dtype, negate, extent, ss, ds, ps, f
     _check(lib().cudecompExtWallPlane3D(src, dst, plane, dtype, int(bool(negate)), a(extent), a(ss), a(ds), a(ps), int(force),
                                         C.byref(cls), stream), "cudecompExtWallPlane3D")
     return cls.value
+
+
+def cudecompExtReduce3D(a, b, dtype, op, extent, strides, readable_before, readable_after, work, results, force=0, stream=None):
+    """One box of one field through the reduction kernels (op over extent[3] cells at a + sum k_i * strides[i] elements; b the second
+    operand of a dot product, else None; results two doubles of device memory); returns the kernel class (0 rows, 2 element-wise,
+    -1 an empty box)."""
+    cls = C.c_int32(-1)
+    v = lambda x: (C.c_int64 * 3)(*[int(k) for k in x])
+    _check(lib().cudecompExtReduce3D(a, b or None, dtype, int(op), v(extent), v(strides), int(readable_before), int(readable_after),
+                                     work, results, int(force), C.byref(cls), stream), "cudecompExtReduce3D")
+    return cls.value
+
+
+def cudecompExtDescribeReduce3D(a_address, b_address, dtype, op, extent, strides, readable_before=0, readable_after=0, force=0):
+    """How cudecompExtReduce3D would run that box (no launch, no GPU): {kind, vec, blocks, read_lo, read_hi}, the last two the lowest
+    byte read and one past the highest, relative to a_address."""
+    out = (C.c_int64 * 5)()
+    v = lambda x: (C.c_int64 * 3)(*[int(k) for k in x])
+    _check(lib().cudecompExtDescribeReduce3D(int(a_address), int(b_address or 0), dtype, int(op), v(extent), v(strides),
+                                             int(readable_before), int(readable_after), int(force), out), "cudecompExtDescribeReduce3D")
+    return dict(zip(("kind", "vec", "blocks", "read_lo", "read_hi"), [int(x) for x in out]))
 
 
 def cudecompExtRotateWalk(nb, walk=-1):

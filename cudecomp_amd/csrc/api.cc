@@ -1032,6 +1032,82 @@ CD_DEFINE_HALO_WALL_PLANES(cudecompAmdSetWallPlaneHalosX, 0)
 CD_DEFINE_HALO_WALL_PLANES(cudecompAmdSetWallPlaneHalosY, 1)
 CD_DEFINE_HALO_WALL_PLANES(cudecompAmdSetWallPlaneHalosZ, 2)
 
+// cudecomp_interior_reduce.h: sum, dot product and largest magnitude over the cells the rank owns.  Local: the pencil from
+// makePencil, no halo plan, no periods.  Checks in the header's order, all on the host, before anything is launched.
+cudecompResult_t cudecompAmdReduceInteriorWorkspaceBytes(int32_t n_fields, int64_t* bytes) {
+  try {
+    if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_REDUCE_FIELDS) CD_INVALID_USAGE("n_fields argument out of range");
+    if (!bytes) CD_INVALID_USAGE("bytes argument cannot be null");
+    *bytes = reduceWorkspaceBytes(n_fields);
+  }
+  CD_API_CATCH()
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+static cudecompResult_t reduceInteriorEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, const void* const a[],
+                                            const void* const b[], int32_t n_fields, int32_t op, double* results, void* work,
+                                            cudecompDataType_t dtype, const int32_t halo_extents[], const int32_t padding[],
+                                            hipStream_t stream) {
+  try {
+    checkHandle(handle);
+    checkGridDesc(handle, grid_desc);
+    checkDataType(dtype);
+    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
+    const Pencil p = makePencil(grid_desc->shape, grid_desc->pidx, axis, halo_extents, padding);  // (negative halos, padding)
+    if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_REDUCE_FIELDS) CD_INVALID_USAGE("n_fields argument out of range");
+    if (op < CUDECOMP_AMD_REDUCE_SUM || op > CUDECOMP_AMD_REDUCE_MAX_ABS) CD_INVALID_USAGE("op argument out of range");
+    if (!a) CD_INVALID_USAGE("a argument cannot be null");
+    for (int32_t f = 0; f < n_fields; ++f)
+      if (!a[f]) CD_INVALID_USAGE("a argument cannot hold a null entry");
+    if (op == CUDECOMP_AMD_REDUCE_DOT) {
+      if (!b) CD_INVALID_USAGE("b argument cannot be null for a dot product");
+      for (int32_t f = 0; f < n_fields; ++f)
+        if (!b[f]) CD_INVALID_USAGE("b argument cannot hold a null entry");
+    }
+    if (!results) CD_INVALID_USAGE("results argument cannot be null");
+    if (reinterpret_cast<uintptr_t>(results) % 8 != 0) CD_INVALID_USAGE("results argument must be 8-byte aligned");
+    if (!work) CD_INVALID_USAGE("work argument cannot be null");
+    if (reinterpret_cast<uintptr_t>(work) % 8 != 0) CD_INVALID_USAGE("work argument must be 8-byte aligned");
+
+    ReduceRequest r;
+    r.a = a;
+    r.b = op == CUDECOMP_AMD_REDUCE_DOT ? b : nullptr;
+    r.n_fields = n_fields;
+    r.op = op;
+    r.es = elementSize(dtype);
+    r.arith = arithOf(dtype);
+    i64 stride = 1;
+    for (int i = 0; i < 3; ++i) {  // memory order: the interior is what is left of the shape without both halos and the padding
+      const int ga = p.order[i];
+      r.extent[i] = std::max<i64>((i64)p.shape[i] - 2 * (i64)p.halo[ga] - p.pad[ga], 0);
+      r.strides[i] = stride;
+      r.box_off += p.halo[ga] * stride;
+      stride *= p.shape[i];
+    }
+    if (p.size == 0) r.extent[0] = r.extent[1] = r.extent[2] = 0, r.box_off = 0;
+    r.readable_before = r.box_off * r.es;
+    i64 last = 0;
+    for (int i = 0; i < 3; ++i) last += (r.extent[i] - 1) * r.strides[i];
+    r.readable_after = r.extent[0] * r.extent[1] * r.extent[2] == 0 ? 0 : (p.size - r.box_off - last - 1) * (i64)r.es;
+    r.tuning = &handle->tuning;
+    ensureDevice(handle);
+    launchReduce(r, results, work, stream);
+  }
+  CD_API_CATCH()
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+#define CD_DEFINE_REDUCE_INTERIOR(NAME, AXIS)                                                                                  \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, const void* const a[], const void* const b[],  \
+                        int32_t n_fields, int32_t op, double* results, void* work, cudecompDataType_t dtype,                   \
+                        const int32_t halo_extents[], const int32_t padding[], hipStream_t stream) {                           \
+    return reduceInteriorEntry(AXIS, handle, grid_desc, a, b, n_fields, op, results, work, dtype, halo_extents, padding,       \
+                               stream);                                                                                        \
+  }
+CD_DEFINE_REDUCE_INTERIOR(cudecompAmdReduceInteriorX, 0)
+CD_DEFINE_REDUCE_INTERIOR(cudecompAmdReduceInteriorY, 1)
+CD_DEFINE_REDUCE_INTERIOR(cudecompAmdReduceInteriorZ, 2)
+
 // cudecomp_halo_fold.h: the ghost cells the reflection writes are added onto their mirror images
 #define CD_DEFINE_HALO_FOLD(NAME, AXIS)                                                                                     \
   cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,       \

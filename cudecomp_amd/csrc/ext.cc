@@ -836,6 +836,65 @@ cudecompResult_t cudecompExtWallPlane3D(const void* src, void* dst, const void* 
   });
 }
 
+// one box of one field through the reduction kernels (kernels.h launchReduce) / how it would run (planReduce)
+static ReduceRequest reduceRequestOf(const void* const* a, const void* const* b, cudecompDataType_t dtype, int32_t op,
+                                     const int64_t extent[3], const int64_t strides[3], int64_t readable_before,
+                                     int64_t readable_after, const KernelTuning* tuning) {
+  if (!extent || !strides) CD_INVALID_USAGE("null argument");
+  if (op < 0 || op > 2) CD_INVALID_USAGE("op must be 0 (sum), 1 (dot) or 2 (max-abs)");
+  if (readable_before < 0 || readable_after < 0) CD_INVALID_USAGE("readable_before and readable_after cannot be negative");
+  ReduceRequest r;
+  r.a = a;
+  r.b = b;
+  r.n_fields = 1;
+  r.op = op;
+  r.es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
+  r.arith = arithOf(dtype);
+  for (int i = 0; i < 3; ++i) {
+    if (extent[i] < 0 || strides[i] < 0) CD_INVALID_USAGE("extents and strides of a reduction cannot be negative");
+    r.extent[i] = extent[i];
+    r.strides[i] = strides[i];
+  }
+  r.readable_before = readable_before;
+  r.readable_after = readable_after;
+  r.tuning = tuning;
+  return r;
+}
+
+cudecompResult_t cudecompExtReduce3D(const void* a, const void* b, cudecompDataType_t dtype, int32_t op, const int64_t extent[3],
+                                     const int64_t strides[3], int64_t readable_before, int64_t readable_after, void* work,
+                                     double* results, int32_t force, int32_t* kernel_class, hipStream_t stream) {
+  return guarded([&] {
+    if (!a || !work || !results || (op == 1 && !b)) CD_INVALID_USAGE("null argument");
+    const KernelTuning t = tuningOfForce(force);
+    const ReduceRequest r = reduceRequestOf(&a, &b, dtype, op, extent, strides, readable_before, readable_after, &t);
+    KernelStats st;
+    launchReduce(r, results, work, stream, &st);
+    if (kernel_class) {
+      *kernel_class = -1;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
+        if (st.launches[c]) *kernel_class = c;
+    }
+  });
+}
+
+cudecompResult_t cudecompExtDescribeReduce3D(uint64_t a_address, uint64_t b_address, cudecompDataType_t dtype, int32_t op,
+                                             const int64_t extent[3], const int64_t strides[3], int64_t readable_before,
+                                             int64_t readable_after, int32_t force, int64_t out[5]) {
+  return guarded([&] {
+    if (!out) CD_INVALID_USAGE("null argument");
+    const void* const a = reinterpret_cast<const void*>(a_address);
+    const void* const b = reinterpret_cast<const void*>(b_address);
+    const KernelTuning t = tuningOfForce(force);
+    const ReducePlan p = planReduce(reduceRequestOf(&a, &b, dtype, op, extent, strides, readable_before, readable_after, &t));
+    out[0] = p.k.kind;
+    out[1] = p.k.vec;
+    out[2] = p.g.blocks;
+    out[3] = p.read_lo;
+    out[4] = p.read_hi;
+  });
+}
+
 cudecompResult_t cudecompExtPlanHaloWallPlanes(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                                const bool periods[], int32_t dim, const int32_t pad[], cudecompDataType_t dtype,
                                                int32_t parity, int32_t centering, int32_t sides, uint64_t pencil_address,

@@ -748,6 +748,8 @@ void spellKernelName(const KernelChoice& k) {
       break;
     case K_ROWS_FIELDS_WALL: snprintf(out, n, "rows_fields_wall_kernel<%s,%d,%d>", arithName(k.arith), k.vec, s); break;
     case K_GENERIC_FIELDS_WALL: snprintf(out, n, "generic_fields_wall_kernel<%s,%d>", arithName(k.arith), k.es); break;
+    case K_ROWS_REDUCE:
+    case K_GENERIC_REDUCE: break;  // (launchReduce spells them: the operation is no part of the record)
   }
 }
 
@@ -840,6 +842,8 @@ void launchBatch(const Launch& l, const Move3D* moves, const void* fill_value, c
     case K_GENERIC_FIELDS_FOLD_TAKE:
     case K_ROWS_FIELDS_WALL:
     case K_GENERIC_FIELDS_WALL: CD_INTERNAL_ERROR("lists of field-moves are launched by launchFieldMoveList and launchFieldWallList");
+    case K_ROWS_REDUCE:
+    case K_GENERIC_REDUCE: CD_INTERNAL_ERROR("reductions are launched by launchReduce");
   }
 }
 
@@ -1291,6 +1295,145 @@ void launchFieldMoveList(const FieldMoveList& list, hipStream_t stream, KernelSt
       else launchFieldMoveBatch(l.k, l.b, l.blocks, stream);
     });
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// reductions of a box of cells (kernels_reduce.hip)
+// ---------------------------------------------------------------------------------------------
+ReducePlan planReduce(const ReduceRequest& r) {
+  if (r.n_fields < 1 || r.n_fields > kMaxFields || !r.a) CD_INTERNAL_ERROR("a reduction of 1 .. kMaxFields fields");
+  if (r.op != kReduceSum && r.op != kReduceDot && r.op != kReduceMaxAbs) CD_INTERNAL_ERROR("reduction operation out of range");
+  if (r.op == kReduceDot && !r.b) CD_INTERNAL_ERROR("a dot product without its second operands");
+  if (r.arith == ARITH_NONE) CD_INTERNAL_ERROR("a reduction needs the real type of its elements");
+  const int es = r.es, rs = arithBytes(r.arith);
+  if (es != rs && es != 2 * rs) CD_INTERNAL_ERROR("element size does not match the real type");
+  if (r.box_off < 0 || r.readable_before < 0 || r.readable_after < 0) CD_INTERNAL_ERROR("negative offset of a reduction");
+  const KernelTuning& tuning = r.tuning ? *r.tuning : kDefaultTuning;
+  ReducePlan p;
+  std::memset(&p, 0, sizeof(p));
+  p.k.es = es;
+  p.k.arith = r.arith;
+  ReduceGeom& g = p.g;
+  g.reals = es / rs;
+  g.n_fields = r.n_fields;
+  g.box_off = r.box_off * es;
+  i64 cells = 1, last = 0;  // `last`: the element offset of the box's last cell
+  for (int i = 0; i < 3; ++i) {
+    if (r.extent[i] < 0 || r.strides[i] < 0) CD_INTERNAL_ERROR("negative extent or stride of a reduction");
+    cells *= r.extent[i];
+    last += (r.extent[i] - 1) * r.strides[i];
+    g.e[i] = r.extent[i];
+    g.s[i] = r.strides[i];
+  }
+  const i64 span = (last + 1) * es;
+  g.rd_lo = -r.readable_before;
+  g.rd_hi = span + r.readable_after;
+  p.k.kind = K_GENERIC_REDUCE;
+  p.k.vec = es;
+  if (cells == 0) return p;  // (no stage one: g.blocks == 0)
+  p.k.access = ((cells * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming) ? 1 : 0;
+
+  // the dims that count, by stride; contiguous ones merged
+  i64 e[3] = {1, 1, 1}, s[3] = {0, 0, 0};
+  int nd = 0, unit = -1;  // `unit`: a dim of stride 1 that is one cell long is still the row (a pencil one cell thick along its fastest axis)
+  for (int i = 0; i < 3; ++i) {
+    if (r.extent[i] > 1) e[nd] = r.extent[i], s[nd] = r.strides[i], ++nd;
+    else if (r.strides[i] == 1) unit = i;
+  }
+  for (int i = 0; i < nd; ++i)
+    for (int j = i + 1; j < nd; ++j)
+      if (s[j] < s[i]) std::swap(s[i], s[j]), std::swap(e[i], e[j]);
+  if (nd > 0 && nd < 3 && s[0] != 1 && unit >= 0) {  // rows of one cell
+    for (int i = nd; i > 0; --i) e[i] = e[i - 1], s[i] = s[i - 1];
+    e[0] = 1, s[0] = 1, ++nd;
+  }
+  bool rows = nd == 0 || s[0] == 1;
+  if (nd == 0) s[0] = 1;
+  while (rows && nd >= 2 && s[1] == e[0]) {  // the next dim follows without a gap: one longer row
+    e[0] *= e[1];
+    e[1] = e[2], s[1] = s[2];
+    e[2] = 1, s[2] = 0;
+    --nd;
+  }
+  if (rows && nd == 3 && s[2] == e[1] * s[1]) e[1] *= e[2], e[2] = 1, s[2] = 0, --nd;
+  // the row kernel's lanes lie on the 16-byte grid of `a`: every field on a boundary of its real type; the second operand of a
+  // DOT at the same phase of that grid; a complex DOT pairs real and imaginary part inside one vector
+  for (int f = 0; f < r.n_fields && rows; ++f) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(r.a[f]);
+    if (a % (uintptr_t)rs != 0) rows = false;
+    if (r.op == kReduceDot) {
+      const uintptr_t b = reinterpret_cast<uintptr_t>(r.b[f]);
+      if ((a & 15) != (b & 15)) rows = false;
+      if (g.reals == 2 && a % (uintptr_t)es != 0) rows = false;
+    }
+  }
+  if (tuning.force_class == MOVE_GENERIC) rows = false;
+
+  if (!rows) {
+    g.p0 = 0;
+    for (int i = 0; i < 3; ++i)
+      if (r.strides[i] == 1 && r.extent[i] > 1) g.p0 = i;
+    const i64 want = (cells + kThreads - 1) / kThreads;
+    g.blocks = (unsigned int)std::min<i64>(std::max<i64>(want, 1), kReduceMaxBlocks);
+    p.read_lo = 0;
+    p.read_hi = span;
+    return p;
+  }
+
+  p.k.kind = K_ROWS_REDUCE;
+  p.k.vec = 16;
+  g.stream = p.k.access;
+  g.row_bytes = g.last_row_bytes = e[0] * es;
+  g.rows = e[1], g.planes = e[2];
+  g.s1 = s[1] * es, g.s2 = s[2] * es;
+  if (nd <= 1 && g.row_bytes > kReduceChunkBytes) {  // one long row: rows of kReduceChunkBytes, the last one what is left
+    g.rows = (g.row_bytes + kReduceChunkBytes - 1) / kReduceChunkBytes;
+    g.last_row_bytes = g.row_bytes - (g.rows - 1) * kReduceChunkBytes;
+    g.row_bytes = g.s1 = kReduceChunkBytes;
+  }
+  g.slots = (g.row_bytes + 14 + 15) / 16;
+  g.p0 = std::min(8, ilog2ceil(g.slots));
+  const i64 lpr = 1LL << g.p0, rows_per_tile = (i64)(kThreads >> g.p0) * kRowsUnroll;
+  const i64 t0 = (g.slots + lpr - 1) / lpr, t1 = (g.rows + rows_per_tile - 1) / rows_per_tile;
+  if (t0 > 0xffffffffLL || t1 > 0xffffffffLL) CD_NOT_SUPPORTED("a reduction of more than 2^32 - 1 tiles along one dim");
+  g.t0 = (unsigned int)t0, g.t1 = (unsigned int)t1;
+  g.tiles = (unsigned long long)t0 * (unsigned long long)t1 * (unsigned long long)g.planes;
+  g.blocks = (unsigned int)std::min<unsigned long long>(g.tiles, kReduceMaxBlocks);
+  // what field 0 reads: whole 16-byte vectors from the boundary below the first cell to the boundary above the last, where the
+  // readable range holds them; the cells alone where it does not
+  const uintptr_t first_cell = reinterpret_cast<uintptr_t>(r.a[0]) + (uintptr_t)g.box_off;
+  const i64 below = (i64)(first_cell & 15), above = (i64)((16 - ((first_cell + (uintptr_t)span) & 15)) & 15);
+  const auto whole = [&](i64 slot) { return slot >= g.rd_lo && slot + 16 <= g.rd_hi; };  // (the kernel's test of a vector)
+  p.read_lo = whole(-below) ? -below : 0;
+  p.read_hi = whole(span + above - 16) ? span + above : span;
+  return p;
+}
+
+void launchReduce(const ReduceRequest& r, double* results, void* work, hipStream_t stream, KernelStats* stats) {
+  const ReducePlan p = planReduce(r);
+  if (p.g.blocks > 0) {
+    ReduceFields fields;
+    std::memset(&fields, 0, sizeof(fields));
+    for (int f = 0; f < r.n_fields; ++f) {
+      fields.a[f] = static_cast<const char*>(r.a[f]);
+      if (r.op == kReduceDot) fields.b[f] = static_cast<const char*>(r.b[f]);
+    }
+    if (p.k.kind == K_ROWS_REDUCE)
+      snprintf(g_last_kernel, sizeof(g_last_kernel), "reduce_rows_kernel<%s,%d>", arithName(p.k.arith), r.op);
+    else
+      snprintf(g_last_kernel, sizeof(g_last_kernel), "reduce_elements_kernel<%s,%d>", arithName(p.k.arith), r.op);
+    ++g_data_launches;
+    launchReduceStageOne(p.k, r.op, p.g, fields, static_cast<double*>(work), stream);
+    if (stats) {
+      const MoveClass cls = classOf(p.k.kind);
+      stats->launches[cls] += 1;
+      stats->elements[cls] += (i64)r.n_fields * r.extent[0] * r.extent[1] * r.extent[2];
+    }
+  } else {
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "reduce_final_kernel<%d>", r.op);
+  }
+  ++g_data_launches;
+  launchReduceFinal(r.op, r.n_fields, p.g.blocks, results, static_cast<const double*>(work), stream);
 }
 
 }  // namespace cudecomp

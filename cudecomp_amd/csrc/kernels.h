@@ -184,7 +184,40 @@ std::vector<FieldWallLaunch> planFieldWallLaunches(const FieldMoveList& list);
 // Launch the list, asynchronous on `stream`: planFieldMoveLaunches' launches, or planFieldWallLaunches' for a wall list.
 void launchFieldMoveList(const FieldMoveList& list, hipStream_t stream, KernelStats* stats = nullptr);
 
-// data-movement launches this process has made so far (launchMoves and launchFieldMoveList; tests count launches per call with it)
+// ---- reductions of a box of cells (kernels_reduce.hip; include/cudecomp_interior_reduce.h) --------------------------------------
+// The request: the same box of `es`-byte elements of every field a[f] (and b[f], DOT only), reduced to two doubles per field.
+// Buffers are only looked at as addresses by the planner.
+struct ReduceRequest {
+  const void* const* a = nullptr;  // n_fields (1 .. kern::kMaxFields) fields, no null entry
+  const void* const* b = nullptr;  // DOT: the second operands, b[f] == a[f] allowed; not read otherwise
+  int n_fields = 0;
+  int op = 0;                      // kern::kReduceSum, kReduceDot, kReduceMaxAbs
+  int es = 0;                      // element size in bytes
+  ArithType arith = ARITH_NONE;    // the real type the elements consist of (one or two of them)
+  i64 extent[3] = {0, 0, 0};       // the box, in elements; strides non-negative
+  i64 strides[3] = {0, 0, 0};
+  i64 box_off = 0;                 // elements from a field's pointer to the first cell of the box
+  // what may be read: the bytes [-readable_before, span + readable_after) around the box, span = the bytes from its first cell to
+  // the end of its last; the same for every field
+  i64 readable_before = 0, readable_after = 0;
+  const KernelTuning* tuning = nullptr;  // force_class == MOVE_GENERIC the element-wise kernel; force_streaming, no_streaming
+};
+// HOW a request runs (pure host code, no device needed).  Rows -- lanes on the 16-byte grid of memory -- when the box has a
+// contiguous dim, every field sits on a boundary of its real type, DOT operands share their phase on the 16-byte grid and complex DOT
+// fields sit on element boundaries; element by element otherwise.  Contiguous dims are merged first (rowVectors' rule for copies),
+// and a box that is one long row is cut into rows of kern::kReduceChunkBytes.  Non-temporal loads from kStreamBytes per field on.
+struct ReducePlan {
+  KernelChoice k;       // kind K_ROWS_REDUCE / K_GENERIC_REDUCE; vec = bytes per lane (16 / one element); access 0, 1
+  kern::ReduceGeom g;   // g.blocks: stage-one workgroups per field, 0 for an empty box
+  i64 read_lo, read_hi; // lowest byte read and one past the highest, relative to the first cell of field 0's box (0, 0: empty box)
+};
+ReducePlan planReduce(const ReduceRequest& r);
+// Launch it, asynchronous on `stream`: stage one (unless the box is empty) into `work` (reduceWorkspaceBytes(n_fields) bytes of
+// device memory), stage two into results[0 .. 2 * n_fields).  Nothing is allocated, nothing waits.
+void launchReduce(const ReduceRequest& r, double* results, void* work, hipStream_t stream, KernelStats* stats = nullptr);
+inline i64 reduceWorkspaceBytes(int n_fields) { return (i64)n_fields * kern::kReduceMaxBlocks * 2 * (i64)sizeof(double); }
+
+// data-movement launches this process has made so far (launchMoves, launchFieldMoveList and both stages of launchReduce; tests count launches per call with it)
 long long dataLaunchCount();
 
 // name (template spelling) of the data-movement kernel launched last by this process, "" before the first launch

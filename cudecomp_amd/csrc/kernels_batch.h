@@ -2,7 +2,7 @@
 // kernel choice (KernelChoice), the launch descriptor (Batch) and the launchers.  The code objects the classifier dispatches
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip, kernels_wall.hip, kernels_wall_plane.hip;
-// kernels_rotate.hip and sync.hip are launched by the executor (and compiled as one unit, kernels_executor.hip; kernels_fill.hip and kernels_reflect.hip likewise as kernels_edge.hip,
+// kernels_rotate.hip and sync.hip are launched by the executor (and compiled as one unit, kernels_executor.hip; kernels_fill.hip, kernels_reflect.hip and kernels_reduce.hip -- the reductions of a box, launchReduce -- likewise as kernels_edge.hip,
 // kernels_accumulate.hip and kernels_take.hip as kernels_sum.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
 // halo phases and transposes), kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) and
 // kernels_field_mirror.hip (the same lists mirrored, with a sign per field: multi-field wall halos) are reached through
@@ -154,6 +154,36 @@ struct FieldWallWalk {
 static_assert(sizeof(FieldMoveBatch) + sizeof(FieldWallTable) + sizeof(FieldWallWalk) + 16 + 8 <= 4096,
               "FieldMoveBatch, addend table, walk, sign mask and the mask of fields stay under the 4 KB of kernel arguments");
 
+// ---- reductions of a box of cells (kernels_reduce.hip; interior reductions, include/cudecomp_interior_reduce.h) ------------------
+// Stage one writes one pair of fp64 partials per workgroup, field f's at work[2 * (f * kReduceMaxBlocks + workgroup)]; stage two
+// combines a field's pairs.  kReduceMaxBlocks caps the workgroups per field, whatever the box: the workspace depends on the number of
+// fields alone (kMaxFields * kReduceMaxBlocks * 16 bytes = 1 MiB at most), and eight workgroups per CU of an MI355X are in flight.
+constexpr int kReduceSum = 0, kReduceDot = 1, kReduceMaxAbs = 2;  // CUDECOMP_AMD_REDUCE_*
+constexpr int kReduceMaxBlocks = 2048;
+// a single row longer than this is cut into rows of this many bytes: a multiple of every element size, and one short of 4 KiB so that
+// a cut row touches at most 256 slots of the 16-byte grid -- one tile column -- whatever its phase on that grid
+constexpr long long kReduceChunkBytes = 4080;
+struct ReduceGeom {
+  // rows: bytes; the last row of every plane may be shorter (a cut row).  element-wise: unused
+  long long row_bytes, last_row_bytes, rows, planes, s1, s2;
+  long long slots;             // rows: 16-byte slots a row can touch at most
+  unsigned long long tiles;    // rows: t0 * t1 * planes
+  unsigned int t0, t1;         // rows: tile columns / tile rows per plane
+  long long e[3], s[3];        // element-wise: extents and strides in ELEMENTS
+  long long box_off;           // bytes from a field's pointer to the first cell of the box
+  long long rd_lo, rd_hi;      // rows: the bytes [rd_lo, rd_hi) relative to the first cell of the box may be read
+  int p0;                      // rows: log2 of the lanes per row; element-wise: the dim the lanes run along
+  int reals;                   // reals per element: 1, or 2 for the complex types
+  int n_fields;
+  int stream;                  // rows: 1 non-temporal loads (KernelChoice::access), 0 default caching
+  unsigned int blocks;         // workgroups PER FIELD, at most kReduceMaxBlocks
+};
+struct ReduceFields {
+  const char* a[kMaxFields];
+  const char* b[kMaxFields];  // DOT only
+};
+static_assert(sizeof(ReduceGeom) + sizeof(ReduceFields) + 8 <= 2048, "geometry, the two tables of fields and the workspace stay well under the 4 KB of kernel arguments");
+
 }  // namespace kern
 
 // ---- what runs: one record per kernel choice ----------------------------------------------------------------------------------
@@ -201,7 +231,9 @@ enum KernelKind {
   K_ROWS_FIELDS_WALL,         // rows_fields_wall_kernel (dst = +-src per field + the field's addend of the destination layer) = 39
   K_GENERIC_FIELDS_WALL,      // generic_fields_wall_kernel = 40
   K_ROWS_WALL_PLANE,          // rows_wall_plane_kernel (dst = +-src + the plane entry of the destination cell, the source backwards along the row or plane index) = 41
-  K_GENERIC_WALL_PLANE        // generic_wall_plane_kernel = 42
+  K_GENERIC_WALL_PLANE,       // generic_wall_plane_kernel = 42
+  K_ROWS_REDUCE,              // reduce_rows_kernel (a box of cells to two fp64 partials per workgroup; no destination) = 43
+  K_GENERIC_REDUCE            // reduce_elements_kernel = 44
 };
 struct KernelChoice {
   KernelKind kind;
@@ -212,6 +244,7 @@ struct KernelChoice {
                     // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads;
                     // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it);
                     // reflections and wall-moves: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores;
+                    // reductions: 0, 1 non-temporal loads;
                     // field-moves: 0, 1 non-temporal loads and stores; transpose_fields_kernel: 0, 2; adding / taking
                     // field-moves: as additions / takes; mirrored field-moves: as reflections / folds; wall field-moves: as reflections
   ArithType arith;  // additions, folds, wall-moves, reflections that flip the sign bits, mirrored field-moves (whatever their signs):
@@ -296,12 +329,14 @@ constexpr KindTraits kKindTraits[] = {
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_FIELDS_WALL
     {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_WALL_PLANE
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_WALL_PLANE
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_REDUCE
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_REDUCE
 };
-static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_WALL_PLANE + 1, "one row per KernelKind");
+static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_REDUCE + 1, "one row per KernelKind");
 
 // the row of a kind; a value outside the enum is an internal error, never a read past the table
 inline const KindTraits& kindTraits(KernelKind kind) {
-  if (kind < K_ROWS || kind > K_GENERIC_WALL_PLANE) CD_INTERNAL_ERROR("kernel kind out of range");
+  if (kind < K_ROWS || kind > K_GENERIC_REDUCE) CD_INTERNAL_ERROR("kernel kind out of range");
   return kKindTraits[kind];
 }
 inline MoveClass classOf(KernelKind kind) { return kindTraits(kind).cls; }
@@ -401,6 +436,12 @@ void launchFieldMirrorBatch(const KernelChoice& k, const kern::FieldMoveBatch& b
 // first; `table` and `walk` as above.  Lanes never narrower than one element.  Local buffers only.
 void launchFieldWallBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, unsigned int fields_neg, const kern::FieldWallTable& table,
                           const kern::FieldWallWalk& walk, unsigned int blocks, hipStream_t stream);
+// kernels_reduce.hip (in the unit kernels_edge.hip): reductions of a box of cells.  Stage one: k.kind K_ROWS_REDUCE or K_GENERIC_REDUCE,
+// k.arith the real type, `op` one of kern::kReduce*; g.blocks * g.n_fields workgroups, each writing its pair of partials to `work`.
+// Stage two: one workgroup per field combines `partials` pairs (0: an empty box) and writes results[2f], results[2f + 1].
+void launchReduceStageOne(const KernelChoice& k, int op, const kern::ReduceGeom& g, const kern::ReduceFields& fields, double* work,
+                          hipStream_t stream);
+void launchReduceFinal(int op, int n_fields, unsigned int partials, double* results, const double* work, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

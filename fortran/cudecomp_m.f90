@@ -124,6 +124,9 @@ module cudecomp
     enumerator :: CUDECOMP_FLOAT_COMPLEX = -3
     enumerator :: CUDECOMP_DOUBLE_COMPLEX = -4
   end enum
+  ! cudecomp_interior_reduce.h: the operations of cudecompAmdReduceInterior{X,Y,Z}, and the most fields a call takes
+  integer(c_int32_t), parameter :: CUDECOMP_AMD_REDUCE_SUM = 0, CUDECOMP_AMD_REDUCE_DOT = 1, CUDECOMP_AMD_REDUCE_MAX_ABS = 2
+  integer(c_int32_t), parameter :: CUDECOMP_AMD_MAX_REDUCE_FIELDS = 32
   enum, bind(c)
     enumerator :: CUDECOMP_RESULT_SUCCESS = 0
     enumerator :: CUDECOMP_RESULT_INVALID_USAGE = 1
@@ -697,6 +700,59 @@ module cudecomp
       integer(c_intptr_t), value :: stream
       integer(c_int) :: res
     end function cudecompAmdSetWallPlaneHalosZ_C
+
+    ! cudecomp_interior_reduce.h: sum, dot product and largest magnitude over the cells a rank owns.  Plain bind(c) interfaces: `a`
+    ! and `b` are arrays of n_fields device addresses (b: c_null_ptr entries are refused for a dot product only), `results` and
+    ! `work` device addresses, `op` one of CUDECOMP_AMD_REDUCE_SUM / _DOT / _MAX_ABS
+    function cudecompAmdReduceInteriorWorkspaceBytes(n_fields, bytes) &
+      bind(C, name="cudecompAmdReduceInteriorWorkspaceBytes") result(res)
+      import
+      integer(c_int32_t), value :: n_fields
+      integer(c_int64_t) :: bytes
+      integer(c_int) :: res
+    end function cudecompAmdReduceInteriorWorkspaceBytes
+
+    function cudecompAmdReduceInteriorX(handle, grid_desc, a, b, n_fields, op, results, work, dtype, halo_extents, padding, stream) &
+      bind(C, name="cudecompAmdReduceInteriorX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: a(*), b(*)
+      integer(c_int32_t), value :: n_fields, op
+      type(c_ptr), value :: results, work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3), padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdReduceInteriorX
+
+    function cudecompAmdReduceInteriorY(handle, grid_desc, a, b, n_fields, op, results, work, dtype, halo_extents, padding, stream) &
+      bind(C, name="cudecompAmdReduceInteriorY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: a(*), b(*)
+      integer(c_int32_t), value :: n_fields, op
+      type(c_ptr), value :: results, work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3), padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdReduceInteriorY
+
+    function cudecompAmdReduceInteriorZ(handle, grid_desc, a, b, n_fields, op, results, work, dtype, halo_extents, padding, stream) &
+      bind(C, name="cudecompAmdReduceInteriorZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: a(*), b(*)
+      integer(c_int32_t), value :: n_fields, op
+      type(c_ptr), value :: results, work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3), padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdReduceInteriorZ
 
     ! cudecomp_halo_wall_value_fields.h: wall values of several pencils, each with a parity and addends of its own
     function cudecompAmdSetWallFieldHalosX_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, sides, values_low, &

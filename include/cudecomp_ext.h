@@ -595,8 +595,27 @@ cudecompResult_t cudecompExtDescribeFieldMoveList(const cudecompExtMove_t* moves
                                                   cudecompExtFieldMoveLaunch_t* launches, int32_t max_launches,
                                                   int32_t* n_launches);
 
-/* Data-movement kernel launches this process has made so far through the kernel layer (launchMoves and
- * launchFieldMoveList; the signal / wait kernels and the copy-engine copies of the transports are not counted -- the chunk copies the
+/* One box of one field through the reduction kernels of cudecompAmdReduceInterior{X,Y,Z} (cudecomp_interior_reduce.h; csrc/kernels.h
+ * launchReduce, kernels_reduce.hip): extent[3] cells of `dtype` at a + sum k_i * strides[i] elements (strides non-negative), reduced
+ * by op (0 sum, 1 dot with the same cells of b, 2 max-abs) to results[0], results[1] (device memory; the header's table).  The
+ * kernels may read the bytes [a - readable_before, a + span + readable_after), span = the bytes from the box's first cell to the end
+ * of its last, and nothing else; the same around b.  `work`: device memory of cudecompAmdReduceInteriorWorkspaceBytes(1) bytes.
+ * force: bit 0 the element-wise kernel, bit 1 non-temporal loads regardless of the size, bit 2 never.  *kernel_class (optional): 0
+ * rows, 2 element-wise, -1 no stage-one launch (an empty box).
+ *
+ * cudecompExtDescribeReduce3D answers how that call would run, without a device and without a launch: the same arguments with
+ * addresses as integers.  out[5] = {kind (csrc/kernels_batch.h KernelKind: 43 reduce_rows_kernel, 44 reduce_elements_kernel), bytes
+ * per lane (16 / one element), stage-one workgroups (at most 2048; 0 for an empty box), read_lo, read_hi}: the lowest byte read and
+ * one past the highest, relative to a. */
+cudecompResult_t cudecompExtReduce3D(const void* a, const void* b, cudecompDataType_t dtype, int32_t op, const int64_t extent[3],
+                                     const int64_t strides[3], int64_t readable_before, int64_t readable_after, void* work,
+                                     double* results, int32_t force, int32_t* kernel_class, hipStream_t stream);
+cudecompResult_t cudecompExtDescribeReduce3D(uint64_t a_address, uint64_t b_address, cudecompDataType_t dtype, int32_t op,
+                                             const int64_t extent[3], const int64_t strides[3], int64_t readable_before,
+                                             int64_t readable_after, int32_t force, int64_t out[5]);
+
+/* Data-movement kernel launches this process has made so far through the kernel layer (launchMoves,
+ * launchFieldMoveList and both stages of launchReduce; the signal / wait kernels and the copy-engine copies of the transports are not counted -- the chunk copies the
  * one-sided transport makes with the row-copy kernel between ranks that share a GPU go through launchMoves and are).  Tests take
  * the difference around a call. */
 cudecompResult_t cudecompExtDataLaunchCount(int64_t* launches);

@@ -1,0 +1,113 @@
+"""Interior reductions (cudecomp_interior_reduce.h: cudecompAmdReduceInterior{X,Y,Z}) on the GPU: both stage-one kernels box by box
+inside NaN poison over every row length, pitch and phase of the 16-byte grid; more tiles than workgroups and more partials than
+stage two has lanes; ghost cells and padding that never reach a result; single-rank pencils of every axis, memory order, halo width,
+padding and data type; several fields against their single-field calls; accuracy against an exactly rounded reference, held to the
+derived bound; IEEE edge values; an empty interior; four ranks on a ragged 2 x 2 grid whose results add up to a closed form; capture
+into a hipGraph with the field changed between replays; asynchrony.  Integer data wherever the comparison is bit for bit
+(tests/interior_reduce_bodies.py says why that holds for any order of the additions).  Every body runs on launched ranks."""
+import numpy as np
+import pytest
+
+import cudecomp_amd as cd
+from tests import accumulate_bodies as AB
+from tests import interior_reduce_bodies as RB
+from tests.mp import run_ranks
+
+pytestmark = pytest.mark.gpu
+
+BODIES = "tests.interior_reduce_bodies"
+
+
+@pytest.mark.parametrize("dtype", AB.ALL_TYPES, ids=[AB.NAMES[t] for t in AB.ALL_TYPES])
+def test_kernel_parity(dtype):
+    assert run_ranks(1, BODIES, "kernel_parity", {"dtype": dtype}, timeout=300)[0] == []
+
+
+def test_more_tiles_than_workgroups_and_more_partials_than_lanes():
+    assert run_ranks(1, BODIES, "workgroups_and_partials", {}, timeout=300)[0] == []
+
+
+def test_ghost_cells_and_padding_never_reach_a_result():
+    args = {"gdims": (13, 10, 11), "pdims": (1, 1), "halo": (2, 1, 3), "padding": (1, 2, 0)}
+    assert run_ranks(1, BODIES, "ghost_independence", args, timeout=300)[0] == []
+
+
+def test_single_rank_sweep():
+    args = {"shapes": [(13, 10, 11), (5, 6, 7)], "halos": [(0, 0, 0), (1, 1, 1), (2, 1, 3)], "paddings": [(0, 0, 0), (1, 2, 0)]}
+    assert run_ranks(1, BODIES, "single_rank_sweep", args, timeout=300)[0] == []
+
+
+def test_a_field_of_a_multi_field_call_equals_its_single_field_call():
+    args = {"gdims": (13, 10, 11), "pdims": (1, 1), "halo": (1, 2, 1), "padding": (0, 1, 0)}
+    assert run_ranks(1, BODIES, "multi_field", args, timeout=300)[0] == []
+
+
+def test_accuracy_within_the_derived_bound():
+    """|got - exact| <= n * 2^-53 * sum |term|: every term enters n - 1 additions at most, each with a relative error of 2^-53 at
+    most (and an fp64 product one more); the reference is exactly rounded and adds 2^-53 of the sum itself, far inside"""
+    res = run_ranks(1, BODIES, "accuracy", {"gdims": (50, 48, 44), "pdims": (1, 1), "halo": (1, 1, 1)}, timeout=300)[0]
+    print("\n".join(res["figures"]))
+    assert res["failures"] == [], res
+
+
+def test_edge_values():
+    args = {"gdims": (13, 10, 11), "pdims": (1, 1), "halo": (1, 0, 2), "padding": (0, 1, 0)}
+    assert run_ranks(1, BODIES, "edge_values", args, timeout=300)[0] == []
+
+
+def _combine(per_rank, gdims):
+    """the ranks' results of every case against the closed form over the whole grid: sums add up, maxima are the maximum"""
+    wa, wb = RB.closed_form(gdims)
+    checked = 0
+    for key in per_rank[0][1]:
+        op = int(key.split()[-1])
+        dtype = per_rank[0][1][key][1]
+        nc = AB.TYPES[dtype][1]
+        ia = np.stack([wa, wb] if nc == 2 else [wa], axis=-1).reshape(-1, nc)
+        ib = np.stack([wb, wa] if nc == 2 else [wb], axis=-1).reshape(-1, nc)
+        want = np.concatenate([RB.reference(op, ia, ib), RB.reference(op, ib, ia)])
+        parts = np.array([r[1][key][0] for r in per_rank])
+        got = parts.max(axis=0) if op == cd.REDUCE_MAX_ABS else parts.sum(axis=0)  # (integers: exact in any order)
+        assert RB.same_bits(got + 0.0, want), (key, parts.tolist(), want.tolist())
+        assert sum(r[1][key][2] for r in per_rank) == int(np.prod(gdims)), key  # the interiors partition the grid
+        checked += 1
+    return checked
+
+
+def test_four_ranks_ragged_grid():
+    """2 x 2 ranks, gdims (10, 9, 11): slabs of 5 + 5, 5 + 4 and 6 + 5 cells.  Every rank's results are numpy's over its slab, and
+    the results of the four add up to the closed form over the whole grid, exactly."""
+    args = {"gdims": (10, 9, 11), "pdims": (2, 2), "halo_backend": cd.HALO_COMM_MPI, "halos": [(1, 1, 1), (2, 0, 3)]}
+    per_rank = run_ranks(4, BODIES, "ranks_sweep", args, timeout=300, fresh=False)
+    for failures, _ in per_rank:
+        assert failures == []
+    assert _combine(per_rank, args["gdims"]) == 3 * 2 * 3
+
+
+def test_a_rank_that_owns_nothing_gets_zeros():
+    """a 1 x 4 grid over 3 cells: the last rank's pencils of axes 0 and 1 have no interior.  Its results are +0.0, and written."""
+    args = {"gdims": (8, 6, 3), "pdims": (1, 4), "halo_backend": cd.HALO_COMM_MPI, "halos": [(1, 1, 1)], "dtype": cd.DOUBLE}
+    per_rank = run_ranks(4, BODIES, "ranks_sweep", args, timeout=300, fresh=False)
+    for failures, _ in per_rank:
+        assert failures == []
+    empty = [key for key, (got, _, cells) in per_rank[3][1].items() if cells == 0]
+    assert len(empty) >= 3, per_rank[3][1]
+    for key in empty:
+        assert RB.same_bits(per_rank[3][1][key][0], [0.0] * 4), (key, per_rank[3][1][key])
+    assert _combine(per_rank, args["gdims"]) == 3 * 1 * 3
+
+
+def test_a_replayed_graph_equals_an_eager_call():
+    for args in ({"gdims": (40, 36, 30), "pdims": (1, 1), "halo": (1, 2, 1), "padding": (0, 1, 0)},
+                 {"gdims": (33, 20, 27), "pdims": (1, 1), "mem_order": ((1, 2, 0),) * 3, "axis": 1, "halo": (2, 1, 2),
+                  "dtype": cd.FLOAT_COMPLEX, "op": cd.REDUCE_SUM}):
+        assert run_ranks(1, BODIES, "graph_replay", args, timeout=300)[0] == []
+
+
+def test_calls_return_before_the_gpu_is_done():
+    """100 kernels over 1 GiB each are enqueued first; the three calls return while they run"""
+    args = {"gdims": (64, 48, 40), "pdims": (1, 1), "halo": (1, 1, 1)}
+    res = run_ranks(1, BODIES, "returns_before_the_gpu_is_done", args, timeout=300)[0]
+    assert res["failures"] == [], res
+    assert res["pending_after_the_calls"], res
+    assert res["host_ms"] < 0.25 * res["total_ms"], res
