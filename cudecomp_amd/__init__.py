@@ -177,7 +177,7 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtRunMirroredFieldMoves", "cudecompExtDescribeMirroredFieldMoves", "cudecompExtHaloPlanCount",
                "cudecompExtRunWallFieldMoves", "cudecompExtDescribeWallFieldMoves", "cudecompExtPlanHaloWallValueFields",
                "cudecompExtPlanHaloWallValues", "cudecompExtWall3D", "cudecompExtPlanHaloWallPlanes", "cudecompExtWallPlane3D",
-               "cudecompExtReduce3D", "cudecompExtDescribeReduce3D",
+               "cudecompExtReduce3D", "cudecompExtDescribeReduce3D", "cudecompExtProfile3D", "cudecompExtDescribeProfile3D",
                "cudecompExtSyncEpochBegin", "cudecompExtSyncSignal",
                "cudecompExtSyncWait", "cudecompExtTagPages", "cudecompExtCheckPages", "cudecompExtChecksum"]
 MAX_FLAGS, FLAG_SCALE = 64, 16  # csrc/kernels.h: kMaxFlags, kFlagScale
@@ -215,6 +215,11 @@ INTERIOR_REDUCE_SYMBOLS = ["cudecompAmdReduceInteriorWorkspaceBytes", "cudecompA
 MAX_REDUCE_FIELDS = 32  # CUDECOMP_AMD_MAX_REDUCE_FIELDS
 REDUCE_SUM, REDUCE_DOT, REDUCE_MAX_ABS = 0, 1, 2  # CUDECOMP_AMD_REDUCE_*
 REDUCE_MAX_BLOCKS = 2048  # csrc/kernels_batch.h kReduceMaxBlocks: stage-one workgroups per field at most
+# include/cudecomp_interior_profile.h: interior profiles (the same reductions over two dims of the interior, kept along the third)
+INTERIOR_PROFILE_SYMBOLS = ["cudecompAmdProfileInteriorWorkspaceBytes", "cudecompAmdProfileInteriorX", "cudecompAmdProfileInteriorY",
+                            "cudecompAmdProfileInteriorZ"]
+PROFILE_PAIRS_PER_FIELD = 65536  # csrc/kernels_batch.h kProfilePairsPerField: pairs of partials per field the workspace holds at least
+PROFILE_MAX_PARTS = 1024  # csrc/kernels_batch.h kProfileMaxParts: parts per entry at most
 # include/cudecomp_halo_wall_value_fields.h: multi-field wall values (several pencils, a parity and addends per field)
 AMD_WALL_VALUE_FIELDS_SYMBOLS = ["cudecompAmdSetWallFieldHalosX", "cudecompAmdSetWallFieldHalosY", "cudecompAmdSetWallFieldHalosZ"]
 MAX_WALL_VALUE_FIELDS = 32  # CUDECOMP_AMD_MAX_WALL_VALUE_FIELDS
@@ -308,6 +313,12 @@ def lib():
         for name in INTERIOR_REDUCE_SYMBOLS[1:]:
             getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), i32, i32, pf64, vp, i32, pi32, pi32, vp]
         L.cudecompExtReduce3D.argtypes = [vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, vp, vp, i32, pi32, vp]
+        L.cudecompAmdProfileInteriorWorkspaceBytes.argtypes = [i32, i64, C.POINTER(i64)]
+        for name in INTERIOR_PROFILE_SYMBOLS[1:]:
+            getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), i32, i32, i32, pf64, i64, vp, i32, pi32, pi32, vp]
+        L.cudecompExtProfile3D.argtypes = [vp, vp, i32, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, vp, vp, i64, i32, pi32, vp]
+        L.cudecompExtDescribeProfile3D.argtypes = [C.c_uint64, C.c_uint64, i32, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, i32,
+                                                   C.POINTER(i64)]
         L.cudecompExtDescribeReduce3D.argtypes = [C.c_uint64, C.c_uint64, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, i32,
                                                   C.POINTER(i64)]
         for name in AMD_FIELDS_SYMBOLS:  # (the update's arguments with the list of fields and its length in the place of `input`)
@@ -628,6 +639,28 @@ def cudecompAmdReduceInterior(axis, handle, gd, a, b, op, results, work, dtype, 
     res = C.cast(C.c_void_p(results or None), C.POINTER(C.c_double))
     _check(getattr(lib(), name)(handle, gd, ptrs(a), ptrs(b), int(n), int(op), res, work or None, dtype, _i3(halo_extents),
                                 _i3(padding), stream), name)
+
+
+def cudecompAmdProfileInteriorWorkspaceBytes(n_fields, length):
+    """Bytes of device workspace a profile of `length` entries of n_fields fields needs (cudecomp_interior_profile.h)."""
+    out = C.c_int64()
+    _check(lib().cudecompAmdProfileInteriorWorkspaceBytes(int(n_fields), int(length), C.byref(out)),
+           "cudecompAmdProfileInteriorWorkspaceBytes")
+    return out.value
+
+
+def cudecompAmdProfileInterior(axis, handle, gd, a, b, op, dim, results, ld, work, dtype, halo_extents, padding=None, stream=None,
+                               n_fields=None):
+    """cudecompAmdProfileInterior{X,Y,Z} (cudecomp_interior_profile.h): `op` over the interior cells of every field of `a` (device
+    addresses; `b` the second operands of a dot product, else None), reduced over two dims and kept along the global dim `dim`: field
+    f, entry k to the two doubles at results[2 * (f * ld + k)] of the DEVICE array at `results`; `work` device memory of
+    cudecompAmdProfileInteriorWorkspaceBytes(len(a), L) bytes.  Arguments are passed as they are: the library makes the checks."""
+    name = "cudecompAmdProfileInterior" + "XYZ"[axis]
+    ptrs = lambda v: None if v is None else (C.c_void_p * max(len(v), 1))(*[x or None for x in v])
+    n = n_fields if n_fields is not None else (len(a) if a is not None else 0)
+    res = C.cast(C.c_void_p(results or None), C.POINTER(C.c_double))
+    _check(getattr(lib(), name)(handle, gd, ptrs(a), ptrs(b), int(n), int(op), int(dim), res, int(ld), work or None, dtype,
+                                _i3(halo_extents), _i3(padding), stream), name)
 
 
 def wall_plane_shape(info, dim, halo_extents):
@@ -1064,6 +1097,30 @@ def cudecompExtDescribeReduce3D(a_address, b_address, dtype, op, extent, strides
     _check(lib().cudecompExtDescribeReduce3D(int(a_address), int(b_address or 0), dtype, int(op), v(extent), v(strides),
                                              int(readable_before), int(readable_after), int(force), out), "cudecompExtDescribeReduce3D")
     return dict(zip(("kind", "vec", "blocks", "read_lo", "read_hi"), [int(x) for x in out]))
+
+
+def cudecompExtProfile3D(a, b, dtype, op, keep, extent, strides, readable_before, readable_after, work, results, ld, force=0,
+                         stream=None):
+    """One box of one field through the profile kernels (cudecompExtReduce3D's box, reduced over two dims and kept along
+    extent[keep]; results extent[keep] pairs of doubles of device memory, ld >= extent[keep]); returns the kernel class (0 rows or
+    columns, 2 element-wise, -1 no stage one)."""
+    cls = C.c_int32(-1)
+    v = lambda x: (C.c_int64 * 3)(*[int(k) for k in x])
+    _check(lib().cudecompExtProfile3D(a, b or None, dtype, int(op), int(keep), v(extent), v(strides), int(readable_before),
+                                      int(readable_after), work, results, int(ld), int(force), C.byref(cls), stream),
+           "cudecompExtProfile3D")
+    return cls.value
+
+
+def cudecompExtDescribeProfile3D(a_address, b_address, dtype, op, keep, extent, strides, readable_before=0, readable_after=0, force=0):
+    """How cudecompExtProfile3D would run that box (no launch, no GPU): {kind, vec, blocks, read_lo, read_hi, parts, entries,
+    final_lanes}; read_lo / read_hi the lowest byte read and one past the highest, relative to a_address."""
+    out = (C.c_int64 * 8)()
+    v = lambda x: (C.c_int64 * 3)(*[int(k) for k in x])
+    _check(lib().cudecompExtDescribeProfile3D(int(a_address), int(b_address or 0), dtype, int(op), int(keep), v(extent), v(strides),
+                                              int(readable_before), int(readable_after), int(force), out),
+           "cudecompExtDescribeProfile3D")
+    return dict(zip(("kind", "vec", "blocks", "read_lo", "read_hi", "parts", "entries", "final_lanes"), [int(x) for x in out]))
 
 
 def cudecompExtRotateWalk(nb, walk=-1):

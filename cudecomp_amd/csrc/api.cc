@@ -1108,6 +1108,86 @@ CD_DEFINE_REDUCE_INTERIOR(cudecompAmdReduceInteriorX, 0)
 CD_DEFINE_REDUCE_INTERIOR(cudecompAmdReduceInteriorY, 1)
 CD_DEFINE_REDUCE_INTERIOR(cudecompAmdReduceInteriorZ, 2)
 
+// cudecomp_interior_profile.h: the reductions of cudecomp_interior_reduce.h over two dims of the interior, kept along the third.
+// Local: the pencil from makePencil, the memory position of `dim` from its order.  Checks in the header's order, on the host.
+cudecompResult_t cudecompAmdProfileInteriorWorkspaceBytes(int32_t n_fields, int64_t length, int64_t* bytes) {
+  try {
+    if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_REDUCE_FIELDS) CD_INVALID_USAGE("n_fields argument out of range");
+    if (length < 0) CD_INVALID_USAGE("length argument cannot be negative");
+    if (!bytes) CD_INVALID_USAGE("bytes argument cannot be null");
+    *bytes = profileWorkspaceBytes(n_fields, length);
+  }
+  CD_API_CATCH()
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+static cudecompResult_t profileInteriorEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, const void* const a[],
+                                             const void* const b[], int32_t n_fields, int32_t op, int32_t dim, double* results,
+                                             int64_t ld, void* work, cudecompDataType_t dtype, const int32_t halo_extents[],
+                                             const int32_t padding[], hipStream_t stream) {
+  try {
+    checkHandle(handle);
+    checkGridDesc(handle, grid_desc);
+    checkDataType(dtype);
+    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
+    const Pencil p = makePencil(grid_desc->shape, grid_desc->pidx, axis, halo_extents, padding);  // (negative halos, padding)
+    if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_REDUCE_FIELDS) CD_INVALID_USAGE("n_fields argument out of range");
+    if (op < CUDECOMP_AMD_REDUCE_SUM || op > CUDECOMP_AMD_REDUCE_MAX_ABS) CD_INVALID_USAGE("op argument out of range");
+    if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
+    if (!a) CD_INVALID_USAGE("a argument cannot be null");
+    for (int32_t f = 0; f < n_fields; ++f)
+      if (!a[f]) CD_INVALID_USAGE("a argument cannot hold a null entry");
+    if (op == CUDECOMP_AMD_REDUCE_DOT) {
+      if (!b) CD_INVALID_USAGE("b argument cannot be null for a dot product");
+      for (int32_t f = 0; f < n_fields; ++f)
+        if (!b[f]) CD_INVALID_USAGE("b argument cannot hold a null entry");
+    }
+    if (!results) CD_INVALID_USAGE("results argument cannot be null");
+    if (reinterpret_cast<uintptr_t>(results) % 8 != 0) CD_INVALID_USAGE("results argument must be 8-byte aligned");
+
+    ProfileRequest r;
+    r.a = a;
+    r.b = op == CUDECOMP_AMD_REDUCE_DOT ? b : nullptr;
+    r.n_fields = n_fields;
+    r.op = op;
+    r.es = elementSize(dtype);
+    r.arith = arithOf(dtype);
+    i64 stride = 1;
+    for (int i = 0; i < 3; ++i) {  // memory order: the interior is what is left of the shape without both halos and the padding
+      const int ga = p.order[i];
+      if (ga == dim) r.keep = i;
+      r.extent[i] = std::max<i64>((i64)p.shape[i] - 2 * (i64)p.halo[ga] - p.pad[ga], 0);
+      r.strides[i] = stride;
+      r.box_off += p.halo[ga] * stride;
+      stride *= p.shape[i];
+    }
+    if (p.size == 0) r.box_off = 0;  // (some extent is 0: nothing is read; the extent along dim may still be positive -- zeros)
+    if (ld < r.extent[r.keep]) CD_INVALID_USAGE("ld argument is smaller than the interior extent along dim");
+    if (!work) CD_INVALID_USAGE("work argument cannot be null");
+    if (reinterpret_cast<uintptr_t>(work) % 8 != 0) CD_INVALID_USAGE("work argument must be 8-byte aligned");
+    r.readable_before = r.box_off * r.es;
+    i64 last = 0;
+    for (int i = 0; i < 3; ++i) last += (r.extent[i] - 1) * r.strides[i];
+    r.readable_after = r.extent[0] * r.extent[1] * r.extent[2] == 0 ? 0 : (p.size - r.box_off - last - 1) * (i64)r.es;
+    r.tuning = &handle->tuning;
+    ensureDevice(handle);
+    launchProfile(r, results, ld, work, stream);
+  }
+  CD_API_CATCH()
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+#define CD_DEFINE_PROFILE_INTERIOR(NAME, AXIS)                                                                                 \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, const void* const a[], const void* const b[],  \
+                        int32_t n_fields, int32_t op, int32_t dim, double* results, int64_t ld, void* work,                    \
+                        cudecompDataType_t dtype, const int32_t halo_extents[], const int32_t padding[], hipStream_t stream) { \
+    return profileInteriorEntry(AXIS, handle, grid_desc, a, b, n_fields, op, dim, results, ld, work, dtype, halo_extents,      \
+                                padding, stream);                                                                              \
+  }
+CD_DEFINE_PROFILE_INTERIOR(cudecompAmdProfileInteriorX, 0)
+CD_DEFINE_PROFILE_INTERIOR(cudecompAmdProfileInteriorY, 1)
+CD_DEFINE_PROFILE_INTERIOR(cudecompAmdProfileInteriorZ, 2)
+
 // cudecomp_halo_fold.h: the ghost cells the reflection writes are added onto their mirror images
 #define CD_DEFINE_HALO_FOLD(NAME, AXIS)                                                                                     \
   cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,       \

@@ -895,6 +895,72 @@ cudecompResult_t cudecompExtDescribeReduce3D(uint64_t a_address, uint64_t b_addr
   });
 }
 
+// one box of one field through the profile kernels (kernels.h launchProfile) / how it would run (planProfile)
+static ProfileRequest profileRequestOf(const void* const* a, const void* const* b, cudecompDataType_t dtype, int32_t op, int32_t keep,
+                                       const int64_t extent[3], const int64_t strides[3], int64_t readable_before,
+                                       int64_t readable_after, const KernelTuning* tuning) {
+  if (!extent || !strides) CD_INVALID_USAGE("null argument");
+  if (op < 0 || op > 2) CD_INVALID_USAGE("op must be 0 (sum), 1 (dot) or 2 (max-abs)");
+  if (keep < 0 || keep > 2) CD_INVALID_USAGE("keep must be 0, 1 or 2");
+  if (readable_before < 0 || readable_after < 0) CD_INVALID_USAGE("readable_before and readable_after cannot be negative");
+  ProfileRequest r;
+  r.a = a;
+  r.b = b;
+  r.n_fields = 1;
+  r.op = op;
+  r.keep = keep;
+  r.es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
+  r.arith = arithOf(dtype);
+  for (int i = 0; i < 3; ++i) {
+    if (extent[i] < 0 || strides[i] < 0) CD_INVALID_USAGE("extents and strides of a profile cannot be negative");
+    r.extent[i] = extent[i];
+    r.strides[i] = strides[i];
+  }
+  r.readable_before = readable_before;
+  r.readable_after = readable_after;
+  r.tuning = tuning;
+  return r;
+}
+
+cudecompResult_t cudecompExtProfile3D(const void* a, const void* b, cudecompDataType_t dtype, int32_t op, int32_t keep,
+                                      const int64_t extent[3], const int64_t strides[3], int64_t readable_before,
+                                      int64_t readable_after, void* work, double* results, int64_t ld, int32_t force,
+                                      int32_t* kernel_class, hipStream_t stream) {
+  return guarded([&] {
+    if (!a || !work || !results || (op == 1 && !b)) CD_INVALID_USAGE("null argument");
+    const KernelTuning t = tuningOfForce(force);
+    const ProfileRequest r = profileRequestOf(&a, &b, dtype, op, keep, extent, strides, readable_before, readable_after, &t);
+    if (ld < r.extent[keep]) CD_INVALID_USAGE("ld is smaller than the kept extent");
+    KernelStats st;
+    launchProfile(r, results, ld, work, stream, &st);
+    if (kernel_class) {
+      *kernel_class = -1;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
+        if (st.launches[c]) *kernel_class = c;
+    }
+  });
+}
+
+cudecompResult_t cudecompExtDescribeProfile3D(uint64_t a_address, uint64_t b_address, cudecompDataType_t dtype, int32_t op,
+                                              int32_t keep, const int64_t extent[3], const int64_t strides[3],
+                                              int64_t readable_before, int64_t readable_after, int32_t force, int64_t out[8]) {
+  return guarded([&] {
+    if (!out) CD_INVALID_USAGE("null argument");
+    const void* const a = reinterpret_cast<const void*>(a_address);
+    const void* const b = reinterpret_cast<const void*>(b_address);
+    const KernelTuning t = tuningOfForce(force);
+    const ProfilePlan p = planProfile(profileRequestOf(&a, &b, dtype, op, keep, extent, strides, readable_before, readable_after, &t));
+    out[0] = p.k.kind;
+    out[1] = p.k.vec;
+    out[2] = p.blocks;
+    out[3] = p.read_lo;
+    out[4] = p.read_hi;
+    out[5] = p.g.parts;
+    out[6] = p.g.L;
+    out[7] = p.g.parts ? 1LL << p.g.final_lanes_log2 : 0;
+  });
+}
+
 cudecompResult_t cudecompExtPlanHaloWallPlanes(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                                const bool periods[], int32_t dim, const int32_t pad[], cudecompDataType_t dtype,
                                                int32_t parity, int32_t centering, int32_t sides, uint64_t pencil_address,

@@ -750,6 +750,9 @@ void spellKernelName(const KernelChoice& k) {
     case K_GENERIC_FIELDS_WALL: snprintf(out, n, "generic_fields_wall_kernel<%s,%d>", arithName(k.arith), k.es); break;
     case K_ROWS_REDUCE:
     case K_GENERIC_REDUCE: break;  // (launchReduce spells them: the operation is no part of the record)
+    case K_ROWS_PROFILE:
+    case K_COLUMNS_PROFILE:
+    case K_GENERIC_PROFILE: break;  // (launchProfile likewise)
   }
 }
 
@@ -844,6 +847,9 @@ void launchBatch(const Launch& l, const Move3D* moves, const void* fill_value, c
     case K_GENERIC_FIELDS_WALL: CD_INTERNAL_ERROR("lists of field-moves are launched by launchFieldMoveList and launchFieldWallList");
     case K_ROWS_REDUCE:
     case K_GENERIC_REDUCE: CD_INTERNAL_ERROR("reductions are launched by launchReduce");
+    case K_ROWS_PROFILE:
+    case K_COLUMNS_PROFILE:
+    case K_GENERIC_PROFILE: CD_INTERNAL_ERROR("profiles are launched by launchProfile");
   }
 }
 
@@ -1434,6 +1440,153 @@ void launchReduce(const ReduceRequest& r, double* results, void* work, hipStream
   }
   ++g_data_launches;
   launchReduceFinal(r.op, r.n_fields, p.g.blocks, results, static_cast<const double*>(work), stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// profiles of a box of cells along one dim (kernels_profile.hip)
+// ---------------------------------------------------------------------------------------------
+ProfilePlan planProfile(const ProfileRequest& r) {
+  if (r.n_fields < 1 || r.n_fields > kMaxFields || !r.a) CD_INTERNAL_ERROR("a profile of 1 .. kMaxFields fields");
+  if (r.op != kReduceSum && r.op != kReduceDot && r.op != kReduceMaxAbs) CD_INTERNAL_ERROR("reduction operation out of range");
+  if (r.op == kReduceDot && !r.b) CD_INTERNAL_ERROR("a dot product without its second operands");
+  if (r.arith == ARITH_NONE) CD_INTERNAL_ERROR("a profile needs the real type of its elements");
+  if (r.keep < 0 || r.keep > 2) CD_INTERNAL_ERROR("the kept dim of a profile is 0, 1 or 2");
+  const int es = r.es, rs = arithBytes(r.arith);
+  if (es != rs && es != 2 * rs) CD_INTERNAL_ERROR("element size does not match the real type");
+  if (r.box_off < 0 || r.readable_before < 0 || r.readable_after < 0) CD_INTERNAL_ERROR("negative offset of a profile");
+  const KernelTuning& tuning = r.tuning ? *r.tuning : kDefaultTuning;
+  ProfilePlan p;
+  std::memset(&p, 0, sizeof(p));
+  p.k.kind = K_GENERIC_PROFILE;
+  p.k.es = es;
+  p.k.vec = es;
+  p.k.arith = r.arith;
+  ProfileGeom& g = p.g;
+  g.reals = es / rs;
+  g.n_fields = r.n_fields;
+  g.box_off = r.box_off * es;
+  i64 cells = 1, last = 0;  // `last`: the element offset of the box's last cell
+  for (int i = 0; i < 3; ++i) {
+    if (r.extent[i] < 0 || r.strides[i] < 0) CD_INTERNAL_ERROR("negative extent or stride of a profile");
+    cells *= r.extent[i];
+    last += (r.extent[i] - 1) * r.strides[i];
+  }
+  const i64 L = r.extent[r.keep];
+  g.L = L;
+  if (cells == 0) return p;  // (no stage one: g.parts == 0)
+  if (L > 0x7fffffffLL) CD_NOT_SUPPORTED("a profile of more than 2^31 - 1 entries");
+  const i64 span = (last + 1) * es;
+  g.rd_lo = -r.readable_before;
+  g.rd_hi = span + r.readable_after;
+  p.k.access = ((cells * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming) ? 1 : 0;
+  g.stream = p.k.access;
+  // parts per entry: what the workspace holds at most, and no more than fills the device -- about kProfileBlocks workgroups per field
+  const i64 cap = std::min<i64>(std::max<i64>(kProfilePairsPerField / L, 1), kProfileMaxParts);
+  const i64 per_entry = std::min<i64>(cap, std::max<i64>(kProfileBlocks / L, 1));
+
+  // the two reduced dims, the one of the smaller stride first (a dim of one cell has no stride that counts)
+  int o1 = (r.keep + 1) % 3, o2 = (r.keep + 2) % 3;
+  const auto pitch = [&](int d) { return r.extent[d] > 1 ? r.strides[d] : 0; };
+  if (r.extent[o2] > 1 && (r.extent[o1] == 1 || r.strides[o2] < r.strides[o1])) std::swap(o1, o2);
+  int c = -1;  // the contiguous dim
+  for (int i = 0; i < 3; ++i)
+    if (r.strides[i] == 1 && (c < 0 || (r.extent[c] == 1 && r.extent[i] > 1))) c = i;
+  // lanes on the 16-byte grid of `a`: planReduce's rules
+  bool fast = c >= 0 && tuning.force_class != MOVE_GENERIC;
+  for (int f = 0; f < r.n_fields && fast; ++f) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(r.a[f]);
+    if (a % (uintptr_t)rs != 0) fast = false;
+    if (r.op == kReduceDot) {
+      const uintptr_t b = reinterpret_cast<uintptr_t>(r.b[f]);
+      if ((a & 15) != (b & 15)) fast = false;
+      if (g.reals == 2 && a % (uintptr_t)es != 0) fast = false;
+    }
+  }
+  const i64 plane_cells = r.extent[o1] * r.extent[o2];
+  // the column form: every row of the box at one phase of the 16-byte grid
+  if (fast && c == r.keep && ((pitch(o1) * es) % 16 != 0 || (pitch(o2) * es) % 16 != 0 || plane_cells > 0x7fffffffLL)) fast = false;
+
+  if (!fast) {
+    g.e1 = r.extent[o1], g.e2 = r.extent[o2];
+    g.s1 = pitch(o1) * es, g.s2 = pitch(o2) * es;
+    g.sk = r.strides[r.keep] * es;
+    g.parts = (unsigned int)std::min<i64>(per_entry, (plane_cells + kThreads - 1) / kThreads);
+    p.blocks = L * g.parts;
+    p.read_lo = 0;
+    p.read_hi = span;
+  } else {
+    p.k.vec = 16;
+    if (c != r.keep) {
+      const int o = 3 - c - r.keep;
+      p.k.kind = K_ROWS_PROFILE;
+      g.row_bytes = r.extent[c] * es;
+      g.rows = r.extent[o];
+      g.s1 = pitch(o) * es;
+      g.sk = r.strides[r.keep] * es;
+      g.slots = (g.row_bytes + 14 + 15) / 16;
+      g.p0 = std::min(8, ilog2ceil(g.slots));
+      const i64 lpr = 1LL << g.p0, rows_per_tile = (i64)(kThreads >> g.p0) * kRowsUnroll;
+      const i64 t0 = (g.slots + lpr - 1) / lpr, t1 = (g.rows + rows_per_tile - 1) / rows_per_tile;
+      if (t0 > 0xffffffffLL || t1 > 0xffffffffLL) CD_NOT_SUPPORTED("a profile of more than 2^32 - 1 tiles along one dim");
+      g.t0 = (unsigned int)t0, g.t1 = (unsigned int)t1;
+      g.parts = (unsigned int)std::min<i64>(per_entry, t0 * t1);
+      p.blocks = L * g.parts;
+    } else {
+      p.k.kind = K_COLUMNS_PROFILE;
+      g.row_bytes = L * es;
+      g.e1 = r.extent[o1], g.e2 = r.extent[o2];
+      g.s1 = pitch(o1) * es, g.s2 = pitch(o2) * es;
+      g.rows = plane_cells;
+      g.slots = (g.row_bytes + 14 + 15) / 16;
+      g.p0 = std::min(5, ilog2ceil(g.slots));  // at most 32 slots per row-lane: eight row-lanes and more per workgroup
+      const i64 lpr = 1LL << g.p0, rows_per_pass = (i64)(kThreads >> g.p0) * kRowsUnroll;
+      const i64 t0 = (g.slots + lpr - 1) / lpr;
+      if (t0 > 0xffffffLL) CD_NOT_SUPPORTED("a profile of more than 2^24 - 1 tile columns");
+      g.t0 = (unsigned int)t0;
+      const i64 want = std::min<i64>(std::min<i64>(cap, std::max<i64>(kProfileBlocks / t0, 1)), (g.rows + rows_per_pass - 1) / rows_per_pass);
+      g.rows_per_part = ((g.rows + want - 1) / want + rows_per_pass - 1) / rows_per_pass * rows_per_pass;  // whole passes
+      g.parts = (unsigned int)((g.rows + g.rows_per_part - 1) / g.rows_per_part);
+      p.blocks = t0 * g.parts;
+    }
+    // what field 0 reads: whole 16-byte vectors from the boundary below the first cell to the boundary above the last, where the
+    // readable range holds them; the cells alone where it does not
+    const uintptr_t first_cell = reinterpret_cast<uintptr_t>(r.a[0]) + (uintptr_t)g.box_off;
+    const i64 below = (i64)(first_cell & 15), above = (i64)((16 - ((first_cell + (uintptr_t)span) & 15)) & 15);
+    const auto whole = [&](i64 slot) { return slot >= g.rd_lo && slot + 16 <= g.rd_hi; };  // (the kernels' test of a vector)
+    p.read_lo = whole(-below) ? -below : 0;
+    p.read_hi = whole(span + above - 16) ? span + above : span;
+  }
+  if (p.blocks * r.n_fields > 0x7fffffffLL) CD_NOT_SUPPORTED("a profile of more than 2^31 - 1 workgroups");
+  g.final_lanes_log2 = g.parts >= 16 ? 6 : 0;
+  return p;
+}
+
+void launchProfile(const ProfileRequest& r, double* results, i64 ld, void* work, hipStream_t stream, KernelStats* stats) {
+  const ProfilePlan p = planProfile(r);
+  if (p.g.L == 0) return;  // nothing to write
+  if (ld < p.g.L) CD_INTERNAL_ERROR("the leading dimension of a profile is shorter than the profile");
+  if (p.g.parts > 0) {
+    ReduceFields fields;
+    std::memset(&fields, 0, sizeof(fields));
+    for (int f = 0; f < r.n_fields; ++f) {
+      fields.a[f] = static_cast<const char*>(r.a[f]);
+      if (r.op == kReduceDot) fields.b[f] = static_cast<const char*>(r.b[f]);
+    }
+    const char* const name = p.k.kind == K_ROWS_PROFILE ? "profile_rows_kernel" : p.k.kind == K_COLUMNS_PROFILE ? "profile_columns_kernel" : "profile_elements_kernel";
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "%s<%s,%d>", name, arithName(p.k.arith), r.op);
+    ++g_data_launches;
+    if (p.k.kind == K_ROWS_PROFILE) launchProfileRows(p.k, r.op, p.g, fields, static_cast<double*>(work), stream);
+    else launchProfileColumnsOrElements(p.k, r.op, p.g, fields, static_cast<double*>(work), stream);
+    if (stats) {
+      const MoveClass cls = classOf(p.k.kind);
+      stats->launches[cls] += 1;
+      stats->elements[cls] += (i64)r.n_fields * r.extent[0] * r.extent[1] * r.extent[2];
+    }
+  } else {
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "profile_final_kernel<%d>", r.op);
+  }
+  ++g_data_launches;
+  launchProfileFinal(r.op, p.g, results, ld, static_cast<const double*>(work), stream);
 }
 
 }  // namespace cudecomp

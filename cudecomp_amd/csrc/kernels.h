@@ -217,7 +217,45 @@ ReducePlan planReduce(const ReduceRequest& r);
 void launchReduce(const ReduceRequest& r, double* results, void* work, hipStream_t stream, KernelStats* stats = nullptr);
 inline i64 reduceWorkspaceBytes(int n_fields) { return (i64)n_fields * kern::kReduceMaxBlocks * 2 * (i64)sizeof(double); }
 
-// data-movement launches this process has made so far (launchMoves, launchFieldMoveList and both stages of launchReduce; tests count launches per call with it)
+// ---- profiles of a box of cells along one dim (kernels_profile.hip; include/cudecomp_interior_profile.h) ------------------------
+// The request: ReduceRequest's box, reduced over two of its dims and KEPT along extent[keep]: extent[keep] pairs of doubles per field.
+struct ProfileRequest {
+  const void* const* a = nullptr;  // n_fields (1 .. kern::kMaxFields) fields, no null entry
+  const void* const* b = nullptr;  // DOT: the second operands; not read otherwise
+  int n_fields = 0;
+  int op = 0;                      // kern::kReduceSum, kReduceDot, kReduceMaxAbs
+  int es = 0;                      // element size in bytes
+  ArithType arith = ARITH_NONE;    // the real type the elements consist of
+  i64 extent[3] = {0, 0, 0};       // the box, in elements; strides non-negative
+  i64 strides[3] = {0, 0, 0};
+  int keep = 0;                    // the dim of the box that is kept, 0 .. 2
+  i64 box_off = 0;                 // elements from a field's pointer to the first cell of the box
+  i64 readable_before = 0, readable_after = 0;  // as ReduceRequest's
+  const KernelTuning* tuning = nullptr;         // force_class == MOVE_GENERIC the element-wise kernel; force_streaming, no_streaming
+};
+// HOW a request runs (pure host code, no device needed).  The contiguous dim is the one of stride 1 (of several, one longer than a
+// cell).  Fields on a boundary of their real type, DOT operands at one phase of the 16-byte grid, complex DOT fields on element
+// boundaries (planReduce's rules) and:
+//   the kept dim is not the contiguous one                                     -> K_ROWS_PROFILE (an entry is a set of contiguous rows)
+//   it is, and both other dims longer than a cell have pitches of 16 bytes' multiples -> K_COLUMNS_PROFILE (a lane per 16-byte slot of the row)
+//   anything else, or forced                                                   -> K_GENERIC_PROFILE (element by element)
+// g.parts parts per entry: at most kern::kProfileMaxParts and at most max(1, kern::kProfilePairsPerField / L), so parts * L pairs of
+// partials per field fit profileWorkspaceBytes(n_fields, L).  Dims are not merged: an entry's rows stay the rows of the box.
+struct ProfilePlan {
+  KernelChoice k;        // kind K_ROWS_PROFILE / K_COLUMNS_PROFILE / K_GENERIC_PROFILE; vec = bytes per lane (16 / one element); access 0, 1
+  kern::ProfileGeom g;   // g.L entries; g.parts == 0: no stage one (L == 0: no launch at all; an empty entry: zeros are written)
+  i64 blocks;            // stage-one workgroups per field
+  i64 read_lo, read_hi;  // lowest byte read and one past the highest, relative to the first cell of field 0's box (0, 0: nothing read)
+};
+ProfilePlan planProfile(const ProfileRequest& r);
+// Launch it, asynchronous on `stream`: stage one into `work` (profileWorkspaceBytes(n_fields, extent[keep]) bytes of device memory),
+// stage two into results[2 * (f * ld + k)], k < extent[keep] <= ld.  Nothing is allocated, nothing waits; extent[keep] == 0: no launch.
+void launchProfile(const ProfileRequest& r, double* results, i64 ld, void* work, hipStream_t stream, KernelStats* stats = nullptr);
+inline i64 profileWorkspaceBytes(int n_fields, i64 length) {
+  return (i64)n_fields * (length > kern::kProfilePairsPerField ? length : (i64)kern::kProfilePairsPerField) * 2 * (i64)sizeof(double);
+}
+
+// data-movement launches this process has made so far (launchMoves, launchFieldMoveList and both stages of launchReduce and launchProfile; tests count launches per call with it)
 long long dataLaunchCount();
 
 // name (template spelling) of the data-movement kernel launched last by this process, "" before the first launch

@@ -3,7 +3,7 @@
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip, kernels_wall.hip, kernels_wall_plane.hip;
 // kernels_rotate.hip and sync.hip are launched by the executor (and compiled as one unit, kernels_executor.hip; kernels_fill.hip, kernels_reflect.hip and kernels_reduce.hip -- the reductions of a box, launchReduce -- likewise as kernels_edge.hip,
-// kernels_accumulate.hip and kernels_take.hip as kernels_sum.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
+// kernels_accumulate.hip and kernels_take.hip as kernels_sum.hip; kernels_profile.hip -- the profiles of a box along one dim, launchProfile -- in two parts, inside kernels_window.hip and kernels_rows.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
 // halo phases and transposes), kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) and
 // kernels_field_mirror.hip (the same lists mirrored, with a sign per field: multi-field wall halos) are reached through
 // launchFieldMoveList (kernels.h); kernels_field_wall.hip (the mirrored lists adding an addend per field and layer: multi-field wall
@@ -184,6 +184,35 @@ struct ReduceFields {
 };
 static_assert(sizeof(ReduceGeom) + sizeof(ReduceFields) + 8 <= 2048, "geometry, the two tables of fields and the workspace stay well under the 4 KB of kernel arguments");
 
+// ---- profiles of a box of cells along one dim (kernels_profile.hip; interior profiles, include/cudecomp_interior_profile.h) -------
+// The reduction over two dims of the box, kept along the third: L entries per field.  Stage one cuts the cells of an entry into
+// `parts` parts and writes one pair of fp64 partials per (field, part, entry) to work[2 * ((f * parts + part) * L + k)]; stage two
+// combines an entry's parts in index order.  parts * L never exceeds max(L, kProfilePairsPerField), parts never kProfileMaxParts:
+// the workspace is a function of the number of fields and of L alone.
+constexpr int kProfilePairsPerField = 65536;
+constexpr int kProfileMaxParts = 1024;
+constexpr int kProfileBlocks = 4096;  // stage-one workgroups per field the planner aims at: sixteen per CU of an MI355X
+struct ProfileGeom {
+  long long L;                 // entries per field: the extent of the kept dim
+  long long sk;                // segments, element-wise: BYTES between two entries
+  long long row_bytes;         // segments: a row of the contiguous dim; columns: a row of the kept dim (L elements)
+  long long rows;              // segments: rows of one entry; columns: all rows of the box, e1 * e2
+  long long e1, e2;            // columns, element-wise: the two reduced extents, e1 the one of the smaller stride
+  long long s1, s2;            // their strides in BYTES (segments: s1 between the rows of an entry); columns: multiples of 16
+  long long rows_per_part;     // columns: part p walks the rows [p * rows_per_part, (p + 1) * rows_per_part)
+  long long slots;             // segments, columns: 16-byte slots a row can touch at most
+  long long box_off;           // bytes from a field's pointer to the first cell of the box
+  long long rd_lo, rd_hi;      // the bytes [rd_lo, rd_hi) relative to the first cell of the box may be read
+  unsigned int t0, t1;         // segments: tile columns / tile rows of an entry; columns: t0 tile columns
+  unsigned int parts;          // parts per entry, 0: an empty entry (no stage one)
+  int p0;                      // segments, columns: log2 of the lanes per row
+  int reals;                   // reals per element: 1, or 2 for the complex types
+  int n_fields;
+  int stream;                  // 1 non-temporal loads (KernelChoice::access), 0 default caching
+  int final_lanes_log2;        // stage two: log2 of the lanes per entry (0 or 6)
+};
+static_assert(sizeof(ProfileGeom) + sizeof(ReduceFields) + 8 <= 2048, "geometry, the two tables of fields and the workspace stay well under the 4 KB of kernel arguments");
+
 }  // namespace kern
 
 // ---- what runs: one record per kernel choice ----------------------------------------------------------------------------------
@@ -233,7 +262,10 @@ enum KernelKind {
   K_ROWS_WALL_PLANE,          // rows_wall_plane_kernel (dst = +-src + the plane entry of the destination cell, the source backwards along the row or plane index) = 41
   K_GENERIC_WALL_PLANE,       // generic_wall_plane_kernel = 42
   K_ROWS_REDUCE,              // reduce_rows_kernel (a box of cells to two fp64 partials per workgroup; no destination) = 43
-  K_GENERIC_REDUCE            // reduce_elements_kernel = 44
+  K_GENERIC_REDUCE,           // reduce_elements_kernel = 44
+  K_ROWS_PROFILE,             // profile_rows_kernel (the kept dim not contiguous: an entry is a set of contiguous rows) = 45
+  K_COLUMNS_PROFILE,          // profile_columns_kernel (the kept dim contiguous: a lane owns a 16-byte slot of the row and walks down the rows) = 46
+  K_GENERIC_PROFILE           // profile_elements_kernel = 47
 };
 struct KernelChoice {
   KernelKind kind;
@@ -244,7 +276,7 @@ struct KernelChoice {
                     // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads;
                     // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it);
                     // reflections and wall-moves: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores;
-                    // reductions: 0, 1 non-temporal loads;
+                    // reductions and profiles: 0, 1 non-temporal loads;
                     // field-moves: 0, 1 non-temporal loads and stores; transpose_fields_kernel: 0, 2; adding / taking
                     // field-moves: as additions / takes; mirrored field-moves: as reflections / folds; wall field-moves: as reflections
   ArithType arith;  // additions, folds, wall-moves, reflections that flip the sign bits, mirrored field-moves (whatever their signs):
@@ -331,12 +363,15 @@ constexpr KindTraits kKindTraits[] = {
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_WALL_PLANE
     {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_REDUCE
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_REDUCE
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_PROFILE
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_COLUMNS_PROFILE
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_PROFILE
 };
-static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_REDUCE + 1, "one row per KernelKind");
+static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_PROFILE + 1, "one row per KernelKind");
 
 // the row of a kind; a value outside the enum is an internal error, never a read past the table
 inline const KindTraits& kindTraits(KernelKind kind) {
-  if (kind < K_ROWS || kind > K_GENERIC_REDUCE) CD_INTERNAL_ERROR("kernel kind out of range");
+  if (kind < K_ROWS || kind > K_GENERIC_PROFILE) CD_INTERNAL_ERROR("kernel kind out of range");
   return kKindTraits[kind];
 }
 inline MoveClass classOf(KernelKind kind) { return kindTraits(kind).cls; }
@@ -442,6 +477,15 @@ void launchFieldWallBatch(const KernelChoice& k, const kern::FieldMoveBatch& b, 
 void launchReduceStageOne(const KernelChoice& k, int op, const kern::ReduceGeom& g, const kern::ReduceFields& fields, double* work,
                           hipStream_t stream);
 void launchReduceFinal(int op, int n_fields, unsigned int partials, double* results, const double* work, hipStream_t stream);
+// kernels_profile.hip (in the units kernels_window.hip and kernels_rows.hip): profiles of a box of cells along one dim.  Stage one:
+// k.kind K_ROWS_PROFILE, K_COLUMNS_PROFILE or K_GENERIC_PROFILE, k.arith the real type, `op` one of kern::kReduce*; each workgroup
+// writes its partials to `work`.  Stage two: a lane (or a wave, g.final_lanes_log2) per (field, entry) combines g.parts pairs (0: +0.0)
+// and writes results[2 * (f * ld + k)] and the double after it.
+void launchProfileRows(const KernelChoice& k, int op, const kern::ProfileGeom& g, const kern::ReduceFields& fields, double* work,
+                       hipStream_t stream);
+void launchProfileColumnsOrElements(const KernelChoice& k, int op, const kern::ProfileGeom& g, const kern::ReduceFields& fields,
+                                    double* work, hipStream_t stream);
+void launchProfileFinal(int op, const kern::ProfileGeom& g, double* results, long long ld, const double* work, hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

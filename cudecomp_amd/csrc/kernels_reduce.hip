@@ -25,6 +25,7 @@
 // on an element's boundary of the 16-byte grid, and for any DOT only when a and b share their phase on that grid (kernels.cc
 // planReduce).
 #include "kernels_dispatch.h"
+#include "kernels_reduce_dev.h"
 #include "kernels_walk.h"
 
 #include "errors.h"
@@ -33,73 +34,8 @@ namespace cudecomp {
 namespace kern {
 namespace {
 
-// ---- the operations on fp64 accumulators ----------------------------------------------------------------------------------------
-// MAX_ABS propagates NaN: a NaN operand wins, and an accumulator that is NaN stays
-template <int OP> __device__ __forceinline__ double combine(double acc, double x) {
-  if constexpr (OP == kReduceMaxAbs) return (x > acc || x != x) ? x : acc;
-  else return acc + x;
-}
-
-// real j of a 16-byte vector, widened exactly
-template <typename T> __device__ __forceinline__ double realOf(const u32x4& v, int j) {
-  if constexpr (sizeof(T) == 8) {
-    return __builtin_bit_cast(double, j == 0 ? (u32x2)v.xy : (u32x2)v.zw);
-  } else if constexpr (sizeof(T) == 4) {
-    return (double)__uint_as_float(v[j]);
-  } else {
-    const unsigned short h = (unsigned short)(v[j >> 1] >> ((j & 1) * 16));
-    if constexpr (std::is_same<T, __bf16>::value) return (double)__uint_as_float((unsigned int)h << 16);
-    else return (double)__builtin_bit_cast(_Float16, h);
-  }
-}
-
-// one real at p, widened exactly
-template <typename T> __device__ __forceinline__ double loadReal(const char* p) {
-  if constexpr (sizeof(T) == 8) return *reinterpret_cast<const double*>(p);
-  else if constexpr (sizeof(T) == 4) return (double)*reinterpret_cast<const float*>(p);
-  else if constexpr (std::is_same<T, __bf16>::value) return (double)__uint_as_float((unsigned int)*reinterpret_cast<const unsigned short*>(p) << 16);
-  else return (double)*reinterpret_cast<const _Float16*>(p);
-}
-
-// the reals [lo, hi) (bytes, multiples of RS) of the 16-byte slot at `slot`, each with a load of its own; zero elsewhere
-template <int RS> __device__ __forceinline__ u32x4 loadPieces(const char* slot, int lo, int hi) {
-  u32x4 v = {0u, 0u, 0u, 0u};
-  if constexpr (RS == 8) {
-    if (lo <= 0 && 8 <= hi) v.xy = *reinterpret_cast<const u32x2*>(slot);
-    if (lo <= 8 && 16 <= hi) v.zw = *reinterpret_cast<const u32x2*>(slot + 8);
-  } else if constexpr (RS == 4) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (lo <= 4 * j && 4 * j + 4 <= hi) v[j] = *reinterpret_cast<const unsigned int*>(slot + 4 * j);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (lo <= 2 * j && 2 * j + 2 <= hi)
-        v[j >> 1] |= (unsigned int)*reinterpret_cast<const unsigned short*>(slot + 2 * j) << ((j & 1) * 16);
-  }
-  return v;
-}
-
-// ---- a workgroup's pair of partials -----------------------------------------------------------------------------------------------
-template <int OP> __device__ __forceinline__ void storePartials(double acc0, double acc1, double* work, unsigned int field, unsigned int wg) {
-  __shared__ double part[kThreads / 64][2];
-#pragma unroll
-  for (int mask = 32; mask >= 1; mask >>= 1) {
-    acc0 = combine<OP>(acc0, __shfl_xor(acc0, mask, 64));
-    acc1 = combine<OP>(acc1, __shfl_xor(acc1, mask, 64));
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) part[wave][0] = acc0, part[wave][1] = acc1;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r0 = part[0][0], r1 = part[0][1];
-#pragma unroll
-    for (int w = 1; w < kThreads / 64; ++w) r0 = combine<OP>(r0, part[w][0]), r1 = combine<OP>(r1, part[w][1]);
-    const u32x2 b0 = __builtin_bit_cast(u32x2, r0), b1 = __builtin_bit_cast(u32x2, r1);
-    const u32x4 pair = {b0.x, b0.y, b1.x, b1.y};
-    *reinterpret_cast<u32x4_g*>(work + 2 * ((size_t)field * kReduceMaxBlocks + wg)) = pair;
-  }
-}
+// (combine, realOf, loadReal, loadPieces, reduceRowTile, reduceElement and storePartials: kernels_reduce_dev.h, shared with
+// kernels_profile.hip)
 
 // ---------------------------------------------------------------------------------------------
 // reduce_rows_kernel: g.slots = 16-byte slots per row (the most a row can touch), g.rows, g.planes; g.s1, g.s2 in BYTES;
@@ -108,7 +44,6 @@ template <int OP> __device__ __forceinline__ void storePartials(double acc0, dou
 // ---------------------------------------------------------------------------------------------
 template <typename T, int OP>
 __global__ __launch_bounds__(kThreads) void reduce_rows_kernel(const ReduceGeom g, const ReduceFields fl, double* __restrict__ work) {
-  constexpr int RS = (int)sizeof(T), NR = 16 / RS;
   const unsigned int field = blockIdx.x / g.blocks, wg = blockIdx.x % g.blocks;
   const char* __restrict__ const a = fl.a[field] + g.box_off;
   const char* __restrict__ const b = OP == kReduceDot ? fl.b[field] + g.box_off : nullptr;
@@ -125,72 +60,11 @@ __global__ __launch_bounds__(kThreads) void reduce_rows_kernel(const ReduceGeom 
     if (col >= g.slots) continue;
     const long long lo16 = col * 16;
 
-    u32x4 va[kRowsUnroll], vb[kRowsUnroll];
-    int lo[kRowsUnroll], hi[kRowsUnroll], par[kRowsUnroll];
-    // phase one: all loads
-#pragma unroll
-    for (int u = 0; u < kRowsUnroll; ++u) {
-      const long long r = r0 + (long long)u * rb;
-      va[u] = u32x4{0u, 0u, 0u, 0u};
-      vb[u] = u32x4{0u, 0u, 0u, 0u};
-      lo[u] = hi[u] = par[u] = 0;
-      if (r >= g.rows) continue;
-      const long long row_off = (long long)plane * g.s2 + r * g.s1;
-      const long long ph = (long long)(reinterpret_cast<uintptr_t>(a + row_off) & 15);  // the row is bytes [ph, ph + n) of its slots
-      const long long n = r == g.rows - 1 ? g.last_row_bytes : g.row_bytes;
-      const long long first = lo16 > ph ? lo16 : ph, end = lo16 + 16 < ph + n ? lo16 + 16 : ph + n;
-      if (first >= end) continue;
-      lo[u] = (int)(first - lo16), hi[u] = (int)(end - lo16);
-      par[u] = (int)((lo16 - ph) / RS) & 1;
-      const long long slot_off = row_off - ph + lo16;
-      if (slot_off >= g.rd_lo && slot_off + 16 <= g.rd_hi) {
-        if (stream) {
-          va[u] = loadVec<true, 16>(a + slot_off);
-          if constexpr (OP == kReduceDot) vb[u] = loadVec<true, 16>(b + slot_off);
-        } else {
-          va[u] = loadVec<false, 16>(a + slot_off);
-          if constexpr (OP == kReduceDot) vb[u] = loadVec<false, 16>(b + slot_off);
-        }
-      } else {  // the pencil's first or last vector: only the reals inside the row
-        va[u] = loadPieces<RS>(a + slot_off, lo[u], hi[u]);
-        if constexpr (OP == kReduceDot) vb[u] = loadPieces<RS>(b + slot_off, lo[u], hi[u]);
-      }
-    }
-    // phase two: the arithmetic
-#pragma unroll
-    for (int u = 0; u < kRowsUnroll; ++u) {
-      if (lo[u] >= hi[u]) continue;
-      if constexpr (OP == kReduceDot) {
-        if (cplx) {  // (rows on element boundaries: reals 2k, 2k + 1 are one element, both inside the row or neither)
-#pragma unroll
-          for (int k = 0; k < NR / 2; ++k) {
-            const bool in = lo[u] <= 2 * k * RS && 2 * k * RS < hi[u];
-            const double ar = in ? realOf<T>(va[u], 2 * k) : 0.0, ai = in ? realOf<T>(va[u], 2 * k + 1) : 0.0;
-            const double br_ = in ? realOf<T>(vb[u], 2 * k) : 0.0, bi = in ? realOf<T>(vb[u], 2 * k + 1) : 0.0;
-            acc0 += ar * br_;
-            acc0 += ai * bi;
-            acc1 += ar * bi;
-            acc1 -= ai * br_;
-          }
-          continue;
-        }
-      }
-      double even = 0.0, odd = 0.0;
-#pragma unroll
-      for (int j = 0; j < NR; ++j) {
-        const bool in = lo[u] <= j * RS && j * RS < hi[u];
-        double x = in ? realOf<T>(va[u], j) : 0.0;
-        if constexpr (OP == kReduceDot) x *= in ? realOf<T>(vb[u], j) : 0.0;
-        if constexpr (OP == kReduceMaxAbs) x = __builtin_fabs(x);
-        if (j & 1) odd = combine<OP>(odd, x);
-        else even = combine<OP>(even, x);
-      }
-      acc0 = combine<OP>(acc0, par[u] ? odd : even);
-      acc1 = combine<OP>(acc1, par[u] ? even : odd);
-    }
+    reduceRowTile<T, OP>(a, b, (long long)plane * g.s2, r0, rb, g.rows, g.s1, g.row_bytes, g.last_row_bytes, lo16, g.rd_lo, g.rd_hi, cplx,
+                         stream, acc0, acc1);
   }
   if (!cplx) acc0 = combine<OP>(acc0, acc1), acc1 = 0.0;
-  storePartials<OP>(acc0, acc1, work, field, wg);
+  storePartials<OP>(acc0, acc1, work + 2 * ((size_t)field * kReduceMaxBlocks + wg));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -209,24 +83,9 @@ __global__ __launch_bounds__(kThreads) void reduce_elements_kernel(const ReduceG
   double acc0 = 0.0, acc1 = 0.0;
   forEachElement(w, [&](unsigned long long kf, unsigned long long kg, unsigned long long kh) CD_INLINED {
     const long long off = (long long)(kf * g.s[w.f] + kg * g.s[w.g] + kh * g.s[w.h]) * es;
-    const double ar = loadReal<T>(a + off), ai = cplx ? loadReal<T>(a + off + RS) : 0.0;
-    if constexpr (OP == kReduceDot) {
-      const double br = loadReal<T>(b + off), bi = cplx ? loadReal<T>(b + off + RS) : 0.0;
-      acc0 += ar * br;
-      if (cplx) {
-        acc0 += ai * bi;
-        acc1 += ar * bi;
-        acc1 -= ai * br;
-      }
-    } else if constexpr (OP == kReduceMaxAbs) {
-      acc0 = combine<OP>(acc0, __builtin_fabs(ar));
-      if (cplx) acc1 = combine<OP>(acc1, __builtin_fabs(ai));
-    } else {
-      acc0 += ar;
-      if (cplx) acc1 += ai;
-    }
+    reduceElement<T, OP>(a, b, off, cplx, acc0, acc1);
   });
-  storePartials<OP>(acc0, acc1, work, field, wg);
+  storePartials<OP>(acc0, acc1, work + 2 * ((size_t)field * kReduceMaxBlocks + wg));
 }
 
 // ---------------------------------------------------------------------------------------------

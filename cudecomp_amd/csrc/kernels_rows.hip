@@ -270,3 +270,9 @@ void launchRowsBatch(const KernelChoice& k, const Batch& b, unsigned int blocks,
 }
 
 }  // namespace cudecomp
+
+// the profiles of a box along one dim (kernels_profile.hip, the column and the element-wise kernel) are compiled into this unit: the family is too large for
+// the unit of the reductions, and this code object has the room (kernels_batch.h says why the library keeps the number of its code
+// objects)
+#define CD_PROFILE_PART 2
+#include "kernels_profile.hip"

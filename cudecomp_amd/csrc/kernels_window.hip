@@ -147,3 +147,9 @@ void launchWindowBatch(const KernelChoice& k, const kern::Batch& b, unsigned int
 }
 
 }  // namespace cudecomp
+
+// the profiles of a box along one dim (kernels_profile.hip, the row kernel and the final stage) are compiled into this unit: the family is too large for
+// the unit of the reductions, and this code object has the room (kernels_batch.h says why the library keeps the number of its code
+// objects)
+#define CD_PROFILE_PART 1
+#include "kernels_profile.hip"

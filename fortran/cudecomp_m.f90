@@ -754,6 +754,68 @@ module cudecomp
       integer(c_int) :: res
     end function cudecompAmdReduceInteriorZ
 
+    ! cudecomp_interior_profile.h: the reductions of cudecomp_interior_reduce.h over two dims of the interior, kept along `dim`.  The
+    ! C entry points (zero-based dim); the wrappers cudecompAmdProfileInterior{X,Y,Z} below take dim = 1/2/3
+    function cudecompAmdProfileInteriorWorkspaceBytes(n_fields, length, bytes) &
+      bind(C, name="cudecompAmdProfileInteriorWorkspaceBytes") result(res)
+      import
+      integer(c_int32_t), value :: n_fields
+      integer(c_int64_t), value :: length
+      integer(c_int64_t) :: bytes
+      integer(c_int) :: res
+    end function cudecompAmdProfileInteriorWorkspaceBytes
+
+    function cudecompAmdProfileInteriorX_C(handle, grid_desc, a, b, n_fields, op, dim, results, ld, work, dtype, halo_extents, &
+                                           padding, stream) &
+      bind(C, name="cudecompAmdProfileInteriorX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: a(*), b(*)
+      integer(c_int32_t), value :: n_fields, op, dim
+      type(c_ptr), value :: results
+      integer(c_int64_t), value :: ld
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3), padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdProfileInteriorX_C
+
+    function cudecompAmdProfileInteriorY_C(handle, grid_desc, a, b, n_fields, op, dim, results, ld, work, dtype, halo_extents, &
+                                           padding, stream) &
+      bind(C, name="cudecompAmdProfileInteriorY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: a(*), b(*)
+      integer(c_int32_t), value :: n_fields, op, dim
+      type(c_ptr), value :: results
+      integer(c_int64_t), value :: ld
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3), padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdProfileInteriorY_C
+
+    function cudecompAmdProfileInteriorZ_C(handle, grid_desc, a, b, n_fields, op, dim, results, ld, work, dtype, halo_extents, &
+                                           padding, stream) &
+      bind(C, name="cudecompAmdProfileInteriorZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: a(*), b(*)
+      integer(c_int32_t), value :: n_fields, op, dim
+      type(c_ptr), value :: results
+      integer(c_int64_t), value :: ld
+      type(c_ptr), value :: work
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3), padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdProfileInteriorZ_C
+
     ! cudecomp_halo_wall_value_fields.h: wall values of several pencils, each with a parity and addends of its own
     function cudecompAmdSetWallFieldHalosX_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, sides, values_low, &
                                              values_high, halo_extents, halo_periods, dim, padding, stream) &
@@ -2562,6 +2624,84 @@ contains
                                            int(dtype, c_int), ih, oh, ip, op, s)
   end function cudecompAmdTransposeFieldsYToX
 
+
+  ! ---- interior profiles (cudecomp_interior_profile.h): `a` and `b` are arrays of n_fields device addresses, `results` and `work`
+  ! device addresses, `op` one of CUDECOMP_AMD_REDUCE_SUM / _DOT / _MAX_ABS; field f, entry k owns the two doubles at
+  ! results(2 * (f * ld + k)), f and k counted from 0 ----
+  function cudecompAmdProfileInteriorX(handle, grid_desc, a, b, n_fields, op, dim, results, ld, work, dtype, halo_extents, padding, &
+                                       stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(c_ptr) :: a(*), b(*)
+    integer :: n_fields, op
+    integer :: dim  ! 1/2/3 = x/y/z
+    type(c_ptr) :: results, work
+    integer(c_int64_t) :: ld
+    integer :: dtype
+    integer :: halo_extents(3)
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    integer(c_intptr_t) :: s
+    h = int(halo_extents, c_int32_t)
+    p = 0
+    s = 0
+    if (present(padding)) p = int(padding, c_int32_t)
+    if (present(stream)) s = stream
+    res = cudecompAmdProfileInteriorX_C(handle, grid_desc, a, b, int(n_fields, c_int32_t), int(op, c_int32_t), &
+                                        int(dim - 1, c_int32_t), results, ld, work, int(dtype, c_int), h, p, s)
+  end function cudecompAmdProfileInteriorX
+
+  function cudecompAmdProfileInteriorY(handle, grid_desc, a, b, n_fields, op, dim, results, ld, work, dtype, halo_extents, padding, &
+                                       stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(c_ptr) :: a(*), b(*)
+    integer :: n_fields, op
+    integer :: dim  ! 1/2/3 = x/y/z
+    type(c_ptr) :: results, work
+    integer(c_int64_t) :: ld
+    integer :: dtype
+    integer :: halo_extents(3)
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    integer(c_intptr_t) :: s
+    h = int(halo_extents, c_int32_t)
+    p = 0
+    s = 0
+    if (present(padding)) p = int(padding, c_int32_t)
+    if (present(stream)) s = stream
+    res = cudecompAmdProfileInteriorY_C(handle, grid_desc, a, b, int(n_fields, c_int32_t), int(op, c_int32_t), &
+                                        int(dim - 1, c_int32_t), results, ld, work, int(dtype, c_int), h, p, s)
+  end function cudecompAmdProfileInteriorY
+
+  function cudecompAmdProfileInteriorZ(handle, grid_desc, a, b, n_fields, op, dim, results, ld, work, dtype, halo_extents, padding, &
+                                       stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(c_ptr) :: a(*), b(*)
+    integer :: n_fields, op
+    integer :: dim  ! 1/2/3 = x/y/z
+    type(c_ptr) :: results, work
+    integer(c_int64_t) :: ld
+    integer :: dtype
+    integer :: halo_extents(3)
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    integer(c_intptr_t) :: s
+    h = int(halo_extents, c_int32_t)
+    p = 0
+    s = 0
+    if (present(padding)) p = int(padding, c_int32_t)
+    if (present(stream)) s = stream
+    res = cudecompAmdProfileInteriorZ_C(handle, grid_desc, a, b, int(n_fields, c_int32_t), int(op, c_int32_t), &
+                                        int(dim - 1, c_int32_t), results, ld, work, int(dtype, c_int), h, p, s)
+  end function cudecompAmdProfileInteriorZ
 
   subroutine halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
     integer(c_int32_t), intent(out) :: h(3), p(3)

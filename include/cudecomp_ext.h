@@ -614,8 +614,27 @@ cudecompResult_t cudecompExtDescribeReduce3D(uint64_t a_address, uint64_t b_addr
                                              const int64_t extent[3], const int64_t strides[3], int64_t readable_before,
                                              int64_t readable_after, int32_t force, int64_t out[5]);
 
+/* One box of one field through the profile kernels of cudecompAmdProfileInterior{X,Y,Z} (cudecomp_interior_profile.h; csrc/kernels.h
+ * launchProfile, kernels_profile.hip): cudecompExtReduce3D's box, reduced over two of its dims and kept along extent[keep]:
+ * extent[keep] pairs of doubles to results[2k], results[2k + 1] (device memory, ld >= extent[keep] pairs; the pairs beyond are not
+ * touched; extent[keep] == 0: no launch).  `work`: device memory of cudecompAmdProfileInteriorWorkspaceBytes(1, extent[keep]) bytes.
+ * readable_before, readable_after and force as for cudecompExtReduce3D.  *kernel_class (optional): 0 the row or the column kernel, 2
+ * element-wise, -1 no stage-one launch.
+ *
+ * cudecompExtDescribeProfile3D answers how that call would run, without a device and without a launch.  out[8] = {kind
+ * (csrc/kernels_batch.h KernelKind: 45 profile_rows_kernel, 46 profile_columns_kernel, 47 profile_elements_kernel), bytes per lane (16
+ * / one element), stage-one workgroups, read_lo, read_hi (the lowest byte read and one past the highest, relative to a), parts per
+ * entry (0: no stage one), entries, lanes per entry of the final stage}. */
+cudecompResult_t cudecompExtProfile3D(const void* a, const void* b, cudecompDataType_t dtype, int32_t op, int32_t keep,
+                                      const int64_t extent[3], const int64_t strides[3], int64_t readable_before,
+                                      int64_t readable_after, void* work, double* results, int64_t ld, int32_t force,
+                                      int32_t* kernel_class, hipStream_t stream);
+cudecompResult_t cudecompExtDescribeProfile3D(uint64_t a_address, uint64_t b_address, cudecompDataType_t dtype, int32_t op,
+                                              int32_t keep, const int64_t extent[3], const int64_t strides[3],
+                                              int64_t readable_before, int64_t readable_after, int32_t force, int64_t out[8]);
+
 /* Data-movement kernel launches this process has made so far through the kernel layer (launchMoves,
- * launchFieldMoveList and both stages of launchReduce; the signal / wait kernels and the copy-engine copies of the transports are not counted -- the chunk copies the
+ * launchFieldMoveList and both stages of launchReduce and of launchProfile; the signal / wait kernels and the copy-engine copies of the transports are not counted -- the chunk copies the
  * one-sided transport makes with the row-copy kernel between ranks that share a GPU go through launchMoves and are).  Tests take
  * the difference around a call. */
 cudecompResult_t cudecompExtDataLaunchCount(int64_t* launches);
