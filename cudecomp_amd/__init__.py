@@ -178,6 +178,7 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtRunWallFieldMoves", "cudecompExtDescribeWallFieldMoves", "cudecompExtPlanHaloWallValueFields",
                "cudecompExtPlanHaloWallValues", "cudecompExtWall3D", "cudecompExtPlanHaloWallPlanes", "cudecompExtWallPlane3D",
                "cudecompExtReduce3D", "cudecompExtDescribeReduce3D", "cudecompExtProfile3D", "cudecompExtDescribeProfile3D",
+               "cudecompExtPlanes3D", "cudecompExtDescribePlanes3D",
                "cudecompExtSyncEpochBegin", "cudecompExtSyncSignal",
                "cudecompExtSyncWait", "cudecompExtTagPages", "cudecompExtCheckPages", "cudecompExtChecksum"]
 MAX_FLAGS, FLAG_SCALE = 64, 16  # csrc/kernels.h: kMaxFlags, kFlagScale
@@ -220,6 +221,9 @@ INTERIOR_PROFILE_SYMBOLS = ["cudecompAmdProfileInteriorWorkspaceBytes", "cudecom
                             "cudecompAmdProfileInteriorZ"]
 PROFILE_PAIRS_PER_FIELD = 65536  # csrc/kernels_batch.h kProfilePairsPerField: pairs of partials per field the workspace holds at least
 PROFILE_MAX_PARTS = 1024  # csrc/kernels_batch.h kProfileMaxParts: parts per entry at most
+# include/cudecomp_interior_planes.h: interior plane updates (the profile's adjoint: a coefficient per plane added or multiplied in place)
+INTERIOR_PLANES_SYMBOLS = ["cudecompAmdApplyPlanesInteriorX", "cudecompAmdApplyPlanesInteriorY", "cudecompAmdApplyPlanesInteriorZ"]
+PLANES_ADD, PLANES_MUL = 0, 1  # CUDECOMP_AMD_PLANES_*
 # include/cudecomp_halo_wall_value_fields.h: multi-field wall values (several pencils, a parity and addends per field)
 AMD_WALL_VALUE_FIELDS_SYMBOLS = ["cudecompAmdSetWallFieldHalosX", "cudecompAmdSetWallFieldHalosY", "cudecompAmdSetWallFieldHalosZ"]
 MAX_WALL_VALUE_FIELDS = 32  # CUDECOMP_AMD_MAX_WALL_VALUE_FIELDS
@@ -321,6 +325,10 @@ def lib():
                                                    C.POINTER(i64)]
         L.cudecompExtDescribeReduce3D.argtypes = [C.c_uint64, C.c_uint64, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, i32,
                                                   C.POINTER(i64)]
+        for name in INTERIOR_PLANES_SYMBOLS:
+            getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, i32, i32, pf64, i64, C.c_double, i32, pi32, pi32, vp]
+        L.cudecompExtPlanes3D.argtypes = [vp, i32, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, vp, C.c_double, i32, pi32, vp]
+        L.cudecompExtDescribePlanes3D.argtypes = [C.c_uint64, i32, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, i32, C.POINTER(i64)]
         for name in AMD_FIELDS_SYMBOLS:  # (the update's arguments with the list of fields and its length in the place of `input`)
             getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         L.cudecompExtPlanHaloFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32,
@@ -661,6 +669,20 @@ def cudecompAmdProfileInterior(axis, handle, gd, a, b, op, dim, results, ld, wor
     res = C.cast(C.c_void_p(results or None), C.POINTER(C.c_double))
     _check(getattr(lib(), name)(handle, gd, ptrs(a), ptrs(b), int(n), int(op), int(dim), res, int(ld), work or None, dtype,
                                 _i3(halo_extents), _i3(padding), stream), name)
+
+
+def cudecompAmdApplyPlanesInterior(axis, handle, gd, fields, op, dim, coef, ld, scale, dtype, halo_extents, padding=None, stream=None,
+                                   n_fields=None):
+    """cudecompAmdApplyPlanesInterior{X,Y,Z} (cudecomp_interior_planes.h): every interior cell of every field of `fields` (device
+    addresses) becomes u + c (PLANES_ADD) or u * c (PLANES_MUL), c = scale * the pair at coef[2 * (f * ld + k)] of the DEVICE array at
+    `coef`, k the cell's interior index along the global dim `dim`; ld == 0: all fields share row 0.  Arguments are passed as they
+    are: the library makes the checks."""
+    name = "cudecompAmdApplyPlanesInterior" + "XYZ"[axis]
+    ptrs = None if fields is None else (C.c_void_p * max(len(fields), 1))(*[x or None for x in fields])
+    n = n_fields if n_fields is not None else (len(fields) if fields is not None else 0)
+    cf = C.cast(C.c_void_p(coef or None), C.POINTER(C.c_double))
+    _check(getattr(lib(), name)(handle, gd, ptrs, int(n), int(op), int(dim), cf, int(ld), float(scale), dtype, _i3(halo_extents),
+                                _i3(padding), stream), name)
 
 
 def wall_plane_shape(info, dim, halo_extents):
@@ -1121,6 +1143,27 @@ def cudecompExtDescribeProfile3D(a_address, b_address, dtype, op, keep, extent, 
                                               int(readable_before), int(readable_after), int(force), out),
            "cudecompExtDescribeProfile3D")
     return dict(zip(("kind", "vec", "blocks", "read_lo", "read_hi", "parts", "entries", "final_lanes"), [int(x) for x in out]))
+
+
+def cudecompExtPlanes3D(a, dtype, op, keep, extent, strides, readable_before, readable_after, coef, scale=1.0, force=0, stream=None):
+    """One box of one field through the plane-update kernels, in place (cudecompExtProfile3D's box; the cell of index k along
+    extent[keep] becomes u + c or u * c, c = scale * the pair at coef[2k] of device memory); returns the kernel class (0 rows or
+    columns, 2 element-wise, -1 no launch)."""
+    cls = C.c_int32(-1)
+    v = lambda x: (C.c_int64 * 3)(*[int(k) for k in x])
+    _check(lib().cudecompExtPlanes3D(a, dtype, int(op), int(keep), v(extent), v(strides), int(readable_before), int(readable_after),
+                                     coef, float(scale), int(force), C.byref(cls), stream), "cudecompExtPlanes3D")
+    return cls.value
+
+
+def cudecompExtDescribePlanes3D(a_address, dtype, op, keep, extent, strides, readable_before=0, readable_after=0, force=0):
+    """How cudecompExtPlanes3D would run that box (no launch, no GPU): {kind, vec, blocks, read_lo, read_hi, write_lo, write_hi};
+    the byte ranges relative to a_address."""
+    out = (C.c_int64 * 7)()
+    v = lambda x: (C.c_int64 * 3)(*[int(k) for k in x])
+    _check(lib().cudecompExtDescribePlanes3D(int(a_address), dtype, int(op), int(keep), v(extent), v(strides), int(readable_before),
+                                             int(readable_after), int(force), out), "cudecompExtDescribePlanes3D")
+    return dict(zip(("kind", "vec", "blocks", "read_lo", "read_hi", "write_lo", "write_hi"), [int(x) for x in out]))
 
 
 def cudecompExtRotateWalk(nb, walk=-1):

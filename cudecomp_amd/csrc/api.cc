@@ -1188,6 +1188,74 @@ CD_DEFINE_PROFILE_INTERIOR(cudecompAmdProfileInteriorX, 0)
 CD_DEFINE_PROFILE_INTERIOR(cudecompAmdProfileInteriorY, 1)
 CD_DEFINE_PROFILE_INTERIOR(cudecompAmdProfileInteriorZ, 2)
 
+// cudecomp_interior_planes.h: the profile's adjoint -- every interior cell updated in place with the coefficient of its index along
+// `dim`.  Local: the pencil from makePencil, the memory position of `dim` from its order.  Checks in the header's order, on the host.
+static cudecompResult_t applyPlanesInteriorEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const fields[],
+                                                 int32_t n_fields, int32_t op, int32_t dim, const double* coef, int64_t ld, double scale,
+                                                 cudecompDataType_t dtype, const int32_t halo_extents[], const int32_t padding[],
+                                                 hipStream_t stream) {
+  try {
+    checkHandle(handle);
+    checkGridDesc(handle, grid_desc);
+    checkDataType(dtype);
+    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
+    const Pencil p = makePencil(grid_desc->shape, grid_desc->pidx, axis, halo_extents, padding);  // (negative halos, padding)
+    if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_REDUCE_FIELDS) CD_INVALID_USAGE("n_fields argument out of range");
+    if (op < CUDECOMP_AMD_PLANES_ADD || op > CUDECOMP_AMD_PLANES_MUL) CD_INVALID_USAGE("op argument out of range");
+    if (dim < 0 || dim > 2) CD_INVALID_USAGE("dim argument out of range");
+    if (!fields) CD_INVALID_USAGE("fields argument cannot be null");
+    for (int32_t f = 0; f < n_fields; ++f)
+      if (!fields[f]) CD_INVALID_USAGE("fields argument cannot hold a null entry");
+    for (int32_t f = 0; f < n_fields; ++f)
+      for (int32_t e = 0; e < f; ++e)
+        if (fields[e] == fields[f]) CD_INVALID_USAGE("fields argument cannot hold the same field twice");
+    if (!coef) CD_INVALID_USAGE("coef argument cannot be null");
+    if (reinterpret_cast<uintptr_t>(coef) % 8 != 0) CD_INVALID_USAGE("coef argument must be 8-byte aligned");
+
+    PlanesRequest r;
+    r.a = fields;
+    r.n_fields = n_fields;
+    r.op = op;
+    r.es = elementSize(dtype);
+    r.arith = arithOf(dtype);
+    i64 stride = 1;
+    for (int i = 0; i < 3; ++i) {  // memory order: the interior is what is left of the shape without both halos and the padding
+      const int ga = p.order[i];
+      if (ga == dim) r.keep = i;
+      r.extent[i] = std::max<i64>((i64)p.shape[i] - 2 * (i64)p.halo[ga] - p.pad[ga], 0);
+      r.strides[i] = stride;
+      r.box_off += p.halo[ga] * stride;
+      stride *= p.shape[i];
+    }
+    if (p.size == 0) r.box_off = 0;  // (some extent is 0: nothing is touched)
+    if (ld != 0 && ld < r.extent[r.keep]) CD_INVALID_USAGE("ld argument is neither 0 nor at least the interior extent along dim");
+    r.ld = ld;
+    r.scale = scale;
+    const bool empty = r.extent[0] * r.extent[1] * r.extent[2] == 0;
+    r.readable_before = r.box_off * r.es;
+    i64 last = 0;
+    for (int i = 0; i < 3; ++i) last += (r.extent[i] - 1) * r.strides[i];
+    r.readable_after = empty ? 0 : (p.size - r.box_off - last - 1) * (i64)r.es;
+    r.tuning = &handle->tuning;
+    if (empty) return CUDECOMP_RESULT_SUCCESS;  // no launch, and no device needed for none
+    ensureDevice(handle);
+    launchPlanes(r, coef, stream);
+  }
+  CD_API_CATCH()
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+#define CD_DEFINE_APPLY_PLANES_INTERIOR(NAME, AXIS)                                                                           \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const fields[], int32_t n_fields,        \
+                        int32_t op, int32_t dim, const double* coef, int64_t ld, double scale, cudecompDataType_t dtype,      \
+                        const int32_t halo_extents[], const int32_t padding[], hipStream_t stream) {                          \
+    return applyPlanesInteriorEntry(AXIS, handle, grid_desc, fields, n_fields, op, dim, coef, ld, scale, dtype, halo_extents, \
+                                    padding, stream);                                                                         \
+  }
+CD_DEFINE_APPLY_PLANES_INTERIOR(cudecompAmdApplyPlanesInteriorX, 0)
+CD_DEFINE_APPLY_PLANES_INTERIOR(cudecompAmdApplyPlanesInteriorY, 1)
+CD_DEFINE_APPLY_PLANES_INTERIOR(cudecompAmdApplyPlanesInteriorZ, 2)
+
 // cudecomp_halo_fold.h: the ghost cells the reflection writes are added onto their mirror images
 #define CD_DEFINE_HALO_FOLD(NAME, AXIS)                                                                                     \
   cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,       \

@@ -961,6 +961,69 @@ cudecompResult_t cudecompExtDescribeProfile3D(uint64_t a_address, uint64_t b_add
   });
 }
 
+// one box of one field through the plane-update kernels (kernels.h launchPlanes) / how it would run (planPlanes)
+static PlanesRequest planesRequestOf(void* const* a, cudecompDataType_t dtype, int32_t op, int32_t keep, const int64_t extent[3],
+                                     const int64_t strides[3], int64_t readable_before, int64_t readable_after, double scale,
+                                     const KernelTuning* tuning) {
+  if (!extent || !strides) CD_INVALID_USAGE("null argument");
+  if (op < 0 || op > 1) CD_INVALID_USAGE("op must be 0 (add) or 1 (multiply)");
+  if (keep < 0 || keep > 2) CD_INVALID_USAGE("keep must be 0, 1 or 2");
+  if (readable_before < 0 || readable_after < 0) CD_INVALID_USAGE("readable_before and readable_after cannot be negative");
+  PlanesRequest r;
+  r.a = a;
+  r.n_fields = 1;
+  r.op = op;
+  r.keep = keep;
+  r.es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
+  r.arith = arithOf(dtype);
+  for (int i = 0; i < 3; ++i) {
+    if (extent[i] < 0 || strides[i] < 0) CD_INVALID_USAGE("extents and strides of a plane update cannot be negative");
+    r.extent[i] = extent[i];
+    r.strides[i] = strides[i];
+  }
+  r.readable_before = readable_before;
+  r.readable_after = readable_after;
+  r.ld = 0;
+  r.scale = scale;
+  r.tuning = tuning;
+  return r;
+}
+
+cudecompResult_t cudecompExtPlanes3D(void* a, cudecompDataType_t dtype, int32_t op, int32_t keep, const int64_t extent[3],
+                                     const int64_t strides[3], int64_t readable_before, int64_t readable_after, const double* coef,
+                                     double scale, int32_t force, int32_t* kernel_class, hipStream_t stream) {
+  return guarded([&] {
+    if (!a || !coef) CD_INVALID_USAGE("null argument");
+    const KernelTuning t = tuningOfForce(force);
+    const PlanesRequest r = planesRequestOf(&a, dtype, op, keep, extent, strides, readable_before, readable_after, scale, &t);
+    KernelStats st;
+    launchPlanes(r, coef, stream, &st);
+    if (kernel_class) {
+      *kernel_class = -1;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
+        if (st.launches[c]) *kernel_class = c;
+    }
+  });
+}
+
+cudecompResult_t cudecompExtDescribePlanes3D(uint64_t a_address, cudecompDataType_t dtype, int32_t op, int32_t keep,
+                                             const int64_t extent[3], const int64_t strides[3], int64_t readable_before,
+                                             int64_t readable_after, int32_t force, int64_t out[7]) {
+  return guarded([&] {
+    if (!out) CD_INVALID_USAGE("null argument");
+    void* const a = reinterpret_cast<void*>(a_address);
+    const KernelTuning t = tuningOfForce(force);
+    const PlanesPlan p = planPlanes(planesRequestOf(&a, dtype, op, keep, extent, strides, readable_before, readable_after, 1.0, &t));
+    out[0] = p.k.kind;
+    out[1] = p.k.vec;
+    out[2] = p.blocks;
+    out[3] = p.read_lo;
+    out[4] = p.read_hi;
+    out[5] = p.write_lo;
+    out[6] = p.write_hi;
+  });
+}
+
 cudecompResult_t cudecompExtPlanHaloWallPlanes(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                                const bool periods[], int32_t dim, const int32_t pad[], cudecompDataType_t dtype,
                                                int32_t parity, int32_t centering, int32_t sides, uint64_t pencil_address,

@@ -753,6 +753,9 @@ void spellKernelName(const KernelChoice& k) {
     case K_ROWS_PROFILE:
     case K_COLUMNS_PROFILE:
     case K_GENERIC_PROFILE: break;  // (launchProfile likewise)
+    case K_ROWS_PLANES:
+    case K_COLUMNS_PLANES:
+    case K_GENERIC_PLANES: break;  // (launchPlanes likewise: planes_rows_kernel / planes_columns_kernel<T,MODE>, planes_elements_kernel<T>)
   }
 }
 
@@ -850,6 +853,9 @@ void launchBatch(const Launch& l, const Move3D* moves, const void* fill_value, c
     case K_ROWS_PROFILE:
     case K_COLUMNS_PROFILE:
     case K_GENERIC_PROFILE: CD_INTERNAL_ERROR("profiles are launched by launchProfile");
+    case K_ROWS_PLANES:
+    case K_COLUMNS_PLANES:
+    case K_GENERIC_PLANES: CD_INTERNAL_ERROR("plane updates are launched by launchPlanes");
   }
 }
 
@@ -1587,6 +1593,151 @@ void launchProfile(const ProfileRequest& r, double* results, i64 ld, void* work,
   }
   ++g_data_launches;
   launchProfileFinal(r.op, p.g, results, ld, static_cast<const double*>(work), stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// plane updates of a box of cells along one dim (kernels_planes.hip)
+// ---------------------------------------------------------------------------------------------
+PlanesPlan planPlanes(const PlanesRequest& r) {
+  if (r.n_fields < 1 || r.n_fields > kMaxFields || !r.a) CD_INTERNAL_ERROR("a plane update of 1 .. kMaxFields fields");
+  if (r.op != kPlanesAdd && r.op != kPlanesMul) CD_INTERNAL_ERROR("plane-update operation out of range");
+  if (r.arith == ARITH_NONE) CD_INTERNAL_ERROR("a plane update needs the real type of its elements");
+  if (r.keep < 0 || r.keep > 2) CD_INTERNAL_ERROR("the kept dim of a plane update is 0, 1 or 2");
+  const int es = r.es, rs = arithBytes(r.arith);
+  if (es != rs && es != 2 * rs) CD_INTERNAL_ERROR("element size does not match the real type");
+  if (es == 2 * rs && r.arith == ARITH_BF16) CD_INTERNAL_ERROR("bf16 has no complex type");
+  if (r.box_off < 0 || r.readable_before < 0 || r.readable_after < 0) CD_INTERNAL_ERROR("negative offset of a plane update");
+  const KernelTuning& tuning = r.tuning ? *r.tuning : kDefaultTuning;
+  PlanesPlan p;
+  std::memset(&p, 0, sizeof(p));
+  p.k.kind = K_GENERIC_PLANES;
+  p.k.es = es;
+  p.k.vec = es;
+  p.k.arith = r.arith;
+  PlanesGeom& g = p.g;
+  g.reals = es / rs;
+  g.n_fields = r.n_fields;
+  g.op = r.op;
+  g.scale = r.scale;
+  g.box_off = r.box_off * es;
+  i64 cells = 1, last = 0;  // `last`: the element offset of the box's last cell
+  for (int i = 0; i < 3; ++i) {
+    if (r.extent[i] < 0 || r.strides[i] < 0) CD_INTERNAL_ERROR("negative extent or stride of a plane update");
+    cells *= r.extent[i];
+    last += (r.extent[i] - 1) * r.strides[i];
+  }
+  const i64 L = r.extent[r.keep];
+  g.L = L;
+  if (r.ld != 0 && r.ld < L) CD_INTERNAL_ERROR("the leading dimension of the coefficients is shorter than the kept extent");
+  g.ld = r.ld;
+  if (cells == 0) return p;  // (no launch: g.parts == 0)
+  if (L > 0x7fffffffLL) CD_NOT_SUPPORTED("a plane update of more than 2^31 - 1 entries");
+  const i64 span = (last + 1) * es;
+  g.rd_lo = -r.readable_before;
+  g.rd_hi = span + r.readable_after;
+  p.k.access = ((cells * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming) ? 1 : 0;
+  g.stream = p.k.access;
+  const i64 per_entry = std::max<i64>(kProfileBlocks / L, 1);  // parts per entry: about kProfileBlocks workgroups per field
+
+  // the two other dims, the one of the smaller stride first (a dim of one cell has no stride that counts)
+  int o1 = (r.keep + 1) % 3, o2 = (r.keep + 2) % 3;
+  const auto pitch = [&](int d) { return r.extent[d] > 1 ? r.strides[d] : 0; };
+  if (r.extent[o2] > 1 && (r.extent[o1] == 1 || r.strides[o2] < r.strides[o1])) std::swap(o1, o2);
+  int c = -1;  // the contiguous dim
+  for (int i = 0; i < 3; ++i)
+    if (r.strides[i] == 1 && (c < 0 || (r.extent[c] == 1 && r.extent[i] > 1))) c = i;
+  // lanes on the 16-byte grid: every field on a boundary of its real type; the complex product pairs the reals 2k, 2k + 1 of a slot,
+  // so its fields sit on element boundaries
+  bool fast = c >= 0 && tuning.force_class != MOVE_GENERIC;
+  const uintptr_t need = (r.op == kPlanesMul && g.reals == 2) ? (uintptr_t)es : (uintptr_t)rs;
+  for (int f = 0; f < r.n_fields && fast; ++f)
+    if (reinterpret_cast<uintptr_t>(r.a[f]) % need != 0) fast = false;
+  const i64 plane_cells = r.extent[o1] * r.extent[o2];
+  // the column form: every row of the box at one phase of the 16-byte grid
+  if (fast && c == r.keep && ((pitch(o1) * es) % 16 != 0 || (pitch(o2) * es) % 16 != 0 || plane_cells > 0x7fffffffLL)) fast = false;
+
+  if (!fast) {
+    g.e1 = r.extent[o1], g.e2 = r.extent[o2];
+    g.s1 = pitch(o1) * es, g.s2 = pitch(o2) * es;
+    g.sk = pitch(r.keep) * es;
+    g.parts = (unsigned int)std::min<i64>(per_entry, (plane_cells + kThreads - 1) / kThreads);
+    p.blocks = L * g.parts;
+    p.read_lo = 0;
+    p.read_hi = span;
+    p.write_hi = (L - 1) * g.sk + (g.e1 - 1) * g.s1 + (g.e2 - 1) * g.s2 + es;
+  } else {
+    p.k.vec = 16;
+    if (c != r.keep) {
+      const int o = 3 - c - r.keep;
+      p.k.kind = K_ROWS_PLANES;
+      g.row_bytes = r.extent[c] * es;
+      g.rows = r.extent[o];
+      g.s1 = pitch(o) * es;
+      g.sk = pitch(r.keep) * es;
+      g.slots = (g.row_bytes + 14 + 15) / 16;
+      g.p0 = std::min(8, ilog2ceil(g.slots));
+      const i64 lpr = 1LL << g.p0, rows_per_tile = (i64)(kThreads >> g.p0) * kRowsUnroll;
+      const i64 t0 = (g.slots + lpr - 1) / lpr, t1 = (g.rows + rows_per_tile - 1) / rows_per_tile;
+      if (t0 > 0xffffffffLL || t1 > 0xffffffffLL) CD_NOT_SUPPORTED("a plane update of more than 2^32 - 1 tiles along one dim");
+      g.t0 = (unsigned int)t0, g.t1 = (unsigned int)t1;
+      g.parts = (unsigned int)std::min<i64>(per_entry, t0 * t1);
+      p.blocks = L * g.parts;
+      p.write_hi = (L - 1) * g.sk + (g.rows - 1) * g.s1 + g.row_bytes;
+    } else {
+      p.k.kind = K_COLUMNS_PLANES;
+      g.row_bytes = L * es;
+      g.e1 = r.extent[o1], g.e2 = r.extent[o2];
+      g.s1 = pitch(o1) * es, g.s2 = pitch(o2) * es;
+      g.rows = plane_cells;
+      g.slots = (g.row_bytes + 14 + 15) / 16;
+      g.p0 = std::min(5, ilog2ceil(g.slots));  // at most 32 slots per row-lane: eight row-lanes and more per workgroup
+      const i64 lpr = 1LL << g.p0, rows_per_pass = (i64)(kThreads >> g.p0) * kRowsUnroll;
+      const i64 t0 = (g.slots + lpr - 1) / lpr;
+      if (t0 > 0xffffffLL) CD_NOT_SUPPORTED("a plane update of more than 2^24 - 1 tile columns");
+      g.t0 = (unsigned int)t0;
+      const i64 want = std::min<i64>(std::max<i64>(kProfileBlocks / t0, 1), (g.rows + rows_per_pass - 1) / rows_per_pass);
+      g.rows_per_part = ((g.rows + want - 1) / want + rows_per_pass - 1) / rows_per_pass * rows_per_pass;  // whole passes
+      g.parts = (unsigned int)((g.rows + g.rows_per_part - 1) / g.rows_per_part);
+      p.blocks = t0 * g.parts;
+      p.write_hi = (g.e1 - 1) * g.s1 + (g.e2 - 1) * g.s2 + g.row_bytes;
+    }
+    // what field 0 reads: whole 16-byte vectors from the boundary below the first cell to the boundary above the last, where the
+    // readable range holds them; the cells alone where it does not (planProfile's closed form: the loads are loadSlot's)
+    const uintptr_t first_cell = reinterpret_cast<uintptr_t>(r.a[0]) + (uintptr_t)g.box_off;
+    const i64 below = (i64)(first_cell & 15), above = (i64)((16 - ((first_cell + (uintptr_t)span) & 15)) & 15);
+    const auto whole = [&](i64 slot) { return slot >= g.rd_lo && slot + 16 <= g.rd_hi; };  // (the kernels' test of a vector)
+    p.read_lo = whole(-below) ? -below : 0;
+    p.read_hi = whole(span + above - 16) ? span + above : span;
+  }
+  p.write_lo = 0;  // (the first cell of the box is the first cell of its first row)
+  if (p.blocks * r.n_fields > 0x7fffffffLL) CD_NOT_SUPPORTED("a plane update of more than 2^31 - 1 workgroups");
+  return p;
+}
+
+void launchPlanes(const PlanesRequest& r, const double* coef, hipStream_t stream, KernelStats* stats) {
+  const PlanesPlan p = planPlanes(r);
+  if (p.g.parts == 0) return;  // an empty box
+  for (int f = 0; f < r.n_fields; ++f)
+    for (int e = 0; e < f; ++e)
+      if (r.a[e] == r.a[f]) CD_INTERNAL_ERROR("a field is named twice in a plane update");
+  PlanesFields fields;
+  std::memset(&fields, 0, sizeof(fields));
+  for (int f = 0; f < r.n_fields; ++f) fields.a[f] = static_cast<char*>(r.a[f]);
+  if (p.k.kind == K_GENERIC_PLANES) {
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "planes_elements_kernel<%s>", arithName(p.k.arith));
+  } else {
+    const int mode = r.op == kPlanesAdd ? 0 : p.g.reals == 2 ? 2 : 1;
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "%s<%s,%d>", p.k.kind == K_ROWS_PLANES ? "planes_rows_kernel" : "planes_columns_kernel",
+             arithName(p.k.arith), mode);
+  }
+  ++g_data_launches;
+  if (p.k.kind == K_ROWS_PLANES) launchPlanesRows(p.k, p.g, fields, coef, stream);
+  else launchPlanesColumnsOrElements(p.k, p.g, fields, coef, stream);
+  if (stats) {
+    const MoveClass cls = classOf(p.k.kind);
+    stats->launches[cls] += 1;
+    stats->elements[cls] += (i64)r.n_fields * r.extent[0] * r.extent[1] * r.extent[2];
+  }
 }
 
 }  // namespace cudecomp

@@ -255,7 +255,44 @@ inline i64 profileWorkspaceBytes(int n_fields, i64 length) {
   return (i64)n_fields * (length > kern::kProfilePairsPerField ? length : (i64)kern::kProfilePairsPerField) * 2 * (i64)sizeof(double);
 }
 
-// data-movement launches this process has made so far (launchMoves, launchFieldMoveList and both stages of launchReduce and launchProfile; tests count launches per call with it)
+// ---- plane updates of a box of cells along one dim (kernels_planes.hip; include/cudecomp_interior_planes.h) ----------------------
+// The request: ProfileRequest's box of every field a[f], updated IN PLACE with the coefficient of each cell's index k along
+// extent[keep]: u <- u + c (kern::kPlanesAdd) or u <- u * c (kern::kPlanesMul), c = scale * the pair at coef[2 * (f * ld + k)]
+// rounded once to the real type (real types: the first double alone; complex: (re, im), MUL the complex product).
+struct PlanesRequest {
+  void* const* a = nullptr;        // n_fields (1 .. kern::kMaxFields) fields, no null entry, no two equal
+  int n_fields = 0;
+  int op = 0;                      // kern::kPlanesAdd, kPlanesMul
+  int es = 0;                      // element size in bytes
+  ArithType arith = ARITH_NONE;    // the real type the elements consist of
+  i64 extent[3] = {0, 0, 0};       // the box, in elements; strides non-negative
+  i64 strides[3] = {0, 0, 0};
+  int keep = 0;                    // the dim of the box whose index picks the coefficient, 0 .. 2
+  i64 box_off = 0;                 // elements from a field's pointer to the first cell of the box
+  i64 readable_before = 0, readable_after = 0;  // as ReduceRequest's
+  i64 ld = 0;                      // pairs between the coefficient rows of two fields, >= extent[keep]; 0: every field takes row 0
+  double scale = 1.0;
+  const KernelTuning* tuning = nullptr;         // force_class == MOVE_GENERIC the element-wise kernel; force_streaming, no_streaming
+};
+// HOW a request runs (pure host code, no device needed).  planProfile's rules: the contiguous dim is the one of stride 1 (of several,
+// one longer than a cell); fields on a boundary of their real type -- for the complex product, of their element -- and:
+//   the kept dim is not the contiguous one                                     -> K_ROWS_PLANES (one coefficient per row)
+//   it is, and both other dims longer than a cell have pitches of 16 bytes' multiples -> K_COLUMNS_PLANES (a lane per 16-byte slot of the row)
+//   anything else, or forced                                                   -> K_GENERIC_PLANES (element by element)
+// Non-temporal loads and stores from kStreamBytes per field on.  One launch serves all fields; an empty box makes none.
+struct PlanesPlan {
+  KernelChoice k;          // kind K_ROWS_PLANES / K_COLUMNS_PLANES / K_GENERIC_PLANES; vec = bytes per lane (16 / one element); access 0, 1
+  kern::PlanesGeom g;      // g.parts == 0: an empty box, no launch
+  i64 blocks;              // workgroups per field
+  i64 read_lo, read_hi;    // lowest byte read and one past the highest, relative to the first cell of field 0's box (0, 0: nothing read)
+  i64 write_lo, write_hi;  // lowest byte stored and one past the highest, likewise: 0 and the box's span, whatever the form
+};
+PlanesPlan planPlanes(const PlanesRequest& r);
+// Launch it, asynchronous on `stream`; `coef` is device memory whose CONTENTS are read when the kernel runs.  Nothing is allocated,
+// nothing waits; an empty box: no launch.
+void launchPlanes(const PlanesRequest& r, const double* coef, hipStream_t stream, KernelStats* stats = nullptr);
+
+// data-movement launches this process has made so far (launchMoves, launchFieldMoveList, both stages of launchReduce and launchProfile, and launchPlanes; tests count launches per call with it)
 long long dataLaunchCount();
 
 // name (template spelling) of the data-movement kernel launched last by this process, "" before the first launch

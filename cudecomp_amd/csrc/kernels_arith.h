@@ -43,6 +43,24 @@ __device__ __forceinline__ u32x2 addDouble(const u32x2& a, const u32x2& b) {
   return __builtin_bit_cast(u32x2, __builtin_bit_cast(double, a) + __builtin_bit_cast(double, b));
 }
 
+// ---- a + b and a * b on ONE real held as its type (the plane updates, kernels_planes.hip): IEEE for _Float16, float and double;
+// __bf16: RNE-to-bf16 of the fp32 result of the widened operands, as Arith<__bf16> above.  Every result is rounded on its own: no
+// caller's expression is contracted into an fma through these
+template <typename T, int OP> __device__ __forceinline__ T arithReal(T a, T b) {  // OP 0: a + b, 1: a * b, 2: a - b
+#pragma clang fp contract(off)
+  if constexpr (sizeof(T) == 2 && !__is_same(T, _Float16)) {
+    const float x = __uint_as_float((unsigned int)__builtin_bit_cast(unsigned short, a) << 16);
+    const float y = __uint_as_float((unsigned int)__builtin_bit_cast(unsigned short, b) << 16);
+    const float s = OP == 0 ? x + y : OP == 1 ? x * y : x - y;
+    return (__bf16)s;
+  } else {
+    return OP == 0 ? (T)(a + b) : OP == 1 ? (T)(a * b) : (T)(a - b);
+  }
+}
+template <typename T> __device__ __forceinline__ T addReal(T a, T b) { return arithReal<T, 0>(a, b); }
+template <typename T> __device__ __forceinline__ T mulReal(T a, T b) { return arithReal<T, 1>(a, b); }
+template <typename T> __device__ __forceinline__ T subReal(T a, T b) { return arithReal<T, 2>(a, b); }
+
 // a + b over a VB-byte lane payload
 template <typename T, int VB>
 __device__ __forceinline__ Bytes<VB> addPayload(const Bytes<VB>& a, const Bytes<VB>& b) {

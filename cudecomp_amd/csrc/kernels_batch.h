@@ -3,7 +3,7 @@
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip, kernels_wall.hip, kernels_wall_plane.hip;
 // kernels_rotate.hip and sync.hip are launched by the executor (and compiled as one unit, kernels_executor.hip; kernels_fill.hip, kernels_reflect.hip and kernels_reduce.hip -- the reductions of a box, launchReduce -- likewise as kernels_edge.hip,
-// kernels_accumulate.hip and kernels_take.hip as kernels_sum.hip; kernels_profile.hip -- the profiles of a box along one dim, launchProfile -- in two parts, inside kernels_window.hip and kernels_rows.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
+// kernels_accumulate.hip and kernels_take.hip as kernels_sum.hip; kernels_profile.hip -- the profiles of a box along one dim, launchProfile -- in two parts, inside kernels_window.hip and kernels_rows.hip; kernels_planes.hip -- the plane updates of a box along one dim, launchPlanes -- in two parts, inside kernels_lines.hip and kernels_rowlines.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
 // halo phases and transposes), kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) and
 // kernels_field_mirror.hip (the same lists mirrored, with a sign per field: multi-field wall halos) are reached through
 // launchFieldMoveList (kernels.h); kernels_field_wall.hip (the mirrored lists adding an addend per field and layer: multi-field wall
@@ -213,6 +213,37 @@ struct ProfileGeom {
 };
 static_assert(sizeof(ProfileGeom) + sizeof(ReduceFields) + 8 <= 2048, "geometry, the two tables of fields and the workspace stay well under the 4 KB of kernel arguments");
 
+// ---- plane updates of a box of cells along one dim (kernels_planes.hip; interior plane updates, include/cudecomp_interior_planes.h) --
+// The profile's adjoint: every cell of the box is updated IN PLACE with the coefficient of its index k along the kept dim,
+// u <- u + c or u <- u * c, c = scale * the pair at coef[2 * (f * ld + k)] rounded once to the real type.  One stage, no workspace; a
+// launch stores the bytes of the box's cells and no others.
+constexpr int kPlanesAdd = 0, kPlanesMul = 1;  // CUDECOMP_AMD_PLANES_*
+struct PlanesGeom {
+  long long L;                 // entries per field: the extent of the kept dim
+  long long sk;                // rows, element-wise: BYTES between two entries
+  long long row_bytes;         // rows: a row of the contiguous dim; columns: a row of the kept dim (L elements)
+  long long rows;              // rows: rows of one entry; columns: all rows of the box, e1 * e2
+  long long e1, e2;            // columns, element-wise: the two other extents, e1 the one of the smaller stride
+  long long s1, s2;            // their strides in BYTES (rows: s1 between the rows of an entry); columns: multiples of 16
+  long long rows_per_part;     // columns: part p walks the rows [p * rows_per_part, (p + 1) * rows_per_part)
+  long long slots;             // rows, columns: 16-byte slots a row can touch at most
+  long long box_off;           // bytes from a field's pointer to the first cell of the box
+  long long rd_lo, rd_hi;      // the bytes [rd_lo, rd_hi) relative to the first cell of the box may be read
+  long long ld;                // pairs of doubles between the coefficient rows of two fields; 0: all fields share row 0
+  double scale;                // the host factor of every coefficient
+  unsigned int t0, t1;         // rows: tile columns / tile rows of an entry; columns: t0 tile columns
+  unsigned int parts;          // rows, element-wise: parts per entry; columns: parts of the rows; 0: an empty box (no launch)
+  int p0;                      // rows, columns: log2 of the lanes per row
+  int reals;                   // reals per element: 1, or 2 for the complex types
+  int n_fields;
+  int stream;                  // 1 non-temporal loads and stores (KernelChoice::access), 0 default caching
+  int op;                      // kPlanesAdd, kPlanesMul
+};
+struct PlanesFields {
+  char* a[kMaxFields];
+};
+static_assert(sizeof(PlanesGeom) + sizeof(PlanesFields) + 8 <= 2048, "geometry, the table of fields and the coefficients stay well under the 4 KB of kernel arguments");
+
 }  // namespace kern
 
 // ---- what runs: one record per kernel choice ----------------------------------------------------------------------------------
@@ -265,7 +296,10 @@ enum KernelKind {
   K_GENERIC_REDUCE,           // reduce_elements_kernel = 44
   K_ROWS_PROFILE,             // profile_rows_kernel (the kept dim not contiguous: an entry is a set of contiguous rows) = 45
   K_COLUMNS_PROFILE,          // profile_columns_kernel (the kept dim contiguous: a lane owns a 16-byte slot of the row and walks down the rows) = 46
-  K_GENERIC_PROFILE           // profile_elements_kernel = 47
+  K_GENERIC_PROFILE,          // profile_elements_kernel = 47
+  K_ROWS_PLANES,              // planes_rows_kernel (the kept dim not contiguous: one coefficient per row, read-modify-write on the 16-byte grid) = 48
+  K_COLUMNS_PLANES,           // planes_columns_kernel (the kept dim contiguous: a lane owns a 16-byte slot of the row and its coefficients) = 49
+  K_GENERIC_PLANES            // planes_elements_kernel = 50
 };
 struct KernelChoice {
   KernelKind kind;
@@ -276,7 +310,7 @@ struct KernelChoice {
                     // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads;
                     // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it);
                     // reflections and wall-moves: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores;
-                    // reductions and profiles: 0, 1 non-temporal loads;
+                    // reductions and profiles: 0, 1 non-temporal loads; plane updates: 0, 1 non-temporal loads and stores;
                     // field-moves: 0, 1 non-temporal loads and stores; transpose_fields_kernel: 0, 2; adding / taking
                     // field-moves: as additions / takes; mirrored field-moves: as reflections / folds; wall field-moves: as reflections
   ArithType arith;  // additions, folds, wall-moves, reflections that flip the sign bits, mirrored field-moves (whatever their signs):
@@ -366,12 +400,15 @@ constexpr KindTraits kKindTraits[] = {
     {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_PROFILE
     {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_COLUMNS_PROFILE
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_PROFILE
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_PLANES
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_COLUMNS_PLANES
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_PLANES
 };
-static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_PROFILE + 1, "one row per KernelKind");
+static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_PLANES + 1, "one row per KernelKind");
 
 // the row of a kind; a value outside the enum is an internal error, never a read past the table
 inline const KindTraits& kindTraits(KernelKind kind) {
-  if (kind < K_ROWS || kind > K_GENERIC_PROFILE) CD_INTERNAL_ERROR("kernel kind out of range");
+  if (kind < K_ROWS || kind > K_GENERIC_PLANES) CD_INTERNAL_ERROR("kernel kind out of range");
   return kKindTraits[kind];
 }
 inline MoveClass classOf(KernelKind kind) { return kindTraits(kind).cls; }
@@ -486,6 +523,13 @@ void launchProfileRows(const KernelChoice& k, int op, const kern::ProfileGeom& g
 void launchProfileColumnsOrElements(const KernelChoice& k, int op, const kern::ProfileGeom& g, const kern::ReduceFields& fields,
                                     double* work, hipStream_t stream);
 void launchProfileFinal(int op, const kern::ProfileGeom& g, double* results, long long ld, const double* work, hipStream_t stream);
+// kernels_planes.hip (in the units kernels_lines.hip and kernels_rowlines.hip): plane updates of a box of cells along one dim, in
+// place.  k.kind K_ROWS_PLANES, or K_COLUMNS_PLANES / K_GENERIC_PLANES; k.arith the real type; g.op, g.scale and g.ld with `coef`
+// (device memory, read when the kernel runs) say what is added or multiplied.
+void launchPlanesRows(const KernelChoice& k, const kern::PlanesGeom& g, const kern::PlanesFields& fields, const double* coef,
+                      hipStream_t stream);
+void launchPlanesColumnsOrElements(const KernelChoice& k, const kern::PlanesGeom& g, const kern::PlanesFields& fields, const double* coef,
+                                   hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

@@ -209,3 +209,8 @@ void launchLinesBatch(const KernelChoice& k, const kern::Batch& b, unsigned int 
 }
 
 }  // namespace cudecomp
+
+// the plane updates of a box along one dim (kernels_planes.hip, the row kernel) are compiled into this unit: the family cannot be a
+// code object of its own, and this one has the room (kernels_batch.h says why the library keeps the number of its code objects)
+#define CD_PLANES_PART 1
+#include "kernels_planes.hip"

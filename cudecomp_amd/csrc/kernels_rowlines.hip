@@ -212,3 +212,9 @@ void launchRowLinesBatch(const KernelChoice& k, const kern::Batch& b, unsigned i
 }
 
 }  // namespace cudecomp
+
+// the plane updates of a box along one dim (kernels_planes.hip, the column and the element-wise kernel) are compiled into this unit:
+// the family cannot be a code object of its own, and this one has the room (kernels_batch.h says why the library keeps the number of
+// its code objects)
+#define CD_PLANES_PART 2
+#include "kernels_planes.hip"

@@ -126,6 +126,7 @@ module cudecomp
   end enum
   ! cudecomp_interior_reduce.h: the operations of cudecompAmdReduceInterior{X,Y,Z}, and the most fields a call takes
   integer(c_int32_t), parameter :: CUDECOMP_AMD_REDUCE_SUM = 0, CUDECOMP_AMD_REDUCE_DOT = 1, CUDECOMP_AMD_REDUCE_MAX_ABS = 2
+  integer(c_int32_t), parameter :: CUDECOMP_AMD_PLANES_ADD = 0, CUDECOMP_AMD_PLANES_MUL = 1
   integer(c_int32_t), parameter :: CUDECOMP_AMD_MAX_REDUCE_FIELDS = 32
   enum, bind(c)
     enumerator :: CUDECOMP_RESULT_SUCCESS = 0
@@ -815,6 +816,59 @@ module cudecomp
       integer(c_intptr_t), value :: stream
       integer(c_int) :: res
     end function cudecompAmdProfileInteriorZ_C
+
+    ! cudecomp_interior_planes.h: the profile's adjoint -- every interior cell updated in place with the coefficient of its index
+    ! along `dim`.  The C entry points (zero-based dim); the wrappers cudecompAmdApplyPlanesInterior{X,Y,Z} below take dim = 1/2/3
+    function cudecompAmdApplyPlanesInteriorX_C(handle, grid_desc, fields, n_fields, op, dim, coef, ld, scale, dtype, halo_extents, &
+                                               padding, stream) &
+      bind(C, name="cudecompAmdApplyPlanesInteriorX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: fields(*)
+      integer(c_int32_t), value :: n_fields, op, dim
+      type(c_ptr), value :: coef
+      integer(c_int64_t), value :: ld
+      real(c_double), value :: scale
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3), padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdApplyPlanesInteriorX_C
+
+    function cudecompAmdApplyPlanesInteriorY_C(handle, grid_desc, fields, n_fields, op, dim, coef, ld, scale, dtype, halo_extents, &
+                                               padding, stream) &
+      bind(C, name="cudecompAmdApplyPlanesInteriorY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: fields(*)
+      integer(c_int32_t), value :: n_fields, op, dim
+      type(c_ptr), value :: coef
+      integer(c_int64_t), value :: ld
+      real(c_double), value :: scale
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3), padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdApplyPlanesInteriorY_C
+
+    function cudecompAmdApplyPlanesInteriorZ_C(handle, grid_desc, fields, n_fields, op, dim, coef, ld, scale, dtype, halo_extents, &
+                                               padding, stream) &
+      bind(C, name="cudecompAmdApplyPlanesInteriorZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: fields(*)
+      integer(c_int32_t), value :: n_fields, op, dim
+      type(c_ptr), value :: coef
+      integer(c_int64_t), value :: ld
+      real(c_double), value :: scale
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3), padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdApplyPlanesInteriorZ_C
 
     ! cudecomp_halo_wall_value_fields.h: wall values of several pencils, each with a parity and addends of its own
     function cudecompAmdSetWallFieldHalosX_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, sides, values_low, &
@@ -2702,6 +2756,87 @@ contains
     res = cudecompAmdProfileInteriorZ_C(handle, grid_desc, a, b, int(n_fields, c_int32_t), int(op, c_int32_t), &
                                         int(dim - 1, c_int32_t), results, ld, work, int(dtype, c_int), h, p, s)
   end function cudecompAmdProfileInteriorZ
+
+  ! ---- interior plane updates (cudecomp_interior_planes.h): `fields` is an array of n_fields device addresses, `coef` a device
+  ! address laid out as the profile's results, `op` one of CUDECOMP_AMD_PLANES_ADD / _MUL; the cell of interior index k along dim
+  ! (counted from 0) of field f takes scale * the pair at coef(2 * (f * ld + k)); ld = 0: all fields share row 0 ----
+  function cudecompAmdApplyPlanesInteriorX(handle, grid_desc, fields, n_fields, op, dim, coef, ld, scale, dtype, halo_extents, padding, &
+                                           stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(c_ptr) :: fields(*)
+    integer :: n_fields, op
+    integer :: dim  ! 1/2/3 = x/y/z
+    type(c_ptr) :: coef
+    integer(c_int64_t) :: ld
+    real(c_double) :: scale
+    integer :: dtype
+    integer :: halo_extents(3)
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    integer(c_intptr_t) :: s
+    h = int(halo_extents, c_int32_t)
+    p = 0
+    s = 0
+    if (present(padding)) p = int(padding, c_int32_t)
+    if (present(stream)) s = stream
+    res = cudecompAmdApplyPlanesInteriorX_C(handle, grid_desc, fields, int(n_fields, c_int32_t), int(op, c_int32_t), &
+                                            int(dim - 1, c_int32_t), coef, ld, scale, int(dtype, c_int), h, p, s)
+  end function cudecompAmdApplyPlanesInteriorX
+
+  function cudecompAmdApplyPlanesInteriorY(handle, grid_desc, fields, n_fields, op, dim, coef, ld, scale, dtype, halo_extents, padding, &
+                                           stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(c_ptr) :: fields(*)
+    integer :: n_fields, op
+    integer :: dim  ! 1/2/3 = x/y/z
+    type(c_ptr) :: coef
+    integer(c_int64_t) :: ld
+    real(c_double) :: scale
+    integer :: dtype
+    integer :: halo_extents(3)
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    integer(c_intptr_t) :: s
+    h = int(halo_extents, c_int32_t)
+    p = 0
+    s = 0
+    if (present(padding)) p = int(padding, c_int32_t)
+    if (present(stream)) s = stream
+    res = cudecompAmdApplyPlanesInteriorY_C(handle, grid_desc, fields, int(n_fields, c_int32_t), int(op, c_int32_t), &
+                                            int(dim - 1, c_int32_t), coef, ld, scale, int(dtype, c_int), h, p, s)
+  end function cudecompAmdApplyPlanesInteriorY
+
+  function cudecompAmdApplyPlanesInteriorZ(handle, grid_desc, fields, n_fields, op, dim, coef, ld, scale, dtype, halo_extents, padding, &
+                                           stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(c_ptr) :: fields(*)
+    integer :: n_fields, op
+    integer :: dim  ! 1/2/3 = x/y/z
+    type(c_ptr) :: coef
+    integer(c_int64_t) :: ld
+    real(c_double) :: scale
+    integer :: dtype
+    integer :: halo_extents(3)
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    integer(c_intptr_t) :: s
+    h = int(halo_extents, c_int32_t)
+    p = 0
+    s = 0
+    if (present(padding)) p = int(padding, c_int32_t)
+    if (present(stream)) s = stream
+    res = cudecompAmdApplyPlanesInteriorZ_C(handle, grid_desc, fields, int(n_fields, c_int32_t), int(op, c_int32_t), &
+                                            int(dim - 1, c_int32_t), coef, ld, scale, int(dtype, c_int), h, p, s)
+  end function cudecompAmdApplyPlanesInteriorZ
 
   subroutine halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
     integer(c_int32_t), intent(out) :: h(3), p(3)

@@ -633,8 +633,25 @@ cudecompResult_t cudecompExtDescribeProfile3D(uint64_t a_address, uint64_t b_add
                                               int32_t keep, const int64_t extent[3], const int64_t strides[3],
                                               int64_t readable_before, int64_t readable_after, int32_t force, int64_t out[8]);
 
+/* One box of one field through the plane-update kernels of cudecompAmdApplyPlanesInterior{X,Y,Z} (cudecomp_interior_planes.h;
+ * csrc/kernels.h launchPlanes, kernels_planes.hip): cudecompExtProfile3D's box, updated IN PLACE -- the cell of index k along
+ * extent[keep] becomes u + c (op 0) or u * c (op 1), c = scale * (coef[2k], coef[2k + 1]) (device memory, extent[keep] pairs, read
+ * when the kernel runs).  readable_before, readable_after and force as for cudecompExtReduce3D.  *kernel_class (optional): 0 the row
+ * or the column kernel, 2 element-wise, -1 no launch (an empty box).
+ *
+ * cudecompExtDescribePlanes3D answers how that call would run, without a device and without a launch.  out[7] = {kind
+ * (csrc/kernels_batch.h KernelKind: 48 planes_rows_kernel, 49 planes_columns_kernel, 50 planes_elements_kernel), bytes per lane (16 /
+ * one element), workgroups, read_lo, read_hi (the lowest byte read and one past the highest, relative to a), write_lo, write_hi (the
+ * lowest byte stored and one past the highest: 0 and the box's span)}. */
+cudecompResult_t cudecompExtPlanes3D(void* a, cudecompDataType_t dtype, int32_t op, int32_t keep, const int64_t extent[3],
+                                     const int64_t strides[3], int64_t readable_before, int64_t readable_after, const double* coef,
+                                     double scale, int32_t force, int32_t* kernel_class, hipStream_t stream);
+cudecompResult_t cudecompExtDescribePlanes3D(uint64_t a_address, cudecompDataType_t dtype, int32_t op, int32_t keep,
+                                             const int64_t extent[3], const int64_t strides[3], int64_t readable_before,
+                                             int64_t readable_after, int32_t force, int64_t out[7]);
+
 /* Data-movement kernel launches this process has made so far through the kernel layer (launchMoves,
- * launchFieldMoveList and both stages of launchReduce and of launchProfile; the signal / wait kernels and the copy-engine copies of the transports are not counted -- the chunk copies the
+ * launchFieldMoveList, both stages of launchReduce and of launchProfile, and launchPlanes; the signal / wait kernels and the copy-engine copies of the transports are not counted -- the chunk copies the
  * one-sided transport makes with the row-copy kernel between ranks that share a GPU go through launchMoves and are).  Tests take
  * the difference around a call. */
 cudecompResult_t cudecompExtDataLaunchCount(int64_t* launches);
