@@ -178,7 +178,7 @@ EXT_SYMBOLS = ["cudecompExtGetTransposePlan", "cudecompExtGetHaloPlan", "cudecom
                "cudecompExtRunWallFieldMoves", "cudecompExtDescribeWallFieldMoves", "cudecompExtPlanHaloWallValueFields",
                "cudecompExtPlanHaloWallValues", "cudecompExtWall3D", "cudecompExtPlanHaloWallPlanes", "cudecompExtWallPlane3D",
                "cudecompExtReduce3D", "cudecompExtDescribeReduce3D", "cudecompExtProfile3D", "cudecompExtDescribeProfile3D",
-               "cudecompExtPlanes3D", "cudecompExtDescribePlanes3D",
+               "cudecompExtPlanes3D", "cudecompExtDescribePlanes3D", "cudecompExtCombine3D", "cudecompExtDescribeCombine3D",
                "cudecompExtSyncEpochBegin", "cudecompExtSyncSignal",
                "cudecompExtSyncWait", "cudecompExtTagPages", "cudecompExtCheckPages", "cudecompExtChecksum"]
 MAX_FLAGS, FLAG_SCALE = 64, 16  # csrc/kernels.h: kMaxFlags, kFlagScale
@@ -224,6 +224,9 @@ PROFILE_MAX_PARTS = 1024  # csrc/kernels_batch.h kProfileMaxParts: parts per ent
 # include/cudecomp_interior_planes.h: interior plane updates (the profile's adjoint: a coefficient per plane added or multiplied in place)
 INTERIOR_PLANES_SYMBOLS = ["cudecompAmdApplyPlanesInteriorX", "cudecompAmdApplyPlanesInteriorY", "cudecompAmdApplyPlanesInteriorZ"]
 PLANES_ADD, PLANES_MUL = 0, 1  # CUDECOMP_AMD_PLANES_*
+# include/cudecomp_interior_combine.h: interior combinations (y <- a*x + b*y, the coefficients ratios of doubles in device memory)
+INTERIOR_COMBINE_SYMBOLS = ["cudecompAmdCombineInteriorX", "cudecompAmdCombineInteriorY", "cudecompAmdCombineInteriorZ"]
+COMBINE_AXPY, COMBINE_XPBY, COMBINE_AXPBY, COMBINE_AX = 0, 1, 2, 3  # CUDECOMP_AMD_COMBINE_*
 # include/cudecomp_halo_wall_value_fields.h: multi-field wall values (several pencils, a parity and addends per field)
 AMD_WALL_VALUE_FIELDS_SYMBOLS = ["cudecompAmdSetWallFieldHalosX", "cudecompAmdSetWallFieldHalosY", "cudecompAmdSetWallFieldHalosZ"]
 MAX_WALL_VALUE_FIELDS = 32  # CUDECOMP_AMD_MAX_WALL_VALUE_FIELDS
@@ -329,6 +332,13 @@ def lib():
             getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, i32, i32, pf64, i64, C.c_double, i32, pi32, pi32, vp]
         L.cudecompExtPlanes3D.argtypes = [vp, i32, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, vp, C.c_double, i32, pi32, vp]
         L.cudecompExtDescribePlanes3D.argtypes = [C.c_uint64, i32, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, i32, C.POINTER(i64)]
+        for name in INTERIOR_COMBINE_SYMBOLS:
+            getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), i32, i32, vp, vp, C.c_double, vp, vp, C.c_double, i32,
+                                         i32, pi32, pi32, vp]
+        L.cudecompExtCombine3D.argtypes = [vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, vp, vp, C.c_double, vp, vp,
+                                           C.c_double, i32, pi32, vp]
+        L.cudecompExtDescribeCombine3D.argtypes = [C.c_uint64, C.c_uint64, i32, i32, C.POINTER(i64), C.POINTER(i64), i64, i64, i32,
+                                                   C.POINTER(i64)]
         for name in AMD_FIELDS_SYMBOLS:  # (the update's arguments with the list of fields and its length in the place of `input`)
             getattr(L, name).argtypes = [vp, vp, C.POINTER(vp), i32, vp, i32, pi32, C.POINTER(C.c_bool), i32, pi32, vp]
         L.cudecompExtPlanHaloFields.argtypes = [C.POINTER(ExtGridSpec), i32, i32, pi32, C.POINTER(C.c_bool), i32, pi32, i32, i32,
@@ -682,6 +692,20 @@ def cudecompAmdApplyPlanesInterior(axis, handle, gd, fields, op, dim, coef, ld, 
     n = n_fields if n_fields is not None else (len(fields) if fields is not None else 0)
     cf = C.cast(C.c_void_p(coef or None), C.POINTER(C.c_double))
     _check(getattr(lib(), name)(handle, gd, ptrs, int(n), int(op), int(dim), cf, int(ld), float(scale), dtype, _i3(halo_extents),
+                                _i3(padding), stream), name)
+
+
+def cudecompAmdCombineInterior(axis, handle, gd, y, x, op, dtype, halo_extents, padding=None, a_num=None, a_den=None, a_scale=1.0,
+                               b_num=None, b_den=None, b_scale=1.0, coef_stride=0, stream=None, n_fields=None):
+    """cudecompAmdCombineInterior{X,Y,Z} (cudecomp_interior_combine.h): every interior cell of every field of `y` (device addresses)
+    becomes a * x + y (COMBINE_AXPY), x + b * y (COMBINE_XPBY), a * x + b * y (COMBINE_AXPBY) or a * x (COMBINE_AX), with
+    a = (a_scale * a_num[2i + c]) / a_den[2i] of the DEVICE arrays at the addresses a_num, a_den (None: the pair (1, 0) / no
+    division), i = f * coef_stride; b likewise.  Arguments are passed as they are: the library makes the checks."""
+    name = "cudecompAmdCombineInterior" + "XYZ"[axis]
+    arr = lambda v: None if v is None else (C.c_void_p * max(len(v), 1))(*[q or None for q in v])
+    n = n_fields if n_fields is not None else (len(y) if y is not None else 0)
+    _check(getattr(lib(), name)(handle, gd, arr(y), arr(x), int(n), int(op), a_num or None, a_den or None, float(a_scale),
+                                b_num or None, b_den or None, float(b_scale), int(coef_stride), dtype, _i3(halo_extents),
                                 _i3(padding), stream), name)
 
 
@@ -1164,6 +1188,31 @@ def cudecompExtDescribePlanes3D(a_address, dtype, op, keep, extent, strides, rea
     _check(lib().cudecompExtDescribePlanes3D(int(a_address), dtype, int(op), int(keep), v(extent), v(strides), int(readable_before),
                                              int(readable_after), int(force), out), "cudecompExtDescribePlanes3D")
     return dict(zip(("kind", "vec", "blocks", "read_lo", "read_hi", "write_lo", "write_hi"), [int(x) for x in out]))
+
+
+def cudecompExtCombine3D(y, x, dtype, op, extent, strides, readable_before=0, readable_after=0, a_num=None, a_den=None, a_scale=1.0,
+                         b_num=None, b_den=None, b_scale=1.0, force=0, stream=None):
+    """One box of one field through the combination kernels (cudecompExtReduce3D's box, the same in x and in y; y's cells become
+    a * x + y, x + b * y, a * x + b * y or a * x by `op`, a = (a_scale * a_num[c]) / a_den[0] of device memory, None: (1, 0) / no
+    division); returns the kernel class (0 rows, 2 element-wise, -1 no launch)."""
+    cls = C.c_int32(-1)
+    v = lambda q: (C.c_int64 * 3)(*[int(k) for k in q])
+    _check(lib().cudecompExtCombine3D(y, x, dtype, int(op), v(extent), v(strides), int(readable_before), int(readable_after),
+                                      a_num or None, a_den or None, float(a_scale), b_num or None, b_den or None, float(b_scale),
+                                      int(force), C.byref(cls), stream), "cudecompExtCombine3D")
+    return cls.value
+
+
+def cudecompExtDescribeCombine3D(y_address, x_address, dtype, op, extent, strides, readable_before=0, readable_after=0, force=0):
+    """How cudecompExtCombine3D would run that box (no launch, no GPU): {kind, vec, blocks, read_x_lo, read_x_hi, read_y_lo,
+    read_y_hi, write_lo, write_hi, row_bytes, rows, last_row_bytes}; the byte ranges relative to x_address / y_address."""
+    out = (C.c_int64 * 12)()
+    v = lambda q: (C.c_int64 * 3)(*[int(k) for k in q])
+    _check(lib().cudecompExtDescribeCombine3D(int(y_address), int(x_address), dtype, int(op), v(extent), v(strides),
+                                              int(readable_before), int(readable_after), int(force), out),
+           "cudecompExtDescribeCombine3D")
+    return dict(zip(("kind", "vec", "blocks", "read_x_lo", "read_x_hi", "read_y_lo", "read_y_hi", "write_lo", "write_hi", "row_bytes",
+                     "rows", "last_row_bytes"), [int(q) for q in out]))
 
 
 def cudecompExtRotateWalk(nb, walk=-1):

@@ -1256,6 +1256,88 @@ CD_DEFINE_APPLY_PLANES_INTERIOR(cudecompAmdApplyPlanesInteriorX, 0)
 CD_DEFINE_APPLY_PLANES_INTERIOR(cudecompAmdApplyPlanesInteriorY, 1)
 CD_DEFINE_APPLY_PLANES_INTERIOR(cudecompAmdApplyPlanesInteriorZ, 2)
 
+// cudecomp_interior_combine.h: y <- a * x + b * y over the interior, the coefficients ratios of doubles in device memory.  Local: the
+// pencil from makePencil, the interior box as the plane updates derive it.  Checks in the header's order, on the host.
+static cudecompResult_t combineInteriorEntry(int axis, cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const y[],
+                                             const void* const x[], int32_t n_fields, int32_t op, const double* a_num, const double* a_den,
+                                             double a_scale, const double* b_num, const double* b_den, double b_scale, int32_t coef_stride,
+                                             cudecompDataType_t dtype, const int32_t halo_extents[], const int32_t padding[],
+                                             hipStream_t stream) {
+  try {
+    checkHandle(handle);
+    checkGridDesc(handle, grid_desc);
+    checkDataType(dtype);
+    if (!halo_extents) CD_INVALID_USAGE("halo_extents argument cannot be null");
+    const Pencil p = makePencil(grid_desc->shape, grid_desc->pidx, axis, halo_extents, padding);  // (negative halos, padding)
+    if (n_fields < 1 || n_fields > CUDECOMP_AMD_MAX_REDUCE_FIELDS) CD_INVALID_USAGE("n_fields argument out of range");
+    if (op < CUDECOMP_AMD_COMBINE_AXPY || op > CUDECOMP_AMD_COMBINE_AX) CD_INVALID_USAGE("op argument out of range");
+    if (!y) CD_INVALID_USAGE("y argument cannot be null");
+    for (int32_t f = 0; f < n_fields; ++f)
+      if (!y[f]) CD_INVALID_USAGE("y argument cannot hold a null entry");
+    if (!x) CD_INVALID_USAGE("x argument cannot be null");
+    for (int32_t f = 0; f < n_fields; ++f)
+      if (!x[f]) CD_INVALID_USAGE("x argument cannot hold a null entry");
+    for (int32_t f = 0; f < n_fields; ++f)
+      for (int32_t e = 0; e < f; ++e)
+        if (y[e] == y[f]) CD_INVALID_USAGE("y argument cannot hold the same field twice");
+    for (int32_t f = 0; f < n_fields; ++f)
+      for (int32_t e = 0; e < n_fields; ++e)
+        if (x[e] == y[f]) CD_INVALID_USAGE("x argument cannot hold a field of the y argument");
+    if (coef_stride < 0 || coef_stride > 1) CD_INVALID_USAGE("coef_stride argument is neither 0 nor 1");
+    const auto aligned = [](const double* q) { return reinterpret_cast<uintptr_t>(q) % 8 == 0; };  // (NULL is)
+    if (op != CUDECOMP_AMD_COMBINE_XPBY) {
+      if (!aligned(a_num)) CD_INVALID_USAGE("a_num argument must be 8-byte aligned");
+      if (!aligned(a_den)) CD_INVALID_USAGE("a_den argument must be 8-byte aligned");
+    }
+    if (op == CUDECOMP_AMD_COMBINE_XPBY || op == CUDECOMP_AMD_COMBINE_AXPBY) {
+      if (!aligned(b_num)) CD_INVALID_USAGE("b_num argument must be 8-byte aligned");
+      if (!aligned(b_den)) CD_INVALID_USAGE("b_den argument must be 8-byte aligned");
+    }
+
+    CombineRequest r;
+    r.y = y;
+    r.x = x;
+    r.n_fields = n_fields;
+    r.op = op;
+    r.es = elementSize(dtype);
+    r.arith = arithOf(dtype);
+    i64 stride = 1;
+    for (int i = 0; i < 3; ++i) {  // memory order: the interior is what is left of the shape without both halos and the padding
+      const int ga = p.order[i];
+      r.extent[i] = std::max<i64>((i64)p.shape[i] - 2 * (i64)p.halo[ga] - p.pad[ga], 0);
+      r.strides[i] = stride;
+      r.box_off += p.halo[ga] * stride;
+      stride *= p.shape[i];
+    }
+    if (p.size == 0) r.box_off = 0;  // (some extent is 0: nothing is touched)
+    r.a_scale = a_scale, r.b_scale = b_scale;
+    r.coef_stride = coef_stride;
+    const bool empty = r.extent[0] * r.extent[1] * r.extent[2] == 0;
+    r.readable_before = r.box_off * r.es;
+    i64 last = 0;
+    for (int i = 0; i < 3; ++i) last += (r.extent[i] - 1) * r.strides[i];
+    r.readable_after = empty ? 0 : (p.size - r.box_off - last - 1) * (i64)r.es;
+    r.tuning = &handle->tuning;
+    if (empty) return CUDECOMP_RESULT_SUCCESS;  // no launch, and no device needed for none
+    ensureDevice(handle);
+    launchCombine(r, a_num, a_den, b_num, b_den, stream);
+  }
+  CD_API_CATCH()
+  return CUDECOMP_RESULT_SUCCESS;
+}
+
+#define CD_DEFINE_COMBINE_INTERIOR(NAME, AXIS)                                                                                   \
+  cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* const y[], const void* const x[],          \
+                        int32_t n_fields, int32_t op, const double* a_num, const double* a_den, double a_scale,                  \
+                        const double* b_num, const double* b_den, double b_scale, int32_t coef_stride, cudecompDataType_t dtype, \
+                        const int32_t halo_extents[], const int32_t padding[], hipStream_t stream) {                             \
+    return combineInteriorEntry(AXIS, handle, grid_desc, y, x, n_fields, op, a_num, a_den, a_scale, b_num, b_den, b_scale,      \
+                                coef_stride, dtype, halo_extents, padding, stream);                                              \
+  }
+CD_DEFINE_COMBINE_INTERIOR(cudecompAmdCombineInteriorX, 0)
+CD_DEFINE_COMBINE_INTERIOR(cudecompAmdCombineInteriorY, 1)
+CD_DEFINE_COMBINE_INTERIOR(cudecompAmdCombineInteriorZ, 2)
+
 // cudecomp_halo_fold.h: the ghost cells the reflection writes are added onto their mirror images
 #define CD_DEFINE_HALO_FOLD(NAME, AXIS)                                                                                     \
   cudecompResult_t NAME(cudecompHandle_t handle, cudecompGridDesc_t grid_desc, void* input, cudecompDataType_t dtype,       \

@@ -1024,6 +1024,76 @@ cudecompResult_t cudecompExtDescribePlanes3D(uint64_t a_address, cudecompDataTyp
   });
 }
 
+// one box of one field through the combination kernels (kernels.h launchCombine) / how it would run (planCombine)
+static CombineRequest combineRequestOf(void* const* y, const void* const* x, cudecompDataType_t dtype, int32_t op, const int64_t extent[3],
+                                       const int64_t strides[3], int64_t readable_before, int64_t readable_after, double a_scale,
+                                       double b_scale, const KernelTuning* tuning) {
+  if (!extent || !strides) CD_INVALID_USAGE("null argument");
+  if (op < 0 || op > 3) CD_INVALID_USAGE("op must be 0 (axpy), 1 (xpby), 2 (axpby) or 3 (ax)");
+  if (readable_before < 0 || readable_after < 0) CD_INVALID_USAGE("readable_before and readable_after cannot be negative");
+  CombineRequest r;
+  r.y = y;
+  r.x = x;
+  r.n_fields = 1;
+  r.op = op;
+  r.es = elementSize(dtype);  // (INVALID_USAGE for an unknown type)
+  r.arith = arithOf(dtype);
+  for (int i = 0; i < 3; ++i) {
+    if (extent[i] < 0 || strides[i] < 0) CD_INVALID_USAGE("extents and strides of a combination cannot be negative");
+    r.extent[i] = extent[i];
+    r.strides[i] = strides[i];
+  }
+  r.readable_before = readable_before;
+  r.readable_after = readable_after;
+  r.a_scale = a_scale, r.b_scale = b_scale;
+  r.coef_stride = 0;
+  r.tuning = tuning;
+  return r;
+}
+
+cudecompResult_t cudecompExtCombine3D(void* y, const void* x, cudecompDataType_t dtype, int32_t op, const int64_t extent[3],
+                                      const int64_t strides[3], int64_t readable_before, int64_t readable_after, const double* a_num,
+                                      const double* a_den, double a_scale, const double* b_num, const double* b_den, double b_scale,
+                                      int32_t force, int32_t* kernel_class, hipStream_t stream) {
+  return guarded([&] {
+    if (!y || !x) CD_INVALID_USAGE("null argument");
+    if (x == y) CD_INVALID_USAGE("x and y cannot be the same field");
+    const KernelTuning t = tuningOfForce(force);
+    const CombineRequest r = combineRequestOf(&y, &x, dtype, op, extent, strides, readable_before, readable_after, a_scale, b_scale, &t);
+    KernelStats st;
+    launchCombine(r, a_num, a_den, b_num, b_den, stream, &st);
+    if (kernel_class) {
+      *kernel_class = -1;
+      for (int c = 0; c < MOVE_CLASS_COUNT; ++c)
+        if (st.launches[c]) *kernel_class = c;
+    }
+  });
+}
+
+cudecompResult_t cudecompExtDescribeCombine3D(uint64_t y_address, uint64_t x_address, cudecompDataType_t dtype, int32_t op,
+                                              const int64_t extent[3], const int64_t strides[3], int64_t readable_before,
+                                              int64_t readable_after, int32_t force, int64_t out[12]) {
+  return guarded([&] {
+    if (!out) CD_INVALID_USAGE("null argument");
+    void* const y = reinterpret_cast<void*>(y_address);
+    const void* const x = reinterpret_cast<const void*>(x_address);
+    const KernelTuning t = tuningOfForce(force);
+    const CombinePlan p = planCombine(combineRequestOf(&y, &x, dtype, op, extent, strides, readable_before, readable_after, 1.0, 1.0, &t));
+    out[0] = p.k.kind;
+    out[1] = p.k.vec;
+    out[2] = p.blocks;
+    out[3] = p.read_x_lo;
+    out[4] = p.read_x_hi;
+    out[5] = p.read_y_lo;
+    out[6] = p.read_y_hi;
+    out[7] = p.write_lo;
+    out[8] = p.write_hi;
+    out[9] = p.g.blocks ? (p.k.kind == K_ROWS_COMBINE ? p.g.row_bytes : 0) : 0;
+    out[10] = p.g.blocks ? (p.k.kind == K_ROWS_COMBINE ? p.g.rows * p.g.planes : 0) : 0;
+    out[11] = p.g.blocks ? (p.k.kind == K_ROWS_COMBINE ? p.g.last_row_bytes : 0) : 0;
+  });
+}
+
 cudecompResult_t cudecompExtPlanHaloWallPlanes(const cudecompExtGridSpec_t* grid, int32_t rank, int32_t axis, const int32_t halo[],
                                                const bool periods[], int32_t dim, const int32_t pad[], cudecompDataType_t dtype,
                                                int32_t parity, int32_t centering, int32_t sides, uint64_t pencil_address,

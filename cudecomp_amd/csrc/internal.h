@@ -21,6 +21,7 @@
 #include "cudecomp_interior_reduce.h"
 #include "cudecomp_interior_profile.h"
 #include "cudecomp_interior_planes.h"
+#include "cudecomp_interior_combine.h"
 #include "cudecomp_halo_fields.h"
 #include "cudecomp_halo_accumulate_fields.h"
 #include "cudecomp_halo_wall_fields.h"

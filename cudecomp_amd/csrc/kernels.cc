@@ -756,6 +756,8 @@ void spellKernelName(const KernelChoice& k) {
     case K_ROWS_PLANES:
     case K_COLUMNS_PLANES:
     case K_GENERIC_PLANES: break;  // (launchPlanes likewise: planes_rows_kernel / planes_columns_kernel<T,MODE>, planes_elements_kernel<T>)
+    case K_ROWS_COMBINE:
+    case K_GENERIC_COMBINE: break;  // (launchCombine likewise: combine_rows_kernel<T,OP,complex>, combine_elements_kernel<T>)
   }
 }
 
@@ -856,6 +858,8 @@ void launchBatch(const Launch& l, const Move3D* moves, const void* fill_value, c
     case K_ROWS_PLANES:
     case K_COLUMNS_PLANES:
     case K_GENERIC_PLANES: CD_INTERNAL_ERROR("plane updates are launched by launchPlanes");
+    case K_ROWS_COMBINE:
+    case K_GENERIC_COMBINE: CD_INTERNAL_ERROR("combinations are launched by launchCombine");
   }
 }
 
@@ -1312,6 +1316,55 @@ void launchFieldMoveList(const FieldMoveList& list, hipStream_t stream, KernelSt
 // ---------------------------------------------------------------------------------------------
 // reductions of a box of cells (kernels_reduce.hip)
 // ---------------------------------------------------------------------------------------------
+// The dims of a box that count, by stride, contiguous ones merged (rowVectors' rule for copies): e[0] x e[1] x e[2] elements at strides
+// s[] with e[0] the row, `nd` of them longer than a cell.  Answers whether the box has rows at all: a dim of stride 1.
+static bool mergeBoxDims(const i64 (&extent)[3], const i64 (&strides)[3], i64 (&e)[3], i64 (&s)[3], int& nd) {
+  e[0] = e[1] = e[2] = 1, s[0] = s[1] = s[2] = 0;
+  nd = 0;
+  int unit = -1;  // a dim of stride 1 that is one cell long is still the row (a pencil one cell thick along its fastest axis)
+  for (int i = 0; i < 3; ++i) {
+    if (extent[i] > 1) e[nd] = extent[i], s[nd] = strides[i], ++nd;
+    else if (strides[i] == 1) unit = i;
+  }
+  for (int i = 0; i < nd; ++i)
+    for (int j = i + 1; j < nd; ++j)
+      if (s[j] < s[i]) std::swap(s[i], s[j]), std::swap(e[i], e[j]);
+  if (nd > 0 && nd < 3 && s[0] != 1 && unit >= 0) {  // rows of one cell
+    for (int i = nd; i > 0; --i) e[i] = e[i - 1], s[i] = s[i - 1];
+    e[0] = 1, s[0] = 1, ++nd;
+  }
+  const bool rows = nd == 0 || s[0] == 1;
+  if (nd == 0) s[0] = 1;
+  while (rows && nd >= 2 && s[1] == e[0]) {  // the next dim follows without a gap: one longer row
+    e[0] *= e[1];
+    e[1] = e[2], s[1] = s[2];
+    e[2] = 1, s[2] = 0;
+    --nd;
+  }
+  if (rows && nd == 3 && s[2] == e[1] * s[1]) e[1] *= e[2], e[2] = 1, s[2] = 0, --nd;
+  return rows;
+}
+
+// The row walk of a merged box on the 16-byte grid, for ReduceGeom and CombineGeom alike: rows of e[0] elements, a box that is one
+// long row cut into rows of kReduceChunkBytes (the last one what is left); 16-byte slots a row can touch, lanes per row, tiles.
+template <typename Geom> static void setRowWalk(Geom& g, const i64 (&e)[3], const i64 (&s)[3], int nd, int es) {
+  g.row_bytes = g.last_row_bytes = e[0] * es;
+  g.rows = e[1], g.planes = e[2];
+  g.s1 = s[1] * es, g.s2 = s[2] * es;
+  if (nd <= 1 && g.row_bytes > kReduceChunkBytes) {
+    g.rows = (g.row_bytes + kReduceChunkBytes - 1) / kReduceChunkBytes;
+    g.last_row_bytes = g.row_bytes - (g.rows - 1) * kReduceChunkBytes;
+    g.row_bytes = g.s1 = kReduceChunkBytes;
+  }
+  g.slots = (g.row_bytes + 14 + 15) / 16;
+  g.p0 = std::min(8, ilog2ceil(g.slots));
+  const i64 lpr = 1LL << g.p0, rows_per_tile = (i64)(kThreads >> g.p0) * kRowsUnroll;
+  const i64 t0 = (g.slots + lpr - 1) / lpr, t1 = (g.rows + rows_per_tile - 1) / rows_per_tile;
+  if (t0 > 0xffffffffLL || t1 > 0xffffffffLL) CD_NOT_SUPPORTED("a box of more than 2^32 - 1 tiles along one dim");
+  g.t0 = (unsigned int)t0, g.t1 = (unsigned int)t1;
+  g.tiles = (unsigned long long)t0 * (unsigned long long)t1 * (unsigned long long)g.planes;
+}
+
 ReducePlan planReduce(const ReduceRequest& r) {
   if (r.n_fields < 1 || r.n_fields > kMaxFields || !r.a) CD_INTERNAL_ERROR("a reduction of 1 .. kMaxFields fields");
   if (r.op != kReduceSum && r.op != kReduceDot && r.op != kReduceMaxAbs) CD_INTERNAL_ERROR("reduction operation out of range");
@@ -1346,28 +1399,9 @@ ReducePlan planReduce(const ReduceRequest& r) {
   p.k.access = ((cells * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming) ? 1 : 0;
 
   // the dims that count, by stride; contiguous ones merged
-  i64 e[3] = {1, 1, 1}, s[3] = {0, 0, 0};
-  int nd = 0, unit = -1;  // `unit`: a dim of stride 1 that is one cell long is still the row (a pencil one cell thick along its fastest axis)
-  for (int i = 0; i < 3; ++i) {
-    if (r.extent[i] > 1) e[nd] = r.extent[i], s[nd] = r.strides[i], ++nd;
-    else if (r.strides[i] == 1) unit = i;
-  }
-  for (int i = 0; i < nd; ++i)
-    for (int j = i + 1; j < nd; ++j)
-      if (s[j] < s[i]) std::swap(s[i], s[j]), std::swap(e[i], e[j]);
-  if (nd > 0 && nd < 3 && s[0] != 1 && unit >= 0) {  // rows of one cell
-    for (int i = nd; i > 0; --i) e[i] = e[i - 1], s[i] = s[i - 1];
-    e[0] = 1, s[0] = 1, ++nd;
-  }
-  bool rows = nd == 0 || s[0] == 1;
-  if (nd == 0) s[0] = 1;
-  while (rows && nd >= 2 && s[1] == e[0]) {  // the next dim follows without a gap: one longer row
-    e[0] *= e[1];
-    e[1] = e[2], s[1] = s[2];
-    e[2] = 1, s[2] = 0;
-    --nd;
-  }
-  if (rows && nd == 3 && s[2] == e[1] * s[1]) e[1] *= e[2], e[2] = 1, s[2] = 0, --nd;
+  i64 e[3], s[3];
+  int nd;
+  bool rows = mergeBoxDims(r.extent, r.strides, e, s, nd);
   // the row kernel's lanes lie on the 16-byte grid of `a`: every field on a boundary of its real type; the second operand of a
   // DOT at the same phase of that grid; a complex DOT pairs real and imaginary part inside one vector
   for (int f = 0; f < r.n_fields && rows; ++f) {
@@ -1395,21 +1429,7 @@ ReducePlan planReduce(const ReduceRequest& r) {
   p.k.kind = K_ROWS_REDUCE;
   p.k.vec = 16;
   g.stream = p.k.access;
-  g.row_bytes = g.last_row_bytes = e[0] * es;
-  g.rows = e[1], g.planes = e[2];
-  g.s1 = s[1] * es, g.s2 = s[2] * es;
-  if (nd <= 1 && g.row_bytes > kReduceChunkBytes) {  // one long row: rows of kReduceChunkBytes, the last one what is left
-    g.rows = (g.row_bytes + kReduceChunkBytes - 1) / kReduceChunkBytes;
-    g.last_row_bytes = g.row_bytes - (g.rows - 1) * kReduceChunkBytes;
-    g.row_bytes = g.s1 = kReduceChunkBytes;
-  }
-  g.slots = (g.row_bytes + 14 + 15) / 16;
-  g.p0 = std::min(8, ilog2ceil(g.slots));
-  const i64 lpr = 1LL << g.p0, rows_per_tile = (i64)(kThreads >> g.p0) * kRowsUnroll;
-  const i64 t0 = (g.slots + lpr - 1) / lpr, t1 = (g.rows + rows_per_tile - 1) / rows_per_tile;
-  if (t0 > 0xffffffffLL || t1 > 0xffffffffLL) CD_NOT_SUPPORTED("a reduction of more than 2^32 - 1 tiles along one dim");
-  g.t0 = (unsigned int)t0, g.t1 = (unsigned int)t1;
-  g.tiles = (unsigned long long)t0 * (unsigned long long)t1 * (unsigned long long)g.planes;
+  setRowWalk(g, e, s, nd, es);
   g.blocks = (unsigned int)std::min<unsigned long long>(g.tiles, kReduceMaxBlocks);
   // what field 0 reads: whole 16-byte vectors from the boundary below the first cell to the boundary above the last, where the
   // readable range holds them; the cells alone where it does not
@@ -1733,6 +1753,120 @@ void launchPlanes(const PlanesRequest& r, const double* coef, hipStream_t stream
   ++g_data_launches;
   if (p.k.kind == K_ROWS_PLANES) launchPlanesRows(p.k, p.g, fields, coef, stream);
   else launchPlanesColumnsOrElements(p.k, p.g, fields, coef, stream);
+  if (stats) {
+    const MoveClass cls = classOf(p.k.kind);
+    stats->launches[cls] += 1;
+    stats->elements[cls] += (i64)r.n_fields * r.extent[0] * r.extent[1] * r.extent[2];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// combinations of two boxes of cells (kernels_combine.hip)
+// ---------------------------------------------------------------------------------------------
+CombinePlan planCombine(const CombineRequest& r) {
+  if (r.n_fields < 1 || r.n_fields > kMaxFields || !r.x || !r.y) CD_INTERNAL_ERROR("a combination of 1 .. kMaxFields fields");
+  if (r.op < kCombineAxpy || r.op > kCombineAx) CD_INTERNAL_ERROR("combination operation out of range");
+  if (r.arith == ARITH_NONE) CD_INTERNAL_ERROR("a combination needs the real type of its elements");
+  if (r.coef_stride != 0 && r.coef_stride != 1) CD_INTERNAL_ERROR("the coefficient stride of a combination is 0 or 1");
+  const int es = r.es, rs = arithBytes(r.arith);
+  if (es != rs && es != 2 * rs) CD_INTERNAL_ERROR("element size does not match the real type");
+  if (es == 2 * rs && r.arith == ARITH_BF16) CD_INTERNAL_ERROR("bf16 has no complex type");
+  if (r.box_off < 0 || r.readable_before < 0 || r.readable_after < 0) CD_INTERNAL_ERROR("negative offset of a combination");
+  const KernelTuning& tuning = r.tuning ? *r.tuning : kDefaultTuning;
+  CombinePlan p;
+  std::memset(&p, 0, sizeof(p));
+  p.k.kind = K_GENERIC_COMBINE;
+  p.k.es = es;
+  p.k.vec = es;
+  p.k.arith = r.arith;
+  CombineGeom& g = p.g;
+  g.reals = es / rs;
+  g.n_fields = r.n_fields;
+  g.op = r.op;
+  g.a_scale = r.a_scale, g.b_scale = r.b_scale;
+  g.coef_stride = r.coef_stride;
+  g.box_off = r.box_off * es;
+  i64 cells = 1, last = 0;  // `last`: the element offset of the box's last cell
+  for (int i = 0; i < 3; ++i) {
+    if (r.extent[i] < 0 || r.strides[i] < 0) CD_INTERNAL_ERROR("negative extent or stride of a combination");
+    cells *= r.extent[i];
+    last += (r.extent[i] - 1) * r.strides[i];
+    g.e[i] = r.extent[i];
+    g.s[i] = r.strides[i];
+  }
+  const i64 span = (last + 1) * es;
+  g.rd_lo = -r.readable_before;
+  g.rd_hi = span + r.readable_after;
+  if (cells == 0) return p;  // (no launch: g.blocks == 0)
+  const bool reads_y = r.op != kCombineAx;
+  p.k.access = ((cells * es >= kStreamBytes || tuning.force_streaming) && !tuning.no_streaming) ? 1 : 0;
+
+  // the dims that count, by stride; contiguous ones merged (planReduce's rules)
+  i64 e[3], s[3];
+  int nd;
+  bool rows = mergeBoxDims(r.extent, r.strides, e, s, nd);
+  // the row kernel's lanes lie on the 16-byte grid of y: every field on a boundary of its real type -- a complex one of its element,
+  // whose two reals a lane pairs inside one vector -- and x[f] at the phase of y[f] on that grid
+  const uintptr_t need = (uintptr_t)es;  // (es == rs for the real types)
+  for (int f = 0; f < r.n_fields && rows; ++f) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(r.x[f]), y = reinterpret_cast<uintptr_t>(r.y[f]);
+    if (x % need != 0 || y % need != 0 || (x & 15) != (y & 15)) rows = false;
+  }
+  if (tuning.force_class == MOVE_GENERIC) rows = false;
+  p.write_lo = 0, p.write_hi = span;  // (the first cell of the box is the first stored, the end of its last cell the end of the last)
+
+  if (!rows) {
+    g.p0 = 0;
+    for (int i = 0; i < 3; ++i)
+      if (r.strides[i] == 1 && r.extent[i] > 1) g.p0 = i;
+    const i64 want = (cells + kThreads - 1) / kThreads;
+    g.blocks = (unsigned int)std::min<i64>(std::max<i64>(want, 1), kCombineBlocks);
+    p.read_x_lo = 0, p.read_x_hi = span;
+    p.read_y_lo = 0, p.read_y_hi = reads_y ? span : 0;
+  } else {
+    p.k.kind = K_ROWS_COMBINE;
+    p.k.vec = 16;
+    g.stream = p.k.access;
+    setRowWalk(g, e, s, nd, es);
+    g.blocks = (unsigned int)std::min<unsigned long long>(g.tiles, kCombineBlocks);
+    // what is read of x[0] and of y[0], which share their phase: whole 16-byte vectors from the boundary below the first cell to the
+    // boundary above the last, where the readable range holds them; the cells alone where it does not (planReduce's closed form)
+    const uintptr_t first_cell = reinterpret_cast<uintptr_t>(r.y[0]) + (uintptr_t)g.box_off;
+    const i64 below = (i64)(first_cell & 15), above = (i64)((16 - ((first_cell + (uintptr_t)span) & 15)) & 15);
+    const auto whole = [&](i64 slot) { return slot >= g.rd_lo && slot + 16 <= g.rd_hi; };  // (the kernel's test of a vector)
+    p.read_x_lo = whole(-below) ? -below : 0;
+    p.read_x_hi = whole(span + above - 16) ? span + above : span;
+    if (reads_y) p.read_y_lo = p.read_x_lo, p.read_y_hi = p.read_x_hi;
+  }
+  p.blocks = g.blocks;
+  if (p.blocks * r.n_fields > 0x7fffffffLL) CD_NOT_SUPPORTED("a combination of more than 2^31 - 1 workgroups");
+  return p;
+}
+
+void launchCombine(const CombineRequest& r, const double* a_num, const double* a_den, const double* b_num, const double* b_den,
+                   hipStream_t stream, KernelStats* stats) {
+  const CombinePlan p = planCombine(r);
+  if (p.g.blocks == 0) return;  // an empty box
+  for (int f = 0; f < r.n_fields; ++f) {
+    for (int e = 0; e < f; ++e)
+      if (r.y[e] == r.y[f]) CD_INTERNAL_ERROR("a field is written twice in a combination");
+    for (int e = 0; e < r.n_fields; ++e)
+      if (r.x[e] == r.y[f]) CD_INTERNAL_ERROR("a field is read and written in a combination");
+  }
+  CombineFields fields;
+  std::memset(&fields, 0, sizeof(fields));
+  for (int f = 0; f < r.n_fields; ++f) fields.y[f] = static_cast<char*>(r.y[f]), fields.x[f] = static_cast<const char*>(r.x[f]);
+  const bool uses_a = r.op != kCombineXpby, uses_b = r.op == kCombineXpby || r.op == kCombineAxpby;
+  const CombineCoefs coefs = {uses_a ? a_num : nullptr, uses_a ? a_den : nullptr, uses_b ? b_num : nullptr, uses_b ? b_den : nullptr};
+  if (p.k.kind == K_GENERIC_COMBINE)
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "combine_elements_kernel<%s>", arithName(p.k.arith));
+  else
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "combine_rows_kernel<%s,%d,%s>", arithName(p.k.arith), r.op, p.g.reals == 2 ? "true" : "false");
+  ++g_data_launches;
+  if (p.k.kind == K_GENERIC_COMBINE) launchCombineElements(p.k, p.g, fields, coefs, stream);
+  else if (arithBytes(p.k.arith) == 2) launchCombineRows2(p.k, p.g, fields, coefs, stream);
+  else if (arithBytes(p.k.arith) == 4) launchCombineRows4(p.k, p.g, fields, coefs, stream);
+  else launchCombineRows8(p.k, p.g, fields, coefs, stream);
   if (stats) {
     const MoveClass cls = classOf(p.k.kind);
     stats->launches[cls] += 1;

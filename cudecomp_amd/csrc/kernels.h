@@ -292,7 +292,46 @@ PlanesPlan planPlanes(const PlanesRequest& r);
 // nothing waits; an empty box: no launch.
 void launchPlanes(const PlanesRequest& r, const double* coef, hipStream_t stream, KernelStats* stats = nullptr);
 
-// data-movement launches this process has made so far (launchMoves, launchFieldMoveList, both stages of launchReduce and launchProfile, and launchPlanes; tests count launches per call with it)
+// ---- combinations of two boxes of cells (kernels_combine.hip; include/cudecomp_interior_combine.h) -------------------------------
+// The request: ReduceRequest's box of every field y[f], overwritten with a * x[f] + b * y[f] (kern::kCombineAxpy: a * x + y,
+// kCombineXpby: x + b * y, kCombineAxpby, kCombineAx: a * x, y never read); a = (a_scale * a_num[2i + c]) / a_den[2i], i = f *
+// coef_stride, rounded once to the real type, b likewise; a null num stands for (1.0, 0.0), a null den for no division.  Buffers are
+// only looked at as addresses by the planner.
+struct CombineRequest {
+  void* const* y = nullptr;        // n_fields (1 .. kern::kMaxFields) fields, no null entry, no two equal
+  const void* const* x = nullptr;  // as many; equal entries allowed, none equal to an entry of y
+  int n_fields = 0;
+  int op = 0;                      // kern::kCombineAxpy, kCombineXpby, kCombineAxpby, kCombineAx
+  int es = 0;                      // element size in bytes
+  ArithType arith = ARITH_NONE;    // the real type the elements consist of
+  i64 extent[3] = {0, 0, 0};       // the box, in elements; strides non-negative; the same in x[f] and y[f]
+  i64 strides[3] = {0, 0, 0};
+  i64 box_off = 0;                 // elements from a field's pointer to the first cell of the box
+  i64 readable_before = 0, readable_after = 0;  // as ReduceRequest's, of x[f] and of y[f] alike
+  double a_scale = 1.0, b_scale = 1.0;
+  int coef_stride = 0;             // 0: all fields share pair 0; 1: field f takes pair f
+  const KernelTuning* tuning = nullptr;         // force_class == MOVE_GENERIC the element-wise kernel; force_streaming, no_streaming
+};
+// HOW a request runs (pure host code, no device needed).  Rows -- lanes on the 16-byte grid of memory, K_ROWS_COMBINE -- when the box
+// has a contiguous dim, every x[f] and y[f] sits on a boundary of its real type (complex types: of its element) and x[f] and y[f]
+// share their phase on the 16-byte grid; element by element (K_GENERIC_COMBINE) otherwise, or forced.  Contiguous dims are merged by
+// planReduce's rules, and a box that is one long row is cut into rows of kern::kReduceChunkBytes.  Non-temporal loads and stores from
+// kStreamBytes per field on.  One launch serves all fields; an empty box makes none.
+struct CombinePlan {
+  KernelChoice k;              // kind K_ROWS_COMBINE / K_GENERIC_COMBINE; vec = bytes per lane (16 / one element); access 0, 1
+  kern::CombineGeom g;         // g.blocks == 0: an empty box, no launch
+  i64 blocks;                  // workgroups per field
+  i64 read_x_lo, read_x_hi;    // lowest byte of x[0] read and one past the highest, relative to the first cell of its box (0, 0: nothing read)
+  i64 read_y_lo, read_y_hi;    // the same of y[0]; AX: 0, 0
+  i64 write_lo, write_hi;      // lowest byte of y[0] stored and one past the highest, likewise: 0 and the box's span, whatever the form
+};
+CombinePlan planCombine(const CombineRequest& r);
+// Launch it, asynchronous on `stream`; the four arrays are device memory whose CONTENTS are read when the kernel runs, those of the
+// coefficient the op does not use are not passed on.  Nothing is allocated, nothing waits; an empty box: no launch.
+void launchCombine(const CombineRequest& r, const double* a_num, const double* a_den, const double* b_num, const double* b_den,
+                   hipStream_t stream, KernelStats* stats = nullptr);
+
+// data-movement launches this process has made so far (launchMoves, launchFieldMoveList, both stages of launchReduce and launchProfile, launchPlanes and launchCombine; tests count launches per call with it)
 long long dataLaunchCount();
 
 // name (template spelling) of the data-movement kernel launched last by this process, "" before the first launch

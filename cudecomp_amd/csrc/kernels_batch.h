@@ -3,7 +3,7 @@
 // to: kernels_rows.hip, kernels_transpose.hip (four, one per element size), kernels_window.hip, kernels_lines.hip,
 // kernels_rowlines.hip, kernels_accumulate.hip, kernels_fill.hip, kernels_take.hip, kernels_reflect.hip, kernels_fold.hip, kernels_wall.hip, kernels_wall_plane.hip;
 // kernels_rotate.hip and sync.hip are launched by the executor (and compiled as one unit, kernels_executor.hip; kernels_fill.hip, kernels_reflect.hip and kernels_reduce.hip -- the reductions of a box, launchReduce -- likewise as kernels_edge.hip,
-// kernels_accumulate.hip and kernels_take.hip as kernels_sum.hip; kernels_profile.hip -- the profiles of a box along one dim, launchProfile -- in two parts, inside kernels_window.hip and kernels_rows.hip; kernels_planes.hip -- the plane updates of a box along one dim, launchPlanes -- in two parts, inside kernels_lines.hip and kernels_rowlines.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
+// kernels_accumulate.hip and kernels_take.hip as kernels_sum.hip; kernels_profile.hip -- the profiles of a box along one dim, launchProfile -- in two parts, inside kernels_window.hip and kernels_rows.hip; kernels_planes.hip -- the plane updates of a box along one dim, launchPlanes -- in two parts, inside kernels_lines.hip and kernels_rowlines.hip; kernels_combine.hip -- the combinations of two boxes, launchCombine -- in four parts, inside the four units of kernels_transpose.hip); kernels_field_transpose.hip (lists of field-moves: multi-field
 // halo phases and transposes), kernels_field_accumulate.hip (the same lists adding or taking: multi-field halo accumulation) and
 // kernels_field_mirror.hip (the same lists mirrored, with a sign per field: multi-field wall halos) are reached through
 // launchFieldMoveList (kernels.h); kernels_field_wall.hip (the mirrored lists adding an addend per field and layer: multi-field wall
@@ -244,6 +244,47 @@ struct PlanesFields {
 };
 static_assert(sizeof(PlanesGeom) + sizeof(PlanesFields) + 8 <= 2048, "geometry, the table of fields and the coefficients stay well under the 4 KB of kernel arguments");
 
+// ---- combinations of two boxes of cells (kernels_combine.hip; interior combinations, include/cudecomp_interior_combine.h) ----------
+// y <- a * x + b * y over the same box of x[f] and y[f], the coefficients ratios of doubles in device memory:
+// a = (a_scale * a_num[2i + c]) / a_den[2i], i = f * coef_stride, rounded once to the real type; b likewise.  The reduction's geometry
+// (ReduceGeom's rows, planes and tiles; a long single row cut into rows of kReduceChunkBytes); one stage, no workspace; a launch
+// stores the bytes of the cells of y's box and no others.
+constexpr int kCombineAxpy = 0, kCombineXpby = 1, kCombineAxpby = 2, kCombineAx = 3;  // CUDECOMP_AMD_COMBINE_*
+// workgroups per field the planner aims at: eight per CU of an MI355X, the most that are resident with four waves each (DESIGN.md
+// section 4)
+constexpr int kCombineBlocks = 2048;
+struct CombineGeom {
+  // rows: bytes; the last row of every plane may be shorter (a cut row).  element-wise: unused
+  long long row_bytes, last_row_bytes, rows, planes, s1, s2;
+  long long slots;             // rows: 16-byte slots a row can touch at most
+  unsigned long long tiles;    // rows: t0 * t1 * planes
+  unsigned int t0, t1;         // rows: tile columns / tile rows per plane
+  long long e[3], s[3];        // element-wise: extents and strides in ELEMENTS
+  long long box_off;           // bytes from a field's pointer to the first cell of the box
+  long long rd_lo, rd_hi;      // rows: the bytes [rd_lo, rd_hi) relative to the first cell of the box may be read, of x[f] and of y[f] alike
+  double a_scale, b_scale;     // the host factors of the two coefficients
+  int p0;                      // rows: log2 of the lanes per row; element-wise: the dim the lanes run along
+  int reals;                   // reals per element: 1, or 2 for the complex types
+  int n_fields;
+  int stream;                  // rows: 1 non-temporal loads and stores (KernelChoice::access), 0 default caching
+  int op;                      // kCombine*
+  int coef_stride;             // 0: all fields share the pair 0 of every coefficient array; 1: field f takes pair f
+  unsigned int blocks;         // workgroups PER FIELD; 0: an empty box (no launch)
+};
+struct CombineFields {
+  char* y[kMaxFields];
+  const char* x[kMaxFields];
+};
+// the four coefficient arrays (device memory, read when the kernel runs); a null `num` stands for the pair (1.0, 0.0), a null `den`
+// for no division; the coefficient an op does not use is all null here, whatever the caller passed
+struct CombineCoefs {
+  const double* a_num;
+  const double* a_den;
+  const double* b_num;
+  const double* b_den;
+};
+static_assert(sizeof(CombineGeom) + sizeof(CombineFields) + sizeof(CombineCoefs) <= 2048, "geometry, the two tables of fields and the coefficients stay well under the 4 KB of kernel arguments");
+
 }  // namespace kern
 
 // ---- what runs: one record per kernel choice ----------------------------------------------------------------------------------
@@ -299,7 +340,9 @@ enum KernelKind {
   K_GENERIC_PROFILE,          // profile_elements_kernel = 47
   K_ROWS_PLANES,              // planes_rows_kernel (the kept dim not contiguous: one coefficient per row, read-modify-write on the 16-byte grid) = 48
   K_COLUMNS_PLANES,           // planes_columns_kernel (the kept dim contiguous: a lane owns a 16-byte slot of the row and its coefficients) = 49
-  K_GENERIC_PLANES            // planes_elements_kernel = 50
+  K_GENERIC_PLANES,           // planes_elements_kernel = 50
+  K_ROWS_COMBINE,             // combine_rows_kernel (lanes on the 16-byte grid of x and y, which share their phase on it) = 51
+  K_GENERIC_COMBINE           // combine_elements_kernel = 52
 };
 struct KernelChoice {
   KernelKind kind;
@@ -310,7 +353,7 @@ struct KernelChoice {
                     // write-through) stores, 4 cached loads + non-temporal stores; additions: 0, 1 non-temporal source loads;
                     // fills: 0, 1 non-temporal stores; takes: 0, 1 non-temporal source loads and zero stores (plain take: all of it);
                     // reflections and wall-moves: 0, 1 non-temporal loads and stores; folds: 0, 1 non-temporal source loads and zero stores;
-                    // reductions and profiles: 0, 1 non-temporal loads; plane updates: 0, 1 non-temporal loads and stores;
+                    // reductions and profiles: 0, 1 non-temporal loads; plane updates and combinations: 0, 1 non-temporal loads and stores;
                     // field-moves: 0, 1 non-temporal loads and stores; transpose_fields_kernel: 0, 2; adding / taking
                     // field-moves: as additions / takes; mirrored field-moves: as reflections / folds; wall field-moves: as reflections
   ArithType arith;  // additions, folds, wall-moves, reflections that flip the sign bits, mirrored field-moves (whatever their signs):
@@ -403,12 +446,14 @@ constexpr KindTraits kKindTraits[] = {
     {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_PLANES
     {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_COLUMNS_PLANES
     {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_PLANES
+    {MOVE_ROWS_VEC, STREAM_AS_ACCESS},     // K_ROWS_COMBINE
+    {MOVE_GENERIC, STREAM_CACHED},         // K_GENERIC_COMBINE
 };
-static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_PLANES + 1, "one row per KernelKind");
+static_assert(sizeof(kKindTraits) / sizeof(kKindTraits[0]) == K_GENERIC_COMBINE + 1, "one row per KernelKind");
 
 // the row of a kind; a value outside the enum is an internal error, never a read past the table
 inline const KindTraits& kindTraits(KernelKind kind) {
-  if (kind < K_ROWS || kind > K_GENERIC_PLANES) CD_INTERNAL_ERROR("kernel kind out of range");
+  if (kind < K_ROWS || kind > K_GENERIC_COMBINE) CD_INTERNAL_ERROR("kernel kind out of range");
   return kKindTraits[kind];
 }
 inline MoveClass classOf(KernelKind kind) { return kindTraits(kind).cls; }
@@ -530,6 +575,17 @@ void launchPlanesRows(const KernelChoice& k, const kern::PlanesGeom& g, const ke
                       hipStream_t stream);
 void launchPlanesColumnsOrElements(const KernelChoice& k, const kern::PlanesGeom& g, const kern::PlanesFields& fields, const double* coef,
                                    hipStream_t stream);
+// kernels_combine.hip (in the four units of kernels_transpose.hip): y <- a * x + b * y over a box of cells.  k.kind K_ROWS_COMBINE
+// (launchCombineRows2 / 4 / 8: the real types of 2, 4 and 8 bytes, one unit each) or K_GENERIC_COMBINE (launchCombineElements: every
+// type); k.arith the real type; g.op, the scales and `coefs` (device memory, read when the kernel runs) say what is combined.
+void launchCombineRows2(const KernelChoice& k, const kern::CombineGeom& g, const kern::CombineFields& fields, const kern::CombineCoefs& coefs,
+                        hipStream_t stream);
+void launchCombineRows4(const KernelChoice& k, const kern::CombineGeom& g, const kern::CombineFields& fields, const kern::CombineCoefs& coefs,
+                        hipStream_t stream);
+void launchCombineRows8(const KernelChoice& k, const kern::CombineGeom& g, const kern::CombineFields& fields, const kern::CombineCoefs& coefs,
+                        hipStream_t stream);
+void launchCombineElements(const KernelChoice& k, const kern::CombineGeom& g, const kern::CombineFields& fields, const kern::CombineCoefs& coefs,
+                           hipStream_t stream);
 // kernels_rotate.hip: in-place rotation of a cubic n^3 array (direction +1: new[p0,p1,p2] = old[p2,p0,p1]; -1: the inverse)
 bool rotateSupported(int es, long long n);
 void launchRotate(void* buffer, long long n, int es, int direction, hipStream_t stream);

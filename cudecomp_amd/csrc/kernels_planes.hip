@@ -38,44 +38,8 @@ namespace cudecomp {
 namespace kern {
 namespace {
 
-// ---- the coefficient in T -----------------------------------------------------------------------------------------------------------
-// d rounded to fp32 TO ODD: the fp32 below |d| with the sticky bit in its last place.  RNE of that to a type of 11 or 8 significant
-// bits is RNE of d itself (24 >= 11 + 2), overflow and subnormals of the narrow type included.
-__device__ __forceinline__ float roundToOddF32(double d) {
-  const float f = (float)d;  // to nearest even
-  const double back = (double)f;
-  if (d != d || back == d) return f;  // NaN; exact (zeros and infinities among them)
-  unsigned int bits = __float_as_uint(f);
-  if (__builtin_fabs(back) > __builtin_fabs(d)) bits -= 1;  // one step towards zero (from infinity: the largest finite)
-  return __uint_as_float(bits | 1u);
-}
-template <typename T> __device__ __forceinline__ T toReal(double d) {
-  if constexpr (sizeof(T) == 8) return d;
-  else if constexpr (sizeof(T) == 4) return (float)d;
-  else return (T)roundToOddF32(d);
-}
-
-// ---- the reals of a 16-byte vector as T ---------------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ T typedReal(const u32x4& v, int j) {
-  if constexpr (sizeof(T) == 8) return __builtin_bit_cast(double, j == 0 ? (u32x2)v.xy : (u32x2)v.zw);
-  else if constexpr (sizeof(T) == 4) return __uint_as_float(v[j]);
-  else return __builtin_bit_cast(T, (unsigned short)(v[j >> 1] >> ((j & 1) * 16)));
-}
-template <typename T, int NR> __device__ __forceinline__ u32x4 packReals(const T (&x)[NR]) {
-  u32x4 v;
-  if constexpr (sizeof(T) == 8) {
-    v.xy = __builtin_bit_cast(u32x2, x[0]);
-    v.zw = __builtin_bit_cast(u32x2, x[1]);
-  } else if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = __float_as_uint(x[j]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      v[j] = (unsigned int)__builtin_bit_cast(unsigned short, x[2 * j]) | ((unsigned int)__builtin_bit_cast(unsigned short, x[2 * j + 1]) << 16);
-  }
-  return v;
-}
+// (toReal, typedReal, packReals, storePieces, storeGrid, loadSlotOf, loadSlots and storeSlot: kernels_reduce_dev.h, shared with
+// kernels_combine.hip)
 
 // the update of one vector: real j with coefficient c[j]; MODE 2: the reals 2k, 2k + 1 are one element, c[2k], c[2k + 1] its (re, im)
 template <typename T, int MODE> __device__ __forceinline__ u32x4 applyVec(const u32x4& v, const T (&c)[16 / sizeof(T)]) {
@@ -93,62 +57,6 @@ template <typename T, int MODE> __device__ __forceinline__ u32x4 applyVec(const 
     for (int j = 0; j < NR; ++j) out[j] = MODE == 0 ? addReal<T>(typedReal<T>(v, j), c[j]) : mulReal<T>(typedReal<T>(v, j), c[j]);
   }
   return packReals<T, NR>(out);
-}
-
-// the reals [lo, hi) (bytes, multiples of RS) of `v` to the 16-byte slot at `slot`, each with a store of its own; nothing else
-template <int RS> __device__ __forceinline__ void storePieces(char* slot, const u32x4& v, int lo, int hi) {
-  if constexpr (RS == 8) {
-    if (lo <= 0 && 8 <= hi) *reinterpret_cast<u32x2*>(slot) = v.xy;
-    if (lo <= 8 && 16 <= hi) *reinterpret_cast<u32x2*>(slot + 8) = v.zw;
-  } else if constexpr (RS == 4) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (lo <= 4 * j && 4 * j + 4 <= hi) *reinterpret_cast<unsigned int*>(slot + 4 * j) = v[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (lo <= 2 * j && 2 * j + 2 <= hi) *reinterpret_cast<unsigned short*>(slot + 2 * j) = (unsigned short)(v[j >> 1] >> ((j & 1) * 16));
-  }
-}
-
-// The slots lie on the 16-byte grid.  The non-temporal accesses say so (a u32x4 of natural alignment), the cached ones go through the
-// library's dword-aligned payload type.  `stream` is a uniform branch; the compiler merges two branches that differ in nothing but
-// their non-temporal mark, and drops the mark.  So the stores differ in their alignment as well, and the loads of a tile sit on the
-// two sides of ONE branch around all of them (loadSlots), not each in a branch of its own.
-__device__ __forceinline__ void storeGrid(char* p, const u32x4& v, bool stream) {
-  if (stream) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p));
-  else *reinterpret_cast<u32x4_g*>(p) = v;
-}
-
-// the slot at a + slot_off, of which the bytes [lo, hi) lie inside a row: one aligned vector when the slot lies wholly inside the
-// readable range [rd_lo, rd_hi), else only the reals inside the row (loadSlot's rule, kernels_reduce_dev.h); lo >= hi: nothing
-template <int RS, bool NT>
-__device__ __forceinline__ u32x4 loadSlotOf(const char* a, long long slot_off, int lo, int hi, long long rd_lo, long long rd_hi) {
-  if (lo >= hi) return u32x4{0u, 0u, 0u, 0u};
-  if (slot_off >= rd_lo && slot_off + 16 <= rd_hi) {
-    if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a + slot_off));
-    else return *reinterpret_cast<const u32x4_g*>(a + slot_off);
-  }
-  return loadPieces<RS>(a + slot_off, lo, hi);
-}
-// the kRowsUnroll slots of a lane's share of a tile, all loads issued before anything else happens to them
-template <int RS>
-__device__ __forceinline__ void loadSlots(const char* a, const long long (&off)[kRowsUnroll], const int (&lo)[kRowsUnroll],
-                                          const int (&hi)[kRowsUnroll], long long rd_lo, long long rd_hi, bool stream,
-                                          u32x4 (&va)[kRowsUnroll]) {
-  if (stream) {
-#pragma unroll
-    for (int u = 0; u < kRowsUnroll; ++u) va[u] = loadSlotOf<RS, true>(a, off[u], lo[u], hi[u], rd_lo, rd_hi);
-  } else {
-#pragma unroll
-    for (int u = 0; u < kRowsUnroll; ++u) va[u] = loadSlotOf<RS, false>(a, off[u], lo[u], hi[u], rd_lo, rd_hi);
-  }
-}
-
-// the same slot back: one 16-byte store when all of it lies inside the row, else real by real inside the row alone
-template <int RS> __device__ __forceinline__ void storeSlot(char* a, long long slot_off, const u32x4& v, int lo, int hi, bool stream) {
-  if (lo == 0 && hi == 16) storeGrid(a + slot_off, v, stream);
-  else storePieces<RS>(a + slot_off, v, lo, hi);
 }
 
 #if CD_PLANES_PART == 1

@@ -67,3 +67,9 @@ void launchTransposeBatch16(const KernelChoice& k, const Batch& b, unsigned int 
 #endif
 
 }  // namespace cudecomp
+
+// the combinations of two boxes (kernels_combine.hip) are compiled into these units, one part each -- the row kernel of the real types
+// as wide as this unit's elements, and the element-wise kernel in the unit of the 16-byte elements: the family cannot be a code object
+// of its own, and these four have the room (kernels_batch.h says why the library keeps the number of its code objects)
+#define CD_COMBINE_PART CUDECOMP_TRANSPOSE_ES
+#include "kernels_combine.hip"

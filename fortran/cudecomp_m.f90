@@ -127,6 +127,8 @@ module cudecomp
   ! cudecomp_interior_reduce.h: the operations of cudecompAmdReduceInterior{X,Y,Z}, and the most fields a call takes
   integer(c_int32_t), parameter :: CUDECOMP_AMD_REDUCE_SUM = 0, CUDECOMP_AMD_REDUCE_DOT = 1, CUDECOMP_AMD_REDUCE_MAX_ABS = 2
   integer(c_int32_t), parameter :: CUDECOMP_AMD_PLANES_ADD = 0, CUDECOMP_AMD_PLANES_MUL = 1
+  integer(c_int32_t), parameter :: CUDECOMP_AMD_COMBINE_AXPY = 0, CUDECOMP_AMD_COMBINE_XPBY = 1, CUDECOMP_AMD_COMBINE_AXPBY = 2, &
+                                   CUDECOMP_AMD_COMBINE_AX = 3
   integer(c_int32_t), parameter :: CUDECOMP_AMD_MAX_REDUCE_FIELDS = 32
   enum, bind(c)
     enumerator :: CUDECOMP_RESULT_SUCCESS = 0
@@ -869,6 +871,65 @@ module cudecomp
       integer(c_intptr_t), value :: stream
       integer(c_int) :: res
     end function cudecompAmdApplyPlanesInteriorZ_C
+
+    ! cudecomp_interior_combine.h: y <- a * x + b * y over the interior, the coefficients ratios of doubles in device memory.  The C
+    ! entry points; the wrappers cudecompAmdCombineInterior{X,Y,Z} below make padding and stream optional
+    function cudecompAmdCombineInteriorX_C(handle, grid_desc, y, x, n_fields, op, a_num, a_den, a_scale, b_num, b_den, b_scale, &
+                                           coef_stride, dtype, halo_extents, padding, stream) &
+      bind(C, name="cudecompAmdCombineInteriorX") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: y(*), x(*)
+      integer(c_int32_t), value :: n_fields, op
+      type(c_ptr), value :: a_num, a_den
+      real(c_double), value :: a_scale
+      type(c_ptr), value :: b_num, b_den
+      real(c_double), value :: b_scale
+      integer(c_int32_t), value :: coef_stride
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3), padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdCombineInteriorX_C
+
+    function cudecompAmdCombineInteriorY_C(handle, grid_desc, y, x, n_fields, op, a_num, a_den, a_scale, b_num, b_den, b_scale, &
+                                           coef_stride, dtype, halo_extents, padding, stream) &
+      bind(C, name="cudecompAmdCombineInteriorY") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: y(*), x(*)
+      integer(c_int32_t), value :: n_fields, op
+      type(c_ptr), value :: a_num, a_den
+      real(c_double), value :: a_scale
+      type(c_ptr), value :: b_num, b_den
+      real(c_double), value :: b_scale
+      integer(c_int32_t), value :: coef_stride
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3), padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdCombineInteriorY_C
+
+    function cudecompAmdCombineInteriorZ_C(handle, grid_desc, y, x, n_fields, op, a_num, a_den, a_scale, b_num, b_den, b_scale, &
+                                           coef_stride, dtype, halo_extents, padding, stream) &
+      bind(C, name="cudecompAmdCombineInteriorZ") result(res)
+      import
+      type(cudecompHandle), value :: handle
+      type(cudecompGridDesc), value :: grid_desc
+      type(c_ptr) :: y(*), x(*)
+      integer(c_int32_t), value :: n_fields, op
+      type(c_ptr), value :: a_num, a_den
+      real(c_double), value :: a_scale
+      type(c_ptr), value :: b_num, b_den
+      real(c_double), value :: b_scale
+      integer(c_int32_t), value :: coef_stride
+      integer(c_int), value :: dtype
+      integer(c_int32_t) :: halo_extents(3), padding(3)
+      integer(c_intptr_t), value :: stream
+      integer(c_int) :: res
+    end function cudecompAmdCombineInteriorZ_C
 
     ! cudecomp_halo_wall_value_fields.h: wall values of several pencils, each with a parity and addends of its own
     function cudecompAmdSetWallFieldHalosX_C(handle, grid_desc, inputs, n_fields, dtype, parities, centering, sides, values_low, &
@@ -2837,6 +2898,90 @@ contains
     res = cudecompAmdApplyPlanesInteriorZ_C(handle, grid_desc, fields, int(n_fields, c_int32_t), int(op, c_int32_t), &
                                             int(dim - 1, c_int32_t), coef, ld, scale, int(dtype, c_int), h, p, s)
   end function cudecompAmdApplyPlanesInteriorZ
+
+  ! ---- interior combinations (cudecomp_interior_combine.h): `y` and `x` are arrays of n_fields device addresses, `op` one of
+  ! CUDECOMP_AMD_COMBINE_AXPY / _XPBY / _AXPBY / _AX; a = (a_scale * a_num(2i + c)) / a_den(2i) with i = f * coef_stride, the four
+  ! coefficient arrays device addresses laid out as the reduction's results (c_null_ptr: the pair (1, 0) / no division); b likewise ----
+  function cudecompAmdCombineInteriorX(handle, grid_desc, y, x, n_fields, op, a_num, a_den, a_scale, b_num, b_den, b_scale, &
+                                       coef_stride, dtype, halo_extents, padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(c_ptr) :: y(*), x(*)
+    integer :: n_fields, op
+    type(c_ptr) :: a_num, a_den
+    real(c_double) :: a_scale
+    type(c_ptr) :: b_num, b_den
+    real(c_double) :: b_scale
+    integer :: coef_stride  ! 0: all fields share pair 0; 1: field f takes pair f
+    integer :: dtype
+    integer :: halo_extents(3)
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    integer(c_intptr_t) :: s
+    h = int(halo_extents, c_int32_t)
+    p = 0
+    s = 0
+    if (present(padding)) p = int(padding, c_int32_t)
+    if (present(stream)) s = stream
+    res = cudecompAmdCombineInteriorX_C(handle, grid_desc, y, x, int(n_fields, c_int32_t), int(op, c_int32_t), a_num, a_den, &
+                                        a_scale, b_num, b_den, b_scale, int(coef_stride, c_int32_t), int(dtype, c_int), h, p, s)
+  end function cudecompAmdCombineInteriorX
+
+  function cudecompAmdCombineInteriorY(handle, grid_desc, y, x, n_fields, op, a_num, a_den, a_scale, b_num, b_den, b_scale, &
+                                       coef_stride, dtype, halo_extents, padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(c_ptr) :: y(*), x(*)
+    integer :: n_fields, op
+    type(c_ptr) :: a_num, a_den
+    real(c_double) :: a_scale
+    type(c_ptr) :: b_num, b_den
+    real(c_double) :: b_scale
+    integer :: coef_stride  ! 0: all fields share pair 0; 1: field f takes pair f
+    integer :: dtype
+    integer :: halo_extents(3)
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    integer(c_intptr_t) :: s
+    h = int(halo_extents, c_int32_t)
+    p = 0
+    s = 0
+    if (present(padding)) p = int(padding, c_int32_t)
+    if (present(stream)) s = stream
+    res = cudecompAmdCombineInteriorY_C(handle, grid_desc, y, x, int(n_fields, c_int32_t), int(op, c_int32_t), a_num, a_den, &
+                                        a_scale, b_num, b_den, b_scale, int(coef_stride, c_int32_t), int(dtype, c_int), h, p, s)
+  end function cudecompAmdCombineInteriorY
+
+  function cudecompAmdCombineInteriorZ(handle, grid_desc, y, x, n_fields, op, a_num, a_den, a_scale, b_num, b_den, b_scale, &
+                                       coef_stride, dtype, halo_extents, padding, stream) result(res)
+    type(cudecompHandle) :: handle
+    type(cudecompGridDesc) :: grid_desc
+    type(c_ptr) :: y(*), x(*)
+    integer :: n_fields, op
+    type(c_ptr) :: a_num, a_den
+    real(c_double) :: a_scale
+    type(c_ptr) :: b_num, b_den
+    real(c_double) :: b_scale
+    integer :: coef_stride  ! 0: all fields share pair 0; 1: field f takes pair f
+    integer :: dtype
+    integer :: halo_extents(3)
+    integer, optional :: padding(3)
+    integer(cudecomp_stream_kind), optional :: stream
+    integer(c_int) :: res
+    integer(c_int32_t) :: h(3), p(3)
+    integer(c_intptr_t) :: s
+    h = int(halo_extents, c_int32_t)
+    p = 0
+    s = 0
+    if (present(padding)) p = int(padding, c_int32_t)
+    if (present(stream)) s = stream
+    res = cudecompAmdCombineInteriorZ_C(handle, grid_desc, y, x, int(n_fields, c_int32_t), int(op, c_int32_t), a_num, a_den, &
+                                        a_scale, b_num, b_den, b_scale, int(coef_stride, c_int32_t), int(dtype, c_int), h, p, s)
+  end function cudecompAmdCombineInteriorZ
 
   subroutine halo_defaults(h, per, p, s, halo_extents, halo_periods, padding, stream)
     integer(c_int32_t), intent(out) :: h(3), p(3)

@@ -650,8 +650,28 @@ cudecompResult_t cudecompExtDescribePlanes3D(uint64_t a_address, cudecompDataTyp
                                              const int64_t extent[3], const int64_t strides[3], int64_t readable_before,
                                              int64_t readable_after, int32_t force, int64_t out[7]);
 
+/* One box of one field through the combination kernels of cudecompAmdCombineInterior{X,Y,Z} (cudecomp_interior_combine.h;
+ * csrc/kernels.h launchCombine, kernels_combine.hip): cudecompExtReduce3D's box, the same in x and in y -- every cell of y's box
+ * becomes a * x + y (op 0), x + b * y (op 1), a * x + b * y (op 2) or a * x (op 3), a = (a_scale * a_num[c]) / a_den[0] and b likewise
+ * (device memory, read when the kernel runs; a NULL num the pair (1, 0), a NULL den no division).  readable_before, readable_after
+ * and force as for cudecompExtReduce3D, of x and y alike.  *kernel_class (optional): 0 the row kernel, 2 element-wise, -1 no launch
+ * (an empty box).
+ *
+ * cudecompExtDescribeCombine3D answers how that call would run, without a device and without a launch.  out[12] = {kind
+ * (csrc/kernels_batch.h KernelKind: 51 combine_rows_kernel, 52 combine_elements_kernel), bytes per lane (16 / one element), workgroups,
+ * read_x_lo, read_x_hi (the lowest byte of x read and one past the highest, relative to x), read_y_lo, read_y_hi (of y, relative to y;
+ * 0, 0 for op 3), write_lo, write_hi (the lowest byte of y stored and one past the highest: 0 and the box's span), and of the row
+ * kernel: bytes per row, rows, bytes of the last row (a long single row is cut; 0, 0, 0 element-wise)}. */
+cudecompResult_t cudecompExtCombine3D(void* y, const void* x, cudecompDataType_t dtype, int32_t op, const int64_t extent[3],
+                                      const int64_t strides[3], int64_t readable_before, int64_t readable_after, const double* a_num,
+                                      const double* a_den, double a_scale, const double* b_num, const double* b_den, double b_scale,
+                                      int32_t force, int32_t* kernel_class, hipStream_t stream);
+cudecompResult_t cudecompExtDescribeCombine3D(uint64_t y_address, uint64_t x_address, cudecompDataType_t dtype, int32_t op,
+                                              const int64_t extent[3], const int64_t strides[3], int64_t readable_before,
+                                              int64_t readable_after, int32_t force, int64_t out[12]);
+
 /* Data-movement kernel launches this process has made so far through the kernel layer (launchMoves,
- * launchFieldMoveList, both stages of launchReduce and of launchProfile, and launchPlanes; the signal / wait kernels and the copy-engine copies of the transports are not counted -- the chunk copies the
+ * launchFieldMoveList, both stages of launchReduce and of launchProfile, launchPlanes and launchCombine; the signal / wait kernels and the copy-engine copies of the transports are not counted -- the chunk copies the
  * one-sided transport makes with the row-copy kernel between ranks that share a GPU go through launchMoves and are).  Tests take
  * the difference around a call. */
 cudecompResult_t cudecompExtDataLaunchCount(int64_t* launches);
